@@ -22,6 +22,12 @@ fragment RHF -> embedding->MO integral transform -> RCCSD to convergence -> 1-RD
 all-reduce (RCCL) of [edge values, centre values, sum centre diag, e1, e2, ec, n_iter, failure flag].  Nothing is cached
 between steps (amplitudes restart from MP2 exactly like the reference).
 value = CCSD iterations completed by all ranks in the K timed steps / wall time (max over ranks).
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else the benchmark measures or checks -- the
+single-stream roofline pass and the clock / MFMA probes, the four-index route, the oracle parity probes, the octane / H8 / DF / k-point
+figures, the fragment-size sweep and the CPU baselines -- runs only under --full (its --no-* options still apply there).
+--dump-outputs DIR writes what the last timed step returned on rank 0 (residual norm and vector, correlation energies, the 1-RDMs of
+the rank's fragments) as DIR/<name>.npy in float64, so that two builds can be compared output for output.
 """
 import os as _os
 # BLAS / OpenMP pools inside the CPU share of this process, before NumPy starts them (quemb_amd/hostthreads.py: on a box that shows 256 cores
@@ -84,13 +90,18 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every figure beside the headline (roofline pass and probes, four-index route, parity probes, octane / H8 / DF / k-point "
+                         "figures, size sweep, CPU baselines); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy in float64")
     ap.add_argument("--frags-per-gpu", type=int, default=8)
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (the driver's contract): --frags-per-gpu fragments on every GPU; strong: --frags-total fragments shared out over the GPUs")
     ap.add_argument("--frags-total", type=int, default=64, help="fragments of the whole job under --scaling strong (BASELINE configs[2]: 64)")
     ap.add_argument("--cu-split", type=int, default=2, help="execution contexts on this many interleaved sets of compute units (qemb_ctx_partition; 0: whole chip each)")
     ap.add_argument("--nstreams", type=int, default=4, help="fragments in flight per GPU (separate HIP streams, be_func(..., nstreams=k)); "
-                    "the roofline of the ladder kernel is measured in a separate single-stream pass after the timed region")
+                    "under --full the roofline of the ladder kernel is measured in a separate single-stream pass after the timed region")
     ap.add_argument("--mo-route", choices=("factor", "four-index"), default="factor",
                     help="how a solve forms its MO integrals: from the fragment's 3-index DF factor (qemb_frag_set_df_factor; the synthetic family IS DF-factorised) "
                          "or by the four quarter transformations of the 4-fold packed block")
@@ -250,6 +261,22 @@ def make_ring(lib, n, o, nf, F_total, owner, rank, scale, opts, mo_route="factor
         f.udim = c
         c = f.set_udim(c)
     return frs, c + 1
+
+
+DUMP_RDM_BYTES = 48 << 20        # --dump-outputs: the 1-RDMs of at most this many bytes (the first fragments of the rank, in ring order)
+
+
+def dump_outputs(d, frs, mine, ernorm, ervec, ecorr, e_parts):
+    """--dump-outputs: what the last timed step returned -- be_func's (ernorm, ervec, [Ecorr, total_e]) -- and the embedding-basis 1-RDMs it left
+    on this rank's fragments (Frags._rdm1, what the density matching reads), as float64 .npy files"""
+    os.makedirs(d, exist_ok=True)
+    n2 = 8 * frs[mine[0]]._rdm1.size
+    keep = mine[:max(1, DUMP_RDM_BYTES // n2)]
+    outs = dict(residual_norm=[ernorm], residual_vec=ervec, e_corr=[ecorr], e_corr_parts=e_parts,
+                rdm1_emb=np.stack([frs[i]._rdm1 for i in keep]), rdm1_fragments=keep)
+    for name, a in outs.items():
+        np.save(os.path.join(d, name + ".npy"), np.asarray(a, dtype=np.float64))
+    return sorted(outs)
 
 
 def read_timer(lib, slot, nctx=1, reset=0):
@@ -800,6 +827,8 @@ def main():
         return cpu_worker(args.cpu_worker, args.cpu_mode, args.nocc, args.cpu_iters, args.cpu_nproc)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args)                 # this process stays off the GPU; the ranks are its children
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); lrank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -924,7 +953,7 @@ def main():
     t0 = time.perf_counter()
     ecorr_sum = 0.0
     for _ in range(args.steps):
-        ernorm, ervec, (ecorr, _) = sweep()
+        ernorm, ervec, (ecorr, e_parts) = sweep()
         ecorr_sum += ecorr
     sync()
     barrier()
@@ -941,27 +970,12 @@ def main():
         lad_ms_c, lad_cnt_c = read_timer(lib, 0, nctx)
         fr0 = frs[mine[0]]
         h0, dm00 = fr0.fock, fr0.dm0
-        log("roofline pass: one fragment, one stream")
-        rp = roofline_pass(lib, fr0.dev, h0, dm00, o, opts, args.roofline_iters)
-        lad_avg = rp["ladder_ms"] * 1e-3
-        npair_o = o * (o + 1) // 2
-        npv, nmv, nmo = v * (v + 1) // 2, v * (v - 1) // 2, o * (o - 1) // 2
-        flop_ladder = 2.0 * npair_o * float(npv) ** 2 + 2.0 * nmo * float(nmv) ** 2   # executed: (+/-) pair-packed products
-        flop_dense = 2.0 * o * o * float(v) ** 4                 # SURVEY 8(d) dense-equivalent figure
-        achieved = flop_ladder / lad_avg / 1e12 if lad_avg > 0 else 0.0
-        traffic, traffic_source = None, None                     # HBM bytes per launch from the separate --pmc passes
-        for cand in (PMC_FILE, "profiles/r04_pmc_ladder.json", "profiles/r03_pmc_ladder.json", "profiles/r02_pmc_ladder.json"):
-            pmc = ROOT / cand
-            if pmc.exists():
-                try:
-                    traffic = json.loads(pmc.read_text()).get("hbm_bytes_per_launch")
-                    traffic_source = f"{cand}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over tools/frag_bench.py (tools/pmc_ladder.sh), NOT collected in this run"
-                    break
-                except Exception:  # noqa: BLE001
-                    traffic = None
+        if args.dump_outputs:
+            names = dump_outputs(args.dump_outputs, frs, mine, ernorm, ervec, ecorr, e_parts)
+            log(f"outputs of the last timed step written to {args.dump_outputs}: {', '.join(names)}")
         res = {
             "metric": "fragment CCSD iters/sec (full BE sweep over synthetic n_occ=20 n_virt=200 fragments); corr-E error vs oracle in parity_max_abs_err_Eh / parity_n220_abs_err_Eh",
-            "value": n_iter_total / dt, "unit": "CCSD iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "value": n_iter_total / dt, "unit": "CCSD iterations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": f"BASELINE configs[2]: synthetic fragment sweep, {F} fragments per GPU ({F_total} total, {args.scaling} scaling), "
@@ -995,22 +1009,41 @@ def main():
             "ccsd_iterations_per_fragment": n_iter_total / max(n_frag_total, 1),
             "mean_e_corr_per_sweep": ecorr_sum / args.steps,
             "residual_norm": float(ernorm),
-            "roofline": {"bound": "mfma", "kernel": "dgemm_mfma_kernel<7,2,2,4,16,true,true,2,1,1> (+ pairs, 224x128 tile) and <6,2,2,4,16,true,true,2,1,1> (- pairs, 192x128): pp-ladder over (+/-) packed pairs, M=npair(o) N=K=npair(v), split-K + slab reduce",
-                         "achieved": achieved, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_FP64_MFMA_TFLOPS,
-                         # one pp-ladder = TWO dispatches of this kernel ((+) and (-) pair blocks); per-dispatch averages:
-                         "traffic": None if traffic is None else traffic / 2.0, "traffic_source": traffic_source,
-                         "avg_launch_ms": lad_avg * 1e3 / 2.0, "launches": 2 * rp["ladder_count"],
-                         "measured": f"HIP events on the launch stream around the two ladder dispatches (+ their slab reductions) in a separate single-stream pass of {args.roofline_iters} CCSD iterations on fragment 0 right after the timed region",
-                         "flop_per_launch": flop_ladder / 2.0, "ladder_ms": lad_avg * 1e3,
-                         "dense_equivalent_tflops": flop_dense / lad_avg / 1e12 if lad_avg > 0 else 0.0,
-                         "algorithmic_bytes_per_launch": 4.0 * (float(npv) ** 2 + float(nmv) ** 2 + 2.0 * npair_o * npv + 2.0 * nmo * nmv),
-                         "ladder_ms_in_timed_region": lad_ms_c / max(lad_cnt_c, 1),
-                         "single_stream_iteration_ms": rp["iter_ms"], "single_stream_rings_ms": rp["rings_ms"]},
             "device_time_ms_rank0": {"note": f"HIP-event brackets inside the timed region; with {args.nstreams} fragment(s) in flight the brackets of different streams overlap",
                                      "ccsd_iteration_avg": it_ms / max(it_cnt, 1), "ccsd_iterations": it_cnt, "rings_avg": ring_ms / max(ring_cnt, 1),
                                      "mo_transform_avg": ao_ms / max(ao_cnt, 1), "fragment_scf_avg": scf_ms / max(scf_cnt, 1)},
         }
-        if world == 1:
+        if args.full:
+            log("roofline pass: one fragment, one stream")
+            rp = roofline_pass(lib, fr0.dev, h0, dm00, o, opts, args.roofline_iters)
+            lad_avg = rp["ladder_ms"] * 1e-3
+            npair_o = o * (o + 1) // 2
+            npv, nmv, nmo = v * (v + 1) // 2, v * (v - 1) // 2, o * (o - 1) // 2
+            flop_ladder = 2.0 * npair_o * float(npv) ** 2 + 2.0 * nmo * float(nmv) ** 2   # executed: (+/-) pair-packed products
+            flop_dense = 2.0 * o * o * float(v) ** 4                 # SURVEY 8(d) dense-equivalent figure
+            achieved = flop_ladder / lad_avg / 1e12 if lad_avg > 0 else 0.0
+            traffic, traffic_source = None, None                     # HBM bytes per launch from the separate --pmc passes
+            for cand in (PMC_FILE, "profiles/r04_pmc_ladder.json", "profiles/r03_pmc_ladder.json", "profiles/r02_pmc_ladder.json"):
+                pmc = ROOT / cand
+                if pmc.exists():
+                    try:
+                        traffic = json.loads(pmc.read_text()).get("hbm_bytes_per_launch")
+                        traffic_source = f"{cand}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over tools/frag_bench.py (tools/pmc_ladder.sh), NOT collected in this run"
+                        break
+                    except Exception:  # noqa: BLE001
+                        traffic = None
+            res["roofline"] = {"bound": "mfma", "kernel": "dgemm_mfma_kernel<7,2,2,4,16,true,true,2,1,1> (+ pairs, 224x128 tile) and <6,2,2,4,16,true,true,2,1,1> (- pairs, 192x128): pp-ladder over (+/-) packed pairs, M=npair(o) N=K=npair(v), split-K + slab reduce",
+                               "achieved": achieved, "peak": PEAK_FP64_MFMA_TFLOPS, "unit": "TFLOP/s", "frac": achieved / PEAK_FP64_MFMA_TFLOPS,
+                               # one pp-ladder = TWO dispatches of this kernel ((+) and (-) pair blocks); per-dispatch averages:
+                               "traffic": None if traffic is None else traffic / 2.0, "traffic_source": traffic_source,
+                               "avg_launch_ms": lad_avg * 1e3 / 2.0, "launches": 2 * rp["ladder_count"],
+                               "measured": f"HIP events on the launch stream around the two ladder dispatches (+ their slab reductions) in a separate single-stream pass of {args.roofline_iters} CCSD iterations on fragment 0 right after the timed region",
+                               "flop_per_launch": flop_ladder / 2.0, "ladder_ms": lad_avg * 1e3,
+                               "dense_equivalent_tflops": flop_dense / lad_avg / 1e12 if lad_avg > 0 else 0.0,
+                               "algorithmic_bytes_per_launch": 4.0 * (float(npv) ** 2 + float(nmv) ** 2 + 2.0 * npair_o * npv + 2.0 * nmo * nmv),
+                               "ladder_ms_in_timed_region": lad_ms_c / max(lad_cnt_c, 1),
+                               "single_stream_iteration_ms": rp["iter_ms"], "single_stream_rings_ms": rp["rings_ms"]}
+        if world == 1 and args.full:
             try:
                 res["roofline"]["peak_measured"] = mfma_peak_probe(lib)
                 res["roofline"]["peak_measured_how"] = "register-only v_mfma_f64_16x16x4_f64 loop, 16 independent accumulator chains per wave, 8 waves per CU (qemb_mfma_f64_peak)"

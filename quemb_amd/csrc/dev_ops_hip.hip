@@ -64,7 +64,7 @@ static constexpr size_t TIMER_MAX_PENDING = 64;
 static constexpr int NPART = 2048;
 struct DevCtx {
   hipStream_t stream = nullptr;
-  bool capturing = false;            // inside hipStreamBeginCapture .. EndCapture (dev_graph_*)
+  std::atomic<bool> capturing{false};      // inside hipStreamBeginCapture .. EndCapture (dev_graph_*); read by other threads' trim_all_contexts
   double* partials = nullptr;        // reduction scratch (8 x NPART doubles: up to eight dot products per pass)
   double* ws = nullptr;              // growable workspace for contract_mid / k_pairs partials
   size_t ws_bytes = 0;
@@ -88,6 +88,7 @@ struct DevCtx {
 struct LiveBlock { size_t bytes; DevCtx* owner; };
 static std::map<void*, LiveBlock> g_live_blocks;   // every block handed out by dev_alloc, any context
 static std::mutex g_alloc_mutex;                   // allocator bookkeeping only (host side, off the kernel path)
+static std::mutex g_miss_mutex;                    // a pool miss: the free-memory check and the driver allocation (dev_alloc)
 static int g_device = -1;
 static DevCtx g_default_ctx;
 static std::vector<DevCtx*> g_extra_ctx;          // created by dev_ctx_count(n); index k >= 1
@@ -230,7 +231,9 @@ int dev_trim() {
   return QEMB_OK;
 }
 // An allocation failed: hand the parked blocks of EVERY context back to the driver (a multi-GB block cached by another stream's
-// context is as good as free).  Each context's stream is drained first, so none of its parked blocks is still in use.
+// context is as good as free).  Each context's stream is drained first, so none of its parked blocks is still in use.  A context that
+// another thread is capturing on keeps its blocks: its stream cannot be synchronised until the capture ends (doing so is an error that
+// also invalidates that thread's capture).
 static int trim_all_contexts() {
   std::vector<DevCtx*> all;
   {
@@ -238,6 +241,7 @@ static int trim_all_contexts() {
     all.push_back(&g_default_ctx);
     for (DevCtx* c : g_extra_ctx) all.push_back(c);
   }
+  all.erase(std::remove_if(all.begin(), all.end(), [](DevCtx* c) { return c != &ctx() && c->capturing; }), all.end());
   for (DevCtx* c : all) if (c->stream) HIP_TRY(hipStreamSynchronize(c->stream));
   std::lock_guard<std::mutex> lock(g_alloc_mutex);
   for (DevCtx* c : all) trim_ctx_locked(*c);
@@ -290,6 +294,9 @@ int dev_alloc(void** p, size_t bytes) {
     ~MissTimer() { g_alloc_misses += 1; g_alloc_miss_bytes += (long long)b; g_alloc_miss_ns += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); }
   } miss_timer;
   miss_timer.b = bytes;
+  // The free-memory check below and the hipMalloc it guards are one step for the whole process: two host threads that missed their pools together (the
+  // fragments in flight of a sweep, each on its own context) would otherwise both pass the check against the same free memory and together ask for more.
+  std::lock_guard<std::mutex> miss_lock(g_miss_mutex);
   {
     // Do not walk INTO an out-of-memory condition: on this runtime a hipMalloc beyond what is free has been seen to crash inside the HSA allocator (or to hang)
     // instead of failing (round 5: bench.py's size sweep after the other sections, ~200 GB parked in the pools of seven contexts).  When the request does not fit

@@ -128,7 +128,7 @@ def test_cpu_baseline_runs_whole_fragments_in_both_pool_settings():
     """bench.py's cpu_baseline on tiny sizes (mock device): full solves in the reference's default pool and in the all-cores pool, the
     GPU-side figure on the same fragments, energies agreeing, and the amplitude-update sample at the timed size beside them."""
     args = [a for a in SMALL if a != "--no-cpu-baseline"]
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *args, "--full-n", "16", "--full-nocc", "3", "--lib", _mock()],
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *args, "--full", "--full-n", "16", "--full-nocc", "3", "--lib", _mock()],
                        env=_env(), capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-2000:]
     r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])

@@ -7,14 +7,14 @@ OUT=gpurun_out/prof_$TAG
 export TMPDIR=/tmp
 mkdir -p $OUT
 # 1. the bench command, one fragment in flight: per-kernel durations of kernels that own the device (agreement with the HIP-event timers)
-rm -rf gpurun_out/kt1
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/kt1 -- python bench.py --nstreams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-octane --no-size-sweep > $OUT/bench_nstreams1.json 2> $OUT/bench_nstreams1.err || echo "rocprofv3 (nstreams 1) left with status $?"
-cp gpurun_out/kt1/*/*kernel_stats.csv $OUT/bench_nstreams1_kernel_stats.csv
-rm -rf gpurun_out/kt1
+rm -rf $OUT/kt1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt1 -- python bench.py --full --nstreams 1 --steps 3 --warmup 1 --no-cpu-baseline --no-octane --no-size-sweep > $OUT/bench_nstreams1.json 2> $OUT/bench_nstreams1.err || echo "rocprofv3 (nstreams 1) left with status $?"
+cp $OUT/kt1/*/*kernel_stats.csv $OUT/bench_nstreams1_kernel_stats.csv
+rm -rf $OUT/kt1
 # 2. the default bench command (four fragments in flight: kernels of different streams overlap, durations are contended; under the profiler the contexts keep plain streams)
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/kt3 -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-octane --no-size-sweep > $OUT/bench_default.json 2> $OUT/bench_default.err || echo "rocprofv3 (default) left with status $? (the profiler's own exit handlers; its CSV files are written before)"
-cp gpurun_out/kt3/*/*kernel_stats.csv $OUT/bench_default_kernel_stats.csv
-rm -rf gpurun_out/kt3
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt3 -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-octane --no-size-sweep > $OUT/bench_default.json 2> $OUT/bench_default.err || echo "rocprofv3 (default) left with status $? (the profiler's own exit handlers; its CSV files are written before)"
+cp $OUT/kt3/*/*kernel_stats.csv $OUT/bench_default_kernel_stats.csv
+rm -rf $OUT/kt3
 # 3. one CCSD iteration, kernel by kernel
 QEMB_GEMM_SHAPELOG=gpurun_out/shapes.txt timeout -k 10 500 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/kt -- python tools/frag_bench.py 220 20 eeval > $OUT/frag_bench.log 2>&1
 python tools/trace_iteration.py gpurun_out/kt > $OUT/iteration_kernel_trace.txt

@@ -108,6 +108,9 @@ def one_size(lib, n, o, nbest=None, lockstep_upto=None):
     if lockstep:
         run = lambda: solve_batch([x[0] for x in frs], [o] * nbest, hs, dm0s, opts=opts, eeval=True)
     else:
+        # the single-stream solves left their working set parked in this thread's context; the fragments in flight allocate theirs on contexts of their
+        # own, so it goes back first (n = 300: 86 GB parked here + 2 x 86 GB in flight + 33 GB of ERI blocks is more than the device holds)
+        check(lib.qemb_trim(), "qemb_trim", lib)
         have = lib.qemb_ctx_count(nbest + 1)
         nw = max(1, min(nbest, have - 1))
 

@@ -148,6 +148,20 @@ int qemb_frag_solve_batch(int nfrag, const qemb_frag_t* frags, const int* nsocc,
                           const qemb_solver_opts* opts, int eeval, double* const* mo_coeff, double* const* mo_energy,
                           double* const* rdm1_emb, double* const* rdm1_mo, double* const* t1, double* const* t2, double* e_frag,
                           double* e_corr_mo, double* e_scf, double* ebe_hf, int* n_iter, int* scf_cycles, int64_t* stats);
+/* solver == "MP2" of be_func (molbe/solver.py:313-317, worker twin molbe/be_parallel.py:123-127): fragment RHF -> solve_mp2 (solver.py:781-826) ->
+ * make_rdm1 (unrelaxed: oo and vv blocks) -> back-rotation -> get_frag_energy, density-fitted on the device: a fragment that holds its 3-index
+ * factor needs only products with it (no ovvv / vvvv block, no iterations); one that holds only the 4-fold packed block goes through the four-index
+ * transformation.  Of opts only scf_*, verbose and strict_convergence are read.  Outputs as qemb_frag_solve (there is no t1); t2 is o*o*v*v,
+ * [i,j,a,b]; any may be NULL.  e_frag[1] is the cumulant two-body term (the dovov part of the MP2 2-RDM); nsocc == n gives the mean-field results. */
+int qemb_frag_solve_mp2(qemb_frag_t f, int nsocc, const double* h, const double* dm0, const qemb_solver_opts* opts, int eeval,
+                        double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* t2, double* e_frag,
+                        double* e_corr_mo, double* e_scf, double* ebe_hf, int* scf_cycles);
+/* ... for every fragment of a sweep in one call, spread over the execution contexts that exist (MP2 has no iterations to run in lock step): what
+ * one-by-one calls return, bit for bit.  Arrays over the fragments as in qemb_frag_solve_batch; e_frag is 3 * nfrag.                             */
+int qemb_frag_solve_mp2_batch(int nfrag, const qemb_frag_t* frags, const int* nsocc, const double* const* h, const double* const* dm0,
+                              const qemb_solver_opts* opts, int eeval, double* const* mo_coeff, double* const* mo_energy,
+                              double* const* rdm1_emb, double* const* rdm1_mo, double* const* t2, double* e_frag, double* e_corr_mo,
+                              double* e_scf, double* ebe_hf, int* scf_cycles);
 /* number of Lambda iterations of the last qemb_frag_solve with relax_density (0 otherwise) */
 int qemb_frag_lambda_iters(qemb_frag_t f, int* n_iter);
 /* fragment RHF only: get_scfObj(fock + heff, eri, nocc, dm0) of molbe/helper.py:73-151 as used by

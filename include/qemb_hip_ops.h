@@ -176,6 +176,10 @@ int qemb_op_cholesky_lower(int64_t n, double* A);
 int qemb_op_tri_inverse_lower(int64_t n, const double* L, double* Linv);
 
 
+/* MP2 amplitudes in one pass (PySCF mp2.kernel, mp/mp2.py: t2 = (ia|jb) / e_ijab, E = sum t2 (2 (ia|jb) - (ib|ja))): from ovov[i,a,j,b] and the
+ * orbital energies (all on the device) t2[i,j,a,b], G[i,a,j,b] = 2 t2[i,j,a,b] - t2[j,i,a,b] and the energy (host).  Outputs must not alias ovov. */
+int qemb_op_mp2_amplitudes(int64_t o, int64_t v, const double* ovov, const double* eo, const double* ev, double* t2, double* G, double* e_host);
+
 /* measurement hooks: set up SCF + integrals once, then run/timed single CCSD iterations                */
 int qemb_frag_prepare_ccsd(qemb_frag_t f, int nsocc, const double* h, const double* dm0, const qemb_solver_opts* opts);
 int qemb_frag_ccsd_iterate(qemb_frag_t f, int niter, double* e_corr, double* normt);

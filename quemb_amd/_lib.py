@@ -87,6 +87,7 @@ def _declare(lib):
     f("qemb_op_outer4", I, C.POINTER(L), P, L, L, P, L, L, P, C.POINTER(L), D, D)
     f("qemb_op_div_denom", I, P, L, L, L, L, P, P, P, P)
     f("qemb_op_dot", I, L, P, P, P)
+    f("qemb_op_mp2_amplitudes", I, L, L, P, P, P, P, P, C.POINTER(D))
     f("qemb_op_absmax", I, L, P, P)
     f("qemb_op_gemv_rows", I, L, L, P, L, P, P, D, D)
     f("qemb_op_gemv_rows_batched", I, L, L, L, P, L, L, P, L, P, D, D)
@@ -166,6 +167,8 @@ def _declare(lib):
     f("qemb_frag_set_energy_data", I, V, P, P, P, D, IP, I)
     f("qemb_frag_jk", I, V, P, P, P)
     f("qemb_frag_solve", I, V, I, P, P, OP, I, P, P, P, P, P, P, P, DP, DP, DP, IP, IP)
+    f("qemb_frag_solve_mp2", I, V, I, P, P, OP, I, P, P, P, P, P, P, DP, DP, DP, IP)
+    f("qemb_frag_solve_mp2_batch", I, I, P, IP, P, P, OP, I, P, P, P, P, P, P, P, P, P, IP)
     f("qemb_frag_lambda_iters", I, P, C.POINTER(C.c_int))
     f("qemb_frag_solve_batch", I, I, P, IP, P, P, OP, I, P, P, P, P, P, P, P, P, P, P, IP, IP, C.POINTER(L))
     f("qemb_frag_scf", I, V, I, P, P, OP, P, P, P, P, DP, IP, IP)

@@ -120,7 +120,7 @@ def be_func_parallel(pot, Fobjs, Nocc, solver, enuc, solver_args=None, scratch_d
                      stats=None, emap=None, nstreams=1, lockstep=False):
     """Same return contract as be_func (molbe/be_parallel.py:413-553).  `Fobjs` is the full fragment list on every
     rank; only the fragments with owner[i] == rank need device state (fock / ERIs) on this rank."""
-    if solver != "CCSD":
+    if solver not in ("CCSD", "MP2"):
         raise ValueError("Solver not implemented")
     rank, ws = world()
     if owner is None:
@@ -132,7 +132,7 @@ def be_func_parallel(pot, Fobjs, Nocc, solver, enuc, solver_args=None, scratch_d
     from .solver import solve_fragments
     err = None
     try:
-        for out in solve_fragments(pot, [Fobjs[i] for i in mine], only_chem, opts, eeval, use_cumulant, relax_density, nstreams, lockstep, stats):
+        for out in solve_fragments(pot, [Fobjs[i] for i in mine], only_chem, opts, eeval, use_cumulant, relax_density, nstreams, lockstep, stats, solver):
             buf[2 * nm + 4] += out["n_iter"]
             if eeval:
                 buf[2 * nm + 1: 2 * nm + 4] += out["e_frag"]

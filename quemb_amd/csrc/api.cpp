@@ -257,6 +257,12 @@ int qemb_op_pack_density_sym(int64_t n, const double* D, double* Dp) { return de
 int qemb_op_jacobi_svd(int64_t m, int64_t n, double* G, double* s, double* U, double* V, int* sweeps) { return dev_jacobi_svd(m, n, G, s, U, V, sweeps); }
 int qemb_op_cholesky_lower(int64_t n, double* A) { return dev_cholesky_lower(n, A); }
 int qemb_op_tri_inverse_lower(int64_t n, const double* L, double* Linv) { return dev_tri_inverse_lower(n, L, Linv); }
+int qemb_op_mp2_amplitudes(int64_t o, int64_t v, const double* ovov, const double* eo, const double* ev, double* t2, double* G, double* e_host) {
+  DBuf part, e;
+  QTRY(part.alloc(dev_mp2_partial_count(o, v))); QTRY(e.alloc(1));
+  QTRY(dev_mp2_amplitudes(o, v, ovov, eo, ev, t2, G, part, e));
+  return e_host ? dev_d2h(e_host, e, sizeof(double)) : dev_sync();
+}
 
 // ---------------------------------------------------------------- fragment solver ----------------
 void qemb_default_opts(qemb_solver_opts* o) {
@@ -376,6 +382,50 @@ int qemb_frag_solve_batch(int nfrag, const qemb_frag_t* frags, const int* nsocc,
     if (ebe_hf) ebe_hf[f] = res[f].ebe_hf;
   }
   if (stats) { stats[0] = st.merged_runs; stats[1] = st.launches; stats[2] = st.grouped; stats[3] = st.operations; stats[4] = st.max_group; }
+  return rc;
+}
+int qemb_frag_solve_mp2(qemb_frag_t f, int nsocc, const double* h, const double* dm0, const qemb_solver_opts* opts, int eeval,
+                        double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* t2, double* e_frag,
+                        double* e_corr_mo, double* e_scf, double* ebe_hf, int* scf_cycles) {
+  CHECK_FRAG(f); CHECK_OPTS(opts);
+  if (!h) { set_error("qemb_frag_solve_mp2: h is NULL"); return QEMB_ERR_ARG; }
+  FragmentResult r;
+  int rc = FRAG(f)->solve_mp2(nsocc, h, dm0, to_opts(opts), eeval, &r, mo_coeff, mo_energy, rdm1_emb, rdm1_mo, t2);
+  if (scf_cycles) *scf_cycles = r.scf_cycles;
+  FRAG(f)->last_lambda_iters = 0;
+  if (rc < 0) return rc;
+  if (e_frag) { e_frag[0] = r.e_frag[0]; e_frag[1] = r.e_frag[1]; e_frag[2] = r.e_frag[2]; }
+  if (e_corr_mo) *e_corr_mo = r.e_corr_mo;
+  if (e_scf) *e_scf = r.e_scf;
+  if (ebe_hf) *ebe_hf = r.ebe_hf;
+  return rc;        // QEMB_OK, or QEMB_WARN_NOCONV with strict_convergence = 0
+}
+int qemb_frag_solve_mp2_batch(int nfrag, const qemb_frag_t* frags, const int* nsocc, const double* const* h, const double* const* dm0,
+                              const qemb_solver_opts* opts, int eeval, double* const* mo_coeff, double* const* mo_energy,
+                              double* const* rdm1_emb, double* const* rdm1_mo, double* const* t2, double* e_frag, double* e_corr_mo,
+                              double* e_scf, double* ebe_hf, int* scf_cycles) {
+  if (nfrag < 0 || (nfrag > 0 && (!frags || !nsocc || !h))) { set_error("qemb_frag_solve_mp2_batch: bad arguments"); return QEMB_ERR_ARG; }
+  CHECK_OPTS(opts);
+  std::vector<Fragment*> frs; std::vector<int> o; std::vector<const double*> hs, dms; std::vector<Fragment::BatchOutputs> outs(nfrag);
+  for (int f = 0; f < nfrag; ++f) {
+    if (!frags[f] || !h[f]) { set_error("qemb_frag_solve_mp2_batch: null fragment handle or h"); return QEMB_ERR_ARG; }
+    for (int g = 0; g < f; ++g) if (frags[g] == frags[f]) { set_error("qemb_frag_solve_mp2_batch: the same fragment twice"); return QEMB_ERR_ARG; }
+    frs.push_back(FRAG(frags[f])); o.push_back(nsocc[f]); hs.push_back(h[f]); dms.push_back(dm0 ? dm0[f] : nullptr);
+    auto pick = [&](double* const* arr) { return arr ? arr[f] : nullptr; };
+    outs[f].mo_coeff = pick(mo_coeff); outs[f].mo_energy = pick(mo_energy); outs[f].rdm1_emb = pick(rdm1_emb);
+    outs[f].rdm1_mo = pick(rdm1_mo); outs[f].t2 = pick(t2);
+  }
+  std::vector<FragmentResult> res;
+  const int rc = Fragment::solve_mp2_batch(frs, o, hs, dms, to_opts(opts), eeval, res, outs);
+  for (int f = 0; f < nfrag && f < (int)res.size(); ++f) {
+    if (scf_cycles) scf_cycles[f] = res[f].scf_cycles;
+    frs[f]->last_lambda_iters = 0;
+    if (rc < 0) continue;
+    if (e_frag) for (int k = 0; k < 3; ++k) e_frag[3 * f + k] = res[f].e_frag[k];
+    if (e_corr_mo) e_corr_mo[f] = res[f].e_corr_mo;
+    if (e_scf) e_scf[f] = res[f].e_scf;
+    if (ebe_hf) ebe_hf[f] = res[f].ebe_hf;
+  }
   return rc;
 }
 int qemb_frag_lambda_iters(qemb_frag_t f, int* n_iter) { CHECK_FRAG(f); if (n_iter) *n_iter = FRAG(f)->last_lambda_iters; return QEMB_OK; }

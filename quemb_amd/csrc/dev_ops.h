@@ -278,6 +278,18 @@ int dev_small_k_update(int64_t batch, int64_t M, int64_t N, int64_t K, double al
 // add ([v][v], or S split-K slabs of it `stride` apart that are added up in slab order): Y = traces + scale * add
 int dev_ccsd_y_traces(int64_t o, int64_t v, const double* ZC, const double* ZB, double* Y, const double* add = nullptr, int S = 1, int64_t stride = 0, double scale = 1.0);
 
+// ---- MP2 amplitudes (mp2.cpp; kernel in mp2_ops.hip, scalar restatement for the mock in mp2_ops_hostcheck.cpp) ------------------------------
+// From ovov[i,a,j,b] = (ia|jb) and the orbital energies, ONE pass over the o^2 v^2 elements (each tile of ovov and its (a <-> b) partner read once):
+//   t2[i,j,a,b] = ovov[i,a,j,b] / (eo[i] + eo[j] - ev[a] - ev[b])          ([o][o][v][v])
+//   G [i,a,j,b] = 2 t2[i,j,a,b] - t2[j,i,a,b]                              ([o][v][o][v], the layout of ovov; (ja|ib) is read as its twin (ib|ja))
+//   e_dev[0]    = sum t2[i,j,a,b] (2 ovov[i,a,j,b] - ovov[i,b,j,a])        (one partial per workgroup, added up by a second small launch in a fixed order)
+// partials: dev_mp2_partial_count(o, v) doubles of scratch.  None of the outputs may alias ovov.
+inline int64_t dev_mp2_partial_count(int64_t o, int64_t v) {
+  const int64_t nt = (v + 31) / 32, oo = o * o;
+  return nt * (nt + 1) / 2 * (oo < 4096 ? oo : 4096);
+}
+int dev_mp2_amplitudes(int64_t o, int64_t v, const double* ovov, const double* eo, const double* ev, double* t2, double* G, double* partials, double* e_dev);
+
 // ---- screening helpers of the semi-sparse DF transform ---------------------------------------------------------------
 // out[i] = (|x[i]| >= eps) ? 1 : 0
 int dev_threshold_mask(int64_t n, const double* x, double eps, double* out);

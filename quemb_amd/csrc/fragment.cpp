@@ -6,6 +6,7 @@
 // helper.py:182-189, :303-304).
 #include "fragment.h"
 #include "ao2mo.h"
+#include "mp2.h"
 #include <string>
 #include <chrono>
 #include <cstdio>
@@ -419,6 +420,31 @@ class PhasePool {
   int active_ = 0, pending_ = 0, nworkers_ = 0;
   unsigned long long gen_ = 0;
 };
+// fn(f) for every fragment of a batched call: each on the worker thread of fragment f bound to execution context f + 1 (threaded), or one after the other; the
+// first failure (in fragment order) is the call's status and error text
+struct Fanout {
+  int F; bool threaded; PhasePool* pool; std::vector<int>& rc; std::vector<std::string>& msg;
+  template <class Fn> int operator()(Fn fn) {
+    if (threaded) {
+      auto body = [&](int f) {
+        rc[f] = dev_ctx_bind(f + 1);
+        if (rc[f] == 0) rc[f] = fn(f);
+        if (rc[f] != 0) msg[f] = last_error();
+      };
+      if (pool) pool->run(F, body);
+      else {
+        std::vector<std::thread> th;
+        for (int f = 0; f < F; ++f) th.emplace_back([&, f] { body(f); });
+        for (auto& t : th) t.join();
+      }
+    } else {
+      for (int f = 0; f < F; ++f) { rc[f] = fn(f); if (rc[f] != 0) msg[f] = last_error(); }
+    }
+    int worst = 0;
+    for (int f = 0; f < F; ++f) if (rc[f] < 0 && worst == 0) { worst = rc[f]; set_error("fragment " + std::to_string(f) + ": " + msg[f]); }
+    return worst;
+  }
+};
 }  // namespace
 
 int Fragment::solve_batch(const std::vector<Fragment*>& frs, const std::vector<int>& o, const std::vector<const double*>& h,
@@ -439,26 +465,7 @@ int Fragment::solve_batch(const std::vector<Fragment*>& frs, const std::vector<i
   static const bool pool_on = !(std::getenv("QEMB_PHASE_POOL") && std::atoi(std::getenv("QEMB_PHASE_POOL")) == 0);      // (0: a std::thread per fragment and phase, for A/B runs)
   PhasePool* pool = (threaded && pool_on) ? PhasePool::acquire(F) : nullptr;
   struct PoolRelease { PhasePool* p; ~PoolRelease() { if (p) p->release(); } } pool_guard{pool};
-  auto per_fragment = [&](auto fn) {
-    if (threaded) {
-      auto body = [&](int f) {
-        rc[f] = dev_ctx_bind(f + 1);
-        if (rc[f] == 0) rc[f] = fn(f);
-        if (rc[f] != 0) msg[f] = last_error();
-      };
-      if (pool) pool->run(F, body);
-      else {
-        std::vector<std::thread> th;
-        for (int f = 0; f < F; ++f) th.emplace_back([&, f] { body(f); });
-        for (auto& t : th) t.join();
-      }
-    } else {
-      for (int f = 0; f < F; ++f) { rc[f] = fn(f); if (rc[f] != 0) msg[f] = last_error(); }
-    }
-    int worst = 0;
-    for (int f = 0; f < F; ++f) if (rc[f] < 0 && worst == 0) { worst = rc[f]; set_error("fragment " + std::to_string(f) + ": " + msg[f]); }
-    return worst;
-  };
+  Fanout per_fragment{F, threaded, pool, rc, msg};
   // Before the iterations: the fragment RHF per fragment (host round trips inside), then MO integrals + CCSD set-up + starting amplitudes.  The latter is a pure
   // launch sequence (~60 launches per small fragment) and CAN be recorded as a tape per fragment and run merged on the home stream like the iterations
   // (QEMB_TAPE_PREPHASE=1).  Measured in round 5 and left off: recording the sequence anew every sweep (stream capture + node queries) and running the merged
@@ -634,6 +641,51 @@ void Fragment::retire_solver() {
   cc_.reset();
 }
 
+// get_frag_energy (helper.py:286-339) from the embedding-basis density and the contracted two-body pieces -- Z1, Z2 (energy_intermediates of the CCSD or the MP2
+// solver), or Imat of the relaxed path -- and update_ebe_hf: the host tail every correlated solve of a fragment shares
+int Fragment::frag_energies(int o, const std::vector<double>& C, const std::vector<double>& rdm, const std::vector<double>& hfdm, const std::vector<double>& Z1,
+                            const std::vector<double>& Z2, const std::vector<double>* Imat, FragmentResult* res) {
+  const int n = n_, v = n - o;
+  const int64_t n2 = (int64_t)n * n;
+  std::vector<double> J((size_t)n2), K((size_t)n2);
+  std::vector<double> e1((size_t)nf_, 0.0), e2((size_t)nf_, 0.0), ec((size_t)nf_, 0.0);
+  for (int P = 0; P < nf_; ++P) {
+    double s1 = 0, sc = 0;
+    for (int Q = 0; Q < n; ++Q) {
+      const double d = 2.0 * (rdm[(size_t)P * n + Q] - hfdm[(size_t)P * n + Q]);   // helper.py:286
+      s1 += h1_[(size_t)P * n + Q] * d; sc += veff0_[(size_t)P * n + Q] * d;
+    }
+    e1[P] = s1; ec[P] = sc;
+    double s2 = 0;
+    if (Imat) {   // e2_P = 1/4 sum_p' C[P,p'] I[p',P]  (cc_lambda.h)
+      for (int q = 0; q < n; ++q) s2 += C[(size_t)P * n + q] * (*Imat)[(size_t)q * nf_ + P];
+      e2[P] = 0.25 * s2;
+      continue;
+    }
+    for (int i = 0; i < o; ++i) s2 += C[(size_t)P * n + i] * Z1[(size_t)i * nf_ + P];
+    for (int a = 0; a < v; ++a) s2 += C[(size_t)P * n + o + a] * Z2[(size_t)a * nf_ + P];
+    e2[P] = 0.5 * s2;
+  }
+  res->e_frag[0] = res->e_frag[1] = res->e_frag[2] = 0.0;
+  for (int c : centers_) { res->e_frag[0] += weight_ * e1[c]; res->e_frag[1] += weight_ * e2[c]; res->e_frag[2] += weight_ * ec[c]; }
+  // update_ebe_hf (pfrag.py:327-400) with D = Co Co^T: e2_i = sum_j D_ij (2 J_ij - K_ij), J/K of D = J,K(dm)/2
+  if (!veff_.empty()) {
+    QTRY(dev_d2h(J.data(), J_, sizeof(double) * n2));
+    QTRY(dev_d2h(K.data(), K_, sizeof(double) * n2));
+    double ehf = 0.0;
+    for (int c : centers_) {
+      double a = 0;
+      for (int Q = 0; Q < n; ++Q) {
+        const double D = hfdm[(size_t)c * n + Q];
+        a += 2.0 * h1_[(size_t)c * n + Q] * D + veff_[(size_t)c * n + Q] * D + D * (J[(size_t)c * n + Q] - 0.5 * K[(size_t)c * n + Q]);
+      }
+      ehf += weight_ * a;
+    }
+    res->ebe_hf = ehf;
+  }
+  return 0;
+}
+
 int Fragment::solve_end(double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* t1_out, double* t2_out) {
   const int o = sp_.o, n = n_, v = n - o, eeval = sp_.eeval;
   const FragmentOptions& opt = sp_.opt;
@@ -642,7 +694,6 @@ int Fragment::solve_end(double* mo_coeff, double* mo_energy, double* rdm1_emb, d
   bool unconverged = sp_.unconverged;
   const int64_t n2 = (int64_t)n * n;
   const std::vector<double>& C = sp_.C; const std::vector<double>& eps = sp_.eps;
-  std::vector<double> J((size_t)n2), K((size_t)n2);
   if (!no_virtuals && !res->ccsd_converged) {
     set_error("CCSD did not converge in max_cycle iterations");
     if (opt.strict) return QEMB_ERR_NOCONV;
@@ -710,41 +761,7 @@ int Fragment::solve_end(double* mo_coeff, double* mo_energy, double* rdm1_emb, d
     std::vector<double> Z1, Z2;
     if (!opt.relax_density && !no_virtuals) QTRY(cc_->energy_intermediates(Z1, Z2));
     if (no_virtuals) { Z1.assign((size_t)o * nf_, 0.0); Z2.clear(); }
-    std::vector<double> e1((size_t)nf_, 0.0), e2((size_t)nf_, 0.0), ec((size_t)nf_, 0.0);
-    for (int P = 0; P < nf_; ++P) {
-      double s1 = 0, sc = 0;
-      for (int Q = 0; Q < n; ++Q) {
-        const double d = 2.0 * (rdm[(size_t)P * n + Q] - hfdm[(size_t)P * n + Q]);   // helper.py:286
-        s1 += h1_[(size_t)P * n + Q] * d; sc += veff0_[(size_t)P * n + Q] * d;
-      }
-      e1[P] = s1; ec[P] = sc;
-      double s2 = 0;
-      if (opt.relax_density) {   // e2_P = 1/4 sum_p' C[P,p'] I[p',P]  (cc_lambda.h)
-        for (int q = 0; q < n; ++q) s2 += C[(size_t)P * n + q] * Imat[(size_t)q * nf_ + P];
-        e2[P] = 0.25 * s2;
-        continue;
-      }
-      for (int i = 0; i < o; ++i) s2 += C[(size_t)P * n + i] * Z1[(size_t)i * nf_ + P];
-      for (int a = 0; a < v; ++a) s2 += C[(size_t)P * n + o + a] * Z2[(size_t)a * nf_ + P];
-      e2[P] = 0.5 * s2;
-    }
-    res->e_frag[0] = res->e_frag[1] = res->e_frag[2] = 0.0;
-    for (int c : centers_) { res->e_frag[0] += weight_ * e1[c]; res->e_frag[1] += weight_ * e2[c]; res->e_frag[2] += weight_ * ec[c]; }
-    // update_ebe_hf (pfrag.py:327-400) with D = Co Co^T: e2_i = sum_j D_ij (2 J_ij - K_ij), J/K of D = J,K(dm)/2
-    if (!veff_.empty()) {
-      QTRY(dev_d2h(J.data(), J_, sizeof(double) * n2));
-      QTRY(dev_d2h(K.data(), K_, sizeof(double) * n2));
-      double ehf = 0.0;
-      for (int c : centers_) {
-        double a = 0;
-        for (int Q = 0; Q < n; ++Q) {
-          const double D = hfdm[(size_t)c * n + Q];
-          a += 2.0 * h1_[(size_t)c * n + Q] * D + veff_[(size_t)c * n + Q] * D + D * (J[(size_t)c * n + Q] - 0.5 * K[(size_t)c * n + Q]);
-        }
-        ehf += weight_ * a;
-      }
-      res->ebe_hf = ehf;
-    }
+    QTRY(frag_energies(o, C, rdm, hfdm, Z1, Z2, opt.relax_density ? &Imat : nullptr, res));
   }
   // ---- keep amplitudes for a warm start of the next sweep
   if ((opt.keep_amplitudes || opt.warm_start) && !no_virtuals) {
@@ -758,6 +775,84 @@ int Fragment::solve_end(double* mo_coeff, double* mo_energy, double* rdm1_emb, d
   QTRY(dev_sync());
   retire_solver();
   return unconverged ? QEMB_WARN_NOCONV : 0;
+}
+
+// ---- solver == "MP2": everything after the fragment RHF is a handful of products with the factor and one pass over o^2 v^2 (mp2.cpp)
+int Fragment::solve_mp2(int o, const double* h, const double* dm0, const FragmentOptions& opt, int eeval, FragmentResult* res,
+                        double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* t2_out) {
+  QTRY(solve_begin_scf(o, h, dm0, opt, eeval, res));
+  const int n = n_, v = n - o;
+  const int64_t n2 = (int64_t)n * n;
+  const std::vector<double>& C = sp_.C;
+  if (eeval && (h1_.empty() || veff0_.empty())) { set_error("Fragment: set_energy_data(h1, veff0, ...) before an energy evaluation"); return QEMB_ERR_ARG; }
+  res->e_corr_mo = 0.0; res->n_iter = 0; res->ccsd_converged = true; res->lambda_iters = 0;
+  std::vector<double> doo((size_t)o * o, 0.0), dvv, Z1, Z2;
+  if (v > 0) {
+    Mp2Solver mp;
+    if (use_factor_route()) {
+      sp_.X1.release();
+      last_route_factor_ = true;
+      QTRY(mp.run_factor(n, o, eeval ? nf_ : 0, df_naux_, df_factor_, C_, eps_));
+    } else {      // the packed block: the four-index transformation, of which ovov, A1, A2 are read (DESIGN.md prices it)
+      MoIntegrals ints;
+      QTRY(mo_integrals(o, eeval ? nf_ : 0, sp_.X1, sp_.x1_unpacked, ints, false, false));
+      sp_.X1.release();
+      QTRY(mp.run_blocks(std::move(ints), eps_));
+    }
+    res->e_corr_mo = mp.e_corr();
+    if (t2_out) QTRY(dev_d2h(t2_out, mp.t2(), sizeof(double) * (int64_t)o * o * v * v));
+    QTRY(mp.rdm1_blocks(doo, dvv));
+    if (eeval) QTRY(mp.energy_intermediates(Z1, Z2));
+  } else {      // no virtual orbitals: the mean-field results, as the CCSD path
+    sp_.X1.release();
+    if (eeval) Z1.assign((size_t)o * nf_, 0.0);
+  }
+  // rdm1_mo = [[2 I + doo + doo^T, 0], [0, dvv + dvv^T]]   (PySCF mp2.make_rdm1)
+  std::vector<double> dm((size_t)n2, 0.0);
+  for (int i = 0; i < o; ++i) for (int j = 0; j < o; ++j) dm[(size_t)i * n + j] = doo[(size_t)i * o + j] + doo[(size_t)j * o + i] + (i == j ? 2.0 : 0.0);
+  for (int a = 0; a < v; ++a) for (int b = 0; b < v; ++b) dm[(size_t)(o + a) * n + o + b] = dvv[(size_t)a * v + b] + dvv[(size_t)b * v + a];
+  if (rdm1_mo) std::memcpy(rdm1_mo, dm.data(), sizeof(double) * n2);
+  // rdm_emb = C rdm1_mo C^T / 2   (solver.py:496-505); hf_dm = Co Co^T
+  std::vector<double> rdm((size_t)n2, 0.0), hfdm((size_t)n2, 0.0);
+  for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int i = 0; i < o; ++i) s += C[(size_t)p * n + i] * C[(size_t)q * n + i]; hfdm[(size_t)p * n + q] = s; }
+  if (v > 0) {
+    DBuf D, T, R;
+    QTRY(D.alloc(n2)); QTRY(T.alloc(n2)); QTRY(R.alloc(n2));
+    QTRY(dev_h2d(D, dm.data(), sizeof(double) * n2));
+    QTRY(gemm_nn(n, n, n, 1.0, C_, D, 0.0, T));
+    QTRY(gemm_nt(n, n, n, 0.5, T, C_, 0.0, R));
+    QTRY(dev_d2h(rdm.data(), R, sizeof(double) * n2));
+    for (int p = 0; p < n; ++p) for (int q = 0; q < p; ++q) { const double sym = 0.5 * (rdm[(size_t)p * n + q] + rdm[(size_t)q * n + p]); rdm[(size_t)p * n + q] = rdm[(size_t)q * n + p] = sym; }
+  } else rdm = hfdm;
+  if (rdm1_emb) std::memcpy(rdm1_emb, rdm.data(), sizeof(double) * n2);
+  if (mo_coeff) std::memcpy(mo_coeff, C.data(), sizeof(double) * n2);
+  if (mo_energy) std::memcpy(mo_energy, sp_.eps.data(), sizeof(double) * n);
+  if (eeval) QTRY(frag_energies(o, C, rdm, hfdm, Z1, Z2, nullptr, res));
+  QTRY(dev_sync());      // (the next sweep may drive this fragment from another execution context, as after solve_end)
+  return sp_.unconverged ? QEMB_WARN_NOCONV : 0;
+}
+
+int Fragment::solve_mp2_batch(const std::vector<Fragment*>& frs, const std::vector<int>& o, const std::vector<const double*>& h, const std::vector<const double*>& dm0,
+                              const FragmentOptions& opt, int eeval, std::vector<FragmentResult>& res, const std::vector<BatchOutputs>& outs) {
+  const int F = (int)frs.size();
+  if (F == 0) return 0;
+  res.assign(F, FragmentResult());
+  const int have = dev_ctx_count(F + 1);
+  if (have < 0) return have;
+  const bool threaded = have >= F + 1 && F > 1;      // (the scalar mock has one execution context: one fragment after the other)
+  std::vector<int> rc(F, 0), rc_solve(F, 0);
+  std::vector<std::string> msg(F);
+  PhasePool* pool = threaded ? PhasePool::acquire(F) : nullptr;
+  struct PoolRelease { PhasePool* p; ~PoolRelease() { if (p) p->release(); } } pool_guard{pool};
+  Fanout per_fragment{F, threaded, pool, rc, msg};
+  const int worst = per_fragment([&](int f) {
+    rc_solve[f] = frs[f]->solve_mp2(o[f], h[f], dm0[f], opt, eeval, &res[f], outs[f].mo_coeff, outs[f].mo_energy, outs[f].rdm1_emb, outs[f].rdm1_mo, outs[f].t2);
+    return rc_solve[f];
+  });
+  if (worst) return worst;
+  int warn = 0;
+  for (int f = 0; f < F; ++f) if (rc_solve[f] > 0) { warn = rc_solve[f]; set_error("fragment " + std::to_string(f) + ": " + msg[f]); }
+  return warn;
 }
 
 }  // namespace qemb

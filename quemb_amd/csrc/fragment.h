@@ -84,6 +84,13 @@ class Fragment {
   static int solve_batch(const std::vector<Fragment*>& frs, const std::vector<int>& o, const std::vector<const double*>& h,
                          const std::vector<const double*>& dm0, const FragmentOptions& opt, int eeval, std::vector<FragmentResult>& res,
                          const std::vector<BatchOutputs>& outs, LockstepStats* stats);
+  // solver == "MP2" of be_func (molbe/solver.py:313-317): fragment RHF -> density-fitted MP2 (mp2.h) -> unrelaxed MP2 1-RDM (oo and vv blocks) -> back-rotation ->
+  // fragment energies.  Of opt only scf and strict are read; no amplitudes are kept.  Outputs as solve(); there is no t1.
+  int solve_mp2(int o, const double* h, const double* dm0, const FragmentOptions& opt, int eeval, FragmentResult* res,
+                double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* t2);
+  // ... for every fragment of a sweep, spread over the execution contexts that exist (MP2 has no iterations to run in lock step).  Results as from solve_mp2(), bit for bit.
+  static int solve_mp2_batch(const std::vector<Fragment*>& frs, const std::vector<int>& o, const std::vector<const double*>& h, const std::vector<const double*>& dm0,
+                             const FragmentOptions& opt, int eeval, std::vector<FragmentResult>& res, const std::vector<BatchOutputs>& outs);
   // Bench hooks: set up the CCSD problem once (SCF + transform), then time single iterations.
   int prepare_ccsd(int o, const double* h, const double* dm0, const FragmentOptions& opt);
   int ccsd_iterate(int niter, double* e_corr, double* normt);
@@ -113,6 +120,8 @@ class Fragment {
   int scf_operand(DBuf& X1, bool* unpacked);
   int check_df_factor();
   int mo_integrals(int o, int nf, DBuf& X1, bool x1_unpacked, MoIntegrals& ints, bool build_Vl, bool build_T34);
+  int frag_energies(int o, const std::vector<double>& C, const std::vector<double>& rdm, const std::vector<double>& hfdm, const std::vector<double>& Z1,
+                    const std::vector<double>& Z2, const std::vector<double>* Imat, FragmentResult* res);
   DBuf df_factor_; int df_naux_ = 0; int mo_route_ = -1; bool last_route_factor_ = false;
   bool have_C_ = false; int c_nocc_ = -1;    // C_ holds the orbitals of a converged earlier solve with c_nocc_ occupied orbitals (the Jacobi eigensolver starts in that basis)
   int n_, nf_, o_ = -1;

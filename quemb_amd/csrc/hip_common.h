@@ -16,4 +16,21 @@ hipStream_t hip_stream();  // the library stream (created by dev_init)
       return QEMB_ERR_DEVICE;                                                              \
     }                                                                                         \
   } while (0)
+
+// XCD-aware logical block index of the tiled HBM passes (round 4; profiles/r04_hbm_pmc.json).  Workgroups are dealt round-robin over the eight
+// XCDs, each with its own L2, so neighbouring 32 x 32 tiles -- whose 256-byte row pieces start at arbitrary offsets and share their first and
+// last 128-byte lines -- ran on different XCDs and every shared line was fetched from HBM twice: FETCH_SIZE showed 1.2-1.5 x the algorithmic
+// reads for the unpack, scatter and finishing passes.  Here the linear block number is mapped so that each XCD works through ONE contiguous
+// range of the logical order (x fastest): neighbours in x run on the same XCD at about the same time and meet in its L2.  A bijection of the
+// grid: placement is a matter of speed only (inside a grouped launch the member's blocks are offset and it is merely another permutation).
+__device__ __forceinline__ uint3 xcd_logical_block(const uint3 BID, const uint3 GDIM) {
+  const unsigned long long total = (unsigned long long)GDIM.x * GDIM.y * GDIM.z;
+  const unsigned long long lin = ((unsigned long long)BID.z * GDIM.y + BID.y) * GDIM.x + BID.x;
+  const unsigned long long q = total >> 3, r = total & 7ull;
+  const unsigned long long xcd = lin & 7ull, k = lin >> 3;
+  const unsigned long long base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+  const unsigned long long L = base + k;
+  const unsigned long long xy = (unsigned long long)GDIM.x * GDIM.y;
+  return make_uint3((unsigned)(L % GDIM.x), (unsigned)((L % xy) / GDIM.x), (unsigned)(L / xy));
+}
 }  // namespace qemb

@@ -131,6 +131,27 @@ class DeviceFragment:
                    scf_cycles=ncyc.value, lambda_iters=nlam.value)
         return out
 
+    def solve_mp2(self, nsocc, h, dm0=None, opts: SolverOpts | None = None, eeval=True, want_t2=False):
+        """solver == "MP2" of be_func (qemb_frag_solve_mp2): fragment RHF -> density-fitted MP2 -> unrelaxed MP2 1-RDM -> fragment energies.
+        The dict `solve` returns, with t1 = None and n_iter = 0; of `opts` only scf_*, verbose and strict_convergence are read."""
+        n, o = self.n, int(nsocc)
+        v = n - o
+        h = np.ascontiguousarray(h, dtype=np.float64)
+        dm0 = None if dm0 is None else np.ascontiguousarray(dm0, dtype=np.float64)
+        opts = opts or default_opts(self.lib)
+        out = dict(mo_coeff=np.empty((n, n)), mo_energy=np.empty(n), rdm1_emb=np.empty((n, n)), rdm1_mo=np.empty((n, n)),
+                   t1=None, t2=np.empty((o, o, v, v)) if want_t2 else None)
+        e_frag = np.zeros(3)
+        ecorr, escf, ebehf = C.c_double(), C.c_double(), C.c_double()
+        ncyc = C.c_int()
+        check(self.lib.qemb_frag_solve_mp2(self.h, o, h.ctypes.data, _p(dm0), C.byref(opts), int(bool(eeval)),
+                                           out["mo_coeff"].ctypes.data, out["mo_energy"].ctypes.data, out["rdm1_emb"].ctypes.data,
+                                           out["rdm1_mo"].ctypes.data, _p(out["t2"]), e_frag.ctypes.data,
+                                           C.byref(ecorr), C.byref(escf), C.byref(ebehf), C.byref(ncyc)),
+              "qemb_frag_solve_mp2", self.lib)
+        out.update(e_frag=e_frag, e_corr_mo=ecorr.value, e_scf=escf.value, ebe_hf=ebehf.value, n_iter=0, scf_cycles=ncyc.value, lambda_iters=0)
+        return out
+
     def scf(self, nsocc, h, dm0=None, opts=None):
         """Fragment RHF only (Frags.scf(fs=True)); returns dict(mo_coeff, mo_energy, J, K, e_scf, converged, cycles)."""
         n = self.n
@@ -187,11 +208,15 @@ class DeviceFragment:
             pass
 
 
-def solve_batch(frags, nsoccs, hs, dm0s=None, opts: SolverOpts | None = None, eeval=True, want_t2=False, stats=None):
+def solve_batch(frags, nsoccs, hs, dm0s=None, opts: SolverOpts | None = None, eeval=True, want_t2=False, stats=None, solver="CCSD"):
     """qemb_frag_solve_batch: every fragment of `frags` (DeviceFragment objects of one library) in one call -- fragment RHF, MO transformation
     and the density / energy evaluation per fragment on its own stream, the CCSD iterations of all fragments in lock step (one grouped
     launch per operation).  Returns the list of dicts DeviceFragment.solve would return, bit for bit; `stats` (a dict) receives the
-    launch counters of the lock-step iterations."""
+    launch counters of the lock-step iterations.
+    solver="MP2": qemb_frag_solve_mp2_batch -- the fragments spread over the execution contexts that exist (there are no iterations to put in lock
+    step); the dicts DeviceFragment.solve_mp2 would return, bit for bit."""
+    if solver not in ("CCSD", "MP2"):
+        raise ValueError("Solver not implemented")
     F = len(frags)
     if F == 0:
         return []
@@ -204,13 +229,23 @@ def solve_batch(frags, nsoccs, hs, dm0s=None, opts: SolverOpts | None = None, ee
     for fr, o in zip(frags, ns):
         n, v = fr.n, fr.n - o
         outs.append(dict(mo_coeff=np.empty((n, n)), mo_energy=np.empty(n), rdm1_emb=np.empty((n, n)), rdm1_mo=np.empty((n, n)),
-                         t1=np.empty((o, v)), t2=np.empty((o, o, v, v)) if want_t2 else None))
+                         t1=np.empty((o, v)) if solver == "CCSD" else None, t2=np.empty((o, o, v, v)) if want_t2 else None))
     VP = C.c_void_p * F
     arr = lambda xs: VP(*[None if x is None else x.ctypes.data for x in xs])
     handles = VP(*[fr.h for fr in frags])
     nso = (C.c_int * F)(*ns)
     e_frag = np.zeros((F, 3)); ecorr = np.zeros(F); escf = np.zeros(F); ebehf = np.zeros(F)
     nit = (C.c_int * F)(); ncyc = (C.c_int * F)(); st = (C.c_int64 * 5)()
+    if solver == "MP2":
+        check(lib.qemb_frag_solve_mp2_batch(F, handles, nso, arr(hs), arr(dm0s), C.byref(opts), int(bool(eeval)),
+                                            arr([o_["mo_coeff"] for o_ in outs]), arr([o_["mo_energy"] for o_ in outs]), arr([o_["rdm1_emb"] for o_ in outs]),
+                                            arr([o_["rdm1_mo"] for o_ in outs]), arr([o_["t2"] for o_ in outs]),
+                                            e_frag.ctypes.data, ecorr.ctypes.data, escf.ctypes.data, ebehf.ctypes.data, ncyc),
+              "qemb_frag_solve_mp2_batch", lib)
+        for f, o_ in enumerate(outs):
+            o_.update(e_frag=e_frag[f].copy(), e_corr_mo=float(ecorr[f]), e_scf=float(escf[f]), ebe_hf=float(ebehf[f]), n_iter=0,
+                      scf_cycles=int(ncyc[f]), lambda_iters=0)
+        return outs
     check(lib.qemb_frag_solve_batch(F, handles, nso, arr(hs), arr(dm0s), C.byref(opts), int(bool(eeval)),
                                     arr([o_["mo_coeff"] for o_ in outs]), arr([o_["mo_energy"] for o_ in outs]), arr([o_["rdm1_emb"] for o_ in outs]),
                                     arr([o_["rdm1_mo"] for o_ in outs]), arr([o_["t1"] for o_ in outs]), arr([o_["t2"] for o_ in outs]),

@@ -256,21 +256,21 @@ class BE:
         return compute_numerical_jacobian(self, solver, only_chem, nproc, step_size=step_size)
 
     # ------------------------------------------------------------------ sweeps
-    def _sweep(self, pot, **kw):
+    def _sweep(self, pot, solver="CCSD", **kw):
         if self.nstreams is None or self.lockstep is None:
             from .solver import sweep_mode
             mine = [f for i, f in enumerate(self.Fobjs) if self.world <= 1 or self.owner[i] == self.rank]
-            self.nstreams, self.lockstep = sweep_mode(mine, self.nstreams, self.lockstep)
+            self.nstreams, self.lockstep = sweep_mode(mine, self.nstreams, self.lockstep, solver=solver)
         if self.world > 1:
-            return be_func_parallel(pot, self.Fobjs, self.Nocc, "CCSD", self.enuc, owner=self.owner, opts=self.opts,
+            return be_func_parallel(pot, self.Fobjs, self.Nocc, solver, self.enuc, owner=self.owner, opts=self.opts,
                                     stats=self.stats, emap=self.emap, nstreams=self.nstreams, lockstep=self.lockstep, **kw)
-        return be_func(pot, self.Fobjs, self.Nocc, "CCSD", self.enuc, opts=self.opts, stats=self.stats, nstreams=self.nstreams, lockstep=self.lockstep, **kw)
+        return be_func(pot, self.Fobjs, self.Nocc, solver, self.enuc, opts=self.opts, stats=self.stats, nstreams=self.nstreams, lockstep=self.lockstep, **kw)
 
     def oneshot(self, solver="CCSD", use_cumulant=True, nproc=1, ompnum=1, solver_args=None):
-        """mbe.py:1240-1310."""
-        if solver != "CCSD":
+        """mbe.py:1240-1310.  solver: "CCSD" or "MP2"."""
+        if solver not in ("CCSD", "MP2"):
             raise ValueError("Solver not implemented")
-        rets = self._sweep(None, eeval=True, use_cumulant=use_cumulant, return_vec=False)
+        rets = self._sweep(None, solver=solver, eeval=True, use_cumulant=use_cumulant, return_vec=False)
         self.ebe_tot = rets[0] + self.ebe_hf
         self.e_corr = rets[0]
         self.e_components = rets[1]
@@ -284,10 +284,11 @@ class BE:
                  warm_start=True):
         """mbe.py:841-977.  `warm_start` (addition): every sweep after the first starts each fragment's CCSD from the
         amplitudes of the previous sweep, which stay resident on the device (the reference restarts from MP2 at every
-        objective evaluation, solver.py:894-907); the converged amplitudes, hence all results, are the same."""
+        objective evaluation, solver.py:894-907); the converged amplitudes, hence all results, are the same.  solver="MP2": MP2 has no
+        iterations, `warm_start` changes nothing, and relax_density is not read (as in the reference's MP2 branch)."""
         from .opt import BEOPT
         from .jacobian import get_be_error_jacobian
-        if solver != "CCSD":
+        if solver not in ("CCSD", "MP2"):
             raise ValueError("Solver not implemented")
         if method != "QN":
             raise ValueError("This optimization method for BE is not supported")
@@ -299,7 +300,7 @@ class BE:
             pot = [0.0]
         be_ = BEOPT(pot, self.Fobjs, self.Nocc, self.enuc, solver=solver, only_chem=only_chem, use_cumulant=use_cumulant,
                     max_space=max_iter, conv_tol=conv_tol, relax_density=relax_density, ebe_hf=self.ebe_hf,
-                    sweep=self._sweep, verbose=self.rank == 0)
+                    sweep=lambda p, **kw: self._sweep(p, solver=solver, **kw), verbose=self.rank == 0)
         if jac_solver == "Numerical":
             J0 = self.compute_numerical_jacobian(solver, only_chem, nproc, step_size=step_size)      # mbe.py:942-945
         else:

@@ -46,16 +46,16 @@ class _Delta:
 
 
 def compute_numerical_jacobian(beobj, solver="CCSD", only_chem=False, nproc=1, step_size=1e-6):
-    if solver != "CCSD":
+    if solver not in ("CCSD", "MP2"):
         raise ValueError("Solver not implemented")
     pot = np.asarray(beobj.pot if not only_chem else beobj.pot[-1:], dtype=float)
     npot = len(pot)
     J0 = np.zeros((npot, npot))
     # chemical potential: +-h sweeps over all fragments
     x = pot.copy(); x[-1] += step_size
-    J0[:, -1] = beobj._sweep(list(x), only_chem=only_chem, eeval=False, return_vec=True)[1]
+    J0[:, -1] = beobj._sweep(list(x), solver=solver, only_chem=only_chem, eeval=False, return_vec=True)[1]
     x[-1] -= 2 * step_size
-    J0[:, -1] -= beobj._sweep(list(x), only_chem=only_chem, eeval=False, return_vec=True)[1]
+    J0[:, -1] -= beobj._sweep(list(x), solver=solver, only_chem=only_chem, eeval=False, return_vec=True)[1]
     J0[:, -1] /= 2 * step_size
     if only_chem:
         return J0
@@ -73,7 +73,8 @@ def compute_numerical_jacobian(beobj, solver="CCSD", only_chem=False, nproc=1, s
                 rd = []
                 for sgn in (+1.0, -1.0):
                     x = pot.copy(); x[idx] += sgn * step_size
-                    out = f.dev.solve(f.nsocc, f.fock + calc_heff(f, x, only_chem), f.dm0, opts=opts, eeval=False)
+                    solve = f.dev.solve_mp2 if solver == "MP2" else f.dev.solve
+                    out = solve(f.nsocc, f.fock + calc_heff(f, x, only_chem), f.dm0, opts=opts, eeval=False)
                     rd.append(out["rdm1_emb"])
                 view = [None] * len(beobj.Fobjs)
                 view[I] = _Delta(rd[0] - rd[1])

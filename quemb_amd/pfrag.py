@@ -164,9 +164,16 @@ class Frags:
         return None
 
     # ------------------------------------------------------------------ the sweep body
-    def solve(self, opts=None, eeval=True, use_cumulant=True, want_t2=False, relax_density=False):
+    def solve(self, opts=None, eeval=True, use_cumulant=True, want_t2=False, relax_density=False, solver="CCSD"):
         """update_heff -> scf -> solve_ccsd -> rdm1 -> get_frag_energy for this fragment (solver.py:301-547).
-        relax_density: solve_ccsd(relax=True) (solver.py:925-939) -- Lambda equations on the device, response densities."""
+        relax_density: solve_ccsd(relax=True) (solver.py:925-939) -- Lambda equations on the device, response densities.
+        solver="MP2": the MP2 branch (solver.py:313-317) -- solve_mp2, unrelaxed MP2 1-RDM; relax_density is not read, as in the reference."""
+        if solver not in ("CCSD", "MP2"):
+            raise ValueError("Solver not implemented")
+        if solver == "MP2":
+            opts = self._solve_inputs(opts, eeval, False)
+            out = self.dev.solve_mp2(self.nsocc, self.fock + self.heff, self.dm0, opts=opts, eeval=eeval, want_t2=want_t2)
+            return self._solve_outputs(out, eeval, use_cumulant)
         opts = self._solve_inputs(opts, eeval, relax_density)
         out = self.dev.solve(self.nsocc, self.fock + self.heff, self.dm0, opts=opts, eeval=eeval, want_t2=want_t2)
         return self._solve_outputs(out, eeval, use_cumulant)
@@ -198,7 +205,8 @@ class Frags:
     def _noncumulant_energy(self, out):
         """get_frag_energy(use_cumulant=False) (helper.py:292-339): the 2-RDM then carries the mean-field pieces
         (make_rdm2_urlx(with_dm1=True), ccsd_rdm.py:40-53).  They are bilinear in D0 = C_o C_o^T and the first-order
-        change D' = C [[0,t1],[t1^T,0]] C^T, so their contraction with the fragment ERIs reduces to J/K builds on the
+        change D' = C [[0,t1],[t1^T,0]] C^T (MP2: the oo and vv blocks of make_rdm1 -- the expression is bilinear in D0 and
+        D' = 2 (rdm1_emb - D0) whatever blocks D' has), so their contraction with the fragment ERIs reduces to J/K builds on the
         device:  e2_P += sum_Q D0_PQ (J[D'] - K[D']/2 + 2 J[D0] - K[D0])_PQ + D'_PQ (J[D0] - K[D0]/2)_PQ."""
         nf, o = self.n_frag, self.nsocc
         C = out["mo_coeff"]

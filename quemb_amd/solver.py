@@ -1,8 +1,9 @@
 """be_func / solve_error / solve_ccsd -- host mirror of molbe/solver.py over the device fragment solver.
 
-`be_func` keeps the reference's signature (molbe/solver.py:244-257) for solver == "CCSD"; every other solver
-string of the reference (MP2, FCI, SCI, DMRG, ...) is a different code path of QuEmb that this package does
-not replace and raises ValueError("Solver not implemented") exactly like the reference's final else (:490-491).
+`be_func` keeps the reference's signature (molbe/solver.py:244-257) for solver == "CCSD" and solver == "MP2"
+(:313-317); every other solver string of the reference (FCI, SCI, DMRG, ...) is a different code path of QuEmb
+that this package does not replace and raises ValueError("Solver not implemented") exactly like the reference's
+final else (:490-491).
 """
 
 from __future__ import annotations
@@ -102,20 +103,48 @@ def solve_ccsd(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_r
     return out["t1"], out["t2"]
 
 
-def fragment_work_bytes(n, o=None):
+def solve_mp2(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, df_factor=None, opts=None, lib=None):
+    """Device counterpart of solve_mp2 (molbe/solver.py:781-826) with the inputs of `solve_ccsd` above: h = fock + heff, the 4-fold packed
+    fragment ERIs (or None with `df_factor`, the 3-index factor (naux, npair(n)) the fragment then lives on), nsocc and dm0.
+    Returns (e_corr, t2) or (e_corr, t2, rdm1_mo, mo_coeff) with rdm_return; rdm1_mo is PySCF's unrelaxed mp2.make_rdm1."""
+    n = h.shape[0]
+    fr = DeviceFragment(n, n_frag, lib=lib)
+    if eri_s4 is not None:
+        fr.set_eri_s4(eri_s4)
+        if df_factor is not None:
+            fr.set_df_factor(df_factor)
+    elif df_factor is not None:
+        fr.set_df_only(df_factor)
+    else:
+        raise ValueError("solve_mp2 needs the fragment ERIs or their 3-index factor")
+    out = fr.solve_mp2(nsocc, h, dm0, opts=opts, eeval=False, want_t2=True)
+    fr.free()
+    if rdm_return:
+        return out["e_corr_mo"], out["t2"], out["rdm1_mo"], out["mo_coeff"]
+    return out["e_corr_mo"], out["t2"]
+
+
+def fragment_work_bytes(n, o=None, solver="CCSD", naux=None):
     """Device memory ONE fragment in flight takes beside its resident ERIs: the two n^2 x npair buffers of the
     embedding->MO transformation (rows at a stride of whole 128-byte lines), the (+/-) pair-packed ladder operands, the ovvv block with its
-    packed images, and ~30 tensors of the size of t2.  Without n_occ the worst split (n_occ = n / 4) is assumed."""
+    packed images, and ~30 tensors of the size of t2.  Without n_occ the worst split (n_occ = n / 4) is assumed.
+    solver="MP2" (factor route, csrc/mp2.cpp): the unpacked factor and its half-rotated virtual columns while Lov is formed (naux n^2 + naux n v), then
+    Lov, Y and its transpose (naux o v each) and three o^2 v^2 tensors (ovov, t2, G); naux = 3 n when not given."""
+    if solver not in ("CCSD", "MP2"):
+        raise ValueError("Solver not implemented")
     n = int(n)
     o = max(1, n // 4) if o is None else int(o)
     v = max(n - o, 1)
+    if solver == "MP2":
+        naux = 3 * n if naux is None else int(naux)
+        return 8.0 * (max(float(naux) * n * (n + v), 3.0 * (o * v) ** 2 + 2.0 * naux * o * v) + naux * o * v)
     ld = (n + 15) // 16 * 16
     npair = n * (n + 1) // 2
     pv, qv = v * (v + 1) // 2, v * (v - 1) // 2
     return 8.0 * (2.0 * n * ld * npair + pv * pv + qv * qv + 2.0 * o * v ** 3 + 30.0 * (o * v) ** 2)
 
 
-def sweep_mode(frags, nstreams=None, lockstep=None, mem_free=None):
+def sweep_mode(frags, nstreams=None, lockstep=None, mem_free=None, solver="CCSD"):
     """How the fragments of a sweep share the GPU when the caller leaves it open (BE(..., nstreams=None, lockstep=None)):
     many small fragments (>= 4 of at most 64 embedding orbitals: launch bound) advance in lock step -- one grouped launch per
     operation for all of them;
@@ -137,7 +166,7 @@ def sweep_mode(frags, nstreams=None, lockstep=None, mem_free=None):
             if mem_free is None:
                 mem_free = _device_free_bytes(frags)
             if mem_free is not None:
-                work = max(fragment_work_bytes(f.nao, getattr(f, "nsocc", None)) for f in frags)
+                work = max(fragment_work_bytes(f.nao, getattr(f, "nsocc", None), solver=solver) for f in frags)
                 nstreams = max(1, min(nstreams, int(0.9 * mem_free // work)))
     return int(nstreams), bool(lockstep)
 
@@ -236,11 +265,16 @@ def map_fragments(fn, frags, nstreams=1):
 
 
 def solve_fragments(pot, frags, only_chem=False, opts=None, eeval=False, use_cumulant=True, relax_density=False, nstreams=1, lockstep=False,
-                    stats=None):
+                    stats=None, solver="CCSD"):
     """The loop body of be_func (molbe/solver.py:301-547) for the fragments `frags`: update_heff, then the device solve of each.
     nstreams > 1: that many fragments in flight on separate streams (map_fragments).  lockstep: ALL fragments in one library call
     (qemb_frag_solve_batch) -- their CCSD iterations advance together, every operation one grouped launch; the small-fragment regime
-    (octane BE2 / BE3), where a fragment alone is bound by its ~110 dependent launches per iteration.  Same results, bit for bit."""
+    (octane BE2 / BE3), where a fragment alone is bound by its ~110 dependent launches per iteration.  Same results, bit for bit.
+    solver="MP2": the MP2 branch of the loop body (solver.py:313-317); `lockstep` then takes qemb_frag_solve_mp2_batch and relax_density is not read."""
+    if solver not in ("CCSD", "MP2"):
+        raise ValueError("Solver not implemented")
+    if solver == "MP2":
+        relax_density = False
     frags = list(frags)
     if lockstep and len(frags) > 1:
         from .fragsolver import solve_batch
@@ -252,27 +286,27 @@ def solve_fragments(pot, frags, only_chem=False, opts=None, eeval=False, use_cum
             o_list.append(f._solve_inputs(opts, eeval, relax_density))
         # one options struct for the batch: the per-fragment ones differ at most by relax_density, which _solve_inputs set identically
         outs = solve_batch([f.dev for f in frags], [f.nsocc for f in frags], [f.fock + f.heff for f in frags], [f.dm0 for f in frags],
-                           opts=o_list[0], eeval=eeval, stats=stats)
+                           opts=o_list[0], eeval=eeval, stats=stats, solver=solver)
         return [f._solve_outputs(out, eeval, use_cumulant) for f, out in zip(frags, outs)]
 
     def one(fobj):
         if pot is not None:
             fobj.update_heff(pot, only_chem=only_chem)
         assert fobj.fock is not None and fobj.heff is not None
-        return fobj.solve(opts=opts, eeval=eeval, use_cumulant=use_cumulant, relax_density=relax_density)
+        return fobj.solve(opts=opts, eeval=eeval, use_cumulant=use_cumulant, relax_density=relax_density, solver=solver)
     return map_fragments(one, frags, nstreams)
 
 
 def be_func(pot, Fobjs, Nocc, solver, enuc, solver_args=None, scratch_dir=None, only_chem=False, eeval=False,
             relax_density=False, return_vec=False, use_cumulant=True, *, opts=None, stats=None, nstreams=1, lockstep=False):
-    """molbe/solver.py:244-562 for solver == 'CCSD'.  `opts` (qemb_solver_opts), `stats` (dict collecting per-sweep
+    """molbe/solver.py:244-562 for solver == 'CCSD' and solver == 'MP2' (relax_density is ignored for MP2: the reference's MP2 branch never reads it).  `opts` (qemb_solver_opts), `stats` (dict collecting per-sweep
     counters), `nstreams` (fragments in flight at once, see map_fragments) and `lockstep` (all fragments in one batched call, see
     solve_fragments) are additions; everything else has the reference's meaning."""
-    if solver != "CCSD":
+    if solver not in ("CCSD", "MP2"):
         raise ValueError("Solver not implemented")
     total_e = [0.0, 0.0, 0.0]
     n_iter = 0
-    for out in solve_fragments(pot, Fobjs, only_chem, opts, eeval, use_cumulant, relax_density, nstreams, lockstep, stats):
+    for out in solve_fragments(pot, Fobjs, only_chem, opts, eeval, use_cumulant, relax_density, nstreams, lockstep, stats, solver):
         n_iter += out["n_iter"]
         if eeval:
             total_e = [a + b for a, b in zip(total_e, out["e_frag"])]

@@ -28,6 +28,7 @@ extern "C" {
 #define QEMB_ERR_DEVICE (-3)
 #define QEMB_ERR_NOCONV (-4)
 #define QEMB_ERR_NUMERIC (-5)
+#define QEMB_ERR_UNSUPPORTED (-6) /* a well-formed request for something this library does not implement (e.g. a relaxed 2-RDM) */
 #define QEMB_WARN_NOCONV 1       /* only with strict_convergence = 0: results returned, but a solve did not converge */
 
 /* ---------------------------------------------------------------- library / device ------------- */
@@ -162,6 +163,29 @@ int qemb_frag_solve_mp2_batch(int nfrag, const qemb_frag_t* frags, const int* ns
                               const qemb_solver_opts* opts, int eeval, double* const* mo_coeff, double* const* mo_energy,
                               double* const* rdm1_emb, double* const* rdm1_mo, double* const* t2, double* e_frag, double* e_corr_mo,
                               double* e_scf, double* ebe_hf, int* scf_cycles);
+/* The fragment 2-RDM in the fragment-MO basis, Frags.rdm2__ (molbe/solver.py:528): out[n^4] (host, [p][q][r][s]) from what the LAST solve of this fragment
+ * left on the device.  kind names that solve and must agree with it:
+ *   QEMB_RDM2_CCSD  make_rdm2_urlx(t1, t2, with_dm1) of shared/external/ccsd_rdm.py:23-55 (unrelaxed), from the kept t1 / t2 of qemb_frag_solve[_batch];
+ *   QEMB_RDM2_MP2   PySCF's mp2.make_rdm2 (unrelaxed; its ovov block is 2 (2 t2 - t2^T)), or its dovov part alone with with_dm1 = 0.  An MP2 solve keeps no
+ *                   amplitudes: t2 is formed again from the resident orbitals and integrals (one product and one pass, small beside the n^4 tensor).
+ * with_dm1 = 0: the ovov / vovo blocks only (the cumulant-like part get_frag_energy contracts); 1: plus the products of the correlation 1-RDM with the
+ * HF determinant and the HF 2-RDM.  The tensor is assembled by one kernel that writes each of the n^4 elements once; 8 n^4 bytes of device memory are
+ * needed beside the amplitudes (QEMB_ERR_ALLOC, with n in the message, when they are not free).  Relaxed (Lambda) 2-RDMs are not implemented: after a
+ * solve with relax_density the call returns QEMB_ERR_UNSUPPORTED.  Without a preceding solve of that kind, or after new ERIs / another SCF: QEMB_ERR_ARG. */
+#define QEMB_RDM2_CCSD 0
+#define QEMB_RDM2_MP2 1
+int qemb_frag_rdm2(qemb_frag_t f, int kind, int with_dm1, double* out);
+/* The device memory qemb_frag_rdm2 of THIS fragment may take: before anything is allocated the call compares 8 n^4 bytes plus its workspace (the 1-RDM; for MP2 the
+ * three o^2 v^2 tensors and the integral work space of forming t2 again) with min(free device memory, bytes) and fails with QEMB_ERR_ALLOC and n in the message when
+ * it does not fit.  bytes < 0 (default): the free device memory alone. */
+int qemb_frag_rdm2_mem_limit(qemb_frag_t f, int64_t bytes);
+/* The same tensor left ON THE DEVICE in out_dev (n^4 doubles from qemb_malloc): what the full-basis accumulation of BE.rdm12_fullbasis rotates (the guard
+ * then counts the workspace of the call alone). */
+int qemb_frag_rdm2_dev(qemb_frag_t f, int kind, int with_dm1, double* out_dev);
+/* The guard of the full-basis 2-RDM (BE.rdm12_fullbasis, BE.compute_energy_full): need_bytes = the N^4 accumulator plus every workspace the call will
+ * allocate, compared with min(free device memory, limit_bytes) (limit_bytes < 0: the free memory alone) BEFORE anything is allocated.  QEMB_ERR_ALLOC with
+ * N (= nao) in the message when it does not fit. */
+int qemb_rdm2_full_guard(int64_t nao, int64_t need_bytes, int64_t limit_bytes);
 /* number of Lambda iterations of the last qemb_frag_solve with relax_density (0 otherwise) */
 int qemb_frag_lambda_iters(qemb_frag_t f, int* n_iter);
 /* fragment RHF only: get_scfObj(fock + heff, eri, nocc, dm0) of molbe/helper.py:73-151 as used by

@@ -180,6 +180,18 @@ int qemb_op_tri_inverse_lower(int64_t n, const double* L, double* Linv);
  * orbital energies (all on the device) t2[i,j,a,b], G[i,a,j,b] = 2 t2[i,j,a,b] - t2[j,i,a,b] and the energy (host).  Outputs must not alias ovov. */
 int qemb_op_mp2_amplitudes(int64_t o, int64_t v, const double* ovov, const double* eo, const double* ev, double* t2, double* G, double* e_host);
 
+/* The fragment 2-RDM from amplitudes that are handed in (all pointers on the device): kind QEMB_RDM2_CCSD (t1 [o][v], t2 [o][o][v][v]) or QEMB_RDM2_MP2 (t2; t1 is
+ * not read), dm1c = dm1 - 2 I_occ ([n][n]) or NULL for with_dm1 = 0, out [n]^4 with n = o + v.  Every element of out is written once.  Returns after the kernel. */
+int qemb_op_rdm2_assemble(int kind, int64_t o, int64_t v, const double* t1, const double* t2, const double* dm1c, double* out);
+/* The full-basis passes of BE.rdm12_fullbasis / compute_energy_full on [m]^4 tensors (device pointers; molbe/mbe.py:543-620, :781-789):
+ *   rdm2_add_nc:     X[i,j,k,l] += alpha (g[i,j] g[k,l] - g[i,l] g[j,k] / 2), g m x m
+ *   rdm2_symmetrize: X = (X + X^T) / 2 in place with X^T[p,q,r,s] = X[s,r,q,p]; g != NULL: plus the non-connected part of g
+ *   rdm2_eri_dot:    *e_host = sum eri[pqrs] K[pqrs]; eri in the form sym = 1 ([m]^4), 4 ([npair][npair]) or 8 (npair(npair)), unpacked in the kernel;
+ *                    two-stage reduction with a partition fixed by m (the same bits on every run) */
+int qemb_op_rdm2_add_nc(int64_t m, const double* g, double alpha, double* X);
+int qemb_op_rdm2_symmetrize(int64_t m, const double* g, double* X);
+int qemb_op_rdm2_eri_dot(int64_t m, int sym, const double* eri, const double* K, double* e_host);
+
 /* measurement hooks: set up SCF + integrals once, then run/timed single CCSD iterations                */
 int qemb_frag_prepare_ccsd(qemb_frag_t f, int nsocc, const double* h, const double* dm0, const qemb_solver_opts* opts);
 int qemb_frag_ccsd_iterate(qemb_frag_t f, int niter, double* e_corr, double* normt);

@@ -21,7 +21,7 @@ c_i64 = C.c_int64
 c_vp = C.c_void_p
 
 
-QEMB_ERR_ARG, QEMB_ERR_ALLOC, QEMB_ERR_DEVICE, QEMB_ERR_NOCONV, QEMB_ERR_NUMERIC = -1, -2, -3, -4, -5      # include/qemb_hip.h
+QEMB_ERR_ARG, QEMB_ERR_ALLOC, QEMB_ERR_DEVICE, QEMB_ERR_NOCONV, QEMB_ERR_NUMERIC, QEMB_ERR_UNSUPPORTED = -1, -2, -3, -4, -5, -6      # include/qemb_hip.h
 
 
 class QembError(RuntimeError):
@@ -88,6 +88,10 @@ def _declare(lib):
     f("qemb_op_div_denom", I, P, L, L, L, L, P, P, P, P)
     f("qemb_op_dot", I, L, P, P, P)
     f("qemb_op_mp2_amplitudes", I, L, L, P, P, P, P, P, C.POINTER(D))
+    f("qemb_op_rdm2_assemble", I, I, L, L, P, P, P, P)
+    f("qemb_op_rdm2_add_nc", I, L, P, D, P)
+    f("qemb_op_rdm2_symmetrize", I, L, P, P)
+    f("qemb_op_rdm2_eri_dot", I, L, I, P, P, C.POINTER(D))
     f("qemb_op_absmax", I, L, P, P)
     f("qemb_op_gemv_rows", I, L, L, P, L, P, P, D, D)
     f("qemb_op_gemv_rows_batched", I, L, L, L, P, L, L, P, L, P, D, D)
@@ -169,6 +173,10 @@ def _declare(lib):
     f("qemb_frag_solve", I, V, I, P, P, OP, I, P, P, P, P, P, P, P, DP, DP, DP, IP, IP)
     f("qemb_frag_solve_mp2", I, V, I, P, P, OP, I, P, P, P, P, P, P, DP, DP, DP, IP)
     f("qemb_frag_solve_mp2_batch", I, I, P, IP, P, P, OP, I, P, P, P, P, P, P, P, P, P, IP)
+    f("qemb_frag_rdm2", I, V, I, I, P)
+    f("qemb_frag_rdm2_mem_limit", I, V, L)
+    f("qemb_frag_rdm2_dev", I, V, I, I, P)
+    f("qemb_rdm2_full_guard", I, L, L, L)
     f("qemb_frag_lambda_iters", I, P, C.POINTER(C.c_int))
     f("qemb_frag_solve_batch", I, I, P, IP, P, P, OP, I, P, P, P, P, P, P, P, P, P, P, IP, IP, C.POINTER(L))
     f("qemb_frag_scf", I, V, I, P, P, OP, P, P, P, P, DP, IP, IP)

@@ -264,6 +264,21 @@ int qemb_op_mp2_amplitudes(int64_t o, int64_t v, const double* ovov, const doubl
   return e_host ? dev_d2h(e_host, e, sizeof(double)) : dev_sync();
 }
 
+int qemb_op_rdm2_assemble(int kind, int64_t o, int64_t v, const double* t1, const double* t2, const double* dm1c, double* out) {
+  QTRY(dev_rdm2_assemble(kind, o, v, t1, t2, dm1c, out));
+  return dev_sync();
+}
+
+int qemb_op_rdm2_add_nc(int64_t m, const double* g, double alpha, double* X) { return dev_rdm2_add_nc(m, g, alpha, X); }
+int qemb_op_rdm2_symmetrize(int64_t m, const double* g, double* X) { return dev_rdm2_symmetrize(m, g, X); }
+int qemb_op_rdm2_eri_dot(int64_t m, int sym, const double* eri, const double* K, double* e_host) {
+  if (!e_host) { set_error("qemb_op_rdm2_eri_dot: e_host is NULL"); return QEMB_ERR_ARG; }
+  DBuf w;
+  QTRY(w.alloc(rdm2_full_grid(m > 0 ? m : 1) + 1));
+  QTRY(dev_rdm2_eri_dot(m, sym, eri, K, w.p + 1, w.p));
+  return dev_d2h(e_host, w.p, sizeof(double));
+}
+
 // ---------------------------------------------------------------- fragment solver ----------------
 void qemb_default_opts(qemb_solver_opts* o) {
   CcsdOptions c; ScfOptions s;
@@ -428,6 +443,31 @@ int qemb_frag_solve_mp2_batch(int nfrag, const qemb_frag_t* frags, const int* ns
   }
   return rc;
 }
+int qemb_frag_rdm2(qemb_frag_t f, int kind, int with_dm1, double* out) {
+  CHECK_FRAG(f);
+  if (!out) { set_error("qemb_frag_rdm2: out is NULL"); return QEMB_ERR_ARG; }
+  return FRAG(f)->rdm2(kind, with_dm1, out);
+}
+int qemb_frag_rdm2_dev(qemb_frag_t f, int kind, int with_dm1, double* out_dev) {
+  CHECK_FRAG(f);
+  if (!out_dev) { set_error("qemb_frag_rdm2_dev: out_dev is NULL"); return QEMB_ERR_ARG; }
+  return FRAG(f)->rdm2(kind, with_dm1, out_dev, true);
+}
+int qemb_rdm2_full_guard(int64_t nao, int64_t need_bytes, int64_t limit_bytes) {
+  size_t free_b = 0, total_b = 0;
+  QTRY(dev_mem_info(&free_b, &total_b));
+  double room = (double)free_b;
+  if (limit_bytes >= 0 && (double)limit_bytes < room) room = (double)limit_bytes;
+  if (nao <= 0 || need_bytes < 0) { set_error("qemb_rdm2_full_guard: bad arguments"); return QEMB_ERR_ARG; }
+  if ((double)need_bytes > room) {
+    const double n4 = 8e-9 * (double)nao * (double)nao * (double)nao * (double)nao;
+    set_error("full-basis 2-RDM: with N = " + std::to_string(nao) + " the N^4 accumulator takes " + std::to_string(n4) + " GB and the workspace " +
+              std::to_string((double)need_bytes * 1e-9 - n4) + " GB, more than the " + std::to_string(room * 1e-9) + " GB of device memory they may take");
+    return QEMB_ERR_ALLOC;
+  }
+  return QEMB_OK;
+}
+int qemb_frag_rdm2_mem_limit(qemb_frag_t f, int64_t bytes) { CHECK_FRAG(f); FRAG(f)->set_rdm2_mem_limit(bytes); return QEMB_OK; }
 int qemb_frag_lambda_iters(qemb_frag_t f, int* n_iter) { CHECK_FRAG(f); if (n_iter) *n_iter = FRAG(f)->last_lambda_iters; return QEMB_OK; }
 int qemb_frag_scf(qemb_frag_t f, int nsocc, const double* h, const double* dm0, const qemb_solver_opts* opts, double* mo_coeff,
                   double* mo_energy, double* J, double* K, double* e_scf, int* converged, int* cycles) {

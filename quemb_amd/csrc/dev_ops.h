@@ -290,6 +290,35 @@ inline int64_t dev_mp2_partial_count(int64_t o, int64_t v) {
 }
 int dev_mp2_amplitudes(int64_t o, int64_t v, const double* ovov, const double* eo, const double* ev, double* t2, double* G, double* partials, double* e_dev);
 
+// ---- fragment 2-RDM (Fragment::rdm2; kernel in rdm2_ops.hip, scalar restatement for the mock in rdm2_ops_hostcheck.cpp) -----------------------
+// The n^4 tensor ([n]^4, n = o + v, fragment-MO basis) of make_rdm2_urlx (kind QEMB_RDM2_CCSD: t1 [o][v], t2 [o][o][v][v]; shared/external/ccsd_rdm.py:23-55)
+// or of PySCF's mp2.make_rdm2 (kind QEMB_RDM2_MP2: t2 only, t1 is not read), every element written once:
+//   CCSD  out[i,a,j,b] = dovov[i,a,j,b] + dovov[j,b,i,a],  dovov[i,a,j,b] = 2 g[i,j,a,b] - g[j,i,a,b],  g = (t1 (x) t1 + t2) / 2
+//   MP2   out[i,a,j,b] = 2 (2 t2[i,j,a,b] - t2[i,j,b,a])
+//   out[a,i,b,j] = out[i,a,j,b];  zero elsewhere;
+//   dm1c != null (with_dm1; dm1c = dm1 - 2 I_occ, [n][n]): the products of dm1c with the HF determinant and the HF 2-RDM are added (ccsd_rdm.py:40-53).
+// v == 0: the amplitudes are not read (they may be null).  out may not alias an input.
+inline int rdm2_check_args(int kind, int64_t o, int64_t v, const double* t1, const double* t2, const double* out) {
+  if (kind != QEMB_RDM2_CCSD && kind != QEMB_RDM2_MP2) { set_error("dev_rdm2_assemble: kind must be QEMB_RDM2_CCSD or QEMB_RDM2_MP2"); return QEMB_ERR_ARG; }
+  if (o <= 0 || v < 0 || !out || (v > 0 && (!t2 || (kind == QEMB_RDM2_CCSD && !t1)))) { set_error("dev_rdm2_assemble: bad arguments"); return QEMB_ERR_ARG; }
+  if (o + v > 32767) { set_error("dev_rdm2_assemble: n = " + std::to_string(o + v) + " is beyond any n^4 tensor"); return QEMB_ERR_ARG; }
+  return 0;
+}
+int dev_rdm2_assemble(int kind, int64_t o, int64_t v, const double* t1, const double* t2, const double* dm1c, double* out);
+// ---- the full-basis passes of BE.rdm12_fullbasis / compute_energy_full (quemb_amd/rdm_full.py; molbe/mbe.py:543-620, :781-789), tensors [m]^4 -------------------
+//   add_nc:      X[i,j,k,l] += alpha (g[i,j] g[k,l] - g[i,l] g[j,k] / 2)              (the non-connected part; g: m x m)
+//   symmetrize:  X = (X + X^T) / 2 in place, X^T[p,q,r,s] = X[s,r,q,p];  g != null: plus the non-connected part of g (nc_AO)
+//   eri_dot:     out_dev[0] = sum eri[pqrs] K[pqrs], eri in the form `sym` (1: [m]^4, 4: [npair][npair], 8: npair(npair)), unpacked on the fly; two stages with a
+//                partition that depends on m alone (partials: rdm2_full_grid(m) doubles), so the result has the same bits on every run
+inline int64_t rdm2_full_grid(int64_t m) { return m * m < 4096 ? m * m : 4096; }
+inline int rdm2_check_full(int64_t m, const void* a, const void* b) {
+  if (m <= 0 || m > 32767 || !a || !b) { set_error("rdm2 full-basis pass: bad arguments (N = " + std::to_string(m) + ")"); return QEMB_ERR_ARG; }
+  return 0;
+}
+int dev_rdm2_add_nc(int64_t m, const double* g, double alpha, double* X);
+int dev_rdm2_symmetrize(int64_t m, const double* g, double* X);
+int dev_rdm2_eri_dot(int64_t m, int sym, const double* eri, const double* K, double* partials, double* out_dev);
+
 // ---- screening helpers of the semi-sparse DF transform ---------------------------------------------------------------
 // out[i] = (|x[i]| >= eps) ? 1 : 0
 int dev_threshold_mask(int64_t n, const double* x, double eps, double* out);

@@ -43,7 +43,7 @@ int Fragment::adopt_eri_s4(DBuf&& s4) {
   return 0;
 }
 // ---- the fragment's 3-index factor B[naux][npair(n)] (eri = B^T B): set AFTER the ERIs it belongs to (new ERIs drop it)
-void Fragment::clear_df_factor() { df_factor_.release(); df_naux_ = 0; }
+void Fragment::clear_df_factor() { df_factor_.release(); df_naux_ = 0; forget_solve(); }      // (every setter of ERIs or of a factor comes through here or adopts)
 // A factor that does not belong to the resident ERIs would give a fragment RHF (which reads the block) and amplitude equations (which would read the
 // factor) of two different Hamiltonians, silently.  When the factor is set the WHOLE block is probed: for two fixed pseudo-random vectors x the products
 // B^T (B x) and eri_s4 x must agree (two gemv-sized passes; round 4 compared the leading 16 x 16 corner only, which a factor that is stale, truncated or
@@ -108,7 +108,7 @@ int Fragment::set_df_only_dev(int naux, const double* B_dev) {
 }
 int Fragment::adopt_df_only(DBuf&& B, int naux) {
   if (naux <= 0 || !B.p || B.n != (int64_t)naux * npair(n_)) { set_error("adopt_df_only: factor of the wrong size"); return QEMB_ERR_ARG; }
-  eri_s4_.release(); s4_transient_.release();
+  eri_s4_.release(); s4_transient_.release(); forget_solve();
   df_factor_ = std::move(B); df_naux_ = naux;
   return 0;
 }
@@ -183,6 +183,7 @@ void Fragment::set_energy_data(const double* h1, const double* veff0, const doub
 int Fragment::run_scf(int o, const double* h, const double* dm0, const ScfOptions& opt, double* X0, ScfResult* sres, bool warm) {
   const int64_t n2 = (int64_t)n_ * n_;
   o_ = o;
+  forget_solve();      // C_ / eps_ are about to change: rdm2() belongs to the solve that sets last_kind_ after this SCF
   // The orbitals of this fragment's previous solve (any sweep) serve as the basis in which the Jacobi eigensolver starts: the Fock
   // matrix of the new sweep is nearly diagonal there (heff moves by a matching step), so the first diagonalisation needs two sweeps
   // instead of eight.  Only the eigensolver's starting point changes -- the SCF still starts from dm0 -- so this does not depend on
@@ -774,6 +775,7 @@ int Fragment::solve_end(double* mo_coeff, double* mo_energy, double* rdm1_emb, d
   // multipliers and orbitals must be complete before this call returns (no inter-stream ordering exists otherwise)
   QTRY(dev_sync());
   retire_solver();
+  last_kind_ = QEMB_RDM2_CCSD; last_o_ = o; last_relaxed_ = opt.relax_density != 0;
   return unconverged ? QEMB_WARN_NOCONV : 0;
 }
 
@@ -829,7 +831,82 @@ int Fragment::solve_mp2(int o, const double* h, const double* dm0, const Fragmen
   if (mo_energy) std::memcpy(mo_energy, sp_.eps.data(), sizeof(double) * n);
   if (eeval) QTRY(frag_energies(o, C, rdm, hfdm, Z1, Z2, nullptr, res));
   QTRY(dev_sync());      // (the next sweep may drive this fragment from another execution context, as after solve_end)
+  mp2_dm1_ = std::move(dm); last_kind_ = QEMB_RDM2_MP2; last_o_ = o; last_relaxed_ = false;
   return sp_.unconverged ? QEMB_WARN_NOCONV : 0;
+}
+
+// ---- Frags.rdm2__ (molbe/solver.py:528): the n^4 tensor of the last solve, written once by one kernel (rdm2_ops.hip)
+// Device bytes of one call: the tensor, the 1-RDM, and for MP2 what forming t2 again takes -- ovov, t2, G and the larger of the two integral routes' work space
+// (factor: the unpacked factor, its half-rotated virtual columns and Lov, mp2.cpp; block: the two buffers of mo_transform and the ovov block it leaves).
+int64_t Fragment::rdm2_bytes(int kind, int o, int with_dm1) const {
+  const int64_t n = n_, v = n - o, n2 = n * n, ov2 = (int64_t)o * v * o * v;
+  int64_t words = n2 * n2 + (with_dm1 ? n2 : 0);
+  if (kind == QEMB_RDM2_MP2 && v > 0) {
+    const int64_t factor = (int64_t)df_naux_ * (n2 + n * v + (int64_t)o * v), block = 2 * mo_transform_work(n_) + ov2;
+    words += 3 * ov2 + (use_factor_route() ? factor : block);
+  }
+  return 8 * words;
+}
+int Fragment::rdm2(int kind, int with_dm1, double* out, bool out_on_device) {
+  if (kind != QEMB_RDM2_CCSD && kind != QEMB_RDM2_MP2) { set_error("Fragment::rdm2: kind must be QEMB_RDM2_CCSD or QEMB_RDM2_MP2"); return QEMB_ERR_ARG; }
+  if (last_kind_ < 0) { set_error("Fragment::rdm2: no solve has run on this fragment since its ERIs or orbitals were last set"); return QEMB_ERR_ARG; }
+  if (kind != last_kind_) { set_error(std::string("Fragment::rdm2: the last solve of this fragment was ") + (last_kind_ == QEMB_RDM2_MP2 ? "MP2" : "CCSD") + ", not the kind asked for"); return QEMB_ERR_ARG; }
+  if (last_relaxed_) { set_error("Fragment::rdm2: relaxed (Lambda) 2-RDMs are not implemented; solve without relax_density"); return QEMB_ERR_UNSUPPORTED; }
+  const int n = n_, o = last_o_, v = n - o;
+  const int64_t n2 = (int64_t)n * n;
+  // ---- the guard: tensor + workspace against what is free (or the fragment's limit), before anything is allocated
+  size_t free_b = 0, total_b = 0;
+  QTRY(dev_mem_info(&free_b, &total_b));
+  double room = (double)free_b;
+  if (rdm2_mem_limit_ >= 0 && (double)rdm2_mem_limit_ < room) room = (double)rdm2_mem_limit_;
+  const int64_t need = rdm2_bytes(kind, o, with_dm1) - (out_on_device ? 8 * n2 * n2 : 0);
+  if ((double)need > room) {
+    set_error("Fragment::rdm2: the 2-RDM of a fragment with n = " + std::to_string(n) + " takes " + std::to_string((double)n2 * (double)n2 * 8e-9) + " GB and " +
+              std::to_string((double)(rdm2_bytes(kind, o, with_dm1) - 8 * n2 * n2) * 1e-9) + " GB of workspace, more than the " + std::to_string(room * 1e-9) + " GB of device memory it may take");
+    return QEMB_ERR_ALLOC;
+  }
+  const double *t1d = nullptr, *t2d = nullptr;
+  Mp2Solver mp;      // (lives until the kernel has run)
+  if (v > 0 && kind == QEMB_RDM2_CCSD) {
+    if (!t_prev_.p || t_prev_o_ != o) { set_error("Fragment::rdm2: the amplitudes of the last CCSD solve were not kept"); return QEMB_ERR_ARG; }
+    t1d = t_prev_.p; t2d = t_prev_.p + (int64_t)o * v;
+  } else if (v > 0) {
+    const bool route = last_route_factor_;      // (mo_route_used keeps describing the solve)
+    int rc;
+    if (use_factor_route()) {
+      rc = mp.run_factor(n, o, 0, df_naux_, df_factor_, C_, eps_);
+    } else {
+      DBuf X1; bool unpacked = false; MoIntegrals ints;
+      rc = scf_operand(X1, &unpacked);
+      if (rc == 0) rc = mo_integrals(o, 0, X1, unpacked, ints, false, false);
+      X1.release();
+      if (rc == 0) rc = mp.run_blocks(std::move(ints), eps_);
+    }
+    last_route_factor_ = route;
+    if (rc) return rc;
+    t2d = mp.t2();
+  }
+  DBuf D, R;
+  if (with_dm1) {      // dm1 - 2 I_occ: [[0, t1], [t1^T, 0]] after CCSD (ccsd_rdm.py:10-20), the oo / vv blocks of mp2.make_rdm1 after MP2
+    std::vector<double> d((size_t)n2, 0.0);
+    if (kind == QEMB_RDM2_MP2) {
+      d = mp2_dm1_;
+      for (int i = 0; i < o; ++i) d[(size_t)i * n + i] -= 2.0;
+    } else if (v > 0) {
+      std::vector<double> t1((size_t)o * v);
+      QTRY(dev_d2h(t1.data(), t1d, sizeof(double) * o * v));
+      for (int i = 0; i < o; ++i) for (int a = 0; a < v; ++a) d[(size_t)i * n + o + a] = d[(size_t)(o + a) * n + i] = t1[(size_t)i * v + a];
+    }
+    QTRY(D.alloc(n2));
+    QTRY(dev_h2d(D, d.data(), sizeof(double) * n2));
+  }
+  if (out_on_device) {
+    QTRY(dev_rdm2_assemble(kind, o, v, t1d, t2d, with_dm1 ? D.p : nullptr, out));
+    return dev_sync();      // (t2 of an MP2 call and D go back to the pool on return)
+  }
+  QTRY(R.alloc(n2 * n2));
+  QTRY(dev_rdm2_assemble(kind, o, v, t1d, t2d, with_dm1 ? D.p : nullptr, R));
+  return dev_d2h(out, R, sizeof(double) * n2 * n2);
 }
 
 int Fragment::solve_mp2_batch(const std::vector<Fragment*>& frs, const std::vector<int>& o, const std::vector<const double*>& h, const std::vector<const double*>& dm0,

@@ -91,6 +91,14 @@ class Fragment {
   // ... for every fragment of a sweep, spread over the execution contexts that exist (MP2 has no iterations to run in lock step).  Results as from solve_mp2(), bit for bit.
   static int solve_mp2_batch(const std::vector<Fragment*>& frs, const std::vector<int>& o, const std::vector<const double*>& h, const std::vector<const double*>& dm0,
                              const FragmentOptions& opt, int eeval, std::vector<FragmentResult>& res, const std::vector<BatchOutputs>& outs);
+  // Frags.rdm2__ (molbe/solver.py:528) of the last solve in the fragment-MO basis, out: n^4 (host).  kind QEMB_RDM2_CCSD: make_rdm2_urlx from the kept t1 / t2;
+  // QEMB_RDM2_MP2: mp2.make_rdm2, t2 formed again from the resident orbitals (an MP2 solve keeps no amplitudes).  One kernel writes the tensor (rdm2_ops.hip).
+  // A relaxed solve: QEMB_ERR_UNSUPPORTED; no solve of that kind, or ERIs / orbitals changed since: QEMB_ERR_ARG.
+  // out_on_device: out is an n^4 device buffer of the caller (the full-basis accumulation); the guard then counts the workspace alone
+  int rdm2(int kind, int with_dm1, double* out, bool out_on_device = false);
+  // device bytes rdm2() may take (tensor + workspace); < 0: whatever is free
+  void set_rdm2_mem_limit(int64_t bytes) { rdm2_mem_limit_ = bytes; }
+  int64_t rdm2_bytes(int kind, int o, int with_dm1) const;      // 8 n^4 + the workspace of the call
   // Bench hooks: set up the CCSD problem once (SCF + transform), then time single iterations.
   int prepare_ccsd(int o, const double* h, const double* dm0, const FragmentOptions& opt);
   int ccsd_iterate(int niter, double* e_corr, double* normt);
@@ -149,6 +157,12 @@ class Fragment {
   DBuf z_prev_;   // warm-start Lambda multipliers (relax_density)
   int z_prev_o_ = -1;
   int t_prev_o_ = -1;
+  // what rdm2() needs of the last solve: its kind (-1: none, or the orbitals / ERIs changed since), whether it was relaxed, nsocc; after an MP2 solve the
+  // 1-RDM (host, n x n): it keeps no amplitudes to form it from (CCSD: [[2 I, t1], [t1^T, 0]] from the kept t1 when asked)
+  int last_kind_ = -1, last_o_ = 0; bool last_relaxed_ = false;
+  std::vector<double> mp2_dm1_;
+  int64_t rdm2_mem_limit_ = -1;
+  void forget_solve() { last_kind_ = -1; }
 };
 
 // lock-step tapes kept from an earlier solve / recorded anew since the last reset (all fragments of the process)

@@ -152,6 +152,27 @@ class DeviceFragment:
         out.update(e_frag=e_frag, e_corr_mo=ecorr.value, e_scf=escf.value, ebe_hf=ebehf.value, n_iter=0, scf_cycles=ncyc.value, lambda_iters=0)
         return out
 
+    def make_rdm2(self, kind="CCSD", with_dm1=True):
+        """Frags.rdm2__ (molbe/solver.py:528) of the last solve of this fragment in the fragment-MO basis, (n, n, n, n): qemb_frag_rdm2.
+        kind="CCSD": make_rdm2_urlx(t1, t2, with_dm1) (shared/external/ccsd_rdm.py:23-55) from the amplitudes `solve` left on the device;
+        kind="MP2": PySCF's mp2.make_rdm2 (with_dm1=False: its dovov part) after `solve_mp2`.  One kernel writes the n^4 tensor on the device.
+        Relaxed (Lambda) 2-RDMs are not implemented: after a solve with relax_density this raises NotImplementedError."""
+        if kind not in RDM2_KINDS:
+            raise ValueError("Solver not implemented")
+        n = self.n
+        out = np.empty((n, n, n, n))
+        try:
+            check(self.lib.qemb_frag_rdm2(self.h, RDM2_KINDS[kind], int(bool(with_dm1)), out.ctypes.data), "qemb_frag_rdm2", self.lib)
+        except _lib.QembError as e:
+            if e.status == _lib.QEMB_ERR_UNSUPPORTED:
+                raise NotImplementedError(str(e)) from None
+            raise
+        return out
+
+    def set_rdm2_mem_limit(self, nbytes):
+        """device bytes `make_rdm2` of this fragment may take, tensor and workspace (qemb_frag_rdm2_mem_limit); negative: whatever is free"""
+        check(self.lib.qemb_frag_rdm2_mem_limit(self.h, int(nbytes)), "qemb_frag_rdm2_mem_limit", self.lib)
+
     def scf(self, nsocc, h, dm0=None, opts=None):
         """Fragment RHF only (Frags.scf(fs=True)); returns dict(mo_coeff, mo_energy, J, K, e_scf, converged, cycles)."""
         n = self.n
@@ -206,6 +227,45 @@ class DeviceFragment:
             self.free()
         except Exception:
             pass
+
+
+RDM2_KINDS = {"CCSD": 0, "MP2": 1}      # QEMB_RDM2_CCSD, QEMB_RDM2_MP2 (include/qemb_hip.h)
+
+
+def rdm2_from_amplitudes(t1, t2, dm1=None, kind="CCSD", lib=None):
+    """The fragment 2-RDM from amplitudes that are handed in (qemb_op_rdm2_assemble, the kernel behind DeviceFragment.make_rdm2): t1 (o, v) -- None for
+    kind="MP2" --, t2 (o, o, v, v); dm1 (n, n): the 1-RDM whose products with the HF determinant are added (with_dm1=True of the reference; for CCSD
+    make_rdm1_ccsd_t1(t1)), None for with_dm1=False.  Returns (n, n, n, n)."""
+    from ._lib import DeviceBuffer
+    if kind not in RDM2_KINDS:
+        raise ValueError("Solver not implemented")
+    lib = lib or _lib.init()
+    t2 = np.ascontiguousarray(t2, dtype=np.float64)
+    o, v = t2.shape[0], t2.shape[2]
+    n = o + v
+    if t2.shape != (o, o, v, v) or (kind == "CCSD" and (t1 is None or np.shape(t1) != (o, v))):
+        raise ValueError("rdm2_from_amplitudes: t1 must be (o, v) and t2 (o, o, v, v)")
+    bufs = []
+    def dev(a):
+        bufs.append(DeviceBuffer.from_numpy(a, lib=lib))
+        return bufs[-1].ptr
+    p_t1 = dev(t1) if kind == "CCSD" and v > 0 else None
+    p_t2 = dev(t2) if v > 0 else None
+    p_d = None
+    if dm1 is not None:
+        d = np.array(dm1, dtype=np.float64)
+        if d.shape != (n, n):
+            raise ValueError(f"rdm2_from_amplitudes: dm1 must be ({n}, {n})")
+        d[np.diag_indices(o)] -= 2.0
+        p_d = dev(d)
+    out = DeviceBuffer(n ** 4, lib=lib)
+    bufs.append(out)
+    try:
+        check(lib.qemb_op_rdm2_assemble(RDM2_KINDS[kind], o, v, p_t1, p_t2, p_d, out.ptr), "qemb_op_rdm2_assemble", lib)
+        return out.numpy((n, n, n, n))
+    finally:
+        for b in bufs:
+            b.free()
 
 
 def solve_batch(frags, nsoccs, hs, dm0s=None, opts: SolverOpts | None = None, eeval=True, want_t2=False, stats=None, solver="CCSD"):

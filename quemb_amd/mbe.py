@@ -54,6 +54,7 @@ class BE:
         self.nstreams = None if nstreams is None else int(nstreams)
         self.lockstep = None if lockstep is None else bool(lockstep)
         self.unrestricted = False
+        self.rdm2_mem_limit = None      # device bytes the full-basis 2-RDM may take (rdm12_fullbasis / compute_energy_full); None: whatever is free
         self.ebe_hf = 0.0
         self.ebe_tot = 0.0
         self.mo_energy = mf.mo_energy
@@ -250,6 +251,182 @@ class BE:
         rdm1LO = self.W.T @ self.S @ rdm1AO @ self.S @ self.W if return_lo else None
         out = rdm1AO if return_ao else self.C.T @ self.S @ rdm1AO @ self.S @ self.C
         return (out, rdm1LO) if return_lo else out
+
+    # ------------------------------------------------------------------ full-basis 2-RDM and energies (mbe.py:488-838)
+    def _rdm2_full_device(self, rdm1AO, return_RDM2, transform=False, eri_words=0):
+        """the symmetrised full-basis two-particle tensor as a device buffer ([N]^4): every owned fragment's centre-projected tensor accumulated on the
+        device (rdm_full.accumulate), summed over the ranks, symmetrised, plus nc_AO of `rdm1AO` (the 1-RDM as accumulated, not yet symmetrised) when return_RDM2 (mbe.py:543-620)"""
+        from . import rdm_full, _lib
+        from ._lib import DeviceBuffer
+        lib = self.lib or _lib.init()
+        nao = self.C.shape[0]
+        frags = [self.Fobjs[I] for I in self.my_frags]
+        for f in frags:
+            if f.rdm1__ is None:
+                raise RuntimeError("rdm12_fullbasis: run oneshot() or optimize() first")
+        rdm_full.guard(lib, nao, frags, transform, eri_words, getattr(self, "rdm2_mem_limit", None))
+        acc = DeviceBuffer.from_numpy(np.zeros(nao ** 4), lib=lib)
+        try:
+            rdm_full.accumulate(lib, acc, nao, self.S, self.W, frags, return_RDM2)
+            if self.world > 1:
+                host = acc.numpy()
+                all_reduce_sum(host)
+                acc.upload(host)
+            rdm_full.symmetrize(lib, acc, nao, rdm1AO if return_RDM2 else None)
+        except BaseException:
+            acc.free()
+            raise
+        return acc
+
+    def _rdm1_full_accumulated(self):
+        """the full-basis 1-RDM as the fragment loop leaves it (mbe.py:571-577), before its symmetrisation (:650): what nc_AO reads (:603-619)"""
+        nao = self.C.shape[0]
+        raw = np.zeros((nao, nao))
+        for I in self.my_frags:
+            f = self.Fobjs[I]
+            cind = [f.AO_in_frag[i] for i in f.weight_and_relAO_per_center[1]]
+            SW = self.S @ self.W[:, cind]
+            raw += f.TA @ ((f.TA.T @ SW @ SW.T @ f.TA) @ (f.mo_coeffs @ f.rdm1__ @ f.mo_coeffs.T)) @ f.TA.T
+        if self.world > 1:
+            all_reduce_sum(raw)
+        return raw
+
+    def _eri_words(self):
+        e = getattr(self.mf, "_eri", None)
+        if e is None:
+            raise ValueError("ERIs have to be available in memory.")
+        return int(np.size(e))
+
+    def rdm12_fullbasis(self, return_ao=True, only_rdm2=False, return_lo=False, return_RDM2=True, print_energy=False):
+        """The one- and two-particle density matrices of the whole system, the reference's `rdm1_fullbasis(only_rdm1=False)` (mbe.py:488-701) with its return
+        conventions: (rdm1, rdm2) in the AO (return_ao) or MO basis, with (rdm1LO, rdm2LO) appended when return_lo, the two-particle tensor alone when only_rdm2.
+        return_RDM2=True: the 2-RDM (the fragments' non-connected parts subtracted, nc_AO of the full 1-RDM added); False: the cumulant as the fragments hold it.
+        The fragment tensors are those of the last sweep (unrelaxed; with_dm1=False, as solver.py:941 leaves rdm2__ with use_cumulant); they are assembled,
+        rotated, projected and accumulated on the device (rdm_full.py, csrc/rdm2_ops.hip).  The 1-RDM is always formed: nc_AO needs it (the reference leaves it
+        undefined under only_rdm2, mbe.py:538-539 / :603-607)."""
+        from . import rdm_full, _lib
+        lib = self.lib or _lib.init()
+        nao = self.C.shape[0]
+        if any(self.Fobjs[I].rdm1__ is None for I in self.my_frags):
+            raise RuntimeError("rdm12_fullbasis: run oneshot() or optimize() first")
+        raw = self._rdm1_full_accumulated()
+        rdm1AO = (raw + raw.T) / 2.0
+        want_energy = return_RDM2 and print_energy
+        acc = self._rdm2_full_device(raw, return_RDM2, transform=return_lo or not return_ao, eri_words=self._eri_words() if want_energy else 0)
+        try:
+            rdm2AO = acc.numpy((nao,) * 4)
+            CmoT_S, CloT_S = self.C.T @ self.S, self.W.T @ self.S
+            rdm2MO = rdm_full.reexpress(lib, acc, nao, CmoT_S) if not return_ao else None
+            rdm2LO = rdm_full.reexpress(lib, acc, nao, CloT_S) if return_lo else None
+            if want_energy:
+                ao = rdm_full.AOIntegrals(lib, self.mf._eri, nao)
+                try:
+                    E2 = 0.5 * ao.dot(acc)
+                finally:
+                    ao.free()
+        finally:
+            acc.free()
+        rdm1MO = CmoT_S @ rdm1AO @ CmoT_S.T if not return_ao else None
+        rdm1LO = CloT_S @ rdm1AO @ CloT_S.T if return_lo else None
+        if want_energy and self.rank == 0:
+            Eh1 = float(np.einsum("ij,ij", self.hcore, rdm1AO))
+            E_tot = Eh1 + E2 + self.E_core + self.enuc
+            print(flush=True)
+            print("-----------------------------------------------------", flush=True)
+            print(" BE ENERGIES with cumulant-based expression", flush=True)
+            print("-----------------------------------------------------", flush=True)
+            print(f" 1-elec E        : {Eh1:>15.8f} Ha", flush=True)
+            print(f" 2-elec E        : {E2:>15.8f} Ha", flush=True)
+            print(f" E_BE            : {E_tot:>15.8f} Ha", flush=True)
+            print(f" Ecorr BE        : {(E_tot) - self.ebe_hf:>15.8f} Ha", flush=True)
+            print("-----------------------------------------------------", flush=True)
+            print(flush=True)
+        r1, r2 = (rdm1AO, rdm2AO) if return_ao else (rdm1MO, rdm2MO)
+        if only_rdm2:
+            return r2
+        if return_lo:
+            return (r1, r2, rdm1LO, rdm2LO)
+        return r1, r2
+
+    def compute_energy_full(self, approx_cumulant=False, use_full_rdm=False, return_rdm=True):
+        """mbe.py:703-838: the BE energy from full-basis densities, E_HF + Tr(F del g) + Tr(V K_approx) / 2 and (approx_cumulant=False)
+        Tr(h g) + Tr(V_eff[g] g) / 2 + Tr(V K_true) / 2; sets `ebe_tot`, prints the reference's table, returns (rdm1, RDM2_full) when return_rdm.  K_approx is
+        rdm12_fullbasis(return_RDM2=False), K_true rdm12_fullbasis(only_rdm2=True).  The N^4 tensors stay on the device: the contractions with the AO
+        integrals read `mf._eri` in its packed form (rdm2_ops.hip, a two-stage reduction in a fixed order).  The energies are kept in `self.e_full`."""
+        from . import rdm_full, _lib
+        from ._lib import DeviceBuffer, check
+        lib = self.lib or _lib.init()
+        nao = self.C.shape[0]
+        if any(self.Fobjs[I].rdm1__ is None for I in self.my_frags):
+            raise RuntimeError("compute_energy_full: run oneshot() or optimize() first")
+        raw = self._rdm1_full_accumulated()
+        rdm1f = (raw + raw.T) / 2.0
+        words = self._eri_words() + (0 if approx_cumulant else nao ** 4)
+        K = self._rdm2_full_device(rdm1f, False, eri_words=words)
+        KT = ao = None
+        RDM2_full = E2 = EKumul_T = None
+        try:
+            ao = rdm_full.AOIntegrals(lib, self.mf._eri, nao)
+            EKumul = ao.dot(K)
+            if not approx_cumulant:
+                KT = self._rdm2_full_device(raw, True, eri_words=words)
+                EKumul_T = ao.dot(KT)
+            if return_rdm:
+                # RDM2_full = nc(rdm1f) + the cumulant (mbe.py:745-757), formed in place on the device
+                full = K if approx_cumulant else KT
+                g = DeviceBuffer.from_numpy(rdm1f, lib=lib)
+                try:
+                    check(lib.qemb_op_rdm2_add_nc(nao, g.ptr, 1.0, full.ptr), "qemb_op_rdm2_add_nc", lib)
+                finally:
+                    g.free()
+                if use_full_rdm:
+                    E2 = ao.dot(full)
+                RDM2_full = full.numpy((nao,) * 4)
+        finally:
+            for b in (K, KT, ao):
+                if b is not None:
+                    b.free()
+        del_gamma = rdm1f - self.hf_dm
+        veff = np.asarray(self.mf.get_veff(dm=rdm1f))
+        Eh1 = float(np.einsum("ij,ij", self.hcore, rdm1f))
+        EVeff = float(np.einsum("ij,ij", veff, rdm1f))
+        Eh1_dg = float(np.einsum("ij,ij", self.hcore, del_gamma))
+        Eveff_dg = float(np.einsum("ij,ij", self.hf_veff, del_gamma))
+        EKapprox = self.ebe_hf + Eh1_dg + Eveff_dg + EKumul / 2.0
+        self.ebe_tot = EKapprox
+        self.e_full = dict(EKapprox=EKapprox, EKumul=EKumul, Eh1_dg=Eh1_dg, Eveff_dg=Eveff_dg, Eh1=Eh1, EVeff=EVeff)
+        if not approx_cumulant:
+            EKtrue = Eh1 + EVeff / 2.0 + EKumul_T / 2.0 + self.enuc + self.E_core
+            self.ebe_tot = EKtrue
+            self.e_full.update(EKtrue=EKtrue, EKumul_T=EKumul_T)
+        if E2 is not None:
+            self.e_full["E2"] = E2
+        if self.rank == 0:
+            print("-----------------------------------------------------", flush=True)
+            print(" BE ENERGIES with cumulant-based expression", flush=True)
+            print("-----------------------------------------------------", flush=True)
+            print(" E_BE = E_HF + Tr(F del g) + Tr(V K_approx)", flush=True)
+            print(f" E_HF            : {self.ebe_hf:>14.8f} Ha", flush=True)
+            print(f" Tr(F del g)     : {Eh1_dg + Eveff_dg:>14.8f} Ha", flush=True)
+            print(f" Tr(V K_aprrox)  : {EKumul / 2.0:>14.8f} Ha", flush=True)
+            print(f" E_BE            : {EKapprox:>14.8f} Ha", flush=True)
+            print(f" Ecorr BE        : {EKapprox - self.ebe_hf:>14.8f} Ha", flush=True)
+            if not approx_cumulant:
+                print(flush=True)
+                print(" E_BE = Tr(F[g] g) + Tr(V K_true)", flush=True)
+                print(f" Tr(h1 g)        : {Eh1:>14.8f} Ha", flush=True)
+                print(f" Tr(Veff[g] g)   : {EVeff / 2.0:>14.8f} Ha", flush=True)
+                print(f" Tr(V K_true)    : {EKumul_T / 2.0:>14.8f} Ha", flush=True)
+                print(f" E_BE            : {EKtrue:>14.8f} Ha", flush=True)
+                if E2 is not None:
+                    print(" E(g+G)          : {:>14.8f} Ha".format(Eh1 + 0.5 * E2 + self.E_core + self.enuc), flush=True)
+                print(f" Ecorr BE        : {EKtrue - self.ebe_hf:>14.8f} Ha", flush=True)
+                print(flush=True)
+                print(f" True - approx   : {EKtrue - EKapprox:>14.4e} Ha")
+            print("-----------------------------------------------------", flush=True)
+            print(flush=True)
+        if return_rdm:
+            return (rdm1f, RDM2_full)
 
     def compute_numerical_jacobian(self, solver="CCSD", only_chem=False, nproc=1, step_size=1e-6):
         from .numerical_jac import compute_numerical_jacobian

@@ -62,6 +62,7 @@ class Frags:
         self.dm0 = None
         self.unitcell_nkpt = 1.0
         self._hf_jk = None
+        self._solver = None      # the solver of the last solve ("CCSD" / "MP2"): what make_rdm2 assembles
 
     # ------------------------------------------------------------------ Schmidt (pfrag.py:146-180)
     def sd(self, lao, lmo, nocc, thr_bath, norb=None, method="eigh"):
@@ -173,10 +174,19 @@ class Frags:
         if solver == "MP2":
             opts = self._solve_inputs(opts, eeval, False)
             out = self.dev.solve_mp2(self.nsocc, self.fock + self.heff, self.dm0, opts=opts, eeval=eeval, want_t2=want_t2)
-            return self._solve_outputs(out, eeval, use_cumulant)
+            return self._solve_outputs(out, eeval, use_cumulant, solver)
         opts = self._solve_inputs(opts, eeval, relax_density)
         out = self.dev.solve(self.nsocc, self.fock + self.heff, self.dm0, opts=opts, eeval=eeval, want_t2=want_t2)
-        return self._solve_outputs(out, eeval, use_cumulant)
+        return self._solve_outputs(out, eeval, use_cumulant, solver)
+
+    def make_rdm2(self, with_dm1=True):
+        """fills `rdm2__` (molbe/solver.py:528) from the last solve of this fragment, in the fragment-MO basis: make_rdm2_urlx(t1, t2, with_dm1) after a
+        CCSD solve, mp2.make_rdm2 after an MP2 solve; assembled on the device (DeviceFragment.make_rdm2).  Unrelaxed only: after a solve with
+        relax_density this raises NotImplementedError."""
+        if self._solver is None:
+            raise RuntimeError("make_rdm2: solve the fragment first")
+        self.rdm2__ = self.dev.make_rdm2(self._solver, with_dm1)
+        return self.rdm2__
 
     def _solve_inputs(self, opts, eeval, relax_density):
         """what has to be on the device before the solve call (shared with the lock-step sweep, solver.solve_fragments)"""
@@ -190,12 +200,14 @@ class Frags:
             self.dev.set_energy_data(self.h1, self.veff0, self.veff, w, cen)
         return opts
 
-    def _solve_outputs(self, out, eeval, use_cumulant):
+    def _solve_outputs(self, out, eeval, use_cumulant, solver):
         """what solver.py:493-505 sets on the fragment object"""
         self.mo_coeffs = out["mo_coeff"]
         self.mo_energy = out["mo_energy"]
         self.t1 = out["t1"]
         self.t2 = out["t2"]
+        self._solver = solver
+        self.rdm2__ = None
         self.rdm1__ = out["rdm1_mo"]
         self._rdm1 = out["rdm1_emb"]
         if eeval and not use_cumulant:

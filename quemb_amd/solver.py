@@ -86,42 +86,52 @@ def solve_ccsd(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_r
     """Device counterpart of solve_ccsd (molbe/solver.py:829-946).  The reference takes a PySCF mean-field object;
     here the fragment RHF is part of the device call, so the inputs are what `get_scfObj` would have been given:
     h = fock + heff, the 4-fold packed fragment ERIs, nsocc and dm0.
-    Returns (t1, t2) or (t1, t2, rdm1_mo, mo_coeff) with rdm_return.  The dense 2-RDM is never formed on the device
-    (rdm2_return raises): its only consumer, get_frag_energy, is evaluated in contracted form by `Frags.solve`."""
+    Returns (t1, t2) or (t1, t2, rdm1_mo, mo_coeff) with rdm_return.  rdm2_return: the fragment 2-RDM in the MO basis,
+    make_rdm2_urlx(t1, t2, with_dm1=not use_cumulant), assembled on the device, takes the place of mo_coeff -- (t1, t2, rdm1_mo, rdm2) as
+    solver.py:940-942 -- or is appended to (t1, t2) without rdm_return.  Unrelaxed only: with relax it raises NotImplementedError.  The energies of a sweep never need it: `Frags.solve` contracts it in place."""
     if relax:
         opts = SolverOpts.from_buffer_copy(opts) if opts is not None else default_opts(lib)
         opts.relax_density = 1
-    if rdm2_return:
-        raise NotImplementedError("the n^4 2-RDM is not materialised; use Frags.solve(eeval=True) for energies")
     n = h.shape[0]
     fr = DeviceFragment(n, n_frag, lib=lib)
-    fr.set_eri_s4(eri_s4)
-    out = fr.solve(nsocc, h, dm0, opts=opts, eeval=False, want_t2=True)
-    fr.free()
+    try:
+        fr.set_eri_s4(eri_s4)
+        out = fr.solve(nsocc, h, dm0, opts=opts, eeval=False, want_t2=True)
+        rdm2 = fr.make_rdm2("CCSD", with_dm1=not use_cumulant) if rdm2_return else None
+    finally:
+        fr.free()
+    if rdm_return and rdm2_return:
+        return out["t1"], out["t2"], out["rdm1_mo"], rdm2          # solver.py:942
     if rdm_return:
         return out["t1"], out["t2"], out["rdm1_mo"], out["mo_coeff"]
-    return out["t1"], out["t2"]
+    return (out["t1"], out["t2"], rdm2) if rdm2_return else (out["t1"], out["t2"])
 
 
-def solve_mp2(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, df_factor=None, opts=None, lib=None):
+def solve_mp2(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, use_cumulant=True, df_factor=None, opts=None, lib=None):
     """Device counterpart of solve_mp2 (molbe/solver.py:781-826) with the inputs of `solve_ccsd` above: h = fock + heff, the 4-fold packed
     fragment ERIs (or None with `df_factor`, the 3-index factor (naux, npair(n)) the fragment then lives on), nsocc and dm0.
-    Returns (e_corr, t2) or (e_corr, t2, rdm1_mo, mo_coeff) with rdm_return; rdm1_mo is PySCF's unrelaxed mp2.make_rdm1."""
+    Returns (e_corr, t2) or (e_corr, t2, rdm1_mo, mo_coeff) with rdm_return; rdm1_mo is PySCF's unrelaxed mp2.make_rdm1.  rdm2_return: the
+    fragment 2-RDM in the MO basis (mp2.make_rdm2, or its dovov part alone with use_cumulant) in the place `solve_ccsd` gives it."""
     n = h.shape[0]
     fr = DeviceFragment(n, n_frag, lib=lib)
-    if eri_s4 is not None:
-        fr.set_eri_s4(eri_s4)
-        if df_factor is not None:
-            fr.set_df_factor(df_factor)
-    elif df_factor is not None:
-        fr.set_df_only(df_factor)
-    else:
-        raise ValueError("solve_mp2 needs the fragment ERIs or their 3-index factor")
-    out = fr.solve_mp2(nsocc, h, dm0, opts=opts, eeval=False, want_t2=True)
-    fr.free()
+    try:
+        if eri_s4 is not None:
+            fr.set_eri_s4(eri_s4)
+            if df_factor is not None:
+                fr.set_df_factor(df_factor)
+        elif df_factor is not None:
+            fr.set_df_only(df_factor)
+        else:
+            raise ValueError("solve_mp2 needs the fragment ERIs or their 3-index factor")
+        out = fr.solve_mp2(nsocc, h, dm0, opts=opts, eeval=False, want_t2=True)
+        rdm2 = fr.make_rdm2("MP2", with_dm1=not use_cumulant) if rdm2_return else None
+    finally:
+        fr.free()
+    if rdm_return and rdm2_return:
+        return out["e_corr_mo"], out["t2"], out["rdm1_mo"], rdm2
     if rdm_return:
         return out["e_corr_mo"], out["t2"], out["rdm1_mo"], out["mo_coeff"]
-    return out["e_corr_mo"], out["t2"]
+    return (out["e_corr_mo"], out["t2"], rdm2) if rdm2_return else (out["e_corr_mo"], out["t2"])
 
 
 def fragment_work_bytes(n, o=None, solver="CCSD", naux=None):
@@ -287,7 +297,7 @@ def solve_fragments(pot, frags, only_chem=False, opts=None, eeval=False, use_cum
         # one options struct for the batch: the per-fragment ones differ at most by relax_density, which _solve_inputs set identically
         outs = solve_batch([f.dev for f in frags], [f.nsocc for f in frags], [f.fock + f.heff for f in frags], [f.dm0 for f in frags],
                            opts=o_list[0], eeval=eeval, stats=stats, solver=solver)
-        return [f._solve_outputs(out, eeval, use_cumulant) for f, out in zip(frags, outs)]
+        return [f._solve_outputs(out, eeval, use_cumulant, solver) for f, out in zip(frags, outs)]
 
     def one(fobj):
         if pot is not None:

@@ -277,6 +277,31 @@ int qemb_df_add_rs_block(qemb_df_t df, int p0, int p1, const double* block);
 int qemb_df_pw_imag_absmax(qemb_df_t df, double* out);
 int qemb_df_pw_select(qemb_df_t df, int part);
 
+/* k-point density fitting of the periodic driver: what kbe/pbe.py:529-565 (int_transform = "out-core-DF") hands to libdmet -- the k-point GDF tensor, one
+ * complex block L^{ki,kj}[P,mu,nu] = (P | mu_ki* nu_kj) per k-point pair (un-normalised Bloch sums) -- stays on the device; a fragment with embedding orbitals
+ * C^k = TA_k receives a REAL 3-index factor with nk * naux rows:
+ *     M^q[P,pq] = sum_ki (C^ki)^H L^{ki,ki+q}[P] C^{ki+q},      (pq|rs) = nk^-3 sum_q sum_P Re( M^q[P,pq] conj(M^q[P,rs]) )
+ *     rows nk^-3/2 Re M^q for a class q = -q;  (2 nk^-3)^1/2 Re M^q and (2 nk^-3)^1/2 Im M^q for the lower-numbered class of every pair (q, -q).
+ * qemb_kdf_create: qclass[ki * nk + kj] = the class of kj - ki (the index of that k-point; the mesh has to close under differences: every row and column of the
+ *   table a permutation of 0..nk-1), qconj[q] = the class of -q.  The memory of the resident blocks is compared with the free device memory first
+ *   (QEMB_ERR_ALLOC with nk, naux, nao in the message).
+ * qemb_kdf_set_pair: the block of the pair (ki, kj), naux x nao x nao interleaved complex128 on the host.  A pair whose class is the -q partner of a kept class
+ *   may be omitted (it is accepted and not stored).
+ * qemb_kdf_transform: TA_k = nk x nao x n interleaved complex128 (host).  factor_only != 0: the fragment lives on the factor (qemb_frag_set_df_only semantics);
+ *   0: it receives the 4-fold packed block (the pair product of the factor) and the factor beside it, like qemb_df_transform.  out_s4_host (nullable): the block.
+ *   A needed pair that was never set: QEMB_ERR_ARG naming the pair.  An embedding basis that is not time-reversal symmetric (M^q not symmetric in its two
+ *   orbital indices beyond 1e-8 of its largest element, or Im M^q != 0 for q = -q): QEMB_ERR_NUMERIC with the deviation in the message.
+ * qemb_kdf_guard: the memory check of create + transform on its own (n_kept classes kept, with_block: the packed block is formed too) against
+ *   min(free device memory, limit_bytes) (limit_bytes < 0: the free memory alone); allocates nothing.                                                        */
+typedef void* qemb_kdf_t;
+int qemb_kdf_create(int nk, int naux, int nao, const int* qclass /* nk*nk */, const int* qconj /* nk */, qemb_kdf_t* out);
+int qemb_kdf_set_pair(qemb_kdf_t kdf, int ki, int kj, const double* L_interleaved_host);
+int qemb_kdf_transform(qemb_kdf_t kdf, const double* TA_k_interleaved /* nk*nao*n */, int n, double* out_s4_host /* or NULL */, qemb_frag_t frag, int factor_only);
+int qemb_kdf_free(qemb_kdf_t kdf);
+int qemb_kdf_guard(int nk, int naux, int nao, int n, int n_kept, int with_block, int64_t limit_bytes);
+/* the resident 3-index factor of a fragment (qemb_frag_mo_route_used gives its naux), naux x npair(n) to the host; QEMB_ERR_ARG without one */
+int qemb_frag_get_df_factor(qemb_frag_t f, double* B_host);
+
 /* ---------------------------------------------------------------- Schmidt decomposition ---------- */
 /* schmidt_decomposition(mo_coeff, nocc, AO_in_frag, thr_bath) -> (TA_lo_eo, n_f, n_b), molbe/pfrag.py:403-411.
  * lmo: N x nmo row-major; TA_lo_eo: caller buffer N x ld (ld >= n_f + n_b; 2*n_f always suffices).      */

@@ -192,6 +192,15 @@ int qemb_op_rdm2_add_nc(int64_t m, const double* g, double alpha, double* X);
 int qemb_op_rdm2_symmetrize(int64_t m, const double* g, double* X);
 int qemb_op_rdm2_eri_dot(int64_t m, int sym, const double* eri, const double* K, double* e_host);
 
+/* The three passes of the k-point DF transform on their own (device pointers; return after the kernel).  ld = nao rounded up to 16 doubles.
+ *   kdf_split: z [rows][nao] interleaved complex128 -> planes [rows][re (ld) | im (ld)], zero beyond nao
+ *   kdf_stack: ta [nk][nao][n] interleaved complex128 -> Cs [nk][2 ld][2 n] = [[C_re, C_im], [-C_im, C_re]] and Dk [nk][2 nao][2 n], rows (mu, re) = [C_re | -C_im], (mu, im) = [C_im | C_re]
+ *   kdf_pack:  M [naux][2][n][n] -> F[P][pair(p,q)] = w Re M, F[naux + P][pair(p,q)] = w Im M (the latter when paired), rows ldf apart; out2_host = {largest component
+ *              of M[P,p,q] - M[P,q,p] (not paired: and of Im M), largest |component| of M}                                                                     */
+int qemb_op_kdf_split(int64_t rows, int64_t nao, const double* z, double* planes);
+int qemb_op_kdf_stack(int64_t nk, int64_t nao, int64_t n, const double* ta, double* Cs, double* Dk);
+int qemb_op_kdf_pack(int64_t naux, int64_t n, const double* M, int paired, double w, double* F, int64_t ldf, double* out2_host);
+
 /* measurement hooks: set up SCF + integrals once, then run/timed single CCSD iterations                */
 int qemb_frag_prepare_ccsd(qemb_frag_t f, int nsocc, const double* h, const double* dm0, const qemb_solver_opts* opts);
 int qemb_frag_ccsd_iterate(qemb_frag_t f, int niter, double* e_corr, double* normt);

@@ -206,6 +206,15 @@ def _declare(lib):
     f("qemb_df_transform_screened", I, V, P, I, P, D, P, V)
     f("qemb_df_transform_factor", I, V, P, I, V)
     f("qemb_df_transform_screened_factor", I, V, P, I, P, D, V)
+    f("qemb_kdf_create", I, I, I, I, IP, IP, C.POINTER(c_vp))
+    f("qemb_kdf_set_pair", I, V, I, I, P)
+    f("qemb_kdf_transform", I, V, P, I, P, V, I)
+    f("qemb_kdf_free", I, V)
+    f("qemb_kdf_guard", I, I, I, I, I, I, I, L)
+    f("qemb_frag_get_df_factor", I, V, P)
+    f("qemb_op_kdf_split", I, L, L, P, P)
+    f("qemb_op_kdf_stack", I, L, L, L, P, P, P)
+    f("qemb_op_kdf_pack", I, L, L, P, I, D, P, L, DP)
     f("qemb_schmidt", I, P, I, I, I, LP, I, D, P, I, IP, IP)
     f("qemb_schmidt_subspace", I, P, I, I, I, LP, I, D, P, I, IP, IP)
     f("qemb_schmidt_svd", I, P, I, LP, I, D, P, I, IP, IP)

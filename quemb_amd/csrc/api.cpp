@@ -12,6 +12,7 @@
 #include "ccsd.h"
 #include "fragment.h"
 #include "ao2mo.h"
+#include "kdf.h"
 
 using namespace qemb;
 namespace qemb {
@@ -279,6 +280,16 @@ int qemb_op_rdm2_eri_dot(int64_t m, int sym, const double* eri, const double* K,
   return dev_d2h(e_host, w.p, sizeof(double));
 }
 
+int qemb_op_kdf_split(int64_t rows, int64_t nao, const double* z, double* planes) { QTRY(dev_kdf_split(rows, nao, z, planes)); return dev_sync(); }
+int qemb_op_kdf_stack(int64_t nk, int64_t nao, int64_t n, const double* ta, double* Cs, double* Dk) { QTRY(dev_kdf_stack(nk, nao, n, ta, Cs, Dk)); return dev_sync(); }
+int qemb_op_kdf_pack(int64_t naux, int64_t n, const double* M, int paired, double w, double* F, int64_t ldf, double* out2_host) {
+  if (!out2_host) { set_error("qemb_op_kdf_pack: out2_host is NULL"); return QEMB_ERR_ARG; }
+  DBuf wk;
+  QTRY(wk.alloc(dev_kdf_partial_count(naux > 0 ? naux : 1, n > 0 ? n : 1) + 2));
+  QTRY(dev_kdf_pack(naux, n, M, paired, w, F, ldf, wk.p + 2, wk.p));
+  return dev_d2h(out2_host, wk.p, 2 * sizeof(double));
+}
+
 // ---------------------------------------------------------------- fragment solver ----------------
 void qemb_default_opts(qemb_solver_opts* o) {
   CcsdOptions c; ScfOptions s;
@@ -342,6 +353,11 @@ int qemb_frag_get_eri_s4(qemb_frag_t f, double* s4) {
   CHECK_FRAG(f);
   if (!s4) { set_error("qemb_frag_get_eri_s4: null buffer"); return QEMB_ERR_ARG; }
   return FRAG(f)->export_eri_s4(s4);      // the resident block, or B^T B of a fragment that lives on its factor (formed for this call)
+}
+int qemb_frag_get_df_factor(qemb_frag_t f, double* B) {
+  CHECK_FRAG(f);
+  if (!B) { set_error("qemb_frag_get_df_factor: null buffer"); return QEMB_ERR_ARG; }
+  return FRAG(f)->export_df_factor(B);
 }
 int qemb_frag_set_energy_data(qemb_frag_t f, const double* h1, const double* veff0, const double* veff, double weight,
                               const int* centers, int ncenter) {
@@ -649,6 +665,30 @@ int qemb_df_transform(qemb_df_t df, const double* TA, int n, double* out_s4_host
   DBuf bb;
   if ((rc = d->transform(dTA, n, s4, nullptr, 0.0, frag ? &bb : nullptr))) return rc;
   return deliver_s4(s4, n, out_s4_host, frag, &bb, d->naux);
+}
+
+// ---------------------------------------------------------------- k-point DF (periodic) ------------
+#define KDF(k) (reinterpret_cast<KdfContext*>(k))
+int qemb_kdf_create(int nk, int naux, int nao, const int* qclass, const int* qconj, qemb_kdf_t* out) {
+  if (!out) { set_error("qemb_kdf_create: bad arguments"); return QEMB_ERR_ARG; }
+  KdfContext* k = new KdfContext();
+  int rc = k->create(nk, naux, nao, qclass, qconj);
+  if (rc) { delete k; return rc; }
+  *out = k;
+  return QEMB_OK;
+}
+int qemb_kdf_set_pair(qemb_kdf_t kdf, int ki, int kj, const double* L) {
+  if (!kdf) { set_error("qemb_kdf_set_pair: null handle"); return QEMB_ERR_ARG; }
+  return KDF(kdf)->set_pair(ki, kj, L);
+}
+int qemb_kdf_transform(qemb_kdf_t kdf, const double* TA_k, int n, double* out_s4_host, qemb_frag_t frag, int factor_only) {
+  if (!kdf) { set_error("qemb_kdf_transform: null handle"); return QEMB_ERR_ARG; }
+  return KDF(kdf)->transform(TA_k, n, out_s4_host, FRAG(frag), factor_only);
+}
+int qemb_kdf_free(qemb_kdf_t kdf) { delete KDF(kdf); return QEMB_OK; }
+int qemb_kdf_guard(int nk, int naux, int nao, int n, int n_kept, int with_block, int64_t limit_bytes) {
+  if (nk <= 0 || naux <= 0 || nao <= 0 || n <= 0 || n_kept <= 0 || n_kept > nk) { set_error("qemb_kdf_guard: bad arguments"); return QEMB_ERR_ARG; }
+  return KdfContext::guard(nk, naux, nao, KdfContext::resident_bytes(nk, naux, nao, n_kept), KdfContext::work_bytes(nk, naux, nao, n, n_kept, with_block != 0), limit_bytes);
 }
 
 // ---------------------------------------------------------------- Schmidt ---------------------------

@@ -319,6 +319,30 @@ int dev_rdm2_add_nc(int64_t m, const double* g, double alpha, double* X);
 int dev_rdm2_symmetrize(int64_t m, const double* g, double* X);
 int dev_rdm2_eri_dot(int64_t m, int sym, const double* eri, const double* K, double* partials, double* out_dev);
 
+// ---- k-point density fitting (kdf.cpp; kernels in kdf_ops.hip, scalar restatement for the mock in kdf_ops_hostcheck.cpp) -------------------------
+// Three HBM passes around the two quarter transforms of KdfContext::transform; no atomics, every output element written once.
+// Row stride of the planar images of a pair block: whole 128-byte lines.
+inline int64_t kdf_ld(int64_t nao) { return (nao + 15) / 16 * 16; }
+//   split: z [rows][nao] interleaved complex128 (re, im) -> planes [rows][2][ld]: row r holds its real parts (ld doubles, zero beyond nao) and then its
+//          imaginary parts -- the K-stacked left operand [L_re | L_im] of the first quarter transform (rows = naux * nao)
+int dev_kdf_split(int64_t rows, int64_t nao, const double* z, double* planes);
+//   stack: ta [nk][nao][n] interleaved complex128 (C^k = TA_k) -> for every k
+//          Cs[k] (2 ld x 2 n):  row nu      = [ C_re[nu,:] | C_im[nu,:] ],  row ld + nu = [ -C_im[nu,:] | C_re[nu,:] ],  zero rows for nu >= nao  (right operand, first quarter)
+//          Dk[k] (2 nao x 2 n): row (mu, 0) = [ C_re[mu,:] | -C_im[mu,:] ], row (mu, 1) = [ C_im[mu,:] | C_re[mu,:] ]                            (conj(C)^T stored K x M, second quarter)
+int dev_kdf_stack(int64_t nk, int64_t nao, int64_t n, const double* ta, double* Cs, double* Dk);
+//   pack:  M [naux][2][n][n] (planes Re, Im of M^q[P,p,q]) -> F[P][pair(p,q)] = w Re M[P,p,q] and, when `paired`, F[naux + P][pair(p,q)] = w Im M[P,p,q]  (p >= q,
+//          rows ldf apart);  out2_dev[0] = the largest component of M[P,p,q] - M[P,q,p] (when not `paired` also of the dropped Im M), out2_dev[1] = the largest
+//          |component| of M: one partial pair per workgroup, reduced by a second small launch in a fixed order.  partials: dev_kdf_partial_count(naux, n) doubles.
+inline int64_t dev_kdf_partial_count(int64_t naux, int64_t n) {
+  const int64_t nt = (n + 31) / 32;
+  return 2 * (nt * (nt + 1) / 2) * (naux < 1024 ? naux : 1024);
+}
+inline int kdf_check_pack(int64_t naux, int64_t n, const void* M, const void* F, int64_t ldf, const void* partials, const void* out2) {
+  if (naux <= 0 || n <= 0 || n > 32767 || !M || !F || !partials || !out2 || ldf < n * (n + 1) / 2) { set_error("dev_kdf_pack: bad arguments"); return QEMB_ERR_ARG; }
+  return 0;
+}
+int dev_kdf_pack(int64_t naux, int64_t n, const double* M, int paired, double w, double* F, int64_t ldf, double* partials, double* out2_dev);
+
 // ---- screening helpers of the semi-sparse DF transform ---------------------------------------------------------------
 // out[i] = (|x[i]| >= eps) ? 1 : 0
 int dev_threshold_mask(int64_t n, const double* x, double eps, double* out);

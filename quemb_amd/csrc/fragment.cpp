@@ -118,6 +118,10 @@ int Fragment::materialize_s4(DBuf& out) {
   QTRY(out.alloc(np * np));
   return df_pair_product(np, df_naux_, df_factor_, out);
 }
+int Fragment::export_df_factor(double* B_host) {
+  if (!df_factor_.p) { set_error("fragment has no 3-index factor"); return QEMB_ERR_ARG; }
+  return dev_d2h(B_host, df_factor_, sizeof(double) * df_naux_ * npair(n_));
+}
 int Fragment::export_eri_s4(double* s4_host) {
   const int64_t np = npair(n_);
   if (eri_s4_.p) return dev_d2h(s4_host, eri_s4_, sizeof(double) * np * np);

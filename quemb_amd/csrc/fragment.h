@@ -59,6 +59,7 @@ class Fragment {
   bool factor_only() const { return !eri_s4_.p && df_factor_.p; }
   bool has_eris() const { return eri_s4_.p || df_factor_.p; }
   int export_eri_s4(double* s4_host);               // the resident block, or B^T B formed for this call
+  int export_df_factor(double* B_host);             // the resident factor (df_naux() x npair(n)); an error without one
   int64_t resident_bytes() const;                   // device bytes this fragment keeps between solves (ERIs / factor, orbitals, kept amplitudes)
   int df_naux() const { return df_naux_; }
   int set_mo_route(int route);                  // -1: by cost (default), 0: four-index transformation of eri_s4, 1: the factor (an error without one)

@@ -21,6 +21,10 @@ Fragment ERIs (`BE._eri_transform`, kbe/pbe.py:502-572):
                                         fragment's TA_k by the same device transform -- what libdmet's `get_emb_eri_fast_gdf(cell, mf.with_df,
                                         C_ao_eo=TA)` computes from the k-point GDF tensor (:529-537): fragment ERIs of BASELINE configs[4]
                                         (polyacetylene, 1 x 1 x 3 k-points) never leave the device
+    int_transform="kpoint-DF-hip"       k-point sampled, what the reference's default "out-core-DF" does (:529-565): the k-point GDF tensor (`df_source`, a
+                                        `kbe_eri_kpoint.KPointDFSource`: one complex block (P | mu_ki nu_kj) per k-point pair) stays on the device and every
+                                        fragment receives a real factor of N_k naux rows from its TA_k -- N_k^2 blocks instead of the N_k^3 supercell tensor
+                                        (`kbe_eri_kpoint.integral_kpoint_DF`, qemb_kdf_transform); `df_resident` as in the molecular driver
     int_transform="fragment-eris"       `eri_provider(fragment) -> (npair(n), npair(n))`: the seam where the reference calls libdmet's
                                         `get_emb_eri_fast_gdf(cell, mf.with_df, C_ao_eo=TA)` (:529-537) or reads a cderi file
                                         (:877-896); no periodic integral code exists in this image, so the provider is an argument
@@ -61,7 +65,7 @@ class KMeanField:
 
 class BE(mbe.BE):
     def __init__(self, mf: KMeanField, fobj, *, lo_method="lowdin", thr_bath=1.0e-10, int_transform="fragment-eris", eri_provider=None,
-                 df_source=None, unitcell=1, compute_hf=True, solver_opts=None, lib=None, distribute=True, nstreams=None, lockstep=None):
+                 df_source=None, unitcell=1, compute_hf=True, solver_opts=None, lib=None, distribute=True, nstreams=None, lockstep=None, df_resident="factor"):
         if lo_method != "lowdin":
             raise NotImplementedError("only lo_method='lowdin' is mirrored (localisation is upstream of the hot path)")
         if getattr(fobj, "frozen_core", False):
@@ -71,6 +75,9 @@ class BE(mbe.BE):
         self.nstreams = None if nstreams is None else int(nstreams)      # None: from the fragments' sizes at the first sweep (solver.sweep_mode)
         self.lockstep = None if lockstep is None else bool(lockstep)
         self.int_transform, self.eri_provider, self.df_source = int_transform, eri_provider, df_source
+        if df_resident not in ("factor", "block"):
+            raise ValueError("df_resident must be 'factor' or 'block'")
+        self.df_resident = df_resident                # read by int_transform="kpoint-DF-hip" (mbe.BE: what a density-fitted fragment keeps resident)
         self.compute_hf = compute_hf
         self.unrestricted = False
         self.kpts, self.kmesh, self.a_vec = np.asarray(mf.kpts, dtype=np.float64), [int(x) for x in mf.kmesh], np.asarray(mf.a_vec)
@@ -96,8 +103,8 @@ class BE(mbe.BE):
         self.C_core = self.P_core = self.core_veff = None
         if int_transform == "int-direct-DF-hip" and np.abs(self.kpts).max() > 0:
             raise NotImplementedError("k-point sampled ERI not implemented for int-direct-DF.")          # kbe/pbe.py:233-236
-        if int_transform not in ("int-direct-DF-hip", "supercell-DF-hip", "fragment-eris"):
-            raise ValueError(f"int_transform {int_transform!r} is not one of ('int-direct-DF-hip', 'supercell-DF-hip', 'fragment-eris')")
+        if int_transform not in ("int-direct-DF-hip", "supercell-DF-hip", "kpoint-DF-hip", "fragment-eris"):
+            raise ValueError(f"int_transform {int_transform!r} is not one of ('int-direct-DF-hip', 'supercell-DF-hip', 'kpoint-DF-hip', 'fragment-eris')")
         self.pot = mbe.initialize_pot(fobj.n_frag, fobj.relAO_per_edge_per_frag)
         self.Fobjs: list[KFrags] = []
         self.stats = {}
@@ -165,6 +172,15 @@ class BE(mbe.BE):
                 def __init__(s_, f):
                     s_.TA, s_.dev = f.real_space_TA(self.a_vec, self.kpts, self.kmesh), f.dev
             keo.integral_direct_DF(self.df_source, [_Super(f) for f in frs], lib=self.lib)
+        elif self.int_transform == "kpoint-DF-hip":
+            from . import kbe_eri_kpoint as kek
+            if self.df_source is None:
+                raise ValueError("`df_source` (a kbe_eri_kpoint.KPointDFSource: the k-point GDF tensor) has to be defined.")
+            if self.df_source.nao != self.S.shape[1] or self.df_source.nk != self.nkpt:
+                raise ValueError(f"kpoint-DF-hip: the source has nao = {self.df_source.nao} and {self.df_source.nk} k-points, the cell nao = {self.S.shape[1]} and {self.nkpt}")
+            if np.abs(np.asarray(self.df_source.kpts) - self.kpts).max() > 1e-9:
+                raise ValueError("kpoint-DF-hip: the k-points of the source are not the k-points of the mean field")
+            kek.integral_kpoint_DF(self.df_source, frs, lib=self.lib, factor_only=self.df_resident == "factor")
         else:
             if self.eri_provider is None:
                 raise ValueError("`eri_provider` has to be defined for int_transform='fragment-eris'")

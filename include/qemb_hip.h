@@ -299,6 +299,34 @@ int qemb_kdf_set_pair(qemb_kdf_t kdf, int ki, int kj, const double* L_interleave
 int qemb_kdf_transform(qemb_kdf_t kdf, const double* TA_k_interleaved /* nk*nao*n */, int n, double* out_s4_host /* or NULL */, qemb_frag_t frag, int factor_only);
 int qemb_kdf_free(qemb_kdf_t kdf);
 int qemb_kdf_guard(int nk, int naux, int nao, int n, int n_kept, int with_block, int64_t limit_bytes);
+/* ---- DF integrals from the basis: (mu nu|P) and (P|Q) evaluated on the device (csrc/int3c.cpp, kernels csrc/int3c_ops.hip) ----
+ * What the reference obtains from libcint (df.incore.aux_e2, auxmol.intor('int2c2e'): molbe/eri_onthefly.py:64-108, eri_sparse_DF.py:410-494).  Contracted,
+ * real-spherical, orbital shells s p d, auxiliary shells s..g; normalisation and component order are those of the records.
+ * qemb_int_basis_create: n_bf records of record_bytes each, one per CARTESIAN contracted function, shell after shell, the components of a shell in libcint
+ *   order (x^l first) sharing centre, exponents and coefficients:
+ *     struct { double ctr[3]; int lmn[3]; int nprim; double ex[8], co[8]; }      (co includes the normalisation; quemb_amd/integrals.py `_BF`)
+ *   c2s: 245 doubles, the Cartesian -> spherical matrices of l = 0..4 one after the other, each ncart(l) x (2l+1) row-major.  The matrices of l = 0 and
+ *   l = 1 must be the identity (p functions in x, y, z order, unit scale): the kernels do not apply them; anything else is QEMB_ERR_UNSUPPORTED.  A record that does not
+ *   continue its shell, or l > 4: QEMB_ERR_UNSUPPORTED naming the function.  A basis is uploaded once and used for any number of calls.
+ * qemb_int3c2e: layout 0 (N, N, naux), 1 (naux, N, N), 2 (naux, npair(N)) with mu >= nu, 3 (n_pairs, naux) for the n_pairs AO pairs (mu, nu) of `pairs`
+ *   (host, 2 n_pairs indices; NULL with the other layouts).  out: host array, or a device pointer when out_on_device != 0 (no host copy is made).
+ *   An orbital shell with l > 2: QEMB_ERR_UNSUPPORTED naming the shell.  Every element is stored once by one thread: the same bits run to run, and
+ *   (mu nu|P) = (nu mu|P) exactly.
+ * qemb_int2c2e: (P|Q), naux x naux; the lower triangle of shell pairs is computed and mirrored.
+ * qemb_df_create_empty + qemb_df_set_ints_from_basis: a DF context filled in place -- (P|Q) is formed, factored and inverted on the device and
+ *   (P|mu nu) is written by the kernels into the resident [naux][N][N] tensor; nothing of size naux N^2 exists on the host.  A context that had a
+ *   metric or integrals gets new ones.  qemb_df_set_ints_semisparse_from_basis: the same for the semi-sparse storage of qemb_df_set_ints_semisparse;
+ *   pairs (host, 2 n_unique indices) names the AO pair of every stored row, in offset order. */
+typedef void* qemb_int_basis_t;
+int qemb_int_basis_create(int n_bf, const void* bf_records, size_t record_bytes, const double* c2s, qemb_int_basis_t* out);
+int qemb_int_basis_free(qemb_int_basis_t basis);
+int qemb_int3c2e(qemb_int_basis_t basis, qemb_int_basis_t auxbasis, const int64_t* pairs, int64_t n_pairs, int layout, double* out, int out_on_device);
+int qemb_int2c2e(qemb_int_basis_t auxbasis, double* out, int out_on_device);
+int qemb_df_create_empty(qemb_df_t* out);
+int qemb_df_set_ints_from_basis(qemb_df_t df, qemb_int_basis_t basis, qemb_int_basis_t auxbasis);
+int qemb_df_set_ints_semisparse_from_basis(qemb_df_t df, qemb_int_basis_t basis, qemb_int_basis_t auxbasis, int64_t n_unique, const int64_t* pairs,
+                                           const int64_t* reach_ptr, const int32_t* reach_nu, const int64_t* reach_off);
+
 /* the resident 3-index factor of a fragment (qemb_frag_mo_route_used gives its naux), naux x npair(n) to the host; QEMB_ERR_ARG without one */
 int qemb_frag_get_df_factor(qemb_frag_t f, double* B_host);
 

@@ -210,6 +210,12 @@ int qemb_frag_ccsd_reset(qemb_frag_t f);
 int qemb_frag_ccsd_export(qemb_frag_t f, const char* name, double* host, int64_t nelem);
 
 
+/* DF integrals (csrc/int3c_ops.hip).  qemb_op_boys: out[i * (m_max + 1) + m] = F_m(x[i]) (device pointers, m_max <= 12).
+ * qemb_op_int3c_class: one block (a b|P) of explicit shells -- bf_*: the record (qemb_int_basis_create) of the first Cartesian component of each shell,
+ * la, lb <= 2, lP <= 4, c2s as qemb_int_basis_create; out_host[(a * (2 lb + 1) + b) * (2 lP + 1) + m] (all host pointers). */
+int qemb_op_boys(int m_max, int64_t n, const double* x, double* out);
+int qemb_op_int3c_class(int la, int lb, int lP, const void* bf_a, const void* bf_b, const void* bf_P, const double* c2s, double* out_host);
+
 #ifdef __cplusplus
 }
 #endif

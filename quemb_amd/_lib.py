@@ -212,6 +212,15 @@ def _declare(lib):
     f("qemb_kdf_free", I, V)
     f("qemb_kdf_guard", I, I, I, I, I, I, I, L)
     f("qemb_frag_get_df_factor", I, V, P)
+    f("qemb_int_basis_create", I, I, P, C.c_size_t, P, C.POINTER(c_vp))
+    f("qemb_int_basis_free", I, V)
+    f("qemb_int3c2e", I, V, V, P, L, I, P, I)
+    f("qemb_int2c2e", I, V, P, I)
+    f("qemb_df_create_empty", I, C.POINTER(c_vp))
+    f("qemb_df_set_ints_from_basis", I, V, V, V)
+    f("qemb_df_set_ints_semisparse_from_basis", I, V, V, V, L, P, P, P, P)
+    f("qemb_op_boys", I, I, L, P, P)
+    f("qemb_op_int3c_class", I, I, I, I, P, P, P, P, P)
     f("qemb_op_kdf_split", I, L, L, P, P)
     f("qemb_op_kdf_stack", I, L, L, L, P, P, P)
     f("qemb_op_kdf_pack", I, L, L, P, I, D, P, L, DP)

@@ -211,8 +211,32 @@ int DfContext::set_ints_packed(int N_, const double* h) {
 
 int DfContext::set_ints_semisparse(int N_, int64_t n_unique_, const double* unique_host, const int64_t* ptr, const int32_t* nu,
                                    const int64_t* off) {
+  if (n_unique_ > 0 && !unique_host) { set_error("set_ints_semisparse: bad arguments"); return QEMB_ERR_ARG; }
+  QTRY(begin_ints_semisparse(N_, n_unique_, ptr, nu, off));
+  return n_unique > 0 ? dev_h2d(Usp, unique_host, sizeof(double) * n_unique * naux) : QEMB_OK;
+}
+
+// the metric from an image that is on the device already (int3c.cpp); J is consumed
+int DfContext::set_metric_from_device(int naux_, DBuf&& J) {
+  if (naux_ <= 0 || !J.p) { set_error("DfContext::set_metric_from_device: bad arguments"); return QEMB_ERR_ARG; }
+  naux = naux_;
+  DBuf L = std::move(J);
+  QTRY(dev_cholesky_lower(naux, L));
+  QTRY(Linv.alloc((int64_t)naux * naux));
+  return dev_tri_inverse_lower(naux, L, Linv);
+}
+// (P|mu nu) as [naux][N][N], allocated for a producer that writes every element (int3c.cpp)
+int DfContext::begin_ints_Lpq(int N_) {
   if (naux <= 0) { set_error("DfContext: set the metric first"); return QEMB_ERR_ARG; }
-  if (N_ <= 0 || n_unique_ < 0 || !ptr || (n_unique_ > 0 && (!unique_host || !nu || !off))) { set_error("set_ints_semisparse: bad arguments"); return QEMB_ERR_ARG; }
+  if (N_ <= 0) { set_error("DfContext::begin_ints_Lpq: N must be positive"); return QEMB_ERR_ARG; }
+  N = N_;
+  Usp.release(); n_unique = 0; Lact = nullptr; Lpq_im.release(); Lpq_sum.release();
+  return Lpq.alloc((int64_t)naux * N * N);
+}
+// the structure of the semi-sparse tensor and its storage; the aux vectors are written by the caller
+int DfContext::begin_ints_semisparse(int N_, int64_t n_unique_, const int64_t* ptr, const int32_t* nu, const int64_t* off) {
+  if (naux <= 0) { set_error("DfContext: set the metric first"); return QEMB_ERR_ARG; }
+  if (N_ <= 0 || n_unique_ < 0 || !ptr || (n_unique_ > 0 && (!nu || !off))) { set_error("set_ints_semisparse: bad arguments"); return QEMB_ERR_ARG; }
   if (ptr[0] != 0) { set_error("set_ints_semisparse: reach_ptr[0] must be 0"); return QEMB_ERR_ARG; }
   for (int mu = 0; mu < N_; ++mu) {
     if (ptr[mu + 1] < ptr[mu]) { set_error("set_ints_semisparse: reach_ptr must be non-decreasing"); return QEMB_ERR_ARG; }
@@ -224,8 +248,7 @@ int DfContext::set_ints_semisparse(int N_, int64_t n_unique_, const double* uniq
   reach_nu.assign(nu, nu + ptr[N]);
   reach_off.assign(off, off + ptr[N]);
   Lpq.release(); Lact = nullptr; Lpq_im.release(); Lpq_sum.release();
-  QTRY(Usp.alloc(std::max<int64_t>(1, n_unique * naux)));
-  return n_unique > 0 ? dev_h2d(Usp, unique_host, sizeof(double) * n_unique * naux) : QEMB_OK;
+  return Usp.alloc(std::max<int64_t>(1, n_unique * naux));
 }
 
 // bpT[P(i,j)][L'] (pair rows of naux) -> (ij|kl) = sum_L bb[ij][L] bb[kl][L], bb = bpT Linv^T   (eval_via_cholesky, eri_sparse_DF.cpp:611-621)

@@ -48,6 +48,11 @@ class DfContext {
   // exch_reachable_with_offsets in CSR form (partners nu of mu and the row of the pair's aux vector).  O(n_unique naux) memory.
   int set_ints_semisparse(int N_, int64_t n_unique_, const double* unique_host, const int64_t* reach_ptr, const int32_t* reach_nu,
                           const int64_t* reach_off);
+  // For a producer on the device (int3c.cpp: the integrals from the basis): the metric from a device image (consumed), and the storage of the dense
+  // [naux][N][N] / semi-sparse [n_unique][naux] tensor without an upload -- the producer writes every element.
+  int set_metric_from_device(int naux_, DBuf&& j2c_dev);
+  int begin_ints_Lpq(int N_);
+  int begin_ints_semisparse(int N_, int64_t n_unique_, const int64_t* reach_ptr, const int32_t* reach_nu, const int64_t* reach_off);
   // S_abs_dev (N x N, may be null) + eps: the MO-coefficient screening of the semi-sparse transform
   // (_cpp/eri_sparse_DF.cpp:443-465 get_AO_per_MO): (P|mu i) is kept only where |S_abs TA|(mu,i) >= eps.
   // keep_bb (nullable): receives the fitted factor B_{ij}^{L} = bb[naux][npair(n)] (eri_onthefly.py:141) the block was formed from

@@ -13,6 +13,9 @@
 #include "fragment.h"
 #include "ao2mo.h"
 #include "kdf.h"
+#include "int3c.h"
+#include <mutex>
+#include <set>
 
 using namespace qemb;
 namespace qemb {
@@ -258,6 +261,10 @@ int qemb_op_pack_density_sym(int64_t n, const double* D, double* Dp) { return de
 int qemb_op_jacobi_svd(int64_t m, int64_t n, double* G, double* s, double* U, double* V, int* sweeps) { return dev_jacobi_svd(m, n, G, s, U, V, sweeps); }
 int qemb_op_cholesky_lower(int64_t n, double* A) { return dev_cholesky_lower(n, A); }
 int qemb_op_tri_inverse_lower(int64_t n, const double* L, double* Linv) { return dev_tri_inverse_lower(n, L, Linv); }
+int qemb_op_boys(int m_max, int64_t n, const double* x, double* out) { QTRY(dev_boys(m_max, n, x, out)); return dev_sync(); }
+int qemb_op_int3c_class(int la, int lb, int lP, const void* bf_a, const void* bf_b, const void* bf_P, const double* c2s, double* out_host) {
+  return int3c_block(la, lb, lP, reinterpret_cast<const BfRecord*>(bf_a), reinterpret_cast<const BfRecord*>(bf_b), reinterpret_cast<const BfRecord*>(bf_P), c2s, out_host);
+}
 int qemb_op_mp2_amplitudes(int64_t o, int64_t v, const double* ovov, const double* eo, const double* ev, double* t2, double* G, double* e_host) {
   DBuf part, e;
   QTRY(part.alloc(dev_mp2_partial_count(o, v))); QTRY(e.alloc(1));
@@ -606,6 +613,88 @@ int qemb_df_pw_select(qemb_df_t df, int part) {
   return reinterpret_cast<DfContext*>(df)->select_part(part);
 }
 int qemb_df_free(qemb_df_t df) { delete reinterpret_cast<DfContext*>(df); return QEMB_OK; }
+
+// ---- DF integrals from the basis (int3c.cpp) ----
+static std::mutex g_basis_mu;
+static std::set<IntBasis*> g_basis_live;      // a freed or foreign handle is an argument error, not a crash
+static IntBasis* live_basis(qemb_int_basis_t b, const char* who) {
+  std::lock_guard<std::mutex> lk(g_basis_mu);
+  IntBasis* p = reinterpret_cast<IntBasis*>(b);
+  if (!p || !g_basis_live.count(p)) { set_error(std::string(who) + ": not a live basis handle (null, freed or foreign)"); return nullptr; }
+  return p;
+}
+int qemb_int_basis_create(int n_bf, const void* bf_records, size_t record_bytes, const double* c2s, qemb_int_basis_t* out) {
+  if (!out) { set_error("qemb_int_basis_create: bad arguments"); return QEMB_ERR_ARG; }
+  if (record_bytes != sizeof(BfRecord)) { set_error("qemb_int_basis_create: record_bytes is " + std::to_string(record_bytes) + ", the record of this library has " + std::to_string(sizeof(BfRecord))); return QEMB_ERR_ARG; }
+  IntBasis* b = new IntBasis();
+  int rc = b->create(n_bf, reinterpret_cast<const BfRecord*>(bf_records), c2s);
+  if (rc) { delete b; return rc; }
+  { std::lock_guard<std::mutex> lk(g_basis_mu); g_basis_live.insert(b); }
+  *out = b;
+  return QEMB_OK;
+}
+int qemb_int_basis_free(qemb_int_basis_t b) {
+  if (!b) return QEMB_OK;
+  IntBasis* p = live_basis(b, "qemb_int_basis_free");
+  if (!p) return QEMB_ERR_ARG;
+  { std::lock_guard<std::mutex> lk(g_basis_mu); g_basis_live.erase(p); }
+  delete p;
+  return QEMB_OK;
+}
+int qemb_int3c2e(qemb_int_basis_t basis, qemb_int_basis_t auxbasis, const int64_t* pairs, int64_t n_pairs, int layout, double* out, int out_on_device) {
+  IntBasis* o = live_basis(basis, "qemb_int3c2e"); if (!o) return QEMB_ERR_ARG;
+  IntBasis* a = live_basis(auxbasis, "qemb_int3c2e"); if (!a) return QEMB_ERR_ARG;
+  if (!out) { set_error("qemb_int3c2e: null output"); return QEMB_ERR_ARG; }
+  if (out_on_device) return int3c_fill(*o, *a, layout, pairs, n_pairs, out);
+  const int64_t N = o->nao, na = a->nao;
+  const int64_t sz = layout == INT_LAYOUT_PAIRS ? std::max<int64_t>(n_pairs, 0) * na : layout == INT_LAYOUT_PACKED ? na * (N * (N + 1) / 2) : na * N * N;
+  DBuf d;
+  QTRY(d.alloc(sz));
+  QTRY(int3c_fill(*o, *a, layout, pairs, n_pairs, d));
+  return sz > 0 ? dev_d2h(out, d, sizeof(double) * sz) : QEMB_OK;
+}
+int qemb_int2c2e(qemb_int_basis_t auxbasis, double* out, int out_on_device) {
+  IntBasis* a = live_basis(auxbasis, "qemb_int2c2e"); if (!a) return QEMB_ERR_ARG;
+  if (!out) { set_error("qemb_int2c2e: null output"); return QEMB_ERR_ARG; }
+  if (out_on_device) return int2c_fill(*a, out);
+  DBuf d;
+  QTRY(d.alloc((int64_t)a->nao * a->nao));
+  QTRY(int2c_fill(*a, d));
+  return dev_d2h(out, d, sizeof(double) * a->nao * a->nao);
+}
+int qemb_df_create_empty(qemb_df_t* out) {
+  if (!out) { set_error("qemb_df_create_empty: bad arguments"); return QEMB_ERR_ARG; }
+  *out = new DfContext();
+  return QEMB_OK;
+}
+static int df_metric_from_basis(DfContext* d, IntBasis* a) {
+  DBuf J;
+  QTRY(J.alloc((int64_t)a->nao * a->nao));
+  QTRY(int2c_fill(*a, J));
+  return d->set_metric_from_device(a->nao, std::move(J));
+}
+int qemb_df_set_ints_from_basis(qemb_df_t df, qemb_int_basis_t basis, qemb_int_basis_t auxbasis) {
+  if (!df) { set_error("qemb_df_set_ints_from_basis: null handle"); return QEMB_ERR_ARG; }
+  IntBasis* o = live_basis(basis, "qemb_df_set_ints_from_basis"); if (!o) return QEMB_ERR_ARG;
+  IntBasis* a = live_basis(auxbasis, "qemb_df_set_ints_from_basis"); if (!a) return QEMB_ERR_ARG;
+  DfContext* d = reinterpret_cast<DfContext*>(df);
+  QTRY(df_metric_from_basis(d, a));
+  QTRY(d->begin_ints_Lpq(o->nao));
+  return int3c_fill(*o, *a, INT_LAYOUT_LPQ, nullptr, 0, d->Lpq);
+}
+int qemb_df_set_ints_semisparse_from_basis(qemb_df_t df, qemb_int_basis_t basis, qemb_int_basis_t auxbasis, int64_t n_unique, const int64_t* pairs,
+                                           const int64_t* reach_ptr, const int32_t* reach_nu, const int64_t* reach_off) {
+  if (!df) { set_error("qemb_df_set_ints_semisparse_from_basis: null handle"); return QEMB_ERR_ARG; }
+  IntBasis* o = live_basis(basis, "qemb_df_set_ints_semisparse_from_basis"); if (!o) return QEMB_ERR_ARG;
+  IntBasis* a = live_basis(auxbasis, "qemb_df_set_ints_semisparse_from_basis"); if (!a) return QEMB_ERR_ARG;
+  if (n_unique > 0 && !pairs) { set_error("qemb_df_set_ints_semisparse_from_basis: null pair list"); return QEMB_ERR_ARG; }
+  DfContext* d = reinterpret_cast<DfContext*>(df);
+  QTRY(df_metric_from_basis(d, a));
+  QTRY(d->begin_ints_semisparse(o->nao, n_unique, reach_ptr, reach_nu, reach_off));
+  if (n_unique == 0) return QEMB_OK;
+  QTRY(dev_fill(d->Usp, n_unique * a->nao, 0.0));      // a row the pair list does not name stays zero rather than undefined
+  return int3c_fill(*o, *a, INT_LAYOUT_PAIRS, pairs, n_unique, d->Usp);
+}
 int qemb_df_set_ints(qemb_df_t df, int N, const double* ints, int layout) {
   if (!df || !ints || N <= 0) { set_error("qemb_df_set_ints: bad arguments"); return QEMB_ERR_ARG; }
   DfContext* d = reinterpret_cast<DfContext*>(df);

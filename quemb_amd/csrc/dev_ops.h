@@ -343,6 +343,14 @@ inline int kdf_check_pack(int64_t naux, int64_t n, const void* M, const void* F,
 }
 int dev_kdf_pack(int64_t naux, int64_t n, const double* M, int paired, double w, double* F, int64_t ldf, double* partials, double* out2_dev);
 
+// ---- DF integrals from the basis (int3c.cpp; kernels in int3c_ops.hip, scalar restatement for the mock in int3c_ops_hostcheck.cpp; arithmetic in int3c_core.h) ----
+// boys: out[i * (m_max + 1) + m] = F_m(x[i]), 0 <= m <= m_max <= 12
+int dev_boys(int m_max, int64_t n, const double* x, double* out);
+// One launch per angular class (la >= lb; la <= 2 for orbital pairs, la <= 4 with lb = 0 for the metric; lp <= 4): every (shell pair, auxiliary shell)
+// block of the class is evaluated and stored, each element once, in the layout args.layout names (int3c_core.h: ClassArgs).
+namespace int3c { struct ClassArgs; }
+int dev_int3c_class(int la, int lb, int lp, const int3c::ClassArgs& args);
+
 // ---- screening helpers of the semi-sparse DF transform ---------------------------------------------------------------
 // out[i] = (|x[i]| >= eps) ? 1 : 0
 int dev_threshold_mask(int64_t n, const double* x, double eps, double* out);

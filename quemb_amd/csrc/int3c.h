@@ -1,0 +1,44 @@
+// int3c.h -- the integral source of density fitting on the device: (mu nu|P) and (P|Q) from a basis uploaded once (what integrals.aux_e2, aux_e2_pairs and
+// int2c2e obtain from the host library; the reference asks libcint: molbe/eri_onthefly.py:64-108, eri_sparse_DF.py:410-494).  The driver groups shell
+// pairs and auxiliary shells by angular momentum and issues one launch per class (dev_int3c_class); results go straight to the layout the consumer reads.
+#pragma once
+#include <cstdint>
+#include <vector>
+#include "dev_ops.h"
+#include "int3c_core.h"
+#include "tensor_utils.h"
+
+namespace qemb {
+
+class DfContext;
+
+// the record integrals.py builds per Cartesian contracted function (`_BF`; csrc_host/gto_ints.c bf_t)
+struct BfRecord {
+  double ctr[3];
+  int lmn[3];
+  int nprim;
+  double ex[int3c::kMaxPrim], co[int3c::kMaxPrim];
+};
+
+class IntBasis {
+ public:
+  int nshell = 0, nao = 0;
+  std::vector<int3c::Shell> shells;      // host copy: the driver sorts work by it
+  DBuf dshells, dc2s;                    // dshells: the nshell shells and, at index nshell, a unit s function (role B of the metric blocks)
+  // records: n_bf Cartesian functions, shell after shell, the components of a shell in libcint order with one set of exponents / coefficients;
+  // c2s: int3c::kC2sLen doubles, integrals.cart2sph(l) for l = 0..4; the matrices of l = 0, 1 must be the identity (QEMB_ERR_UNSUPPORTED otherwise)
+  int create(int n_bf, const BfRecord* records, const double* c2s_host);
+  const int3c::Shell* dev() const { return reinterpret_cast<const int3c::Shell*>(dshells.p); }
+};
+
+enum { INT_LAYOUT_PQL = 0, INT_LAYOUT_LPQ = 1, INT_LAYOUT_PACKED = 2, INT_LAYOUT_PAIRS = 3 };
+
+// (mu nu|P) into out_dev: (N, N, naux), (naux, N, N), (naux, npair(N)) or, with a pair list (n_pairs x 2 AO indices, host), (n_pairs, naux).
+// Orbital shells beyond d: QEMB_ERR_UNSUPPORTED naming the shell.
+int int3c_fill(const IntBasis& orb, const IntBasis& aux, int layout, const int64_t* pairs_host, int64_t n_pairs, double* out_dev);
+// (P|Q) into out_dev (naux x naux): the lower triangle of shell pairs is computed, the upper one copied
+int int2c_fill(const IntBasis& aux, double* out_dev);
+// one explicit block (qemb_op_int3c_class): out_host[(a * (2 lb + 1) + b) * (2 lP + 1) + m]
+int int3c_block(int la, int lb, int lp, const BfRecord* A, const BfRecord* B, const BfRecord* P, const double* c2s_host, double* out_host);
+
+}  // namespace qemb

@@ -70,8 +70,15 @@ def _get_AO_per_AO(S_abs, epsilon: float, TA=None, lib=None) -> dict[int, list[i
     return {int(i): [int(x) for x in np.nonzero(S_abs[:, i] >= epsilon)[0]] for i in sources}
 
 
-def get_sparse_P_mu_nu(mol: Mole, auxmol: Mole, exch_reachable) -> et.SemiSparseSym3DTensor:
-    """eri_sparse_DF.py:410-494: the 3-centre integrals of the reachable AO pairs in the reference's semi-sparse storage."""
+def _int_backend(integral_backend):
+    if integral_backend not in ("host", "hip"):
+        raise ValueError(f"integral_backend {integral_backend!r}: 'host' (the default) or 'hip'")
+    return integral_backend == "hip"
+
+
+def get_sparse_P_mu_nu(mol: Mole, auxmol: Mole, exch_reachable, fill: bool = True) -> et.SemiSparseSym3DTensor:
+    """eri_sparse_DF.py:410-494: the 3-centre integrals of the reachable AO pairs in the reference's semi-sparse storage.
+    fill=False: the structure alone (the device fills the stored pairs, DFContext.set_ints_from_mol)."""
     reach = [sorted(exch_reachable.get(mu, [])) for mu in range(mol.nao)]
     # the storage needs a symmetric relation (indexers.hpp:149-162); S_abs is symmetric, the per-fragment source selection is not
     sym = [set(r) for r in reach]
@@ -79,6 +86,8 @@ def get_sparse_P_mu_nu(mol: Mole, auxmol: Mole, exch_reachable) -> et.SemiSparse
         for nu in r:
             sym[nu].add(mu)
     t = et.SemiSparseSym3DTensor((auxmol.nao, mol.nao, mol.nao), [sorted(x) for x in sym])
+    if not fill:
+        return t
     pairs = sorted(((mu, nu) for mu, r in enumerate(t.exch_reachable_unique) for nu in r), key=lambda pq: t.offsets[et.ravel_symmetric(*pq)])
     if pairs:
         vals = aux_e2_pairs(mol, auxmol, pairs)                        # (n_unique, naux), in offset order
@@ -88,38 +97,52 @@ def get_sparse_P_mu_nu(mol: Mole, auxmol: Mole, exch_reachable) -> et.SemiSparse
 
 
 def transform_sparse_DF_integral_hip(mf, Fobjs, auxbasis, AO_coeff_epsilon: float = 1e-10, MO_coeff_epsilon: float = 1e-5,
-                                     precompute_P_mu_nu: bool = True, lib=None, stats=None, factor_only: bool = False):
+                                     precompute_P_mu_nu: bool = True, lib=None, stats=None, factor_only: bool = False,
+                                     integral_backend: str = "host"):
     """`_run_sparse_df_driver` (eri_sparse_DF.py:535-656) with the device transform injected, as `transform_sparse_DF_integral_gpu`
     (:686-706) does with its cuBLAS one.  The fragment ERIs go straight into each fragment's device handle (the reference writes dataset
     `f{I}` of eri_file.h5).  Defaults as BE.__init__ (mbe.py:188-189)."""
     mol = mf.mol
     auxmol = make_auxmol(mol, auxbasis)
     S_abs = approx_S_abs(mol, lib=lib)
-    df = et.DFContext(j2c=int2c2e(auxmol), lib=lib)                      # (P|Q) -> Cholesky on the device (build_lowtri_PQ)
+    hip = _int_backend(integral_backend)
+    # (P|Q) -> Cholesky on the device (build_lowtri_PQ); integral_backend="hip": the metric and the stored pairs come from the device kernels
+    df = et.DFContext.empty(lib=lib) if hip else et.DFContext(j2c=int2c2e(auxmol), lib=lib)
+
+    def load(reach):
+        P = get_sparse_P_mu_nu(mol, auxmol, reach, fill=not hip)
+        if hip:
+            df.set_ints_from_mol(mol, auxmol, int_P_mu_nu=P)
+        else:
+            df.set_ints_semisparse(P)
+        return P
+
     try:
         if precompute_P_mu_nu:
-            P_mu_nu = get_sparse_P_mu_nu(mol, auxmol, _get_AO_per_AO(S_abs, AO_coeff_epsilon, None, lib=lib))
-            df.set_ints_semisparse(P_mu_nu)
+            P_mu_nu = load(_get_AO_per_AO(S_abs, AO_coeff_epsilon, None, lib=lib))
             if stats is not None:
                 stats.update(n_unique=P_mu_nu.unique_dense_data.shape[1], n_pairs_dense=mol.nao * (mol.nao + 1) // 2, naux=auxmol.nao)
         for f in Fobjs:
             if not precompute_P_mu_nu:                                   # "on-fly-sparse-DF": only what this fragment reaches
-                P_mu_nu = get_sparse_P_mu_nu(mol, auxmol, _get_AO_per_AO(S_abs, AO_coeff_epsilon, f.TA, lib=lib))
-                df.set_ints_semisparse(P_mu_nu)
+                P_mu_nu = load(_get_AO_per_AO(S_abs, AO_coeff_epsilon, f.TA, lib=lib))
             df.transform(f.TA, frag=f.dev, want_host=False, S_abs=S_abs, MO_coeff_epsilon=MO_coeff_epsilon, factor_only=factor_only)
     finally:
         df.free()
     return S_abs
 
 
-def integral_direct_DF_hip(mf, Fobjs, auxbasis, lib=None, factor_only: bool = False):
+def integral_direct_DF_hip(mf, Fobjs, auxbasis, lib=None, factor_only: bool = False, integral_backend: str = "host"):
     """molbe/eri_onthefly.py:45-145 (`int-direct-DF`): dense (mu nu|P), fragment transform, fit with the Cholesky factor of (P|Q).  No
     auxiliary-index blocking: the blocks of :18-42 exist to stay inside host RAM; naux N^2 doubles fit in HBM."""
     mol = mf.mol
     auxmol = make_auxmol(mol, auxbasis)
-    df = et.DFContext(j2c=int2c2e(auxmol), lib=lib)
+    if _int_backend(integral_backend):      # metric and (P|mu nu) from the device kernels, written into the resident tensor
+        df = et.DFContext.from_mol(mol, auxmol, lib=lib)
+    else:
+        df = et.DFContext(j2c=int2c2e(auxmol), lib=lib)
     try:
-        df.set_ints(aux_e2(mol, auxmol), mol.nao, "pqL")
+        if not _int_backend(integral_backend):
+            df.set_ints(aux_e2(mol, auxmol), mol.nao, "pqL")
         for f in Fobjs:
             df.transform(f.TA, frag=f.dev, want_host=False, factor_only=factor_only)
     finally:

@@ -181,6 +181,45 @@ class DFContext:
         self.h, self.nao, self.ischol = h, None, bool(ischol.value)
         return self
 
+    @classmethod
+    def empty(cls, lib=None):
+        """Context without a metric: `set_ints_from_mol` forms it on the device."""
+        self = cls.__new__(cls)
+        self.lib = lib or _lib.init()
+        h = c_vp()
+        check(self.lib.qemb_df_create_empty(C.byref(h)), "qemb_df_create_empty", self.lib)
+        self.h, self.nao, self.naux = h, None, 0
+        return self
+
+    @classmethod
+    def from_mol(cls, mol, auxmol, lib=None):
+        """Context whose metric and (P|mu nu) both come from the device integral kernels (`set_ints_from_mol`)."""
+        self = cls.empty(lib)
+        self.set_ints_from_mol(mol, auxmol)
+        return self
+
+    def set_ints_from_mol(self, mol, auxmol, int_P_mu_nu=None):
+        """In-place fill from the geometry (qemb_df_set_ints_from_basis): (P|Q) is formed and factored on the device and the kernels write (P|mu nu)
+        into the resident tensor; no array of naux N^2 doubles exists on the host.  With `int_P_mu_nu` (a SemiSparseSym3DTensor, its data unread)
+        the stored pairs of that structure are filled instead (qemb_df_set_ints_semisparse_from_basis)."""
+        from .integrals import DeviceBasis
+        b, a = DeviceBasis(mol, self.lib), DeviceBasis(auxmol, self.lib)
+        try:
+            if int_P_mu_nu is None:
+                check(self.lib.qemb_df_set_ints_from_basis(self.h, b.h, a.h), "qemb_df_set_ints_from_basis", self.lib)
+            else:
+                t = int_P_mu_nu
+                ptr, nu, off = _reach_csr(t.exch_reachable_with_offsets)
+                pairs = np.zeros((len(t.offsets), 2), dtype=np.int64)
+                for mu, r in enumerate(t.exch_reachable_unique):
+                    for q in r:
+                        pairs[t.offsets[ravel_symmetric(mu, q)]] = (mu, q)
+                check(self.lib.qemb_df_set_ints_semisparse_from_basis(self.h, b.h, a.h, len(pairs), pairs.ctypes.data, ptr.ctypes.data, nu.ctypes.data,
+                                                                      off.ctypes.data), "qemb_df_set_ints_semisparse_from_basis", self.lib)
+        finally:
+            b.free(); a.free()
+        self.naux, self.nao = auxmol.nao, mol.nao
+
     def alloc_ints(self, nao: int):
         """zeroed fitted tensor (L|mu nu) (real and imaginary part) for `add_pw_block` / `add_rs_block`"""
         check(self.lib.qemb_df_alloc_ints(self.h, int(nao)), "qemb_df_alloc_ints", self.lib)

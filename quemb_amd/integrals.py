@@ -290,8 +290,72 @@ def make_auxmol(mol: Mole, auxbasis):
     return aux
 
 
-def int2c2e(auxmol: Mole):
-    """(P|Q), auxmol.intor('int2c2e') (molbe/eri_onthefly.py:106-108, eri_sparse_DF.py:611)."""
+def _backend(backend):
+    if backend not in ("host", "hip"):
+        raise ValueError(f"backend {backend!r}: 'host' (libqemb_gto, the default) or 'hip' (the device kernels of libqemb_hip)")
+    return backend == "hip"
+
+
+def c2s_table():
+    """The Cartesian -> spherical matrices of l = 0..4 one after the other (245 doubles): what qemb_int_basis_create uploads."""
+    return np.ascontiguousarray(np.concatenate([cart2sph(l).ravel() for l in range(5)]))
+
+
+class DeviceBasis:
+    """A basis uploaded once to the device (qemb_int_basis_create) in the record format of `Mole.bfs`; freed on __del__ / .free()."""
+
+    def __init__(self, mol: Mole, lib=None):
+        from . import _lib
+        self.lib = lib or _lib.init()
+        h = C.c_void_p()
+        arr, tab = mol._arr(), c2s_table()
+        _lib.check(self.lib.qemb_int_basis_create(mol.ncart, C.addressof(arr), C.sizeof(_BF), tab.ctypes.data, C.byref(h)), "qemb_int_basis_create", self.lib)
+        self.h, self.nao = h, mol.nao
+
+    def free(self):
+        if getattr(self, "h", None):
+            self.lib.qemb_int_basis_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+INT_LAYOUTS = {"pqL": 0, "Lpq": 1, "packed": 2, "pairs": 3}
+
+
+def _int3c_hip(mol, auxmol, layout, pairs=None, lib=None):
+    from . import _lib
+    b, a = DeviceBasis(mol, lib), DeviceBasis(auxmol, lib)
+    try:
+        N, na = mol.nao, auxmol.nao
+        if pairs is None:
+            out = np.empty({"pqL": (N, N, na), "Lpq": (na, N, N), "packed": (na, N * (N + 1) // 2)}[layout])
+            pp, n = None, 0
+        else:
+            pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+            out = np.empty((len(pairs), na))
+            pp, n = pairs.ctypes.data, len(pairs)
+        _lib.check(b.lib.qemb_int3c2e(b.h, a.h, pp, n, INT_LAYOUTS[layout], out.ctypes.data, 0), "qemb_int3c2e", b.lib)
+        return out
+    finally:
+        b.free(); a.free()
+
+
+def int2c2e(auxmol: Mole, backend="host", lib=None):
+    """(P|Q), auxmol.intor('int2c2e') (molbe/eri_onthefly.py:106-108, eri_sparse_DF.py:611).  backend="hip": evaluated on the device."""
+    if _backend(backend):
+        from . import _lib
+        a = DeviceBasis(auxmol, lib)
+        try:
+            out = np.empty((auxmol.nao, auxmol.nao))
+            _lib.check(a.lib.qemb_int2c2e(a.h, out.ctypes.data, 0), "qemb_int2c2e", a.lib)
+            return out
+        finally:
+            a.free()
     lib = _load()
     n = auxmol.ncart
     out = np.zeros((n, n))
@@ -299,8 +363,11 @@ def int2c2e(auxmol: Mole):
     return auxmol._sph2(out)
 
 
-def aux_e2(mol: Mole, auxmol: Mole):
-    """(mu nu|P), dense (N, N, naux): pyscf.df.incore.aux_e2(mol, auxmol, 'int3c2e') (eri_onthefly.py:64-98)."""
+def aux_e2(mol: Mole, auxmol: Mole, backend="host", lib=None):
+    """(mu nu|P), dense (N, N, naux): pyscf.df.incore.aux_e2(mol, auxmol, 'int3c2e') (eri_onthefly.py:64-98).  backend="hip": the same array
+    from the device kernels (qemb_int3c2e)."""
+    if _backend(backend):
+        return _int3c_hip(mol, auxmol, "pqL", lib=lib)
     lib = _load()
     out = np.zeros((mol.ncart, mol.ncart, auxmol.ncart))
     lib.gto_eri_3c(mol.ncart, mol._arr(), auxmol.ncart, auxmol._arr(), out.ctypes.data_as(C.c_void_p))
@@ -311,9 +378,12 @@ def aux_e2(mol: Mole, auxmol: Mole):
     return out
 
 
-def aux_e2_pairs(mol: Mole, auxmol: Mole, pairs):
+def aux_e2_pairs(mol: Mole, auxmol: Mole, pairs, backend="host", lib=None):
     """(mu nu|P) for a list of AO pairs only: (npairs, naux), one auxiliary vector per pair -- the fill of the semi-sparse tensor
-    (get_sparse_P_mu_nu, eri_sparse_DF.py:410-494, which asks libcint for the shell blocks that contain the reachable pairs)."""
+    (get_sparse_P_mu_nu, eri_sparse_DF.py:410-494, which asks libcint for the shell blocks that contain the reachable pairs).
+    backend="hip": the shell blocks that hold the pairs are evaluated on the device."""
+    if _backend(backend):
+        return _int3c_hip(mol, auxmol, "pairs", pairs=pairs, lib=lib)
     lib = _load()
     pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
     if mol.cart:

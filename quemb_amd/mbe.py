@@ -32,7 +32,8 @@ def initialize_pot(n_frag, relAO_per_edge):
 class BE:
     def __init__(self, mf, fobj, *, lo_method="lowdin", thr_bath=1.0e-10, int_transform="in-core-hip", auxbasis=None,
                  df_ints=None, nproc=1, ompnum=1, initialize_fragment_idx=None, solver_opts=None, lib=None, distribute=True, nstreams=None, lockstep=None,
-                 eri_file=None, scratch_dir=None, restart=False, schmidt_method="subspace", MO_coeff_epsilon=1e-5, AO_coeff_epsilon=1e-10, df_resident="factor"):
+                 eri_file=None, scratch_dir=None, restart=False, schmidt_method="subspace", MO_coeff_epsilon=1e-5, AO_coeff_epsilon=1e-10, df_resident="factor",
+                 integral_backend="host"):
         if lo_method != "lowdin":
             raise NotImplementedError("only lo_method='lowdin' is mirrored (localisation is upstream of the hot path)")
         if restart:
@@ -46,6 +47,12 @@ class BE:
         if df_resident not in ("factor", "block"):
             raise ValueError("df_resident must be 'factor' or 'block'")
         self.df_resident = df_resident
+        # where the from-geometry DF transforms take (mu nu|P) and (P|Q) from: "host" (libqemb_gto) or "hip" (the device kernels; nothing of size naux N^2 on the host)
+        if integral_backend not in ("host", "hip"):
+            raise ValueError("integral_backend must be 'host' or 'hip'")
+        if integral_backend == "hip" and df_ints is not None:
+            raise ValueError("integral_backend='hip' evaluates the DF integrals from the geometry; with `df_ints` the integrals are the caller's")
+        self.integral_backend = integral_backend
         self.auxbasis = auxbasis
         self.MO_coeff_epsilon, self.AO_coeff_epsilon = float(MO_coeff_epsilon), float(AO_coeff_epsilon)      # mbe.py:191-192
         self.opts = solver_opts
@@ -153,13 +160,14 @@ class BE:
                 raise ValueError("`auxbasis` has to be defined.")                # mbe.py:1050
             frs = [self.Fobjs[I] for I in idx]
             if it == "int-direct-DF-hip":
-                sdf.integral_direct_DF_hip(self.mf, frs, self.auxbasis, lib=self.lib, factor_only=self.df_resident == "factor")
+                sdf.integral_direct_DF_hip(self.mf, frs, self.auxbasis, lib=self.lib, factor_only=self.df_resident == "factor",
+                                           integral_backend=self.integral_backend)
             else:
                 self.df_stats = {}
                 self.S_abs = sdf.transform_sparse_DF_integral_hip(self.mf, frs, self.auxbasis, AO_coeff_epsilon=self.AO_coeff_epsilon,
                                                                   MO_coeff_epsilon=self.MO_coeff_epsilon, lib=self.lib,
                                                                   precompute_P_mu_nu=(it == "sparse-DF-hip"), stats=self.df_stats,
-                                                                  factor_only=self.df_resident == "factor")
+                                                                  factor_only=self.df_resident == "factor", integral_backend=self.integral_backend)
         elif it in ("int-direct-DF-hip", "sparse-DF-hip"):
             # df_ints: (ints, j2c, layout) or a dict(ints=, layout= | int_P_mu_nu=, j2c= | L_PQ=, S_abs=, MO_coeff_epsilon=).
             # "sparse-DF-hip" applies the MO-coefficient screening of the reference's semi-sparse transform

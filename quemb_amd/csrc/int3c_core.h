@@ -2,6 +2,7 @@
 // the gfx950 kernels (int3c_ops.hip: one thread per block) and the scalar restatement of the mock device layer (int3c_ops_hostcheck.cpp: a loop) both
 // instantiate.  Same mathematics, normalisation and component order as the host source csrc_host/gto_ints.c behind integrals.aux_e2:
 //   (ab|c) = sum_prim ca cb cc K_ab 2 pi^5/2 / (p q sqrt(p + q)) sum_{tuv} E^{ab}_{tuv} sum_{t'u'v'} (-1)^{t'+u'+v'} E^{c}_{t'u'v'} R_{t+t',u+u',v+v'}(alpha, P - C)
+// (of the auxiliary expansion only the top term t' + u' + v' = l_P is carried: the others vanish in the solid-harmonic contraction, see block_cart)
 // with Cartesian components in libcint order (xx xy xz yy yz zz ...), then the Cartesian -> real-spherical matrix of integrals.cart2sph on each centre.
 // (P|Q) is the same block with a unit s function (exponent 0) as the second orbital shell -- what gto_eri_2c does.
 #pragma once
@@ -106,8 +107,9 @@ QEMB_I3_HD void hermite_e(double h, double XPA, double XPB, double* E) {
 }
 
 // The Cartesian block acc[(ia * ncart(LB) + ib) * ncart(LP) + ic] of the shells A, B (orbital pair) and C (auxiliary), summed over primitive triples.
+// harmonic_a (the metric: B is the unit s function, so A alone is a solid-harmonic Gaussian after block_to_sph): the top Hermite term of role A only, as for C.
 template <int LA, int LB, int LP>
-QEMB_I3_HD void block_cart(const Shell& A, const Shell& B, const Shell& Cs, double* acc) {
+QEMB_I3_HD void block_cart(const Shell& A, const Shell& B, const Shell& Cs, double* acc, bool harmonic_a = false) {
   constexpr int LAB = LA + LB, L = LAB + LP, NTA = LAB + 1, ncB = ncart(LB), ncP = ncart(LP);
   constexpr double kPref = 34.98683665524972497;      // 2 pi^(5/2)
   for (int k = 0; k < ncart(LA) * ncB * ncP; ++k) acc[k] = 0.0;
@@ -137,12 +139,11 @@ QEMB_I3_HD void block_cart(const Shell& A, const Shell& B, const Shell& Cs, doub
             for (int t = 0; t <= LAB; ++t)
               for (int u = 0; u <= LAB - t; ++u)
                 for (int v = 0; v <= LAB - t - u; ++v) {
-                  double g = 0.0;
-                  for (int tt = cx & 1; tt <= cx; tt += 2)
-                    for (int uu = cy & 1; uu <= cy; uu += 2)
-                      for (int vv = cz & 1; vv <= cz; vv += 2)
-                        g += Ec[cx * (LP + 1) + tt] * Ec[cy * (LP + 1) + uu] * Ec[cz * (LP + 1) + vv] * R[hidx(t + tt, u + uu, v + vv)];
-                  G[hidx(t, u, v)] = (LP & 1) ? -pref * g : pref * g;      // t' + u' + v' has the parity of LP in every term kept
+                  // only the top Hermite term t' = cx, u' = cy, v' = cz: block_to_sph contracts the component with a harmonic polynomial, and
+                  // S_lm(r) exp(-q r^2) = (2q)^-l S_lm(d/dC) exp(-q r^2), so the lower terms sum to zero there.  Carrying them would subtract Cartesian
+                  // integrals that keep the R^-1 ... R^-l parts from one another: 1e-10 of a far (g|g) block as rounding.  (s, p: the only term anyway.)
+                  const double g = Ec[cx * (LP + 1) + cx] * Ec[cy * (LP + 1) + cy] * Ec[cz * (LP + 1) + cz] * R[hidx(t + cx, u + cy, v + cz)];
+                  G[hidx(t, u, v)] = (LP & 1) ? -pref * g : pref * g;      // t' + u' + v' = LP
                 }
             int ia = 0;
             for (int ax = LA; ax >= 0; --ax)
@@ -156,10 +157,10 @@ QEMB_I3_HD void block_cart(const Shell& A, const Shell& B, const Shell& Cs, doub
                     const double* ey = Ey + (ay * (LB + 1) + by) * NTA;
                     const double* ez = Ez + (az * (LB + 1) + bz) * NTA;
                     double s = 0.0;
-                    for (int t = 0; t <= ax + bx; ++t)
-                      for (int u = 0; u <= ay + by; ++u) {
+                    for (int t = harmonic_a ? ax : 0; t <= ax + bx; ++t)
+                      for (int u = harmonic_a ? ay : 0; u <= ay + by; ++u) {
                         const double e2 = ex[t] * ey[u];
-                        for (int v = 0; v <= az + bz; ++v) s += e2 * ez[v] * G[hidx(t, u, v)];
+                        for (int v = harmonic_a ? az : 0; v <= az + bz; ++v) s += e2 * ez[v] * G[hidx(t, u, v)];
                       }
                     acc[(ia * ncB + ib) * ncP + ic] += s;
                   }
@@ -250,7 +251,7 @@ QEMB_I3_HD void class_item(const ClassArgs& g, int64_t item) {
     if (g.ps[s] > g.pa[k]) return;      // the lower triangle of shell pairs is computed, the upper one is its copy
     const Shell& A = g.orb[g.pa[k]];
     const Shell& U = g.orb[g.unit];
-    block_cart<LA, LB, LP>(A, U, C, acc);
+    block_cart<LA, LB, LP>(A, U, C, acc, true);
     block_to_sph<LA, LB, LP>(acc, g.c2s);
     const bool same = g.pa[k] == g.ps[s];
     for (int a = 0; a < nsA; ++a)

@@ -152,7 +152,11 @@ void gto_one_electron(int nbf, const bf_t* bf, int natm, const double* atm_xyz, 
 /* primitive-pair data: exponent sum, centre, Hermite coefficients per direction (t <= MAXLPAIR) times the contraction coefs */
 typedef struct { double p, P[3], Ex[MAXLPAIR + 1], Ey[MAXLPAIR + 1], Ez[MAXLPAIR + 1], c; int tx, ty, tz; } ppair_t;
 
-static int build_pairs(const bf_t* a, const bf_t* b, ppair_t* out) {
+/* top != 0 (an auxiliary function times the unit s function on its own centre): only the Hermite term of the highest order, t = l, is kept.  The callers
+ * contract the shell with a Cartesian -> solid-harmonic matrix, and S_lm(r) exp(-q r^2) = (2q)^-l S_lm(d/dC) exp(-q r^2) for a harmonic polynomial, so the
+ * lower-order terms sum to zero there.  Carrying them through would subtract Cartesian integrals that keep the R^-1 ... R^-l parts from one another to get a
+ * block that falls like R^-(l+1): for a far (g|g) block of 2e-6 that left 1e-10 of the block as rounding.  For s and p nothing changes. */
+static int build_pairs_x(const bf_t* a, const bf_t* b, ppair_t* out, int top) {
   int n = 0;
   for (int pa = 0; pa < a->nprim; ++pa)
     for (int pb = 0; pb < b->nprim; ++pb) {
@@ -167,9 +171,16 @@ static int build_pairs(const bf_t* a, const bf_t* b, ppair_t* out) {
         q->Ez[t] = Ecoef(a->lmn[2], b->lmn[2], t, a->ctr[2] - b->ctr[2], ea, eb);
       }
       q->c = a->co[pa] * b->co[pb];
+      if (top)
+        for (int t = 0; t <= MAXLPAIR; ++t) {
+          if (t != q->tx) q->Ex[t] = 0.0;
+          if (t != q->ty) q->Ey[t] = 0.0;
+          if (t != q->tz) q->Ez[t] = 0.0;
+        }
     }
   return n;
 }
+static int build_pairs(const bf_t* a, const bf_t* b, ppair_t* out) { return build_pairs_x(a, b, out, 0); }
 
 static double eri_from_pairs(const ppair_t* ab, int nab, const ppair_t* cd, int ncd) {
   double tot = 0.0;
@@ -231,7 +242,8 @@ void gto_eri_s1(int nbf, const bf_t* bf, double* eri) {
   free(pairs); free(npp);
 }
 
-/* 3-centre (ab|P) and 2-centre (P|Q) Coulomb integrals with an auxiliary set of basis functions (for DF tests) */
+/* 3-centre (ab|P) and 2-centre (P|Q) Coulomb integrals with an auxiliary set of basis functions (for DF tests).  For auxiliary shells with l >= 2 the values are
+ * meant for the Cartesian -> solid-harmonic contraction of integrals.py only (build_pairs_x, top): a single Cartesian d, f or g component is not the full integral. */
 void gto_eri_3c(int nbf, const bf_t* bf, int naux, const bf_t* aux, double* out /* nbf*nbf*naux */) {
   bf_t unit; memset(&unit, 0, sizeof(unit)); unit.nprim = 1; unit.ex[0] = 0.0; unit.co[0] = 1.0;
 #pragma omp parallel for schedule(dynamic)
@@ -241,7 +253,7 @@ void gto_eri_3c(int nbf, const bf_t* bf, int naux, const bf_t* aux, double* out 
       const int nab = build_pairs(&bf[i], &bf[j], ab);
       for (int P = 0; P < naux; ++P) {
         bf_t u = unit; memcpy(u.ctr, aux[P].ctr, sizeof(u.ctr));
-        const int ncd = build_pairs(&aux[P], &u, cd);
+        const int ncd = build_pairs_x(&aux[P], &u, cd, 1);
         const double v = eri_from_pairs(ab, nab, cd, ncd);
         out[((long)i * nbf + j) * naux + P] = out[((long)j * nbf + i) * naux + P] = v;
       }
@@ -254,10 +266,10 @@ void gto_eri_2c(int naux, const bf_t* aux, double* out /* naux*naux */) {
   for (int P = 0; P < naux; ++P) {
     ppair_t ab[MAXPRIM * MAXPRIM], cd[MAXPRIM * MAXPRIM];
     bf_t u = unit; memcpy(u.ctr, aux[P].ctr, sizeof(u.ctr));
-    const int nab = build_pairs(&aux[P], &u, ab);
+    const int nab = build_pairs_x(&aux[P], &u, ab, 1);
     for (int Q = 0; Q <= P; ++Q) {
       bf_t w = unit; memcpy(w.ctr, aux[Q].ctr, sizeof(w.ctr));
-      const int ncd = build_pairs(&aux[Q], &w, cd);
+      const int ncd = build_pairs_x(&aux[Q], &w, cd, 1);
       out[(long)P * naux + Q] = out[(long)Q * naux + P] = eri_from_pairs(ab, nab, cd, ncd);
     }
   }
@@ -273,7 +285,7 @@ void gto_eri_3c_pairs(int nbf, const bf_t* bf, int naux, const bf_t* aux, long n
   int* nauxp = (int*)malloc(sizeof(int) * (size_t)naux);
   for (int P = 0; P < naux; ++P) {
     bf_t u = unit; memcpy(u.ctr, aux[P].ctr, sizeof(u.ctr));
-    nauxp[P] = build_pairs(&aux[P], &u, auxp + (size_t)P * MAXPRIM);
+    nauxp[P] = build_pairs_x(&aux[P], &u, auxp + (size_t)P * MAXPRIM, 1);
   }
 #pragma omp parallel for schedule(dynamic)
   for (long x = 0; x < npairs; ++x) {

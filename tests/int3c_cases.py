@@ -1,6 +1,10 @@
 """Shared cases of the DF-integral tests (test_gpu_int3c.py on the device, test_int3c_hostlogic.py through the scalar twin): every check takes the
-library handle, so the same comparison against the host integral source runs on both."""
+library handle, so the same comparison runs on both -- against the host integral source, and against the independent quadrature reference of
+int3c_reference.py, whose cases and blocks are stored in golden/int3c_ref.npz (written by golden/make_golden_int3c_ref.py)."""
 import ctypes as C
+import functools
+import json
+from pathlib import Path
 
 import numpy as np
 
@@ -8,8 +12,13 @@ from quemb_amd import _lib
 from quemb_amd import integrals as I
 
 BAR = 1e-10                      # max |dev - host| <= BAR * max(1, max |host|): ten times inside the 1e-9 of the DF transform comparisons
+BAR_REL = 1e-10                  # max |dev - ref| <= BAR_REL * max |ref| per block against the quadrature reference: BAR, relative to the block itself
+MIN_BLOCK = 1e-8                 # every reference block has an element at least this large (asserted when the fixture is written)
 BOYS_SWITCH = 35.0               # series below, asymptotic form from here on (int3c_core.h)
-BOYS_POINTS = [0.0, 1e-12, 1e-6, 0.1, 1.0, 5.0, 15.0, 25.0, 30.0, 35.0, 60.0, 200.0, BOYS_SWITCH * (1 - 1e-9), BOYS_SWITCH * (1 + 1e-9), 34.5, 35.5]
+BOYS_POINTS = [0.0, 1e-12, 1e-6, 0.1, 1.0, 5.0, 15.0, 25.0, 30.0, 35.0, 60.0, 200.0, BOYS_SWITCH * (1 - 1e-9), BOYS_SWITCH * (1 + 1e-9), 34.5, 35.5,
+               745.0, 1e3, 1e4, 1e5]            # from 745 on exp(-x) underflows
+BOYS_M_MAX = 12                  # dev_boys accepts 0..12; the kernels use 0..8
+REF_NPZ = Path(__file__).resolve().parent / "golden" / "int3c_ref.npz"
 
 # 2-3 primitives per shell, exponents of ordinary valence / fitting functions
 _EXP = {0: ([2.3, 0.7, 0.25], [0.3, 0.5, 0.4]), 1: ([1.6, 0.45], [0.55, 0.6]), 2: ([1.2, 0.5, 0.3], [0.4, 0.5, 0.3]), 3: ([1.4, 0.6], [0.6, 0.5]),
@@ -27,29 +36,34 @@ def close(dev, host):
     return d, d <= BAR * max(1.0, float(np.abs(host).max()) if np.size(host) else 0.0)
 
 
-def boys_reference(xs, m_max=8):
-    from scipy import special as sp
-    m = np.arange(m_max + 1)
-    ref = np.empty((len(xs), m_max + 1))
-    for i, x in enumerate(xs):
-        ref[i] = 1.0 / (2 * m + 1) if x == 0 else 0.5 * x ** -(m + 0.5) * sp.gamma(m + 0.5) * sp.gammainc(m + 0.5, x)
-    return ref
+@functools.lru_cache(None)
+def boys_xs():
+    return np.concatenate([BOYS_POINTS, np.random.default_rng(20261017).uniform(0.0, 60.0, 200)])
 
 
-def check_boys(lib, on_device):
-    xs = np.concatenate([BOYS_POINTS, np.random.default_rng(20261017).uniform(0.0, 60.0, 200)])
-    out = np.empty((len(xs), 9))
+@functools.lru_cache(None)
+def boys_reference():
+    """F_0..F_12 at boys_xs() from mpmath's incomplete gamma function at 40 digits (computed once per process)."""
+    from int3c_reference import boys_mp
+    return boys_mp(boys_xs(), BOYS_M_MAX)
+
+
+def check_boys(lib, on_device, m_max=8):
+    """One call with this m_max: the series of the x < 35 branch starts at F[m_max], the upward recursion of the other branch ends there."""
+    xs = boys_xs()
+    out = np.empty((len(xs), m_max + 1))
     if on_device:
         dx = _lib.DeviceBuffer.from_numpy(xs, lib=lib); do = _lib.DeviceBuffer(out.size, lib=lib)
-        _lib.check(lib.qemb_op_boys(8, len(xs), dx.ptr, do.ptr), "qemb_op_boys", lib)
+        _lib.check(lib.qemb_op_boys(m_max, len(xs), dx.ptr, do.ptr), "qemb_op_boys", lib)
         out = do.numpy(out.shape)
         dx.free(); do.free()
     else:
-        _lib.check(lib.qemb_op_boys(8, len(xs), xs.ctypes.data, out.ctypes.data), "qemb_op_boys", lib)
-    rel = np.abs(out / boys_reference(xs) - 1.0)
-    print(f"boys: max relative deviation {rel.max():.2e} at x = {xs[np.unravel_index(rel.argmax(), rel.shape)[0]]!r}")
+        _lib.check(lib.qemb_op_boys(m_max, len(xs), xs.ctypes.data, out.ctypes.data), "qemb_op_boys", lib)
+    rel = np.abs(out / boys_reference()[:, : m_max + 1] - 1.0)
+    i, m = np.unravel_index(rel.argmax(), rel.shape)
+    print(f"boys m_max = {m_max}: max relative deviation {rel.max():.2e} at x = {xs[i]!r}, m = {m}")
     assert rel.max() <= 1e-13, rel.max(axis=1)
-    assert (out[0] == 1.0 / (2 * np.arange(9) + 1)).all()
+    assert (out[0] == 1.0 / (2 * np.arange(m_max + 1) + 1)).all()
 
 
 def class_block(lib, la, lb, lp, geom):
@@ -74,6 +88,118 @@ def check_class(lib, la, lb, lp):
         print(f"class ({la},{lb}|{lp}) {geom}: max |dev - host| = {d:.2e}, max |host| = {np.abs(host).max():.3e}")
         assert ok, (la, lb, lp, geom, d)
         assert np.abs(host).max() > 0 or geom == "one"      # (on one centre most classes vanish by parity: the zeros must come out as zeros too)
+
+
+# ---- the quadrature reference (golden/int3c_ref.npz) ---------------------------------------------------------------------------------------------
+@functools.lru_cache(None)
+def reference():
+    """(cases, arrays): the case definitions (name, family, kind "3c" / "2c", shells a, b, p as {l, ex, co, r}) and the npz with "ref/<name>" blocks."""
+    z = np.load(REF_NPZ)
+    return json.loads(str(z["cases"])), z
+
+
+def reference_cases(kind=None, family=None):
+    return [c for c in reference()[0] if kind in (None, c["kind"]) and family in (None, c["family"])]
+
+
+def reference_families():
+    return sorted({c["family"] for c in reference()[0]})
+
+
+def case_moles(case):
+    """3c: (mol with the shells a, b; aux with the shell p).  2c: (aux with the shells a, p,)."""
+    sh = lambda k: (case[k]["l"], case[k]["ex"], case[k]["co"])
+    if case["kind"] == "2c":
+        return (I.Mole([("H", case["a"]["r"]), ("C", case["p"]["r"])], basis={"H": [sh("a")], "C": [sh("p")]}, unit="Bohr"),)
+    return (I.Mole([("H", case["a"]["r"]), ("C", case["b"]["r"])], basis={"H": [sh("a")], "C": [sh("b")]}, unit="Bohr"),
+            I.Mole([("H", case["p"]["r"])], basis={"H": [sh("p")]}, unit="Bohr"))
+
+
+def case_block(case, lib=None):
+    """The block of a case from the host source (lib None), or from `lib`: qemb_op_int3c_class in the case's shell order, qemb_int2c2e for the metric."""
+    na = 2 * case["a"]["l"] + 1
+    if case["kind"] == "2c":
+        aux, = case_moles(case)
+        return (I.int2c2e(aux) if lib is None else I.int2c2e(aux, backend="hip", lib=lib))[:na, na:]
+    mol, aux = case_moles(case)
+    if lib is None:
+        return I.aux_e2(mol, aux)[:na, na:, :]
+    la, lb, lp = (case[k]["l"] for k in "abp")
+    out = np.empty((na, 2 * lb + 1, 2 * lp + 1))
+    rec = [mol.bfs[mol.shells[0][5]], mol.bfs[mol.shells[1][5]], aux.bfs[0]]
+    tab = I.c2s_table()
+    _lib.check(lib.qemb_op_int3c_class(la, lb, lp, C.addressof(rec[0]), C.addressof(rec[1]), C.addressof(rec[2]), tab.ctypes.data, out.ctypes.data),
+               "qemb_op_int3c_class", lib)
+    return out
+
+
+def rel_dev(got, ref):
+    return float(np.abs(got - ref).max()) / float(np.abs(ref).max())
+
+
+def check_class_against_reference(lib, case):
+    """lib None: the host source."""
+    ref = reference()[1]["ref/" + case["name"]]
+    got = case_block(case, lib)
+    assert got.shape == ref.shape and np.abs(ref).max() >= MIN_BLOCK
+    d = rel_dev(got, ref)
+    print(f"{case['name']}: max |got - ref| = {d:.2e} of max |ref| = {np.abs(ref).max():.3e}")
+    assert d <= BAR_REL, (case["name"], d)
+    return d
+
+
+def h3_layout_case():
+    """H3 / cc-pVDZ, N = 15, with an auxiliary basis whose shell counts per l (17, 13, 5) are coprime to the shell-pair counts per class (21, 18, 6) and no
+    multiple of a workgroup: the etb basis on the first two atoms and 1 s, 1 p, 3 d shells on the third (the etb basis on all three would give 24, 18, 3,
+    which share factors with the pair counts).  naux = 81."""
+    mol = I.Mole([["H", (0.0, 0.0, float(i))] for i in range(3)], basis="cc-pvdz")
+    etb = I.etb_auxbasis(mol)["H"]
+    third = [(0, [0.9], [1.0]), (1, [1.3], [1.0]), (2, [0.7], [1.0]), (2, [1.454], [1.0]), (2, [2.9], [1.0])]
+    aux = I.Mole([("H", mol.atom[0][1]), ("H", mol.atom[1][1]), ("C", mol.atom[2][1])], basis={"H": etb, "C": third}, unit="Bohr")
+    npair = {}                                                   # shell pairs I >= J per class (larger l, smaller l): what qemb_int3c2e launches
+    for i in range(mol.nbas):
+        for j in range(i + 1):
+            key = tuple(sorted((mol.shells[i][1], mol.shells[j][1]), reverse=True))
+            npair[key] = npair.get(key, 0) + 1
+    assert npair == {(1, 1): 6, (1, 0): 18, (0, 0): 21} and mol.nao == 15 and aux.nao == 81
+    naux_sh = [sum(1 for s in aux.shells if s[1] == l) for l in range(3)]
+    assert naux_sh == [17, 13, 5]
+    assert all(np.gcd(a, b) == 1 and a % 64 and b % 64 for a in npair.values() for b in naux_sh)
+    return mol, aux
+
+
+def check_layouts_on(lib):
+    """The three dense layouts from `lib` agree bit for bit, and the pqL one meets the reference block by block."""
+    mol, aux = h3_layout_case()
+    pql = I.aux_e2(mol, aux, backend="hip", lib=lib)
+    lpq = I._int3c_hip(mol, aux, "Lpq", lib=lib)
+    packed = I._int3c_hip(mol, aux, "packed", lib=lib)
+    assert (lpq == pql.transpose(2, 0, 1)).all()
+    il = np.tril_indices(mol.nao)
+    assert (packed == lpq[:, il[0], il[1]]).all()
+    check_h3_against_reference(pql)
+
+
+def check_h3_against_reference(j3):
+    """Every (shell pair | auxiliary shell) block of the H3 case that the fixture holds (largest element >= MIN_BLOCK), to BAR_REL of the block."""
+    mol, aux = h3_layout_case()
+    z = reference()[1]
+    ref, blocks = z["h3/ref"], z["h3/blocks"]
+    il = np.tril_indices(mol.nao)
+    got = j3[il[0], il[1]]
+    assert got.shape == ref.shape
+    lo, la = mol.ao_loc_nr(), aux.ao_loc_nr()
+    pair_shell = np.searchsorted(lo, il[0], side="right") - 1, np.searchsorted(lo, il[1], side="right") - 1
+    worst = 0.0
+    for i, j, k in blocks:
+        rows = (pair_shell[0] == i) & (pair_shell[1] == j)
+        r = ref[rows, la[k]: la[k + 1]]
+        assert np.abs(r).max() >= MIN_BLOCK
+        d = rel_dev(got[rows, la[k]: la[k + 1]], r)
+        worst = max(worst, d)
+        assert d <= BAR_REL, (i, j, k, d)
+    print(f"H3 / cc-pVDZ: {len(blocks)} blocks, worst deviation {worst:.2e} of a block's largest element")
+    assert len(blocks) == 1451                     # of 1575: the others hold no element of 3e-8
 
 
 def h8(basis="sto-3g", n=8):

@@ -1,6 +1,8 @@
 """DF integrals on the device (csrc/int3c_ops.hip) against the host integral source (csrc_host/gto_ints.c behind integrals.aux_e2 / int2c2e):
 the Boys function, every angular class at the smallest shape, whole molecules, the pair list, the in-place fill of a DF context and the
-from-geometry BE drivers with integral_backend="hip".  The cases are those of int3c_cases.py, shared with the scalar-twin tests."""
+from-geometry BE drivers with integral_backend="hip" -- and against the independent quadrature reference of int3c_reference.py (blocks stored in
+golden/int3c_ref.npz): every class in both shell orders, the metric classes, the stress families, the three dense layouts.  The Boys function is
+compared with mpmath for every m_max.  The cases are those of int3c_cases.py, shared with the scalar-twin tests."""
 import sys
 from pathlib import Path
 
@@ -14,8 +16,26 @@ import int3c_cases as cases
 pytestmark = pytest.mark.gpu
 
 
-def test_boys_function(qlib):
-    cases.check_boys(qlib, on_device=True)
+@pytest.mark.parametrize("m_max", range(cases.BOYS_M_MAX + 1))
+def test_boys_function(qlib, m_max):
+    cases.check_boys(qlib, on_device=True, m_max=m_max)
+
+
+@pytest.mark.parametrize("case", cases.reference_cases(family="class"), ids=lambda c: c["name"])
+def test_class_against_quadrature_reference(qlib, case):
+    """All 45 classes in both shell orders of qemb_op_int3c_class (l_a >= l_b and l_a <= l_b: both output orders of the block layout) and the 25
+    metric classes."""
+    cases.check_class_against_reference(qlib, case)
+
+
+@pytest.mark.parametrize("case", [c for c in cases.reference_cases() if c["family"] != "class"], ids=lambda c: c["name"])
+def test_stress_family_against_quadrature_reference(qlib, case):
+    cases.check_class_against_reference(qlib, case)
+
+
+def test_dense_layouts_on_the_device(qlib):
+    """pqL, Lpq and packed as kernels (the latter two split the item index by the pair count), on counts that are coprime."""
+    cases.check_layouts_on(qlib)
 
 
 @pytest.mark.parametrize("cls", cases.CLASSES, ids=lambda c: "%d%d%d" % c)

@@ -21,8 +21,29 @@ def hlib():
     return _lib.declare(C.CDLL(str(hc_build.build())))
 
 
-def test_boys_function(hlib):
-    cases.check_boys(hlib, on_device=False)
+@pytest.mark.parametrize("m_max", range(cases.BOYS_M_MAX + 1))
+def test_boys_function(hlib, m_max):
+    cases.check_boys(hlib, on_device=False, m_max=m_max)
+
+
+def _twin_subset():
+    """Two classes per stress family (the lowest and (2,2|4)), one low and one high class in each shell order, and three metric classes."""
+    keep = ("_00_0", "_22_4")
+    names = {"class_01_1", "class_10_1", "class_12_3", "class_21_3", "class_22_4", "class_m4_4", "class_m1_3", "class_m3_1"}
+    keep4 = ("_00_0", "_12_2")                             # T1e4 holds no (2,2|4): no such block reaches 1e-8 above T = 1e3
+    return [c for c in cases.reference_cases() if c["name"] in names or (c["family"] != "class" and c["name"].endswith(keep4 if c["family"] == "T1e4" else keep))]
+
+
+@pytest.mark.parametrize("case", _twin_subset(), ids=lambda c: c["name"])
+def test_against_quadrature_reference(hlib, case):
+    cases.check_class_against_reference(hlib, case)
+
+
+def test_twin_subset_covers_every_family():
+    got = {}
+    for c in _twin_subset():
+        got[c["family"]] = got.get(c["family"], 0) + 1
+    assert set(got) == set(cases.reference_families()) and all(n >= 2 for n in got.values()), got
 
 
 @pytest.mark.parametrize("cls", [(0, 1, 1), (2, 2, 4)], ids=lambda c: "%d%d%d" % c)
@@ -42,6 +63,7 @@ def test_layouts_agree(hlib):
     assert (lpq == pql.transpose(2, 0, 1)).all()
     il = np.tril_indices(mol.nao)
     assert (packed == lpq[:, il[0], il[1]]).all()
+    cases.check_layouts_on(hlib)          # and on coprime counts per class, with the pqL blocks against the quadrature reference
 
 
 def test_pair_list(hlib):

@@ -326,6 +326,23 @@ int qemb_df_create_empty(qemb_df_t* out);
 int qemb_df_set_ints_from_basis(qemb_df_t df, qemb_int_basis_t basis, qemb_int_basis_t auxbasis);
 int qemb_df_set_ints_semisparse_from_basis(qemb_df_t df, qemb_int_basis_t basis, qemb_int_basis_t auxbasis, int64_t n_unique, const int64_t* pairs,
                                            const int64_t* reach_ptr, const int32_t* reach_nu, const int64_t* reach_off);
+/* ---- the four-centre AO integrals (mu nu|la si) evaluated on the device from the basis (csrc/int4c.cpp, kernels csrc/int4c_ops.hip) ----
+ * What the reference takes from mf._eri (libcint) on its "in-core" branch (molbe/mbe.py:1036).  Contracted, real-spherical, orbital shells s p d, the handles of
+ * qemb_int_basis_create.  Only canonical shell quartets are evaluated; every element of the output is stored once, all images of an integral from one value:
+ * the same bits run to run, and the 8 images of the full tensor are bit-identical.
+ * qemb_int4c2e: sym = 8: 1-D npair (npair + 1) / 2 doubles, element ij (ij + 1) / 2 + kl for pair indices ij >= kl (PySCF's 8-fold form); sym = 4: [npair][npair];
+ *   sym = 1: [N]^4.  Another sym: QEMB_ERR_ARG.  out: host array, or a device pointer when out_on_device != 0.  thresh > 0: Schwarz screening -- Q_ab = sqrt(max (ab|ab))
+ *   per shell pair is evaluated on the device once per basis, a shell quartet with Q_ab Q_cd < thresh is stored as zeros; thresh = 0: nothing is skipped.
+ *   An orbital shell with l > 2: QEMB_ERR_UNSUPPORTED naming the shell.  Before anything is allocated the work space (and the output, when the call allocates it)
+ *   is compared with min(free device memory, the limit of qemb_int4c_mem_limit): QEMB_ERR_ALLOC with N in the message when it does not fit.
+ * qemb_int4c_mem_limit: the device bytes the four-centre calls of THIS basis may take (bytes < 0, the default: the free device memory alone).
+ * qemb_int4c_stats: the canonical shell quartets of the last fill of this basis and how many of them were screened (either pointer may be NULL).
+ * qemb_aoeri_from_basis: the 4-fold packed integrals written by the kernels into a resident qemb_aoeri_t -- the operand of qemb_ao2mo_dense without an N^4 (or any)
+ *   integral array on the host; the counterpart of qemb_df_set_ints_from_basis.  Same guard (output included) and refusals as qemb_int4c2e. */
+int qemb_int4c2e(qemb_int_basis_t basis, int sym, double thresh, double* out, int out_on_device);
+int qemb_int4c_mem_limit(qemb_int_basis_t basis, int64_t bytes);
+int qemb_int4c_stats(qemb_int_basis_t basis, int64_t* n_quartets, int64_t* n_screened);
+int qemb_aoeri_from_basis(qemb_int_basis_t basis, double thresh, qemb_aoeri_t* out);
 
 /* the resident 3-index factor of a fragment (qemb_frag_mo_route_used gives its naux), naux x npair(n) to the host; QEMB_ERR_ARG without one */
 int qemb_frag_get_df_factor(qemb_frag_t f, double* B_host);

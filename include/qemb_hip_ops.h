@@ -215,6 +215,10 @@ int qemb_frag_ccsd_export(qemb_frag_t f, const char* name, double* host, int64_t
  * la, lb <= 2, lP <= 4, c2s as qemb_int_basis_create; out_host[(a * (2 lb + 1) + b) * (2 lP + 1) + m] (all host pointers). */
 int qemb_op_boys(int m_max, int64_t n, const double* x, double* out);
 int qemb_op_int3c_class(int la, int lb, int lP, const void* bf_a, const void* bf_b, const void* bf_P, const double* c2s, double* out_host);
+/* Four-centre AO integrals (csrc/int4c_ops.hip).  qemb_op_int4c_class: one block (a b|c d) of explicit orbital shells in ANY order of angular momenta (the kernels run
+ * the canonical class l_a >= l_b, l_c >= l_d, bra pair class >= ket pair class; the block is put back into the caller's order) -- bf_*: the record of the first
+ * Cartesian component of each shell, l <= 2, c2s as qemb_int_basis_create; out_host[((a * (2 lb + 1) + b) * (2 lc + 1) + c) * (2 ld + 1) + d] (all host pointers). */
+int qemb_op_int4c_class(int la, int lb, int lc, int ld, const void* bf_a, const void* bf_b, const void* bf_c, const void* bf_d, const double* c2s, double* out_host);
 
 #ifdef __cplusplus
 }

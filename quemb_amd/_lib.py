@@ -219,6 +219,11 @@ def _declare(lib):
     f("qemb_df_create_empty", I, C.POINTER(c_vp))
     f("qemb_df_set_ints_from_basis", I, V, V, V)
     f("qemb_df_set_ints_semisparse_from_basis", I, V, V, V, L, P, P, P, P)
+    f("qemb_int4c2e", I, V, I, D, P, I)
+    f("qemb_int4c_mem_limit", I, V, L)
+    f("qemb_int4c_stats", I, V, C.POINTER(L), C.POINTER(L))
+    f("qemb_aoeri_from_basis", I, V, D, C.POINTER(c_vp))
+    f("qemb_op_int4c_class", I, I, I, I, I, P, P, P, P, P, P)
     f("qemb_op_boys", I, I, L, P, P)
     f("qemb_op_int3c_class", I, I, I, I, P, P, P, P, P)
     f("qemb_op_kdf_split", I, L, L, P, P)

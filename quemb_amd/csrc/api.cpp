@@ -14,6 +14,7 @@
 #include "ao2mo.h"
 #include "kdf.h"
 #include "int3c.h"
+#include "int4c.h"
 #include <mutex>
 #include <set>
 
@@ -262,6 +263,11 @@ int qemb_op_jacobi_svd(int64_t m, int64_t n, double* G, double* s, double* U, do
 int qemb_op_cholesky_lower(int64_t n, double* A) { return dev_cholesky_lower(n, A); }
 int qemb_op_tri_inverse_lower(int64_t n, const double* L, double* Linv) { return dev_tri_inverse_lower(n, L, Linv); }
 int qemb_op_boys(int m_max, int64_t n, const double* x, double* out) { QTRY(dev_boys(m_max, n, x, out)); return dev_sync(); }
+int qemb_op_int4c_class(int la, int lb, int lc, int ld, const void* bf_a, const void* bf_b, const void* bf_c, const void* bf_d, const double* c2s, double* out_host) {
+  const int l[4] = {la, lb, lc, ld};
+  const BfRecord* const rec[4] = {reinterpret_cast<const BfRecord*>(bf_a), reinterpret_cast<const BfRecord*>(bf_b), reinterpret_cast<const BfRecord*>(bf_c), reinterpret_cast<const BfRecord*>(bf_d)};
+  return int4c_block(l, rec, c2s, out_host);
+}
 int qemb_op_int3c_class(int la, int lb, int lP, const void* bf_a, const void* bf_b, const void* bf_P, const double* c2s, double* out_host) {
   return int3c_block(la, lb, lP, reinterpret_cast<const BfRecord*>(bf_a), reinterpret_cast<const BfRecord*>(bf_b), reinterpret_cast<const BfRecord*>(bf_P), c2s, out_host);
 }
@@ -661,6 +667,41 @@ int qemb_int2c2e(qemb_int_basis_t auxbasis, double* out, int out_on_device) {
   QTRY(d.alloc((int64_t)a->nao * a->nao));
   QTRY(int2c_fill(*a, d));
   return dev_d2h(out, d, sizeof(double) * a->nao * a->nao);
+}
+// ---- four-centre AO integrals from the basis (int4c.cpp) ----
+int qemb_int4c2e(qemb_int_basis_t basis, int sym, double thresh, double* out, int out_on_device) {
+  IntBasis* o = live_basis(basis, "qemb_int4c2e"); if (!o) return QEMB_ERR_ARG;
+  if (!out) { set_error("qemb_int4c2e: null output"); return QEMB_ERR_ARG; }
+  QTRY(int4c_guard(*o, sym, !out_on_device, "qemb_int4c2e"));
+  if (out_on_device) return int4c_fill(*o, sym, thresh, out);
+  const int64_t sz = int4c_out_words(o->nao, sym);
+  DBuf d;
+  QTRY(d.alloc(sz));
+  QTRY(int4c_fill(*o, sym, thresh, d));
+  return dev_d2h(out, d, sizeof(double) * sz);
+}
+int qemb_int4c_mem_limit(qemb_int_basis_t basis, int64_t bytes) {
+  IntBasis* o = live_basis(basis, "qemb_int4c_mem_limit"); if (!o) return QEMB_ERR_ARG;
+  o->int4c_mem_limit = bytes;
+  return QEMB_OK;
+}
+int qemb_int4c_stats(qemb_int_basis_t basis, int64_t* n_quartets, int64_t* n_screened) {
+  IntBasis* o = live_basis(basis, "qemb_int4c_stats"); if (!o) return QEMB_ERR_ARG;
+  if (n_quartets) *n_quartets = o->int4c_stats[0];
+  if (n_screened) *n_screened = o->int4c_stats[1];
+  return QEMB_OK;
+}
+int qemb_aoeri_from_basis(qemb_int_basis_t basis, double thresh, qemb_aoeri_t* out) {
+  IntBasis* o = live_basis(basis, "qemb_aoeri_from_basis"); if (!o) return QEMB_ERR_ARG;
+  if (!out) { set_error("qemb_aoeri_from_basis: bad arguments"); return QEMB_ERR_ARG; }
+  QTRY(int4c_guard(*o, 4, true, "qemb_aoeri_from_basis"));
+  AoEri* a = new AoEri();
+  a->N = o->nao;
+  int rc = a->s4.alloc(int4c_out_words(o->nao, 4));
+  if (!rc) rc = int4c_fill(*o, 4, thresh, a->s4);      // written in place by the kernels: the operand of ao2mo_dense
+  if (rc) { delete a; return rc; }
+  *out = a;
+  return QEMB_OK;
 }
 int qemb_df_create_empty(qemb_df_t* out) {
   if (!out) { set_error("qemb_df_create_empty: bad arguments"); return QEMB_ERR_ARG; }

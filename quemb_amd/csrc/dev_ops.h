@@ -351,6 +351,13 @@ int dev_boys(int m_max, int64_t n, const double* x, double* out);
 namespace int3c { struct ClassArgs; }
 int dev_int3c_class(int la, int lb, int lp, const int3c::ClassArgs& args);
 
+// ---- four-centre AO integrals from the basis (int4c.cpp; kernels in int4c_ops.hip, scalar restatement in int4c_ops_hostcheck.cpp; arithmetic in int4c_core.h) ----
+// pairs: per (shell pair, primitive pair) of one pair class la >= lb <= 2 the exponent sum, the centre and the Hermite expansion of the spherical products.
+// class: one launch per canonical class (la >= lb | lc >= ld), pair class of the bra >= that of the ket: every quartet of the two lists, each output element stored once.
+namespace int4c { struct PairArgs; struct ClassArgs; }
+int dev_int4c_pairs(int la, int lb, const int4c::PairArgs& args);
+int dev_int4c_class(int la, int lb, int lc, int ld, const int4c::ClassArgs& args);
+
 // ---- screening helpers of the semi-sparse DF transform ---------------------------------------------------------------
 // out[i] = (|x[i]| >= eps) ? 1 : 0
 int dev_threshold_mask(int64_t n, const double* x, double eps, double* out);

@@ -29,6 +29,11 @@ class IntBasis {
   // c2s: int3c::kC2sLen doubles, integrals.cart2sph(l) for l = 0..4; the matrices of l = 0, 1 must be the identity (QEMB_ERR_UNSUPPORTED otherwise)
   int create(int n_bf, const BfRecord* records, const double* c2s_host);
   const int3c::Shell* dev() const { return reinterpret_cast<const int3c::Shell*>(dshells.p); }
+  // the four-centre integrals of the basis (int4c.cpp): Schwarz factors sqrt(max (ab|ab)) per shell pair of each of the six pair classes (ss ps pp ds dp dd; filled
+  // by the first screened call), the device bytes a call may take (< 0: the free memory) and [canonical shell quartets, of which screened] of the last fill
+  std::vector<double> schwarz[6];
+  int64_t int4c_mem_limit = -1;
+  int64_t int4c_stats[2] = {0, 0};
 };
 
 enum { INT_LAYOUT_PQL = 0, INT_LAYOUT_LPQ = 1, INT_LAYOUT_PACKED = 2, INT_LAYOUT_PAIRS = 3 };

@@ -1,0 +1,25 @@
+// int4c.h -- the four-centre AO integrals (mu nu|lambda sigma) on the device from an uploaded basis (IntBasis, int3c.h): what Mole.eri_s1 obtains from the host
+// library and the reference from libcint (mf._eri, the operand of the "in-core" branch, molbe/mbe.py:1036).  The driver sorts the shell pairs into the six pair
+// classes, has the pair stage written once (dev_int4c_pairs) and issues one launch per canonical class of quartets (dev_int4c_class); the result goes straight
+// to the form the consumer reads: 8-fold packed (rdm2_eri_dot, RHF), 4-fold packed (AoEri, the operand of ao2mo_dense) or the full [N]^4 tensor.
+#pragma once
+#include <cstdint>
+#include "int3c.h"
+#include "int4c_core.h"
+
+namespace qemb {
+
+// device bytes the call allocates beside its output: pair stage, index lists, Schwarz factors
+int64_t int4c_work_bytes(const IntBasis& orb);
+// doubles of the output in form sym (8, 4 or 1); -1 for another sym
+int64_t int4c_out_words(int64_t N, int sym);
+// Compared with min(free device memory, orb.int4c_mem_limit) before anything is allocated: the work space, plus the output when the call allocates it.
+// QEMB_ERR_ALLOC with N in the message.  An orbital shell with l > 2: QEMB_ERR_UNSUPPORTED naming the shell.  who: the entry point, for the messages.
+int int4c_guard(const IntBasis& orb, int sym, bool with_output, const char* who);
+// (mu nu|la si) into out_dev in form sym.  thresh > 0: quartets with Q_ab Q_cd < thresh are stored as zeros (Q from the device, cached in the basis);
+// orb.int4c_stats receives the canonical shell quartets and how many of them were screened.
+int int4c_fill(IntBasis& orb, int sym, double thresh, double* out_dev);
+// one explicit block in the caller's shell order (qemb_op_int4c_class): out_host[((a * (2 lb + 1) + b) * (2 lc + 1) + c) * (2 ld + 1) + d]
+int int4c_block(const int l[4], const BfRecord* const rec[4], const double* c2s_host, double* out_host);
+
+}  // namespace qemb

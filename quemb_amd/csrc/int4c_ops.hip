@@ -1,0 +1,100 @@
+// int4c_ops.hip -- the four-centre AO Coulomb integrals (mu nu|lambda sigma) on the device (dev_ops.h: dev_int4c_pairs, dev_int4c_class; driver in int4c.cpp;
+// arithmetic in int4c_core.h, which reuses the Boys function, the Hermite coefficients and the R table of int3c_core.h).
+//
+// Two kernel families.  int4c_pair_kernel<la, lb> (6 instantiations): one thread per (shell pair, primitive pair) writes p, P and the Hermite expansion of
+// the pair's real-spherical products to a work buffer.  int4c_class_kernel<la, lb, lc, ld> (the 21 canonical classes la >= lb, lc >= ld, bra pair class >=
+// ket pair class): one thread per (shell quartet, ket component pair) -- a block is split over up to 25 threads, a thread carries at most 25 accumulators, the
+// 35 folded Hermite integrals G and the R table of the class (10 to 165 numbers; the compiler's per-class register and scratch figures are in DESIGN.md
+// section 4, "AO integrals on the device").  Every output element is stored once by plain stores.  l_a + l_b + l_c + l_d >= 4 runs in 64-thread workgroups.
+#include "hip_common.h"
+#include "int4c_core.h"
+
+namespace qemb {
+namespace {
+
+using namespace int4c;
+
+template <int LA, int LB>
+__global__ void __launch_bounds__(128) int4c_pair_kernel(const PairArgs g, const long long nitem) {
+  const long long item = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (item >= nitem) return;
+  pair_item<LA, LB>(g, item);
+}
+
+template <int LA, int LB, int LC, int LD>
+__global__ void __launch_bounds__(LA + LB + LC + LD >= 4 ? 64 : 128) int4c_class_kernel(const ClassArgs g, const long long nitem) {
+  const long long item = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (item >= nitem) return;
+  quartet_item<LA, LB, LC, LD>(g, item);
+}
+
+template <int LA, int LB>
+int launch_pairs(const PairArgs& g, hipStream_t st) {
+  const long long nitem = (long long)g.pairs.n * kPrimPairs, nb = (nitem + 127) / 128;
+  if (nb > 0x7fffffffLL) { set_error("dev_int4c_pairs: too many shell pairs in one class"); return QEMB_ERR_ARG; }
+  hipLaunchKernelGGL((int4c_pair_kernel<LA, LB>), dim3((unsigned)nb), dim3(128), 0, st, g, nitem);
+  HIP_TRY(hipGetLastError());
+  return QEMB_OK;
+}
+
+template <int LA, int LB, int LC, int LD>
+int launch_class(const ClassArgs& g, hipStream_t st) {
+  const long long nitem = class_items<LC, LD>(g);
+  const int bs = LA + LB + LC + LD >= 4 ? 64 : 128;
+  const long long nb = (nitem + bs - 1) / bs;
+  if (nb > 0x7fffffffLL) { set_error("dev_int4c_class: too many blocks in one class"); return QEMB_ERR_ARG; }
+  hipLaunchKernelGGL((int4c_class_kernel<LA, LB, LC, LD>), dim3((unsigned)nb), dim3(bs), 0, st, g, nitem);
+  HIP_TRY(hipGetLastError());
+  return QEMB_OK;
+}
+
+// the ket pair classes up to the bra's: only canonical classes are instantiated
+template <int LA, int LB>
+int launch_bra(int kc, const ClassArgs& g, hipStream_t st) {
+  constexpr int bc = pair_class(LA, LB);
+  switch (kc) {
+    case 0: return launch_class<LA, LB, 0, 0>(g, st);
+    case 1: if constexpr (bc >= 1) return launch_class<LA, LB, 1, 0>(g, st); break;
+    case 2: if constexpr (bc >= 2) return launch_class<LA, LB, 1, 1>(g, st); break;
+    case 3: if constexpr (bc >= 3) return launch_class<LA, LB, 2, 0>(g, st); break;
+    case 4: if constexpr (bc >= 4) return launch_class<LA, LB, 2, 1>(g, st); break;
+    case 5: if constexpr (bc >= 5) return launch_class<LA, LB, 2, 2>(g, st); break;
+  }
+  set_error("dev_int4c_class: not a canonical class");
+  return QEMB_ERR_UNSUPPORTED;
+}
+
+}  // namespace
+
+int dev_int4c_pairs(int la, int lb, const int4c::PairArgs& g) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (int rc = int4c_check_pairs(la, lb, g)) return rc;
+  if (g.pairs.n == 0) return QEMB_OK;
+  switch (pair_class(la, lb)) {
+    case 0: return launch_pairs<0, 0>(g, st);
+    case 1: return launch_pairs<1, 0>(g, st);
+    case 2: return launch_pairs<1, 1>(g, st);
+    case 3: return launch_pairs<2, 0>(g, st);
+    case 4: return launch_pairs<2, 1>(g, st);
+    default: return launch_pairs<2, 2>(g, st);
+  }
+}
+
+int dev_int4c_class(int la, int lb, int lc, int ld, const int4c::ClassArgs& g) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (int rc = int4c_check_class(la, lb, lc, ld, g)) return rc;
+  if (g.bra.n == 0 || g.ket.n == 0) return QEMB_OK;
+  const int kc = pair_class(lc, ld);
+  switch (pair_class(la, lb)) {
+    case 0: return launch_bra<0, 0>(kc, g, st);
+    case 1: return launch_bra<1, 0>(kc, g, st);
+    case 2: return launch_bra<1, 1>(kc, g, st);
+    case 3: return launch_bra<2, 0>(kc, g, st);
+    case 4: return launch_bra<2, 1>(kc, g, st);
+    default: return launch_bra<2, 2>(kc, g, st);
+  }
+}
+
+}  // namespace qemb

@@ -58,6 +58,17 @@ class AOEri:
         check(self.lib.qemb_aoeri_upload(self.nao, eri.ctypes.data, sym, C.byref(h)), "qemb_aoeri_upload", self.lib)
         self.h = h
 
+    @classmethod
+    def from_basis(cls, basis, thresh=0.0):
+        """The AO integrals evaluated on the device from an uploaded basis (integrals.DeviceBasis) and kept there, 4-fold packed (qemb_aoeri_from_basis): the
+        from-geometry form of the "in-core" operand -- no integral array exists on the host."""
+        self = cls.__new__(cls)
+        self.lib, self.nao = basis.lib, int(basis.nao)
+        h = c_vp()
+        check(self.lib.qemb_aoeri_from_basis(basis.h, float(thresh), C.byref(h)), "qemb_aoeri_from_basis", self.lib)
+        self.h = h
+        return self
+
     def transform(self, TA, frag=None, want_host=True):
         """(ij|kl) in the fragment embedding basis, 4-fold packed; optionally stored straight into `frag`."""
         TA = _arr(TA)

@@ -312,6 +312,28 @@ class DeviceBasis:
         _lib.check(self.lib.qemb_int_basis_create(mol.ncart, C.addressof(arr), C.sizeof(_BF), tab.ctypes.data, C.byref(h)), "qemb_int_basis_create", self.lib)
         self.h, self.nao = h, mol.nao
 
+    def eri(self, sym=8, thresh=0.0, out_dev=None):
+        """(mu nu|la si) from the device kernels (qemb_int4c2e) in form `sym`: 8 (1-D, PySCF's 8-fold packed form), 4 ([npair][npair]) or 1 ([N]^4).  out_dev: a
+        device pointer the integrals are left at (nothing is copied to the host; returns None); otherwise a host array."""
+        from . import _lib
+        if sym not in (1, 4, 8):
+            raise ValueError("sym must be 1, 4 or 8")
+        N = self.nao
+        npair = N * (N + 1) // 2
+        if out_dev is not None:
+            _lib.check(self.lib.qemb_int4c2e(self.h, int(sym), float(thresh), out_dev, 1), "qemb_int4c2e", self.lib)
+            return None
+        out = np.empty({8: (npair * (npair + 1) // 2,), 4: (npair, npair), 1: (N,) * 4}[sym])
+        _lib.check(self.lib.qemb_int4c2e(self.h, int(sym), float(thresh), out.ctypes.data, 0), "qemb_int4c2e", self.lib)
+        return out
+
+    def eri_stats(self):
+        """(canonical shell quartets, of which screened) of the last four-centre fill of this basis"""
+        n, z = C.c_int64(), C.c_int64()
+        from . import _lib
+        _lib.check(self.lib.qemb_int4c_stats(self.h, C.byref(n), C.byref(z)), "qemb_int4c_stats", self.lib)
+        return n.value, z.value
+
     def free(self):
         if getattr(self, "h", None):
             self.lib.qemb_int_basis_free(self.h)
@@ -413,10 +435,42 @@ def aux_e2_pairs(mol: Mole, auxmol: Mole, pairs, backend="host", lib=None):
     return res
 
 
-class RHF:
-    """Closed-shell RHF with DIIS in the AO basis (generalised eigenproblem through S^-1/2)."""
+def pack_eri(eri_s1, sym):
+    """The full [N]^4 tensor in PySCF's 4-fold ([npair][npair]) or 8-fold (1-D npair (npair + 1) / 2) packed form (pair index ij = i (i + 1) / 2 + j, i >= j)."""
+    if sym == 1:
+        return eri_s1
+    N = eri_s1.shape[0]
+    il = np.tril_indices(N)
+    s4 = eri_s1[il[0], il[1]][:, il[0], il[1]]
+    if sym == 4:
+        return np.ascontiguousarray(s4)
+    if sym == 8:
+        return np.ascontiguousarray(s4[np.tril_indices(s4.shape[0])])
+    raise ValueError("sym must be 1, 4 or 8")
 
-    def __init__(self, mol: Mole, conv_tol=1e-12, max_cycle=100):
+
+def eri(mol: Mole, sym=1, backend="host", thresh=0.0, lib=None):
+    """The four-centre AO integrals (mu nu|la si), mol.intor('int2e', aosym=...) of the reference's mean field: sym = 1 [N]^4, 4 [npair][npair], 8 1-D.
+    backend="host": Mole.eri_s1() packed; backend="hip": evaluated on the device (qemb_int4c2e), with Schwarz screening when thresh > 0 (a shell quartet with
+    Q_ab Q_cd < thresh is stored as zeros; the host source is never screened)."""
+    if sym not in (1, 4, 8):
+        raise ValueError("sym must be 1, 4 or 8")
+    if _backend(backend):
+        b = DeviceBasis(mol, lib)
+        try:
+            return b.eri(sym, thresh)
+        finally:
+            b.free()
+    return pack_eri(mol.eri_s1(), sym)
+
+
+class RHF:
+    """Closed-shell RHF with DIIS in the AO basis (generalised eigenproblem through S^-1/2).  integral_backend="hip": `_eri` comes from the device kernels in the
+    8-fold packed form (PySCF's own form of mf._eri); J and K are then contracted from the packed integrals."""
+
+    def __init__(self, mol: Mole, conv_tol=1e-12, max_cycle=100, integral_backend="host", lib=None):
+        self.integral_backend, self._lib = ("hip" if _backend(integral_backend) else "host"), lib
+        self._pk = None
         self.mol = mol
         self.conv_tol, self.max_cycle = conv_tol, max_cycle
         self.mo_coeff = self.mo_energy = self.mo_occ = None
@@ -440,7 +494,41 @@ class RHF:
 
     def _jk(self, dm):
         e = self._eri
+        if np.ndim(e) != 4:
+            return self._jk_packed(dm)
         return np.einsum("pqrs,rs->pq", e, dm, optimize=True), np.einsum("pqrs,qs->pr", e, dm, optimize=True)
+
+    def _jk_packed(self, dm):
+        """J and K from `_eri` in the 4-fold or 8-fold packed form: rows over the pairs p >= q, each row unpacked to a symmetric N x N image once."""
+        N = self.mol.nao
+        il = np.tril_indices(N)
+        npair = len(il[0])
+        if self._pk is None or self._pk[0] is not self._eri:
+            e = np.asarray(self._eri)
+            if e.size == npair * npair:
+                s4 = e.reshape(npair, npair)
+            elif e.size == npair * (npair + 1) // 2:
+                s4 = np.zeros((npair, npair))
+                s4[np.tril_indices(npair)] = e.ravel()
+                s4 = s4 + s4.T - np.diag(np.diag(s4))
+            else:
+                raise ValueError("RHF: `_eri` must be [N]^4, [npair][npair] or 1-D npair (npair + 1) / 2")
+            rows = np.zeros((npair, N, N))
+            rows[:, il[0], il[1]] = s4
+            rows[:, il[1], il[0]] = s4
+            self._pk = (self._eri, s4, rows)
+        _, s4, rows = self._pk
+        dm = np.asarray(dm)
+        dp = dm[il] + dm.T[il]
+        dp[il[0] == il[1]] *= 0.5
+        J = np.zeros((N, N))
+        J[il] = s4 @ dp
+        J = J + J.T - np.diag(np.diag(J))
+        K = np.zeros((N, N))
+        np.add.at(K, il[0], np.einsum("xrs,xs->xr", rows, dm[il[1]]))      # K[p, r] += (pq|rs) D[q, s]
+        off = il[0] != il[1]
+        np.add.at(K, il[1][off], np.einsum("xrs,xs->xr", rows[off], dm[il[0][off]]))
+        return J, K
 
     def get_veff(self, dm=None):
         dm = self.make_rdm1() if dm is None else dm
@@ -454,7 +542,7 @@ class RHF:
     def kernel(self):
         S = self.get_ovlp(); h = self._h
         if self._eri is None:
-            self._eri = self.mol.eri_s1()
+            self._eri = eri(self.mol, 8, "hip", lib=self._lib) if self.integral_backend == "hip" else self.mol.eri_s1()
         no = self.mol.nelectron // 2
         w, U = np.linalg.eigh(S)
         X = U / np.sqrt(w) @ U.T

@@ -47,7 +47,8 @@ class BE:
         if df_resident not in ("factor", "block"):
             raise ValueError("df_resident must be 'factor' or 'block'")
         self.df_resident = df_resident
-        # where the from-geometry DF transforms take (mu nu|P) and (P|Q) from: "host" (libqemb_gto) or "hip" (the device kernels; nothing of size naux N^2 on the host)
+        # where the from-geometry DF transforms take (mu nu|P) and (P|Q) from: "host" (libqemb_gto) or "hip" (the device kernels; nothing of size naux N^2 on the host).
+        # With int_transform="in-core-hip" and no `mf._eri`, "hip" evaluates (mu nu|la si) on the device from mf.mol ("host" keeps the reference's error)
         if integral_backend not in ("host", "hip"):
             raise ValueError("integral_backend must be 'host' or 'hip'")
         if integral_backend == "hip" and df_ints is not None:
@@ -146,12 +147,25 @@ class BE:
         """BE._eri_transform (mbe.py:1004-1113) with the device literals of eri_transform.HIP_INT_TRANSFORMS."""
         it = self.int_transform
         if it in ("in-core-hip", "in-core"):
-            if eri_ is None:
+            if eri_ is None and self.integral_backend != "hip":
                 raise ValueError("ERIs have to be available in memory.")      # mbe.py:1036
-            ao = et.AOEri(eri_, self.S.shape[0], lib=self.lib)
-            for I in idx:
-                ao.transform(self.Fobjs[I].TA, frag=self.Fobjs[I].dev, want_host=False)
-            ao.free()
+            if eri_ is None:
+                # from the geometry: (mu nu|la si) evaluated on the device and left there, 4-fold packed (csrc/int4c_ops.hip); no integral array on the host
+                from . import _lib
+                from .integrals import DeviceBasis
+                basis = DeviceBasis(self.mf.mol, self.lib or _lib.init())
+                try:
+                    ao = et.AOEri.from_basis(basis)
+                finally:
+                    basis.free()
+                self._eri_from_geometry = True
+            else:
+                ao = et.AOEri(eri_, self.S.shape[0], lib=self.lib)
+            try:
+                for I in idx:
+                    ao.transform(self.Fobjs[I].TA, frag=self.Fobjs[I].dev, want_host=False)
+            finally:
+                ao.free()
         elif it in ("int-direct-DF-hip", "sparse-DF-hip", "on-fly-sparse-DF-hip") and self._df_ints is None:
             # from the geometry alone, like the reference's "int-direct-DF" / "sparse-DF(-gpu)" / "on-fly-sparse-DF(-gpu)" branches
             # (mbe.py:1049-1110): auxiliary molecule, (P|Q), (mu nu|P) from the integral source, AO screening, device transform
@@ -302,8 +316,21 @@ class BE:
     def _eri_words(self):
         e = getattr(self.mf, "_eri", None)
         if e is None:
+            if getattr(self, "_eri_from_geometry", False):      # evaluated on the device in the 8-fold packed form (_ao_integrals)
+                npair = self.C.shape[0] * (self.C.shape[0] + 1) // 2
+                return npair * (npair + 1) // 2
             raise ValueError("ERIs have to be available in memory.")
         return int(np.size(e))
+
+    def _ao_integrals(self, lib, nao):
+        """the AO integrals the full-basis energies contract, on the device: `mf._eri` in the form it has, or -- a driver that evaluated its integrals from the
+        geometry (integral_backend="hip" without `mf._eri`) -- the 8-fold packed form from the device kernels.  On that route EVERY call evaluates the whole
+        integral set again (on top of the 4-fold packed evaluation of `_eri_transform`): nothing of size N^4 is kept between calls, on the host or on the device, at
+        the price of one more integral evaluation per compute_energy_full / rdm12_fullbasis(print_energy=True)"""
+        from . import rdm_full
+        if getattr(self.mf, "_eri", None) is None and getattr(self, "_eri_from_geometry", False):
+            return rdm_full.AOIntegrals.from_mol(lib, self.mf.mol, nao)
+        return rdm_full.AOIntegrals(lib, self.mf._eri, nao)
 
     def rdm12_fullbasis(self, return_ao=True, only_rdm2=False, return_lo=False, return_RDM2=True, print_energy=False):
         """The one- and two-particle density matrices of the whole system, the reference's `rdm1_fullbasis(only_rdm1=False)` (mbe.py:488-701) with its return
@@ -327,7 +354,7 @@ class BE:
             rdm2MO = rdm_full.reexpress(lib, acc, nao, CmoT_S) if not return_ao else None
             rdm2LO = rdm_full.reexpress(lib, acc, nao, CloT_S) if return_lo else None
             if want_energy:
-                ao = rdm_full.AOIntegrals(lib, self.mf._eri, nao)
+                ao = self._ao_integrals(lib, nao)
                 try:
                     E2 = 0.5 * ao.dot(acc)
                 finally:
@@ -374,7 +401,7 @@ class BE:
         KT = ao = None
         RDM2_full = E2 = EKumul_T = None
         try:
-            ao = rdm_full.AOIntegrals(lib, self.mf._eri, nao)
+            ao = self._ao_integrals(lib, nao)
             EKumul = ao.dot(K)
             if not approx_cumulant:
                 KT = self._rdm2_full_device(raw, True, eri_words=words)

@@ -131,6 +131,24 @@ class AOIntegrals:
         self.lib, self.nao, self.sym = lib, nao, eri_form(eri_, nao)
         self.buf = DeviceBuffer.from_numpy(np.asarray(eri_, dtype=np.float64).reshape(-1), lib=lib)
 
+    @classmethod
+    def from_mol(cls, lib, mol, nao):
+        """the 8-fold packed integrals evaluated on the device from the geometry (qemb_int4c2e) and left there"""
+        from .integrals import DeviceBasis
+        self = cls.__new__(cls)
+        npair = nao * (nao + 1) // 2
+        self.lib, self.nao, self.sym = lib, nao, 8
+        self.buf = DeviceBuffer(npair * (npair + 1) // 2, lib=lib)
+        b = DeviceBasis(mol, lib)
+        try:
+            b.eri(8, out_dev=self.buf.ptr)
+        except BaseException:
+            self.buf.free()
+            raise
+        finally:
+            b.free()
+        return self
+
     def dot(self, K):
         """sum eri[pqrs] K[pqrs] with K an [N]^4 device buffer (two-stage reduction in a fixed order)"""
         e = C.c_double()

@@ -343,6 +343,20 @@ int qemb_int4c2e(qemb_int_basis_t basis, int sym, double thresh, double* out, in
 int qemb_int4c_mem_limit(qemb_int_basis_t basis, int64_t bytes);
 int qemb_int4c_stats(qemb_int_basis_t basis, int64_t* n_quartets, int64_t* n_screened);
 int qemb_aoeri_from_basis(qemb_int_basis_t basis, double thresh, qemb_aoeri_t* out);
+/* ---- integral-direct J and K: the mean field of a basis whose N^4 integrals are never formed (csrc/int4c.cpp: int4c_jk_direct) ----
+ * What PySCF's direct SCF does with mf._eri = None.  J[mu,nu] = sum (mu nu|la si) D[la,si], K[mu,la] = sum (mu nu|la si) D[nu,si] for a SYMMETRIC dm (N x N, row-major):
+ * every canonical shell quartet is evaluated as in qemb_int4c2e and contracted with the density in the thread that evaluated it; nothing is stored.
+ * J or K may be NULL (that matrix is not formed), not both.  dm, J, K: host arrays, or device pointers when io_on_device != 0.
+ * The first call on a basis writes the pair stage and the Schwarz factors and keeps them on the device until qemb_int_basis_free; later calls (the SCF cycles)
+ * issue the class launches and O(N^2) passes only.  Device memory: pair stage, lists and O(N^2) -- qemb_int_jk_direct_bytes reports it before anything is
+ * allocated; the guard is that of qemb_int4c2e without an output term (qemb_int4c_mem_limit applies; QEMB_ERR_ALLOC with N in the message).
+ * thresh > 0: a quartet is skipped when Q_ab Q_cd < thresh or Q_ab Q_cd dmax < thresh, dmax the largest |D| over the six shell blocks of dm the quartet reads;
+ * thresh = 0 skips nothing; qemb_int4c_stats reports quartets and skipped quartets of the call.  thresh < 0, NULL dm, both outputs NULL: QEMB_ERR_ARG; an
+ * orbital shell with l > 2: QEMB_ERR_UNSUPPORTED.
+ * J and K are accumulated on one triangle with FP64 atomic adds and mirrored: symmetric to the bit, but -- unlike the stored forms of qemb_int4c2e -- the last
+ * bits depend on the arrival order of the adds and may differ from run to run. */
+int qemb_int_jk_direct(qemb_int_basis_t basis, const double* dm, double thresh, double* J, double* K, int io_on_device);
+int qemb_int_jk_direct_bytes(qemb_int_basis_t basis, int64_t* bytes);
 
 /* the resident 3-index factor of a fragment (qemb_frag_mo_route_used gives its naux), naux x npair(n) to the host; QEMB_ERR_ARG without one */
 int qemb_frag_get_df_factor(qemb_frag_t f, double* B_host);

@@ -223,6 +223,8 @@ def _declare(lib):
     f("qemb_int4c_mem_limit", I, V, L)
     f("qemb_int4c_stats", I, V, C.POINTER(L), C.POINTER(L))
     f("qemb_aoeri_from_basis", I, V, D, C.POINTER(c_vp))
+    f("qemb_int_jk_direct", I, V, P, D, P, P, I)
+    f("qemb_int_jk_direct_bytes", I, V, C.POINTER(L))
     f("qemb_op_int4c_class", I, I, I, I, I, P, P, P, P, P, P)
     f("qemb_op_boys", I, I, L, P, P)
     f("qemb_op_int3c_class", I, I, I, I, P, P, P, P, P)

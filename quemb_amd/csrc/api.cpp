@@ -691,6 +691,16 @@ int qemb_int4c_stats(qemb_int_basis_t basis, int64_t* n_quartets, int64_t* n_scr
   if (n_screened) *n_screened = o->int4c_stats[1];
   return QEMB_OK;
 }
+int qemb_int_jk_direct(qemb_int_basis_t basis, const double* dm, double thresh, double* J, double* K, int io_on_device) {
+  IntBasis* o = live_basis(basis, "qemb_int_jk_direct"); if (!o) return QEMB_ERR_ARG;
+  return int4c_jk_direct(*o, dm, thresh, J, K, io_on_device);
+}
+int qemb_int_jk_direct_bytes(qemb_int_basis_t basis, int64_t* bytes) {
+  IntBasis* o = live_basis(basis, "qemb_int_jk_direct_bytes"); if (!o) return QEMB_ERR_ARG;
+  if (!bytes) { set_error("qemb_int_jk_direct_bytes: bad arguments"); return QEMB_ERR_ARG; }
+  *bytes = int4c_jk_bytes(*o);
+  return QEMB_OK;
+}
 int qemb_aoeri_from_basis(qemb_int_basis_t basis, double thresh, qemb_aoeri_t* out) {
   IntBasis* o = live_basis(basis, "qemb_aoeri_from_basis"); if (!o) return QEMB_ERR_ARG;
   if (!out) { set_error("qemb_aoeri_from_basis: bad arguments"); return QEMB_ERR_ARG; }

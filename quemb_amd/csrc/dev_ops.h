@@ -357,6 +357,12 @@ int dev_int3c_class(int la, int lb, int lp, const int3c::ClassArgs& args);
 namespace int4c { struct PairArgs; struct ClassArgs; }
 int dev_int4c_pairs(int la, int lb, const int4c::PairArgs& args);
 int dev_int4c_class(int la, int lb, int lc, int ld, const int4c::ClassArgs& args);
+// jk_class: the digest form of a canonical class -- the same quartets, each unique integral contracted with the density into J and / or K (lower triangles,
+// accumulated with FP64 atomic adds: arrival order decides the last bits) instead of stored.  dmax: out[I * nshell + J] = max |D| over the block of shells I, J.
+namespace int4c { struct JkArgs; }
+namespace int3c { struct Shell; }
+int dev_int4c_jk_class(int la, int lb, int lc, int ld, const int4c::JkArgs& args);
+int dev_int4c_dmax(const int3c::Shell* sh, int nshell, int64_t N, const double* dm, double* out);
 
 // ---- screening helpers of the semi-sparse DF transform ---------------------------------------------------------------
 // out[i] = (|x[i]| >= eps) ? 1 : 0

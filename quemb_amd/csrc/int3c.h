@@ -3,6 +3,7 @@
 // pairs and auxiliary shells by angular momentum and issues one launch per class (dev_int3c_class); results go straight to the layout the consumer reads.
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <vector>
 #include "dev_ops.h"
 #include "int3c_core.h"
@@ -11,6 +12,7 @@
 namespace qemb {
 
 class DfContext;
+struct Int4cCache;      // int4c.cpp: what qemb_int_jk_direct keeps on the device between calls
 
 // the record integrals.py builds per Cartesian contracted function (`_BF`; csrc_host/gto_ints.c bf_t)
 struct BfRecord {
@@ -34,6 +36,8 @@ class IntBasis {
   std::vector<double> schwarz[6];
   int64_t int4c_mem_limit = -1;
   int64_t int4c_stats[2] = {0, 0};
+  // the direct J / K calls (int4c_jk_direct): pair lists, pair stage and Schwarz factors resident on the device from the first call to the end of the basis
+  std::shared_ptr<Int4cCache> jk_cache;
 };
 
 enum { INT_LAYOUT_PQL = 0, INT_LAYOUT_LPQ = 1, INT_LAYOUT_PACKED = 2, INT_LAYOUT_PAIRS = 3 };

@@ -8,6 +8,7 @@ namespace qemb {
 
 using int3c::Shell;
 using int4c::ClassArgs;
+using int4c::JkArgs;
 using int4c::PairArgs;
 using int4c::PairList;
 using int4c::kNPairClass;
@@ -104,6 +105,11 @@ int schwarz_factors(IntBasis& orb, const PairPlan& p, const DevicePlan& d) {
 
 }  // namespace
 
+struct Int4cCache {
+  PairPlan plan;
+  DevicePlan dev;
+};
+
 int64_t int4c_work_bytes(const IntBasis& orb) { return plan_of(orb).bytes(); }
 
 int64_t int4c_out_words(int64_t N, int sym) {
@@ -159,6 +165,87 @@ int int4c_fill(IntBasis& orb, int sym, double thresh, double* out) {
             if (orb.schwarz[cb][(size_t)i] * orb.schwarz[ck][(size_t)j] < thresh) ++orb.int4c_stats[1];
     }
   return dev_sync();      // the work buffers are released on return
+}
+
+namespace {
+int64_t jk_small_bytes(const IntBasis& orb) { return 8 * (3 * (int64_t)orb.nao * orb.nao + (int64_t)orb.nshell * orb.nshell) + 4096; }      // D, J, K, the shell-block table
+}  // namespace
+
+int64_t int4c_jk_bytes(const IntBasis& orb) { return int4c_work_bytes(orb) + jk_small_bytes(orb); }
+
+int int4c_jk_direct(IntBasis& orb, const double* dm, double thresh, double* J, double* K, int io_on_device) {
+  const char* who = "qemb_int_jk_direct";
+  if (!dm) { set_error(std::string(who) + ": null density"); return QEMB_ERR_ARG; }
+  if (!J && !K) { set_error(std::string(who) + ": J and K are both null"); return QEMB_ERR_ARG; }
+  if (!(thresh >= 0.0)) { set_error(std::string(who) + ": the screening threshold must be >= 0"); return QEMB_ERR_ARG; }
+  QTRY(check_orbital(orb, who));
+  // the guard of qemb_int4c2e without an output term; what a cached basis holds already is not asked of the free memory again
+  size_t free_b = 0, total_b = 0;
+  QTRY(dev_mem_info(&free_b, &total_b));
+  const double need = (double)int4c_jk_bytes(orb), fresh = orb.jk_cache ? (double)jk_small_bytes(orb) : need;
+  if ((orb.int4c_mem_limit >= 0 && need > (double)orb.int4c_mem_limit) || fresh > (double)free_b) {
+    const double room = orb.int4c_mem_limit >= 0 && (double)orb.int4c_mem_limit < (double)free_b ? (double)orb.int4c_mem_limit : (double)free_b;
+    set_error(std::string(who) + ": with N = " + std::to_string(orb.nao) + " the pair stage, the lists and the N x N matrices take " + std::to_string(need * 1e-9) +
+              " GB, more than the " + std::to_string(room * 1e-9) + " GB of device memory they may take");
+    return QEMB_ERR_ALLOC;
+  }
+  if (!orb.jk_cache) {      // first call on this basis: lists, pair stage, Schwarz factors -- kept
+    auto c = std::make_shared<Int4cCache>();
+    c->plan = plan_of(orb);
+    int rc = c->dev.build(c->plan, orb.dev(), orb.dc2s);
+    if (!rc) rc = schwarz_factors(orb, c->plan, c->dev);
+    if (!rc) {
+      std::vector<double> q;
+      for (int k = 0; k < kNPairClass; ++k) q.insert(q.end(), orb.schwarz[k].begin(), orb.schwarz[k].end());
+      rc = c->dev.dq.alloc((int64_t)q.size() + 1);
+      if (!rc && !q.empty()) rc = dev_h2d(c->dev.dq, q.data(), sizeof(double) * q.size());
+    }
+    if (rc) { dev_sync(); return rc; }
+    orb.jk_cache = c;
+  }
+  const DevicePlan& d = orb.jk_cache->dev;
+  const int64_t N = orb.nao, nsh = orb.nshell;
+  const bool screen = thresh > 0.0;
+  DBuf bD, bJ, bK, btab;
+  const double* dD = dm;
+  double *dJ = J, *dK = K;
+  if (!io_on_device) {
+    QTRY(bD.alloc(N * N)); QTRY(dev_h2d(bD, dm, sizeof(double) * N * N)); dD = bD;
+    if (J) { QTRY(bJ.alloc(N * N)); dJ = bJ; }
+    if (K) { QTRY(bK.alloc(N * N)); dK = bK; }
+  }
+  std::vector<double> tab;
+  if (screen) {
+    QTRY(btab.alloc(nsh * nsh));
+    QTRY(dev_int4c_dmax(orb.dev(), (int)nsh, N, dD, btab));
+    tab.resize((size_t)(nsh * nsh));
+    QTRY(dev_d2h(tab.data(), btab, sizeof(double) * tab.size()));      // for the census below
+  }
+  if (dJ) QTRY(dev_fill(dJ, N * N, 0.0));
+  if (dK) QTRY(dev_fill(dK, N * N, 0.0));
+  orb.int4c_stats[0] = orb.int4c_stats[1] = 0;
+  const PairPlan& p = orb.jk_cache->plan;
+  for (int cb = 0; cb < kNPairClass; ++cb)
+    for (int ck = 0; ck <= cb; ++ck) {
+      if (!d.n[cb] || !d.n[ck]) continue;
+      JkArgs g{};
+      g.sh = orb.dev(); g.data = d.data; g.bra = d.list(cb, screen); g.ket = d.list(ck, screen);
+      g.same = cb == ck; g.thresh = thresh; g.N = N; g.nshell = (int)nsh; g.dm = dD; g.dmax = screen ? btab.p : nullptr; g.J = dJ; g.K = dK;
+      if (int rc = dev_int4c_jk_class(kLa[cb], kLb[cb], kLa[ck], kLb[ck], g)) { dev_sync(); return rc; }
+      orb.int4c_stats[0] += g.same ? d.n[cb] * (d.n[cb] + 1) / 2 : d.n[cb] * d.n[ck];
+      if (screen)      // the census of qemb_int4c_stats: the decision of the items (int4c::jk_screened) repeated on the host, O(n_pairs^2) -- part of the call's time when thresh > 0
+        for (int64_t i = 0; i < d.n[cb]; ++i)
+          for (int64_t j = 0; j < (g.same ? i + 1 : d.n[ck]); ++j)
+            if (int4c::jk_screened(thresh, orb.schwarz[cb][(size_t)i], orb.schwarz[ck][(size_t)j], tab.data(), (int)nsh, p.a[cb][(size_t)i], p.b[cb][(size_t)i],
+                                   p.a[ck][(size_t)j], p.b[ck][(size_t)j])) ++orb.int4c_stats[1];
+    }
+  if (dJ) QTRY(dev_mirror_lower(N, dJ, N));
+  if (dK) QTRY(dev_mirror_lower(N, dK, N));
+  if (!io_on_device) {
+    if (J) QTRY(dev_d2h(J, dJ, sizeof(double) * N * N));
+    if (K) QTRY(dev_d2h(K, dK, sizeof(double) * N * N));
+  }
+  return dev_sync();
 }
 
 int int4c_block(const int l[4], const BfRecord* const rec[4], const double* c2s_host, double* out_host) {

@@ -19,6 +19,13 @@ int int4c_guard(const IntBasis& orb, int sym, bool with_output, const char* who)
 // (mu nu|la si) into out_dev in form sym.  thresh > 0: quartets with Q_ab Q_cd < thresh are stored as zeros (Q from the device, cached in the basis);
 // orb.int4c_stats receives the canonical shell quartets and how many of them were screened.
 int int4c_fill(IntBasis& orb, int sym, double thresh, double* out_dev);
+// Integral-direct J[mu,nu] = sum (mu nu|la si) D[la,si] and K[mu,la] = sum (mu nu|la si) D[nu,si] for a symmetric D: every canonical quartet is evaluated and
+// contracted in the thread that evaluated it (dev_int4c_jk_class); nothing of size N^4 exists.  The first call on a basis writes the pair stage and the Schwarz
+// factors and keeps them with the lists on the device (orb.jk_cache); later calls issue the class launches and the O(N^2) passes only.  J or K may be null.
+// thresh > 0 skips a quartet with Q_ab Q_cd < thresh or Q_ab Q_cd max|D| < thresh (max over the six shell blocks of D the quartet reads); orb.int4c_stats as
+// for int4c_fill.  The sums are accumulated with FP64 atomic adds: J and K are symmetric to the bit but not bit-reproducible from run to run.
+int64_t int4c_jk_bytes(const IntBasis& orb);      // device bytes of a call: pair stage, lists, Schwarz factors, the N x N matrices and the shell-block table
+int int4c_jk_direct(IntBasis& orb, const double* dm, double thresh, double* J, double* K, int io_on_device);
 // one explicit block in the caller's shell order (qemb_op_int4c_class): out_host[((a * (2 lb + 1) + b) * (2 lc + 1) + c) * (2 ld + 1) + d]
 int int4c_block(const int l[4], const BfRecord* const rec[4], const double* c2s_host, double* out_host);
 

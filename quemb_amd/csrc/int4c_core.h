@@ -122,12 +122,51 @@ inline int64_t class_items(const ClassArgs& g) {
   return (g.out == kDiag ? g.bra.n : g.bra.n * g.ket.n) * (nsph(LC) * nsph(LD));
 }
 
+// The primitive loops of one item: acc[ab] += (a b|c d) for the bra products ab0 <= ab < ab1 and the ket product cd, over every primitive quartet of the two
+// pairs (boff / koff: their first doubles in `data`).  Shared by the stored forms (quartet_item) and the digest form (quartet_jk_item).
+template <int LA, int LB, int LC, int LD>
+QEMB_I3_HD void quartet_acc(const Shell& A, const Shell& B, const Shell& C, const Shell& D, const double* data, int64_t boff, int64_t koff, int cd, int ab0, int ab1,
+                            double* acc) {
+  constexpr int LAB = LA + LB, LCD = LC + LD, L = LAB + LCD, nhAB = nherm(LAB), nhCD = nherm(LCD);
+  constexpr double kPref = 34.98683665524972497;      // 2 pi^(5/2)
+  const int npab = A.nprim * B.nprim, npcd = C.nprim * D.nprim;
+  double R[nherm(L)], G[nhAB];
+  for (int ib = 0; ib < npab; ++ib) {
+    const double* eb = data + boff + (int64_t)ib * pair_stride(LA, LB);
+    const double p = eb[0];
+    for (int ik = 0; ik < npcd; ++ik) {
+      const double* ek = data + koff + (int64_t)ik * pair_stride(LC, LD);
+      const double q = ek[0];
+      const double PQ[3] = {eb[1] - ek[1], eb[2] - ek[2], eb[3] - ek[3]};
+      int3c::rtable<L>(p * q / (p + q), PQ, R);
+      const double pref = kPref / (p * q * sqrt(p + q));
+      const double* ecd = ek + 4 + cd * nhCD;
+      for (int t = 0; t <= LAB; ++t)
+        for (int u = 0; u <= LAB - t; ++u)
+          for (int v = 0; v <= LAB - t - u; ++v) {
+            double s = 0.0;
+            for (int t2 = 0; t2 <= LCD; ++t2)
+              for (int u2 = 0; u2 <= LCD - t2; ++u2)
+                for (int v2 = 0; v2 <= LCD - t2 - u2; ++v2) {
+                  const double term = ecd[hidx(t2, u2, v2)] * R[hidx(t + t2, u + u2, v + v2)];
+                  s += ((t2 + u2 + v2) & 1) ? -term : term;
+                }
+            G[hidx(t, u, v)] = pref * s;
+          }
+      for (int ab = ab0; ab < ab1; ++ab) {
+        const double* e = eb + 4 + ab * nhAB;
+        double s = 0.0;
+        for (int hh = 0; hh < nhAB; ++hh) s += e[hh] * G[hh];
+        acc[ab] += s;
+      }
+    }
+  }
+}
+
 // Every element of `dst` that belongs to the item is written exactly once, by plain stores, all images of an integral from one value: the same bits run to run.
 template <int LA, int LB, int LC, int LD>
 QEMB_I3_HD void quartet_item(const ClassArgs& g, int64_t item) {
-  constexpr int LAB = LA + LB, LCD = LC + LD, L = LAB + LCD, nhAB = nherm(LAB), nhCD = nherm(LCD);
   constexpr int nsA = nsph(LA), nsB = nsph(LB), nsC = nsph(LC), nsD = nsph(LD), nab = nsA * nsB, ncd = nsC * nsD;
-  constexpr double kPref = 34.98683665524972497;      // 2 pi^(5/2)
   const int cd = (int)(item % ncd);
   const int64_t qi = item / ncd;
   const int64_t kb = g.out == kDiag ? qi : qi / g.ket.n, kk = g.out == kDiag ? qi : qi % g.ket.n;
@@ -144,40 +183,7 @@ QEMB_I3_HD void quartet_item(const ClassArgs& g, int64_t item) {
   const bool screened = g.thresh > 0.0 && g.bra.q && g.ket.q && g.bra.q[kb] * g.ket.q[kk] < g.thresh;
   const int abd = (c % nsA) * nsB + (d % nsB);                                      // kDiag (LA == LC, LB == LD): the one bra product the item stores, (c d|c d)
   const int ab0 = g.out == kDiag ? abd : 0, ab1 = g.out == kDiag ? abd + 1 : nab;
-  if (!screened) {
-    const int npab = A.nprim * B.nprim, npcd = C.nprim * D.nprim;
-    double R[nherm(L)], G[nhAB];
-    for (int ib = 0; ib < npab; ++ib) {
-      const double* eb = g.data + g.bra.off[kb] + (int64_t)ib * pair_stride(LA, LB);
-      const double p = eb[0];
-      for (int ik = 0; ik < npcd; ++ik) {
-        const double* ek = g.data + g.ket.off[kk] + (int64_t)ik * pair_stride(LC, LD);
-        const double q = ek[0];
-        const double PQ[3] = {eb[1] - ek[1], eb[2] - ek[2], eb[3] - ek[3]};
-        int3c::rtable<L>(p * q / (p + q), PQ, R);
-        const double pref = kPref / (p * q * sqrt(p + q));
-        const double* ecd = ek + 4 + cd * nhCD;
-        for (int t = 0; t <= LAB; ++t)
-          for (int u = 0; u <= LAB - t; ++u)
-            for (int v = 0; v <= LAB - t - u; ++v) {
-              double s = 0.0;
-              for (int t2 = 0; t2 <= LCD; ++t2)
-                for (int u2 = 0; u2 <= LCD - t2; ++u2)
-                  for (int v2 = 0; v2 <= LCD - t2 - u2; ++v2) {
-                    const double term = ecd[hidx(t2, u2, v2)] * R[hidx(t + t2, u + u2, v + v2)];
-                    s += ((t2 + u2 + v2) & 1) ? -term : term;
-                  }
-              G[hidx(t, u, v)] = pref * s;
-            }
-        for (int ab = ab0; ab < ab1; ++ab) {
-          const double* e = eb + 4 + ab * nhAB;
-          double s = 0.0;
-          for (int hh = 0; hh < nhAB; ++hh) s += e[hh] * G[hh];
-          acc[ab] += s;
-        }
-      }
-    }
-  }
+  if (!screened) quartet_acc<LA, LB, LC, LD>(A, B, C, D, g.data, g.bra.off[kb], g.ket.off[kk], cd, ab0, ab1, acc);
   if (g.out == kDiag) {      // LA == LC, LB == LD
     g.dst[kb * ncd + cd] = acc[abd];
     return;
@@ -219,6 +225,138 @@ QEMB_I3_HD void quartet_item(const ClassArgs& g, int64_t item) {
     }
 }
 
+// ---- the digest form: J and K from the quartets, no integral stored (qemb_int_jk_direct) -----------------------------------------------------------
+// One item is the item of quartet_item: (shell quartet, ket component pair c d), the same primitive loops (quartet_acc) and the same filters (sameAB / sameCD /
+// diag), so every unique integral v = (mu nu|la si) -- one per orbit of the 8 index permutations -- is met exactly once.  Its orbit contributes to
+//   J[p,q] = sum_rs (pq|rs) D[r,s]        K[p,r] = sum_qs (pq|rs) D[q,s]
+// the sum over its DISTINCT images.  The 8 permutations (mu <-> nu, la <-> si, bra <-> ket) form a group; the images of v are the cosets of its stabiliser,
+// whose order is 2^(number of coincidences among mu = nu, la = si, (mu nu) = (la si)) -- mu = si with nu = la cannot hold unless all four are equal.  So
+// applying ALL 8 permutations with the scaled value
+//   v' = v  *  (mu = nu ? 1/2 : 1)  *  (la = si ? 1/2 : 1)  *  (ij = kl ? 1/2 : 1)
+// counts every distinct image once.  With D symmetric the 8 terms are
+//   J_full[mu,nu] += 2 v' D[la,si]    J_full[nu,mu] += 2 v' D[la,si]    J_full[la,si] += 2 v' D[mu,nu]    J_full[si,la] += 2 v' D[mu,nu]
+//   K = T + T^T,   T[mu,la] += v' D[nu,si]    T[nu,la] += v' D[mu,si]    T[mu,si] += v' D[nu,la]    T[nu,si] += v' D[mu,la]
+// Only the lower triangle L (p >= r) is accumulated and mirrored afterwards (dev_mirror_lower), so J and K are symmetric to the bit:
+//   J:  L[max(mu,nu), min] += (mu = nu ? 4 : 2) v' D[la,si],   L[max(la,si), min] += (la = si ? 4 : 2) v' D[mu,nu]
+//       -- with the factors of v' that is  w_kl v D[la,si]  and  w_ij v D[mu,nu]  (w = 2 off the diagonal of the pair, 1 on it), halved each when ij = kl,
+//       where both land on one element
+//   K:  a term x for T[p,r] becomes  L[max(p,r), min] += (p = r ? 2 : 1) x        (K[p,p] = 2 T[p,p];  K[p,r] = T[p,r] + T[r,p])
+// e.g. mu = nu = la = si: v' = v / 8, J: 2 adds of 4 v' D = v D; K: 4 terms of 2 v' D = v D.
+// Inside the item everything that shares a destination is summed first: J[la,si] gets one add (sum over a b), the K rows (mu, la), (mu, si) one add per a
+// (summed over b), (nu, la), (nu, si) one per b (summed over a): nab + 1 + 2 (nsA + nsB) adds per item, through QEMB_JK_ADD -- an FP64 atomic add on the
+// device (the sums then depend on arrival order: not bit-reproducible from run to run), a plain += in the scalar restatement.
+#ifndef QEMB_JK_ADD
+#if defined(__HIP_DEVICE_COMPILE__)
+#define QEMB_JK_ADD(p, x) unsafeAtomicAdd((p), (x))
+#else
+#define QEMB_JK_ADD(p, x) (*(p) += (x))
+#endif
+#endif
+
+struct JkArgs {
+  const Shell* sh;
+  const double* data;          // what pair_item wrote
+  PairList bra, ket;
+  int same;                    // as ClassArgs
+  double thresh;               // > 0 with bra.q / ket.q: a quartet with q_bra q_ket < thresh, or q_bra q_ket dmax < thresh, is skipped
+  int64_t N;
+  int nshell;
+  const double* dm;            // [N][N], symmetric
+  const double* dmax;          // [nshell][nshell] max |D| per shell block (dmax_item), or null: the bound is not weighted
+  double* J;                   // [N][N] lower triangle accumulated (zeroed by the caller, mirrored afterwards); null: not formed
+  double* K;                   // likewise
+};
+
+template <int LC, int LD>
+inline int64_t jk_items(const JkArgs& g) { return g.bra.n * g.ket.n * (nsph(LC) * nsph(LD)); }
+
+// max |D| over the block of shells (I, J): one item per ordered shell pair
+QEMB_I3_HD void dmax_item(const Shell* sh, int nshell, int64_t N, const double* dm, double* out, int64_t item) {
+  const Shell& A = sh[item / nshell];
+  const Shell& B = sh[item % nshell];
+  double m = 0.0;
+  for (int a = 0; a < 2 * A.l + 1; ++a)
+    for (int b = 0; b < 2 * B.l + 1; ++b) m = fmax(m, fabs(dm[(A.ao0 + a) * N + B.ao0 + b]));
+  out[item] = m;
+}
+
+// the screening decision of one quartet (shells ia, ib | ic, id with Schwarz factors qb, qk): shared by the items and by the census of the driver
+QEMB_I3_HD bool jk_screened(double thresh, double qb, double qk, const double* dmax, int nshell, int ia, int ib, int ic, int id) {
+  if (!(thresh > 0.0)) return false;
+  const double qq = qb * qk;
+  if (qq < thresh) return true;
+  if (!dmax) return false;
+  double m = fmax(dmax[ic * nshell + id], dmax[ia * nshell + ib]);
+  m = fmax(m, fmax(dmax[ib * nshell + id], dmax[ib * nshell + ic]));
+  m = fmax(m, fmax(dmax[ia * nshell + id], dmax[ia * nshell + ic]));
+  return qq * m < thresh;
+}
+
+QEMB_I3_HD void jk_add_lower(double* M, int64_t N, int64_t p, int64_t r, double x) {
+  if (x == 0.0) return;
+  QEMB_JK_ADD(M + (p >= r ? p * N + r : r * N + p), p == r ? 2.0 * x : x);
+}
+
+template <int LA, int LB, int LC, int LD>
+QEMB_I3_HD void quartet_jk_item(const JkArgs& g, int64_t item) {
+  constexpr int nsA = nsph(LA), nsB = nsph(LB), nsD = nsph(LD), nab = nsA * nsB, ncd = nsph(LC) * nsD;
+  const int cd = (int)(item % ncd);
+  const int64_t qi = item / ncd;
+  const int64_t kb = qi / g.ket.n, kk = qi % g.ket.n;
+  if (g.same && kk > kb) return;
+  const int c = cd / nsD, d = cd % nsD;
+  const int ia = g.bra.a[kb], ib = g.bra.b[kb], ic = g.ket.a[kk], id = g.ket.b[kk];
+  const bool sameAB = ia == ib, sameCD = ic == id, diag = g.same && kb == kk;
+  if (sameCD && d > c) return;
+  if (g.bra.q && g.ket.q && jk_screened(g.thresh, g.bra.q[kb], g.ket.q[kk], g.dmax, g.nshell, ia, ib, ic, id)) return;
+  const Shell& A = g.sh[ia];
+  const Shell& B = g.sh[ib];
+  const Shell& C = g.sh[ic];
+  const Shell& D = g.sh[id];
+  double acc[nab];
+  for (int k = 0; k < nab; ++k) acc[k] = 0.0;
+  quartet_acc<LA, LB, LC, LD>(A, B, C, D, g.data, g.bra.off[kb], g.ket.off[kk], cd, 0, nab, acc);
+  const int64_t N = g.N;
+  const int64_t la = C.ao0 + c, si = D.ao0 + d;
+  const int64_t kl = la >= si ? la * (la + 1) / 2 + si : si * (si + 1) / 2 + la;
+  const double* Dl = g.dm + la * N;
+  const double* Ds = g.dm + si * N;
+  const double fcd = la == si ? 0.5 : 1.0, dls = Dl[si];
+  double jcd = 0.0, kbl[nsB], kbs[nsB];
+  for (int b = 0; b < nsB; ++b) kbl[b] = kbs[b] = 0.0;
+  for (int a = 0; a < nsA; ++a) {
+    const int64_t mu = A.ao0 + a;
+    double kal = 0.0, kas = 0.0;
+    for (int b = 0; b < nsB; ++b) {
+      if (sameAB && b > a) continue;
+      const int64_t nu = B.ao0 + b;
+      const int64_t ij = mu >= nu ? mu * (mu + 1) / 2 + nu : nu * (nu + 1) / 2 + mu;
+      if (diag && kl > ij) continue;
+      const double v = acc[a * nsB + b] * (fcd * (mu == nu ? 0.5 : 1.0) * (ij == kl ? 0.5 : 1.0));      // v'
+      if (g.J) {
+        jk_add_lower(g.J, N, mu, nu, 2.0 * v * dls);
+        jcd += v * g.dm[mu * N + nu];
+      }
+      if (g.K) {
+        kal += v * Ds[nu];          // T[mu,la] += v' D[nu,si]
+        kas += v * Dl[nu];          // T[mu,si] += v' D[nu,la]
+        kbl[b] += v * Ds[mu];       // T[nu,la] += v' D[mu,si]
+        kbs[b] += v * Dl[mu];       // T[nu,si] += v' D[mu,la]
+      }
+    }
+    if (g.K) {
+      jk_add_lower(g.K, N, mu, la, kal);
+      jk_add_lower(g.K, N, mu, si, kas);
+    }
+  }
+  if (g.J) jk_add_lower(g.J, N, la, si, 2.0 * jcd);
+  if (g.K)
+    for (int b = 0; b < nsB; ++b) {
+      jk_add_lower(g.K, N, B.ao0 + b, la, kbl[b]);
+      jk_add_lower(g.K, N, B.ao0 + b, si, kbs[b]);
+    }
+}
+
 }  // namespace int4c
 
 // argument checks shared by the device layer and its scalar restatement
@@ -241,6 +379,17 @@ inline int int4c_check_class(int la, int lb, int lc, int ld, const int4c::ClassA
   if ((g.same && !same_class) || (g.out == kDiag && !g.same)) { set_error("dev_int4c_class: one list on both sides needs equal pair classes"); return QEMB_ERR_ARG; }
   if (g.bra.n < 0 || g.ket.n < 0 || !g.sh || !g.data || !g.dst || !g.bra.a || !g.bra.b || !g.bra.off || !g.ket.a || !g.ket.b || !g.ket.off ||
       (g.out != kBlock && g.out != kDiag && g.N <= 0)) { set_error("dev_int4c_class: bad arguments"); return QEMB_ERR_ARG; }
+  return 0;
+}
+inline int int4c_check_jk(int la, int lb, int lc, int ld, const int4c::JkArgs& g) {
+  using namespace int4c;
+  if (la < 0 || la > kMaxLOrb || lb < 0 || lb > la || lc < 0 || lc > kMaxLOrb || ld < 0 || ld > lc || pair_class(lc, ld) > pair_class(la, lb)) {
+    set_error("dev_int4c_jk_class: not a canonical angular class (" + std::to_string(la) + "," + std::to_string(lb) + "|" + std::to_string(lc) + "," + std::to_string(ld) + ")");
+    return QEMB_ERR_UNSUPPORTED;
+  }
+  if (g.same && !(la == lc && lb == ld)) { set_error("dev_int4c_jk_class: one list on both sides needs equal pair classes"); return QEMB_ERR_ARG; }
+  if (g.bra.n < 0 || g.ket.n < 0 || !g.sh || !g.data || !g.dm || (!g.J && !g.K) || !g.bra.a || !g.bra.b || !g.bra.off || !g.ket.a || !g.ket.b || !g.ket.off || g.N <= 0 ||
+      g.nshell <= 0) { set_error("dev_int4c_jk_class: bad arguments"); return QEMB_ERR_ARG; }
   return 0;
 }
 

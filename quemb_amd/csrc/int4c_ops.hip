@@ -6,6 +6,8 @@
 // ket pair class): one thread per (shell quartet, ket component pair) -- a block is split over up to 25 threads, a thread carries at most 25 accumulators, the
 // 35 folded Hermite integrals G and the R table of the class (10 to 165 numbers; the compiler's per-class register and scratch figures are in DESIGN.md
 // section 4, "AO integrals on the device").  Every output element is stored once by plain stores.  l_a + l_b + l_c + l_d >= 4 runs in 64-thread workgroups.
+// int4c_jk_kernel<la, lb, lc, ld> is the digest form of the class kernel (dev_int4c_jk_class): the same items and primitive loops, the unique integrals
+// contracted with the density into the lower triangles of J and K by FP64 atomic adds instead of stored ("Integral-direct J and K").
 #include "hip_common.h"
 #include "int4c_core.h"
 
@@ -28,6 +30,19 @@ __global__ void __launch_bounds__(LA + LB + LC + LD >= 4 ? 64 : 128) int4c_class
   quartet_item<LA, LB, LC, LD>(g, item);
 }
 
+template <int LA, int LB, int LC, int LD>
+__global__ void __launch_bounds__(LA + LB + LC + LD >= 4 ? 64 : 128) int4c_jk_kernel(const JkArgs g, const long long nitem) {
+  const long long item = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (item >= nitem) return;
+  quartet_jk_item<LA, LB, LC, LD>(g, item);
+}
+
+__global__ void __launch_bounds__(128) int4c_dmax_kernel(const Shell* sh, const int nshell, const long long N, const double* dm, double* out) {
+  const long long item = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (item >= (long long)nshell * nshell) return;
+  dmax_item(sh, nshell, N, dm, out, item);
+}
+
 template <int LA, int LB>
 int launch_pairs(const PairArgs& g, hipStream_t st) {
   const long long nitem = (long long)g.pairs.n * kPrimPairs, nb = (nitem + 127) / 128;
@@ -46,6 +61,32 @@ int launch_class(const ClassArgs& g, hipStream_t st) {
   hipLaunchKernelGGL((int4c_class_kernel<LA, LB, LC, LD>), dim3((unsigned)nb), dim3(bs), 0, st, g, nitem);
   HIP_TRY(hipGetLastError());
   return QEMB_OK;
+}
+
+template <int LA, int LB, int LC, int LD>
+int launch_jk(const JkArgs& g, hipStream_t st) {
+  const long long nitem = jk_items<LC, LD>(g);
+  const int bs = LA + LB + LC + LD >= 4 ? 64 : 128;
+  const long long nb = (nitem + bs - 1) / bs;
+  if (nb > 0x7fffffffLL) { set_error("dev_int4c_jk_class: too many blocks in one class"); return QEMB_ERR_ARG; }
+  hipLaunchKernelGGL((int4c_jk_kernel<LA, LB, LC, LD>), dim3((unsigned)nb), dim3(bs), 0, st, g, nitem);
+  HIP_TRY(hipGetLastError());
+  return QEMB_OK;
+}
+
+template <int LA, int LB>
+int launch_jk_bra(int kc, const JkArgs& g, hipStream_t st) {
+  constexpr int bc = pair_class(LA, LB);
+  switch (kc) {
+    case 0: return launch_jk<LA, LB, 0, 0>(g, st);
+    case 1: if constexpr (bc >= 1) return launch_jk<LA, LB, 1, 0>(g, st); break;
+    case 2: if constexpr (bc >= 2) return launch_jk<LA, LB, 1, 1>(g, st); break;
+    case 3: if constexpr (bc >= 3) return launch_jk<LA, LB, 2, 0>(g, st); break;
+    case 4: if constexpr (bc >= 4) return launch_jk<LA, LB, 2, 1>(g, st); break;
+    case 5: if constexpr (bc >= 5) return launch_jk<LA, LB, 2, 2>(g, st); break;
+  }
+  set_error("dev_int4c_jk_class: not a canonical class");
+  return QEMB_ERR_UNSUPPORTED;
 }
 
 // the ket pair classes up to the bra's: only canonical classes are instantiated
@@ -95,6 +136,32 @@ int dev_int4c_class(int la, int lb, int lc, int ld, const int4c::ClassArgs& g) {
     case 4: return launch_bra<2, 1>(kc, g, st);
     default: return launch_bra<2, 2>(kc, g, st);
   }
+}
+
+int dev_int4c_jk_class(int la, int lb, int lc, int ld, const int4c::JkArgs& g) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (int rc = int4c_check_jk(la, lb, lc, ld, g)) return rc;
+  if (g.bra.n == 0 || g.ket.n == 0) return QEMB_OK;
+  const int kc = pair_class(lc, ld);
+  switch (pair_class(la, lb)) {
+    case 0: return launch_jk_bra<0, 0>(kc, g, st);
+    case 1: return launch_jk_bra<1, 0>(kc, g, st);
+    case 2: return launch_jk_bra<1, 1>(kc, g, st);
+    case 3: return launch_jk_bra<2, 0>(kc, g, st);
+    case 4: return launch_jk_bra<2, 1>(kc, g, st);
+    default: return launch_jk_bra<2, 2>(kc, g, st);
+  }
+}
+
+int dev_int4c_dmax(const int3c::Shell* sh, int nshell, int64_t N, const double* dm, double* out) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (!sh || nshell <= 0 || N <= 0 || !dm || !out) { set_error("dev_int4c_dmax: bad arguments"); return QEMB_ERR_ARG; }
+  const long long nitem = (long long)nshell * nshell;
+  hipLaunchKernelGGL(int4c_dmax_kernel, dim3((unsigned)((nitem + 127) / 128)), dim3(128), 0, st, sh, nshell, (long long)N, dm, out);
+  HIP_TRY(hipGetLastError());
+  return QEMB_OK;
 }
 
 }  // namespace qemb

@@ -33,6 +33,25 @@ void run_bra(int kc, const ClassArgs& g) {
   }
 }
 
+template <int LA, int LB, int LC, int LD>
+void run_jk(const JkArgs& g) {
+  const int64_t nitem = jk_items<LC, LD>(g);
+  for (int64_t item = 0; item < nitem; ++item) quartet_jk_item<LA, LB, LC, LD>(g, item);      // QEMB_JK_ADD is a plain += here: one fixed order
+}
+
+template <int LA, int LB>
+void run_jk_bra(int kc, const JkArgs& g) {
+  constexpr int bc = pair_class(LA, LB);
+  switch (kc) {
+    case 0: run_jk<LA, LB, 0, 0>(g); break;
+    case 1: if constexpr (bc >= 1) run_jk<LA, LB, 1, 0>(g); break;
+    case 2: if constexpr (bc >= 2) run_jk<LA, LB, 1, 1>(g); break;
+    case 3: if constexpr (bc >= 3) run_jk<LA, LB, 2, 0>(g); break;
+    case 4: if constexpr (bc >= 4) run_jk<LA, LB, 2, 1>(g); break;
+    case 5: if constexpr (bc >= 5) run_jk<LA, LB, 2, 2>(g); break;
+  }
+}
+
 }  // namespace
 
 int dev_int4c_pairs(int la, int lb, const int4c::PairArgs& g) {
@@ -59,6 +78,26 @@ int dev_int4c_class(int la, int lb, int lc, int ld, const int4c::ClassArgs& g) {
     case 4: run_bra<2, 1>(kc, g); break;
     default: run_bra<2, 2>(kc, g); break;
   }
+  return 0;
+}
+
+int dev_int4c_jk_class(int la, int lb, int lc, int ld, const int4c::JkArgs& g) {
+  if (int rc = int4c_check_jk(la, lb, lc, ld, g)) return rc;
+  const int kc = pair_class(lc, ld);
+  switch (pair_class(la, lb)) {
+    case 0: run_jk_bra<0, 0>(kc, g); break;
+    case 1: run_jk_bra<1, 0>(kc, g); break;
+    case 2: run_jk_bra<1, 1>(kc, g); break;
+    case 3: run_jk_bra<2, 0>(kc, g); break;
+    case 4: run_jk_bra<2, 1>(kc, g); break;
+    default: run_jk_bra<2, 2>(kc, g); break;
+  }
+  return 0;
+}
+
+int dev_int4c_dmax(const int3c::Shell* sh, int nshell, int64_t N, const double* dm, double* out) {
+  if (!sh || nshell <= 0 || N <= 0 || !dm || !out) { set_error("dev_int4c_dmax: bad arguments"); return QEMB_ERR_ARG; }
+  for (int64_t item = 0; item < (int64_t)nshell * nshell; ++item) dmax_item(sh, nshell, N, dm, out, item);
   return 0;
 }
 

@@ -334,6 +334,30 @@ class DeviceBasis:
         _lib.check(self.lib.qemb_int4c_stats(self.h, C.byref(n), C.byref(z)), "qemb_int4c_stats", self.lib)
         return n.value, z.value
 
+    def get_jk(self, dm, thresh=0.0, with_j=True, with_k=True):
+        """Integral-direct J[mu,nu] = sum (mu nu|la si) D[la,si] and K[mu,la] = sum (mu nu|la si) D[nu,si] for a symmetric `dm` (qemb_int_jk_direct): the shell
+        quartets are evaluated on the device and contracted with the density where they were evaluated, no integral is stored.  The first call writes the pair
+        stage and the Schwarz factors and keeps them on the device with this object; later calls reuse them.  thresh > 0 skips a quartet with Q_ab Q_cd < thresh
+        or Q_ab Q_cd max|D| < thresh (`eri_stats()` counts them).  Returns (J, K); a matrix that was not asked for is None.  J and K are symmetric to the bit,
+        but their sums are accumulated with FP64 atomic adds: unlike the stored integrals of `eri()` the last bits may differ from run to run."""
+        from . import _lib
+        if not (with_j or with_k):
+            raise ValueError("get_jk: with_j and with_k are both False")
+        N = self.nao
+        dm = _symmetric_density(dm, N)
+        J = np.empty((N, N)) if with_j else None
+        K = np.empty((N, N)) if with_k else None
+        _lib.check(self.lib.qemb_int_jk_direct(self.h, dm.ctypes.data, float(thresh), J.ctypes.data if with_j else None, K.ctypes.data if with_k else None, 0),
+                   "qemb_int_jk_direct", self.lib)
+        return J, K
+
+    def jk_bytes(self):
+        """device bytes a get_jk call of this basis takes (pair stage, lists, O(N^2)): qemb_int_jk_direct_bytes"""
+        from . import _lib
+        n = C.c_int64()
+        _lib.check(self.lib.qemb_int_jk_direct_bytes(self.h, C.byref(n)), "qemb_int_jk_direct_bytes", self.lib)
+        return n.value
+
     def free(self):
         if getattr(self, "h", None):
             self.lib.qemb_int_basis_free(self.h)
@@ -344,6 +368,16 @@ class DeviceBasis:
             self.free()
         except Exception:
             pass
+
+
+def _symmetric_density(dm, N):
+    """`dm` as a contiguous, exactly symmetric N x N array; ValueError when max |D - D^T| > 1e-12 max |D| (the direct J / K digest assumes D = D^T)"""
+    dm = np.asarray(dm, dtype=float)
+    if dm.shape != (N, N):
+        raise ValueError(f"get_jk: the density must be {N} x {N}, not {dm.shape}")
+    if np.abs(dm - dm.T).max() > 1e-12 * np.abs(dm).max():
+        raise ValueError("get_jk: the density matrix is not symmetric (max |D - D^T| > 1e-12 max |D|)")
+    return np.ascontiguousarray(0.5 * (dm + dm.T))
 
 
 INT_LAYOUTS = {"pqL": 0, "Lpq": 1, "packed": 2, "pairs": 3}
@@ -464,12 +498,32 @@ def eri(mol: Mole, sym=1, backend="host", thresh=0.0, lib=None):
     return pack_eri(mol.eri_s1(), sym)
 
 
+def get_jk(mol: Mole, dm, backend="hip", thresh=0.0, lib=None):
+    """(J, K) of a symmetric density.  backend="hip": integral-direct on the device (DeviceBasis.get_jk: nothing of size N^4 is formed; thresh > 0 screens
+    with the density-weighted Schwarz bound); backend="host": contracted from Mole.eri_s1(), for comparison (never screened)."""
+    dm = _symmetric_density(dm, mol.nao)
+    if _backend(backend):
+        b = DeviceBasis(mol, lib)
+        try:
+            return b.get_jk(dm, thresh)
+        finally:
+            b.free()
+    e = mol.eri_s1()
+    return np.einsum("pqrs,rs->pq", e, dm, optimize=True), np.einsum("pqrs,qs->pr", e, dm, optimize=True)
+
+
 class RHF:
     """Closed-shell RHF with DIIS in the AO basis (generalised eigenproblem through S^-1/2).  integral_backend="hip": `_eri` comes from the device kernels in the
-    8-fold packed form (PySCF's own form of mf._eri); J and K are then contracted from the packed integrals."""
+    8-fold packed form (PySCF's own form of mf._eri); J and K are then contracted from the packed integrals.  direct=True (with integral_backend="hip"): direct
+    SCF -- `_eri` stays None, every J and K of kernel() and get_veff() is formed integral-direct on the device (DeviceBasis.get_jk, screened at direct_thresh)
+    from one DeviceBasis kept on the object; those sums are accumulated with atomic adds, so energies agree from run to run to rounding, not to the bit."""
 
-    def __init__(self, mol: Mole, conv_tol=1e-12, max_cycle=100, integral_backend="host", lib=None):
+    def __init__(self, mol: Mole, conv_tol=1e-12, max_cycle=100, integral_backend="host", lib=None, direct=False, direct_thresh=0.0):
         self.integral_backend, self._lib = ("hip" if _backend(integral_backend) else "host"), lib
+        self.direct, self.direct_thresh = bool(direct), float(direct_thresh)
+        if self.direct and self.integral_backend != "hip":
+            raise ValueError("RHF: direct=True forms J and K on the device; it needs integral_backend='hip'")
+        self._basis = None
         self._pk = None
         self.mol = mol
         self.conv_tol, self.max_cycle = conv_tol, max_cycle
@@ -492,7 +546,23 @@ class RHF:
     def energy_nuc(self):
         return self.mol.energy_nuc()
 
+    def free(self):
+        """release the device basis of a direct mean field (it is uploaded again when needed)"""
+        b, self._basis = getattr(self, "_basis", None), None
+        if b is not None:
+            b.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
     def _jk(self, dm):
+        if self.direct:
+            if self._basis is None:
+                self._basis = DeviceBasis(self.mol, self._lib)
+            return self._basis.get_jk(dm, self.direct_thresh)
         e = self._eri
         if np.ndim(e) != 4:
             return self._jk_packed(dm)
@@ -541,7 +611,7 @@ class RHF:
 
     def kernel(self):
         S = self.get_ovlp(); h = self._h
-        if self._eri is None:
+        if self._eri is None and not self.direct:
             self._eri = eri(self.mol, 8, "hip", lib=self._lib) if self.integral_backend == "hip" else self.mol.eri_s1()
         no = self.mol.nelectron // 2
         w, U = np.linalg.eigh(S)

@@ -357,6 +357,25 @@ int qemb_aoeri_from_basis(qemb_int_basis_t basis, double thresh, qemb_aoeri_t* o
  * bits depend on the arrival order of the adds and may differ from run to run. */
 int qemb_int_jk_direct(qemb_int_basis_t basis, const double* dm, double thresh, double* J, double* K, int io_on_device);
 int qemb_int_jk_direct_bytes(qemb_int_basis_t basis, int64_t* bytes);
+/* ---- integral-direct AO -> fragment transform: the "in-core" fragment integrals without the N^4 array (csrc/int4c.cpp: int4c_ao2mo_direct) ----
+ * The 4-fold packed fragment integrals of qemb_ao2mo_dense, G_f[pq,rs] = sum TA_f[mu,p] TA_f[nu,q] TA_f[la,r] TA_f[si,s] (mu nu|la si), for nfrag fragments in ONE
+ * pass over the integrals.  The canonical shell pairs are cut into slabs of at most tile_pairs AO pairs (whole shell pairs; a larger shell pair is a slab of its
+ * own); for every pair of slabs the kernels of qemb_int4c2e write one tile of the 4-fold packed tensor and every fragment consumes it (two FP64 GEMMs) before the
+ * next tile overwrites it.  Every unique integral is evaluated once; no buffer grows as N^4 or npair(N)^2: device memory is O(tile^2 + tile n^2 + sum_f npair(n_f)^2)
+ * beside the pair stage of qemb_int_jk_direct, which is shared with that call (a basis that served one does not write it again).
+ * TA[f]: N x n[f], host, row-major.  out_s4_host (NULL, or an array of nfrag host pointers, each nullable): npair(n[f])^2 doubles; frags (NULL, or nfrag handles,
+ * each nullable): the block goes straight into the fragment, as with qemb_ao2mo_dense.  tile_pairs <= 0: chosen from the free device memory.
+ * thresh > 0: a shell quartet with Q_ab Q_cd < thresh counts as zeros, as in qemb_int4c2e, and a whole tile is skipped when max Q over its rows times max Q over its
+ * columns is below thresh; thresh = 0 skips nothing.  qemb_int4c_stats: canonical quartets and screened ones of the call (those of a skipped tile included);
+ * qemb_int4c_tile_stats: tiles visited and tiles skipped (either pointer may be NULL).
+ * Fixed loop order, no atomics: the result is bit-reproducible run to run and exactly symmetric (G[pq,rs] = G[rs,pq] to the bit).
+ * qemb_ao2mo_direct_bytes: the device bytes of a call.  The same figure is compared with min(free device memory, the limit of qemb_int4c_mem_limit) before
+ * anything is allocated: QEMB_ERR_ALLOC with N, the tile size and the bytes in the message.  thresh < 0, NULL TA, n[f] outside 1..N, a fragment handle of
+ * another n: QEMB_ERR_ARG; an orbital shell with l > 2: QEMB_ERR_UNSUPPORTED naming the shell. */
+int qemb_ao2mo_direct(qemb_int_basis_t basis, int nfrag, const double* const* TA, const int* n, double* const* out_s4_host, const qemb_frag_t* frags,
+                      int64_t tile_pairs, double thresh);
+int qemb_ao2mo_direct_bytes(qemb_int_basis_t basis, int nfrag, const int* n, int64_t tile_pairs, int64_t* bytes);
+int qemb_int4c_tile_stats(qemb_int_basis_t basis, int64_t* n_visited, int64_t* n_skipped);
 
 /* the resident 3-index factor of a fragment (qemb_frag_mo_route_used gives its naux), naux x npair(n) to the host; QEMB_ERR_ARG without one */
 int qemb_frag_get_df_factor(qemb_frag_t f, double* B_host);

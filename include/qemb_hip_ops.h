@@ -219,6 +219,11 @@ int qemb_op_int3c_class(int la, int lb, int lP, const void* bf_a, const void* bf
  * the canonical class l_a >= l_b, l_c >= l_d, bra pair class >= ket pair class; the block is put back into the caller's order) -- bf_*: the record of the first
  * Cartesian component of each shell, l <= 2, c2s as qemb_int_basis_create; out_host[((a * (2 lb + 1) + b) * (2 lc + 1) + c) * (2 ld + 1) + d] (all host pointers). */
 int qemb_op_int4c_class(int la, int lb, int lc, int ld, const void* bf_a, const void* bf_b, const void* bf_c, const void* bf_d, const double* c2s, double* out_host);
+/* One explicit tile of the 4-fold packed tensor as qemb_ao2mo_direct forms it (the kTile form of the class kernels).  basis: a handle of qemb_int_basis_create
+ * (void*).  pairs_r / pairs_s: n_r / n_s canonical shell pairs (I, J), I >= J, two int32 each; the two lists are the same list or have no shell pair in common.
+ * Rows: the AO pairs of the shell pairs of pairs_r in list order, inside a shell pair in increasing AO pair index; columns likewise from pairs_s.
+ * out_host[row * n_cols + col] = (mu nu|la si), host.  thresh as qemb_int4c2e. */
+int qemb_op_int4c_tile(void* basis, const int32_t* pairs_r, int64_t n_r, const int32_t* pairs_s, int64_t n_s, double thresh, double* out_host);
 
 #ifdef __cplusplus
 }

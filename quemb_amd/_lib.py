@@ -225,6 +225,10 @@ def _declare(lib):
     f("qemb_aoeri_from_basis", I, V, D, C.POINTER(c_vp))
     f("qemb_int_jk_direct", I, V, P, D, P, P, I)
     f("qemb_int_jk_direct_bytes", I, V, C.POINTER(L))
+    f("qemb_ao2mo_direct", I, V, I, P, P, P, P, L, D)
+    f("qemb_ao2mo_direct_bytes", I, V, I, P, L, C.POINTER(L))
+    f("qemb_int4c_tile_stats", I, V, C.POINTER(L), C.POINTER(L))
+    f("qemb_op_int4c_tile", I, V, P, L, P, L, D, P)
     f("qemb_op_int4c_class", I, I, I, I, I, P, P, P, P, P, P)
     f("qemb_op_boys", I, I, L, P, P)
     f("qemb_op_int3c_class", I, I, I, I, P, P, P, P, P)

@@ -11,6 +11,7 @@
 //   packed result -- no n^2 x n^2 intermediate and no restore step.  288 GB of HBM hold the whole (P|mu nu)
 //   tensor, so the reference's memory-driven aux blocking (eri_onthefly.py:18-42) is not needed.
 #include "ao2mo.h"
+#include "int4c_core.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -66,6 +67,21 @@ int ao2mo_dense(const AoEri& ao, const double* TA, int n, double* out_s4) {
   QTRY(dev_pack_pair_rows(n, npn, W2, out_s4));
   QTRY(lap_AO2MO.close());
   return 0;
+}
+
+int ao2mo_tile_accumulate(const double* E, int64_t ld, const TileRows& R, const TileRows& S, bool diagonal, const double* TA, int n, double* PR, double* PS,
+                          double* T, double* A) {
+  const int64_t npq = npair(n);
+  int4c::PairProdArgs g{};
+  g.TA = TA; g.n = n; g.npq = npq;
+  g.mu = S.mu; g.nu = S.nu; g.rows = S.rows; g.P = PS;
+  QTRY(dev_int4c_pairprod(g));
+  if (!diagonal) {
+    g.mu = R.mu; g.nu = R.nu; g.rows = R.rows; g.P = PR;
+    QTRY(dev_int4c_pairprod(g));
+  }
+  QTRY(gemm(R.rows, npq, S.rows, 1.0, E, ld, true, PS, npq, false, 0.0, T, npq));                                      // T[ij,rs] = sum_kl E[ij,kl] P_S[kl,rs]
+  return gemm(npq, npq, R.rows, diagonal ? 0.5 : 1.0, diagonal ? PS : PR, npq, false, T, npq, false, 1.0, A, npq);      // A[pq,rs] += w sum_ij P_R[ij,pq] T[ij,rs]
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -19,6 +19,14 @@ class AoEri {
 // (ij|kl) = sum TA_mu,i TA_nu,j TA_ka,k TA_la,l (mu nu|ka la), 4-fold packed output (device, npair(n)^2)
 int ao2mo_dense(const AoEri& ao, const double* TA_dev, int n, double* out_s4_dev);
 
+// The consumer of one tile E_RS (rows: the AO pairs of slab R, columns: those of slab S, leading dimension ld) of the integral-direct transform (int4c.cpp:
+// int4c_ao2mo_direct):  P_S[kl,pq] from TA (dev_int4c_pairprod), T = E_RS P_S, A += w P_R^T T with w = 1/2 on a diagonal tile (R = S, where P_R is P_S) and 1
+// otherwise, so that G = A + A^T is the transformed block.  2 rows_R rows_S npq + 2 rows_R npq^2 flop per fragment and tile.  PR, PS, T: work space of
+// rows x npq doubles each.
+struct TileRows { const int32_t* mu; const int32_t* nu; int64_t rows; };      // the AO pair (mu >= nu) of every row of a slab (device)
+int ao2mo_tile_accumulate(const double* E, int64_t ld, const TileRows& R, const TileRows& S, bool diagonal, const double* TA_dev, int n, double* PR, double* PS,
+                          double* T, double* A);
+
 // Density-fitted transform with a resident metric factor.
 class DfContext {
  public:

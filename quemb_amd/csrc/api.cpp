@@ -701,6 +701,32 @@ int qemb_int_jk_direct_bytes(qemb_int_basis_t basis, int64_t* bytes) {
   *bytes = int4c_jk_bytes(*o);
   return QEMB_OK;
 }
+int qemb_int4c_tile_stats(qemb_int_basis_t basis, int64_t* n_visited, int64_t* n_skipped) {
+  IntBasis* o = live_basis(basis, "qemb_int4c_tile_stats"); if (!o) return QEMB_ERR_ARG;
+  if (n_visited) *n_visited = o->int4c_tiles[0];
+  if (n_skipped) *n_skipped = o->int4c_tiles[1];
+  return QEMB_OK;
+}
+int qemb_ao2mo_direct_bytes(qemb_int_basis_t basis, int nfrag, const int* n, int64_t tile_pairs, int64_t* bytes) {
+  IntBasis* o = live_basis(basis, "qemb_ao2mo_direct_bytes"); if (!o) return QEMB_ERR_ARG;
+  return int4c_ao2mo_direct_bytes(*o, nfrag, n, tile_pairs, bytes);
+}
+int qemb_ao2mo_direct(qemb_int_basis_t basis, int nfrag, const double* const* TA, const int* n, double* const* out_s4_host, const qemb_frag_t* frags, int64_t tile_pairs,
+                      double thresh) {
+  IntBasis* o = live_basis(basis, "qemb_ao2mo_direct"); if (!o) return QEMB_ERR_ARG;
+  if (nfrag <= 0 || !n) { set_error("qemb_ao2mo_direct: need at least one fragment"); return QEMB_ERR_ARG; }
+  if (frags)
+    for (int f = 0; f < nfrag; ++f)
+      if (frags[f] && FRAG(frags[f])->n() != n[f]) { set_error("qemb_ao2mo_direct: fragment handle " + std::to_string(f) + " has a different n"); return QEMB_ERR_ARG; }
+  std::vector<DBuf> g;
+  QTRY(int4c_ao2mo_direct(*o, nfrag, TA, n, tile_pairs, thresh, g));
+  for (int f = 0; f < nfrag; ++f) QTRY(deliver_s4(g[(size_t)f], n[f], out_s4_host ? out_s4_host[f] : nullptr, frags ? frags[f] : nullptr));
+  return QEMB_OK;
+}
+int qemb_op_int4c_tile(qemb_int_basis_t basis, const int32_t* pairs_r, int64_t n_r, const int32_t* pairs_s, int64_t n_s, double thresh, double* out_host) {
+  IntBasis* o = live_basis(basis, "qemb_op_int4c_tile"); if (!o) return QEMB_ERR_ARG;
+  return int4c_tile(*o, pairs_r, n_r, pairs_s, n_s, thresh, out_host);
+}
 int qemb_aoeri_from_basis(qemb_int_basis_t basis, double thresh, qemb_aoeri_t* out) {
   IntBasis* o = live_basis(basis, "qemb_aoeri_from_basis"); if (!o) return QEMB_ERR_ARG;
   if (!out) { set_error("qemb_aoeri_from_basis: bad arguments"); return QEMB_ERR_ARG; }

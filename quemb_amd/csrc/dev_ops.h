@@ -363,6 +363,12 @@ namespace int4c { struct JkArgs; }
 namespace int3c { struct Shell; }
 int dev_int4c_jk_class(int la, int lb, int lc, int ld, const int4c::JkArgs& args);
 int dev_int4c_dmax(const int3c::Shell* sh, int nshell, int64_t N, const double* dm, double* out);
+// the element-wise passes of the integral-direct AO -> fragment transform (int4c.cpp: ao2mo_direct).  pairprod: P[r][pq] = TA[mu_r,p] TA[nu_r,q] + TA[nu_r,p] TA[mu_r,q]
+// (one term where mu_r = nu_r) for the AO pairs of a tile's rows and the packed fragment pairs, one store-bound pass coalesced along pq.
+// add_transpose: A = A + A^T in place (m x m), exactly symmetric.
+namespace int4c { struct PairProdArgs; }
+int dev_int4c_pairprod(const int4c::PairProdArgs& args);
+int dev_int4c_add_transpose(int64_t m, double* A);
 
 // ---- screening helpers of the semi-sparse DF transform ---------------------------------------------------------------
 // out[i] = (|x[i]| >= eps) ? 1 : 0

@@ -36,6 +36,7 @@ class IntBasis {
   std::vector<double> schwarz[6];
   int64_t int4c_mem_limit = -1;
   int64_t int4c_stats[2] = {0, 0};
+  int64_t int4c_tiles[2] = {0, 0};      // tiles visited / skipped by the last integral-direct AO -> fragment transform (int4c_ao2mo_direct)
   // the direct J / K calls (int4c_jk_direct): pair lists, pair stage and Schwarz factors resident on the device from the first call to the end of the basis
   std::shared_ptr<Int4cCache> jk_cache;
 };

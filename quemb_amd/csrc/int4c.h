@@ -4,6 +4,7 @@
 // to the form the consumer reads: 8-fold packed (rdm2_eri_dot, RHF), 4-fold packed (AoEri, the operand of ao2mo_dense) or the full [N]^4 tensor.
 #pragma once
 #include <cstdint>
+#include <vector>
 #include "int3c.h"
 #include "int4c_core.h"
 
@@ -26,6 +27,19 @@ int int4c_fill(IntBasis& orb, int sym, double thresh, double* out_dev);
 // for int4c_fill.  The sums are accumulated with FP64 atomic adds: J and K are symmetric to the bit but not bit-reproducible from run to run.
 int64_t int4c_jk_bytes(const IntBasis& orb);      // device bytes of a call: pair stage, lists, Schwarz factors, the N x N matrices and the shell-block table
 int int4c_jk_direct(IntBasis& orb, const double* dm, double thresh, double* J, double* K, int io_on_device);
+// Integral-direct AO -> fragment transform: G_f[pq,rs] = sum P_f[ij,pq] (ij|kl) P_f[kl,rs] for every fragment f of the call in ONE pass over the integrals, with no
+// array of size N^4 or npair^2.  The canonical shell pairs are cut into slabs of at most tile_pairs AO pairs (whole shell pairs; a larger shell pair is a slab of its
+// own); for every pair of slabs R >= S the quartet stage writes the tile E_RS of the 4-fold packed tensor (the kTile form: every unique integral still evaluated once
+// in total) and each fragment consumes it, T = E_RS P_S, A += P_R^T T (ao2mo_tile_accumulate; R = S weighted 1/2); at the end G = A + A^T.  Fixed loop order, no
+// atomics: bit-reproducible.  tile_pairs <= 0: chosen from the free memory.  thresh > 0: quartets screened as in int4c_fill, and a tile with max Q_R max Q_S < thresh
+// is skipped altogether.  orb.int4c_stats as for int4c_fill (the quartets of a skipped tile count as screened), orb.int4c_tiles: tiles visited, tiles skipped.
+// Pair stage, lists and Schwarz factors are those of orb.jk_cache.  out[f]: npair(n_f)^2 doubles on the device, allocated here.
+// bytes: the device footprint of a call -- compared with min(free memory, orb.int4c_mem_limit) before anything is allocated (QEMB_ERR_ALLOC).
+int int4c_ao2mo_direct_bytes(const IntBasis& orb, int nfrag, const int* n, int64_t tile_pairs, int64_t* bytes);
+int int4c_ao2mo_direct(IntBasis& orb, int nfrag, const double* const* TA_host, const int* n, int64_t tile_pairs, double thresh, std::vector<DBuf>& out);
+// one explicit tile (qemb_op_int4c_tile): rows = the AO pairs of the shell pairs pairs_r[k] = (I, J), I >= J, in list order and inside a shell pair in increasing
+// AO pair index; columns likewise from pairs_s.  The two lists are the same list or have no shell pair in common.  out_host[row * ncol + col].
+int int4c_tile(IntBasis& orb, const int32_t* pairs_r, int64_t n_r, const int32_t* pairs_s, int64_t n_s, double thresh, double* out_host);
 // one explicit block in the caller's shell order (qemb_op_int4c_class): out_host[((a * (2 lb + 1) + b) * (2 lc + 1) + c) * (2 ld + 1) + d]
 int int4c_block(const int l[4], const BfRecord* const rec[4], const double* c2s_host, double* out_host);
 

@@ -10,6 +10,8 @@
 //   quartet_item  per (shell quartet, ket component pair c d): over the primitive quartets one R table, G_{tuv} = pref sum (-1)^{..} Ebar^{cd}_{t'u'v'} R_{t+t',..}
 //                 (at most 35 numbers) and acc[a b] += sum_{tuv} Ebar^{ab}_{tuv} G_{tuv} for the nsph(la) nsph(lb) <= 25 bra products; then every element
 //                 of the output that belongs to (a b|c d) is stored once, from that one value.
+// The stored forms include a TILE of the 4-fold packed tensor (kTile: rows and columns are two sets of AO pairs), the operand of the integral-direct
+// AO -> fragment transform; pairprod_item and addt_item are the two element-wise passes of that transform (int4c.cpp: ao2mo_direct).
 #pragma once
 #include "int3c_core.h"
 
@@ -103,7 +105,8 @@ QEMB_I3_HD void pair_item(const PairArgs& g, int64_t item) {
 }
 
 // ---- one launch: the shell quartets of one angular class (la >= lb | lc >= ld), bra pair class >= ket pair class ---------------------------------
-enum Out { kBlock = 0, kS1 = 1, kDiag = 2, kS4 = 4, kS8 = 8 };
+enum Out { kBlock = 0, kS1 = 1, kDiag = 2, kS4 = 4, kS8 = 8, kTile = 16 };
+enum TileStore { kTileAsIs = 0, kTileTransposed = 1, kTileBoth = 2 };
 
 struct ClassArgs {
   const Shell* sh;
@@ -113,8 +116,16 @@ struct ClassArgs {
   double thresh;               // > 0 with bra.q / ket.q: a quartet with q_bra q_ket < thresh is stored as zeros
   int out;                     // kS8: 1-D npair (npair + 1) / 2; kS4: [npair][npair]; kS1: [N]^4; kBlock: one block [a][b][c][d];
                                // kDiag: dst[k * nsph(lc) nsph(ld) + c d] = (c d|c d) of pair k (bra == ket list, the source of the Schwarz factors)
+                               // kTile: dst[row[ij] * ld + col[kl]] -- a tile of the kS4 tensor whose rows / columns are the AO pairs of two sets of shell pairs
   int64_t N;
   double* dst;
+  // kTile only.  row / col: AO pair index -> compact tile row / column (defined for the AO pairs of the bra / ket lists' shell pairs; for kTileTransposed the
+  // other way round).  store: kTileAsIs (ij|kl) -> [row[ij]][col[kl]]; kTileTransposed -> [row[kl]][col[ij]] (the class kernels need bra class >= ket class: a
+  // quartet whose bra pair belongs to the column set is computed in that orientation and stored transposed); kTileBoth: both, once where ij = kl (rows = columns)
+  const int32_t* row;
+  const int32_t* col;
+  int64_t ld;
+  int store;
 };
 
 template <int LC, int LD>
@@ -205,6 +216,9 @@ QEMB_I3_HD void quartet_item(const ClassArgs& g, int64_t item) {
       } else if (g.out == kS4) {
         g.dst[ij * np + kl] = v;
         if (ij != kl) g.dst[kl * np + ij] = v;
+      } else if (g.out == kTile) {
+        if (g.store != kTileTransposed) g.dst[g.row[ij] * g.ld + g.col[kl]] = v;
+        if (g.store == kTileTransposed || (g.store == kTileBoth && ij != kl)) g.dst[g.row[kl] * g.ld + g.col[ij]] = v;
       } else {      // kS1: the 8 images (fewer where indices coincide), each stored once
         double* o = g.dst;
         o[((mu * N + nu) * N + la) * N + si] = v;
@@ -223,6 +237,35 @@ QEMB_I3_HD void quartet_item(const ClassArgs& g, int64_t item) {
         }
       }
     }
+}
+
+// ---- the element-wise passes of the integral-direct AO -> fragment transform ----------------------------------------------------------------------------
+// P[r][pq] = TA[mu,p] TA[nu,q] + TA[nu,p] TA[mu,q] (mu != nu), TA[mu,p] TA[mu,q] (mu = nu) for the AO pair (mu[r], nu[r]) of tile row r and the packed fragment
+// pair pq = p (p + 1) / 2 + q, p >= q: one item per element, consecutive items along pq (the stores of a wavefront are one contiguous run).
+struct PairProdArgs {
+  const double* TA;            // [N][n]
+  int64_t n, npq, rows;
+  const int32_t* mu;           // [rows], mu >= nu
+  const int32_t* nu;
+  double* P;                   // [rows][npq]
+};
+
+QEMB_I3_HD void pairprod_item(const PairProdArgs& g, int64_t r, int64_t pq) {
+  int64_t p = (int64_t)((sqrtf(8.0f * (float)pq + 1.0f) - 1.0f) * 0.5f);      // single precision is 2^-7 of a unit off at pq = 2^31: the two loops settle it
+  while (p * (p + 1) / 2 > pq) --p;
+  while ((p + 1) * (p + 2) / 2 <= pq) ++p;
+  const int64_t q = pq - p * (p + 1) / 2;
+  const double* tm = g.TA + (int64_t)g.mu[r] * g.n;
+  const double* tn = g.TA + (int64_t)g.nu[r] * g.n;
+  g.P[r * g.npq + pq] = g.mu[r] == g.nu[r] ? tm[p] * tm[q] : tm[p] * tn[q] + tn[p] * tm[q];
+}
+
+// A = A + A^T in place (m x m): the item of (i, j), i >= j, owns both elements
+QEMB_I3_HD void addt_item(double* A, int64_t m, int64_t i, int64_t j) {
+  if (j > i) return;
+  const double s = A[i * m + j] + A[j * m + i];
+  A[i * m + j] = s;
+  A[j * m + i] = s;
 }
 
 // ---- the digest form: J and K from the quartets, no integral stored (qemb_int_jk_direct) -----------------------------------------------------------
@@ -374,11 +417,19 @@ inline int int4c_check_class(int la, int lb, int lc, int ld, const int4c::ClassA
     set_error("dev_int4c_class: not a canonical angular class (" + std::to_string(la) + "," + std::to_string(lb) + "|" + std::to_string(lc) + "," + std::to_string(ld) + ")");
     return QEMB_ERR_UNSUPPORTED;
   }
-  if (g.out != kBlock && g.out != kS1 && g.out != kDiag && g.out != kS4 && g.out != kS8) { set_error("dev_int4c_class: unknown output form " + std::to_string(g.out)); return QEMB_ERR_ARG; }
+  if (g.out != kBlock && g.out != kS1 && g.out != kDiag && g.out != kS4 && g.out != kS8 && g.out != kTile) { set_error("dev_int4c_class: unknown output form " + std::to_string(g.out)); return QEMB_ERR_ARG; }
   const bool same_class = la == lc && lb == ld;
   if ((g.same && !same_class) || (g.out == kDiag && !g.same)) { set_error("dev_int4c_class: one list on both sides needs equal pair classes"); return QEMB_ERR_ARG; }
   if (g.bra.n < 0 || g.ket.n < 0 || !g.sh || !g.data || !g.dst || !g.bra.a || !g.bra.b || !g.bra.off || !g.ket.a || !g.ket.b || !g.ket.off ||
       (g.out != kBlock && g.out != kDiag && g.N <= 0)) { set_error("dev_int4c_class: bad arguments"); return QEMB_ERR_ARG; }
+  if (g.out == kTile && (!g.row || !g.col || g.ld <= 0 || g.store < kTileAsIs || g.store > kTileBoth || (g.same && g.store != kTileBoth))) {
+    set_error("dev_int4c_class: a tile needs its row and column maps, a leading dimension and a store mode (both triangles when bra and ket are one list)");
+    return QEMB_ERR_ARG;
+  }
+  return 0;
+}
+inline int int4c_check_pairprod(const int4c::PairProdArgs& g) {
+  if (!g.TA || !g.mu || !g.nu || !g.P || g.n <= 0 || g.npq != g.n * (g.n + 1) / 2 || g.rows < 0 || g.npq > 0x7fffffffLL) { set_error("dev_int4c_pairprod: bad arguments"); return QEMB_ERR_ARG; }
   return 0;
 }
 inline int int4c_check_jk(int la, int lb, int lc, int ld, const int4c::JkArgs& g) {

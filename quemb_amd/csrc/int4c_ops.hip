@@ -8,6 +8,8 @@
 // section 4, "AO integrals on the device").  Every output element is stored once by plain stores.  l_a + l_b + l_c + l_d >= 4 runs in 64-thread workgroups.
 // int4c_jk_kernel<la, lb, lc, ld> is the digest form of the class kernel (dev_int4c_jk_class): the same items and primitive loops, the unique integrals
 // contracted with the density into the lower triangles of J and K by FP64 atomic adds instead of stored ("Integral-direct J and K").
+// The class kernel also writes a tile of the 4-fold packed tensor (kTile, a runtime branch of the same 21 instantiations); int4c_pairprod_kernel and
+// int4c_addt_kernel are the two element-wise passes of the transform that consumes the tiles ("Integral-direct AO -> fragment transform").
 #include "hip_common.h"
 #include "int4c_core.h"
 
@@ -41,6 +43,19 @@ __global__ void __launch_bounds__(128) int4c_dmax_kernel(const Shell* sh, const 
   const long long item = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (item >= (long long)nshell * nshell) return;
   dmax_item(sh, nshell, N, dm, out, item);
+}
+
+// one thread per element of P, x along pq: a wavefront stores 512 contiguous bytes; the two TA rows of a tile row are read from cache
+__global__ void __launch_bounds__(256) int4c_pairprod_kernel(const PairProdArgs g) {
+  const long long pq = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pq >= g.npq) return;
+  for (long long r = blockIdx.y; r < g.rows; r += gridDim.y) pairprod_item(g, r, pq);
+}
+
+__global__ void __launch_bounds__(256) int4c_addt_kernel(double* A, const long long m) {
+  const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  for (long long i = blockIdx.y; i < m; i += gridDim.y) addt_item(A, m, i, j);
 }
 
 template <int LA, int LB>
@@ -152,6 +167,27 @@ int dev_int4c_jk_class(int la, int lb, int lc, int ld, const int4c::JkArgs& g) {
     case 4: return launch_jk_bra<2, 1>(kc, g, st);
     default: return launch_jk_bra<2, 2>(kc, g, st);
   }
+}
+
+int dev_int4c_pairprod(const int4c::PairProdArgs& g) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (int rc = int4c_check_pairprod(g)) return rc;
+  if (g.rows == 0) return QEMB_OK;
+  const long long gy = g.rows < 65535 ? g.rows : 65535;
+  hipLaunchKernelGGL(int4c_pairprod_kernel, dim3((unsigned)((g.npq + 255) / 256), (unsigned)gy), dim3(256), 0, st, g);
+  HIP_TRY(hipGetLastError());
+  return QEMB_OK;
+}
+
+int dev_int4c_add_transpose(int64_t m, double* A) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (m <= 0 || m > 0x7fffffffLL || !A) { set_error("dev_int4c_add_transpose: bad arguments"); return QEMB_ERR_ARG; }
+  const long long gy = m < 65535 ? m : 65535;
+  hipLaunchKernelGGL(int4c_addt_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)gy), dim3(256), 0, st, A, (long long)m);
+  HIP_TRY(hipGetLastError());
+  return QEMB_OK;
 }
 
 int dev_int4c_dmax(const int3c::Shell* sh, int nshell, int64_t N, const double* dm, double* out) {

@@ -95,6 +95,20 @@ int dev_int4c_jk_class(int la, int lb, int lc, int ld, const int4c::JkArgs& g) {
   return 0;
 }
 
+int dev_int4c_pairprod(const int4c::PairProdArgs& g) {
+  if (int rc = int4c_check_pairprod(g)) return rc;
+  for (int64_t r = 0; r < g.rows; ++r)
+    for (int64_t pq = 0; pq < g.npq; ++pq) pairprod_item(g, r, pq);
+  return 0;
+}
+
+int dev_int4c_add_transpose(int64_t m, double* A) {
+  if (m <= 0 || m > 0x7fffffffLL || !A) { set_error("dev_int4c_add_transpose: bad arguments"); return QEMB_ERR_ARG; }
+  for (int64_t i = 0; i < m; ++i)
+    for (int64_t j = 0; j < m; ++j) addt_item(A, m, i, j);
+  return 0;
+}
+
 int dev_int4c_dmax(const int3c::Shell* sh, int nshell, int64_t N, const double* dm, double* out) {
   if (!sh || nshell <= 0 || N <= 0 || !dm || !out) { set_error("dev_int4c_dmax: bad arguments"); return QEMB_ERR_ARG; }
   for (int64_t item = 0; item < (int64_t)nshell * nshell; ++item) dmax_item(sh, nshell, N, dm, out, item);

@@ -4,6 +4,7 @@ qemb_schmidt*).  Host mirror of the reference seams:
 * `ao2mo.incore.full(eri_, TA, compact=True)`            molbe/mbe.py:1038            -> AOEri.transform
 * `integral_direct_DF(mf, Fobjs, file_eri, auxbasis)`     molbe/eri_onthefly.py:45     -> DFContext.transform
 * `transform_integral[_cuda](P_mu_nu, TA, S_abs, L_PQ, e)` molbe/eri_sparse_DF.py:677-702 -> DFContext (packed ints)
+* the same fragment integrals with no N^4 array (no seam in the reference)             -> integrals.DeviceBasis.ao2mo ("int-direct-hip")
 * `schmidt_decomposition(mo_coeff, nocc, AO_in_frag, ...)` molbe/pfrag.py:403           -> schmidt_decomposition
 * `schmidt_decomp_svd(rdm, Frag_sites, thr_bath)`          kbe/solver.py:9              -> schmidt_decomp_svd
 """
@@ -18,7 +19,7 @@ from . import _lib
 from ._lib import c_vp, check
 
 #: new `int_transform` literals next to the reference's IntTransforms (molbe/mbe.py:63-71)
-HIP_INT_TRANSFORMS = ("in-core-hip", "int-direct-DF-hip", "sparse-DF-hip", "on-fly-sparse-DF-hip")
+HIP_INT_TRANSFORMS = ("in-core-hip", "int-direct-DF-hip", "sparse-DF-hip", "on-fly-sparse-DF-hip", "int-direct-hip")
 
 
 def _arr(a):

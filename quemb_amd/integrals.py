@@ -358,6 +358,46 @@ class DeviceBasis:
         _lib.check(self.lib.qemb_int_jk_direct_bytes(self.h, C.byref(n)), "qemb_int_jk_direct_bytes", self.lib)
         return n.value
 
+    def ao2mo(self, TAs, frags=None, want_host=True, tile_pairs=None, thresh=0.0):
+        """Integral-direct AO -> fragment transform (qemb_ao2mo_direct): the 4-fold packed fragment integrals of `AOEri.transform` for every coefficient matrix
+        of `TAs` (each N x n_f) from ONE pass over the integrals, which are evaluated tile by tile and never stored -- device memory is
+        O(tile^2 + tile n^2 + sum_f npair(n_f)^2), nothing grows as N^4.  frags: fragment handles (DeviceFragment, or None) the blocks go straight into;
+        want_host: also return them as host arrays.  tile_pairs: AO pairs per tile (None: chosen from the free device memory).  thresh > 0: Schwarz screening
+        of quartets and of whole tiles (`eri_stats()`, `tile_stats()`).  Returns a list of (npair(n_f), npair(n_f)) arrays, or None with want_host=False.
+        Bit-reproducible from run to run and exactly symmetric."""
+        from . import _lib
+        TAs = [np.ascontiguousarray(t, dtype=np.float64) for t in TAs]
+        nf = len(TAs)
+        if nf == 0:
+            raise ValueError("ao2mo: no coefficient matrix")
+        if any(t.ndim != 2 or t.shape[0] != self.nao for t in TAs):
+            raise ValueError(f"ao2mo: every TA must have {self.nao} rows")
+        if frags is not None and len(frags) != nf:
+            raise ValueError("ao2mo: one fragment handle (or None) per coefficient matrix")
+        ns = (C.c_int * nf)(*[t.shape[1] for t in TAs])
+        ta = (C.c_void_p * nf)(*[t.ctypes.data for t in TAs])
+        outs = [np.empty((n * (n + 1) // 2,) * 2) for n in ns] if want_host else None
+        op = (C.c_void_p * nf)(*[o.ctypes.data for o in outs]) if want_host else None
+        fh = None if frags is None else (C.c_void_p * nf)(*[None if f is None else f.h.value for f in frags])
+        _lib.check(self.lib.qemb_ao2mo_direct(self.h, nf, ta, ns, op, fh, int(tile_pairs or 0), float(thresh)), "qemb_ao2mo_direct", self.lib)
+        return outs
+
+    def ao2mo_bytes(self, ns, tile_pairs=None):
+        """device bytes an `ao2mo` call for fragments of `ns` embedding orbitals takes at this tile size (qemb_ao2mo_direct_bytes): the figure the call checks
+        against the free memory and the limit of qemb_int4c_mem_limit before it allocates anything"""
+        from . import _lib
+        ns = [int(n) for n in ns]
+        arr, b = (C.c_int * len(ns))(*ns), C.c_int64()
+        _lib.check(self.lib.qemb_ao2mo_direct_bytes(self.h, len(ns), arr, int(tile_pairs or 0), C.byref(b)), "qemb_ao2mo_direct_bytes", self.lib)
+        return b.value
+
+    def tile_stats(self):
+        """(tiles visited, tiles skipped) of the last `ao2mo` call of this basis"""
+        from . import _lib
+        v, z = C.c_int64(), C.c_int64()
+        _lib.check(self.lib.qemb_int4c_tile_stats(self.h, C.byref(v), C.byref(z)), "qemb_int4c_tile_stats", self.lib)
+        return v.value, z.value
+
     def free(self):
         if getattr(self, "h", None):
             self.lib.qemb_int_basis_free(self.h)

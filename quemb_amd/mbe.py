@@ -33,7 +33,7 @@ class BE:
     def __init__(self, mf, fobj, *, lo_method="lowdin", thr_bath=1.0e-10, int_transform="in-core-hip", auxbasis=None,
                  df_ints=None, nproc=1, ompnum=1, initialize_fragment_idx=None, solver_opts=None, lib=None, distribute=True, nstreams=None, lockstep=None,
                  eri_file=None, scratch_dir=None, restart=False, schmidt_method="subspace", MO_coeff_epsilon=1e-5, AO_coeff_epsilon=1e-10, df_resident="factor",
-                 integral_backend="host"):
+                 integral_backend="host", int_direct_tile=None, int_direct_thresh=0.0):
         if lo_method != "lowdin":
             raise NotImplementedError("only lo_method='lowdin' is mirrored (localisation is upstream of the hot path)")
         if restart:
@@ -54,6 +54,16 @@ class BE:
         if integral_backend == "hip" and df_ints is not None:
             raise ValueError("integral_backend='hip' evaluates the DF integrals from the geometry; with `df_ints` the integrals are the caller's")
         self.integral_backend = integral_backend
+        # int_transform="int-direct-hip": the exact fragment integrals of "in-core-hip" from mf.mol with no N^4 array -- the AO integrals are evaluated tile by tile on
+        # the device and consumed by every fragment (DeviceBasis.ao2mo).  int_direct_tile: AO pairs per tile (None: from the free device memory); int_direct_thresh:
+        # Schwarz threshold of quartets and tiles (0: nothing skipped).  Needs integral_backend="hip" and a mean field with `mol`; `mf._eri` is ignored.
+        if int_transform == "int-direct-hip":
+            if integral_backend != "hip":
+                raise ValueError("int_transform='int-direct-hip' evaluates the integrals on the device: it needs integral_backend='hip'")
+            if getattr(mf, "mol", None) is None:
+                raise ValueError("int_transform='int-direct-hip' evaluates the integrals from the geometry: the mean field needs `mol`")
+        self.int_direct_tile = None if int_direct_tile is None else int(int_direct_tile)
+        self.int_direct_thresh = float(int_direct_thresh)
         self.auxbasis = auxbasis
         self.MO_coeff_epsilon, self.AO_coeff_epsilon = float(MO_coeff_epsilon), float(AO_coeff_epsilon)      # mbe.py:191-192
         self.opts = solver_opts
@@ -166,6 +176,20 @@ class BE:
                     ao.transform(self.Fobjs[I].TA, frag=self.Fobjs[I].dev, want_host=False)
             finally:
                 ao.free()
+        elif it == "int-direct-hip":
+            # integral-direct: one pass over the AO integrals, tile by tile, serves every fragment of `idx` (csrc/int4c.cpp: int4c_ao2mo_direct); nothing of size
+            # N^4 exists on the host or the device.  `eri_` (mf._eri) is ignored: the integrals come from mf.mol
+            from . import _lib
+            from .integrals import DeviceBasis
+            basis = DeviceBasis(self.mf.mol, self.lib or _lib.init())
+            try:
+                if idx:
+                    self.int_direct_bytes = basis.ao2mo_bytes([self.Fobjs[I].TA.shape[1] for I in idx], self.int_direct_tile)
+                    basis.ao2mo([self.Fobjs[I].TA for I in idx], frags=[self.Fobjs[I].dev for I in idx], want_host=False, tile_pairs=self.int_direct_tile,
+                                thresh=self.int_direct_thresh)
+            finally:
+                basis.free()
+            self._eri_from_geometry = True
         elif it in ("int-direct-DF-hip", "sparse-DF-hip", "on-fly-sparse-DF-hip") and self._df_ints is None:
             # from the geometry alone, like the reference's "int-direct-DF" / "sparse-DF(-gpu)" / "on-fly-sparse-DF(-gpu)" branches
             # (mbe.py:1049-1110): auxiliary molecule, (P|Q), (mu nu|P) from the integral source, AO screening, device transform

@@ -17,6 +17,17 @@ hipStream_t hip_stream();  // the library stream (created by dev_init)
     }                                                                                         \
   } while (0)
 
+// One 1-D launch of kernel(g, nitem): nitem work items in blocks of bs threads (bs: the kernel's launch bound).  who: for the messages.
+template <class Args>
+int launch_items(void (*kernel)(Args, long long), int bs, const Args& g, long long nitem, const char* who, hipStream_t st) {
+  const long long nb = (nitem + bs - 1) / bs;
+  if (nb > 0x7fffffffLL) { set_error(std::string(who) + ": too many blocks in one launch"); return QEMB_ERR_ARG; }
+  if (nb <= 0) return QEMB_OK;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(bs), 0, st, g, nitem);
+  HIP_TRY(hipGetLastError());
+  return QEMB_OK;
+}
+
 // XCD-aware logical block index of the tiled HBM passes (round 4; profiles/r04_hbm_pmc.json).  Workgroups are dealt round-robin over the eight
 // XCDs, each with its own L2, so neighbouring 32 x 32 tiles -- whose 256-byte row pieces start at arbitrary offsets and share their first and
 // last 128-byte lines -- ran on different XCDs and every shared line was fetched from HBM twice: FETCH_SIZE showed 1.2-1.5 x the algorithmic

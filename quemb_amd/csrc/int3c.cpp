@@ -1,4 +1,5 @@
-// int3c.cpp -- driver of the DF integrals on the device (see int3c.h): shells from the uploaded records, work lists per angular class, one launch per class.
+// int3c.cpp -- driver of the DF integrals on the device (see int3c.h): shells from the uploaded records, work lists per angular class, one launch per class;
+// and the refusals and the record -> shell copy it shares with the four-centre driver (int4c.cpp).
 #include "int3c.h"
 #include <algorithm>
 #include <cstring>
@@ -11,13 +12,37 @@ namespace qemb {
 using int3c::ClassArgs;
 using int3c::Shell;
 
-// The kernels skip the Cartesian -> spherical step for s and p shells: the matrices of l = 0, 1 have to be the identity (x, y, z order, unit scale)
-static int check_c2s(const double* c2s_host, const char* who) {
+// ---- the refusals and the record -> shell copy that the DF and the four-centre drivers share (int3c.h) ----
+int check_c2s(const double* c2s_host, const char* who) {
   for (int k = 0; k < 10; ++k)
     if (c2s_host[k] != ((k == 0 || k == 1 || k == 5 || k == 9) ? 1.0 : 0.0)) {
       set_error(std::string(who) + ": the Cartesian -> spherical matrices of l = 0 and l = 1 must be the identity (p functions in x, y, z order)");
       return QEMB_ERR_UNSUPPORTED;
     }
+  return 0;
+}
+
+int check_orbital(const IntBasis& orb, const char* who) {
+  for (int i = 0; i < orb.nshell; ++i)
+    if (orb.shells[i].l > 2) {
+      set_error(std::string(who) + ": orbital shell " + std::to_string(i) + " has l = " + std::to_string(orb.shells[i].l) + "; orbital shells beyond d are not supported");
+      return QEMB_ERR_UNSUPPORTED;
+    }
+  return 0;
+}
+
+int check_thresh(double thresh, const char* who) {
+  if (thresh >= 0.0) return 0;      // a NaN is refused too
+  set_error(std::string(who) + ": the screening threshold must be >= 0");
+  return QEMB_ERR_ARG;
+}
+
+int shell_of(const BfRecord& r, int l, int ao0, const std::string& who, Shell* s) {
+  if (r.nprim < 1 || r.nprim > int3c::kMaxPrim) { set_error(who + ": 1 to 8 primitives per contraction"); return QEMB_ERR_ARG; }
+  *s = Shell{};
+  for (int d = 0; d < 3; ++d) s->r[d] = r.ctr[d];
+  s->l = l; s->nprim = r.nprim; s->ao0 = ao0;
+  for (int i = 0; i < r.nprim; ++i) { s->ex[i] = r.ex[i]; s->co[i] = r.co[i]; }
   return 0;
 }
 
@@ -30,7 +55,8 @@ int IntBasis::create(int n_bf, const BfRecord* rec, const double* c2s_host) {
     const int l = r0.lmn[0] + r0.lmn[1] + r0.lmn[2];
     const std::string where = "qemb_int_basis_create: function " + std::to_string(f);
     if (l < 0 || l > int3c::kMaxL || r0.lmn[0] != l) { set_error(where + " does not start a shell of l <= 4 (components in libcint order, x^l first)"); return QEMB_ERR_UNSUPPORTED; }
-    if (r0.nprim < 1 || r0.nprim > int3c::kMaxPrim) { set_error(where + ": 1 to 8 primitives per contraction"); return QEMB_ERR_ARG; }
+    Shell s;
+    QTRY(shell_of(r0, l, nao, where, &s));
     const int nc = int3c::ncart(l);
     if (f + nc > n_bf) { set_error(where + ": the shell is incomplete"); return QEMB_ERR_ARG; }
     int k = 0;
@@ -41,10 +67,6 @@ int IntBasis::create(int n_bf, const BfRecord* rec, const double* c2s_host) {
                           !std::memcmp(r.ex, r0.ex, sizeof(double) * r0.nprim) && !std::memcmp(r.co, r0.co, sizeof(double) * r0.nprim);
         if (!same) { set_error(where + ": component " + std::to_string(k) + " of the shell differs in order, centre, exponents or coefficients"); return QEMB_ERR_UNSUPPORTED; }
       }
-    Shell s{};
-    for (int d = 0; d < 3; ++d) s.r[d] = r0.ctr[d];
-    s.l = l; s.nprim = r0.nprim; s.ao0 = nao;
-    for (int i = 0; i < r0.nprim; ++i) { s.ex[i] = r0.ex[i]; s.co[i] = r0.co[i]; }
     shells.push_back(s);
     nao += 2 * l + 1;
     f += nc;
@@ -86,15 +108,6 @@ struct PairClass {
   size_t o_pa = 0, o_pb = 0, o_ptr = 0, o_row = 0, o_ab = 0;
 };
 
-int check_orbital(const IntBasis& orb) {
-  for (int i = 0; i < orb.nshell; ++i)
-    if (orb.shells[i].l > 2) {
-      set_error("qemb_int3c2e: orbital shell " + std::to_string(i) + " has l = " + std::to_string(orb.shells[i].l) + "; orbital shells beyond d are not supported");
-      return QEMB_ERR_UNSUPPORTED;
-    }
-  return 0;
-}
-
 // auxiliary shells by l: offsets into pool.i32
 void aux_lists(const IntBasis& aux, IndexPool& pool, size_t off[int3c::kMaxL + 1], int64_t cnt[int3c::kMaxL + 1]) {
   for (int l = 0; l <= int3c::kMaxL; ++l) {
@@ -109,7 +122,7 @@ void aux_lists(const IntBasis& aux, IndexPool& pool, size_t off[int3c::kMaxL + 1
 int int3c_fill(const IntBasis& orb, const IntBasis& aux, int layout, const int64_t* pairs, int64_t n_pairs, double* out) {
   if (layout < INT_LAYOUT_PQL || layout > INT_LAYOUT_PAIRS) { set_error("qemb_int3c2e: unknown layout " + std::to_string(layout) + " (0 pqL, 1 Lpq, 2 packed, 3 pair list)"); return QEMB_ERR_ARG; }
   if (!out || (layout == INT_LAYOUT_PAIRS) != (pairs != nullptr) || (pairs && n_pairs < 0)) { set_error("qemb_int3c2e: a pair list goes with layout 3 and only with it"); return QEMB_ERR_ARG; }
-  QTRY(check_orbital(orb));
+  QTRY(check_orbital(orb, "qemb_int3c2e"));
   std::map<int, PairClass> cls;      // key la * 8 + lb
   auto role = [&](int I, int J, int& A, int& B) { const bool sw = orb.shells[I].l < orb.shells[J].l; A = sw ? J : I; B = sw ? I : J; return sw; };
   if (layout != INT_LAYOUT_PAIRS) {
@@ -202,13 +215,7 @@ int int3c_block(int la, int lb, int lp, const BfRecord* A, const BfRecord* B, co
   const BfRecord* rec[3] = {A, B, P};
   const int ls[3] = {la, lb, lp};
   Shell sh[3];
-  for (int k = 0; k < 3; ++k) {
-    if (rec[k]->nprim < 1 || rec[k]->nprim > int3c::kMaxPrim) { set_error("qemb_op_int3c_class: 1 to 8 primitives per contraction"); return QEMB_ERR_ARG; }
-    sh[k] = Shell{};
-    for (int d = 0; d < 3; ++d) sh[k].r[d] = rec[k]->ctr[d];
-    sh[k].l = ls[k]; sh[k].nprim = rec[k]->nprim; sh[k].ao0 = 0;
-    for (int i = 0; i < rec[k]->nprim; ++i) { sh[k].ex[i] = rec[k]->ex[i]; sh[k].co[i] = rec[k]->co[i]; }
-  }
+  for (int k = 0; k < 3; ++k) QTRY(shell_of(*rec[k], ls[k], 0, "qemb_op_int3c_class", &sh[k]));
   const int64_t nout = (int64_t)(2 * la + 1) * (2 * lb + 1) * (2 * lp + 1);
   DBuf dsh, dc, dout, didx;
   const int32_t idx[4] = {la >= lb ? 0 : 1, la >= lb ? 1 : 0, 2, 0};      // role A, role B, the auxiliary shell

@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdint>
 #include <memory>
+#include <string>
 #include <vector>
 #include "dev_ops.h"
 #include "int3c_core.h"
@@ -12,7 +13,7 @@
 namespace qemb {
 
 class DfContext;
-struct Int4cCache;      // int4c.cpp: what qemb_int_jk_direct keeps on the device between calls
+struct PairCache;      // int4c.cpp: the resident pair stage, pair lists and Schwarz factors of a basis
 
 // the record integrals.py builds per Cartesian contracted function (`_BF`; csrc_host/gto_ints.c bf_t)
 struct BfRecord {
@@ -37,9 +38,17 @@ class IntBasis {
   int64_t int4c_mem_limit = -1;
   int64_t int4c_stats[2] = {0, 0};
   int64_t int4c_tiles[2] = {0, 0};      // tiles visited / skipped by the last integral-direct AO -> fragment transform (int4c_ao2mo_direct)
-  // the direct J / K calls (int4c_jk_direct): pair lists, pair stage and Schwarz factors resident on the device from the first call to the end of the basis
-  std::shared_ptr<Int4cCache> jk_cache;
+  // pair lists, pair stage and Schwarz factors resident on the device, from the first call that needs them (direct J / K, the direct AO -> fragment transform,
+  // the explicit tile) to the end of the basis
+  std::shared_ptr<PairCache> pair_cache;
 };
+
+// The refusals the DF and the four-centre drivers share; who: the entry point, for the messages.
+int check_orbital(const IntBasis& orb, const char* who);       // an orbital shell beyond d: QEMB_ERR_UNSUPPORTED naming the shell and its l
+int check_c2s(const double* c2s_host, const char* who);        // the kernels skip the Cartesian -> spherical step of s and p shells: QEMB_ERR_UNSUPPORTED unless identity
+int check_thresh(double thresh, const char* who);              // a screening threshold must be >= 0 (QEMB_ERR_ARG)
+// the shell of angular momentum l that starts at record r (1 to 8 primitives: QEMB_ERR_ARG otherwise)
+int shell_of(const BfRecord& r, int l, int ao0, const std::string& who, int3c::Shell* s);
 
 enum { INT_LAYOUT_PQL = 0, INT_LAYOUT_LPQ = 1, INT_LAYOUT_PACKED = 2, INT_LAYOUT_PAIRS = 3 };
 

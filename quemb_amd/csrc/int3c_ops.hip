@@ -6,8 +6,9 @@
 // applies the Cartesian -> spherical matrices and stores each element of its block once.  The shells are read in place (const Shell&).  Per the compiler's
 // resource report the classes (0,0|0..2), (1,0|0..1), (1,1|0) and (2,0|0) use no scratch memory; all others keep part of their private arrays there (256 bytes to
 // 7.6 kB per lane, 256 VGPRs, one wave per SIMD for the high classes); l_a + l_b + l_P >= 4 runs in 64-thread workgroups ("DF integrals on the device").
+// Runtime (la, lb | lP) become template arguments in int_dispatch.h (shared with the mock's restatement); the launcher is launch_items of hip_common.h.
 #include "hip_common.h"
-#include "int3c_core.h"
+#include "int_dispatch.h"
 
 namespace qemb {
 namespace {
@@ -29,28 +30,6 @@ __global__ void __launch_bounds__(128) boys_kernel(int m_max, long long n, const
   for (int m = 0; m <= m_max; ++m) out[i * (m_max + 1) + m] = F[m];
 }
 
-template <int LA, int LB, int LP>
-int launch_class(const ClassArgs& g, hipStream_t st) {
-  const long long nitem = (long long)g.npair * g.naux_sh;
-  const int bs = LA + LB + LP >= 4 ? 64 : 128;
-  const long long nb = (nitem + bs - 1) / bs;
-  if (nb > 0x7fffffffLL) { set_error("dev_int3c_class: too many blocks in one class"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL((int3c_class_kernel<LA, LB, LP>), dim3((unsigned)nb), dim3(bs), 0, st, g, nitem);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
-}
-
-template <int LA, int LB>
-int launch_ab(int lp, const ClassArgs& g, hipStream_t st) {
-  switch (lp) {
-    case 0: return launch_class<LA, LB, 0>(g, st);
-    case 1: return launch_class<LA, LB, 1>(g, st);
-    case 2: return launch_class<LA, LB, 2>(g, st);
-    case 3: return launch_class<LA, LB, 3>(g, st);
-    default: return launch_class<LA, LB, 4>(g, st);
-  }
-}
-
 }  // namespace
 
 int dev_boys(int m_max, int64_t n, const double* x, double* out) {
@@ -67,17 +46,9 @@ int dev_int3c_class(int la, int lb, int lp, const int3c::ClassArgs& g) {
   hipStream_t st = hip_stream();
   if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
   if (int rc = int3c_check_class(la, lb, lp, g)) return rc;
-  if (g.npair == 0 || g.naux_sh == 0) return QEMB_OK;
-  switch (la * 8 + lb) {
-    case 0: return launch_ab<0, 0>(lp, g, st);
-    case 8: return launch_ab<1, 0>(lp, g, st);
-    case 9: return launch_ab<1, 1>(lp, g, st);
-    case 16: return launch_ab<2, 0>(lp, g, st);
-    case 17: return launch_ab<2, 1>(lp, g, st);
-    case 18: return launch_ab<2, 2>(lp, g, st);
-    case 24: return launch_ab<3, 0>(lp, g, st);      // l_a > 2: auxiliary shells of the metric only (int3c_check_class)
-    default: return launch_ab<4, 0>(lp, g, st);
-  }
+  return dispatch_int3c(la, lb, lp, [&](auto A, auto B, auto P) {
+    return launch_items(int3c_class_kernel<A(), B(), P()>, A() + B() + P() >= 4 ? 64 : 128, g, (long long)g.npair * g.naux_sh, "dev_int3c_class", st);
+  });
 }
 
 }  // namespace qemb

@@ -1,4 +1,7 @@
-// int4c.cpp -- driver of the four-centre AO integrals on the device (see int4c.h): shell pairs per pair class, the pair stage, one launch per canonical class.
+// int4c.cpp -- driver of the four-centre AO integrals on the device (see int4c.h): shell pairs per pair class (PairPlan, with the table that says where every
+// canonical shell pair sits), the pair stage (DevicePlan), and the four routes -- stored integrals, direct J / K, the direct AO -> fragment transform, the explicit
+// tile -- as callers of ONE walk over the canonical class pairs (for_class_pairs: the launches, their quartet count and the tile orientation), ONE census of
+// the screened quartets (census, given the screening predicate) and ONE memory guard (mem_guard).  The refusals shared with the DF driver are in int3c.h.
 #include "int4c.h"
 #include "ao2mo.h"
 #include <algorithm>
@@ -23,10 +26,13 @@ const int kLa[kNPairClass] = {0, 1, 1, 2, 2, 2}, kLb[kNPairClass] = {0, 0, 1, 0,
 struct PairPlan {
   std::vector<int32_t> a[kNPairClass], b[kNPairClass];
   std::vector<int64_t> off[kNPairClass];
+  std::vector<int> cls;          // the pair table: class and position in its class list of every pair, in the order it was added (plan_of: I (I + 1) / 2 + J)
+  std::vector<int64_t> idx;
   int64_t data_words = 0, n_pairs = 0;
   void add(const std::vector<Shell>& sh, int I, int J) {      // I >= J in the caller's order; role A: the larger l
     const bool sw = sh[I].l < sh[J].l;
     const int A = sw ? J : I, B = sw ? I : J, c = int4c::pair_class(sh[A].l, sh[B].l);
+    cls.push_back(c); idx.push_back((int64_t)a[c].size());
     a[c].push_back(A); b[c].push_back(B); off[c].push_back(data_words);
     data_words += (int64_t)sh[A].nprim * sh[B].nprim * int4c::pair_stride(sh[A].l, sh[B].l);
     ++n_pairs;
@@ -41,24 +47,15 @@ PairPlan plan_of(const IntBasis& orb) {
   return p;
 }
 
-int check_orbital(const IntBasis& orb, const char* who) {
-  for (int i = 0; i < orb.nshell; ++i)
-    if (orb.shells[i].l > int4c::kMaxLOrb) {
-      set_error(std::string(who) + ": orbital shell " + std::to_string(i) + " has l = " + std::to_string(orb.shells[i].l) + "; orbital shells beyond d are not supported");
-      return QEMB_ERR_UNSUPPORTED;
-    }
-  return 0;
-}
-
 // the plan on the device: index lists, pair stage written
 struct DevicePlan {
   DBuf d32, d64, dq, data;
   size_t o_a[kNPairClass], o_b[kNPairClass], o_off[kNPairClass];
   int64_t n[kNPairClass];
-  PairList list(int c, bool with_q) const {
+  PairList list(int c, bool with_q, int64_t first = 0, int64_t cnt = -1) const {      // the class list, or its sub-range [first, first + cnt)
     PairList l{};
-    l.a = reinterpret_cast<const int32_t*>(d32.p) + o_a[c]; l.b = reinterpret_cast<const int32_t*>(d32.p) + o_b[c];
-    l.off = reinterpret_cast<const int64_t*>(d64.p) + o_off[c]; l.q = with_q ? dq.p + o_off[c] : nullptr; l.n = n[c];
+    l.a = reinterpret_cast<const int32_t*>(d32.p) + o_a[c] + first; l.b = reinterpret_cast<const int32_t*>(d32.p) + o_b[c] + first;
+    l.off = reinterpret_cast<const int64_t*>(d64.p) + o_off[c] + first; l.q = with_q ? dq.p + o_off[c] + first : nullptr; l.n = cnt < 0 ? n[c] : cnt;
     return l;
   }
   int upload(const PairPlan& p) {      // the index lists alone (a plan whose offsets point into another plan's pair stage)
@@ -118,7 +115,7 @@ int schwarz_factors(IntBasis& orb, const PairPlan& p, const DevicePlan& d) {
 
 }  // namespace
 
-struct Int4cCache {
+struct PairCache {
   PairPlan plan;
   DevicePlan dev;
 };
@@ -130,67 +127,128 @@ int64_t int4c_out_words(int64_t N, int sym) {
   return sym == 8 ? np * (np + 1) / 2 : sym == 4 ? np * np : sym == 1 ? N * N * N * N : -1;
 }
 
+namespace {
+
+// ---- the one walk over the canonical class pairs ----
+// A side: per pair class a sub-range [first, first + cnt) of the class lists of a plan (the whole plan, a slab of it, or a list uploaded for one call).
+struct Side {
+  int64_t first[kNPairClass] = {0, 0, 0, 0, 0, 0}, cnt[kNPairClass] = {0, 0, 0, 0, 0, 0};
+};
+Side whole(const PairPlan& p) {
+  Side s;
+  for (int c = 0; c < kNPairClass; ++c) s.cnt[c] = (int64_t)p.a[c].size();
+  return s;
+}
+// One launch of the walk: bra class cb >= ket class ck, the bra range [b0, b0 + bn) and the ket range [k0, k0 + kn) of their class lists.  swapped: the bra
+// range is S's and the ket range R's (the pair of the higher class sits in the column set: computed as (S|R), stored transposed).  same: bra and ket are ONE
+// range, only the quartets with bra index >= ket index exist.  store: how a tile whose rows are R and whose columns are S receives the launch.
+struct Step {
+  int cb, ck;
+  int64_t b0, bn, k0, kn;
+  bool swapped;
+  int same, store;
+  int64_t quartets() const { return same ? bn * (bn + 1) / 2 : bn * kn; }      // the canonical shell quartets of the launch
+};
+// Every canonical shell quartet with one pair in R and one in S -- `one`: R and S are the same set (S is not read); otherwise they have no pair in common --
+// exactly once, in the orientation the class kernels need: f(step) per non-empty launch, stopping at the first error.
+template <class F>
+int for_class_pairs(const Side& R, const Side& S, bool one, F f) {
+  for (int cb = 0; cb < kNPairClass; ++cb)
+    for (int ck = 0; ck <= cb; ++ck)
+      for (int pass = 0; pass < (one || cb == ck ? 1 : 2); ++pass) {
+        const Side &B = pass ? S : R, &K = one ? R : pass ? R : S;
+        if (!B.cnt[cb] || !K.cnt[ck]) continue;
+        const Step s{cb, ck, B.first[cb], B.cnt[cb], K.first[ck], K.cnt[ck], pass == 1, one && cb == ck, one ? int4c::kTileBoth : pass ? int4c::kTileTransposed : int4c::kTileAsIs};
+        QTRY(f(s));
+      }
+  return 0;
+}
+// The census of qemb_int4c_stats: the quartets of a step that screened(cb, i, ck, j) names -- the decision of the items repeated on the host over positions in
+// the class lists of the whole plan, O(n_pairs^2): part of the call's time when thresh > 0.
+template <class P>
+int64_t census(const Step& s, P screened) {
+  int64_t n = 0;
+  for (int64_t i = s.b0; i < s.b0 + s.bn; ++i)
+    for (int64_t j = s.k0; j < (s.same ? i + 1 : s.k0 + s.kn); ++j)
+      if (screened(s.cb, i, s.ck, j)) ++n;
+  return n;
+}
+auto schwarz_screened(const IntBasis& orb, double thresh) {
+  return [&orb, thresh](int cb, int64_t i, int ck, int64_t j) { return orb.schwarz[cb][(size_t)i] * orb.schwarz[ck][(size_t)j] < thresh; };
+}
+
+// ---- the one memory guard ----
+// what the four-centre calls may take: min(free device memory, orb.int4c_mem_limit)
+struct Room { double free_b = 0.0, room = 0.0; };
+int room_of(const IntBasis& orb, Room* r) {
+  size_t free_b = 0, total_b = 0;
+  QTRY(dev_mem_info(&free_b, &total_b));
+  r->free_b = r->room = (double)free_b;
+  if (orb.int4c_mem_limit >= 0 && (double)orb.int4c_mem_limit < r->room) r->room = (double)orb.int4c_mem_limit;
+  return 0;
+}
+// Before anything is allocated: a call that takes `need` bytes in all, of which the basis holds `resident` on the device already (not asked of the free memory
+// again), is refused when need exceeds the limit or the rest the free memory.  what: what takes the memory, for the message.
+int mem_guard(const IntBasis& orb, double need, double resident, const char* who, const std::string& what) {
+  Room r;
+  QTRY(room_of(orb, &r));
+  if (!((orb.int4c_mem_limit >= 0 && need > (double)orb.int4c_mem_limit) || need - resident > r.free_b)) return 0;
+  auto bytes = [](double b) { const std::string t = std::to_string(b); return t.substr(0, t.find('.')) + " bytes"; };
+  set_error(std::string(who) + ": with N = " + std::to_string(orb.nao) + ", " + what + " take " + bytes(need) + ", more than the " + bytes(r.room) + " of device memory they may take");
+  return QEMB_ERR_ALLOC;
+}
+
+}  // namespace
+
 int int4c_guard(const IntBasis& orb, int sym, bool with_output, const char* who) {
   if (int4c_out_words(orb.nao, sym) < 0) { set_error(std::string(who) + ": sym must be 1, 4 or 8, not " + std::to_string(sym)); return QEMB_ERR_ARG; }
   QTRY(check_orbital(orb, who));
-  size_t free_b = 0, total_b = 0;
-  QTRY(dev_mem_info(&free_b, &total_b));
-  double room = (double)free_b;
-  if (orb.int4c_mem_limit >= 0 && (double)orb.int4c_mem_limit < room) room = (double)orb.int4c_mem_limit;
   const double out_b = with_output ? 8.0 * (double)int4c_out_words(orb.nao, sym) : 0.0, work_b = (double)int4c_work_bytes(orb);
-  if (out_b + work_b > room) {
-    set_error(std::string(who) + ": with N = " + std::to_string(orb.nao) + " the integrals (sym = " + std::to_string(sym) + ") take " + std::to_string(out_b * 1e-9) +
-              " GB and the pair stage " + std::to_string(work_b * 1e-9) + " GB, more than the " + std::to_string(room * 1e-9) + " GB of device memory they may take");
-    return QEMB_ERR_ALLOC;
-  }
-  return 0;
+  return mem_guard(orb, out_b + work_b, 0.0, who, "the integrals (sym = " + std::to_string(sym) + ") and the pair stage");
 }
 
 int int4c_fill(IntBasis& orb, int sym, double thresh, double* out) {
-  if (!out) { set_error("qemb_int4c2e: null output"); return QEMB_ERR_ARG; }
-  if (int4c_out_words(orb.nao, sym) < 0) { set_error("qemb_int4c2e: sym must be 1, 4 or 8, not " + std::to_string(sym)); return QEMB_ERR_ARG; }
-  if (!(thresh >= 0.0)) { set_error("qemb_int4c2e: the screening threshold must be >= 0"); return QEMB_ERR_ARG; }
-  QTRY(check_orbital(orb, "qemb_int4c2e"));
-  const PairPlan p = plan_of(orb);
+  const char* who = "qemb_int4c2e";
+  if (!out) { set_error(std::string(who) + ": null output"); return QEMB_ERR_ARG; }
+  if (int4c_out_words(orb.nao, sym) < 0) { set_error(std::string(who) + ": sym must be 1, 4 or 8, not " + std::to_string(sym)); return QEMB_ERR_ARG; }
+  QTRY(check_thresh(thresh, who));
+  QTRY(check_orbital(orb, who));
+  const PairPlan p = plan_of(orb);      // the call's own plan, released on return
   DevicePlan d;
   QTRY(d.build(p, orb.dev(), orb.dc2s));
   const bool screen = thresh > 0.0;
   if (screen) {
     int rc = schwarz_factors(orb, p, d);
     if (rc) { dev_sync(); return rc; }
-    std::vector<double> q;
-    for (int c = 0; c < kNPairClass; ++c) q.insert(q.end(), orb.schwarz[c].begin(), orb.schwarz[c].end());      // the order of the offsets list
-    QTRY(d.dq.alloc((int64_t)q.size() + 1));
-    if (!q.empty()) QTRY(dev_h2d(d.dq, q.data(), sizeof(double) * q.size()));
+    QTRY(d.upload_q(orb.schwarz));
   }
   orb.int4c_stats[0] = orb.int4c_stats[1] = 0;
-  for (int cb = 0; cb < kNPairClass; ++cb)
-    for (int ck = 0; ck <= cb; ++ck) {
-      if (!d.n[cb] || !d.n[ck]) continue;
-      ClassArgs g{};
-      g.sh = orb.dev(); g.data = d.data; g.bra = d.list(cb, screen); g.ket = d.list(ck, screen);
-      g.same = cb == ck; g.thresh = thresh; g.out = sym; g.N = orb.nao; g.dst = out;
-      if (int rc = dev_int4c_class(kLa[cb], kLb[cb], kLa[ck], kLb[ck], g)) { dev_sync(); return rc; }      // earlier launches still read the lists
-      orb.int4c_stats[0] += g.same ? d.n[cb] * (d.n[cb] + 1) / 2 : d.n[cb] * d.n[ck];
-      if (screen)      // the census of qemb_int4c_stats: a host loop over the quartets of the class pair, O(n_pairs^2) -- part of the call's time when thresh > 0
-        for (int64_t i = 0; i < d.n[cb]; ++i)
-          for (int64_t j = 0; j < (g.same ? i + 1 : d.n[ck]); ++j)
-            if (orb.schwarz[cb][(size_t)i] * orb.schwarz[ck][(size_t)j] < thresh) ++orb.int4c_stats[1];
-    }
+  const Side all = whole(p);
+  int rc = for_class_pairs(all, all, true, [&](const Step& s) {
+    ClassArgs g{};
+    g.sh = orb.dev(); g.data = d.data; g.bra = d.list(s.cb, screen); g.ket = d.list(s.ck, screen);
+    g.same = s.same; g.thresh = thresh; g.out = sym; g.N = orb.nao; g.dst = out;
+    QTRY(dev_int4c_class(kLa[s.cb], kLb[s.cb], kLa[s.ck], kLb[s.ck], g));
+    orb.int4c_stats[0] += s.quartets();
+    if (screen) orb.int4c_stats[1] += census(s, schwarz_screened(orb, thresh));
+    return 0;
+  });
+  if (rc) { dev_sync(); return rc; }      // earlier launches still read the lists
   return dev_sync();      // the work buffers are released on return
 }
 
 namespace {
-// lists, pair stage and Schwarz factors of the basis on the device, written by the first direct call (J / K or AO -> fragment transform) and kept
-int ensure_cache(IntBasis& orb) {
-  if (orb.jk_cache) return 0;
-  auto c = std::make_shared<Int4cCache>();
+// The basis's resident pair stage, lists and Schwarz factors (IntBasis::pair_cache): written by the first call that needs them -- direct J / K, the AO ->
+// fragment transform or the explicit tile -- and kept to the end of the basis
+int ensure_pair_cache(IntBasis& orb) {
+  if (orb.pair_cache) return 0;
+  auto c = std::make_shared<PairCache>();
   c->plan = plan_of(orb);
   int rc = c->dev.build(c->plan, orb.dev(), orb.dc2s);
   if (!rc) rc = schwarz_factors(orb, c->plan, c->dev);
   if (!rc) rc = c->dev.upload_q(orb.schwarz);
   if (rc) { dev_sync(); return rc; }
-  orb.jk_cache = c;
+  orb.pair_cache = c;
   return 0;
 }
 int64_t jk_small_bytes(const IntBasis& orb) { return 8 * (3 * (int64_t)orb.nao * orb.nao + (int64_t)orb.nshell * orb.nshell) + 4096; }      // D, J, K, the shell-block table
@@ -202,20 +260,12 @@ int int4c_jk_direct(IntBasis& orb, const double* dm, double thresh, double* J, d
   const char* who = "qemb_int_jk_direct";
   if (!dm) { set_error(std::string(who) + ": null density"); return QEMB_ERR_ARG; }
   if (!J && !K) { set_error(std::string(who) + ": J and K are both null"); return QEMB_ERR_ARG; }
-  if (!(thresh >= 0.0)) { set_error(std::string(who) + ": the screening threshold must be >= 0"); return QEMB_ERR_ARG; }
+  QTRY(check_thresh(thresh, who));
   QTRY(check_orbital(orb, who));
-  // the guard of qemb_int4c2e without an output term; what a cached basis holds already is not asked of the free memory again
-  size_t free_b = 0, total_b = 0;
-  QTRY(dev_mem_info(&free_b, &total_b));
-  const double need = (double)int4c_jk_bytes(orb), fresh = orb.jk_cache ? (double)jk_small_bytes(orb) : need;
-  if ((orb.int4c_mem_limit >= 0 && need > (double)orb.int4c_mem_limit) || fresh > (double)free_b) {
-    const double room = orb.int4c_mem_limit >= 0 && (double)orb.int4c_mem_limit < (double)free_b ? (double)orb.int4c_mem_limit : (double)free_b;
-    set_error(std::string(who) + ": with N = " + std::to_string(orb.nao) + " the pair stage, the lists and the N x N matrices take " + std::to_string(need * 1e-9) +
-              " GB, more than the " + std::to_string(room * 1e-9) + " GB of device memory they may take");
-    return QEMB_ERR_ALLOC;
-  }
-  QTRY(ensure_cache(orb));
-  const DevicePlan& d = orb.jk_cache->dev;
+  QTRY(mem_guard(orb, (double)int4c_jk_bytes(orb), orb.pair_cache ? (double)int4c_work_bytes(orb) : 0.0, who, "the pair stage, the lists and the N x N matrices"));
+  QTRY(ensure_pair_cache(orb));
+  const DevicePlan& d = orb.pair_cache->dev;
+  const PairPlan& p = orb.pair_cache->plan;
   const int64_t N = orb.nao, nsh = orb.nshell;
   const bool screen = thresh > 0.0;
   DBuf bD, bJ, bK, btab;
@@ -236,21 +286,21 @@ int int4c_jk_direct(IntBasis& orb, const double* dm, double thresh, double* J, d
   if (dJ) QTRY(dev_fill(dJ, N * N, 0.0));
   if (dK) QTRY(dev_fill(dK, N * N, 0.0));
   orb.int4c_stats[0] = orb.int4c_stats[1] = 0;
-  const PairPlan& p = orb.jk_cache->plan;
-  for (int cb = 0; cb < kNPairClass; ++cb)
-    for (int ck = 0; ck <= cb; ++ck) {
-      if (!d.n[cb] || !d.n[ck]) continue;
-      JkArgs g{};
-      g.sh = orb.dev(); g.data = d.data; g.bra = d.list(cb, screen); g.ket = d.list(ck, screen);
-      g.same = cb == ck; g.thresh = thresh; g.N = N; g.nshell = (int)nsh; g.dm = dD; g.dmax = screen ? btab.p : nullptr; g.J = dJ; g.K = dK;
-      if (int rc = dev_int4c_jk_class(kLa[cb], kLb[cb], kLa[ck], kLb[ck], g)) { dev_sync(); return rc; }
-      orb.int4c_stats[0] += g.same ? d.n[cb] * (d.n[cb] + 1) / 2 : d.n[cb] * d.n[ck];
-      if (screen)      // the census of qemb_int4c_stats: the decision of the items (int4c::jk_screened) repeated on the host, O(n_pairs^2) -- part of the call's time when thresh > 0
-        for (int64_t i = 0; i < d.n[cb]; ++i)
-          for (int64_t j = 0; j < (g.same ? i + 1 : d.n[ck]); ++j)
-            if (int4c::jk_screened(thresh, orb.schwarz[cb][(size_t)i], orb.schwarz[ck][(size_t)j], tab.data(), (int)nsh, p.a[cb][(size_t)i], p.b[cb][(size_t)i],
-                                   p.a[ck][(size_t)j], p.b[ck][(size_t)j])) ++orb.int4c_stats[1];
-    }
+  const Side all = whole(p);
+  int rc = for_class_pairs(all, all, true, [&](const Step& s) {
+    JkArgs g{};
+    g.sh = orb.dev(); g.data = d.data; g.bra = d.list(s.cb, screen); g.ket = d.list(s.ck, screen);
+    g.same = s.same; g.thresh = thresh; g.N = N; g.nshell = (int)nsh; g.dm = dD; g.dmax = screen ? btab.p : nullptr; g.J = dJ; g.K = dK;
+    QTRY(dev_int4c_jk_class(kLa[s.cb], kLb[s.cb], kLa[s.ck], kLb[s.ck], g));
+    orb.int4c_stats[0] += s.quartets();
+    if (screen)
+      orb.int4c_stats[1] += census(s, [&](int cb, int64_t i, int ck, int64_t j) {
+        return int4c::jk_screened(thresh, orb.schwarz[cb][(size_t)i], orb.schwarz[ck][(size_t)j], tab.data(), (int)nsh, p.a[cb][(size_t)i], p.b[cb][(size_t)i],
+                                  p.a[ck][(size_t)j], p.b[ck][(size_t)j]);
+      });
+    return 0;
+  });
+  if (rc) { dev_sync(); return rc; }
   if (dJ) QTRY(dev_mirror_lower(N, dJ, N));
   if (dK) QTRY(dev_mirror_lower(N, dK, N));
   if (!io_on_device) {
@@ -267,8 +317,7 @@ inline int64_t npair_of(int64_t n) { return n * (n + 1) / 2; }
 
 // the canonical shell pairs (I >= J, I outer: the order of plan_of) cut into slabs of at most tile_pairs AO pairs; a slab holds whole shell pairs, so the shell
 // pairs of a slab are ONE sub-range [first, first + cnt) of each class list of the plan -- no list is written for a slab
-struct Slab {
-  int64_t first[kNPairClass], cnt[kNPairClass];
+struct Slab : Side {
   int64_t rows = 0, c0 = 0;      // AO pairs of the slab; its first entry in the (mu, nu) tables
   double qmax = 0.0;             // largest Schwarz factor (filled when screening)
 };
@@ -289,21 +338,25 @@ int64_t n_ao_pairs(const Shell& A, const Shell& B, bool same) {
   return same ? na * (na + 1) / 2 : na * nb;
 }
 
-TileLayout tile_layout(const IntBasis& orb, int64_t tile_pairs, bool with_maps) {
+TileLayout tile_layout(const IntBasis& orb, const PairPlan& plan, int64_t tile_pairs, bool with_maps) {
   TileLayout t;
   if (with_maps) { const size_t np = (size_t)npair_of(orb.nao); t.pos.assign(np, -1); t.mu.assign(np, 0); t.nu.assign(np, 0); }
-  int64_t seen[kNPairClass] = {0, 0, 0, 0, 0, 0}, c = 0;
+  int64_t c = 0;
   Slab cur;
-  auto open = [&]() { cur = Slab(); for (int k = 0; k < kNPairClass; ++k) { cur.first[k] = seen[k]; cur.cnt[k] = 0; } cur.c0 = c; };
   auto close = [&]() { if (cur.rows) { t.slabs.push_back(cur); t.max_rows = std::max(t.max_rows, cur.rows); } };
-  open();
+  size_t w = 0;      // the shell pair in the order of plan_of
   for (int I = 0; I < orb.nshell; ++I)
-    for (int J = 0; J <= I; ++J) {
+    for (int J = 0; J <= I; ++J, ++w) {
       const Shell &A = orb.shells[I], &B = orb.shells[J];
       const int64_t sz = n_ao_pairs(A, B, I == J);
-      if (cur.rows && cur.rows + sz > tile_pairs) { close(); open(); }
-      const int cls = int4c::pair_class(std::max(A.l, B.l), std::min(A.l, B.l));
-      ++cur.cnt[cls]; ++seen[cls];
+      if (cur.rows && cur.rows + sz > tile_pairs) {      // the next slab opens where this one ends in every class list
+        close();
+        Slab next;
+        for (int k = 0; k < kNPairClass; ++k) next.first[k] = cur.first[k] + cur.cnt[k];
+        next.c0 = c;
+        cur = next;
+      }
+      ++cur.cnt[plan.cls[w]];
       if (with_maps)
         for_ao_pairs(A, B, I == J, [&](int64_t m, int64_t n) {      // shells are in AO order: m >= n
           t.pos[(size_t)(m * (m + 1) / 2 + n)] = (int32_t)(c - cur.c0);
@@ -317,55 +370,18 @@ TileLayout tile_layout(const IntBasis& orb, int64_t tile_pairs, bool with_maps) 
   return t;
 }
 
-// the canonical shell quartets of tile (R, S), R >= S
-int64_t tile_quartets(const Slab& R, const Slab& S, bool same) {
-  int64_t q = 0;
-  for (int cb = 0; cb < kNPairClass; ++cb)
-    for (int ck = 0; ck <= cb; ++ck) {
-      if (same) q += cb == ck ? R.cnt[cb] * (R.cnt[cb] + 1) / 2 : R.cnt[cb] * R.cnt[ck];
-      else q += R.cnt[cb] * S.cnt[ck] + (cb != ck ? S.cnt[cb] * R.cnt[ck] : 0);
-    }
-  return q;
-}
-
-struct TileSide { PairList l[kNPairClass]; };
-
-// One tile: rows = the AO pairs of the shell pairs of R, columns = those of S (R and S the same set, or disjoint).  Every canonical quartet with one pair in R
-// and one in S is evaluated once, in the orientation the class kernels need (bra class >= ket class), and lands at [row[.]][col[.]]: every element of the tile
-// is written exactly once (a screened quartet as zeros).
-int fill_tile(const IntBasis& orb, const double* data, const TileSide& R, const TileSide& S, bool same, const int32_t* row, const int32_t* col, int64_t ld,
-              double thresh, double* dst) {
-  for (int cb = 0; cb < kNPairClass; ++cb)
-    for (int ck = 0; ck <= cb; ++ck) {
-      ClassArgs g{};
-      g.sh = orb.dev(); g.data = data; g.thresh = thresh; g.out = int4c::kTile; g.N = orb.nao; g.dst = dst; g.row = row; g.col = col; g.ld = ld;
-      if (same) {
-        if (!R.l[cb].n || !R.l[ck].n) continue;
-        g.bra = R.l[cb]; g.ket = R.l[ck]; g.same = cb == ck; g.store = int4c::kTileBoth;
-        QTRY(dev_int4c_class(kLa[cb], kLb[cb], kLa[ck], kLb[ck], g));
-        continue;
-      }
-      if (R.l[cb].n && S.l[ck].n) {
-        g.bra = R.l[cb]; g.ket = S.l[ck]; g.same = 0; g.store = int4c::kTileAsIs;
-        QTRY(dev_int4c_class(kLa[cb], kLb[cb], kLa[ck], kLb[ck], g));
-      }
-      if (cb != ck && S.l[cb].n && R.l[ck].n) {      // the pair of the higher class sits in the column set: computed as (S|R), stored transposed
-        g.bra = S.l[cb]; g.ket = R.l[ck]; g.same = 0; g.store = int4c::kTileTransposed;
-        QTRY(dev_int4c_class(kLa[cb], kLb[cb], kLa[ck], kLb[ck], g));
-      }
-    }
-  return 0;
-}
-
-TileSide side_of(const DevicePlan& d, const Slab& s, bool with_q) {
-  TileSide t;
-  for (int c = 0; c < kNPairClass; ++c) {
-    PairList l = d.list(c, with_q);
-    l.a += s.first[c]; l.b += s.first[c]; l.off += s.first[c]; if (l.q) l.q += s.first[c];
-    l.n = s.cnt[c];
-    t.l[c] = l;
-  }
-  return t;
+// One tile: rows = the AO pairs of the shell pairs of R (a range of the lists of dR), columns = those of S in dS (R and S the same set, or disjoint).  Every
+// canonical quartet with one pair in R and one in S is evaluated once (for_class_pairs) and lands at [row[.]][col[.]]: every element of the tile is written
+// exactly once (a screened quartet as zeros).
+int fill_tile(const IntBasis& orb, const double* data, const DevicePlan& dR, const Side& R, const DevicePlan& dS, const Side& S, bool same, const int32_t* row,
+              const int32_t* col, int64_t ld, double thresh, double* dst) {
+  return for_class_pairs(R, S, same, [&](const Step& s) {
+    ClassArgs g{};
+    g.sh = orb.dev(); g.data = data; g.thresh = thresh; g.out = int4c::kTile; g.N = orb.nao; g.dst = dst; g.row = row; g.col = col; g.ld = ld;
+    g.bra = (s.swapped ? dS : dR).list(s.cb, thresh > 0.0, s.b0, s.bn); g.ket = (same || s.swapped ? dR : dS).list(s.ck, thresh > 0.0, s.k0, s.kn);
+    g.same = s.same; g.store = s.store;
+    return dev_int4c_class(kLa[s.cb], kLb[s.cb], kLa[s.ck], kLb[s.ck], g);
+  });
 }
 
 struct DirectSizes { int64_t sum_npq2 = 0, sum_ta = 0, npq_max = 0; };
@@ -379,19 +395,14 @@ int direct_sizes(const IntBasis& orb, int nfrag, const int* n, const char* who, 
   return 0;
 }
 // what a call holds beside the tile and the three tile-row operands: pair stage and lists, the three tables of the layout, the accumulators, the coefficients
-int64_t direct_fixed_bytes(const IntBasis& orb, const DirectSizes& z) { return int4c_work_bytes(orb) + 12 * npair_of(orb.nao) + 8 * (z.sum_npq2 + z.sum_ta) + 4096; }
+int64_t direct_fixed_bytes(const PairPlan& plan, int64_t N, const DirectSizes& z) { return plan.bytes() + 12 * npair_of(N) + 8 * (z.sum_npq2 + z.sum_ta) + 4096; }
 int64_t direct_tile_bytes(int64_t rows, const DirectSizes& z) { return 8 * (rows * rows + 3 * rows * z.npq_max); }
-double direct_room(const IntBasis& orb) {
-  size_t free_b = 0, total_b = 0;
-  if (dev_mem_info(&free_b, &total_b)) return 0.0;
-  double room = (double)free_b;
-  if (orb.int4c_mem_limit >= 0 && (double)orb.int4c_mem_limit < room) room = (double)orb.int4c_mem_limit;
-  return room;
-}
 // the default tile: the tile and its operands take at most half of what the fixed part leaves, at most 8192 AO pairs (a 512 MB tile: the products are long
 // enough for the GEMM's best rate, and a larger tile saves nothing but launches)
-int64_t default_tile_pairs(const IntBasis& orb, const DirectSizes& z) {
-  const double avail = 0.5 * (direct_room(orb) - (double)direct_fixed_bytes(orb, z)) / 8.0, m = 1.5 * (double)z.npq_max;
+int64_t default_tile_pairs(const IntBasis& orb, const PairPlan& plan, const DirectSizes& z) {
+  Room r;
+  room_of(orb, &r);      // no figure: no room, the smallest tile
+  const double avail = 0.5 * (r.room - (double)direct_fixed_bytes(plan, orb.nao, z)) / 8.0, m = 1.5 * (double)z.npq_max;
   int64_t t = avail > 0.0 ? (int64_t)(-m + std::sqrt(m * m + avail)) : 1;
   return std::max<int64_t>(1, std::min<int64_t>(t, std::min<int64_t>(npair_of(orb.nao), 8192)));
 }
@@ -404,36 +415,32 @@ int int4c_ao2mo_direct_bytes(const IntBasis& orb, int nfrag, const int* n, int64
   QTRY(check_orbital(orb, who));
   DirectSizes z;
   QTRY(direct_sizes(orb, nfrag, n, who, &z));
-  if (tile_pairs <= 0) tile_pairs = default_tile_pairs(orb, z);
-  *bytes = direct_fixed_bytes(orb, z) + direct_tile_bytes(tile_layout(orb, tile_pairs, false).max_rows, z);
+  const PairPlan plan = plan_of(orb);
+  if (tile_pairs <= 0) tile_pairs = default_tile_pairs(orb, plan, z);
+  *bytes = direct_fixed_bytes(plan, orb.nao, z) + direct_tile_bytes(tile_layout(orb, plan, tile_pairs, false).max_rows, z);
   return 0;
 }
 
 int int4c_ao2mo_direct(IntBasis& orb, int nfrag, const double* const* TA_host, const int* n, int64_t tile_pairs, double thresh, std::vector<DBuf>& out) {
   const char* who = "qemb_ao2mo_direct";
   if (!TA_host) { set_error(std::string(who) + ": null coefficients"); return QEMB_ERR_ARG; }
-  if (!(thresh >= 0.0)) { set_error(std::string(who) + ": the screening threshold must be >= 0"); return QEMB_ERR_ARG; }
+  QTRY(check_thresh(thresh, who));
   QTRY(check_orbital(orb, who));
   DirectSizes z;
   QTRY(direct_sizes(orb, nfrag, n, who, &z));
   for (int f = 0; f < nfrag; ++f)
     if (!TA_host[f]) { set_error(std::string(who) + ": null coefficients of fragment " + std::to_string(f)); return QEMB_ERR_ARG; }
-  if (tile_pairs <= 0) tile_pairs = default_tile_pairs(orb, z);
   const int64_t N = orb.nao;
-  TileLayout lay = tile_layout(orb, tile_pairs, true);
-  {      // the guard, before anything is allocated; what a cached basis holds already is not asked of the free memory again
-    size_t free_b = 0, total_b = 0;
-    QTRY(dev_mem_info(&free_b, &total_b));
-    const double need = (double)(direct_fixed_bytes(orb, z) + direct_tile_bytes(lay.max_rows, z)), fresh = need - (orb.jk_cache ? (double)int4c_work_bytes(orb) : 0.0);
-    if ((orb.int4c_mem_limit >= 0 && need > (double)orb.int4c_mem_limit) || fresh > (double)free_b) {
-      set_error(std::string(who) + ": with N = " + std::to_string(N) + ", " + std::to_string(nfrag) + " fragments and tiles of " + std::to_string(lay.max_rows) +
-                " AO pairs the call takes " + std::to_string((int64_t)need) + " bytes, more than the " + std::to_string((int64_t)direct_room(orb)) +
-                " bytes of device memory it may take");
-      return QEMB_ERR_ALLOC;
-    }
+  TileLayout lay;
+  {      // layout and guard from the plan on the host, before anything is allocated
+    const PairPlan plan = plan_of(orb);
+    if (tile_pairs <= 0) tile_pairs = default_tile_pairs(orb, plan, z);
+    lay = tile_layout(orb, plan, tile_pairs, true);
+    QTRY(mem_guard(orb, (double)(direct_fixed_bytes(plan, N, z) + direct_tile_bytes(lay.max_rows, z)), orb.pair_cache ? (double)plan.bytes() : 0.0, who,
+                   std::to_string(nfrag) + " fragments and tiles of " + std::to_string(lay.max_rows) + " AO pairs"));
   }
-  QTRY(ensure_cache(orb));
-  const DevicePlan& d = orb.jk_cache->dev;
+  QTRY(ensure_pair_cache(orb));
+  const DevicePlan& d = orb.pair_cache->dev;
   const bool screen = thresh > 0.0;
   if (screen)
     for (Slab& s : lay.slabs)
@@ -461,23 +468,18 @@ int int4c_ao2mo_direct(IntBasis& orb, int nfrag, const double* const* TA_host, c
     for (int64_t s = 0; s <= r; ++s) {      // a fixed order and no atomics: the same bits run to run
       const Slab &R = lay.slabs[(size_t)r], &S = lay.slabs[(size_t)s];
       const bool same = r == s;
-      const int64_t nq = tile_quartets(R, S, same);
+      const bool skip = screen && R.qmax * S.qmax < thresh;      // every quartet of the tile is below the threshold: the tile counts as zeros
+      int64_t nq = 0, nscr = 0;
+      for_class_pairs(R, S, same, [&](const Step& st) {
+        nq += st.quartets();
+        if (screen && !skip) nscr += census(st, schwarz_screened(orb, thresh));
+        return 0;
+      });
       orb.int4c_stats[0] += nq;
-      if (screen && R.qmax * S.qmax < thresh) {      // every quartet of the tile is below the threshold: the tile counts as zeros
-        orb.int4c_stats[1] += nq; ++orb.int4c_tiles[1];
-        continue;
-      }
-      ++orb.int4c_tiles[0];
-      if (int rc = fill_tile(orb, d.data, side_of(d, R, screen), side_of(d, S, screen), same, dpos, dpos, S.rows, thresh, E)) { dev_sync(); return rc; }
-      if (screen)      // the census of qemb_int4c_stats, as in int4c_fill: a host loop over the quartets of the tile
-        for (int cb = 0; cb < kNPairClass; ++cb)
-          for (int ck = 0; ck <= cb; ++ck)
-            for (int pass = 0; pass < (same || cb == ck ? 1 : 2); ++pass) {
-              const Slab &B = pass ? S : R, &K = pass ? R : S;
-              for (int64_t i = B.first[cb]; i < B.first[cb] + B.cnt[cb]; ++i)
-                for (int64_t j = K.first[ck]; j < (same && cb == ck ? i + 1 : K.first[ck] + K.cnt[ck]); ++j)
-                  if (orb.schwarz[cb][(size_t)i] * orb.schwarz[ck][(size_t)j] < thresh) ++orb.int4c_stats[1];
-            }
+      orb.int4c_stats[1] += skip ? nq : nscr;
+      ++orb.int4c_tiles[skip ? 1 : 0];
+      if (skip) continue;
+      if (int rc = fill_tile(orb, d.data, d, R, d, S, same, dpos, dpos, S.rows, thresh, E)) { dev_sync(); return rc; }
       const TileRows tr{dmu + R.c0, dnu + R.c0, R.rows}, ts{dmu + S.c0, dnu + S.c0, S.rows};
       for (int f = 0; f < nfrag; ++f)
         if (int rc = ao2mo_tile_accumulate(E, S.rows, tr, ts, same, dTA[(size_t)f], n[f], PR, PS, T, out[(size_t)f])) { dev_sync(); return rc; }
@@ -490,7 +492,7 @@ int int4c_ao2mo_direct(IntBasis& orb, int nfrag, const double* const* TA_host, c
 int int4c_tile(IntBasis& orb, const int32_t* pr, int64_t nr, const int32_t* ps, int64_t nsp, double thresh, double* out_host) {
   const char* who = "qemb_op_int4c_tile";
   if (!pr || !ps || nr <= 0 || nsp <= 0 || !out_host) { set_error(std::string(who) + ": bad arguments"); return QEMB_ERR_ARG; }
-  if (!(thresh >= 0.0)) { set_error(std::string(who) + ": the screening threshold must be >= 0"); return QEMB_ERR_ARG; }
+  QTRY(check_thresh(thresh, who));
   QTRY(check_orbital(orb, who));
   const int64_t nsh = orb.nshell, np = npair_of(orb.nao);
   // the two sets: canonical shell pairs (I >= J), none twice; the same list on both sides, or no pair in common
@@ -508,19 +510,9 @@ int int4c_tile(IntBasis& orb, const int32_t* pr, int64_t nr, const int32_t* ps, 
       if (side && !same && inR[(size_t)(I * (I + 1) / 2 + J)]) { set_error(std::string(who) + ": the two sets must be the same list or have no shell pair in common"); return QEMB_ERR_ARG; }
     }
   }
-  QTRY(ensure_cache(orb));
-  const PairPlan& full = orb.jk_cache->plan;
-  // class and position in its class list of every canonical shell pair, in the order of plan_of
-  std::vector<int> cls((size_t)npair_of(nsh)); std::vector<int64_t> idx((size_t)npair_of(nsh));
-  {
-    int64_t seen[kNPairClass] = {0, 0, 0, 0, 0, 0};
-    for (int64_t I = 0, k = 0; I < nsh; ++I)
-      for (int64_t J = 0; J <= I; ++J, ++k) {
-        const int la = orb.shells[(size_t)I].l, lb = orb.shells[(size_t)J].l;
-        cls[(size_t)k] = int4c::pair_class(std::max(la, lb), std::min(la, lb)); idx[(size_t)k] = seen[cls[(size_t)k]]++;
-      }
-  }
-  PairPlan sub[2];
+  QTRY(ensure_pair_cache(orb));
+  const PairPlan& full = orb.pair_cache->plan;
+  PairPlan sub[2];      // the listed shell pairs in list order, looked up in the pair table of the plan
   std::vector<double> q[2][kNPairClass];
   std::vector<int32_t> map[2];
   int64_t rows[2] = {0, 0};
@@ -529,7 +521,7 @@ int int4c_tile(IntBasis& orb, const int32_t* pr, int64_t nr, const int32_t* ps, 
     map[side].assign((size_t)np, -1);
     for (int64_t k = 0; k < (side ? nsp : nr); ++k) {
       const int64_t I = p[2 * k], J = p[2 * k + 1], w = I * (I + 1) / 2 + J;
-      const int c = cls[(size_t)w]; const size_t i = (size_t)idx[(size_t)w];
+      const int c = full.cls[(size_t)w]; const size_t i = (size_t)full.idx[(size_t)w];
       sub[side].a[c].push_back(full.a[c][i]); sub[side].b[c].push_back(full.b[c][i]); sub[side].off[c].push_back(full.off[c][i]);
       q[side][c].push_back(orb.schwarz[c][i]);
       for_ao_pairs(orb.shells[(size_t)I], orb.shells[(size_t)J], I == J, [&](int64_t m, int64_t n) { map[side][(size_t)(m * (m + 1) / 2 + n)] = (int32_t)rows[side]++; });
@@ -540,14 +532,12 @@ int int4c_tile(IntBasis& orb, const int32_t* pr, int64_t nr, const int32_t* ps, 
   QTRY(maps.alloc(np + 2));
   int32_t* drow = reinterpret_cast<int32_t*>(maps.p);
   int32_t* dcol = drow + np;
-  TileSide side[2];
   for (int k = 0; k < 2; ++k) {
     QTRY(dl[k].upload(sub[k])); QTRY(dl[k].upload_q(q[k]));
     QTRY(dev_h2d(k ? dcol : drow, map[k].data(), sizeof(int32_t) * np));
-    for (int c = 0; c < kNPairClass; ++c) side[k].l[c] = dl[k].list(c, thresh > 0.0);
   }
   QTRY(E.alloc(rows[0] * rows[1]));
-  if (int rc = fill_tile(orb, orb.jk_cache->dev.data, side[0], side[1], same, drow, dcol, rows[1], thresh, E)) { dev_sync(); return rc; }
+  if (int rc = fill_tile(orb, orb.pair_cache->dev.data, dl[0], whole(sub[0]), dl[1], whole(sub[1]), same, drow, dcol, rows[1], thresh, E)) { dev_sync(); return rc; }
   QTRY(dev_d2h(out_host, E, sizeof(double) * rows[0] * rows[1]));
   return dev_sync();
 }
@@ -559,19 +549,9 @@ int int4c_block(const int l[4], const BfRecord* const rec[4], const double* c2s_
       set_error("qemb_op_int4c_class: unsupported angular class (" + std::to_string(l[0]) + "," + std::to_string(l[1]) + "|" + std::to_string(l[2]) + "," + std::to_string(l[3]) + ")");
       return QEMB_ERR_UNSUPPORTED;
     }
-  for (int k = 0; k < 10; ++k)
-    if (c2s_host[k] != ((k == 0 || k == 1 || k == 5 || k == 9) ? 1.0 : 0.0)) {
-      set_error("qemb_op_int4c_class: the Cartesian -> spherical matrices of l = 0 and l = 1 must be the identity (p functions in x, y, z order)");
-      return QEMB_ERR_UNSUPPORTED;
-    }
+  QTRY(check_c2s(c2s_host, "qemb_op_int4c_class"));
   std::vector<Shell> sh(4);
-  for (int k = 0; k < 4; ++k) {
-    if (rec[k]->nprim < 1 || rec[k]->nprim > int3c::kMaxPrim) { set_error("qemb_op_int4c_class: 1 to 8 primitives per contraction"); return QEMB_ERR_ARG; }
-    sh[k] = Shell{};
-    for (int d = 0; d < 3; ++d) sh[k].r[d] = rec[k]->ctr[d];
-    sh[k].l = l[k]; sh[k].nprim = rec[k]->nprim; sh[k].ao0 = 0;
-    for (int i = 0; i < rec[k]->nprim; ++i) { sh[k].ex[i] = rec[k]->ex[i]; sh[k].co[i] = rec[k]->co[i]; }
-  }
+  for (int k = 0; k < 4; ++k) QTRY(shell_of(*rec[k], l[k], 0, "qemb_op_int4c_class", &sh[k]));
   // canonical roles: inside each pair the larger l first, the pair of the higher class as the bra; the block is put back into the caller's order on the host
   int r[4] = {0, 1, 2, 3};
   if (l[0] < l[1]) std::swap(r[0], r[1]);

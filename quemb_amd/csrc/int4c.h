@@ -14,15 +14,15 @@ namespace qemb {
 int64_t int4c_work_bytes(const IntBasis& orb);
 // doubles of the output in form sym (8, 4 or 1); -1 for another sym
 int64_t int4c_out_words(int64_t N, int sym);
-// Compared with min(free device memory, orb.int4c_mem_limit) before anything is allocated: the work space, plus the output when the call allocates it.
-// QEMB_ERR_ALLOC with N in the message.  An orbital shell with l > 2: QEMB_ERR_UNSUPPORTED naming the shell.  who: the entry point, for the messages.
+// The guard of the stored forms, before anything is allocated: the work space, plus the output when the call allocates it, against min(free device memory,
+// orb.int4c_mem_limit) -- the one guard of int4c.cpp (mem_guard), which the direct calls apply to their own figures.  QEMB_ERR_ALLOC with N in the message.  An orbital shell with l > 2: QEMB_ERR_UNSUPPORTED naming the shell.  who: the entry point, for the messages.
 int int4c_guard(const IntBasis& orb, int sym, bool with_output, const char* who);
 // (mu nu|la si) into out_dev in form sym.  thresh > 0: quartets with Q_ab Q_cd < thresh are stored as zeros (Q from the device, cached in the basis);
 // orb.int4c_stats receives the canonical shell quartets and how many of them were screened.
 int int4c_fill(IntBasis& orb, int sym, double thresh, double* out_dev);
 // Integral-direct J[mu,nu] = sum (mu nu|la si) D[la,si] and K[mu,la] = sum (mu nu|la si) D[nu,si] for a symmetric D: every canonical quartet is evaluated and
 // contracted in the thread that evaluated it (dev_int4c_jk_class); nothing of size N^4 exists.  The first call on a basis writes the pair stage and the Schwarz
-// factors and keeps them with the lists on the device (orb.jk_cache); later calls issue the class launches and the O(N^2) passes only.  J or K may be null.
+// factors and keeps them with the lists on the device (orb.pair_cache); later calls issue the class launches and the O(N^2) passes only.  J or K may be null.
 // thresh > 0 skips a quartet with Q_ab Q_cd < thresh or Q_ab Q_cd max|D| < thresh (max over the six shell blocks of D the quartet reads); orb.int4c_stats as
 // for int4c_fill.  The sums are accumulated with FP64 atomic adds: J and K are symmetric to the bit but not bit-reproducible from run to run.
 int64_t int4c_jk_bytes(const IntBasis& orb);      // device bytes of a call: pair stage, lists, Schwarz factors, the N x N matrices and the shell-block table
@@ -33,7 +33,7 @@ int int4c_jk_direct(IntBasis& orb, const double* dm, double thresh, double* J, d
 // in total) and each fragment consumes it, T = E_RS P_S, A += P_R^T T (ao2mo_tile_accumulate; R = S weighted 1/2); at the end G = A + A^T.  Fixed loop order, no
 // atomics: bit-reproducible.  tile_pairs <= 0: chosen from the free memory.  thresh > 0: quartets screened as in int4c_fill, and a tile with max Q_R max Q_S < thresh
 // is skipped altogether.  orb.int4c_stats as for int4c_fill (the quartets of a skipped tile count as screened), orb.int4c_tiles: tiles visited, tiles skipped.
-// Pair stage, lists and Schwarz factors are those of orb.jk_cache.  out[f]: npair(n_f)^2 doubles on the device, allocated here.
+// Pair stage, lists and Schwarz factors are those of orb.pair_cache.  out[f]: npair(n_f)^2 doubles on the device, allocated here.
 // bytes: the device footprint of a call -- compared with min(free memory, orb.int4c_mem_limit) before anything is allocated (QEMB_ERR_ALLOC).
 int int4c_ao2mo_direct_bytes(const IntBasis& orb, int nfrag, const int* n, int64_t tile_pairs, int64_t* bytes);
 int int4c_ao2mo_direct(IntBasis& orb, int nfrag, const double* const* TA_host, const int* n, int64_t tile_pairs, double thresh, std::vector<DBuf>& out);

@@ -10,8 +10,9 @@
 // contracted with the density into the lower triangles of J and K by FP64 atomic adds instead of stored ("Integral-direct J and K").
 // The class kernel also writes a tile of the 4-fold packed tensor (kTile, a runtime branch of the same 21 instantiations); int4c_pairprod_kernel and
 // int4c_addt_kernel are the two element-wise passes of the transform that consumes the tiles ("Integral-direct AO -> fragment transform").
+// Runtime (la, lb | lc, ld) become template arguments in int_dispatch.h (shared with the mock's restatement); every class goes through one launcher (launch_items).
 #include "hip_common.h"
-#include "int4c_core.h"
+#include "int_dispatch.h"
 
 namespace qemb {
 namespace {
@@ -58,67 +59,7 @@ __global__ void __launch_bounds__(256) int4c_addt_kernel(double* A, const long l
   for (long long i = blockIdx.y; i < m; i += gridDim.y) addt_item(A, m, i, j);
 }
 
-template <int LA, int LB>
-int launch_pairs(const PairArgs& g, hipStream_t st) {
-  const long long nitem = (long long)g.pairs.n * kPrimPairs, nb = (nitem + 127) / 128;
-  if (nb > 0x7fffffffLL) { set_error("dev_int4c_pairs: too many shell pairs in one class"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL((int4c_pair_kernel<LA, LB>), dim3((unsigned)nb), dim3(128), 0, st, g, nitem);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
-}
-
-template <int LA, int LB, int LC, int LD>
-int launch_class(const ClassArgs& g, hipStream_t st) {
-  const long long nitem = class_items<LC, LD>(g);
-  const int bs = LA + LB + LC + LD >= 4 ? 64 : 128;
-  const long long nb = (nitem + bs - 1) / bs;
-  if (nb > 0x7fffffffLL) { set_error("dev_int4c_class: too many blocks in one class"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL((int4c_class_kernel<LA, LB, LC, LD>), dim3((unsigned)nb), dim3(bs), 0, st, g, nitem);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
-}
-
-template <int LA, int LB, int LC, int LD>
-int launch_jk(const JkArgs& g, hipStream_t st) {
-  const long long nitem = jk_items<LC, LD>(g);
-  const int bs = LA + LB + LC + LD >= 4 ? 64 : 128;
-  const long long nb = (nitem + bs - 1) / bs;
-  if (nb > 0x7fffffffLL) { set_error("dev_int4c_jk_class: too many blocks in one class"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL((int4c_jk_kernel<LA, LB, LC, LD>), dim3((unsigned)nb), dim3(bs), 0, st, g, nitem);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
-}
-
-template <int LA, int LB>
-int launch_jk_bra(int kc, const JkArgs& g, hipStream_t st) {
-  constexpr int bc = pair_class(LA, LB);
-  switch (kc) {
-    case 0: return launch_jk<LA, LB, 0, 0>(g, st);
-    case 1: if constexpr (bc >= 1) return launch_jk<LA, LB, 1, 0>(g, st); break;
-    case 2: if constexpr (bc >= 2) return launch_jk<LA, LB, 1, 1>(g, st); break;
-    case 3: if constexpr (bc >= 3) return launch_jk<LA, LB, 2, 0>(g, st); break;
-    case 4: if constexpr (bc >= 4) return launch_jk<LA, LB, 2, 1>(g, st); break;
-    case 5: if constexpr (bc >= 5) return launch_jk<LA, LB, 2, 2>(g, st); break;
-  }
-  set_error("dev_int4c_jk_class: not a canonical class");
-  return QEMB_ERR_UNSUPPORTED;
-}
-
-// the ket pair classes up to the bra's: only canonical classes are instantiated
-template <int LA, int LB>
-int launch_bra(int kc, const ClassArgs& g, hipStream_t st) {
-  constexpr int bc = pair_class(LA, LB);
-  switch (kc) {
-    case 0: return launch_class<LA, LB, 0, 0>(g, st);
-    case 1: if constexpr (bc >= 1) return launch_class<LA, LB, 1, 0>(g, st); break;
-    case 2: if constexpr (bc >= 2) return launch_class<LA, LB, 1, 1>(g, st); break;
-    case 3: if constexpr (bc >= 3) return launch_class<LA, LB, 2, 0>(g, st); break;
-    case 4: if constexpr (bc >= 4) return launch_class<LA, LB, 2, 1>(g, st); break;
-    case 5: if constexpr (bc >= 5) return launch_class<LA, LB, 2, 2>(g, st); break;
-  }
-  set_error("dev_int4c_class: not a canonical class");
-  return QEMB_ERR_UNSUPPORTED;
-}
+constexpr int quartet_block(int L) { return L >= 4 ? 64 : 128; }      // the launch bound of the class and digest kernels
 
 }  // namespace
 
@@ -126,47 +67,28 @@ int dev_int4c_pairs(int la, int lb, const int4c::PairArgs& g) {
   hipStream_t st = hip_stream();
   if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
   if (int rc = int4c_check_pairs(la, lb, g)) return rc;
-  if (g.pairs.n == 0) return QEMB_OK;
-  switch (pair_class(la, lb)) {
-    case 0: return launch_pairs<0, 0>(g, st);
-    case 1: return launch_pairs<1, 0>(g, st);
-    case 2: return launch_pairs<1, 1>(g, st);
-    case 3: return launch_pairs<2, 0>(g, st);
-    case 4: return launch_pairs<2, 1>(g, st);
-    default: return launch_pairs<2, 2>(g, st);
-  }
+  return dispatch_pair(pair_class(la, lb), [&](auto A, auto B) {
+    return launch_items(int4c_pair_kernel<A(), B()>, 128, g, (long long)g.pairs.n * kPrimPairs, "dev_int4c_pairs", st);
+  });
 }
 
+// the stored forms and the digest form: two callers of one dispatcher and one launcher, which differ in kernel and item count
 int dev_int4c_class(int la, int lb, int lc, int ld, const int4c::ClassArgs& g) {
   hipStream_t st = hip_stream();
   if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
   if (int rc = int4c_check_class(la, lb, lc, ld, g)) return rc;
-  if (g.bra.n == 0 || g.ket.n == 0) return QEMB_OK;
-  const int kc = pair_class(lc, ld);
-  switch (pair_class(la, lb)) {
-    case 0: return launch_bra<0, 0>(kc, g, st);
-    case 1: return launch_bra<1, 0>(kc, g, st);
-    case 2: return launch_bra<1, 1>(kc, g, st);
-    case 3: return launch_bra<2, 0>(kc, g, st);
-    case 4: return launch_bra<2, 1>(kc, g, st);
-    default: return launch_bra<2, 2>(kc, g, st);
-  }
+  return dispatch_quartet(pair_class(la, lb), pair_class(lc, ld), "dev_int4c_class", [&](auto A, auto B, auto C, auto D) {
+    return launch_items(int4c_class_kernel<A(), B(), C(), D()>, quartet_block(A() + B() + C() + D()), g, (long long)class_items<C(), D()>(g), "dev_int4c_class", st);
+  });
 }
 
 int dev_int4c_jk_class(int la, int lb, int lc, int ld, const int4c::JkArgs& g) {
   hipStream_t st = hip_stream();
   if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
   if (int rc = int4c_check_jk(la, lb, lc, ld, g)) return rc;
-  if (g.bra.n == 0 || g.ket.n == 0) return QEMB_OK;
-  const int kc = pair_class(lc, ld);
-  switch (pair_class(la, lb)) {
-    case 0: return launch_jk_bra<0, 0>(kc, g, st);
-    case 1: return launch_jk_bra<1, 0>(kc, g, st);
-    case 2: return launch_jk_bra<1, 1>(kc, g, st);
-    case 3: return launch_jk_bra<2, 0>(kc, g, st);
-    case 4: return launch_jk_bra<2, 1>(kc, g, st);
-    default: return launch_jk_bra<2, 2>(kc, g, st);
-  }
+  return dispatch_quartet(pair_class(la, lb), pair_class(lc, ld), "dev_int4c_jk_class", [&](auto A, auto B, auto C, auto D) {
+    return launch_items(int4c_jk_kernel<A(), B(), C(), D()>, quartet_block(A() + B() + C() + D()), g, (long long)jk_items<C(), D()>(g), "dev_int4c_jk_class", st);
+  });
 }
 
 int dev_int4c_pairprod(const int4c::PairProdArgs& g) {

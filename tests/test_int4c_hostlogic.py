@@ -23,7 +23,7 @@ def hlib():
 
 @pytest.mark.parametrize("ls", [(0, 0, 0, 0), (1, 0, 0, 0), (2, 0, 0, 0), (1, 0, 1, 0), (1, 1, 1, 0), (2, 0, 1, 1), (2, 1, 2, 0), (2, 2, 2, 2)], ids=lambda c: "%d%d%d%d" % c)
 def test_class_against_host_source(hlib, ls):
-    """a low, the mixed and the highest class (all 21 run on the device)"""
+    """a low, the mixed and the highest class (all 21 run on the device, chosen by the same dispatcher, csrc/int_dispatch.h; all 21 take 24 s on the mock)"""
     cases.check_class(hlib, ls)
 
 
@@ -38,7 +38,7 @@ def test_unit_s_cases_cover_every_class_in_both_orders():
     assert got == {(a, b, p) for a in range(3) for b in range(3) for p in range(3)}
 
 
-@pytest.mark.parametrize("pc", [(0, 0), (2, 1), (2, 2)], ids=lambda c: "%d%d" % c)
+@pytest.mark.parametrize("pc", cases.PAIR_CLASSES, ids=lambda c: "%d%d" % c)
 def test_ss_ket_by_the_product_rule(hlib, pc):
     cases.check_ss_ket(hlib, *pc)
 

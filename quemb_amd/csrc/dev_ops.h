@@ -20,7 +20,12 @@ namespace qemb {
 void set_error(const std::string& msg);
 const char* last_error();
 
-// status codes: QEMB_OK / QEMB_ERR_* from the public header
+// status codes: QEMB_OK / QEMB_ERR_* from the public header; QTRY hands the first failure to the caller
+#define QTRY(expr)              \
+  do {                          \
+    int _rc = (expr);           \
+    if (_rc != 0) return _rc;   \
+  } while (0)
 
 
 // ---- device / memory -----------------------------------------------------------------------

@@ -441,8 +441,7 @@ int dev_d2d(void* dst, const void* src, size_t bytes) {
   REQUIRE_INIT();
   if (g_capturing && bytes % 8 == 0 && ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 7) == 0) {
     const long long n = (long long)(bytes / 8);
-    if (n > 0) hipLaunchKernelGGL(copy_words_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 4096)), dim3(256), 0, g_stream, (double*)dst, (const double*)src, n);
-    HIP_TRY(hipGetLastError());
+    if (n > 0) QTRY(launch("dev_d2d", copy_words_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 4096)), dim3(256), 0, g_stream, (double*)dst, (const double*)src, n));
     return QEMB_OK;
   }
   HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, g_stream));
@@ -533,18 +532,13 @@ int dev_graph_launch(dev_graph_t g) { REQUIRE_INIT(); HIP_TRY(hipGraphLaunch((hi
 int dev_graph_destroy(dev_graph_t g) { if (g) (void)hipGraphExecDestroy((hipGraphExec_t)g); return QEMB_OK; }
 
 // ---- grouped launches --------------------------------------------------------------------------------------------------------------
-// A kernel written as `__device__ name_body(BID, GDIM, args...)` + a one-line `__global__ name(args...)` wrapper can also run GROUPED: one
-// launch whose grid is the concatenation of the members' grids; a workgroup finds its member, takes that member's arguments from a table
-// in device memory and runs the body with its block index inside that member.  Kernels are registered by the address of their wrapper,
-// which is what a captured graph node carries.
+// A kernel written as `__device__ name_body(BID, GDIM, args...)` + a one-line `__global__ name(args...)` wrapper + one registrar under the
+// wrapper, `static const Groupable<name_body, 256> reg_name(name);`, can also run GROUPED: one launch whose grid is the concatenation of the
+// members' grids; a workgroup finds its member, takes that member's arguments from the table in the kernel-argument segment and runs the body
+// with its block index inside that member.  Kernels are registered by the address of their wrapper, which is what a captured graph node
+// carries; the registrars run when the library is loaded, so the map below is complete before anything reads it (grouped_launch.h).
 std::map<const void*, GroupInfo>& groupable() { static std::map<const void*, GroupInfo> m; return m; }
 bool group_xcd_mode() { static const bool on = [] { const char* e = std::getenv("QEMB_GROUP_XCD"); return e && e[0] != '0'; }(); return on; }
-void register_groupable_gemm();         // gemm_f64.hip
-static void register_groupable_kernels();   // end of this file (after the kernels)
-static void ensure_groupable_registered() {
-  static std::once_flag once;
-  std::call_once(once, [] { register_groupable_kernels(); register_groupable_gemm(); });
-}
 
 // ---- tapes: captured launch sequences executed together -------------------------------------------------------------------------------
 // A tape keeps the captured hipGraph alive (it owns the argument storage of its nodes) and lists the nodes in execution order.
@@ -635,7 +629,6 @@ int dev_tape_equal(dev_tape_t ap, dev_tape_t bp) {
   auto differ = [&](size_t i, const char* what) { set_error("tapes differ at operation " + std::to_string(i) + ": " + what); return 0; };
   if (!a || !b) return differ(0, "no tape");
   if (a->nodes.size() != b->nodes.size()) return differ(0, "number of operations");
-  ensure_groupable_registered();
   std::vector<unsigned char> xa, xb;
   for (size_t i = 0; i < a->nodes.size(); ++i) {
     const TapeNode& x = a->nodes[i]; const TapeNode& y = b->nodes[i];
@@ -760,7 +753,6 @@ static std::vector<TapeSegment> tape_segments(const Tape* t) {
 }
 
 static int build_plan(const dev_tape_t* tapes, int n, TapePlan** out) {
-  ensure_groupable_registered();
   static const bool grouping = !(std::getenv("QEMB_TAPE_GROUP") && std::atoi(std::getenv("QEMB_TAPE_GROUP")) == 0);
   const bool regions_on = regions_enabled();
   TapePlan* plan = new TapePlan();
@@ -1019,10 +1011,8 @@ int dev_abs_overlap_prim(int nsh, const int* l, const double* ex, const double* 
                          const double* roots, const double* weights, double* out) {
   REQUIRE_INIT();
   if (nsh <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(abs_overlap_prim_kernel, dim3((unsigned)nsh, (unsigned)nsh), dim3(256), 0, g_stream, nsh, l, ex, xyz,
-                     (const long long*)cart0, (long long)ncart, nroots, roots, weights, out);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_abs_overlap_prim", abs_overlap_prim_kernel, dim3((unsigned)nsh, (unsigned)nsh), dim3(256), 0, g_stream, nsh, l, ex, xyz,
+                (const long long*)cart0, ncart, nroots, roots, weights, out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1033,14 +1023,13 @@ __device__ __forceinline__ void fill_kernel_body(const uint3 BID, const uint3 GD
   const long long stride = (long long)GDIM.x * blockDim.x;
   for (; i < n; i += stride) x[i] = v;
 }
-__global__ void fill_kernel(double* x, long long n, double v) { fill_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), x, n, v); }
+__global__ void fill_kernel(double* x, long long n, double v) { fill_kernel_body(block_id(), grid_dim(), x, n, v); }
+static const Groupable<fill_kernel_body, 1024> reg_fill(fill_kernel);
 int dev_fill(double* x, int64_t n, double value) {
   REQUIRE_INIT();
   if (n <= 0) return QEMB_OK;
   const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
-  hipLaunchKernelGGL(fill_kernel, dim3(grid), dim3(256), 0, g_stream, x, (long long)n, value);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_fill", fill_kernel, dim3(grid), dim3(256), 0, g_stream, x, n, value);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1073,7 +1062,8 @@ __device__ __forceinline__ void copy4_linear_kernel_body(const uint3 BID, const 
     }
   }
 }
-__global__ void __launch_bounds__(256) copy4_linear_kernel(Copy4K c) { copy4_linear_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), c); }
+__global__ void __launch_bounds__(256) copy4_linear_kernel(Copy4K c) { copy4_linear_kernel_body(block_id(), grid_dim(), c); }
+static const Groupable<copy4_linear_kernel_body, 256> reg_copy4_linear(copy4_linear_kernel);
 
 // dims canonicalised so that si3 == 1 (input contiguous along i3) and so2 == 1 (output contiguous along i2)
 __device__ __forceinline__ void copy4_transpose_kernel_body(const uint3 BID, const uint3 GDIM, Copy4K c, int tiles3) {
@@ -1106,7 +1096,8 @@ __device__ __forceinline__ void copy4_transpose_kernel_body(const uint3 BID, con
     }
   }
 }
-__global__ void __launch_bounds__(256) copy4_transpose_kernel(Copy4K c, int tiles3) { copy4_transpose_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), c, tiles3); }
+__global__ void __launch_bounds__(256) copy4_transpose_kernel(Copy4K c, int tiles3) { copy4_transpose_kernel_body(block_id(), grid_dim(), c, tiles3); }
+static const Groupable<copy4_transpose_kernel_body, 256> reg_copy4_transpose(copy4_transpose_kernel);
 
 int dev_copy4(const Copy4Desc& cd) {
   REQUIRE_INIT();
@@ -1138,14 +1129,11 @@ int dev_copy4(const Copy4Desc& cd) {
   if (transpose) {
     const long long tiles2 = (c.d2 + 31) / 32, tiles3 = (c.d3 + 31) / 32;
     if (tiles2 * tiles3 > 0x7fffffffLL) { set_error("dev_copy4: too many tiles"); return QEMB_ERR_ARG; }
-    hipLaunchKernelGGL(copy4_transpose_kernel, dim3((unsigned)(tiles2 * tiles3), gy, gz), dim3(256), 0, g_stream, c, (int)tiles3);
-  } else {
-    const long long n23 = c.d2 * c.d3;
-    const unsigned gx = (unsigned)std::min<long long>((n23 + 255) / 256, 1 << 20);
-    hipLaunchKernelGGL(copy4_linear_kernel, dim3(gx, gy, gz), dim3(256), 0, g_stream, c);
+    return launch("dev_copy4", copy4_transpose_kernel, dim3((unsigned)(tiles2 * tiles3), gy, gz), dim3(256), 0, g_stream, c, (int)tiles3);
   }
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  const long long n23 = c.d2 * c.d3;
+  const unsigned gx = (unsigned)std::min<long long>((n23 + 255) / 256, 1 << 20);
+  return launch("dev_copy4", copy4_linear_kernel, dim3(gx, gy, gz), dim3(256), 0, g_stream, c);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1166,16 +1154,15 @@ __device__ __forceinline__ void outer4_kernel_body(const uint3 BID, const uint3 
         c.out[off] = (c.beta != 0.0) ? val + c.beta * c.base[off] : val;
       }
 }
-__global__ void __launch_bounds__(256) outer4_kernel(Outer4K c) { outer4_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), c); }
+__global__ void __launch_bounds__(256) outer4_kernel(Outer4K c) { outer4_kernel_body(block_id(), grid_dim(), c); }
+static const Groupable<outer4_kernel_body, 256> reg_outer4(outer4_kernel);
 int dev_outer4(const Outer4Desc& o) {
   REQUIRE_INIT();
   for (int k = 0; k < 4; ++k) if (o.dim[k] <= 0) return QEMB_OK;
   Outer4K c{o.dim[0], o.dim[1], o.dim[2], o.dim[3], o.su0, o.su2, o.sv1, o.sv3, o.so[0], o.so[1], o.so[2], o.so[3], o.u, o.v, o.out, o.alpha, o.beta, o.base ? o.base : o.out};
   const long long n23 = c.d2 * c.d3;
   const unsigned gx = (unsigned)std::min<long long>((n23 + 255) / 256, 1 << 20);
-  hipLaunchKernelGGL(outer4_kernel, dim3(gx, (unsigned)std::min<long long>(c.d1, 65535), (unsigned)std::min<long long>(c.d0, 65535)), dim3(256), 0, g_stream, c);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_outer4", outer4_kernel, dim3(gx, (unsigned)std::min<long long>(c.d1, 65535), (unsigned)std::min<long long>(c.d0, 65535)), dim3(256), 0, g_stream, c);
 }
 
 __device__ __forceinline__ void div_denom_kernel_body(const uint3 BID, const uint3 GDIM, double* x, long long d0, long long d1, long long d2, long long d3,
@@ -1192,16 +1179,15 @@ __device__ __forceinline__ void div_denom_kernel_body(const uint3 BID, const uin
     }
 }
 __global__ void __launch_bounds__(256) div_denom_kernel(double* x, long long d0, long long d1, long long d2, long long d3,
-                                                        const double* ea, const double* eb, const double* ec, const double* ed) { div_denom_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), x, d0, d1, d2, d3, ea, eb, ec, ed); }
+                                                        const double* ea, const double* eb, const double* ec, const double* ed) { div_denom_kernel_body(block_id(), grid_dim(), x, d0, d1, d2, d3, ea, eb, ec, ed); }
+static const Groupable<div_denom_kernel_body, 256> reg_div_denom(div_denom_kernel);
 int dev_div_denom(double* x, int64_t d0, int64_t d1, int64_t d2, int64_t d3, const double* ea, const double* eb, const double* ec, const double* ed) {
   REQUIRE_INIT();
   if (d0 <= 0 || d1 <= 0 || d2 <= 0 || d3 <= 0) return QEMB_OK;
   const long long n23 = d2 * d3;
   const unsigned gx = (unsigned)std::min<long long>((n23 + 255) / 256, 1 << 20);
-  hipLaunchKernelGGL(div_denom_kernel, dim3(gx, (unsigned)std::min<long long>(d1, 65535), (unsigned)std::min<long long>(d0, 65535)), dim3(256), 0, g_stream,
-                     x, (long long)d0, (long long)d1, (long long)d2, (long long)d3, ea, eb, ec, ed);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_div_denom", div_denom_kernel, dim3(gx, (unsigned)std::min<long long>(d1, 65535), (unsigned)std::min<long long>(d0, 65535)), dim3(256), 0, g_stream,
+                x, d0, d1, d2, d3, ea, eb, ec, ed);
 }
 
 // ---- screening helpers (semi-sparse DF) --------------------------------------------------------------------------
@@ -1212,9 +1198,7 @@ __global__ void threshold_mask_kernel(long long n, const double* __restrict__ x,
 int dev_threshold_mask(int64_t n, const double* x, double eps, double* out) {
   REQUIRE_INIT();
   if (n <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(threshold_mask_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, g_stream, (long long)n, x, eps, out);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_threshold_mask", threshold_mask_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, g_stream, n, x, eps, out);
 }
 __global__ void __launch_bounds__(256) mul_bcast_rows_kernel(long long rows, long long cols, double* __restrict__ x, const double* __restrict__ m) {
   for (long long r = blockIdx.y; r < rows; r += gridDim.y)
@@ -1224,10 +1208,8 @@ __global__ void __launch_bounds__(256) mul_bcast_rows_kernel(long long rows, lon
 int dev_mul_bcast_rows(int64_t rows, int64_t cols, double* x, const double* m) {
   REQUIRE_INIT();
   if (rows <= 0 || cols <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(mul_bcast_rows_kernel, dim3((unsigned)std::min<int64_t>((cols + 255) / 256, 1024), (unsigned)std::min<int64_t>(rows, 65535)), dim3(256), 0, g_stream,
-                     (long long)rows, (long long)cols, x, m);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_mul_bcast_rows", mul_bcast_rows_kernel, dim3((unsigned)std::min<int64_t>((cols + 255) / 256, 1024), (unsigned)std::min<int64_t>(rows, 65535)), dim3(256), 0, g_stream,
+                rows, cols, x, m);
 }
 
 // one 32 x 32 tile (c-range, b-range) of one (k, j) pair per workgroup: X = t2[k,j] is read as the tile and as the mirrored tile
@@ -1274,16 +1256,15 @@ __device__ __forceinline__ void ccsd_ph_layouts_kernel_body(const uint3 BID, con
 }
 __global__ void __launch_bounds__(256) ccsd_ph_layouts_kernel(long long o, long long v, const double* __restrict__ t2, const double* __restrict__ t1,
                                                               double* __restrict__ T, double* __restrict__ Tp, double* __restrict__ S,
-                                                              double* __restrict__ Ut, double* __restrict__ Tpt, double* __restrict__ Th, int tiles) { ccsd_ph_layouts_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, v, t2, t1, T, Tp, S, Ut, Tpt, Th, tiles); }
+                                                              double* __restrict__ Ut, double* __restrict__ Tpt, double* __restrict__ Th, int tiles) { ccsd_ph_layouts_kernel_body(block_id(), grid_dim(), o, v, t2, t1, T, Tp, S, Ut, Tpt, Th, tiles); }
+static const Groupable<ccsd_ph_layouts_kernel_body, 256> reg_ccsd_ph_layouts(ccsd_ph_layouts_kernel);
 int dev_ccsd_ph_layouts(int64_t o, int64_t v, const double* t2, const double* t1, double* T, double* Tp, double* S, double* Ut, double* Tpt, double* Th) {
   REQUIRE_INIT();
   if (o <= 0 || v <= 0) return QEMB_OK;
   if (o > 65535) { set_error("dev_ccsd_ph_layouts: too many occupied orbitals"); return QEMB_ERR_ARG; }
   const long long tiles_c = (v + 31) / 32, tiles = (v + 15 + 31) / 32;      // b-tiles: one more may be needed for the line-aligning shift (<= 15)
-  hipLaunchKernelGGL(ccsd_ph_layouts_kernel, dim3((unsigned)(tiles_c * tiles), (unsigned)o, (unsigned)o), dim3(256), 0, g_stream, (long long)o, (long long)v, t2, t1,
-                     T, Tp, S, Ut, Tpt, Th, (int)tiles);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_ccsd_ph_layouts", ccsd_ph_layouts_kernel, dim3((unsigned)(tiles_c * tiles), (unsigned)o, (unsigned)o), dim3(256), 0, g_stream, o, v, t2, t1,
+                T, Tp, S, Ut, Tpt, Th, (int)tiles);
 }
 
 __device__ __forceinline__ void small_k_update_kernel_body(const uint3 BID, const uint3 GDIM, long long M, long long N, long long K, double alpha, const double* __restrict__ A, long long sA,
@@ -1322,7 +1303,8 @@ __device__ __forceinline__ void small_k_update_kernel_body(const uint3 BID, cons
   }
 }
 __global__ void __launch_bounds__(256) small_k_update_kernel(long long M, long long N, long long K, double alpha, const double* __restrict__ A, long long sA,
-                                                             const double* __restrict__ B, long long sB, double* __restrict__ C, long long sC, int tiles_n) { small_k_update_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), M, N, K, alpha, A, sA, B, sB, C, sC, tiles_n); }
+                                                             const double* __restrict__ B, long long sB, double* __restrict__ C, long long sC, int tiles_n) { small_k_update_kernel_body(block_id(), grid_dim(), M, N, K, alpha, A, sA, B, sB, C, sC, tiles_n); }
+static const Groupable<small_k_update_kernel_body, 256> reg_small_k_update(small_k_update_kernel);
 // The same update on the matrix pipe (M, N >= 16, K <= 64): 2 K M N flop per batch entry is
 // 6.4 GFLOP for the rank-n_occ updates of the o^2 v^2 tensors -- 100 us of FP64 VALU time, which is what the tile version above and a
 // VALU strip version both take, twice the HBM time of the 256 MB they move.  B[z] (K x N) and the
@@ -1373,7 +1355,8 @@ __device__ __forceinline__ void small_k_update_mfma_kernel_body(const uint3 BID,
   }
 }
 __global__ void __launch_bounds__(256) small_k_update_mfma_kernel(int M, int N, int K, double alpha, const double* __restrict__ A, long long sA,
-                                                                  const double* __restrict__ B, long long sB, double* __restrict__ C, long long sC) { small_k_update_mfma_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), M, N, K, alpha, A, sA, B, sB, C, sC); }
+                                                                  const double* __restrict__ B, long long sB, double* __restrict__ C, long long sC) { small_k_update_mfma_kernel_body(block_id(), grid_dim(), M, N, K, alpha, A, sA, B, sB, C, sC); }
+static const Groupable<small_k_update_mfma_kernel_body, 256> reg_small_k_update_mfma(small_k_update_mfma_kernel);
 int dev_small_k_update(int64_t batch, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t sA, const double* B, int64_t sB,
                        double* C, int64_t sC) {
   REQUIRE_INIT();
@@ -1381,16 +1364,12 @@ int dev_small_k_update(int64_t batch, int64_t M, int64_t N, int64_t K, double al
   if (batch > 65535) { set_error("dev_small_k_update: batch too large"); return QEMB_ERR_ARG; }
   if (N >= 16 && M >= 16 && K <= 64 && M <= (1 << 20) && N <= (1 << 20)) {
     const long long items = ((M + 31) / 32) * ((N + 15) / 16);
-    hipLaunchKernelGGL(small_k_update_mfma_kernel, dim3((unsigned)((items + 3) / 4), (unsigned)batch), dim3(256), 0, g_stream, (int)M, (int)N, (int)K, alpha,
-                       A, (long long)sA, B, (long long)sB, C, (long long)sC);
-    HIP_TRY(hipGetLastError());
-    return QEMB_OK;
+    return launch("dev_small_k_update", small_k_update_mfma_kernel, dim3((unsigned)((items + 3) / 4), (unsigned)batch), dim3(256), 0, g_stream, (int)M, (int)N, (int)K, alpha,
+                  A, sA, B, sB, C, sC);
   }
   const long long tiles_m = (M + 31) / 32, tiles_n = (N + 31) / 32;
-  hipLaunchKernelGGL(small_k_update_kernel, dim3((unsigned)(tiles_m * tiles_n), (unsigned)batch), dim3(256), 0, g_stream, (long long)M, (long long)N, (long long)K, alpha,
-                     A, (long long)sA, B, (long long)sB, C, (long long)sC, (int)tiles_n);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_small_k_update", small_k_update_kernel, dim3((unsigned)(tiles_m * tiles_n), (unsigned)batch), dim3(256), 0, g_stream, M, N, K, alpha,
+                A, sA, B, sB, C, sC, (int)tiles_n);
 }
 
 // sum of the S split-K slabs of one element, in slab order (what the reduction pass forms); the common counts are spelled out so that their loads are
@@ -1434,13 +1413,12 @@ __device__ __forceinline__ void ccsd_y_traces_kernel_body(const uint3 BID, const
   if (in && q == 0) Y[idx] = add ? s + scale * slab_sum(add + idx, S, stride) : s;
 }
 __global__ void __launch_bounds__(256) ccsd_y_traces_kernel(long long o, long long v, const double* __restrict__ ZC, const double* __restrict__ ZB,
-                                                            double* __restrict__ Y, const double* __restrict__ add, int S, long long stride, double scale) { ccsd_y_traces_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, v, ZC, ZB, Y, add, S, stride, scale); }
+                                                            double* __restrict__ Y, const double* __restrict__ add, int S, long long stride, double scale) { ccsd_y_traces_kernel_body(block_id(), grid_dim(), o, v, ZC, ZB, Y, add, S, stride, scale); }
+static const Groupable<ccsd_y_traces_kernel_body, 256> reg_ccsd_y_traces(ccsd_y_traces_kernel);
 int dev_ccsd_y_traces(int64_t o, int64_t v, const double* ZC, const double* ZB, double* Y, const double* add, int S, int64_t stride, double scale) {
   REQUIRE_INIT();
   if (v <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(ccsd_y_traces_kernel, dim3((unsigned)((v * v * 8 + 255) / 256)), dim3(256), 0, g_stream, (long long)o, (long long)v, ZC, ZB, Y, add, std::max(S, 1), (long long)stride, scale);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_ccsd_y_traces", ccsd_y_traces_kernel, dim3((unsigned)((v * v * 8 + 255) / 256)), dim3(256), 0, g_stream, o, v, ZC, ZB, Y, add, std::max(S, 1), stride, scale);
 }
 
 // one row per blockIdx.y (grid-stride), 256 threads stride along the row: reads and writes are contiguous runs of `len` doubles
@@ -1457,10 +1435,8 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(long long nrows, long 
 int dev_gather_rows(int64_t nrows, int64_t len, const int64_t* idx_dev, const double* src, int64_t ld, double* dst) {
   REQUIRE_INIT();
   if (nrows <= 0 || len <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)std::min<int64_t>((len + 255) / 256, 64), (unsigned)std::min<int64_t>(nrows, 65535)), dim3(256), 0, g_stream,
-                     (long long)nrows, (long long)len, (const long long*)idx_dev, src, (long long)ld, dst);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_gather_rows", gather_rows_kernel, dim3((unsigned)std::min<int64_t>((len + 255) / 256, 64), (unsigned)std::min<int64_t>(nrows, 65535)), dim3(256), 0, g_stream,
+                nrows, len, (const long long*)idx_dev, src, ld, dst);
 }
 __global__ void __launch_bounds__(256) scale_rows_kernel(long long nrows, long long len, double* __restrict__ x, const double* __restrict__ s) {
   for (long long r = blockIdx.y; r < nrows; r += gridDim.y) {
@@ -1473,10 +1449,8 @@ __global__ void __launch_bounds__(256) scale_rows_kernel(long long nrows, long l
 int dev_scale_rows(int64_t nrows, int64_t len, double* x, const double* s) {
   REQUIRE_INIT();
   if (nrows <= 0 || len <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(scale_rows_kernel, dim3((unsigned)std::min<int64_t>((len + 255) / 256, 64), (unsigned)std::min<int64_t>(nrows, 65535)), dim3(256), 0, g_stream,
-                     (long long)nrows, (long long)len, x, s);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_scale_rows", scale_rows_kernel, dim3((unsigned)std::min<int64_t>((len + 255) / 256, 64), (unsigned)std::min<int64_t>(nrows, 65535)), dim3(256), 0, g_stream,
+                nrows, len, x, s);
 }
 
 __global__ void __launch_bounds__(256) mirror_lower_kernel(long long n, double* __restrict__ A, long long lda) {
@@ -1504,9 +1478,7 @@ int dev_mirror_lower(int64_t n, double* A, int64_t lda) {
   REQUIRE_INIT();
   if (n <= 1) return QEMB_OK;
   const long long nt = (n + 31) / 32;
-  hipLaunchKernelGGL(mirror_lower_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, g_stream, (long long)n, A, (long long)lda);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_mirror_lower", mirror_lower_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, g_stream, n, A, lda);
 }
 
 struct LincombK { const double* x[8]; double c[8]; int n; };
@@ -1518,7 +1490,8 @@ __device__ __forceinline__ void lincomb_kernel_body(const uint3 BID, const uint3
     out[t] = acc;
   }
 }
-__global__ void __launch_bounds__(256) lincomb_kernel(long long n, LincombK k, double beta, double* __restrict__ out) { lincomb_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), n, k, beta, out); }
+__global__ void __launch_bounds__(256) lincomb_kernel(long long n, LincombK k, double beta, double* __restrict__ out) { lincomb_kernel_body(block_id(), grid_dim(), n, k, beta, out); }
+static const Groupable<lincomb_kernel_body, 256> reg_lincomb(lincomb_kernel);
 int dev_lincomb(int64_t n, int nterms, const double* coef, const double* const* xs, double beta, double* out) {
   REQUIRE_INIT();
   if (n <= 0) return QEMB_OK;
@@ -1527,9 +1500,7 @@ int dev_lincomb(int64_t n, int nterms, const double* coef, const double* const* 
   k.n = nterms;
   for (int q = 0; q < nterms; ++q) { k.x[q] = xs[q]; k.c[q] = coef[q]; }
   const long long blocks = std::min<long long>((n + 255) / 256, 256 * 16);
-  hipLaunchKernelGGL(lincomb_kernel, dim3((unsigned)blocks), dim3(256), 0, g_stream, (long long)n, k, beta, out);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_lincomb", lincomb_kernel, dim3((unsigned)blocks), dim3(256), 0, g_stream, n, k, beta, out);
 }
 
 // ---- pair-packed MO transformation helpers --------------------------------------------------------------------------
@@ -1553,10 +1524,8 @@ int dev_pack_pair_rows(int64_t n, int64_t ncols, const double* in, double* out) 
   REQUIRE_INIT();
   const long long np = n * (n + 1) / 2;
   if (np <= 0 || ncols <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(pack_pair_rows_kernel, dim3((unsigned)std::min<long long>((ncols + 255) / 256, 256), (unsigned)std::min<long long>(np, 65535)), dim3(256), 0, g_stream,
-                     (long long)n, (long long)ncols, in, out);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_pack_pair_rows", pack_pair_rows_kernel, dim3((unsigned)std::min<long long>((ncols + 255) / 256, 256), (unsigned)std::min<long long>(np, 65535)), dim3(256), 0, g_stream,
+                n, ncols, in, out);
 }
 // ---- gathers from the pair-first MO tensor ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) extract_pf_kernel(long long n, const double* __restrict__ Mp, long long p0, long long q0, long long r0, long long s0,
@@ -1575,10 +1544,8 @@ __global__ void __launch_bounds__(256) extract_pf_kernel(long long n, const doub
 int dev_extract_pf(int64_t n, const double* Mp, int64_t p0, int64_t q0, int64_t r0, int64_t s0, int64_t sp, int64_t sq, int64_t sr, int64_t ss, double* out) {
   REQUIRE_INIT();
   if (sp <= 0 || sq <= 0 || sr <= 0 || ss <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(extract_pf_kernel, dim3((unsigned)std::min<int64_t>(sp * sq, 1 << 20)), dim3(256), 0, g_stream, (long long)n, Mp, (long long)p0, (long long)q0,
-                     (long long)r0, (long long)s0, (long long)sp, (long long)sq, (long long)sr, (long long)ss, out);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_extract_pf", extract_pf_kernel, dim3((unsigned)std::min<int64_t>(sp * sq, 1 << 20)), dim3(256), 0, g_stream, n, Mp, p0, q0,
+                r0, s0, sp, sq, sr, ss, out);
 }
 // out[x][r][s][c] = T[P(r0+r,s0+s)][c0+c][x0+x]: one workgroup per (r,s) slab reads the sc x sx corner (rows of sx contiguous doubles)
 __global__ void __launch_bounds__(256) extract_pf_t_kernel(long long n, const double* __restrict__ T, long long x0, long long r0, long long s0, long long c0,
@@ -1597,10 +1564,8 @@ int dev_extract_pf_t(int64_t n, const double* T, int64_t x0, int64_t r0, int64_t
   if (sx <= 0 || sr <= 0 || ss <= 0 || sc <= 0) return QEMB_OK;
   if (slab <= 0) slab = n * n;          // (a pair's slab holds all n rows; the factor route of mo_transform keeps only the first nf)
   if (c0 + sc > slab / n) { set_error("dev_extract_pf_t: rows beyond the slab"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL(extract_pf_t_kernel, dim3((unsigned)std::min<int64_t>(sr * ss, 1 << 20)), dim3(256), 0, g_stream, (long long)n, T, (long long)x0, (long long)r0,
-                     (long long)s0, (long long)c0, (long long)sx, (long long)sr, (long long)ss, (long long)sc, out, (long long)slab);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_extract_pf_t", extract_pf_t_kernel, dim3((unsigned)std::min<int64_t>(sr * ss, 1 << 20)), dim3(256), 0, g_stream, n, T, x0, r0,
+                s0, c0, sx, sr, ss, sc, out, slab);
 }
 // one workgroup per output row P(a,b); for every c the two source runs (d = 0..c) are contiguous:
 //   (ac|bd) = Mp[P(va,vc)][vb][vd],   (ad|bc) = (bc|ad) = Mp[P(vb,vc)][va][vd]
@@ -1641,9 +1606,7 @@ int dev_ladder_pack_vvvv_pf(int64_t n, int64_t o, const double* Mp, double* Vp, 
   REQUIRE_INIT();
   const long long v = n - o, np = v * (v + 1) / 2;
   if (np <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(ladder_pack_vvvv_pf_kernel, dim3((unsigned)std::min<long long>(np, 1 << 20)), dim3(256), 0, g_stream, (long long)n, (long long)o, Mp, Vp, (long long)ldp, Vm, (long long)ldm);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_ladder_pack_vvvv_pf", ladder_pack_vvvv_pf_kernel, dim3((unsigned)std::min<long long>(np, 1 << 20)), dim3(256), 0, g_stream, n, o, Mp, Vp, ldp, Vm, ldm);
 }
 
 // ---- (+/-) packed ladder ------------------------------------------------------------------------------------
@@ -1670,9 +1633,7 @@ int dev_ladder_pack_vvvv(int64_t n, int64_t o, const double* M, double* Vp, int6
   REQUIRE_INIT();
   const long long v = n - o, np = v * (v + 1) / 2;
   if (np <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(ladder_pack_vvvv_kernel, dim3((unsigned)std::min<long long>(np, 1 << 20)), dim3(256), 0, g_stream, (long long)n, (long long)o, M, Vp, (long long)ldp, Vm, (long long)ldm);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_ladder_pack_vvvv", ladder_pack_vvvv_kernel, dim3((unsigned)std::min<long long>(np, 1 << 20)), dim3(256), 0, g_stream, n, o, M, Vp, ldp, Vm, ldm);
 }
 // (+/-) pair packing of the last two indices of v x v slabs through LDS tiles (round 3).  The element-wise kernels below read in[c][d] along d
 // but in[d][c] with a stride of v doubles -- one cache line per lane -- and spend a double-precision square root per element on the pair
@@ -1685,7 +1646,7 @@ __global__ void __launch_bounds__(256) pack_pm_tiled_kernel(long long rows, long
                                                             long long ldp, double* __restrict__ Om, long long ldm) {
   __shared__ double tB[32][33];       // only the mirror tile goes through LDS; the straight tile stays in the registers of the threads that write it
   const long long np = v * (v + 1) / 2, nm = v * (v - 1) / 2;
-  const uint3 LB = xcd_logical_block(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z));
+  const uint3 LB = xcd_logical_block(block_id(), grid_dim());
   long long tc, td; unpair_ge((long long)LB.x, tc, td);
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const bool diag = (tc == td);
@@ -1753,22 +1714,19 @@ __device__ __forceinline__ void ladder_pack_tau_kernel_body(const uint3 BID, con
   if (tm && BID.y == 0) for (long long q = nm + threadIdx.x; q < ldm; q += blockDim.x) tm[q] = 0.0;
 }
 __global__ void __launch_bounds__(256) ladder_pack_tau_kernel(long long o, long long v, const double* __restrict__ tau,
-                                                             double* __restrict__ Tp, long long ldp, double* __restrict__ Tm, long long ldm) { ladder_pack_tau_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, v, tau, Tp, ldp, Tm, ldm); }
+                                                             double* __restrict__ Tp, long long ldp, double* __restrict__ Tm, long long ldm) { ladder_pack_tau_kernel_body(block_id(), grid_dim(), o, v, tau, Tp, ldp, Tm, ldm); }
+static const Groupable<ladder_pack_tau_kernel_body, 256> reg_ladder_pack_tau(ladder_pack_tau_kernel);
 int dev_ladder_pack_tau(int64_t o, int64_t v, const double* tau, double* Tp, int64_t ldp, double* Tm, int64_t ldm) {
   REQUIRE_INIT();
   const long long npo = o * (o + 1) / 2;
   if (npo <= 0 || v <= 0) return QEMB_OK;
   if (v >= 32) {
     const long long nt = (v + 31) / 32;
-    hipLaunchKernelGGL(pack_pm_tiled_kernel<1>, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)std::min<long long>(npo, 65535)), dim3(256), 0, g_stream,
-                       npo, (long long)o, (long long)v, tau, Tp, (long long)ldp, Tm, (long long)ldm);
-    HIP_TRY(hipGetLastError());
-    return QEMB_OK;
+    return launch("dev_ladder_pack_tau", pack_pm_tiled_kernel<1>, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)std::min<long long>(npo, 65535)), dim3(256), 0, g_stream,
+                  npo, o, v, tau, Tp, ldp, Tm, ldm);
   }
   const unsigned slices = (unsigned)std::max<long long>(1, std::min<long long>(16, ldp / 2048));
-  hipLaunchKernelGGL(ladder_pack_tau_kernel, dim3((unsigned)npo, slices), dim3(256), 0, g_stream, (long long)o, (long long)v, tau, Tp, (long long)ldp, Tm, (long long)ldm);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_ladder_pack_tau", ladder_pack_tau_kernel, dim3((unsigned)npo, slices), dim3(256), 0, g_stream, o, v, tau, Tp, ldp, Tm, ldm);
 }
 __global__ void __launch_bounds__(256) pack_pm_cols_kernel(long long rows, long long v, const double* __restrict__ in, double* __restrict__ Op, long long ldp,
                                                           double* __restrict__ Om, long long ldm) {
@@ -1792,14 +1750,10 @@ int dev_pack_pm_cols(int64_t rows, int64_t v, const double* in, double* Op, int6
   if (rows <= 0 || v <= 0) return QEMB_OK;
   if (v >= 32) {
     const long long nt = (v + 31) / 32;
-    hipLaunchKernelGGL(pack_pm_tiled_kernel<0>, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)std::min<int64_t>(rows, 16384)), dim3(256), 0, g_stream,
-                       (long long)rows, 0LL, (long long)v, in, Op, (long long)ldp, Om, (long long)ldm);
-    HIP_TRY(hipGetLastError());
-    return QEMB_OK;
+    return launch("dev_pack_pm_cols", pack_pm_tiled_kernel<0>, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)std::min<int64_t>(rows, 16384)), dim3(256), 0, g_stream,
+                  rows, 0LL, v, in, Op, ldp, Om, ldm);
   }
-  hipLaunchKernelGGL(pack_pm_cols_kernel, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(256), 0, g_stream, (long long)rows, (long long)v, in, Op, (long long)ldp, Om, (long long)ldm);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_pack_pm_cols", pack_pm_cols_kernel, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(256), 0, g_stream, rows, v, in, Op, ldp, Om, ldm);
 }
 __device__ __forceinline__ void scatter_pm_rows_kernel_body(const uint3 BID, const uint3 GDIM, long long o, long long ncols, const double* __restrict__ Xp, const double* __restrict__ Xm, double* __restrict__ out, const double* __restrict__ add,
                                                             int Sp, long long strideP, int Sm, long long strideM) {
@@ -1817,15 +1771,14 @@ __device__ __forceinline__ void scatter_pm_rows_kernel_body(const uint3 BID, con
     else oij[c] = add ? aij[c] + p : p;
   }
 }
-__global__ void __launch_bounds__(256) scatter_pm_rows_kernel(long long o, long long ncols, const double* __restrict__ Xp, const double* __restrict__ Xm, double* __restrict__ out, const double* __restrict__ add, int Sp, long long strideP, int Sm, long long strideM) { scatter_pm_rows_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, ncols, Xp, Xm, out, add, Sp, strideP, Sm, strideM); }
+__global__ void __launch_bounds__(256) scatter_pm_rows_kernel(long long o, long long ncols, const double* __restrict__ Xp, const double* __restrict__ Xm, double* __restrict__ out, const double* __restrict__ add, int Sp, long long strideP, int Sm, long long strideM) { scatter_pm_rows_kernel_body(block_id(), grid_dim(), o, ncols, Xp, Xm, out, add, Sp, strideP, Sm, strideM); }
+static const Groupable<scatter_pm_rows_kernel_body, 256> reg_scatter_pm_rows(scatter_pm_rows_kernel);
 int dev_scatter_pm_rows(int64_t o, int64_t ncols, const double* Xp, const double* Xm, double* out, const double* add, int Sp, int64_t strideP, int Sm, int64_t strideM) {
   REQUIRE_INIT();
   const long long npo = o * (o + 1) / 2;
   if (npo <= 0 || ncols <= 0) return QEMB_OK;
   if (npo > 65535) { set_error("dev_scatter_pm_rows: too many pairs"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL(scatter_pm_rows_kernel, dim3((unsigned)std::min<long long>((ncols + 255) / 256, 64), (unsigned)npo), dim3(256), 0, g_stream, (long long)o, (long long)ncols, Xp, Xm, out, add, std::max(Sp, 1), (long long)strideP, std::max(Sm, 1), (long long)strideM);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_scatter_pm_rows", scatter_pm_rows_kernel, dim3((unsigned)std::min<long long>((ncols + 255) / 256, 64), (unsigned)npo), dim3(256), 0, g_stream, o, ncols, Xp, Xm, out, add, std::max(Sp, 1), strideP, std::max(Sm, 1), strideM);
 }
 // grid (32 x 32 tiles of (a,b), o*o): U[j,i,b,a] is read with a fastest (coalesced) and transposed through LDS
 __device__ __forceinline__ void ccsd_finish_t2_kernel_body(const uint3 BID, const uint3 GDIM, long long o, long long v, double* __restrict__ t2n, const double* __restrict__ U,
@@ -1856,15 +1809,14 @@ __device__ __forceinline__ void ccsd_finish_t2_kernel_body(const uint3 BID, cons
   }
 }
 __global__ void __launch_bounds__(256) ccsd_finish_t2_kernel(long long o, long long v, double* __restrict__ t2n, const double* __restrict__ U,
-                                                            const double* __restrict__ OV, const double* __restrict__ eo, const double* __restrict__ ev) { ccsd_finish_t2_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, v, t2n, U, OV, eo, ev); }
+                                                            const double* __restrict__ OV, const double* __restrict__ eo, const double* __restrict__ ev) { ccsd_finish_t2_kernel_body(block_id(), grid_dim(), o, v, t2n, U, OV, eo, ev); }
+static const Groupable<ccsd_finish_t2_kernel_body, 256> reg_ccsd_finish_t2(ccsd_finish_t2_kernel);
 int dev_ccsd_finish_t2(int64_t o, int64_t v, double* t2n, const double* U, const double* OV, const double* eo, const double* ev) {
   REQUIRE_INIT();
   if (o <= 0 || v <= 0) return QEMB_OK;
   if (o * o > 65535) { set_error("dev_ccsd_finish_t2: too many occupied pairs"); return QEMB_ERR_ARG; }
   const long long nt = (v + 31) / 32;
-  hipLaunchKernelGGL(ccsd_finish_t2_kernel, dim3((unsigned)(nt * nt), (unsigned)(o * o)), dim3(256), 0, g_stream, (long long)o, (long long)v, t2n, U, OV, eo, ev);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_ccsd_finish_t2", ccsd_finish_t2_kernel, dim3((unsigned)(nt * nt), (unsigned)(o * o)), dim3(256), 0, g_stream, o, v, t2n, U, OV, eo, ev);
 }
 // finish_t2 with the two ring products taken where the GEMMs left them ([o][v][o][v]) and every (i >= j) PAIR of tiles handled once: the tile (ta,tb) of
 // t2n[i,j] and the tile (tb,ta) of t2n[j,i] are transposes of each other, so one workgroup reads the ten operand tiles, forms the 32 x 32 result once and
@@ -1926,16 +1878,15 @@ __device__ __forceinline__ void ccsd_finish_t2_rings_kernel_body(const uint3 BID
 __global__ void __launch_bounds__(256) ccsd_finish_t2_rings_kernel(long long o, long long v, double* __restrict__ t2n, const double* __restrict__ U, const double* __restrict__ OV,
                                                                   const double* __restrict__ RS, const double* __restrict__ M, const double* __restrict__ eo,
                                                                   const double* __restrict__ ev, double* __restrict__ t1n) {
-  ccsd_finish_t2_rings_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, v, t2n, U, OV, RS, M, eo, ev, t1n);
+  ccsd_finish_t2_rings_kernel_body(block_id(), grid_dim(), o, v, t2n, U, OV, RS, M, eo, ev, t1n);
 }
+static const Groupable<ccsd_finish_t2_rings_kernel_body, 256> reg_ccsd_finish_t2_rings(ccsd_finish_t2_rings_kernel);
 int dev_ccsd_finish_t2_rings(int64_t o, int64_t v, double* t2n, const double* U, const double* OV, const double* RS, const double* M, const double* eo, const double* ev, double* t1n) {
   REQUIRE_INIT();
   if (o <= 0 || v <= 0) return QEMB_OK;
   const long long npo = o * (o + 1) / 2, nt = (v + 31) / 32;
   if (npo > 65535) { set_error("dev_ccsd_finish_t2_rings: too many occupied pairs"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL(ccsd_finish_t2_rings_kernel, dim3((unsigned)(nt * nt), (unsigned)npo), dim3(256), 0, g_stream, (long long)o, (long long)v, t2n, U, OV, RS, M, eo, ev, t1n);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_ccsd_finish_t2_rings", ccsd_finish_t2_rings_kernel, dim3((unsigned)(nt * nt), (unsigned)npo), dim3(256), 0, g_stream, o, v, t2n, U, OV, RS, M, eo, ev, t1n);
 }
 // grid (lower-triangle 32 x 32 tiles of (a,b), npair(o)): the tile of R+/R- is staged through LDS so that both the [a][b] image
 // and its mirror [b][a] are updated in 256-byte runs, for t2[i,j] and t2[j,i].
@@ -1992,7 +1943,8 @@ __device__ __forceinline__ void ladder_scatter_pm_kernel_body(const uint3 BID, c
 __global__ void __launch_bounds__(256) ladder_scatter_pm_kernel(long long o, long long v, const double* __restrict__ Rp, long long ldp,
                                                                const double* __restrict__ Rm, long long ldm, double* __restrict__ t2,
                                                                const double* __restrict__ Hp, const double* __restrict__ Hm, int assign,
-                                                               int Sp, long long strideP, int Sm, long long strideM, long long ldhp, long long ldhm) { ladder_scatter_pm_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, v, Rp, ldp, Rm, ldm, t2, Hp, Hm, assign, Sp, strideP, Sm, strideM, ldhp, ldhm); }
+                                                               int Sp, long long strideP, int Sm, long long strideM, long long ldhp, long long ldhm) { ladder_scatter_pm_kernel_body(block_id(), grid_dim(), o, v, Rp, ldp, Rm, ldm, t2, Hp, Hm, assign, Sp, strideP, Sm, strideM, ldhp, ldhm); }
+static const Groupable<ladder_scatter_pm_kernel_body, 256> reg_ladder_scatter_pm(ladder_scatter_pm_kernel);
 int dev_ladder_scatter_pm2(int64_t o, int64_t v, const double* Rp, int64_t ldp, const double* Rm, int64_t ldm, const double* Hp, const double* Hm,
                            int assign, double* t2, int Sp, int64_t strideP, int Sm, int64_t strideM, int64_t ldhp, int64_t ldhm) {
   REQUIRE_INIT();
@@ -2000,10 +1952,8 @@ int dev_ladder_scatter_pm2(int64_t o, int64_t v, const double* Rp, int64_t ldp, 
   if (npo <= 0 || v <= 0) return QEMB_OK;
   if (npo > 65535) { set_error("dev_ladder_scatter_pm: too many pairs"); return QEMB_ERR_ARG; }
   const long long nt = (v + 31) / 32;
-  hipLaunchKernelGGL(ladder_scatter_pm_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)npo), dim3(256), 0, g_stream, (long long)o, (long long)v, Rp, (long long)ldp, Rm, (long long)ldm, t2,
-                     Hp, Hm, assign, std::max(Sp, 1), (long long)strideP, std::max(Sm, 1), (long long)strideM, (long long)(ldhp ? ldhp : ldp), (long long)(ldhm ? ldhm : ldm));
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_ladder_scatter_pm2", ladder_scatter_pm_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)npo), dim3(256), 0, g_stream, o, v, Rp, ldp, Rm, ldm, t2,
+                Hp, Hm, assign, std::max(Sp, 1), strideP, std::max(Sm, 1), strideM, (long long)(ldhp ? ldhp : ldp), (long long)(ldhm ? ldhm : ldm));
 }
 int dev_ladder_scatter_pm(int64_t o, int64_t v, const double* Rp, int64_t ldp, const double* Rm, int64_t ldm, double* t2) {
   return dev_ladder_scatter_pm2(o, v, Rp, ldp, Rm, ldm, nullptr, nullptr, 0, t2);
@@ -2034,7 +1984,8 @@ __device__ __forceinline__ void pack_w_pm_kernel_body(const uint3 BID, const uin
   pack_w_pm_any(BID, o, [=](long long k, long long l, long long i, long long j) { return W[((k * o + l) * o + i) * o + j]; }, Ap, lda_p, Am, lda_m);
 }
 __global__ void __launch_bounds__(256) pack_w_pm_kernel(long long o, const double* __restrict__ W, double* __restrict__ Ap, long long lda_p,
-                                                        double* __restrict__ Am, long long lda_m) { pack_w_pm_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, W, Ap, lda_p, Am, lda_m); }
+                                                        double* __restrict__ Am, long long lda_m) { pack_w_pm_kernel_body(block_id(), grid_dim(), o, W, Ap, lda_p, Am, lda_m); }
+static const Groupable<pack_w_pm_kernel_body, 256> reg_pack_w_pm(pack_w_pm_kernel);
 __device__ __forceinline__ void pack_w_pm_sum_kernel_body(const uint3 BID, const uint3 GDIM, long long o, const double* __restrict__ Wp, const double* __restrict__ X, const double* __restrict__ O1,      // (Wp = Wt, O1 = At of dev_ops.h)
                                                             double* __restrict__ Ap, long long lda_p, double* __restrict__ Am, long long lda_m) {
   // every operand is addressed [row pair][column pair]: a row of the packed images reads the (i,j) and (j,i) blocks of o^2 contiguous doubles of each (round 5:
@@ -2044,8 +1995,9 @@ __device__ __forceinline__ void pack_w_pm_sum_kernel_body(const uint3 BID, const
 }
 __global__ void __launch_bounds__(256) pack_w_pm_sum_kernel(long long o, const double* __restrict__ Wp, const double* __restrict__ X, const double* __restrict__ O1,
                                                             double* __restrict__ Ap, long long lda_p, double* __restrict__ Am, long long lda_m) {
-  pack_w_pm_sum_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, Wp, X, O1, Ap, lda_p, Am, lda_m);
+  pack_w_pm_sum_kernel_body(block_id(), grid_dim(), o, Wp, X, O1, Ap, lda_p, Am, lda_m);
 }
+static const Groupable<pack_w_pm_sum_kernel_body, 256> reg_pack_w_pm_sum(pack_w_pm_sum_kernel);
 // one wave per output (k,i), lanes over l (then strides of 64): a thread per output walks l in a chain of L2 round trips (14.7 us at n_occ = 21)
 __device__ __forceinline__ double wave_sum_fwd(double v);
 __device__ __forceinline__ void foo_from_x_kernel_body(const uint3 BID, const uint3 GDIM, long long o, const double* __restrict__ X, double* __restrict__ F) {
@@ -2058,13 +2010,12 @@ __device__ __forceinline__ void foo_from_x_kernel_body(const uint3 BID, const ui
   s = wave_sum_fwd(s);
   if (lane == 0) F[t] = s;
 }
-__global__ void __launch_bounds__(256) foo_from_x_kernel(long long o, const double* __restrict__ X, double* __restrict__ F) { foo_from_x_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, X, F); }
+__global__ void __launch_bounds__(256) foo_from_x_kernel(long long o, const double* __restrict__ X, double* __restrict__ F) { foo_from_x_kernel_body(block_id(), grid_dim(), o, X, F); }
+static const Groupable<foo_from_x_kernel_body, 256> reg_foo_from_x(foo_from_x_kernel);
 int dev_foo_from_x(int64_t o, const double* X, double* F) {
   REQUIRE_INIT();
   if (o <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(foo_from_x_kernel, dim3((unsigned)((o * o + 3) / 4)), dim3(256), 0, g_stream, (long long)o, X, F);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_foo_from_x", foo_from_x_kernel, dim3((unsigned)((o * o + 3) / 4)), dim3(256), 0, g_stream, o, X, F);
 }
 int dev_pack_w_pm_sum(int64_t o, const double* Wp, const double* X, const double* O1, double* Ap, int64_t lda_p, double* Am, int64_t lda_m) {
   REQUIRE_INIT();
@@ -2072,9 +2023,7 @@ int dev_pack_w_pm_sum(int64_t o, const double* Wp, const double* X, const double
   const long long npo = o * (o + 1) / 2, nmo = o * (o - 1) / 2;
   if (lda_p < npo || (nmo > 0 && lda_m < nmo)) { set_error("dev_pack_w_pm_sum: leading dimension too small"); return QEMB_ERR_ARG; }
   if (npo > 65535) { set_error("dev_pack_w_pm_sum: too many pairs"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL(pack_w_pm_sum_kernel, dim3((unsigned)((lda_p + 255) / 256), (unsigned)npo), dim3(256), 0, g_stream, (long long)o, Wp, X, O1, Ap, (long long)lda_p, nmo > 0 ? Am : nullptr, (long long)lda_m);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_pack_w_pm_sum", pack_w_pm_sum_kernel, dim3((unsigned)((lda_p + 255) / 256), (unsigned)npo), dim3(256), 0, g_stream, o, Wp, X, O1, Ap, lda_p, nmo > 0 ? Am : nullptr, lda_m);
 }
 int dev_pack_w_pm(int64_t o, const double* W, double* Ap, int64_t lda_p, double* Am, int64_t lda_m) {
   REQUIRE_INIT();
@@ -2082,9 +2031,7 @@ int dev_pack_w_pm(int64_t o, const double* W, double* Ap, int64_t lda_p, double*
   const long long npo = o * (o + 1) / 2, nmo = o * (o - 1) / 2;
   if (lda_p < npo || (nmo > 0 && lda_m < nmo)) { set_error("dev_pack_w_pm: leading dimension too small"); return QEMB_ERR_ARG; }
   if (npo > 65535) { set_error("dev_pack_w_pm: too many pairs"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL(pack_w_pm_kernel, dim3((unsigned)((lda_p + 255) / 256), (unsigned)npo), dim3(256), 0, g_stream, (long long)o, W, Ap, (long long)lda_p, nmo > 0 ? Am : nullptr, (long long)lda_m);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_pack_w_pm", pack_w_pm_kernel, dim3((unsigned)((lda_p + 255) / 256), (unsigned)npo), dim3(256), 0, g_stream, o, W, Ap, lda_p, nmo > 0 ? Am : nullptr, lda_m);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2136,10 +2083,8 @@ __global__ void __launch_bounds__(256) reduce_stage2(int np, const double* parti
 int dev_dot(int64_t n, const double* x, const double* y, double* out_dev) {
   REQUIRE_INIT();
   const int np = (int)std::max<int64_t>(1, std::min<int64_t>((n + 1023) / 1024, NPART));
-  hipLaunchKernelGGL(reduce_stage1<false>, dim3(np), dim3(256), 0, g_stream, (long long)n, x, y, g_partials);
-  hipLaunchKernelGGL(reduce_stage2<false>, dim3(1), dim3(256), 0, g_stream, np, g_partials, out_dev);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  QTRY(launch("dev_dot", reduce_stage1<false>, dim3(np), dim3(256), 0, g_stream, n, x, y, g_partials));
+  return launch("dev_dot", reduce_stage2<false>, dim3(1), dim3(256), 0, g_stream, np, g_partials, out_dev);
 }
 // out[j] = <x, ys[j]>, j < m <= 8, reading x once.  Same partition and summation order as dev_dot, so each result is
 // bit-identical to the single dot product.
@@ -2176,10 +2121,8 @@ int dev_dot_many(int64_t n, const double* x, int m, const double* const* ys, dou
   DotManyK k{};
   k.m = m;
   for (int j = 0; j < m; ++j) k.y[j] = ys[j];
-  hipLaunchKernelGGL(dot_many_stage1, dim3(np), dim3(256), 0, g_stream, (long long)n, x, k, g_partials, np);
-  hipLaunchKernelGGL(dot_many_stage2, dim3(m), dim3(256), 0, g_stream, np, (const double*)g_partials, out_dev);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  QTRY(launch("dev_dot_many", dot_many_stage1, dim3(np), dim3(256), 0, g_stream, n, x, k, g_partials, np));
+  return launch("dev_dot_many", dot_many_stage2, dim3(m), dim3(256), 0, g_stream, np, g_partials, out_dev);
 }
 // ---- single-launch reductions: every workgroup leaves its partial sums, the LAST one to finish (device-scope counter) adds them up in the
 // fixed order of the two-stage reductions above and writes the result to device memory and to a pinned host word -- no second kernel, no copy
@@ -2228,8 +2171,9 @@ __device__ __forceinline__ void finish_partials_kernel_body(const uint3 BID, con
 }
 __global__ void __launch_bounds__(256) finish_partials_kernel(int m, int np, const double* __restrict__ partial, double* out_dev, double* out_host,
                                                               unsigned long long* flag_host, unsigned long long seq) {
-  finish_partials_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), m, np, partial, out_dev, out_host, flag_host, seq);
+  finish_partials_kernel_body(block_id(), grid_dim(), m, np, partial, out_dev, out_host, flag_host, seq);
 }
+static const Groupable<finish_partials_kernel_body, 256> reg_finish_partials(finish_partials_kernel);
 int dev_wait_flag(const void* flag_host, unsigned long long seq) {
   REQUIRE_INIT();
   const unsigned long long* p = (const unsigned long long*)flag_host;
@@ -2336,8 +2280,10 @@ __device__ __forceinline__ void diis_push_kernel_body(const uint3 BID, const uin
 template <bool VEC2>
 __global__ void __launch_bounds__(256) diis_push_kernel(long long n, const double* trial, const double* prev, double* e, double* xcopy, DiisPushK k, double* partial,
                                                         unsigned* counter, double* row_dev, double* row_host, int finish, unsigned long long* flag_host, unsigned long long seq) {
-  diis_push_kernel_body<VEC2>(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), n, trial, prev, e, xcopy, k, partial, counter, row_dev, row_host, finish, flag_host, seq);
+  diis_push_kernel_body<VEC2>(block_id(), grid_dim(), n, trial, prev, e, xcopy, k, partial, counter, row_dev, row_host, finish, flag_host, seq);
 }
+static const Groupable<diis_push_kernel_body<false>, 256> reg_diis_push_w1(diis_push_kernel<false>);
+static const Groupable<diis_push_kernel_body<true>, 256> reg_diis_push_w2(diis_push_kernel<true>);
 int dev_diis_push(int64_t n, const double* trial, const double* prev, double* e, double* xcopy, int m, const double* const* ys, int self,
                   double* row_dev, double* row_host, void* flag_host, unsigned long long seq) {
   REQUIRE_INIT();
@@ -2358,12 +2304,11 @@ int dev_diis_push(int64_t n, const double* trial, const double* prev, double* e,
     t_batch.entries.push_back(b);
     return QEMB_OK;
   }
-  if (vec2) hipLaunchKernelGGL(diis_push_kernel<true>, dim3(np), dim3(256), 0, g_stream, (long long)n, trial, prev, e, xcopy, k, g_partials, (unsigned*)(g_partials + 8 * NPART), row_dev, row_host, post_finish_mode(),
-                               (unsigned long long*)flag_host, seq);
-  else hipLaunchKernelGGL(diis_push_kernel<false>, dim3(np), dim3(256), 0, g_stream, (long long)n, trial, prev, e, xcopy, k, g_partials, (unsigned*)(g_partials + 8 * NPART), row_dev, row_host, post_finish_mode(),
-                          (unsigned long long*)flag_host, seq);
-  if (post_finish_mode() == 0) hipLaunchKernelGGL(finish_partials_kernel, dim3(1), dim3(256), 0, g_stream, m, np, (const double*)g_partials, row_dev, row_host, (unsigned long long*)flag_host, seq);
-  HIP_TRY(hipGetLastError());
+  if (vec2) QTRY(launch("dev_diis_push", diis_push_kernel<true>, dim3(np), dim3(256), 0, g_stream, n, trial, prev, e, xcopy, k, g_partials, (unsigned*)(g_partials + 8 * NPART), row_dev, row_host, post_finish_mode(),
+                        (unsigned long long*)flag_host, seq));
+  else QTRY(launch("dev_diis_push", diis_push_kernel<false>, dim3(np), dim3(256), 0, g_stream, n, trial, prev, e, xcopy, k, g_partials, (unsigned*)(g_partials + 8 * NPART), row_dev, row_host, post_finish_mode(),
+                   (unsigned long long*)flag_host, seq));
+  if (post_finish_mode() == 0) QTRY(launch("dev_diis_push", finish_partials_kernel, dim3(1), dim3(256), 0, g_stream, m, np, g_partials, row_dev, row_host, (unsigned long long*)flag_host, seq));
   return QEMB_OK;
 }
 // grid (o * o tiles (i,j), chunks of `rows` rows a): the workgroup forms the new t1[i, its rows] and t1[j, :] in LDS, then streams its rows of the tile --
@@ -2434,8 +2379,10 @@ __device__ __forceinline__ void ccsd_extrapolate_energy_kernel_body(const uint3 
 template <bool VEC2>
 __global__ void __launch_bounds__(256) ccsd_extrapolate_energy_kernel(int o, int v, int rows, ExtrapK k, double* amp, const double* __restrict__ L, double* __restrict__ tau,
                                                                       double* partial, unsigned* counter, double* e_dev, double* e_host, int finish, unsigned long long* flag_host, unsigned long long seq) {
-  ccsd_extrapolate_energy_kernel_body<VEC2>(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, v, rows, k, amp, L, tau, partial, counter, e_dev, e_host, finish, flag_host, seq);
+  ccsd_extrapolate_energy_kernel_body<VEC2>(block_id(), grid_dim(), o, v, rows, k, amp, L, tau, partial, counter, e_dev, e_host, finish, flag_host, seq);
 }
+static const Groupable<ccsd_extrapolate_energy_kernel_body<false>, 256> reg_ccsd_extrapolate_energy_w1(ccsd_extrapolate_energy_kernel<false>);
+static const Groupable<ccsd_extrapolate_energy_kernel_body<true>, 256> reg_ccsd_extrapolate_energy_w2(ccsd_extrapolate_energy_kernel<true>);
 int dev_ccsd_extrapolate_energy(int64_t o, int64_t v, int nterms, const double* coef, const double* const* xs, double* amp, const double* L,
                                 double* tau, double* e_dev, double* e_host, void* flag_host, unsigned long long seq) {
   REQUIRE_INIT();
@@ -2460,12 +2407,11 @@ int dev_ccsd_extrapolate_energy(int64_t o, int64_t v, int nterms, const double* 
     t_batch.entries.push_back(b);
     return QEMB_OK;
   }
-  if (vec2) hipLaunchKernelGGL(ccsd_extrapolate_energy_kernel<true>, dim3((unsigned)(o * o), (unsigned)chunks), dim3(256), lds, g_stream, (int)o, (int)v, rows, k, amp, L, tau,
-                               g_partials, (unsigned*)(g_partials + 8 * NPART), e_dev, e_host, post_finish_mode(), (unsigned long long*)flag_host, seq);
-  else hipLaunchKernelGGL(ccsd_extrapolate_energy_kernel<false>, dim3((unsigned)(o * o), (unsigned)chunks), dim3(256), lds, g_stream, (int)o, (int)v, rows, k, amp, L, tau,
-                          g_partials, (unsigned*)(g_partials + 8 * NPART), e_dev, e_host, post_finish_mode(), (unsigned long long*)flag_host, seq);
-  if (post_finish_mode() == 0) hipLaunchKernelGGL(finish_partials_kernel, dim3(1), dim3(256), 0, g_stream, 1, (int)(o * o * chunks), (const double*)g_partials, e_dev, e_host, (unsigned long long*)flag_host, seq);
-  HIP_TRY(hipGetLastError());
+  if (vec2) QTRY(launch("dev_ccsd_extrapolate_energy", ccsd_extrapolate_energy_kernel<true>, dim3((unsigned)(o * o), (unsigned)chunks), dim3(256), lds, g_stream, (int)o, (int)v, rows, k, amp, L, tau,
+                        g_partials, (unsigned*)(g_partials + 8 * NPART), e_dev, e_host, post_finish_mode(), (unsigned long long*)flag_host, seq));
+  else QTRY(launch("dev_ccsd_extrapolate_energy", ccsd_extrapolate_energy_kernel<false>, dim3((unsigned)(o * o), (unsigned)chunks), dim3(256), lds, g_stream, (int)o, (int)v, rows, k, amp, L, tau,
+                   g_partials, (unsigned*)(g_partials + 8 * NPART), e_dev, e_host, post_finish_mode(), (unsigned long long*)flag_host, seq));
+  if (post_finish_mode() == 0) QTRY(launch("dev_ccsd_extrapolate_energy", finish_partials_kernel, dim3(1), dim3(256), 0, g_stream, 1, (int)(o * o * chunks), g_partials, e_dev, e_host, (unsigned long long*)flag_host, seq));
   return QEMB_OK;
 }
 int dev_batch_begin() {
@@ -2475,22 +2421,12 @@ int dev_batch_begin() {
   t_batch.entries.clear();
   return QEMB_OK;
 }
-static void register_groupable_kernels();
 int dev_batch_flush() {
   REQUIRE_INIT();
   t_batch.on = false;
   std::vector<BatchEntry> ent;
   ent.swap(t_batch.entries);
   if (ent.empty()) return QEMB_OK;
-  static std::once_flag once;
-  std::lock_guard<std::mutex> reg_lock(g_plan_mutex);      // the registry of groupable kernels is filled lazily, also by the first dev_tape_run of another thread
-  std::call_once(once, [] {
-    register_groupable<diis_push_kernel_body<false>, 256, long long, const double*, const double*, double*, double*, DiisPushK, double*, unsigned*, double*, double*, int, unsigned long long*, unsigned long long>((const void*)diis_push_kernel<false>);
-    register_groupable<diis_push_kernel_body<true>, 256, long long, const double*, const double*, double*, double*, DiisPushK, double*, unsigned*, double*, double*, int, unsigned long long*, unsigned long long>((const void*)diis_push_kernel<true>);
-    register_groupable<ccsd_extrapolate_energy_kernel_body<false>, 256, int, int, int, ExtrapK, double*, const double*, double*, double*, unsigned*, double*, double*, int, unsigned long long*, unsigned long long>((const void*)ccsd_extrapolate_energy_kernel<false>);
-    register_groupable<ccsd_extrapolate_energy_kernel_body<true>, 256, int, int, int, ExtrapK, double*, const double*, double*, double*, unsigned*, double*, double*, int, unsigned long long*, unsigned long long>((const void*)ccsd_extrapolate_energy_kernel<true>);
-    register_groupable<finish_partials_kernel_body, 256, int, int, const double*, double*, double*, unsigned long long*, unsigned long long>((const void*)finish_partials_kernel);
-  });
   if (!batch_region(ent.size() - 1)) { set_error("dev_batch_flush: scratch allocation failed"); return QEMB_ERR_ALLOC; }
   const void* wrappers[4] = {(const void*)diis_push_kernel<false>, (const void*)diis_push_kernel<true>, (const void*)ccsd_extrapolate_energy_kernel<false>,
                              (const void*)ccsd_extrapolate_energy_kernel<true>};
@@ -2549,10 +2485,8 @@ int dev_batch_flush() {
 int dev_absmax(int64_t n, const double* x, double* out_dev) {
   REQUIRE_INIT();
   const int np = (int)std::max<int64_t>(1, std::min<int64_t>((n + 1023) / 1024, NPART));
-  hipLaunchKernelGGL(reduce_stage1<true>, dim3(np), dim3(256), 0, g_stream, (long long)n, x, x, g_partials);
-  hipLaunchKernelGGL(reduce_stage2<true>, dim3(1), dim3(256), 0, g_stream, np, g_partials, out_dev);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  QTRY(launch("dev_absmax", reduce_stage1<true>, dim3(np), dim3(256), 0, g_stream, n, x, x, g_partials));
+  return launch("dev_absmax", reduce_stage2<true>, dim3(1), dim3(256), 0, g_stream, np, g_partials, out_dev);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2570,14 +2504,13 @@ __device__ __forceinline__ void gemv_rows_kernel_body(const uint3 BID, const uin
   }
 }
 __global__ void __launch_bounds__(256) gemv_rows_kernel(long long rows, long long cols, const double* T, long long ldt,
-                                                        const double* x, double* y, double alpha, double beta) { gemv_rows_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), rows, cols, T, ldt, x, y, alpha, beta); }
+                                                        const double* x, double* y, double alpha, double beta) { gemv_rows_kernel_body(block_id(), grid_dim(), rows, cols, T, ldt, x, y, alpha, beta); }
+static const Groupable<gemv_rows_kernel_body, 256> reg_gemv_rows(gemv_rows_kernel);
 int dev_gemv_rows(int64_t rows, int64_t cols, const double* T, int64_t ldt, const double* x, double* y, double alpha, double beta) {
   REQUIRE_INIT();
   if (rows <= 0) return QEMB_OK;
   const unsigned grid = (unsigned)std::min<int64_t>(rows, 1 << 20);
-  hipLaunchKernelGGL(gemv_rows_kernel, dim3(grid), dim3(256), 0, g_stream, (long long)rows, (long long)cols, T, (long long)ldt, x, y, alpha, beta);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_gemv_rows", gemv_rows_kernel, dim3(grid), dim3(256), 0, g_stream, rows, cols, T, ldt, x, y, alpha, beta);
 }
 
 // two matrix-vector products into one result, one pass: y[r] = alpha (T1[r,:] . x1 + T2[r,:] . x2) + beta y[r]
@@ -2595,15 +2528,14 @@ __device__ __forceinline__ void gemv_rows2_kernel_body(const uint3 BID, const ui
 }
 __global__ void __launch_bounds__(256) gemv_rows2_kernel(long long rows, long long cols, const double* T1, long long ld1, const double* x1, const double* T2, long long ld2, const double* x2,
                                                          double* y, double alpha, double beta) {
-  gemv_rows2_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), rows, cols, T1, ld1, x1, T2, ld2, x2, y, alpha, beta);
+  gemv_rows2_kernel_body(block_id(), grid_dim(), rows, cols, T1, ld1, x1, T2, ld2, x2, y, alpha, beta);
 }
+static const Groupable<gemv_rows2_kernel_body, 256> reg_gemv_rows2(gemv_rows2_kernel);
 int dev_gemv_rows2(int64_t rows, int64_t cols, const double* T1, int64_t ld1, const double* x1, const double* T2, int64_t ld2, const double* x2, double* y, double alpha, double beta) {
   REQUIRE_INIT();
   if (rows <= 0) return QEMB_OK;
   const unsigned grid = (unsigned)std::min<int64_t>(rows, 1 << 20);
-  hipLaunchKernelGGL(gemv_rows2_kernel, dim3(grid), dim3(256), 0, g_stream, (long long)rows, (long long)cols, T1, (long long)ld1, x1, T2, (long long)ld2, x2, y, alpha, beta);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_gemv_rows2", gemv_rows2_kernel, dim3(grid), dim3(256), 0, g_stream, rows, cols, T1, ld1, x1, T2, ld2, x2, y, alpha, beta);
 }
 // The four small products of the T1 equation in one launch.  grid (o, chunks of 64 rows a): every workgroup forms Q[i,:] for its i (o dot products over v),
 // then one wave per row a:  t1n[i,a] = sum_c t1[i,c] Lvv[a,c] + sum_k (Q[i,k] - Loo[k,i]) t1[k,a]
@@ -2630,15 +2562,14 @@ __device__ __forceinline__ void ccsd_t1_small_kernel_body(const uint3 BID, const
 }
 __global__ void __launch_bounds__(256) ccsd_t1_small_kernel(int o, int v, const double* __restrict__ t1, const double* __restrict__ Lvv, const double* __restrict__ Loo,
                                                             const double* __restrict__ Fov, double* __restrict__ t1n) {
-  ccsd_t1_small_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, v, t1, Lvv, Loo, Fov, t1n);
+  ccsd_t1_small_kernel_body(block_id(), grid_dim(), o, v, t1, Lvv, Loo, Fov, t1n);
 }
+static const Groupable<ccsd_t1_small_kernel_body, 256> reg_ccsd_t1_small(ccsd_t1_small_kernel);
 int dev_ccsd_t1_small(int64_t o, int64_t v, const double* t1, const double* Lvv, const double* Loo, const double* Fov, double* t1n) {
   REQUIRE_INIT();
   if (o <= 0 || v <= 0) return QEMB_OK;
   if (o > 1024 || (v + 63) / 64 > 65535) { set_error("dev_ccsd_t1_small: n_occ <= 1024"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL(ccsd_t1_small_kernel, dim3((unsigned)o, (unsigned)((v + 63) / 64)), dim3(256), 0, g_stream, (int)o, (int)v, t1, Lvv, Loo, Fov, t1n);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_ccsd_t1_small", ccsd_t1_small_kernel, dim3((unsigned)o, (unsigned)((v + 63) / 64)), dim3(256), 0, g_stream, (int)o, (int)v, t1, Lvv, Loo, Fov, t1n);
 }
 // The right-hand side of the T1 equation, one workgroup per element r = (i,a): the o dot products Q[i,k] - Loo[k,i] first (waves over k), then every thread
 // strides over the two long rows S[r,:], Lph1[r,:], the short rows of the small products and the slabs of the two long-K products; one block sum.
@@ -2678,17 +2609,16 @@ __global__ void __launch_bounds__(256) ccsd_t1_assemble_kernel(int o, int v, con
                                                                const double* __restrict__ Fov, const double* __restrict__ Sm, const double* __restrict__ Lph1,
                                                                const double* __restrict__ PA, int SA, long long strideA, const double* __restrict__ PB, int SB, long long strideB,
                                                                double* __restrict__ t1n) {
-  ccsd_t1_assemble_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), o, v, t1, Lvv, Loo, Fov, Sm, Lph1, PA, SA, strideA, PB, SB, strideB, t1n);
+  ccsd_t1_assemble_kernel_body(block_id(), grid_dim(), o, v, t1, Lvv, Loo, Fov, Sm, Lph1, PA, SA, strideA, PB, SB, strideB, t1n);
 }
+static const Groupable<ccsd_t1_assemble_kernel_body, 256> reg_ccsd_t1_assemble(ccsd_t1_assemble_kernel);
 int dev_ccsd_t1_assemble(int64_t o, int64_t v, const double* t1, const double* Lvv, const double* Loo, const double* Fov, const double* S, const double* Lph1,
                          const double* PA, int SA, int64_t strideA, const double* PB, int SB, int64_t strideB, double* t1n) {
   REQUIRE_INIT();
   if (o <= 0 || v <= 0) return QEMB_OK;
   if (o > 1024) { set_error("dev_ccsd_t1_assemble: n_occ <= 1024"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL(ccsd_t1_assemble_kernel, dim3((unsigned)std::min<int64_t>(o * v, 1 << 20)), dim3(256), 0, g_stream, (int)o, (int)v, t1, Lvv, Loo, Fov, S, Lph1,
-                     PA, std::max(SA, 0), (long long)strideA, PB, std::max(SB, 0), (long long)strideB, t1n);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_ccsd_t1_assemble", ccsd_t1_assemble_kernel, dim3((unsigned)std::min<int64_t>(o * v, 1 << 20)), dim3(256), 0, g_stream, (int)o, (int)v, t1, Lvv, Loo, Fov, S, Lph1,
+                PA, std::max(SA, 0), strideA, PB, std::max(SB, 0), strideB, t1n);
 }
 // two independent matrix-vector passes, one launch: the first rows1 workgroups take the first product, the rest the second
 __device__ __forceinline__ void gemv_rows_two_kernel_body(const uint3 BID, const uint3 GDIM, long long rows1, long long cols1, const double* T1, long long ld1, const double* x1, double* y1,
@@ -2712,16 +2642,15 @@ __device__ __forceinline__ void gemv_rows_two_kernel_body(const uint3 BID, const
 }
 __global__ void __launch_bounds__(256) gemv_rows_two_kernel(long long rows1, long long cols1, const double* T1, long long ld1, const double* x1, double* y1, double a1, double b1,
                                                             long long rows2, long long cols2, const double* T2, long long ld2, const double* x2, double* y2, double a2, double b2) {
-  gemv_rows_two_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), rows1, cols1, T1, ld1, x1, y1, a1, b1, rows2, cols2, T2, ld2, x2, y2, a2, b2);
+  gemv_rows_two_kernel_body(block_id(), grid_dim(), rows1, cols1, T1, ld1, x1, y1, a1, b1, rows2, cols2, T2, ld2, x2, y2, a2, b2);
 }
+static const Groupable<gemv_rows_two_kernel_body, 256> reg_gemv_rows_two(gemv_rows_two_kernel);
 int dev_gemv_rows_two(int64_t rows1, int64_t cols1, const double* T1, int64_t ld1, const double* x1, double* y1, double a1, double b1,
                       int64_t rows2, int64_t cols2, const double* T2, int64_t ld2, const double* x2, double* y2, double a2, double b2) {
   REQUIRE_INIT();
   if (rows1 + rows2 <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(gemv_rows_two_kernel, dim3((unsigned)std::min<int64_t>(rows1 + rows2, 1 << 20)), dim3(256), 0, g_stream, (long long)rows1, (long long)cols1, T1, (long long)ld1, x1, y1, a1, b1,
-                     (long long)rows2, (long long)cols2, T2, (long long)ld2, x2, y2, a2, b2);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_gemv_rows_two", gemv_rows_two_kernel, dim3((unsigned)std::min<int64_t>(rows1 + rows2, 1 << 20)), dim3(256), 0, g_stream, rows1, cols1, T1, ld1, x1, y1, a1, b1,
+                rows2, cols2, T2, ld2, x2, y2, a2, b2);
 }
 __global__ void __launch_bounds__(256) gemv_rows_batched_kernel(long long rows, long long cols, long long nbatch, const double* __restrict__ T,
                                                                long long ldt, long long strideT, const double* __restrict__ x, long long stridex,
@@ -2742,10 +2671,8 @@ int dev_gemv_rows_batched(int64_t rows, int64_t cols, int64_t nbatch, const doub
                           int64_t stridex, double* y, double alpha, double beta) {
   REQUIRE_INIT();
   if (rows <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(gemv_rows_batched_kernel, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(256), 0, g_stream, (long long)rows, (long long)cols,
-                     (long long)nbatch, T, (long long)ldt, (long long)strideT, x, (long long)stridex, y, alpha, beta);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_gemv_rows_batched", gemv_rows_batched_kernel, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(256), 0, g_stream, rows, cols,
+                nbatch, T, ldt, strideT, x, stridex, y, alpha, beta);
 }
 
 // partial[p][chunk][r] = sum_{m in chunk} x[m] * T[p][m][r];  threads run along r (contiguous), blockIdx.z tiles r
@@ -2765,7 +2692,8 @@ __device__ __forceinline__ void contract_mid_stage1_body(const uint3 BID, const 
   }
 }
 __global__ void __launch_bounds__(256) contract_mid_stage1(long long mid, long long inner, int nchunk, const double* __restrict__ T,
-                                                           const double* __restrict__ x, double* __restrict__ partial) { contract_mid_stage1_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), mid, inner, nchunk, T, x, partial); }
+                                                           const double* __restrict__ x, double* __restrict__ partial) { contract_mid_stage1_body(block_id(), grid_dim(), mid, inner, nchunk, T, x, partial); }
+static const Groupable<contract_mid_stage1_body, 256> reg_contract_mid_stage1(contract_mid_stage1);
 __device__ __forceinline__ void contract_mid_stage2_body(const uint3 BID, const uint3 GDIM, long long outer, long long inner, int nchunk, const double* partial,
                                                            double* Y, long long ldy, double alpha, double beta) {
   const long long t = (long long)BID.x * blockDim.x + threadIdx.x;
@@ -2777,7 +2705,8 @@ __device__ __forceinline__ void contract_mid_stage2_body(const uint3 BID, const 
   *y = (beta != 0.0) ? alpha * acc + beta * (*y) : alpha * acc;
 }
 __global__ void __launch_bounds__(256) contract_mid_stage2(long long outer, long long inner, int nchunk, const double* partial,
-                                                           double* Y, long long ldy, double alpha, double beta) { contract_mid_stage2_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), outer, inner, nchunk, partial, Y, ldy, alpha, beta); }
+                                                           double* Y, long long ldy, double alpha, double beta) { contract_mid_stage2_body(block_id(), grid_dim(), outer, inner, nchunk, partial, Y, ldy, alpha, beta); }
+static const Groupable<contract_mid_stage2_body, 256> reg_contract_mid_stage2(contract_mid_stage2);
 int dev_contract_mid(int64_t outer, int64_t mid, int64_t inner, const double* T, const double* x, double* Y, int64_t ldy, double alpha, double beta) {
   REQUIRE_INIT();
   if (outer <= 0 || inner <= 0) return QEMB_OK;
@@ -2787,11 +2716,9 @@ int dev_contract_mid(int64_t outer, int64_t mid, int64_t inner, const double* T,
   int nchunk = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(mid / 8, 128), std::max<int64_t>(1, (4096 + outer * rblocks - 1) / (outer * rblocks))));   // <= 128 partial slabs: stage 2 sums them serially
   int rc = ensure_ws((size_t)outer * nchunk * inner * sizeof(double));
   if (rc) return rc;
-  hipLaunchKernelGGL(contract_mid_stage1, dim3(nchunk, (unsigned)outer, (unsigned)rblocks), dim3(256), 0, g_stream, (long long)mid, (long long)inner, nchunk, T, x, g_ws);
+  QTRY(launch("dev_contract_mid", contract_mid_stage1, dim3(nchunk, (unsigned)outer, (unsigned)rblocks), dim3(256), 0, g_stream, mid, inner, nchunk, T, x, g_ws));
   const long long tot = outer * inner;
-  hipLaunchKernelGGL(contract_mid_stage2, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, g_stream, (long long)outer, (long long)inner, nchunk, g_ws, Y, (long long)ldy, alpha, beta);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_contract_mid", contract_mid_stage2, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, g_stream, outer, inner, nchunk, g_ws, Y, ldy, alpha, beta);
 }
 
 // exchange matrix from pair rows: stage 1 = per-row partial vectors, stage 2 = fixed-order sum over the rows that feed K[p,:]
@@ -2828,10 +2755,8 @@ int dev_k_from_pairs(int64_t n, const double* H, const double* D, double* K) {
   int rc = ensure_ws((size_t)2 * np * n * sizeof(double));
   if (rc) return rc;
   double* P1 = g_ws; double* P2 = g_ws + np * n;
-  hipLaunchKernelGGL(k_pairs_stage1, dim3((unsigned)np), dim3(256), (size_t)2 * n * sizeof(double), g_stream, (long long)n, H, D, P1, P2);
-  hipLaunchKernelGGL(k_pairs_stage2, dim3((unsigned)n), dim3(256), 0, g_stream, (long long)n, (const double*)P1, (const double*)P2, K);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  QTRY(launch("dev_k_from_pairs", k_pairs_stage1, dim3((unsigned)np), dim3(256), (size_t)2 * n * sizeof(double), g_stream, n, H, D, P1, P2));
+  return launch("dev_k_from_pairs", k_pairs_stage2, dim3((unsigned)n), dim3(256), 0, g_stream, n, P1, P2, K);
 }
 
 // Coulomb AND exchange matrix in ONE pass over the 4-fold packed block S4[P(p,q)][P(r,s)] (a quarter of the n^4 tensor, half of the
@@ -3093,7 +3018,7 @@ int dev_jk_from_packed(int64_t n, const double* S4, const double* D, const doubl
     else launch(jk_packed_stage1<16>);
   }
   HIP_TRY(attr_err);
-  if (K) hipLaunchKernelGGL(k_pairs_stage2, dim3((unsigned)n), dim3(256), 0, g_stream, (long long)n, (const double*)P1, (const double*)P2, K);
+  if (K) QTRY(launch("dev_jk_from_packed", k_pairs_stage2, dim3((unsigned)n), dim3(256), 0, g_stream, n, P1, P2, K));
   HIP_TRY(hipGetLastError());
   return QEMB_OK;
 }
@@ -3162,7 +3087,8 @@ __device__ __forceinline__ void unpack_tril_tiled_kernel_body(const uint3 BID, c
   }
 }
 __global__ void __launch_bounds__(256) unpack_tril_tiled_kernel(long long rows, long long n, const double* __restrict__ packed,
-                                                               double* __restrict__ full, int dup, long long nr, long long ld) { unpack_tril_tiled_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), rows, n, packed, full, dup, nr, ld); }
+                                                               double* __restrict__ full, int dup, long long nr, long long ld) { unpack_tril_tiled_kernel_body(block_id(), grid_dim(), rows, n, packed, full, dup, nr, ld); }
+static const Groupable<unpack_tril_tiled_kernel_body, 256> reg_unpack_tril_tiled(unpack_tril_tiled_kernel);
 
 // s1[i,j,k,l] = s4[pair(i,j), pair(k,l)];  one block row per (i,j), threads along (k,l)
 __global__ void __launch_bounds__(256) unpack_s4_kernel(long long n, const double* s4, double* s1) {
@@ -3182,12 +3108,9 @@ int dev_unpack_s4(int64_t n, const double* s4, double* s1) {
   if (n >= 32) {
     const int64_t np = n * (n + 1) / 2;
     const int64_t nt = (n + 31) / 32;
-    hipLaunchKernelGGL(unpack_tril_tiled_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)unpack_walkers(np, nt * (nt + 1) / 2)), dim3(256), 0, g_stream, (long long)np, (long long)n, s4, s1, 1, (long long)n, (long long)n);
-  } else {
-    hipLaunchKernelGGL(unpack_s4_kernel, dim3((unsigned)std::min<int64_t>(n * n, 1 << 20)), dim3(256), 0, g_stream, (long long)n, s4, s1);
+    return launch("dev_unpack_s4", unpack_tril_tiled_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)unpack_walkers(np, nt * (nt + 1) / 2)), dim3(256), 0, g_stream, np, n, s4, s1, 1, n, n);
   }
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_unpack_s4", unpack_s4_kernel, dim3((unsigned)std::min<int64_t>(n * n, 1 << 20)), dim3(256), 0, g_stream, n, s4, s1);
 }
 __global__ void __launch_bounds__(256) pack_s4_kernel(long long n, const double* s1, double* s4) {
   const long long np = n * (n + 1) / 2, n2 = n * n;
@@ -3211,9 +3134,7 @@ __global__ void __launch_bounds__(256) pack_s4_kernel(long long n, const double*
 int dev_pack_s4(int64_t n, const double* s1, double* s4) {
   REQUIRE_INIT();
   const int64_t np = n * (n + 1) / 2;
-  hipLaunchKernelGGL(pack_s4_kernel, dim3((unsigned)std::min<int64_t>(np, 1 << 20)), dim3(256), 0, g_stream, (long long)n, s1, s4);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_pack_s4", pack_s4_kernel, dim3((unsigned)std::min<int64_t>(np, 1 << 20)), dim3(256), 0, g_stream, n, s1, s4);
 }
 __global__ void __launch_bounds__(256) unpack_s8_kernel(long long np, const double* s8, double* s4) {
   for (long long r = blockIdx.x; r < np; r += gridDim.x)
@@ -3222,9 +3143,7 @@ __global__ void __launch_bounds__(256) unpack_s8_kernel(long long np, const doub
 int dev_unpack_s8_to_s4(int64_t n, const double* s8, double* s4) {
   REQUIRE_INIT();
   const int64_t np = n * (n + 1) / 2;
-  hipLaunchKernelGGL(unpack_s8_kernel, dim3((unsigned)std::min<int64_t>(np, 1 << 20)), dim3(256), 0, g_stream, (long long)np, s8, s4);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_unpack_s8_to_s4", unpack_s8_kernel, dim3((unsigned)std::min<int64_t>(np, 1 << 20)), dim3(256), 0, g_stream, np, s8, s4);
 }
 __device__ __forceinline__ void unpack_tril_rows_kernel_body(const uint3 BID, const uint3 GDIM, long long rows, long long n, const double* packed, double* full) {
   const long long np = n * (n + 1) / 2, n2 = n * n;
@@ -3234,7 +3153,8 @@ __device__ __forceinline__ void unpack_tril_rows_kernel_body(const uint3 BID, co
       full[r * n2 + kl] = packed[r * np + pair_idx(k, l)];
     }
 }
-__global__ void __launch_bounds__(256) unpack_tril_rows_kernel(long long rows, long long n, const double* packed, double* full) { unpack_tril_rows_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), rows, n, packed, full); }
+__global__ void __launch_bounds__(256) unpack_tril_rows_kernel(long long rows, long long n, const double* packed, double* full) { unpack_tril_rows_kernel_body(block_id(), grid_dim(), rows, n, packed, full); }
+static const Groupable<unpack_tril_rows_kernel_body, 256> reg_unpack_tril_rows(unpack_tril_rows_kernel);
 int dev_unpack_tril_rows(int64_t rows, int64_t n, const double* packed, double* full) { return dev_unpack_tril_rows_ld(rows, n, n, packed, full); }
 int dev_unpack_tril_rows_ld(int64_t rows, int64_t n, int64_t ld, const double* packed, double* full) {
   REQUIRE_INIT();
@@ -3243,12 +3163,9 @@ int dev_unpack_tril_rows_ld(int64_t rows, int64_t n, int64_t ld, const double* p
   if (n >= 32 || ld != n)
   {
     const int64_t nt = (n + 31) / 32;
-    hipLaunchKernelGGL(unpack_tril_tiled_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)unpack_walkers(rows, nt * (nt + 1) / 2)), dim3(256), 0, g_stream, (long long)rows, (long long)n, packed, full, 0, (long long)n, (long long)ld);
+    return launch("dev_unpack_tril_rows_ld", unpack_tril_tiled_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)unpack_walkers(rows, nt * (nt + 1) / 2)), dim3(256), 0, g_stream, rows, n, packed, full, 0, n, ld);
   }
-  else
-    hipLaunchKernelGGL(unpack_tril_rows_kernel, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(256), 0, g_stream, (long long)rows, (long long)n, packed, full);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_unpack_tril_rows_ld", unpack_tril_rows_kernel, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(256), 0, g_stream, rows, n, packed, full);
 }
 // full[P(x,y)][k][l] = in[(x*nr + y)][P(k,l)] for x >= y (x, y < nr; k, l < n): "keep the x >= y rows" and "unpack the pair column"
 // in one pass
@@ -3267,9 +3184,7 @@ int dev_unpack_tril_pair_rows_ld(int64_t nr, int64_t n, int64_t ld, const double
     return rc;
   }
   const int64_t nt = (n + 31) / 32;
-  hipLaunchKernelGGL(unpack_tril_tiled_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)unpack_walkers(npr, nt * (nt + 1) / 2)), dim3(256), 0, g_stream, (long long)npr, (long long)n, in, full, 2, (long long)nr, (long long)ld);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_unpack_tril_pair_rows_ld", unpack_tril_tiled_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)unpack_walkers(npr, nt * (nt + 1) / 2)), dim3(256), 0, g_stream, npr, n, in, full, 2, nr, ld);
 }
 __global__ void __launch_bounds__(256) pack_tril_rows_kernel(long long rows, long long n, const double* full, double* packed) {
   const long long np = n * (n + 1) / 2, n2 = n * n;
@@ -3282,40 +3197,7 @@ __global__ void __launch_bounds__(256) pack_tril_rows_kernel(long long rows, lon
 int dev_pack_tril_rows(int64_t rows, int64_t n, const double* full, double* packed) {
   REQUIRE_INIT();
   if (rows <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(pack_tril_rows_kernel, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(256), 0, g_stream, (long long)rows, (long long)n, full, packed);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
-}
-
-// every kernel of this file that exists in body + wrapper form (see "grouped launches" at the top)
-static void register_groupable_kernels() {
-  register_groupable<copy4_linear_kernel_body, 256, Copy4K>((const void*)copy4_linear_kernel);
-  register_groupable<copy4_transpose_kernel_body, 256, Copy4K, int>((const void*)copy4_transpose_kernel);
-  register_groupable<outer4_kernel_body, 256, Outer4K>((const void*)outer4_kernel);
-  register_groupable<div_denom_kernel_body, 256, double*, long long, long long, long long, long long, const double*, const double*, const double*, const double*>((const void*)div_denom_kernel);
-  register_groupable<ccsd_ph_layouts_kernel_body, 256, long long, long long, const double*, const double*, double*, double*, double*, double*, double*, double*, int>((const void*)ccsd_ph_layouts_kernel);
-  register_groupable<small_k_update_kernel_body, 256, long long, long long, long long, double, const double*, long long, const double*, long long, double*, long long, int>((const void*)small_k_update_kernel);
-  register_groupable<small_k_update_mfma_kernel_body, 256, int, int, int, double, const double*, long long, const double*, long long, double*, long long>((const void*)small_k_update_mfma_kernel);
-  register_groupable<ccsd_y_traces_kernel_body, 256, long long, long long, const double*, const double*, double*, const double*, int, long long, double>((const void*)ccsd_y_traces_kernel);
-  register_groupable<lincomb_kernel_body, 256, long long, LincombK, double, double*>((const void*)lincomb_kernel);
-  register_groupable<ladder_pack_tau_kernel_body, 256, long long, long long, const double*, double*, long long, double*, long long>((const void*)ladder_pack_tau_kernel);
-  register_groupable<scatter_pm_rows_kernel_body, 256, long long, long long, const double*, const double*, double*, const double*, int, long long, int, long long>((const void*)scatter_pm_rows_kernel);
-  register_groupable<ccsd_finish_t2_kernel_body, 256, long long, long long, double*, const double*, const double*, const double*, const double*>((const void*)ccsd_finish_t2_kernel);
-  register_groupable<ladder_scatter_pm_kernel_body, 256, long long, long long, const double*, long long, const double*, long long, double*, const double*, const double*, int, int, long long, int, long long, long long, long long>((const void*)ladder_scatter_pm_kernel);
-  register_groupable<pack_w_pm_kernel_body, 256, long long, const double*, double*, long long, double*, long long>((const void*)pack_w_pm_kernel);
-  register_groupable<pack_w_pm_sum_kernel_body, 256, long long, const double*, const double*, const double*, double*, long long, double*, long long>((const void*)pack_w_pm_sum_kernel);
-  register_groupable<foo_from_x_kernel_body, 256, long long, const double*, double*>((const void*)foo_from_x_kernel);
-  register_groupable<gemv_rows2_kernel_body, 256, long long, long long, const double*, long long, const double*, const double*, long long, const double*, double*, double, double>((const void*)gemv_rows2_kernel);
-  register_groupable<ccsd_t1_small_kernel_body, 256, int, int, const double*, const double*, const double*, const double*, double*>((const void*)ccsd_t1_small_kernel);
-  register_groupable<ccsd_t1_assemble_kernel_body, 256, int, int, const double*, const double*, const double*, const double*, const double*, const double*, const double*, int, long long, const double*, int, long long, double*>((const void*)ccsd_t1_assemble_kernel);
-  register_groupable<gemv_rows_two_kernel_body, 256, long long, long long, const double*, long long, const double*, double*, double, double, long long, long long, const double*, long long, const double*, double*, double, double>((const void*)gemv_rows_two_kernel);
-  register_groupable<ccsd_finish_t2_rings_kernel_body, 256, long long, long long, double*, const double*, const double*, const double*, const double*, const double*, const double*, double*>((const void*)ccsd_finish_t2_rings_kernel);
-  register_groupable<gemv_rows_kernel_body, 256, long long, long long, const double*, long long, const double*, double*, double, double>((const void*)gemv_rows_kernel);
-  register_groupable<contract_mid_stage1_body, 256, long long, long long, int, const double*, const double*, double*>((const void*)contract_mid_stage1);
-  register_groupable<contract_mid_stage2_body, 256, long long, long long, int, const double*, double*, long long, double, double>((const void*)contract_mid_stage2);
-  register_groupable<unpack_tril_rows_kernel_body, 256, long long, long long, const double*, double*>((const void*)unpack_tril_rows_kernel);
-  register_groupable<unpack_tril_tiled_kernel_body, 256, long long, long long, const double*, double*, int, long long, long long>((const void*)unpack_tril_tiled_kernel);
-  register_groupable<fill_kernel_body, 1024, double*, long long, double>((const void*)fill_kernel);
+  return launch("dev_pack_tril_rows", pack_tril_rows_kernel, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(256), 0, g_stream, rows, n, full, packed);
 }
 
 }  // namespace qemb

@@ -526,8 +526,24 @@ __device__ __forceinline__ void dgemm_mfma_body(const uint3 BID, const uint3 GDI
 template <int WM, int WN, int WAVES_M, int WAVES_N, int BK, bool A_KC, bool B_KC, int VEC, int TAG = 0, int MODE = 0>
 __global__ void __launch_bounds__(WAVES_M* WAVES_N * 64, (WM * WN <= 16) ? 2 : 1)
     dgemm_mfma_kernel(GemmKArgs g) {
-  dgemm_mfma_body<WM, WN, WAVES_M, WAVES_N, BK, A_KC, B_KC, VEC, TAG, MODE>(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), g);
+  dgemm_mfma_body<WM, WN, WAVES_M, WAVES_N, BK, A_KC, B_KC, VEC, TAG, MODE>(block_id(), grid_dim(), g);
 }
+// grouped execution of several fragments' GEMMs in one launch (dev_ops_hip.hip "grouped launches"): the tiles small fragments run on -- 32 x 32, 64 x 64 and
+// the skinny 128 x 32 / 32 x 128 -- with every operand layout and 16- and 8-byte loads
+template <int WM, int WN, int WAVES_M, int WAVES_N, int BK, int MODE>
+struct GroupableGemmTile {
+  GroupableGemmTile() {
+#define QEMB_REG(AK, BKC)                                                                                                                                                                      \
+  register_groupable<dgemm_mfma_body<WM, WN, WAVES_M, WAVES_N, BK, AK, BKC, 2, 0, MODE>, WAVES_M * WAVES_N * 64>(dgemm_mfma_kernel<WM, WN, WAVES_M, WAVES_N, BK, AK, BKC, 2, 0, MODE>);       \
+  register_groupable<dgemm_mfma_body<WM, WN, WAVES_M, WAVES_N, BK, AK, BKC, 1, 0, 0>, WAVES_M * WAVES_N * 64>(dgemm_mfma_kernel<WM, WN, WAVES_M, WAVES_N, BK, AK, BKC, 1, 0, 0>);
+    QEMB_REG(true, true) QEMB_REG(true, false) QEMB_REG(false, true) QEMB_REG(false, false)
+#undef QEMB_REG
+  }
+};
+static const GroupableGemmTile<1, 1, 2, 2, 32, 0> reg_gemm_cfg2;
+static const GroupableGemmTile<2, 2, 2, 2, 16, 1> reg_gemm_cfg1;
+static const GroupableGemmTile<4, 1, 2, 2, 16, 0> reg_gemm_cfg20;
+static const GroupableGemmTile<1, 4, 2, 2, 16, 0> reg_gemm_cfg21;
 
 // C[b][m][n] = alpha * sum_s ws[b][s][m][n] + beta * C   (fixed summation order: deterministic)
 __device__ __forceinline__ void splitk_reduce_kernel_body(const uint3 BID, const uint3 GDIM, const double* __restrict__ ws, int S, long long M, long long N,
@@ -554,7 +570,8 @@ __device__ __forceinline__ void splitk_reduce_kernel_body(const uint3 BID, const
 }
 __global__ void __launch_bounds__(256) splitk_reduce_kernel(const double* __restrict__ ws, int S, long long M, long long N,
                                                             double* __restrict__ C, long long ldc, long long strideC,
-                                                            double alpha, double beta) { splitk_reduce_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), ws, S, M, N, C, ldc, strideC, alpha, beta); }
+                                                            double alpha, double beta) { splitk_reduce_kernel_body(block_id(), grid_dim(), ws, S, M, N, C, ldc, strideC, alpha, beta); }
+static const Groupable<splitk_reduce_kernel_body, 256> reg_splitk_reduce(splitk_reduce_kernel);
 // Few outputs, many slabs (the o x o / v x v shaped intermediates with K = o v^2 split several hundred ways): one WAVE per
 // output element, lane l sums slabs l, l+64, ... and the 64 partial sums are combined in a fixed butterfly order.
 __device__ __forceinline__ void splitk_reduce_wave_kernel_body(const uint3 BID, const uint3 GDIM, const double* __restrict__ ws, int S, long long M, long long N,
@@ -579,7 +596,8 @@ __device__ __forceinline__ void splitk_reduce_wave_kernel_body(const uint3 BID, 
 }
 __global__ void __launch_bounds__(256) splitk_reduce_wave_kernel(const double* __restrict__ ws, int S, long long M, long long N,
                                                                  double* __restrict__ C, long long ldc, long long strideC,
-                                                                 double alpha, double beta) { splitk_reduce_wave_kernel_body(make_uint3(blockIdx.x, blockIdx.y, blockIdx.z), make_uint3(gridDim.x, gridDim.y, gridDim.z), ws, S, M, N, C, ldc, strideC, alpha, beta); }
+                                                                 double alpha, double beta) { splitk_reduce_wave_kernel_body(block_id(), grid_dim(), ws, S, M, N, C, ldc, strideC, alpha, beta); }
+static const Groupable<splitk_reduce_wave_kernel_body, 256> reg_splitk_reduce_wave(splitk_reduce_wave_kernel);
 
 double* gemm_workspace(size_t bytes);   // dev_ops_hip.hip
 static long long* g_gemm_cyc = nullptr;          // QEMB_GEMM_TRACE: per-workgroup tick buffer of the traced launch
@@ -659,20 +677,16 @@ static int launch_cfg(const GemmDesc& d, hipStream_t s) {
   dim3 grid((unsigned)(g.tiles_m * g.tiles_n), (unsigned)(d.batch * g.ksplit), 1);
   dim3 block(WAVES_M * WAVES_N * 64, 1, 1);
   if (g_gemm_cyc_on && g_gemm_cyc && (long long)grid.x * grid.y * (TAG == 2 ? 72 : 1) <= g_gemm_cyc_cap) { g.cyc = g_gemm_cyc; g_gemm_cyc_blocks = (long long)grid.x * grid.y; if (TAG == 2) g.cyc2 = g_gemm_cyc + (long long)grid.x * grid.y * (WAVES_M * WAVES_N) * 5; }
-  hipLaunchKernelGGL(kern, grid, block, lds, s, g);
+  QTRY(launch("dev_gemm", kern, grid, block, lds, s, g));
   if (g.ksplit > 1 && !d.keep_slabs) {
     const long long mn = d.M * d.N;
     if (g.ksplit >= 128 && mn <= 65536) {
       const unsigned gx = (unsigned)((mn + 3) / 4 < 4096 ? (mn + 3) / 4 : 4096);      // 4 waves per block, one wave per element
-      hipLaunchKernelGGL(splitk_reduce_wave_kernel, dim3(gx, (unsigned)d.batch), dim3(256), 0, s, (const double*)g.C, g.ksplit,
-                         (long long)d.M, (long long)d.N, d.C, (long long)d.ldc, (long long)d.strideC, d.alpha, d.beta);
-    } else {
-      const unsigned gx = (unsigned)((mn + 255) / 256 < 2048 ? (mn + 255) / 256 : 2048);
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(gx, (unsigned)d.batch), dim3(256), 0, s, (const double*)g.C, g.ksplit,
-                         (long long)d.M, (long long)d.N, d.C, (long long)d.ldc, (long long)d.strideC, d.alpha, d.beta);
+      return launch("dev_gemm", splitk_reduce_wave_kernel, dim3(gx, (unsigned)d.batch), dim3(256), 0, s, g.C, g.ksplit, d.M, d.N, d.C, d.ldc, d.strideC, d.alpha, d.beta);
     }
+    const unsigned gx = (unsigned)((mn + 255) / 256 < 2048 ? (mn + 255) / 256 : 2048);
+    return launch("dev_gemm", splitk_reduce_kernel, dim3(gx, (unsigned)d.batch), dim3(256), 0, s, g.C, g.ksplit, d.M, d.N, d.C, d.ldc, d.strideC, d.alpha, d.beta);
   }
-  HIP_TRY(hipGetLastError());
   return QEMB_OK;
 }
 
@@ -739,9 +753,9 @@ int dev_mfma_f64_peak(int iters, int blocks_per_cu, double* tflops) {
   hipEvent_t e0, e1;
   HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
   const int grid = 256 * blocks_per_cu;
-  hipLaunchKernelGGL(mfma_f64_peak_kernel<NACC>, dim3(grid), dim3(256), 0, s, out, 64, 0.731);   // warm-up
+  QTRY(launch("dev_mfma_f64_peak", mfma_f64_peak_kernel<NACC>, dim3(grid), dim3(256), 0, s, out, 64, 0.731));   // warm-up
   HIP_TRY(hipEventRecord(e0, s));
-  hipLaunchKernelGGL(mfma_f64_peak_kernel<NACC>, dim3(grid), dim3(256), 0, s, out, iters, 0.731);
+  QTRY(launch("dev_mfma_f64_peak", mfma_f64_peak_kernel<NACC>, dim3(grid), dim3(256), 0, s, out, iters, 0.731));
   HIP_TRY(hipEventRecord(e1, s));
   HIP_TRY(hipEventSynchronize(e1));
   float ms = 0.f;
@@ -926,27 +940,6 @@ static int dev_gemm_dispatch(const GemmDesc& d) {
     case 235: return launch_layout<5, 2, 2, 4, 16>(d, s, vec2);
     default: set_error("dev_gemm: unknown tile config"); return QEMB_ERR_ARG;
   }
-}
-
-// grouped execution of several fragments' GEMMs in one launch (dev_ops_hip.hip "grouped launches"): registered there
-// (the tiles small fragments run on: 32 x 32, 64 x 64 and the skinny 128 x 32 / 32 x 128, every operand layout, 16- and 8-byte loads)
-template <int WM, int WN, int WAVES_M, int WAVES_N, int BK, int MODE>
-static void register_gemm_tile() {
-#define QEMB_REG(AK, BKC)                                                                                                                          \
-  register_groupable<dgemm_mfma_body<WM, WN, WAVES_M, WAVES_N, BK, AK, BKC, 2, 0, MODE>, WAVES_M * WAVES_N * 64, GemmKArgs>(                        \
-      (const void*)dgemm_mfma_kernel<WM, WN, WAVES_M, WAVES_N, BK, AK, BKC, 2, 0, MODE>);                                                           \
-  register_groupable<dgemm_mfma_body<WM, WN, WAVES_M, WAVES_N, BK, AK, BKC, 1, 0, 0>, WAVES_M * WAVES_N * 64, GemmKArgs>(                           \
-      (const void*)dgemm_mfma_kernel<WM, WN, WAVES_M, WAVES_N, BK, AK, BKC, 1, 0, 0>);
-  QEMB_REG(true, true) QEMB_REG(true, false) QEMB_REG(false, true) QEMB_REG(false, false)
-#undef QEMB_REG
-}
-void register_groupable_gemm() {
-  register_gemm_tile<1, 1, 2, 2, 32, 0>();     // cfg 2
-  register_gemm_tile<2, 2, 2, 2, 16, 1>();     // cfg 1
-  register_gemm_tile<4, 1, 2, 2, 16, 0>();     // cfg 20
-  register_gemm_tile<1, 4, 2, 2, 16, 0>();     // cfg 21
-  register_groupable<splitk_reduce_kernel_body, 256, const double*, int, long long, long long, double*, long long, long long, double, double>((const void*)splitk_reduce_kernel);
-  register_groupable<splitk_reduce_wave_kernel_body, 256, const double*, int, long long, long long, double*, long long, long long, double, double>((const void*)splitk_reduce_wave_kernel);
 }
 
 }  // namespace qemb

@@ -1,5 +1,8 @@
 // grouped_launch.h -- one launch for the same kernel of several fragments, or of several independent operations of one fragment (the chains of a
 // parallel region, dev_region_*) (see dev_ops_hip.hip "grouped launches" and dev_ops.h dev_tape_run).
+// A kernel becomes groupable by three things written next to each other: its `__device__ name_body(BID, GDIM, args...)`, the one-line `__global__
+// name(args...)` wrapper, and under it one registrar, `static const Groupable<name_body, 256> reg_name(name);`.  The argument types are deduced from the
+// wrapper -- whose types the kernelParams of a captured node have -- and the body must take exactly them after its two block coordinates.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -57,9 +60,10 @@ struct GroupInfo {
 std::map<const void*, GroupInfo>& groupable();      // dev_ops_hip.hip
 bool group_xcd_mode();                                // dev_ops_hip.hip (QEMB_GROUP_XCD)
 template <auto Body, int MAXT, class... A>
-static void register_groupable(const void* wrapper) {
+static void register_groupable(void (*wrapper)(A...)) {
   using P = Pack<A...>;
   using GA = GroupArgs<P>;
+  static_assert(std::is_same<decltype(Body), void (*)(uint3, uint3, A...)>::value, "the body of a groupable kernel takes (BID, GDIM) and then exactly the wrapper's parameters");
   static_assert(std::is_trivially_copyable<P>::value, "grouped kernel arguments must be plain data");
   static_assert(sizeof(GA) <= 4000, "grouped launch arguments exceed the kernel-argument segment");
   GroupInfo gi;
@@ -78,6 +82,11 @@ static void register_groupable(const void* wrapper) {
   gi.launch = [](const void* args, unsigned blocks, dim3 block, size_t lds, hipStream_t s) {
     hipLaunchKernelGGL((grouped_kernel<Body, MAXT, A...>), dim3(blocks), block, lds, s, *reinterpret_cast<const GA*>(args));
   };
-  groupable()[wrapper] = gi;
+  groupable()[(const void*)wrapper] = gi;
 }
+// The registrar of one groupable kernel: a namespace-scope constant under the wrapper, constructed when the library is loaded (it takes the stub's address and
+// fills a GroupInfo: no call into the HIP runtime), so the map is complete before any thread reads it and is only read afterwards.
+template <auto Body, int MAXT> struct Groupable {
+  template <class... A> explicit Groupable(void (*wrapper)(A...)) { register_groupable<Body, MAXT>(wrapper); }
+};
 }  // namespace qemb

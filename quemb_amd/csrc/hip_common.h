@@ -17,16 +17,27 @@ hipStream_t hip_stream();  // the library stream (created by dev_init)
     }                                                                                         \
   } while (0)
 
+// One launch of kernel(args...) -- every argument is converted to the kernel's own parameter type -- and its check.  who: the calling dev_* function, for the message.
+template <class... P, class... X>
+int launch(const char* who, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, X&&... args) {
+  static_assert(sizeof...(P) == sizeof...(X), "launch: one argument per kernel parameter");
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<X&&>(args)...);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { set_error(std::string(who) + ": kernel launch failed: " + hipGetErrorString(e)); return QEMB_ERR_DEVICE; }
+  return QEMB_OK;
+}
 // One 1-D launch of kernel(g, nitem): nitem work items in blocks of bs threads (bs: the kernel's launch bound).  who: for the messages.
 template <class Args>
 int launch_items(void (*kernel)(Args, long long), int bs, const Args& g, long long nitem, const char* who, hipStream_t st) {
   const long long nb = (nitem + bs - 1) / bs;
   if (nb > 0x7fffffffLL) { set_error(std::string(who) + ": too many blocks in one launch"); return QEMB_ERR_ARG; }
   if (nb <= 0) return QEMB_OK;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3(bs), 0, st, g, nitem);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch(who, kernel, dim3((unsigned)nb), dim3(bs), 0, st, g, nitem);
 }
+
+// The block's index and the grid's extent as the (BID, GDIM) a groupable kernel's wrapper hands to its body (grouped_launch.h).
+__device__ __forceinline__ uint3 block_id() { return make_uint3(blockIdx.x, blockIdx.y, blockIdx.z); }
+__device__ __forceinline__ uint3 grid_dim() { return make_uint3(gridDim.x, gridDim.y, gridDim.z); }
 
 // XCD-aware logical block index of the tiled HBM passes (round 4; profiles/r04_hbm_pmc.json).  Workgroups are dealt round-robin over the eight
 // XCDs, each with its own L2, so neighbouring 32 x 32 tiles -- whose 256-byte row pieces start at arbitrary offsets and share their first and

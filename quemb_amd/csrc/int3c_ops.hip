@@ -37,9 +37,7 @@ int dev_boys(int m_max, int64_t n, const double* x, double* out) {
   if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
   if (int rc = int3c_check_boys(m_max, n, x, out)) return rc;
   if (n == 0) return QEMB_OK;
-  hipLaunchKernelGGL(boys_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, m_max, (long long)n, x, out);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_boys", boys_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, m_max, n, x, out);
 }
 
 int dev_int3c_class(int la, int lb, int lp, const int3c::ClassArgs& g) {

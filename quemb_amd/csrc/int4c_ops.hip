@@ -97,9 +97,7 @@ int dev_int4c_pairprod(const int4c::PairProdArgs& g) {
   if (int rc = int4c_check_pairprod(g)) return rc;
   if (g.rows == 0) return QEMB_OK;
   const long long gy = g.rows < 65535 ? g.rows : 65535;
-  hipLaunchKernelGGL(int4c_pairprod_kernel, dim3((unsigned)((g.npq + 255) / 256), (unsigned)gy), dim3(256), 0, st, g);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_int4c_pairprod", int4c_pairprod_kernel, dim3((unsigned)((g.npq + 255) / 256), (unsigned)gy), dim3(256), 0, st, g);
 }
 
 int dev_int4c_add_transpose(int64_t m, double* A) {
@@ -107,9 +105,7 @@ int dev_int4c_add_transpose(int64_t m, double* A) {
   if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
   if (m <= 0 || m > 0x7fffffffLL || !A) { set_error("dev_int4c_add_transpose: bad arguments"); return QEMB_ERR_ARG; }
   const long long gy = m < 65535 ? m : 65535;
-  hipLaunchKernelGGL(int4c_addt_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)gy), dim3(256), 0, st, A, (long long)m);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_int4c_add_transpose", int4c_addt_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)gy), dim3(256), 0, st, A, m);
 }
 
 int dev_int4c_dmax(const int3c::Shell* sh, int nshell, int64_t N, const double* dm, double* out) {
@@ -117,9 +113,7 @@ int dev_int4c_dmax(const int3c::Shell* sh, int nshell, int64_t N, const double* 
   if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
   if (!sh || nshell <= 0 || N <= 0 || !dm || !out) { set_error("dev_int4c_dmax: bad arguments"); return QEMB_ERR_ARG; }
   const long long nitem = (long long)nshell * nshell;
-  hipLaunchKernelGGL(int4c_dmax_kernel, dim3((unsigned)((nitem + 127) / 128)), dim3(128), 0, st, sh, nshell, (long long)N, dm, out);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_int4c_dmax", int4c_dmax_kernel, dim3((unsigned)((nitem + 127) / 128)), dim3(128), 0, st, sh, nshell, N, dm, out);
 }
 
 }  // namespace qemb

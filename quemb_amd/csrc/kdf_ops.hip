@@ -137,9 +137,7 @@ int dev_kdf_split(int64_t rows, int64_t nao, const double* z, double* planes) {
   if (rows <= 0 || nao <= 0 || !z || !planes) { set_error("dev_kdf_split: bad arguments"); return QEMB_ERR_ARG; }
   const long long nb = (rows + 3) / 4;
   if (nb > 0x7fffffffLL || ((uintptr_t)z & 15)) { set_error("dev_kdf_split: too many rows or a source that is not 16-byte aligned"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL(kdf_split_kernel, dim3((unsigned)nb), dim3(256), 0, st, (long long)rows, (long long)nao, (long long)kdf_ld(nao), reinterpret_cast<const double2*>(z), planes);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_kdf_split", kdf_split_kernel, dim3((unsigned)nb), dim3(256), 0, st, rows, nao, kdf_ld(nao), reinterpret_cast<const double2*>(z), planes);
 }
 
 int dev_kdf_stack(int64_t nk, int64_t nao, int64_t n, const double* ta, double* Cs, double* Dk) {
@@ -149,9 +147,7 @@ int dev_kdf_stack(int64_t nk, int64_t nao, int64_t n, const double* ta, double* 
   const long long ld = kdf_ld(nao), total = nk * (4 * ld * n + 4 * nao * n);
   long long nb = (total + 255) / 256;
   if (nb > 4096) nb = 4096;
-  hipLaunchKernelGGL(kdf_stack_kernel, dim3((unsigned)nb), dim3(256), 0, st, (long long)nk, (long long)nao, (long long)n, ld, ta, Cs, Dk);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_kdf_stack", kdf_stack_kernel, dim3((unsigned)nb), dim3(256), 0, st, nk, nao, n, ld, ta, Cs, Dk);
 }
 
 int dev_kdf_pack(int64_t naux, int64_t n, const double* M, int paired, double w, double* F, int64_t ldf, double* partials, double* out2_dev) {
@@ -159,10 +155,8 @@ int dev_kdf_pack(int64_t naux, int64_t n, const double* M, int paired, double w,
   if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
   if (int rc = kdf_check_pack(naux, n, M, F, ldf, partials, out2_dev)) return rc;
   const long long nt = (n + 31) / 32, ntp = nt * (nt + 1) / 2, gy = naux < 1024 ? naux : 1024;
-  hipLaunchKernelGGL(kdf_pack_kernel, dim3((unsigned)ntp, (unsigned)gy), dim3(256), 0, st, (long long)naux, (long long)n, M, paired, w, F, (long long)ldf, partials);
-  hipLaunchKernelGGL(kdf_pack_max_kernel, dim3(1), dim3(256), 0, st, ntp * gy, (const double*)partials, out2_dev);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  QTRY(launch("dev_kdf_pack", kdf_pack_kernel, dim3((unsigned)ntp, (unsigned)gy), dim3(256), 0, st, naux, n, M, paired, w, F, ldf, partials));
+  return launch("dev_kdf_pack", kdf_pack_max_kernel, dim3(1), dim3(256), 0, st, ntp * gy, partials, out2_dev);
 }
 
 }  // namespace qemb

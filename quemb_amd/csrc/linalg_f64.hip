@@ -654,8 +654,7 @@ static int jacobi_rows(int nvec, int64_t len, double* W, int64_t ldw, double* Vt
     const size_t lds = sizeof(double) * ((size_t)nvec * (len + 1) + (size_t)nvec * (nvec + 1));
     static std::atomic<bool> attr_set{false};   // benign if two threads both set the attribute once
     if (!attr_set) { HIP_TRY(hipFuncSetAttribute((const void*)jacobi_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64)); attr_set = true; }
-    hipLaunchKernelGGL(jacobi_small_kernel, dim3(1), dim3(1024), lds, s, W, (long long)ldw, (int)len, Vt, nvec, np, tol_s, floor2, 40, d_sw);
-    HIP_TRY(hipGetLastError());
+    QTRY(launch("jacobi_rows", jacobi_small_kernel, dim3(1), dim3(1024), lds, s, W, ldw, (int)len, Vt, nvec, np, tol_s, floor2, 40, d_sw));
     int sw = 0;
     HIP_TRY(hipMemcpyAsync(&sw, d_sw, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -708,7 +707,7 @@ static int jacobi_rows(int nvec, int64_t len, double* W, int64_t ldw, double* Vt
       for (int r = 0; r < nbp - 1; ++r) HIP_TRY(launch_block_round(r));
     } else
     for (int r = 0; r < np - 1; ++r)
-      hipLaunchKernelGGL(jacobi_round_kernel, dim3(np / 2), dim3(256), 0, s, W, (long long)ldw, (long long)len, Vt, nvec, np, r, tol, floor2, d_off);
+      QTRY(launch("jacobi_rows", jacobi_round_kernel, dim3(np / 2), dim3(256), 0, s, W, ldw, len, Vt, nvec, np, r, tol, floor2, d_off));
     HIP_TRY(hipGetLastError());
     unsigned long long bits = 0;
     HIP_TRY(hipMemcpyAsync(&bits, d_off, sizeof(bits), hipMemcpyDeviceToHost, s));
@@ -752,13 +751,12 @@ int dev_jacobi_eigh_until(int64_t n64, double* A, double* w, double* V, int* swe
       if (!attr_db) { HIP_TRY(hipFuncSetAttribute((const void*)jacobi_eigh_small_db_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64)); attr_db = true; }
       const int items = nh * n;                    // <= 4 per thread
       const int nthreads = std::min(1024, std::max(64, (items + 63) / 64 * 64));
-      hipLaunchKernelGGL(jacobi_eigh_small_db_kernel, dim3(1), dim3(nthreads), lds_db, s, (const double*)A, n, w, V, tol, stop_below, 40, d_st,
-                         (const double*)nullptr, (double*)nullptr, 0, (double*)nullptr);
+      QTRY(launch("dev_jacobi_eigh_until", jacobi_eigh_small_db_kernel, dim3(1), dim3(nthreads), lds_db, s, A, n, w, V, tol, stop_below, 40, d_st,
+                  nullptr, nullptr, 0, nullptr));
     } else {
     const int nthreads = n <= 32 ? 256 : (n <= 64 ? 512 : 1024);
-    hipLaunchKernelGGL(jacobi_eigh_small_kernel, dim3(1), dim3(nthreads), lds, s, (const double*)A, n, w, V, tol, stop_below, 40, d_st);
+    QTRY(launch("dev_jacobi_eigh_until", jacobi_eigh_small_kernel, dim3(1), dim3(nthreads), lds, s, A, n, w, V, tol, stop_below, 40, d_st));
     }
-    HIP_TRY(hipGetLastError());
     int st = 0;
     HIP_TRY(hipMemcpyAsync(&st, d_st, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -772,19 +770,19 @@ int dev_jacobi_eigh_until(int64_t n64, double* A, double* w, double* V, int* swe
   QTRY_ALLOC(tmp, sizeof(double) * (size_t)n);
   QTRY_ALLOC(d_perm, sizeof(int) * (size_t)n);
   // Gershgorin shift
-  hipLaunchKernelGGL(rowabssum_kernel, dim3(n), dim3(256), 0, s, n, (long long)n, A, (long long)n, tmp);
+  QTRY(launch("dev_jacobi_eigh_until", rowabssum_kernel, dim3(n), dim3(256), 0, s, n, n, A, n, tmp));
   std::vector<double> h(n);
   HIP_TRY(hipMemcpyAsync(h.data(), tmp, sizeof(double) * n, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   double gersh = 0.0;
   for (double x : h) gersh = std::max(gersh, x);
   const double sigma = 1.0625 * gersh + 1.0e-300;
-  hipLaunchKernelGGL(add_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, A, (long long)n, sigma);
-  hipLaunchKernelGGL(set_identity_kernel, dim3((unsigned)(((long long)n * n + 255) / 256)), dim3(256), 0, s, n, Vt);
+  QTRY(launch("dev_jacobi_eigh_until", add_diag_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, A, n, sigma));
+  QTRY(launch("dev_jacobi_eigh_until", set_identity_kernel, dim3((unsigned)(((long long)n * n + 255) / 256)), dim3(256), 0, s, n, Vt));
   int rc = jacobi_rows(n, n, A, n, Vt, 0.0, sweeps_out, stop_below);
   if (rc == QEMB_OK) {
     // Rayleigh quotients lambda_i + sigma = W_i . Vt_i
-    hipLaunchKernelGGL(rowdot_kernel, dim3(n), dim3(256), 0, s, n, (long long)n, A, (long long)n, Vt, (long long)n, tmp);
+    QTRY(launch("dev_jacobi_eigh_until", rowdot_kernel, dim3(n), dim3(256), 0, s, n, n, A, n, Vt, n, tmp));
     HIP_TRY(hipMemcpyAsync(h.data(), tmp, sizeof(double) * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     std::vector<int> perm(n);
@@ -794,8 +792,7 @@ int dev_jacobi_eigh_until(int64_t n64, double* A, double* w, double* V, int* swe
     for (int i = 0; i < n; ++i) ws[i] = h[perm[i]] - sigma;
     HIP_TRY(hipMemcpyAsync(w, ws.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemcpyAsync(d_perm, perm.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(gather_rows_to_cols_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, n, (long long)n, Vt, (long long)n, d_perm, (const double*)nullptr, V, (long long)n);
-    HIP_TRY(hipGetLastError());
+    QTRY(launch("dev_jacobi_eigh_until", gather_rows_to_cols_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, n, n, Vt, n, d_perm, nullptr, V, n));
     HIP_TRY(hipStreamSynchronize(s));
   }
   (void)dev_free(Vt); (void)dev_free(tmp); (void)dev_free(d_perm);
@@ -820,9 +817,7 @@ int dev_jacobi_eigh_in_basis(int64_t n64, const double* F, const double* Cp, dou
   const double tol = std::max(1.0e-15, std::sqrt((double)n) * 2.22e-16);
   const int items = nh * n;
   const int nthreads = std::min(1024, std::max(64, (items + 63) / 64 * 64));
-  hipLaunchKernelGGL(jacobi_eigh_small_db_kernel, dim3(1), dim3(nthreads), lds_db, s, F, n, w, C_out, tol, stop_below, 40, status_dev, Cp, C2_out, nocc, dm_out);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_jacobi_eigh_in_basis", jacobi_eigh_small_db_kernel, dim3(1), dim3(nthreads), lds_db, s, F, n, w, C_out, tol, stop_below, 40, status_dev, Cp, C2_out, nocc, dm_out);
 }
 int dev_scf_fock_small(int64_t n64, const double* h, const double* J, const double* K, const double* D, double* F, double* err, double* scal2) {
   hipStream_t s = hip_stream();
@@ -834,9 +829,7 @@ int dev_scf_fock_small(int64_t n64, const double* h, const double* J, const doub
   const size_t lds = sizeof(double) * ((size_t)2 * n * ld + 2 * nthreads);
   static std::atomic<bool> attr{false};
   if (!attr) { HIP_TRY(hipFuncSetAttribute((const void*)scf_fock_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64)); attr = true; }
-  hipLaunchKernelGGL(scf_fock_small_kernel, dim3(1), dim3(nthreads), lds, s, n, h, J, K, D, F, err, scal2);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_scf_fock_small", scf_fock_small_kernel, dim3(1), dim3(nthreads), lds, s, n, h, J, K, D, F, err, scal2);
 }
 int dev_pack_density_sym(int64_t n64, const double* D, double* Dp) {
   hipStream_t s = hip_stream();
@@ -844,9 +837,7 @@ int dev_pack_density_sym(int64_t n64, const double* D, double* Dp) {
   const int n = (int)n64;
   if (n <= 0) return QEMB_OK;
   const long long np = (long long)n * (n + 1) / 2;
-  hipLaunchKernelGGL(pack_density_sym_kernel, dim3((unsigned)std::min<long long>((np + 255) / 256, 4096)), dim3(256), 0, s, n, D, Dp);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_pack_density_sym", pack_density_sym_kernel, dim3((unsigned)std::min<long long>((np + 255) / 256, 4096)), dim3(256), 0, s, n, D, Dp);
 }
 
 int dev_jacobi_svd(int64_t m64, int64_t n64, double* G, double* sv, double* U, double* V, int* sweeps_out) {
@@ -868,9 +859,9 @@ int dev_jacobi_svd(int64_t m64, int64_t n64, double* G, double* sv, double* U, d
   c.alpha = 1.0; c.beta = 0.0;
   int rc = dev_copy4(c);
   if (rc == QEMB_OK) {
-    hipLaunchKernelGGL(set_identity_kernel, dim3((unsigned)(((long long)n * n + 255) / 256)), dim3(256), 0, s, n, Vt);
+    QTRY(launch("dev_jacobi_svd", set_identity_kernel, dim3((unsigned)(((long long)n * n + 255) / 256)), dim3(256), 0, s, n, Vt));
     // scale for the "zero vector" floor: ||G||_F^2
-    hipLaunchKernelGGL(rowdot_kernel, dim3(n), dim3(256), 0, s, n, m, Wt, m, Wt, m, tmp);
+    QTRY(launch("dev_jacobi_svd", rowdot_kernel, dim3(n), dim3(256), 0, s, n, m, Wt, m, Wt, m, tmp));
     std::vector<double> h(n);
     HIP_TRY(hipMemcpyAsync(h.data(), tmp, sizeof(double) * n, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -879,7 +870,7 @@ int dev_jacobi_svd(int64_t m64, int64_t n64, double* G, double* sv, double* U, d
     const double floor2 = fro2 * 1.0e-30;   // vectors below 1e-15 * ||G||_F are numerically zero
     rc = jacobi_rows(n, m, Wt, m, Vt, floor2, sweeps_out);
     if (rc == QEMB_OK) {
-      hipLaunchKernelGGL(rowdot_kernel, dim3(n), dim3(256), 0, s, n, m, Wt, m, Wt, m, tmp);
+      QTRY(launch("dev_jacobi_svd", rowdot_kernel, dim3(n), dim3(256), 0, s, n, m, Wt, m, Wt, m, tmp));
       HIP_TRY(hipMemcpyAsync(h.data(), tmp, sizeof(double) * n, hipMemcpyDeviceToHost, s));
       HIP_TRY(hipStreamSynchronize(s));
       std::vector<int> perm(n);
@@ -893,9 +884,8 @@ int dev_jacobi_svd(int64_t m64, int64_t n64, double* G, double* sv, double* U, d
       HIP_TRY(hipMemcpyAsync(sv, ss.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
       HIP_TRY(hipMemcpyAsync(tmp, inv.data(), sizeof(double) * n, hipMemcpyHostToDevice, s));
       HIP_TRY(hipMemcpyAsync(d_perm, perm.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
-      if (U) hipLaunchKernelGGL(gather_rows_to_cols_kernel, dim3((unsigned)std::min<long long>((m + 255) / 256, 65535), n), dim3(256), 0, s, n, m, Wt, m, d_perm, tmp, U, (long long)n);
-      if (V) hipLaunchKernelGGL(gather_rows_to_cols_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, n, (long long)n, Vt, (long long)n, d_perm, (const double*)nullptr, V, (long long)n);
-      HIP_TRY(hipGetLastError());
+      if (U) QTRY(launch("dev_jacobi_svd", gather_rows_to_cols_kernel, dim3((unsigned)std::min<long long>((m + 255) / 256, 65535), n), dim3(256), 0, s, n, m, Wt, m, d_perm, tmp, U, n));
+      if (V) QTRY(launch("dev_jacobi_svd", gather_rows_to_cols_kernel, dim3((n + 255) / 256, n), dim3(256), 0, s, n, n, Vt, n, d_perm, nullptr, V, n));
       HIP_TRY(hipStreamSynchronize(s));
     }
   }
@@ -976,7 +966,7 @@ int dev_cholesky_lower(int64_t n64, double* A) {
   for (int k0 = 0; k0 < n && rc == QEMB_OK; k0 += NB) {
     const int nb = std::min(NB, n - k0);
     double* Akk = A + (long long)k0 * n + k0;
-    hipLaunchKernelGGL(diag_block_kernel, dim3(1), dim3(256), 0, s, Akk, (long long)n, nb, Dinv, 1, d_fail);
+    QTRY(launch("dev_cholesky_lower", diag_block_kernel, dim3(1), dim3(256), 0, s, Akk, n, nb, Dinv, 1, d_fail));
     const int rest = n - k0 - nb;
     if (rest > 0) {
       double* A21 = A + (long long)(k0 + nb) * n + k0;
@@ -1005,7 +995,7 @@ int dev_cholesky_lower(int64_t n64, double* A) {
     }
   }
   if (rc == QEMB_OK) {
-    hipLaunchKernelGGL(zero_upper_kernel, dim3((unsigned)(((long long)n * n + 255) / 256)), dim3(256), 0, s, n, A);
+    QTRY(launch("dev_cholesky_lower", zero_upper_kernel, dim3((unsigned)(((long long)n * n + 255) / 256)), dim3(256), 0, s, n, A));
     int fail = 0;
     HIP_TRY(hipMemcpyAsync(&fail, d_fail, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -1028,7 +1018,7 @@ int dev_tri_inverse_lower(int64_t n64, const double* L, double* X) {
   int rc = dev_fill(X, (int64_t)n * n, 0.0);
   for (int i0 = 0; i0 < n && rc == QEMB_OK; i0 += NB) {
     const int nb = std::min(NB, n - i0);
-    hipLaunchKernelGGL(diag_block_kernel, dim3(1), dim3(256), 0, s, Lc + (long long)i0 * n + i0, (long long)n, nb, Dinv, 0, (int*)nullptr);
+    QTRY(launch("dev_tri_inverse_lower", diag_block_kernel, dim3(1), dim3(256), 0, s, Lc + (long long)i0 * n + i0, n, nb, Dinv, 0, nullptr));
     // X[i,i] = Dinv
     Copy4Desc c{};
     c.dim[0] = 1; c.dim[1] = 1; c.dim[2] = nb; c.dim[3] = nb;

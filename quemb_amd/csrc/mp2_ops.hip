@@ -107,10 +107,8 @@ int dev_mp2_amplitudes(int64_t o, int64_t v, const double* ovov, const double* e
   const long long nt = (v + 31) / 32, ntp = nt * (nt + 1) / 2, oo = o * o;
   const long long gy = oo < 4096 ? oo : 4096;
   if (ntp > 0x7fffffffLL) { set_error("dev_mp2_amplitudes: too many virtual tiles"); return QEMB_ERR_ARG; }
-  hipLaunchKernelGGL(mp2_amplitudes_kernel, dim3((unsigned)ntp, (unsigned)gy), dim3(256), 0, st, (long long)o, (long long)v, ovov, eo, ev, t2, G, partials);
-  hipLaunchKernelGGL(mp2_energy_sum_kernel, dim3(1), dim3(256), 0, st, ntp * gy, (const double*)partials, e_dev);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  QTRY(launch("dev_mp2_amplitudes", mp2_amplitudes_kernel, dim3((unsigned)ntp, (unsigned)gy), dim3(256), 0, st, o, v, ovov, eo, ev, t2, G, partials));
+  return launch("dev_mp2_amplitudes", mp2_energy_sum_kernel, dim3(1), dim3(256), 0, st, ntp * gy, partials, e_dev);
 }
 
 }  // namespace qemb

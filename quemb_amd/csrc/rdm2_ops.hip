@@ -159,28 +159,22 @@ int dev_rdm2_assemble(int kind, int64_t o, int64_t v, const double* t1, const do
   if (int rc = rdm2_check_args(kind, o, v, t1, t2, out)) return rc;
   const long long n = o + v, n2 = n * n;
   const unsigned grid = (unsigned)(n2 < (1LL << 20) ? n2 : (1LL << 20));
-  if (kind == QEMB_RDM2_CCSD) hipLaunchKernelGGL(rdm2_assemble_kernel<QEMB_RDM2_CCSD>, dim3(grid), dim3(256), 0, st, (long long)o, (long long)v, t1, t2, dm1c, out);
-  else hipLaunchKernelGGL(rdm2_assemble_kernel<QEMB_RDM2_MP2>, dim3(grid), dim3(256), 0, st, (long long)o, (long long)v, t1, t2, dm1c, out);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  if (kind == QEMB_RDM2_CCSD) return launch("dev_rdm2_assemble", rdm2_assemble_kernel<QEMB_RDM2_CCSD>, dim3(grid), dim3(256), 0, st, o, v, t1, t2, dm1c, out);
+  return launch("dev_rdm2_assemble", rdm2_assemble_kernel<QEMB_RDM2_MP2>, dim3(grid), dim3(256), 0, st, o, v, t1, t2, dm1c, out);
 }
 
 int dev_rdm2_add_nc(int64_t m, const double* g, double alpha, double* X) {
   hipStream_t st = hip_stream();
   if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
   if (int rc = rdm2_check_full(m, g, X)) return rc;
-  hipLaunchKernelGGL(rdm2_add_nc_kernel, dim3((unsigned)rdm2_full_grid(m)), dim3(256), 0, st, (long long)m, g, alpha, X);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_rdm2_add_nc", rdm2_add_nc_kernel, dim3((unsigned)rdm2_full_grid(m)), dim3(256), 0, st, m, g, alpha, X);
 }
 
 int dev_rdm2_symmetrize(int64_t m, const double* g, double* X) {
   hipStream_t st = hip_stream();
   if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
   if (int rc = rdm2_check_full(m, X, X)) return rc;
-  hipLaunchKernelGGL(rdm2_symmetrize_kernel, dim3((unsigned)rdm2_full_grid(m)), dim3(256), 0, st, (long long)m, g, X);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  return launch("dev_rdm2_symmetrize", rdm2_symmetrize_kernel, dim3((unsigned)rdm2_full_grid(m)), dim3(256), 0, st, m, g, X);
 }
 
 int dev_rdm2_eri_dot(int64_t m, int sym, const double* eri, const double* K, double* partials, double* out_dev) {
@@ -189,11 +183,8 @@ int dev_rdm2_eri_dot(int64_t m, int sym, const double* eri, const double* K, dou
   if (int rc = rdm2_check_full(m, eri, K)) return rc;
   if ((sym != 1 && sym != 4 && sym != 8) || !partials || !out_dev) { set_error("dev_rdm2_eri_dot: sym must be 1, 4 or 8 and the outputs non-null"); return QEMB_ERR_ARG; }
   const int64_t grid = rdm2_full_grid(m);
-  hipLaunchKernelGGL(rdm2_eri_dot_kernel, dim3((unsigned)grid), dim3(256), 0, st, (long long)m, sym, eri, K, partials);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(rdm2_sum_partials_kernel, dim3(1), dim3(256), 0, st, (long long)grid, partials, out_dev);
-  HIP_TRY(hipGetLastError());
-  return QEMB_OK;
+  QTRY(launch("dev_rdm2_eri_dot", rdm2_eri_dot_kernel, dim3((unsigned)grid), dim3(256), 0, st, m, sym, eri, K, partials));
+  return launch("dev_rdm2_eri_dot", rdm2_sum_partials_kernel, dim3(1), dim3(256), 0, st, grid, partials, out_dev);
 }
 
 }  // namespace qemb

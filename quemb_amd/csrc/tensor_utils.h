@@ -12,12 +12,6 @@
 
 namespace qemb {
 
-#define QTRY(expr)              \
-  do {                          \
-    int _rc = (expr);           \
-    if (_rc != 0) return _rc;   \
-  } while (0)
-
 struct DBuf {
   double* p = nullptr;
   int64_t n = 0;

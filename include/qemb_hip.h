@@ -377,6 +377,26 @@ int qemb_ao2mo_direct(qemb_int_basis_t basis, int nfrag, const double* const* TA
 int qemb_ao2mo_direct_bytes(qemb_int_basis_t basis, int nfrag, const int* n, int64_t tile_pairs, int64_t* bytes);
 int qemb_int4c_tile_stats(qemb_int_basis_t basis, int64_t* n_visited, int64_t* n_skipped);
 
+/* ---- Cholesky-decomposed AO integrals: a 3-index factor from the geometry with no auxiliary basis (csrc/int4c.cpp: int4c_cholesky; kernels csrc/cd_ops.hip) ----
+ * Pivoted, incomplete Cholesky decomposition of the 4-fold packed tensor V[ij,kl] = (ij|kl) ~ sum_K L[K,ij] L[K,kl], blocked at shell-pair granularity and
+ * entirely on the device.  |V - L^T L| <= tol element by element (on a positive semidefinite residual |R[ij,kl]| <= sqrt(R[ij,ij] R[kl,kl]) <= tol); only the
+ * rank x npair integrals of the pivot columns are evaluated and nothing of size npair^2 exists.
+ * tol > 0; span in (0, 1]: a panel takes the shell pairs whose largest residual diagonal exceeds max(span max d, tol), at most panel_pairs AO pairs (<= 0: 128; a
+ * larger shell pair is a panel of its own); max_rank <= 0: what the memory the call may take allows, at most npair(N).
+ * qemb_int_cholesky: out_packed_host (nullable): [rank][npair(N)] in canonical packed order (pair mu (mu + 1) / 2 + nu, mu >= nu), with room for max_rank rows
+ *   (npair(N) rows when max_rank <= 0); *rank: the number of vectors.  Two calls give the same bits, on any execution context.
+ * qemb_int_cholesky_bytes: the device bytes of a call (pair stage and lists, the diagonal, one panel npair x panel, the factor up to max_rank).  The same figure is
+ *   compared with min(free device memory, the limit of qemb_int4c_mem_limit) before anything is allocated: QEMB_ERR_ALLOC with N in the message.
+ * qemb_int_cholesky_stats: out4 = rank, panels, integral columns evaluated, the final largest residual diagonal of the last decomposition of this basis.
+ * qemb_df_set_ints_from_cholesky: fills a context of qemb_df_create_empty with L as its [rank][N][N] tensor and an IDENTITY metric: no fit step, no rank x rank
+ *   matrix; qemb_df_transform* skip the product with the inverse metric factor.
+ * tol <= 0, span outside (0, 1]: QEMB_ERR_ARG; an orbital shell with l > 2: QEMB_ERR_UNSUPPORTED naming the shell; max_rank vectors with the largest residual diagonal
+ * still above tol: QEMB_ERR_NOCONV, the message names N, the rank and that diagonal -- never a silently worse factor. */
+int qemb_int_cholesky(qemb_int_basis_t basis, double tol, double span, int64_t panel_pairs, int64_t max_rank, double* out_packed_host, int64_t* rank);
+int qemb_int_cholesky_bytes(qemb_int_basis_t basis, int64_t panel_pairs, int64_t max_rank, int64_t* bytes);
+int qemb_int_cholesky_stats(qemb_int_basis_t basis, double* out4);
+int qemb_df_set_ints_from_cholesky(qemb_df_t df, qemb_int_basis_t basis, double tol, double span, int64_t panel_pairs, int64_t max_rank);
+
 /* the resident 3-index factor of a fragment (qemb_frag_mo_route_used gives its naux), naux x npair(n) to the host; QEMB_ERR_ARG without one */
 int qemb_frag_get_df_factor(qemb_frag_t f, double* B_host);
 

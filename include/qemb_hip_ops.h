@@ -224,6 +224,20 @@ int qemb_op_int4c_class(int la, int lb, int lc, int ld, const void* bf_a, const 
  * Rows: the AO pairs of the shell pairs of pairs_r in list order, inside a shell pair in increasing AO pair index; columns likewise from pairs_s.
  * out_host[row * n_cols + col] = (mu nu|la si), host.  thresh as qemb_int4c2e. */
 int qemb_op_int4c_tile(void* basis, const int32_t* pairs_r, int64_t n_r, const int32_t* pairs_s, int64_t n_s, double thresh, double* out_host);
+/* The kernels of the Cholesky decomposition of the AO integrals on their own (csrc/cd_ops.hip), host arrays in and out.
+ * qemb_op_cd_panel_factor: pivoted, rank-revealing Cholesky of the symmetric positive semidefinite n x n block A by one workgroup: pivots by the largest remaining
+ *   diagonal (ties: the lower column) until it is <= thr.  piv[j]: the pivot column of step j < *rank; T[j * n + c]: vector j at column c, so that
+ *   A ~ sum_j T[j][:]^T T[j][:] with a residual diagonal <= thr (rows >= *rank of T are zero).  *in_lds (nullable): 1 when the block was held in LDS.
+ * qemb_op_cd_diag_update: d[row] -= sum_{k < r} Lnew[k * np + row]^2 over np rows, the r rows pivrow[k] set to exactly 0 and negative residue clamped to 0; spmax[w]:
+ *   the largest d of rows row0[w] .. row0[w] + cnt[w] - 1 (nsp shell pairs), *dmax their maximum.
+ * qemb_op_cd_permute: out[k][ij] = L[k * npair + pos[ij]] (full = 0: [M][npair(N)]) or out[k][mu][nu] = L[k * npair + pos[pair(mu, nu)]] (full = 1: [M][N][N]).
+ * qemb_op_df_get_ints: the dense [naux][N][N] tensor of a DF context (qemb_df_t as void*) to the host; *identity_metric (nullable): 1 for a context filled by
+ *   qemb_df_set_ints_from_cholesky. */
+int qemb_op_cd_panel_factor(int n, const double* A_host, double thr, double* T_host, int32_t* piv_host, int32_t* rank, int* in_lds);
+int qemb_op_cd_diag_update(int64_t np, int r, const double* Lnew_host, const int32_t* pivrow_host, double* d_host, int64_t nsp, const int32_t* row0_host, const int32_t* cnt_host,
+                           double* spmax_host, double* dmax_host);
+int qemb_op_cd_permute(int64_t M, int64_t N, const double* L_host, const int32_t* pos_host, int full, double* out_host);
+int qemb_op_df_get_ints(void* df, double* out_host, int* identity_metric);
 
 #ifdef __cplusplus
 }

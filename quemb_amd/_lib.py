@@ -229,6 +229,14 @@ def _declare(lib):
     f("qemb_ao2mo_direct_bytes", I, V, I, P, L, C.POINTER(L))
     f("qemb_int4c_tile_stats", I, V, C.POINTER(L), C.POINTER(L))
     f("qemb_op_int4c_tile", I, V, P, L, P, L, D, P)
+    f("qemb_int_cholesky", I, V, D, D, L, L, P, C.POINTER(L))
+    f("qemb_int_cholesky_bytes", I, V, L, L, C.POINTER(L))
+    f("qemb_int_cholesky_stats", I, V, P)
+    f("qemb_df_set_ints_from_cholesky", I, V, V, D, D, L, L)
+    f("qemb_op_cd_panel_factor", I, I, P, D, P, P, C.POINTER(C.c_int32), C.POINTER(I))
+    f("qemb_op_cd_diag_update", I, L, I, P, P, P, L, P, P, P, P)
+    f("qemb_op_cd_permute", I, L, L, P, P, I, P)
+    f("qemb_op_df_get_ints", I, V, P, C.POINTER(I))
     f("qemb_op_int4c_class", I, I, I, I, I, P, P, P, P, P, P)
     f("qemb_op_boys", I, I, L, P, P)
     f("qemb_op_int3c_class", I, I, I, I, P, P, P, P, P)

@@ -86,7 +86,7 @@ int ao2mo_tile_accumulate(const double* E, int64_t ld, const TileRows& R, const 
 
 // ---------------------------------------------------------------------------------------------------------
 int DfContext::set_metric(int naux_, const double* j2c) {
-  naux = naux_;
+  naux = naux_; identity_metric = false;
   DBuf L;
   QTRY(L.alloc((int64_t)naux * naux));
   QTRY(dev_h2d(L, j2c, sizeof(double) * naux * naux));
@@ -95,7 +95,7 @@ int DfContext::set_metric(int naux_, const double* j2c) {
   return dev_tri_inverse_lower(naux, L, Linv);
 }
 int DfContext::set_cholesky_factor(int naux_, const double* Lh) {
-  naux = naux_;
+  naux = naux_; identity_metric = false;
   DBuf L;
   QTRY(L.alloc((int64_t)naux * naux));
   QTRY(dev_h2d(L, Lh, sizeof(double) * naux * naux));
@@ -103,7 +103,7 @@ int DfContext::set_cholesky_factor(int naux_, const double* Lh) {
   return dev_tri_inverse_lower(naux, L, Linv);
 }
 int DfContext::set_metric_pbc(int naux_, const double* j2c, int* ischol) {
-  naux = naux_;
+  naux = naux_; identity_metric = false;
   DBuf A, w, V;
   const int64_t n2 = (int64_t)naux * naux;
   QTRY(A.alloc(n2));
@@ -235,7 +235,7 @@ int DfContext::set_ints_semisparse(int N_, int64_t n_unique_, const double* uniq
 // the metric from an image that is on the device already (int3c.cpp); J is consumed
 int DfContext::set_metric_from_device(int naux_, DBuf&& J) {
   if (naux_ <= 0 || !J.p) { set_error("DfContext::set_metric_from_device: bad arguments"); return QEMB_ERR_ARG; }
-  naux = naux_;
+  naux = naux_; identity_metric = false;
   DBuf L = std::move(J);
   QTRY(dev_cholesky_lower(naux, L));
   QTRY(Linv.alloc((int64_t)naux * naux));
@@ -246,6 +246,13 @@ int DfContext::begin_ints_Lpq(int N_) {
   if (naux <= 0) { set_error("DfContext: set the metric first"); return QEMB_ERR_ARG; }
   if (N_ <= 0) { set_error("DfContext::begin_ints_Lpq: N must be positive"); return QEMB_ERR_ARG; }
   N = N_;
+  Usp.release(); n_unique = 0; Lact = nullptr; Lpq_im.release(); Lpq_sum.release();
+  return Lpq.alloc((int64_t)naux * N * N);
+}
+int DfContext::begin_ints_identity(int N_, int naux_) {
+  if (N_ <= 0 || naux_ <= 0) { set_error("DfContext::begin_ints_identity: N and the number of vectors must be positive"); return QEMB_ERR_ARG; }
+  N = N_; naux = naux_;
+  Linv.release(); identity_metric = true;
   Usp.release(); n_unique = 0; Lact = nullptr; Lpq_im.release(); Lpq_sum.release();
   return Lpq.alloc((int64_t)naux * N * N);
 }
@@ -377,11 +384,12 @@ int DfContext::transform_semisparse(const double* TA, int n, double* out_s4, con
 int DfContext::transform(const double* TA, int n, double* out_s4, const double* S_abs, double eps, DBuf* keep_bb) const {
   if (n <= 0 || n > N) { set_error("df transform: need 0 < n <= N"); return QEMB_ERR_ARG; }
   if (Linv.p && Usp.p) return transform_semisparse(TA, n, out_s4, S_abs, eps, keep_bb);
-  if (!Linv.p || !Lpq.p) { set_error("DfContext: metric and 3-index integrals must be set"); return QEMB_ERR_ARG; }
+  if ((!Linv.p && !identity_metric) || !Lpq.p) { set_error("DfContext: metric and 3-index integrals must be set"); return QEMB_ERR_ARG; }
   const int64_t np = npair(n);
   DBuf T1, T2, bp, bb;
   QTRY(T1.alloc((int64_t)naux * n * N)); QTRY(T2.alloc((int64_t)naux * n * n));
-  QTRY(bp.alloc((int64_t)naux * np)); QTRY(bb.alloc((int64_t)naux * np));
+  QTRY(bp.alloc((int64_t)naux * np));
+  if (!identity_metric) QTRY(bb.alloc((int64_t)naux * np));
   TimerScope lap_DF(TIMER_DF);
   // T1[L,i,nu] = sum_mu TA[mu,i] (L|mu nu)              (eri_onthefly.py:134, batched over L)
   QTRY(gemm(n, N, N, 1.0, TA, n, false, Lact ? Lact : Lpq.p, N, false, 0.0, T1, N, naux, 0, (int64_t)N * N, (int64_t)n * N));
@@ -407,7 +415,9 @@ int DfContext::transform(const double* TA, int n, double* out_s4, const double* 
   // unique pairs i >= j                                   (eri_sparse_DF.cpp:560-605 sym_P_pq)
   QTRY(dev_pack_tril_rows(naux, n, T2, bp));
   // bb = L^-1 bp                                          (eri_onthefly.py:141 / cublasDtrsm :667)
-  QTRY(gemm(naux, np, naux, 1.0, Linv, naux, true, bp, np, false, 0.0, bb, np));
+  // (an identity metric -- Cholesky vectors of the integrals themselves -- has no fit step: bb is bp)
+  if (identity_metric) bb = std::move(bp);
+  else QTRY(gemm(naux, np, naux, 1.0, Linv, naux, true, bp, np, false, 0.0, bb, np));
   // (ij|kl) = sum_L bb[L,ij] bb[L,kl] over packed pairs   (eri_onthefly.py:143 / cublasDsyrk :684, beta = 0)
   if (out_s4) QTRY(df_pair_product(np, naux, bb, out_s4));      // (null: the caller wants the factor alone -- a fragment that lives on it)
   if (keep_bb) *keep_bb = std::move(bb);                  // B_{ij}^{L} itself: the fragment's 3-index factor (MO integrals straight from it, ccsd.cpp)

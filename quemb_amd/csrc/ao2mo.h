@@ -60,6 +60,10 @@ class DfContext {
   // [naux][N][N] / semi-sparse [n_unique][naux] tensor without an upload -- the producer writes every element.
   int set_metric_from_device(int naux_, DBuf&& j2c_dev);
   int begin_ints_Lpq(int N_);
+  // A factor that needs no fit (int4c.cpp: the Cholesky vectors of the AO integrals, (mu nu|la si) ~ sum_K L[K,mu nu] L[K,la si]): the [naux_][N_][N_] storage for a
+  // producer on the device and an IDENTITY metric -- no naux x naux matrix exists and `transform` skips the product with Linv.  Any set_metric* call ends it.
+  int begin_ints_identity(int N_, int naux_);
+  bool identity_metric = false;
   int begin_ints_semisparse(int N_, int64_t n_unique_, const int64_t* reach_ptr, const int32_t* reach_nu, const int64_t* reach_off);
   // S_abs_dev (N x N, may be null) + eps: the MO-coefficient screening of the semi-sparse transform
   // (_cpp/eri_sparse_DF.cpp:443-465 get_AO_per_MO): (P|mu i) is kept only where |S_abs TA|(mu,i) >= eps.

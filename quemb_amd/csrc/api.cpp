@@ -15,6 +15,7 @@
 #include "kdf.h"
 #include "int3c.h"
 #include "int4c.h"
+#include "cd_core.h"
 #include <mutex>
 #include <set>
 
@@ -758,6 +759,84 @@ int qemb_df_set_ints_from_basis(qemb_df_t df, qemb_int_basis_t basis, qemb_int_b
   QTRY(df_metric_from_basis(d, a));
   QTRY(d->begin_ints_Lpq(o->nao));
   return int3c_fill(*o, *a, INT_LAYOUT_LPQ, nullptr, 0, d->Lpq);
+}
+// ---- Cholesky-decomposed AO integrals (int4c.cpp: int4c_cholesky) ----
+int qemb_int_cholesky(qemb_int_basis_t basis, double tol, double span, int64_t panel_pairs, int64_t max_rank, double* out_packed_host, int64_t* rank) {
+  IntBasis* o = live_basis(basis, "qemb_int_cholesky"); if (!o) return QEMB_ERR_ARG;
+  return int4c_cholesky(*o, tol, span, panel_pairs, max_rank, out_packed_host, rank);
+}
+int qemb_int_cholesky_bytes(qemb_int_basis_t basis, int64_t panel_pairs, int64_t max_rank, int64_t* bytes) {
+  IntBasis* o = live_basis(basis, "qemb_int_cholesky_bytes"); if (!o) return QEMB_ERR_ARG;
+  return int4c_cholesky_bytes(*o, panel_pairs, max_rank, bytes);
+}
+int qemb_int_cholesky_stats(qemb_int_basis_t basis, double* out4) {
+  IntBasis* o = live_basis(basis, "qemb_int_cholesky_stats"); if (!o) return QEMB_ERR_ARG;
+  if (!out4) { set_error("qemb_int_cholesky_stats: bad arguments"); return QEMB_ERR_ARG; }
+  for (int k = 0; k < 3; ++k) out4[k] = (double)o->cd_stats[k];
+  out4[3] = o->cd_dmax;
+  return QEMB_OK;
+}
+int qemb_df_set_ints_from_cholesky(qemb_df_t df, qemb_int_basis_t basis, double tol, double span, int64_t panel_pairs, int64_t max_rank) {
+  if (!df) { set_error("qemb_df_set_ints_from_cholesky: null handle"); return QEMB_ERR_ARG; }
+  IntBasis* o = live_basis(basis, "qemb_df_set_ints_from_cholesky"); if (!o) return QEMB_ERR_ARG;
+  return int4c_cholesky_to_df(*o, tol, span, panel_pairs, max_rank, *reinterpret_cast<DfContext*>(df));
+}
+// the op-level hooks of the decomposition's own kernels: host arrays in and out
+int qemb_op_cd_panel_factor(int n, const double* A_host, double thr, double* T_host, int32_t* piv_host, int32_t* rank, int* in_lds) {
+  if (n <= 0 || !A_host || !T_host || !piv_host || !rank) { set_error("qemb_op_cd_panel_factor: bad arguments"); return QEMB_ERR_ARG; }
+  DBuf A, T, work, ib;
+  QTRY(A.alloc((int64_t)n * n)); QTRY(T.alloc((int64_t)n * n)); QTRY(work.alloc(n)); QTRY(ib.alloc(n + 2));
+  int32_t *srow = reinterpret_cast<int32_t*>(ib.p), *piv = srow + n, *rk = piv + n;
+  std::vector<int32_t> id((size_t)n);
+  for (int c = 0; c < n; ++c) id[(size_t)c] = c;
+  QTRY(dev_h2d(A, A_host, sizeof(double) * n * n)); QTRY(dev_h2d(srow, id.data(), sizeof(int32_t) * n));
+  QTRY(dev_fill(T, (int64_t)n * n, 0.0));
+  if (int rc = dev_cd_panel_factor(A, n, srow, n, thr, nullptr, T, piv, rk, work)) { dev_sync(); return rc; }
+  QTRY(dev_d2h(rank, rk, sizeof(int32_t))); QTRY(dev_d2h(piv_host, piv, sizeof(int32_t) * n)); QTRY(dev_d2h(T_host, T, sizeof(double) * n * n));
+  if (in_lds) *in_lds = cd::panel_in_lds(n) ? 1 : 0;
+  return dev_sync();
+}
+int qemb_op_cd_diag_update(int64_t np, int r, const double* Lnew_host, const int32_t* pivrow_host, double* d_host, int64_t nsp, const int32_t* row0_host, const int32_t* cnt_host,
+                           double* spmax_host, double* dmax_host) {
+  if (np <= 0 || r < 0 || (r > 0 && (!Lnew_host || !pivrow_host)) || !d_host || nsp <= 0 || !row0_host || !cnt_host || !spmax_host || !dmax_host) {
+    set_error("qemb_op_cd_diag_update: bad arguments"); return QEMB_ERR_ARG;
+  }
+  for (int64_t w = 0; w < nsp; ++w)
+    if (row0_host[w] < 0 || cnt_host[w] < 0 || (int64_t)row0_host[w] + cnt_host[w] > np) { set_error("qemb_op_cd_diag_update: a shell pair leaves the diagonal"); return QEMB_ERR_ARG; }
+  for (int k = 0; k < r; ++k)
+    if (pivrow_host[k] < 0 || pivrow_host[k] >= np) { set_error("qemb_op_cd_diag_update: a pivot row leaves the diagonal"); return QEMB_ERR_ARG; }
+  const int64_t nb = cd::pair_max_partials(nsp);
+  DBuf Ln, d, red, ib;
+  QTRY(Ln.alloc(std::max<int64_t>(1, r * np))); QTRY(d.alloc(np)); QTRY(red.alloc(1 + nsp + nb)); QTRY(ib.alloc(nsp + r + 2));
+  int32_t *row0 = reinterpret_cast<int32_t*>(ib.p), *cnt = row0 + nsp, *srow = cnt + nsp, *piv = srow + r;      // srow = the pivot rows, piv = 0 .. r - 1
+  std::vector<int32_t> id((size_t)r);
+  for (int k = 0; k < r; ++k) id[(size_t)k] = k;
+  QTRY(dev_h2d(d, d_host, sizeof(double) * np)); QTRY(dev_h2d(row0, row0_host, sizeof(int32_t) * nsp)); QTRY(dev_h2d(cnt, cnt_host, sizeof(int32_t) * nsp));
+  if (r > 0) { QTRY(dev_h2d(Ln, Lnew_host, sizeof(double) * r * np)); QTRY(dev_h2d(srow, pivrow_host, sizeof(int32_t) * r)); QTRY(dev_h2d(piv, id.data(), sizeof(int32_t) * r)); }
+  if (int rc = dev_cd_diag_update(np, r, Ln, np, piv, srow, d, nsp, row0, cnt, red.p + 1, red.p + 1 + nsp, red.p)) { dev_sync(); return rc; }
+  QTRY(dev_d2h(d_host, d, sizeof(double) * np)); QTRY(dev_d2h(dmax_host, red, sizeof(double))); QTRY(dev_d2h(spmax_host, red.p + 1, sizeof(double) * nsp));
+  return dev_sync();
+}
+int qemb_op_cd_permute(int64_t M, int64_t N, const double* L_host, const int32_t* pos_host, int full, double* out_host) {
+  const int64_t np = N * (N + 1) / 2;
+  if (M <= 0 || N <= 0 || N > 32767 || !L_host || !pos_host || !out_host) { set_error("qemb_op_cd_permute: bad arguments"); return QEMB_ERR_ARG; }
+  for (int64_t k = 0; k < np; ++k)
+    if (pos_host[k] < 0 || pos_host[k] >= np) { set_error("qemb_op_cd_permute: a table entry leaves the row"); return QEMB_ERR_ARG; }
+  const int64_t nout = full ? M * N * N : M * np;
+  DBuf L, out, ib;
+  QTRY(L.alloc(M * np)); QTRY(out.alloc(nout)); QTRY(ib.alloc(np / 2 + 1));
+  int32_t* pos = reinterpret_cast<int32_t*>(ib.p);
+  QTRY(dev_h2d(L, L_host, sizeof(double) * M * np)); QTRY(dev_h2d(pos, pos_host, sizeof(int32_t) * np));
+  if (int rc = full ? dev_cd_unpack(M, N, L, np, pos, out) : dev_cd_gather_cols(M, np, L, np, pos, out, np)) { dev_sync(); return rc; }
+  QTRY(dev_d2h(out_host, out, sizeof(double) * nout));
+  return dev_sync();
+}
+int qemb_op_df_get_ints(qemb_df_t df, double* out_host, int* identity_metric) {
+  if (!df || !out_host) { set_error("qemb_op_df_get_ints: bad arguments"); return QEMB_ERR_ARG; }
+  DfContext* d = reinterpret_cast<DfContext*>(df);
+  if (!d->Lpq.p) { set_error("qemb_op_df_get_ints: the context holds no dense [naux][N][N] tensor"); return QEMB_ERR_ARG; }
+  if (identity_metric) *identity_metric = d->identity_metric ? 1 : 0;
+  return dev_d2h(out_host, d->Lpq, sizeof(double) * (int64_t)d->naux * d->N * d->N);
 }
 int qemb_df_set_ints_semisparse_from_basis(qemb_df_t df, qemb_int_basis_t basis, qemb_int_basis_t auxbasis, int64_t n_unique, const int64_t* pairs,
                                            const int64_t* reach_ptr, const int32_t* reach_nu, const int64_t* reach_off) {

@@ -375,6 +375,25 @@ namespace int4c { struct PairProdArgs; }
 int dev_int4c_pairprod(const int4c::PairProdArgs& args);
 int dev_int4c_add_transpose(int64_t m, double* A);
 
+// ---- pivoted Cholesky decomposition of the AO integrals (int4c.cpp: int4c_cholesky; kernels in cd_ops.hip, scalar restatement in cd_ops_hostcheck.cpp; arithmetic
+// in cd_core.h).  Rows are AO pairs in the order of the pair plan; a panel is n of them, srow[c] the row of panel column c, E[row * ld + c] its residual integrals.
+// Index arrays are int32 on the device.  No atomics: every result has the same bits on every run.
+//   gather_cols:  out[k * ldo + c] = in[k * ldi + idx[c]]   (k < rows, c < ncols)
+//   panel_factor: pivoted, rank-revealing Cholesky of the panel's own block A[c][c'] = E[srow[c] * ld + c'] by ONE workgroup (held in LDS up to cd::kPanelLdsMax
+//                 columns, in T and work beyond).  d (nullable): the running residual diagonal over all rows, the start of the panel's (null: the diagonal of A).
+//                 Pivots by the largest remaining diagonal (ties: the lower column) until it is <= thr.  piv[j]: the pivot column of step j; rank[0] = r; T[j * n + c]:
+//                 vector j at column c (row j has exact zeros at earlier pivots).  T: n * n doubles, work: n doubles.
+//   new_rows:     Lnew[j * ldl + row] for j < r and every row < np: forward substitution of E[row][piv[.]] against T
+//   diag_update:  d[row] -= sum_{k < r} Lnew[k * ldl + row]^2, pivot rows srow[piv[k]] exactly 0, negative residue 0 (r = 0: d as it is); then spmax[w] = the
+//                 largest d of shell pair w (rows row0[w] .. + cnt[w]) and dmax[0] = their maximum in two stages (partials: (nsp + 255) / 256 doubles)
+//   unpack:       out[k][mu][nu] = L[k * ld + pos[pair(mu, nu)]]: the [M][N][N] image of a DF context from plan-row order, every element once
+int dev_cd_gather_cols(int64_t rows, int64_t ncols, const double* in, int64_t ldi, const int32_t* idx, double* out, int64_t ldo);
+int dev_cd_panel_factor(const double* E, int64_t ld, const int32_t* srow, int n, double thr, const double* d, double* T, int32_t* piv, int32_t* rank, double* work);
+int dev_cd_new_rows(int64_t np, int n, int r, const double* E, int64_t ld, const double* T, const int32_t* piv, double* Lnew, int64_t ldl);
+int dev_cd_diag_update(int64_t np, int r, const double* Lnew, int64_t ldl, const int32_t* piv, const int32_t* srow, double* d, int64_t nsp, const int32_t* row0, const int32_t* cnt,
+                       double* spmax, double* partials, double* dmax);
+int dev_cd_unpack(int64_t M, int64_t N, const double* L, int64_t ld, const int32_t* pos, double* out);
+
 // ---- screening helpers of the semi-sparse DF transform ---------------------------------------------------------------
 // out[i] = (|x[i]| >= eps) ? 1 : 0
 int dev_threshold_mask(int64_t n, const double* x, double eps, double* out);

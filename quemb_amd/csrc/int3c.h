@@ -38,6 +38,8 @@ class IntBasis {
   int64_t int4c_mem_limit = -1;
   int64_t int4c_stats[2] = {0, 0};
   int64_t int4c_tiles[2] = {0, 0};      // tiles visited / skipped by the last integral-direct AO -> fragment transform (int4c_ao2mo_direct)
+  int64_t cd_stats[3] = {0, 0, 0};      // the last Cholesky decomposition of the basis (int4c_cholesky): rank, panels, integral columns evaluated
+  double cd_dmax = 0.0;                 // ... and the largest residual diagonal it ended with
   // pair lists, pair stage and Schwarz factors resident on the device, from the first call that needs them (direct J / K, the direct AO -> fragment transform,
   // the explicit tile) to the end of the basis
   std::shared_ptr<PairCache> pair_cache;

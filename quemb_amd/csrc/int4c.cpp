@@ -6,6 +6,7 @@
 #include "ao2mo.h"
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -539,6 +540,243 @@ int int4c_tile(IntBasis& orb, const int32_t* pr, int64_t nr, const int32_t* ps, 
   QTRY(E.alloc(rows[0] * rows[1]));
   if (int rc = fill_tile(orb, orb.pair_cache->dev.data, dl[0], whole(sub[0]), dl[1], whole(sub[1]), same, drow, dcol, rows[1], thresh, E)) { dev_sync(); return rc; }
   QTRY(dev_d2h(out_host, E, sizeof(double) * rows[0] * rows[1]));
+  return dev_sync();
+}
+
+// ---- pivoted Cholesky decomposition of the 4-fold packed tensor: blocked, at shell-pair granularity (int4c.h) ----
+namespace {
+
+constexpr int64_t kCdDefaultPanel = 128;
+
+inline int32_t* i32(double* p) { return reinterpret_cast<int32_t*>(p); }
+
+// the plan rows of the decomposition: every AO pair once, shell pair after shell pair in the order of plan_of (ONE slab of the tile layout), and per shell pair
+// its first row and its number of rows
+struct CdRows {
+  TileLayout lay;
+  std::vector<int32_t> row0, cnt;
+  int64_t max_sp = 0;
+};
+CdRows cd_rows(const IntBasis& orb, const PairPlan& plan, bool with_maps) {
+  CdRows r;
+  r.lay = tile_layout(orb, plan, npair_of(orb.nao), with_maps);
+  int64_t c = 0;
+  for (int I = 0; I < orb.nshell; ++I)
+    for (int J = 0; J <= I; ++J) {
+      const int64_t sz = n_ao_pairs(orb.shells[I], orb.shells[J], I == J);
+      r.row0.push_back((int32_t)c); r.cnt.push_back((int32_t)sz);
+      c += sz; r.max_sp = std::max(r.max_sp, sz);
+    }
+  return r;
+}
+// what a decomposition holds beside the factor: pair stage and lists (with the kDiag buffers), the diagonal, four int32 tables of npair entries, one panel, the
+// factor's columns at the panel's rows, the panel's own factor and its small arrays, the shell-pair tables and maxima
+int64_t cd_fixed_bytes(const PairPlan& plan, int64_t np, int64_t cap) {
+  return plan.bytes() + 8 * np + 16 * np + 8 * np * cap + 8 * cap * cap + 24 * cap + 32 * plan.n_pairs + 8192;
+}
+int64_t cd_rank_bytes(int64_t np, int64_t cap) { return 8 * (np + cap); }      // per vector: its row of the factor and of the gathered columns
+struct CdSizes { int64_t np, cap, panel_pairs, max_rank, bytes; };
+int cd_sizes(const IntBasis& orb, const PairPlan& plan, int64_t max_sp, int64_t panel_pairs, int64_t max_rank, CdSizes* z) {
+  z->np = npair_of(orb.nao);
+  z->panel_pairs = panel_pairs > 0 ? panel_pairs : kCdDefaultPanel;
+  z->cap = std::min(z->np, std::max(z->panel_pairs, max_sp));
+  if (max_rank <= 0) {      // what the memory allows, at most npair
+    Room r;
+    room_of(orb, &r);      // no figure: no room, one vector
+    const double left = r.room - (double)cd_fixed_bytes(plan, z->np, z->cap);
+    max_rank = left > 0.0 ? (int64_t)std::min((double)z->np, left / (double)cd_rank_bytes(z->np, z->cap)) : 0;
+    max_rank = std::max<int64_t>(1, max_rank);
+  }
+  z->max_rank = std::min(max_rank, z->np);
+  z->bytes = cd_fixed_bytes(plan, z->np, z->cap) + z->max_rank * cd_rank_bytes(z->np, z->cap);
+  return 0;
+}
+int cd_check_args(const IntBasis& orb, double tol, double span, const char* who) {
+  if (!(tol > 0.0) || !std::isfinite(tol)) { set_error(std::string(who) + ": the tolerance must be positive"); return QEMB_ERR_ARG; }
+  if (!(span > 0.0 && span <= 1.0)) { set_error(std::string(who) + ": the span factor must lie in (0, 1]"); return QEMB_ERR_ARG; }
+  return check_orbital(orb, who);
+}
+
+// the factor on the device in plan-row order, with the table that leads back to the canonical pair index
+struct CdFactor {
+  DBuf L, tables;
+  int64_t rank = 0, np = 0;
+  const int32_t* pos = nullptr;      // device: canonical AO pair index -> plan row
+};
+
+int cd_decompose(IntBasis& orb, double tol, double span, int64_t panel_pairs, int64_t max_rank, const char* who, CdFactor* out) {
+  QTRY(cd_check_args(orb, tol, span, who));
+  CdRows rows;
+  CdSizes z;
+  {      // sizes and guard from the plan on the host, before anything is allocated
+    const PairPlan plan = plan_of(orb);
+    rows = cd_rows(orb, plan, true);
+    QTRY(cd_sizes(orb, plan, rows.max_sp, panel_pairs, max_rank, &z));
+    QTRY(mem_guard(orb, (double)z.bytes, orb.pair_cache ? (double)plan.bytes() : 0.0, who,
+                   "the pair stage, the diagonal, a panel of " + std::to_string(z.cap) + " AO pairs and a factor of up to " + std::to_string(z.max_rank) + " vectors"));
+  }
+  QTRY(ensure_pair_cache(orb));
+  const DevicePlan& d = orb.pair_cache->dev;
+  const PairPlan& full = orb.pair_cache->plan;
+  const int64_t np = z.np, nsp = full.n_pairs, cap = z.cap, nb = (nsp + 255) / 256;
+  // int32 tables: pos, col (per canonical pair index), gidx (per plan row), row0, cnt (per shell pair), srow, piv (per panel column), the panel's rank
+  DBuf &tables = out->tables, dD, red, E, LS, T, work, diag;
+  QTRY(tables.alloc((3 * np + 2 * nsp + 2 * cap + 2) / 2 + 1));
+  int32_t *dpos = i32(tables.p), *dcol = dpos + np, *dgidx = dcol + np, *drow0 = dgidx + np, *dcnt = drow0 + nsp, *dsrow = dcnt + nsp, *dpiv = dsrow + cap, *drank = dpiv + cap;
+  QTRY(dD.alloc(np)); QTRY(red.alloc(1 + nsp + nb)); QTRY(E.alloc(np * cap)); QTRY(T.alloc(cap * cap)); QTRY(work.alloc(cap));
+  double *dmax_d = red.p, *spmax_d = red.p + 1, *part_d = red.p + 1 + nsp;
+  QTRY(dev_h2d(dpos, rows.lay.pos.data(), sizeof(int32_t) * np));
+  QTRY(dev_h2d(drow0, rows.row0.data(), sizeof(int32_t) * nsp)); QTRY(dev_h2d(dcnt, rows.cnt.data(), sizeof(int32_t) * nsp));
+  {      // 1. the diagonal: the launches of schwarz_factors, every (ab|ab) kept -- gathered from the class buffers into plan-row order
+    int64_t base[kNPairClass], words = 0;
+    for (int c = 0; c < kNPairClass; ++c) { base[c] = words; words += d.n[c] * (2 * kLa[c] + 1) * (2 * kLb[c] + 1); }
+    QTRY(diag.alloc(words));
+    for (int c = 0; c < kNPairClass; ++c) {
+      if (!d.n[c]) continue;
+      ClassArgs g{};
+      g.sh = orb.dev(); g.data = d.data; g.bra = g.ket = d.list(c, false); g.same = 1; g.thresh = 0.0; g.out = int4c::kDiag; g.N = orb.nao; g.dst = diag.p + base[c];
+      if (int rc = dev_int4c_class(kLa[c], kLb[c], kLa[c], kLb[c], g)) { dev_sync(); return rc; }
+    }
+    std::vector<int32_t> gidx((size_t)np);
+    size_t w = 0;
+    for (int I = 0; I < orb.nshell; ++I)
+      for (int J = 0; J <= I; ++J, ++w) {
+        const Shell &A = orb.shells[I], &B = orb.shells[J];
+        const bool sw = A.l < B.l;      // role A of the pair stage: the larger l (PairPlan::add)
+        const int c = full.cls[w], nsB = 2 * kLb[c] + 1, ncd = (2 * kLa[c] + 1) * nsB;
+        int64_t row = rows.row0[w];
+        for_ao_pairs(A, B, I == J, [&](int64_t m, int64_t n) {
+          const int a = (int)(m - A.ao0), b = (int)(n - B.ao0);
+          gidx[(size_t)row++] = (int32_t)(base[c] + full.idx[w] * ncd + (sw ? b * nsB + a : a * nsB + b));
+        });
+      }
+    if (words > 0x7fffffffLL) { set_error(std::string(who) + ": too many shell pairs"); return QEMB_ERR_ARG; }
+    QTRY(dev_h2d(dgidx, gidx.data(), sizeof(int32_t) * np));
+    if (int rc = dev_cd_gather_cols(1, np, diag, words, dgidx, dD, np)) { dev_sync(); return rc; }
+    if (int rc = dev_cd_diag_update(np, 0, nullptr, 0, nullptr, nullptr, dD, nsp, drow0, dcnt, spmax_d, part_d, dmax_d)) { dev_sync(); return rc; }
+  }
+  DBuf& L = out->L;
+  int64_t capL = std::min(z.max_rank, std::max<int64_t>(4 * cap, 64)), M = 0, panels = 0, cols = 0;
+  QTRY(L.alloc(capL * np));
+  std::vector<double> hred((size_t)(1 + nsp));
+  std::vector<int32_t> colmap((size_t)np), srow;
+  std::vector<int64_t> cand;
+  std::vector<char> inS((size_t)nsp);
+  double dmax = 0.0;
+  for (;;) {
+    QTRY(dev_d2h(hred.data(), red, sizeof(double) * (1 + nsp)));      // waits for everything issued so far
+    dmax = hred[0];
+    if (!(dmax > tol)) break;      // 2. the stop test
+    if (M >= z.max_rank) {
+      orb.cd_stats[0] = M; orb.cd_stats[1] = panels; orb.cd_stats[2] = cols; orb.cd_dmax = dmax;
+      char buf[64];
+      std::snprintf(buf, sizeof buf, "%.3e", dmax);
+      set_error(std::string(who) + ": with N = " + std::to_string(orb.nao) + ", the factor reached rank " + std::to_string(M) + " = max_rank with the largest residual diagonal still " + buf +
+                ", above the tolerance");
+      return QEMB_ERR_NOCONV;
+    }
+    // 3. the panel: whole shell pairs above the threshold, largest first
+    const double thr = std::max(span * dmax, tol);
+    cand.clear();
+    for (int64_t w = 0; w < nsp; ++w)
+      if (hred[(size_t)(1 + w)] > thr) cand.push_back(w);
+    std::stable_sort(cand.begin(), cand.end(), [&](int64_t a, int64_t b) { return hred[(size_t)(1 + a)] > hred[(size_t)(1 + b)]; });      // stable: ties by the lower index
+    std::fill(inS.begin(), inS.end(), 0);
+    std::fill(colmap.begin(), colmap.end(), -1);
+    srow.clear();
+    PairPlan sub[2];      // [0]: every shell pair outside the panel, [1]: the panel's, looked up in the pair table of the plan
+    auto add_to = [&](PairPlan& s, int64_t w) {
+      const int c = full.cls[(size_t)w]; const size_t i = (size_t)full.idx[(size_t)w];
+      s.a[c].push_back(full.a[c][i]); s.b[c].push_back(full.b[c][i]); s.off[c].push_back(full.off[c][i]);
+    };
+    for (int64_t w : cand) {
+      if (!srow.empty() && (int64_t)srow.size() + rows.cnt[(size_t)w] > z.panel_pairs) break;
+      inS[(size_t)w] = 1;
+      add_to(sub[1], w);
+      for (int e = 0; e < rows.cnt[(size_t)w]; ++e) {
+        const int64_t row = rows.row0[(size_t)w] + e, m = rows.lay.mu[(size_t)row], n = rows.lay.nu[(size_t)row];
+        colmap[(size_t)(m * (m + 1) / 2 + n)] = (int32_t)srow.size();
+        srow.push_back((int32_t)row);
+      }
+    }
+    for (int64_t w = 0; w < nsp; ++w)
+      if (!inS[(size_t)w]) add_to(sub[0], w);
+    const int64_t nS = (int64_t)srow.size();
+    DevicePlan dl[2];
+    for (int k = 0; k < 2; ++k) QTRY(dl[k].upload(sub[k]));
+    QTRY(dev_h2d(dcol, colmap.data(), sizeof(int32_t) * np)); QTRY(dev_h2d(dsrow, srow.data(), sizeof(int32_t) * nS));
+    // 4. E[:, S] = (all ij | kl in S), unscreened: (pairs outside S) x S and S x S into one buffer
+    int rc = fill_tile(orb, d.data, dl[0], whole(sub[0]), dl[1], whole(sub[1]), false, dpos, dcol, nS, 0.0, E);
+    if (!rc) rc = fill_tile(orb, d.data, dl[1], whole(sub[1]), dl[1], whole(sub[1]), true, dpos, dcol, nS, 0.0, E);
+    // 5. E -= L^T L[:, S]
+    if (!rc && M > 0) {
+      rc = LS.alloc(M * nS);
+      if (!rc) rc = dev_cd_gather_cols(M, nS, L, np, dsrow, LS, nS);
+      if (!rc) rc = gemm(np, nS, M, -1.0, L, np, false, LS, nS, false, 1.0, E, nS);
+    }
+    // 6. the panel's own block
+    if (!rc) rc = dev_cd_panel_factor(E, nS, dsrow, (int)nS, thr, dD, T, dpiv, drank, work);
+    int32_t r32 = 0;
+    if (!rc) rc = dev_d2h(&r32, drank, sizeof(int32_t));
+    if (rc) { dev_sync(); return rc; }      // the launches read the lists of dl
+    if (r32 <= 0) { set_error(std::string(who) + ": a panel above the threshold gave no pivot"); return QEMB_ERR_NUMERIC; }
+    const int64_t r = std::min<int64_t>(r32, z.max_rank - M);      // at max_rank the first pivots of the panel are kept; the stop test above then fails the call
+    if (M + r > capL) {
+      const int64_t ncap = std::min(z.max_rank, std::max(2 * capL, M + r));
+      DBuf bigger;
+      QTRY(bigger.alloc(ncap * np));
+      if (M > 0) QTRY(dev_d2d(bigger, L, sizeof(double) * M * np));
+      QTRY(dev_sync());
+      L = std::move(bigger); capL = ncap;
+    }
+    // 7. the new vectors at every AO pair, 8. the diagonal
+    rc = dev_cd_new_rows(np, (int)nS, (int)r, E, nS, T, dpiv, L.p + M * np, np);
+    if (!rc) rc = dev_cd_diag_update(np, (int)r, L.p + M * np, np, dpiv, dsrow, dD, nsp, drow0, dcnt, spmax_d, part_d, dmax_d);
+    if (rc) { dev_sync(); return rc; }
+    M += r; ++panels; cols += nS;
+  }
+  orb.cd_stats[0] = M; orb.cd_stats[1] = panels; orb.cd_stats[2] = cols; orb.cd_dmax = dmax;
+  out->rank = M; out->np = np; out->pos = dpos;
+  return 0;
+}
+
+}  // namespace
+
+int int4c_cholesky_bytes(const IntBasis& orb, int64_t panel_pairs, int64_t max_rank, int64_t* bytes) {
+  const char* who = "qemb_int_cholesky_bytes";
+  if (!bytes) { set_error(std::string(who) + ": bad arguments"); return QEMB_ERR_ARG; }
+  QTRY(check_orbital(orb, who));
+  const PairPlan plan = plan_of(orb);
+  CdSizes z;
+  QTRY(cd_sizes(orb, plan, cd_rows(orb, plan, false).max_sp, panel_pairs, max_rank, &z));
+  *bytes = z.bytes;
+  return 0;
+}
+
+int int4c_cholesky(IntBasis& orb, double tol, double span, int64_t panel_pairs, int64_t max_rank, double* out_host, int64_t* rank) {
+  const char* who = "qemb_int_cholesky";
+  if (!rank) { set_error(std::string(who) + ": bad arguments"); return QEMB_ERR_ARG; }
+  CdFactor f;
+  QTRY(cd_decompose(orb, tol, span, panel_pairs, max_rank, who, &f));
+  *rank = f.rank;
+  if (!out_host || f.rank == 0) return dev_sync();
+  DBuf P;      // 9. canonical packed order: the columns of the factor gathered by the table of plan rows
+  QTRY(P.alloc(f.rank * f.np));
+  if (int rc = dev_cd_gather_cols(f.rank, f.np, f.L, f.np, f.pos, P, f.np)) { dev_sync(); return rc; }
+  QTRY(dev_d2h(out_host, P, sizeof(double) * f.rank * f.np));
+  return dev_sync();
+}
+
+int int4c_cholesky_to_df(IntBasis& orb, double tol, double span, int64_t panel_pairs, int64_t max_rank, DfContext& df) {
+  const char* who = "qemb_df_set_ints_from_cholesky";
+  CdFactor f;
+  QTRY(cd_decompose(orb, tol, span, panel_pairs, max_rank, who, &f));
+  if (f.rank == 0) { set_error(std::string(who) + ": every integral is below the tolerance, the factor is empty"); return QEMB_ERR_NUMERIC; }
+  const int64_t N = orb.nao;
+  QTRY(mem_guard(orb, 8.0 * (double)f.rank * (double)(N * N + f.np), 8.0 * (double)f.rank * (double)f.np, who,
+                 "the factor of " + std::to_string(f.rank) + " vectors and its [rank][N][N] image"));
+  QTRY(df.begin_ints_identity((int)N, (int)f.rank));
+  if (int rc = dev_cd_unpack(f.rank, N, f.L, f.np, f.pos, df.Lpq)) { dev_sync(); return rc; }      // 9. straight into the context, every element once
   return dev_sync();
 }
 

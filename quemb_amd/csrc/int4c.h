@@ -40,6 +40,24 @@ int int4c_ao2mo_direct(IntBasis& orb, int nfrag, const double* const* TA_host, c
 // one explicit tile (qemb_op_int4c_tile): rows = the AO pairs of the shell pairs pairs_r[k] = (I, J), I >= J, in list order and inside a shell pair in increasing
 // AO pair index; columns likewise from pairs_s.  The two lists are the same list or have no shell pair in common.  out_host[row * ncol + col].
 int int4c_tile(IntBasis& orb, const int32_t* pairs_r, int64_t n_r, const int32_t* pairs_s, int64_t n_s, double thresh, double* out_host);
+// Pivoted, incomplete Cholesky decomposition of the 4-fold packed AO integrals, V[ij,kl] = (ij|kl) ~ sum_K L[K,ij] L[K,kl], blocked at shell-pair granularity and
+// entirely on the device: the residual diagonal d (kDiag form), then until max d <= tol a panel S of whole shell pairs whose largest d exceeds
+// max(span max d, tol) (descending, ties by the lower index, at most panel_pairs AO pairs; a larger shell pair alone), its integral columns (all ij | kl in S)
+// by the kTile form, the update with the vectors so far (ONE FP64 GEMM, K = rank), the pivoted factorisation of the panel's own block (dev_cd_panel_factor), the
+// new vectors at every AO pair (dev_cd_new_rows) and the diagonal update (dev_cd_diag_update).  On a positive semidefinite residual |R[ij,kl]| <=
+// sqrt(R[ij,ij] R[kl,kl]) <= tol at the end.  rank x npair integrals are evaluated instead of npair^2 / 2, nothing of size npair^2 exists.  Fixed orders and no
+// atomics: the same bits on every run and execution context.
+// The panel's columns are written by two fill_tile calls into ONE buffer with a common leading dimension: (all pairs but S) x S -- two sets without a pair in
+// common -- and S x S, the same list on both sides; the restriction fill_tile documents is kept.
+// panel_pairs <= 0: 128.  max_rank <= 0: what the memory the call may take allows, at most npair.  bytes: pair stage and lists, the diagonal, one panel
+// (npair x panel), the panel's work space and the factor up to max_rank -- compared with min(free memory, orb.int4c_mem_limit) before anything is allocated
+// (QEMB_ERR_ALLOC, N in the message).  tol <= 0 or span outside (0, 1]: QEMB_ERR_ARG.  max_rank vectors with max d still above tol: QEMB_ERR_NOCONV, the message
+// names N, the rank and the remaining max d.  orb.cd_stats / cd_dmax: rank, panels, columns evaluated, the final max d.
+// The factor leaves in canonical packed order (out_host, nullable: [rank][npair(N)], room for max_rank -- or npair -- rows) or as the [rank][N][N] tensor of a DF
+// context with an identity metric (DfContext::begin_ints_identity: no fit step).
+int int4c_cholesky_bytes(const IntBasis& orb, int64_t panel_pairs, int64_t max_rank, int64_t* bytes);
+int int4c_cholesky(IntBasis& orb, double tol, double span, int64_t panel_pairs, int64_t max_rank, double* out_host, int64_t* rank);
+int int4c_cholesky_to_df(IntBasis& orb, double tol, double span, int64_t panel_pairs, int64_t max_rank, DfContext& df);
 // one explicit block in the caller's shell order (qemb_op_int4c_class): out_host[((a * (2 lb + 1) + b) * (2 lc + 1) + c) * (2 ld + 1) + d]
 int int4c_block(const int l[4], const BfRecord* const rec[4], const double* c2s_host, double* out_host);
 

@@ -19,7 +19,7 @@ from . import _lib
 from ._lib import c_vp, check
 
 #: new `int_transform` literals next to the reference's IntTransforms (molbe/mbe.py:63-71)
-HIP_INT_TRANSFORMS = ("in-core-hip", "int-direct-DF-hip", "sparse-DF-hip", "on-fly-sparse-DF-hip", "int-direct-hip")
+HIP_INT_TRANSFORMS = ("in-core-hip", "int-direct-DF-hip", "sparse-DF-hip", "on-fly-sparse-DF-hip", "int-direct-hip", "cholesky-hip")
 
 
 def _arr(a):
@@ -208,6 +208,28 @@ class DFContext:
         """Context whose metric and (P|mu nu) both come from the device integral kernels (`set_ints_from_mol`)."""
         self = cls.empty(lib)
         self.set_ints_from_mol(mol, auxmol)
+        return self
+
+    @classmethod
+    def from_cholesky(cls, mol, tol=1e-8, span=0.01, panel_pairs=None, max_rank=None, lib=None, basis=None):
+        """Context whose 3-index tensor is the Cholesky factor of the AO integrals themselves, (mu nu|la si) ~ sum_K L[K,mu nu] L[K,la si] to `tol` element by
+        element, decomposed on the device from the geometry (qemb_df_set_ints_from_cholesky; integrals.DeviceBasis.cholesky has the parameters).  No auxiliary
+        basis and no fit: the metric is the identity and `transform` skips its product.  basis: an uploaded DeviceBasis of `mol` to use (its resident pair stage
+        is shared); None: one is made for the call.  `cd_stats`: rank, panels, columns evaluated, final largest diagonal."""
+        from .integrals import DeviceBasis
+        self = cls.empty(lib if basis is None else basis.lib)
+        b = DeviceBasis(mol, self.lib) if basis is None else basis
+        try:
+            check(self.lib.qemb_df_set_ints_from_cholesky(self.h, b.h, float(tol), float(span), int(panel_pairs or 0), int(max_rank or 0)),
+                  "qemb_df_set_ints_from_cholesky", self.lib)
+            self.cd_stats = b.cholesky_stats()
+        except Exception:
+            self.free()
+            raise
+        finally:
+            if basis is None:
+                b.free()
+        self.naux, self.nao = self.cd_stats["rank"], mol.nao
         return self
 
     def set_ints_from_mol(self, mol, auxmol, int_P_mu_nu=None):

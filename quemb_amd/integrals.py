@@ -398,6 +398,36 @@ class DeviceBasis:
         _lib.check(self.lib.qemb_int4c_tile_stats(self.h, C.byref(v), C.byref(z)), "qemb_int4c_tile_stats", self.lib)
         return v.value, z.value
 
+    def cholesky(self, tol=1e-8, span=0.01, panel_pairs=None, max_rank=None):
+        """Pivoted, incomplete Cholesky decomposition of the AO integrals on the device (qemb_int_cholesky): an (M, npair) array L in canonical packed order with
+        max |(ij|kl) - sum_K L[K,ij] L[K,kl]| <= tol, from M npair integrals instead of npair^2 / 2 and with no auxiliary basis.  span: a panel takes the shell
+        pairs whose largest residual diagonal exceeds max(span max d, tol); panel_pairs: AO pairs per panel (None: 128); max_rank: the most vectors the factor
+        may have (None: what the device memory allows, at most npair) -- a decomposition that needs more raises QembError (QEMB_ERR_NOCONV) instead of
+        returning a worse factor.  The same bits on every call; `cholesky_stats()` afterwards.  (The host buffer has room for max_rank rows: for large systems
+        keep the factor on the device with eri_transform.DFContext.from_cholesky.)"""
+        from . import _lib
+        npair = self.nao * (self.nao + 1) // 2
+        rows = npair if not max_rank else min(int(max_rank), npair)
+        out, m = np.empty((rows, npair)), C.c_int64()
+        _lib.check(self.lib.qemb_int_cholesky(self.h, float(tol), float(span), int(panel_pairs or 0), int(max_rank or 0), out.ctypes.data, C.byref(m)),
+                   "qemb_int_cholesky", self.lib)
+        return np.ascontiguousarray(out[: m.value])
+
+    def cholesky_bytes(self, panel_pairs=None, max_rank=None):
+        """device bytes a `cholesky` call takes (qemb_int_cholesky_bytes): pair stage and lists, the diagonal, one panel (npair x panel) and the factor up to
+        max_rank -- the figure the call checks against the free memory and the limit of qemb_int4c_mem_limit before it allocates anything"""
+        from . import _lib
+        b = C.c_int64()
+        _lib.check(self.lib.qemb_int_cholesky_bytes(self.h, int(panel_pairs or 0), int(max_rank or 0), C.byref(b)), "qemb_int_cholesky_bytes", self.lib)
+        return b.value
+
+    def cholesky_stats(self):
+        """dict(rank, panels, columns, max_d) of the last decomposition of this basis: vectors, panels, integral columns evaluated, the final largest residual diagonal"""
+        from . import _lib
+        out = (C.c_double * 4)()
+        _lib.check(self.lib.qemb_int_cholesky_stats(self.h, out), "qemb_int_cholesky_stats", self.lib)
+        return dict(rank=int(out[0]), panels=int(out[1]), columns=int(out[2]), max_d=float(out[3]))
+
     def free(self):
         if getattr(self, "h", None):
             self.lib.qemb_int_basis_free(self.h)
@@ -536,6 +566,18 @@ def eri(mol: Mole, sym=1, backend="host", thresh=0.0, lib=None):
         finally:
             b.free()
     return pack_eri(mol.eri_s1(), sym)
+
+
+def cholesky_eri(mol: Mole, tol=1e-8, backend="hip", span=0.01, panel_pairs=None, max_rank=None, lib=None):
+    """The Cholesky vectors of the AO integrals of `mol`, (M, npair) in canonical packed order (DeviceBasis.cholesky).  The decomposition exists on the device only:
+    backend="host" raises ValueError."""
+    if not _backend(backend):
+        raise ValueError("cholesky_eri: the decomposition runs on the device only (backend='hip')")
+    b = DeviceBasis(mol, lib)
+    try:
+        return b.cholesky(tol, span, panel_pairs, max_rank)
+    finally:
+        b.free()
 
 
 def get_jk(mol: Mole, dm, backend="hip", thresh=0.0, lib=None):

@@ -33,7 +33,7 @@ class BE:
     def __init__(self, mf, fobj, *, lo_method="lowdin", thr_bath=1.0e-10, int_transform="in-core-hip", auxbasis=None,
                  df_ints=None, nproc=1, ompnum=1, initialize_fragment_idx=None, solver_opts=None, lib=None, distribute=True, nstreams=None, lockstep=None,
                  eri_file=None, scratch_dir=None, restart=False, schmidt_method="subspace", MO_coeff_epsilon=1e-5, AO_coeff_epsilon=1e-10, df_resident="factor",
-                 integral_backend="host", int_direct_tile=None, int_direct_thresh=0.0):
+                 integral_backend="host", int_direct_tile=None, int_direct_thresh=0.0, cd_tol=1e-8, cd_span=0.01, cd_panel=None):
         if lo_method != "lowdin":
             raise NotImplementedError("only lo_method='lowdin' is mirrored (localisation is upstream of the hot path)")
         if restart:
@@ -62,6 +62,15 @@ class BE:
                 raise ValueError("int_transform='int-direct-hip' evaluates the integrals on the device: it needs integral_backend='hip'")
             if getattr(mf, "mol", None) is None:
                 raise ValueError("int_transform='int-direct-hip' evaluates the integrals from the geometry: the mean field needs `mol`")
+        # int_transform="cholesky-hip": a 3-index factor from mf.mol with no auxiliary basis -- the AO integrals are Cholesky-decomposed on the device to cd_tol
+        # (element-wise bound; DFContext.from_cholesky) and every fragment is transformed from the factor, as on the DF routes.  cd_span / cd_panel: the panel
+        # selection of the decomposition.  Needs integral_backend="hip" and a mean field with `mol`; `mf._eri` is ignored.  `cd_stats`: rank, panels, columns.
+        if int_transform == "cholesky-hip":
+            if integral_backend != "hip":
+                raise ValueError("int_transform='cholesky-hip' decomposes the integrals on the device: it needs integral_backend='hip'")
+            if getattr(mf, "mol", None) is None:
+                raise ValueError("int_transform='cholesky-hip' evaluates the integrals from the geometry: the mean field needs `mol`")
+        self.cd_tol, self.cd_span, self.cd_panel = float(cd_tol), float(cd_span), None if cd_panel is None else int(cd_panel)
         self.int_direct_tile = None if int_direct_tile is None else int(int_direct_tile)
         self.int_direct_thresh = float(int_direct_thresh)
         self.auxbasis = auxbasis
@@ -189,6 +198,18 @@ class BE:
                                 thresh=self.int_direct_thresh)
             finally:
                 basis.free()
+            self._eri_from_geometry = True
+        elif it == "cholesky-hip":
+            # the Cholesky factor of the AO integrals, decomposed once on the device (csrc/int4c.cpp: int4c_cholesky), is the 3-index tensor of a DF context with an
+            # identity metric: every fragment is transformed from it like on "int-direct-DF-hip".  `eri_` (mf._eri) is ignored: the integrals come from mf.mol
+            from . import _lib
+            df = et.DFContext.from_cholesky(self.mf.mol, tol=self.cd_tol, span=self.cd_span, panel_pairs=self.cd_panel, lib=self.lib or _lib.init())
+            try:
+                self.cd_stats = dict(df.cd_stats)
+                for I in idx:
+                    df.transform(self.Fobjs[I].TA, frag=self.Fobjs[I].dev, want_host=False, factor_only=self.df_resident == "factor")
+            finally:
+                df.free()
             self._eri_from_geometry = True
         elif it in ("int-direct-DF-hip", "sparse-DF-hip", "on-fly-sparse-DF-hip") and self._df_ints is None:
             # from the geometry alone, like the reference's "int-direct-DF" / "sparse-DF(-gpu)" / "on-fly-sparse-DF(-gpu)" branches

@@ -163,6 +163,36 @@ int qemb_frag_solve_mp2_batch(int nfrag, const qemb_frag_t* frags, const int* ns
                               const qemb_solver_opts* opts, int eeval, double* const* mo_coeff, double* const* mo_energy,
                               double* const* rdm1_emb, double* const* rdm1_mo, double* const* t2, double* e_frag, double* e_corr_mo,
                               double* e_scf, double* ebe_hf, int* scf_cycles);
+/* solver == "FCI" of be_func (molbe/solver.py:339-342, :507-547; the literal of this package is "FCI-hip"): fragment RHF -> `fci.FCI(mf, mo_coeff).kernel()` with
+ * h1 = C^T (fock + heff) C, the fragment's ERIs in the fragment-MO basis, nelec = (nsocc, nsocc) and a zero constant -> make_rdm1 -> back-rotation -> get_frag_energy
+ * with the cumulant of make_rdm2 (its mean-field part, solver.py:513-527, subtracted), in the determinant basis on the device: N_det = C(n, nsocc)^2 determinants
+ * |Ia Ib> over the occupation strings of each spin in ascending order of their bit patterns, the vector c[Ia][Ib] row-major.  One application of H is two gather
+ * passes around one FP64 product (pq|rs) D[rs, I] of shape n^2 x n^2 x N_det; the lowest state of the M_s = 0 space comes from a Davidson-Liu iteration started at
+ * the determinant of lowest diagonal, converged on the residual ||H c - E c||_2 <= conv_tol.  No atomics anywhere: two calls return the same bits.
+ * qemb_fci_opts: always start from qemb_default_fci_opts (conv_tol 1e-9, max_cycle 100 applications of H, max_space 12 basis vectors before the collapse to the
+ *   Ritz vector, lindep 1e-14); NULL means these defaults; another struct_size is QEMB_ERR_ARG.  Of opts only scf_*, verbose and strict_convergence are read;
+ *   non-convergence follows strict_convergence as for CCSD (QEMB_ERR_NOCONV, or results and QEMB_WARN_NOCONV).
+ * Outputs as qemb_frag_solve; rdm1_mo is make_rdm1 (symmetrised), civec (nullable) ns * ns doubles: normalised, its largest-magnitude component positive;
+ * e_fci the eigenvalue (e_fci - e_scf is the correlation energy of the embedding problem), n_iter the applications of H.  nsocc == n is a single determinant: the
+ * mean-field results.
+ * Limits: n > 16 is QEMB_ERR_UNSUPPORTED naming n.  Before anything is allocated the working set -- D and G (2 x 8 n^2 N_det bytes), (2 max_space + 4) vectors of
+ * N_det, the tables and the n^4 pieces; qemb_frag_fci_bytes reports it -- is compared with min(free device memory, the limit of qemb_frag_fci_mem_limit):
+ * QEMB_ERR_ALLOC naming n, nsocc and N_det.  In practice n <= 14 (7 alpha, 7 beta: 11.8 M determinants, 18.5 GB each for D and G).
+ * qemb_frag_fci_residual: ||H c - E c||_2 of the last FCI solve of the fragment. */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(qemb_fci_opts); set by qemb_default_fci_opts, checked by every entry point that takes the struct */
+  double conv_tol;           /* ||H c - E c||_2     default 1e-9  (PySCF: 1e-10 on the energy change) */
+  int max_cycle;             /* applications of H   default 100 */
+  int max_space;             /* basis vectors       default 12 */
+  double lindep;             /*                     default 1e-14 */
+} qemb_fci_opts;
+void qemb_default_fci_opts(qemb_fci_opts* opts);
+int qemb_frag_solve_fci(qemb_frag_t f, int nsocc, const double* h, const double* dm0, const qemb_solver_opts* opts, const qemb_fci_opts* fci_opts, int eeval,
+                        double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* civec, double* e_frag, double* e_fci, double* e_scf,
+                        double* ebe_hf, int* n_iter, int* scf_cycles);
+int qemb_frag_fci_bytes(int n, int nsocc, int max_space, int64_t* bytes);
+int qemb_frag_fci_mem_limit(qemb_frag_t f, int64_t bytes);
+int qemb_frag_fci_residual(qemb_frag_t f, double* residual);
 /* The fragment 2-RDM in the fragment-MO basis, Frags.rdm2__ (molbe/solver.py:528): out[n^4] (host, [p][q][r][s]) from what the LAST solve of this fragment
  * left on the device.  kind names that solve and must agree with it:
  *   QEMB_RDM2_CCSD  make_rdm2_urlx(t1, t2, with_dm1) of shared/external/ccsd_rdm.py:23-55 (unrelaxed), from the kept t1 / t2 of qemb_frag_solve[_batch];
@@ -171,9 +201,13 @@ int qemb_frag_solve_mp2_batch(int nfrag, const qemb_frag_t* frags, const int* ns
  * with_dm1 = 0: the ovov / vovo blocks only (the cumulant-like part get_frag_energy contracts); 1: plus the products of the correlation 1-RDM with the
  * HF determinant and the HF 2-RDM.  The tensor is assembled by one kernel that writes each of the n^4 elements once; 8 n^4 bytes of device memory are
  * needed beside the amplitudes (QEMB_ERR_ALLOC, with n in the message, when they are not free).  Relaxed (Lambda) 2-RDMs are not implemented: after a
- * solve with relax_density the call returns QEMB_ERR_UNSUPPORTED.  Without a preceding solve of that kind, or after new ERIs / another SCF: QEMB_ERR_ARG. */
+ * solve with relax_density the call returns QEMB_ERR_UNSUPPORTED.  Without a preceding solve of that kind, or after new ERIs / another SCF: QEMB_ERR_ARG.
+ *   QEMB_RDM2_FCI   make_rdm2 of the vector qemb_frag_solve_fci left on the device, in PySCF's convention dm2[p,q,r,s] = <p+ r+ s q> (E = sum h dm1 + 1/2 sum (pq|rs) dm2);
+ *                   with_dm1 = 0: minus the mean-field part of solver.py:513-527, what rdm2__ holds with use_cumulant.  D is formed once more and multiplied with itself
+ *                   (8 n^2 N_det bytes of work space beside two n^4 tensors). */
 #define QEMB_RDM2_CCSD 0
 #define QEMB_RDM2_MP2 1
+#define QEMB_RDM2_FCI 2
 int qemb_frag_rdm2(qemb_frag_t f, int kind, int with_dm1, double* out);
 /* The device memory qemb_frag_rdm2 of THIS fragment may take: before anything is allocated the call compares 8 n^4 bytes plus its workspace (the 1-RDM; for MP2 the
  * three o^2 v^2 tensors and the integral work space of forming t2 again) with min(free device memory, bytes) and fails with QEMB_ERR_ALLOC and n in the message when

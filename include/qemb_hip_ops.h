@@ -239,6 +239,16 @@ int qemb_op_cd_diag_update(int64_t np, int r, const double* Lnew_host, const int
 int qemb_op_cd_permute(int64_t M, int64_t N, const double* L_host, const int32_t* pos_host, int full, double* out_host);
 int qemb_op_df_get_ints(void* df, double* out_host, int* identity_metric);
 
+/* ---- determinant-space FCI (csrc/fci.cpp, kernels csrc/fci_ops.hip): the two operations behind qemb_frag_solve_fci on handed-in data.  Determinants and strings as
+ * in qemb_hip.h.  h_host: [n][n] (host); V_dev: [n^2][n^2] = (pq|rs), c_dev: N_det (device).
+ * qemb_op_fci_sigma: sigma_dev = H c.   qemb_op_fci_rdm12: dm1_host [n][n] (symmetrised) and, when dm2_dev != NULL, dm2 (n^4, device); cumulant != 0: minus the
+ * mean-field part with nsocc occupied orbitals.   qemb_op_fci_links: the link table of one spin, nsocc (n - nsocc + 1) x ns words (host, nullable: the counts only). */
+int qemb_op_fci_sigma(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev);
+int qemb_op_fci_rdm12(int n, int nsocc, const double* c_dev, int cumulant, double* dm1_host, double* dm2_dev);
+/* measurement hook (tools/fci_bench.py): one untimed application of H, then one whose three steps are bracketed by device timers; ms3 = D gather, G = V D, sigma gather */
+int qemb_op_fci_sigma_timed(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev, double* ms3);
+int qemb_op_fci_links(int n, int nsocc, int64_t* ns, int* nlink, int32_t* strings_host, int32_t* links_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,11 @@ class SolverOpts(C.Structure):
                 ("strict_convergence", C.c_int)]
 
 
+class FciOpts(C.Structure):
+    """qemb_fci_opts (include/qemb_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("conv_tol", C.c_double), ("max_cycle", C.c_int), ("max_space", C.c_int), ("lindep", C.c_double)]
+
+
 _lib = None
 _initialised_device = None
 
@@ -173,6 +178,15 @@ def _declare(lib):
     f("qemb_frag_solve", I, V, I, P, P, OP, I, P, P, P, P, P, P, P, DP, DP, DP, IP, IP)
     f("qemb_frag_solve_mp2", I, V, I, P, P, OP, I, P, P, P, P, P, P, DP, DP, DP, IP)
     f("qemb_frag_solve_mp2_batch", I, I, P, IP, P, P, OP, I, P, P, P, P, P, P, P, P, P, IP)
+    f("qemb_default_fci_opts", None, C.POINTER(FciOpts))
+    f("qemb_frag_solve_fci", I, V, I, P, P, OP, C.POINTER(FciOpts), I, P, P, P, P, P, P, DP, DP, DP, IP, IP)
+    f("qemb_frag_fci_bytes", I, I, I, I, C.POINTER(L))
+    f("qemb_frag_fci_mem_limit", I, V, L)
+    f("qemb_frag_fci_residual", I, V, DP)
+    f("qemb_op_fci_sigma", I, I, I, P, P, P, P)
+    f("qemb_op_fci_rdm12", I, I, I, P, I, P, P)
+    f("qemb_op_fci_sigma_timed", I, I, I, P, P, P, P, P)
+    f("qemb_op_fci_links", I, I, I, C.POINTER(L), IP, P, P)
     f("qemb_frag_rdm2", I, V, I, I, P)
     f("qemb_frag_rdm2_mem_limit", I, V, L)
     f("qemb_frag_rdm2_dev", I, V, I, I, P)

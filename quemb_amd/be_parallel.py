@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from .fragsolver import SOLVERS
 from .solver import ErrorMap
 
 
@@ -120,7 +121,7 @@ def be_func_parallel(pot, Fobjs, Nocc, solver, enuc, solver_args=None, scratch_d
                      stats=None, emap=None, nstreams=1, lockstep=False):
     """Same return contract as be_func (molbe/be_parallel.py:413-553).  `Fobjs` is the full fragment list on every
     rank; only the fragments with owner[i] == rank need device state (fock / ERIs) on this rank."""
-    if solver not in ("CCSD", "MP2"):
+    if solver not in SOLVERS:
         raise ValueError("Solver not implemented")
     rank, ws = world()
     if owner is None:

@@ -473,6 +473,95 @@ int qemb_frag_solve_mp2_batch(int nfrag, const qemb_frag_t* frags, const int* ns
   }
   return rc;
 }
+// ---- solver == "FCI-hip"
+void qemb_default_fci_opts(qemb_fci_opts* o) {
+  FciOptions d;
+  memset(o, 0, sizeof *o);
+  o->struct_size = (uint32_t)sizeof(qemb_fci_opts);
+  o->conv_tol = d.conv_tol; o->max_cycle = d.max_cycle; o->max_space = d.max_space; o->lindep = d.lindep;
+}
+int qemb_frag_solve_fci(qemb_frag_t f, int nsocc, const double* h, const double* dm0, const qemb_solver_opts* opts, const qemb_fci_opts* fci_opts, int eeval,
+                        double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* civec, double* e_frag, double* e_fci, double* e_scf,
+                        double* ebe_hf, int* n_iter, int* scf_cycles) {
+  CHECK_FRAG(f); CHECK_OPTS(opts);
+  if (fci_opts && fci_opts->struct_size != (uint32_t)sizeof(qemb_fci_opts)) {
+    set_error("qemb_fci_opts.struct_size is " + std::to_string(fci_opts->struct_size) + ", this library expects " + std::to_string(sizeof(qemb_fci_opts)) +
+              ": initialise the struct with qemb_default_fci_opts()");
+    return QEMB_ERR_ARG;
+  }
+  if (!h) { set_error("qemb_frag_solve_fci: h is NULL"); return QEMB_ERR_ARG; }
+  FciOptions fo;
+  if (fci_opts) { fo.conv_tol = fci_opts->conv_tol; fo.max_cycle = fci_opts->max_cycle; fo.max_space = fci_opts->max_space; fo.lindep = fci_opts->lindep; }
+  FragmentResult r;
+  int rc = FRAG(f)->solve_fci(nsocc, h, dm0, to_opts(opts), fo, eeval, &r, mo_coeff, mo_energy, rdm1_emb, rdm1_mo, civec);
+  if (n_iter) *n_iter = r.n_iter;
+  if (scf_cycles) *scf_cycles = r.scf_cycles;
+  FRAG(f)->last_lambda_iters = 0;
+  if (rc < 0) return rc;
+  if (e_frag) { e_frag[0] = r.e_frag[0]; e_frag[1] = r.e_frag[1]; e_frag[2] = r.e_frag[2]; }
+  if (e_fci) *e_fci = r.e_scf + r.e_corr_mo;
+  if (e_scf) *e_scf = r.e_scf;
+  if (ebe_hf) *ebe_hf = r.ebe_hf;
+  return rc;        // QEMB_OK, or QEMB_WARN_NOCONV with strict_convergence = 0
+}
+int qemb_frag_fci_bytes(int n, int nsocc, int max_space, int64_t* bytes) {
+  if (n <= 0 || nsocc <= 0 || nsocc > n || max_space < 2 || !bytes) { set_error("qemb_frag_fci_bytes: bad arguments"); return QEMB_ERR_ARG; }
+  if (n > kFciMaxOrb) { set_error("qemb_frag_fci_bytes: n = " + std::to_string(n) + " embedding orbitals; the determinant-space solver takes at most " + std::to_string(kFciMaxOrb)); return QEMB_ERR_UNSUPPORTED; }
+  *bytes = fci_bytes(n, nsocc, max_space);
+  return QEMB_OK;
+}
+int qemb_frag_fci_mem_limit(qemb_frag_t f, int64_t bytes) { CHECK_FRAG(f); FRAG(f)->set_fci_mem_limit(bytes); return QEMB_OK; }
+int qemb_frag_fci_residual(qemb_frag_t f, double* residual) { CHECK_FRAG(f); if (residual) *residual = FRAG(f)->fci_residual(); return QEMB_OK; }
+int qemb_op_fci_links(int n, int nsocc, int64_t* ns, int* nlink, int32_t* strings_host, int32_t* links_host) {
+  const FciTables* T = nullptr;
+  QTRY(fci_tables(n, nsocc, &T));
+  if (ns) *ns = T->ns;
+  if (nlink) *nlink = T->nlink;
+  if (strings_host) std::memcpy(strings_host, T->strings.data(), sizeof(int32_t) * T->strings.size());
+  if (links_host) std::memcpy(links_host, T->links.data(), sizeof(int32_t) * T->links.size());
+  return QEMB_OK;
+}
+int qemb_op_fci_sigma(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev) {
+  if (!h_host || !V_dev || !c_dev || !sigma_dev) { set_error("qemb_op_fci_sigma: null argument"); return QEMB_ERR_ARG; }
+  const FciTables* T = nullptr;
+  QTRY(fci_tables(n, nsocc, &T));
+  const int64_t n2 = (int64_t)n * n, N = T->ndet();
+  std::vector<double> Vh((size_t)(n2 * n2)), kh((size_t)n2);
+  QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
+  fci_one_body(n, h_host, Vh.data(), kh.data());
+  DBuf kd, D, G;
+  QTRY(kd.alloc(n2)); QTRY(D.alloc(n2 * N)); QTRY(G.alloc(n2 * N));
+  QTRY(dev_h2d(kd, kh.data(), sizeof(double) * n2));
+  QTRY(fci_apply(*T, kd, V_dev, c_dev, D, G, sigma_dev));
+  return dev_sync();
+}
+// measurement hook (tools/fci_bench.py): one untimed application, then one with the three steps bracketed by device timers; ms3 = gather, product, sigma gather
+int qemb_op_fci_sigma_timed(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev, double* ms3) {
+  if (!h_host || !V_dev || !c_dev || !sigma_dev || !ms3) { set_error("qemb_op_fci_sigma_timed: null argument"); return QEMB_ERR_ARG; }
+  const FciTables* T = nullptr;
+  QTRY(fci_tables(n, nsocc, &T));
+  const int64_t n2 = (int64_t)n * n, N = T->ndet();
+  std::vector<double> Vh((size_t)(n2 * n2)), kh((size_t)n2);
+  QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
+  fci_one_body(n, h_host, Vh.data(), kh.data());
+  DBuf kd, D, G;
+  QTRY(kd.alloc(n2)); QTRY(D.alloc(n2 * N)); QTRY(G.alloc(n2 * N));
+  QTRY(dev_h2d(kd, kh.data(), sizeof(double) * n2));
+  QTRY(fci_apply(*T, kd, V_dev, c_dev, D, G, sigma_dev));
+  const int slot[3] = {10, 11, 12};
+  for (int s : slot) QTRY(dev_timer_reset(s));
+  { TimerScope t(slot[0]); QTRY(dev_fci_gather(n, T->ns, T->nlink, T->links_dev, c_dev, D)); QTRY(t.close()); }
+  { TimerScope t(slot[1]); QTRY(gemm(n2, N, n2, 1.0, V_dev, n2, true, D, N, false, 0.0, G, N)); QTRY(t.close()); }
+  { TimerScope t(slot[2]); QTRY(dev_fci_sigma(n, T->ns, T->nlink, T->links_dev, kd, D, G, sigma_dev)); QTRY(t.close()); }
+  for (int k = 0; k < 3; ++k) { int64_t cnt = 0; QTRY(dev_timer_read(slot[k], &ms3[k], &cnt)); }
+  return QEMB_OK;
+}
+int qemb_op_fci_rdm12(int n, int nsocc, const double* c_dev, int cumulant, double* dm1_host, double* dm2_dev) {
+  if (!c_dev || !dm1_host) { set_error("qemb_op_fci_rdm12: null argument"); return QEMB_ERR_ARG; }
+  const FciTables* T = nullptr;
+  QTRY(fci_tables(n, nsocc, &T));
+  return fci_rdm12(*T, c_dev, cumulant ? nsocc : -1, dm1_host, dm2_dev);
+}
 int qemb_frag_rdm2(qemb_frag_t f, int kind, int with_dm1, double* out) {
   CHECK_FRAG(f);
   if (!out) { set_error("qemb_frag_rdm2: out is NULL"); return QEMB_ERR_ARG; }

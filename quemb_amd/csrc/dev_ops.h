@@ -324,6 +324,30 @@ int dev_rdm2_add_nc(int64_t m, const double* g, double alpha, double* X);
 int dev_rdm2_symmetrize(int64_t m, const double* g, double* X);
 int dev_rdm2_eri_dot(int64_t m, int sym, const double* eri, const double* K, double* partials, double* out_dev);
 
+// ---- determinant-space FCI (fci.cpp; kernels in fci_ops.hip, scalar restatement for the mock in fci_ops_hostcheck.cpp) ----------------------------------------
+// Determinants I = Ia * ns + Ib over the ns = C(n, nsocc) occupation strings of one spin (lexical order), c[Ia][Ib] row-major.  links: one spin's table,
+// links[l * ns + I] = (J << 9) | (pq << 1) | neg with <I|E_pq|J> = neg ? -1 : +1, nlink = nsocc (n - nsocc + 1) words per string; strings[I]: the bit pattern.
+//   gather:  D[pq * N + I] = sum_J <I|E^a_pq + E^b_pq|J> c[J]   (N = ns^2; every entry written by the thread that owns I, zeros included)
+//   sigma:   sigma[I] = sum_pq k[pq] D[pq * N + I] + 1/2 sum_pq sum_J <I|E_pq|J> G[pq * N + J]      (G = V D, formed by dev_gemm in between)
+//   diag:    hdiag[I] = <I|H|I> from the occupations, h [n][n], V [n^2][n^2] = (pq|rs)
+//   precond: out[I] = r[I] / (hdiag[I] - theta), |denominator| >= 1e-8
+//   dm2:     out[p,q,r,s] = A[qp][rs] - delta_qr dm1[p,s]  (A = D D^T), o_cum >= 0: minus the mean-field part of molbe/solver.py:513-527 with o_cum occupied orbitals
+// No atomics, one owner per output element: the same bits on every run.
+constexpr int kFciMaxOrb = 16;
+constexpr int64_t kFciMaxDet = (int64_t)12870 * 12870;      // C(16, 8)^2
+inline int fci_check_args(const char* who, int n, int64_t ns, int nlink, const void* a, const void* b, const void* c) {
+  if (n <= 0 || n > kFciMaxOrb || ns <= 0 || ns > 12870 || nlink <= 0 || nlink > kFciMaxOrb * kFciMaxOrb || !a || !b || !c) {
+    set_error(std::string(who) + ": bad arguments (n = " + std::to_string(n) + ", strings = " + std::to_string(ns) + ")");
+    return QEMB_ERR_ARG;
+  }
+  return 0;
+}
+int dev_fci_gather(int n, int64_t ns, int nlink, const int32_t* links, const double* c, double* D);
+int dev_fci_sigma(int n, int64_t ns, int nlink, const int32_t* links, const double* k, const double* D, const double* G, double* sigma);
+int dev_fci_diag(int n, int64_t ns, const int32_t* strings, const double* h, const double* V, double* hdiag);
+int dev_fci_precond(int64_t N, const double* r, const double* hdiag, double theta, double* out);
+int dev_fci_dm2(int n, int o_cum, const double* A, const double* dm1, double* out);
+
 // ---- k-point density fitting (kdf.cpp; kernels in kdf_ops.hip, scalar restatement for the mock in kdf_ops_hostcheck.cpp) -------------------------
 // Three HBM passes around the two quarter transforms of KdfContext::transform; no atomics, every output element written once.
 // Row stride of the planar images of a pair block: whole 128-byte lines.

@@ -1,0 +1,154 @@
+// fci_ops.hip -- the passes of the determinant-space FCI around its one FP64 product (dev_ops.h: dev_fci_*; driver: fci.cpp).
+//
+// Knowles-Handy form: with D[pq][I] = sum_J <I|E_pq|J> c_J (E = E^alpha + E^beta) one application of H is
+//     G = V D  (the MFMA GEMM, V[pq][rs] = (pq|rs)),      sigma_I = sum_pq k_pq D[pq][I] + 1/2 sum_pq sum_J <I|E_pq|J> G[pq][J].
+// Both passes here are GATHERS: one thread owns the determinant I = (Ia, Ib) and every entry of its column of D -- no atomics, a fixed order of additions,
+// the same bits on every run.  Ib is the fast thread index: the alpha links of a wave read one row of c / G contiguously (Ia, hence J, is uniform across
+// the threads of a row), the beta links gather within one row of ns doubles (27 kB at n = 14: cache), D is written in runs of consecutive I per pq.
+// The link table of one spin: links[l * ns + I] = (J << 9) | (pq << 1) | neg with <I|E_pq|J> = neg ? -1 : +1, nlink = nsocc (n - nsocc + 1) words per string
+// (string fast: the threads of a wave read consecutive words).  Within one spin a string meets every pq at most once.
+// Bytes of one application: D written (zeros, then the links) and read, G written and read: four passes over 8 n^2 N_det.
+#include "hip_common.h"
+
+namespace qemb {
+namespace {
+
+__global__ void __launch_bounds__(256) fci_gather_kernel(int n, long long ns, int nlink, const int* __restrict__ links, const double* __restrict__ c, double* D) {
+  const long long N = ns * ns;
+  const long long I = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (I >= N) return;
+  const long long Ia = I / ns, Ib = I - Ia * ns;
+  const int n2 = n * n;
+  for (int pq = 0; pq < n2; ++pq) D[pq * N + I] = 0.0;      // the owner writes every entry of its column: zeros where no link lands
+  for (int l = 0; l < nlink; ++l) {                          // alpha: |Ia Ib> <- E_pq |Ja Ib>
+    const int w = links[(long long)l * ns + Ia];
+    const double x = c[(long long)(w >> 9) * ns + Ib];
+    D[(long long)((w >> 1) & 255) * N + I] = (w & 1) ? -x : x;
+  }
+  for (int l = 0; l < nlink; ++l) {                          // beta: |Ia Ib> <- E_pq |Ia Jb>, added to what this thread stored above
+    const int w = links[(long long)l * ns + Ib];
+    const double x = c[Ia * ns + (w >> 9)];
+    double* d = D + (long long)((w >> 1) & 255) * N + I;
+    *d += (w & 1) ? -x : x;
+  }
+}
+
+__global__ void __launch_bounds__(256) fci_sigma_kernel(int n, long long ns, int nlink, const int* __restrict__ links, const double* __restrict__ k,
+                                                        const double* __restrict__ D, const double* __restrict__ G, double* __restrict__ sigma) {
+  const long long N = ns * ns;
+  const long long I = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (I >= N) return;
+  const long long Ia = I / ns, Ib = I - Ia * ns;
+  const int n2 = n * n;
+  double one = 0.0, two = 0.0;
+  for (int pq = 0; pq < n2; ++pq) one += k[pq] * D[pq * N + I];
+  for (int l = 0; l < nlink; ++l) {
+    const int w = links[(long long)l * ns + Ia];
+    const double x = G[(long long)((w >> 1) & 255) * N + (long long)(w >> 9) * ns + Ib];
+    two += (w & 1) ? -x : x;
+  }
+  for (int l = 0; l < nlink; ++l) {
+    const int w = links[(long long)l * ns + Ib];
+    const double x = G[(long long)((w >> 1) & 255) * N + Ia * ns + (w >> 9)];
+    two += (w & 1) ? -x : x;
+  }
+  sigma[I] = one + 0.5 * two;
+}
+
+// H_II from the occupations: sum_i (na_i + nb_i) h_ii + 1/2 sum_ij [(na_i na_j + nb_i nb_j)(J_ij - K_ij) + 2 na_i nb_j J_ij], J_ij = (ii|jj), K_ij = (ij|ji)
+__global__ void __launch_bounds__(256) fci_diag_kernel(int n, long long ns, const int* __restrict__ strings, const double* __restrict__ h, const double* __restrict__ V,
+                                                       double* __restrict__ hdiag) {
+  const long long N = ns * ns;
+  const long long I = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (I >= N) return;
+  const long long Ia = I / ns, Ib = I - Ia * ns;
+  const unsigned a = (unsigned)strings[Ia], b = (unsigned)strings[Ib];
+  const long long n2 = (long long)n * n;
+  double e = 0.0;
+  for (int i = 0; i < n; ++i) {
+    const int ai = (a >> i) & 1, bi = (b >> i) & 1;
+    if (!(ai | bi)) continue;
+    double s = (ai + bi) * h[i * n + i], t = 0.0;
+    for (int j = 0; j < n; ++j) {
+      const int aj = (a >> j) & 1, bj = (b >> j) & 1;
+      if (!(aj | bj)) continue;
+      const double Jij = V[(long long)(i * n + i) * n2 + j * n + j], Kij = V[(long long)(i * n + j) * n2 + j * n + i];
+      t += (ai * aj + bi * bj) * (Jij - Kij) + (ai * bj + bi * aj) * Jij;
+    }
+    e += s + 0.5 * t;
+  }
+  hdiag[I] = e;
+}
+
+// out = r / (H_II - theta), the denominator kept away from zero (1e-8, with its sign)
+__global__ void __launch_bounds__(256) fci_precond_kernel(long long N, const double* __restrict__ r, const double* __restrict__ hdiag, double theta, double* __restrict__ out) {
+  const long long I = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (I >= N) return;
+  double d = hdiag[I] - theta;
+  if (fabs(d) < 1e-8) d = d < 0.0 ? -1e-8 : 1e-8;
+  out[I] = r[I] / d;
+}
+
+// dm2[p,q,r,s] = A[qp][rs] - delta_qr dm1[p,s]   (A[pq][rs] = sum_I D[pq][I] D[rs][I] = <E_qp E_rs>; PySCF's dm2[p,q,r,s] = <p+ r+ s q>), every element written once;
+// o_cum >= 0: minus the mean-field part nc of the reference (hf = 2 I_occ over the first o_cum orbitals, del = dm1 - hf):
+//   nc[p,q,r,s] = hf_pq hf_rs + hf_pq del_rs + del_pq hf_rs - (hf_ps hf_qr + hf_ps del_qr + del_ps hf_qr) / 2
+__global__ void __launch_bounds__(256) fci_dm2_kernel(int n, int o_cum, const double* __restrict__ A, const double* __restrict__ dm1, double* __restrict__ out) {
+  const int n2 = n * n;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n2 * n2) return;
+  const int pq = idx / n2, rs = idx - pq * n2;
+  const int p = pq / n, q = pq - p * n, r = rs / n, s = rs - r * n;
+  double x = A[(q * n + p) * n2 + rs];
+  if (q == r) x -= dm1[p * n + s];
+  if (o_cum >= 0) {
+    const double hf_pq = (p == q && p < o_cum) ? 2.0 : 0.0, hf_rs = (r == s && r < o_cum) ? 2.0 : 0.0;
+    const double hf_ps = (p == s && p < o_cum) ? 2.0 : 0.0, hf_qr = (q == r && q < o_cum) ? 2.0 : 0.0;
+    const double d_pq = dm1[p * n + q] - hf_pq, d_rs = dm1[r * n + s] - hf_rs, d_ps = dm1[p * n + s] - hf_ps, d_qr = dm1[q * n + r] - hf_qr;
+    x -= hf_pq * hf_rs + hf_pq * d_rs + d_pq * hf_rs - 0.5 * (hf_ps * hf_qr + hf_ps * d_qr + d_ps * hf_qr);
+  }
+  out[idx] = x;
+}
+
+inline unsigned det_grid(int64_t N) { return (unsigned)((N + 255) / 256); }
+
+}  // namespace
+
+int dev_fci_gather(int n, int64_t ns, int nlink, const int32_t* links, const double* c, double* D) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (int rc = fci_check_args("dev_fci_gather", n, ns, nlink, links, c, D)) return rc;
+  return launch("dev_fci_gather", fci_gather_kernel, dim3(det_grid(ns * ns)), dim3(256), 0, st, n, ns, nlink, links, c, D);
+}
+
+int dev_fci_sigma(int n, int64_t ns, int nlink, const int32_t* links, const double* k, const double* D, const double* G, double* sigma) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (int rc = fci_check_args("dev_fci_sigma", n, ns, nlink, links, D, sigma)) return rc;
+  if (!k || !G) { set_error("dev_fci_sigma: bad arguments"); return QEMB_ERR_ARG; }
+  return launch("dev_fci_sigma", fci_sigma_kernel, dim3(det_grid(ns * ns)), dim3(256), 0, st, n, ns, nlink, links, k, D, G, sigma);
+}
+
+int dev_fci_diag(int n, int64_t ns, const int32_t* strings, const double* h, const double* V, double* hdiag) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (int rc = fci_check_args("dev_fci_diag", n, ns, 1, strings, h, hdiag)) return rc;
+  if (!V) { set_error("dev_fci_diag: bad arguments"); return QEMB_ERR_ARG; }
+  return launch("dev_fci_diag", fci_diag_kernel, dim3(det_grid(ns * ns)), dim3(256), 0, st, n, ns, strings, h, V, hdiag);
+}
+
+int dev_fci_precond(int64_t N, const double* r, const double* hdiag, double theta, double* out) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (N <= 0 || N > kFciMaxDet || !r || !hdiag || !out) { set_error("dev_fci_precond: bad arguments"); return QEMB_ERR_ARG; }
+  return launch("dev_fci_precond", fci_precond_kernel, dim3(det_grid(N)), dim3(256), 0, st, N, r, hdiag, theta, out);
+}
+
+int dev_fci_dm2(int n, int o_cum, const double* A, const double* dm1, double* out) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (n <= 0 || n > kFciMaxOrb || o_cum > n || !A || !dm1 || !out) { set_error("dev_fci_dm2: bad arguments"); return QEMB_ERR_ARG; }
+  const int n4 = n * n * n * n;
+  return launch("dev_fci_dm2", fci_dm2_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, n, o_cum, A, dm1, out);
+}
+
+}  // namespace qemb

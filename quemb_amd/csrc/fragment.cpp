@@ -649,7 +649,7 @@ void Fragment::retire_solver() {
 // get_frag_energy (helper.py:286-339) from the embedding-basis density and the contracted two-body pieces -- Z1, Z2 (energy_intermediates of the CCSD or the MP2
 // solver), or Imat of the relaxed path -- and update_ebe_hf: the host tail every correlated solve of a fragment shares
 int Fragment::frag_energies(int o, const std::vector<double>& C, const std::vector<double>& rdm, const std::vector<double>& hfdm, const std::vector<double>& Z1,
-                            const std::vector<double>& Z2, const std::vector<double>* Imat, FragmentResult* res) {
+                            const std::vector<double>& Z2, const std::vector<double>* Imat, FragmentResult* res, const std::vector<double>* e2_sites) {
   const int n = n_, v = n - o;
   const int64_t n2 = (int64_t)n * n;
   std::vector<double> J((size_t)n2), K((size_t)n2);
@@ -662,6 +662,7 @@ int Fragment::frag_energies(int o, const std::vector<double>& C, const std::vect
     }
     e1[P] = s1; ec[P] = sc;
     double s2 = 0;
+    if (e2_sites) { e2[P] = (*e2_sites)[(size_t)P]; continue; }      // (the FCI path contracts its 2-RDM on the device: one value per fragment site)
     if (Imat) {   // e2_P = 1/4 sum_p' C[P,p'] I[p',P]  (cc_lambda.h)
       for (int q = 0; q < n; ++q) s2 += C[(size_t)P * n + q] * (*Imat)[(size_t)q * nf_ + P];
       e2[P] = 0.25 * s2;
@@ -839,12 +840,122 @@ int Fragment::solve_mp2(int o, const double* h, const double* dm0, const Fragmen
   return sp_.unconverged ? QEMB_WARN_NOCONV : 0;
 }
 
+// ---- solver == "FCI-hip": the fragment RHF, then the exact ground state of the embedding Hamiltonian in the determinant basis (fci.cpp)
+// (pq|rs) in the fragment-MO basis as an n^2 x n^2 matrix from whichever residency the fragment has: the packed block (or B^T B of a fragment that lives on its
+// factor) unpacked to [n]^4 and multiplied from both sides with CC[(mu nu)][(pq)] = C[mu,p] C[nu,q] -- two products of n^2 x n^2 matrices (n <= 16)
+int Fragment::fci_mo_integrals(const std::vector<double>& C, DBuf& Vao, DBuf& CC, DBuf& Vmo) {
+  const int n = n_;
+  const int64_t n2 = (int64_t)n * n;
+  DBuf s4tmp, Tm;
+  const double* s4 = s4_ptr();
+  if (!s4) { QTRY(materialize_s4(s4tmp)); s4 = s4tmp; }
+  QTRY(Vao.alloc(n2 * n2)); QTRY(CC.alloc(n2 * n2)); QTRY(Vmo.alloc(n2 * n2)); QTRY(Tm.alloc(n2 * n2));
+  QTRY(dev_unpack_s4(n, s4, Vao));
+  std::vector<double> cc((size_t)(n2 * n2));
+  for (int mu = 0; mu < n; ++mu) for (int nu = 0; nu < n; ++nu) for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q)
+    cc[(size_t)((mu * n + nu) * n2 + p * n + q)] = C[(size_t)mu * n + p] * C[(size_t)nu * n + q];
+  QTRY(dev_h2d(CC, cc.data(), sizeof(double) * n2 * n2));
+  QTRY(gemm_nn(n2, n2, n2, 1.0, Vao, CC, 0.0, Tm));
+  QTRY(gemm_tn(n2, n2, n2, 1.0, CC, Tm, 0.0, Vmo));
+  s4_transient_.release();
+  return dev_sync();      // (Tm and a transient block go back to the pool on return)
+}
+
+int Fragment::solve_fci(int o, const double* h, const double* dm0, const FragmentOptions& opt, const FciOptions& fopt, int eeval, FragmentResult* res,
+                        double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* civec) {
+  const int n = n_, v = n - o;
+  const int64_t n2 = (int64_t)n * n;
+  if (n > kFciMaxOrb) { set_error("Fragment::solve_fci: n = " + std::to_string(n) + " embedding orbitals; the determinant-space solver takes at most " + std::to_string(kFciMaxOrb)); return QEMB_ERR_UNSUPPORTED; }
+  if (o <= 0 || o > n) { set_error("Fragment: need 0 < nsocc <= n"); return QEMB_ERR_ARG; }
+  if (eeval && (h1_.empty() || veff0_.empty())) { set_error("Fragment: set_energy_data(h1, veff0, ...) before an energy evaluation"); return QEMB_ERR_ARG; }
+  {      // the guard: D, G, the Davidson vectors, the tables and the n^4 pieces against what is free (or the fragment's limit), before anything is allocated
+    size_t free_b = 0, total_b = 0;
+    QTRY(dev_mem_info(&free_b, &total_b));
+    double room = (double)free_b;
+    if (fci_mem_limit_ >= 0 && (double)fci_mem_limit_ < room) room = (double)fci_mem_limit_;
+    const int64_t ns = fci_string_count(n, o);
+    const double need = (double)fci_bytes(n, o, fopt.max_space);
+    if (v > 0 && need > room) {
+      set_error("Fragment::solve_fci: n = " + std::to_string(n) + ", nsocc = " + std::to_string(o) + " gives N_det = " + std::to_string(ns * ns) + " determinants and a working set of " +
+                std::to_string(need * 1e-9) + " GB, more than the " + std::to_string(room * 1e-9) + " GB of device memory it may take");
+      return QEMB_ERR_ALLOC;
+    }
+  }
+  QTRY(solve_begin_scf(o, h, dm0, opt, eeval, res));
+  sp_.X1.release();
+  const std::vector<double>& C = sp_.C;
+  bool unconverged = sp_.unconverged;
+  res->e_corr_mo = 0.0; res->n_iter = 0; res->ccsd_converged = true; res->lambda_iters = 0;
+  fci_c_.release(); fci_residual_ = 0.0;
+  std::vector<double> dm((size_t)n2, 0.0), e2_sites((size_t)nf_, 0.0);
+  if (v > 0) {
+    const FciTables* T = nullptr;
+    QTRY(fci_tables(n, o, &T));
+    const int64_t N = T->ndet();
+    DBuf Vao, CC, Vmo;
+    QTRY(fci_mo_integrals(C, Vao, CC, Vmo));
+    std::vector<double> hmo((size_t)n2, 0.0), tmp((size_t)n2, 0.0);      // h in the fragment-MO basis: C^T h C
+    for (int p = 0; p < n; ++p) for (int nu = 0; nu < n; ++nu) { double s = 0; for (int mu = 0; mu < n; ++mu) s += C[(size_t)mu * n + p] * h[(size_t)mu * n + nu]; tmp[(size_t)p * n + nu] = s; }
+    for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int nu = 0; nu < n; ++nu) s += tmp[(size_t)p * n + nu] * C[(size_t)nu * n + q]; hmo[(size_t)p * n + q] = s; }
+    QTRY(fci_c_.alloc(N));
+    FciResult fr;
+    QTRY(fci_davidson(*T, hmo.data(), Vmo, fopt, fci_c_, &fr));
+    res->n_iter = fr.n_iter; res->ccsd_converged = fr.converged; fci_residual_ = fr.residual;
+    res->e_corr_mo = fr.e - res->e_scf;
+    if (!fr.converged) {
+      set_error("FCI: the Davidson iteration did not converge in max_cycle applications of H (residual " + std::to_string(fr.residual) + ")");
+      if (opt.strict) { fci_c_.release(); return QEMB_ERR_NOCONV; }
+      unconverged = true;
+    }
+    if (civec) QTRY(dev_d2h(civec, fci_c_, sizeof(double) * N));
+    DBuf G2;
+    if (eeval) QTRY(G2.alloc(n2 * n2));
+    QTRY(fci_rdm12(*T, fci_c_, o, dm.data(), eeval ? G2.p : nullptr));
+    if (eeval && nf_ > 0) {      // e2_P = 1/2 sum_qrs Gamma_emb[P,q,r,s] (Pq|rs), Gamma_emb = (C x C) Gamma (C x C)^T the cumulant in the embedding basis; rows P < n_f only
+      DBuf Tm, Ge, ed;
+      QTRY(Tm.alloc(n2 * n2)); QTRY(Ge.alloc(n2 * n2)); QTRY(ed.alloc(nf_));
+      QTRY(gemm_nn(n2, n2, n2, 1.0, CC, G2, 0.0, Tm));
+      QTRY(gemm_nt(n2, n2, n2, 1.0, Tm, CC, 0.0, Ge));
+      const int64_t n3 = n2 * n;
+      for (int P = 0; P < nf_; ++P) QTRY(dev_dot(n3, Ge.p + P * n3, Vao.p + P * n3, ed.p + P));
+      QTRY(dev_d2h(e2_sites.data(), ed, sizeof(double) * nf_));
+      for (double& e : e2_sites) e *= 0.5;
+    }
+  } else {      // a single determinant: the mean-field results, as the other solvers
+    for (int i = 0; i < n; ++i) dm[(size_t)i * n + i] = 2.0;
+    if (civec) civec[0] = 1.0;
+  }
+  if (rdm1_mo) std::memcpy(rdm1_mo, dm.data(), sizeof(double) * n2);
+  // rdm_emb = C rdm1 C^T / 2 (solver.py:496-505); hf_dm = Co Co^T
+  std::vector<double> rdm((size_t)n2, 0.0), hfdm((size_t)n2, 0.0), Y((size_t)n2, 0.0);
+  for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int i = 0; i < o; ++i) s += C[(size_t)p * n + i] * C[(size_t)q * n + i]; hfdm[(size_t)p * n + q] = s; }
+  if (v > 0) {
+    for (int p = 0; p < n; ++p) for (int r = 0; r < n; ++r) { const double c = C[(size_t)p * n + r]; for (int q = 0; q < n; ++q) Y[(size_t)p * n + q] += c * dm[(size_t)r * n + q]; }
+    for (int p = 0; p < n; ++p) for (int q = 0; q <= p; ++q) {
+      double t = 0, u = 0;
+      for (int r = 0; r < n; ++r) { t += Y[(size_t)p * n + r] * C[(size_t)q * n + r]; u += Y[(size_t)q * n + r] * C[(size_t)p * n + r]; }
+      rdm[(size_t)p * n + q] = rdm[(size_t)q * n + p] = 0.25 * (t + u);
+    }
+  } else rdm = hfdm;
+  if (rdm1_emb) std::memcpy(rdm1_emb, rdm.data(), sizeof(double) * n2);
+  if (mo_coeff) std::memcpy(mo_coeff, C.data(), sizeof(double) * n2);
+  if (mo_energy) std::memcpy(mo_energy, sp_.eps.data(), sizeof(double) * n);
+  if (eeval) QTRY(frag_energies(o, C, rdm, hfdm, std::vector<double>(), std::vector<double>(), nullptr, res, &e2_sites));
+  QTRY(dev_sync());      // (the next sweep may drive this fragment from another execution context, as after solve_end)
+  fci_dm1_ = std::move(dm); last_kind_ = QEMB_RDM2_FCI; last_o_ = o; last_relaxed_ = false;
+  return unconverged ? QEMB_WARN_NOCONV : 0;
+}
+
 // ---- Frags.rdm2__ (molbe/solver.py:528): the n^4 tensor of the last solve, written once by one kernel (rdm2_ops.hip)
 // Device bytes of one call: the tensor, the 1-RDM, and for MP2 what forming t2 again takes -- ovov, t2, G and the larger of the two integral routes' work space
 // (factor: the unpacked factor, its half-rotated virtual columns and Lov, mp2.cpp; block: the two buffers of mo_transform and the ovov block it leaves).
 int64_t Fragment::rdm2_bytes(int kind, int o, int with_dm1) const {
   const int64_t n = n_, v = n - o, n2 = n * n, ov2 = (int64_t)o * v * o * v;
   int64_t words = n2 * n2 + (with_dm1 ? n2 : 0);
+  if (kind == QEMB_RDM2_FCI) {      // the tensor, A = D D^T, the 1-RDM and D itself (fci_rdm12)
+    const int64_t ns = fci_string_count(n_, o);
+    return 8 * (2 * n2 * n2 + n2 + (v > 0 ? n2 * ns * ns : 0));
+  }
   if (kind == QEMB_RDM2_MP2 && v > 0) {
     const int64_t factor = (int64_t)df_naux_ * (n2 + n * v + (int64_t)o * v), block = 2 * mo_transform_work(n_) + ov2;
     words += 3 * ov2 + (use_factor_route() ? factor : block);
@@ -852,9 +963,9 @@ int64_t Fragment::rdm2_bytes(int kind, int o, int with_dm1) const {
   return 8 * words;
 }
 int Fragment::rdm2(int kind, int with_dm1, double* out, bool out_on_device) {
-  if (kind != QEMB_RDM2_CCSD && kind != QEMB_RDM2_MP2) { set_error("Fragment::rdm2: kind must be QEMB_RDM2_CCSD or QEMB_RDM2_MP2"); return QEMB_ERR_ARG; }
+  if (kind != QEMB_RDM2_CCSD && kind != QEMB_RDM2_MP2 && kind != QEMB_RDM2_FCI) { set_error("Fragment::rdm2: kind must be QEMB_RDM2_CCSD, QEMB_RDM2_MP2 or QEMB_RDM2_FCI"); return QEMB_ERR_ARG; }
   if (last_kind_ < 0) { set_error("Fragment::rdm2: no solve has run on this fragment since its ERIs or orbitals were last set"); return QEMB_ERR_ARG; }
-  if (kind != last_kind_) { set_error(std::string("Fragment::rdm2: the last solve of this fragment was ") + (last_kind_ == QEMB_RDM2_MP2 ? "MP2" : "CCSD") + ", not the kind asked for"); return QEMB_ERR_ARG; }
+  if (kind != last_kind_) { set_error(std::string("Fragment::rdm2: the last solve of this fragment was ") + (last_kind_ == QEMB_RDM2_MP2 ? "MP2" : last_kind_ == QEMB_RDM2_FCI ? "FCI" : "CCSD") + ", not the kind asked for"); return QEMB_ERR_ARG; }
   if (last_relaxed_) { set_error("Fragment::rdm2: relaxed (Lambda) 2-RDMs are not implemented; solve without relax_density"); return QEMB_ERR_UNSUPPORTED; }
   const int n = n_, o = last_o_, v = n - o;
   const int64_t n2 = (int64_t)n * n;
@@ -868,6 +979,23 @@ int Fragment::rdm2(int kind, int with_dm1, double* out, bool out_on_device) {
     set_error("Fragment::rdm2: the 2-RDM of a fragment with n = " + std::to_string(n) + " takes " + std::to_string((double)n2 * (double)n2 * 8e-9) + " GB and " +
               std::to_string((double)(rdm2_bytes(kind, o, with_dm1) - 8 * n2 * n2) * 1e-9) + " GB of workspace, more than the " + std::to_string(room * 1e-9) + " GB of device memory it may take");
     return QEMB_ERR_ALLOC;
+  }
+  if (kind == QEMB_RDM2_FCI) {      // make_rdm2 of the kept vector; with_dm1 = 0: minus the mean-field part (what rdm2__ holds with use_cumulant)
+    DBuf R;
+    double* target = out;
+    if (!out_on_device) { QTRY(R.alloc(n2 * n2)); target = R; }
+    if (v == 0) {      // a single determinant: the HF 2-RDM, whose cumulant is zero
+      std::vector<double> d2((size_t)(n2 * n2), 0.0);
+      if (with_dm1) for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { d2[(size_t)((p * n + p) * n2 + q * n + q)] += 4.0; d2[(size_t)((p * n + q) * n2 + q * n + p)] -= 2.0; }
+      QTRY(dev_h2d(target, d2.data(), sizeof(double) * n2 * n2));
+    } else {
+      if (!fci_c_.p) { set_error("Fragment::rdm2: the vector of the last FCI solve was not kept"); return QEMB_ERR_ARG; }
+      const FciTables* T = nullptr;
+      QTRY(fci_tables(n, o, &T));
+      std::vector<double> d1((size_t)n2);
+      QTRY(fci_rdm12(*T, fci_c_, with_dm1 ? -1 : o, d1.data(), target));
+    }
+    return out_on_device ? dev_sync() : dev_d2h(out, R, sizeof(double) * n2 * n2);
   }
   const double *t1d = nullptr, *t2d = nullptr;
   Mp2Solver mp;      // (lives until the kernel has run)

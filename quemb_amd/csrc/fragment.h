@@ -8,6 +8,7 @@
 #include "ccsd.h"
 #include "cc_lambda.h"
 #include "scf.h"
+#include "fci.h"
 
 namespace qemb {
 
@@ -92,6 +93,14 @@ class Fragment {
   // ... for every fragment of a sweep, spread over the execution contexts that exist (MP2 has no iterations to run in lock step).  Results as from solve_mp2(), bit for bit.
   static int solve_mp2_batch(const std::vector<Fragment*>& frs, const std::vector<int>& o, const std::vector<const double*>& h, const std::vector<const double*>& dm0,
                              const FragmentOptions& opt, int eeval, std::vector<FragmentResult>& res, const std::vector<BatchOutputs>& outs);
+  // solver == "FCI" of be_func (molbe/solver.py:339-342, :507-547): fragment RHF -> determinant-space FCI of h = fock + heff with the fragment's ERIs in the fragment-MO
+  // basis, nelec = (o, o) (fci.h) -> make_rdm1 -> back-rotation -> get_frag_energy with the cumulant of make_rdm2, contracted on the device against the resident
+  // integrals.  Of opt only scf and strict are read.  civec: ns * ns (host, nullable).  n > 16: QEMB_ERR_UNSUPPORTED; the working set against the free device memory
+  // (or set_fci_mem_limit): QEMB_ERR_ALLOC.  The vector stays on the device for a later rdm2(QEMB_RDM2_FCI).
+  int solve_fci(int o, const double* h, const double* dm0, const FragmentOptions& opt, const FciOptions& fopt, int eeval, FragmentResult* res,
+                double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* civec);
+  void set_fci_mem_limit(int64_t bytes) { fci_mem_limit_ = bytes; }
+  double fci_residual() const { return fci_residual_; }
   // Frags.rdm2__ (molbe/solver.py:528) of the last solve in the fragment-MO basis, out: n^4 (host).  kind QEMB_RDM2_CCSD: make_rdm2_urlx from the kept t1 / t2;
   // QEMB_RDM2_MP2: mp2.make_rdm2, t2 formed again from the resident orbitals (an MP2 solve keeps no amplitudes).  One kernel writes the tensor (rdm2_ops.hip).
   // A relaxed solve: QEMB_ERR_UNSUPPORTED; no solve of that kind, or ERIs / orbitals changed since: QEMB_ERR_ARG.
@@ -130,7 +139,7 @@ class Fragment {
   int check_df_factor();
   int mo_integrals(int o, int nf, DBuf& X1, bool x1_unpacked, MoIntegrals& ints, bool build_Vl, bool build_T34);
   int frag_energies(int o, const std::vector<double>& C, const std::vector<double>& rdm, const std::vector<double>& hfdm, const std::vector<double>& Z1,
-                    const std::vector<double>& Z2, const std::vector<double>* Imat, FragmentResult* res);
+                    const std::vector<double>& Z2, const std::vector<double>* Imat, FragmentResult* res, const std::vector<double>* e2_sites = nullptr);
   DBuf df_factor_; int df_naux_ = 0; int mo_route_ = -1; bool last_route_factor_ = false;
   bool have_C_ = false; int c_nocc_ = -1;    // C_ holds the orbitals of a converged earlier solve with c_nocc_ occupied orbitals (the Jacobi eigensolver starts in that basis)
   int n_, nf_, o_ = -1;
@@ -163,6 +172,12 @@ class Fragment {
   int last_kind_ = -1, last_o_ = 0; bool last_relaxed_ = false;
   std::vector<double> mp2_dm1_;
   int64_t rdm2_mem_limit_ = -1;
+  // after an FCI solve: the CI vector (device, ns * ns) and the symmetrised 1-RDM (host)
+  DBuf fci_c_;
+  std::vector<double> fci_dm1_;
+  double fci_residual_ = 0.0;
+  int64_t fci_mem_limit_ = -1;
+  int fci_mo_integrals(const std::vector<double>& C, DBuf& Vao, DBuf& CC, DBuf& Vmo);
   void forget_solve() { last_kind_ = -1; }
 };
 

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import SolverOpts, c_vp, check
+from ._lib import FciOpts, SolverOpts, c_vp, check
 
 
 def _p(a):
@@ -28,6 +28,24 @@ def default_opts(lib=None, **kw) -> SolverOpts:
             raise TypeError(f"unknown solver option {k!r}")
         setattr(o, k, v)
     return o
+
+
+def default_fci_opts(lib=None, **kw) -> FciOpts:
+    """qemb_fci_opts with the library's defaults (conv_tol 1e-9 on the residual, max_cycle 100, max_space 12, lindep 1e-14), single fields changed by keyword"""
+    lib = lib or _lib.init()
+    o = FciOpts()
+    lib.qemb_default_fci_opts(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"unknown FCI option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def fci_ndet(n, nsocc):
+    """N_det = C(n, nsocc)^2 determinants of the M_s = 0 space"""
+    from math import comb
+    return comb(int(n), int(nsocc)) ** 2
 
 
 class DeviceFragment:
@@ -152,10 +170,41 @@ class DeviceFragment:
         out.update(e_frag=e_frag, e_corr_mo=ecorr.value, e_scf=escf.value, ebe_hf=ebehf.value, n_iter=0, scf_cycles=ncyc.value, lambda_iters=0)
         return out
 
+    def solve_fci(self, nsocc, h, dm0=None, opts: SolverOpts | None = None, fci_opts: FciOpts | None = None, eeval=True, want_civec=False):
+        """solver == "FCI-hip" of be_func (qemb_frag_solve_fci): fragment RHF -> determinant-space FCI on the device -> make_rdm1 -> fragment energies from the cumulant
+        of make_rdm2.  The dict `solve` returns with t1 = t2 = None, plus e_fci (the eigenvalue; e_corr_mo = e_fci - e_scf), residual (||H c - E c||_2), n_iter (the
+        applications of H) and civec ((ns, ns), row = alpha string; None unless want_civec).  Of `opts` only scf_*, verbose and strict_convergence are read;
+        fci_opts None: the defaults of `default_fci_opts`."""
+        n, o = self.n, int(nsocc)
+        h = np.ascontiguousarray(h, dtype=np.float64)
+        dm0 = None if dm0 is None else np.ascontiguousarray(dm0, dtype=np.float64)
+        opts = opts or default_opts(self.lib)
+        from math import comb
+        ns = comb(n, o) if 0 < o <= n else 1
+        out = dict(mo_coeff=np.empty((n, n)), mo_energy=np.empty(n), rdm1_emb=np.empty((n, n)), rdm1_mo=np.empty((n, n)), t1=None, t2=None,
+                   civec=np.empty((ns, ns)) if want_civec and n <= 16 else None)
+        e_frag = np.zeros(3)
+        efci, escf, ebehf, resid = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        nit, ncyc = C.c_int(), C.c_int()
+        check(self.lib.qemb_frag_solve_fci(self.h, o, h.ctypes.data, _p(dm0), C.byref(opts), None if fci_opts is None else C.byref(fci_opts), int(bool(eeval)),
+                                           out["mo_coeff"].ctypes.data, out["mo_energy"].ctypes.data, out["rdm1_emb"].ctypes.data,
+                                           out["rdm1_mo"].ctypes.data, _p(out["civec"]), e_frag.ctypes.data,
+                                           C.byref(efci), C.byref(escf), C.byref(ebehf), C.byref(nit), C.byref(ncyc)),
+              "qemb_frag_solve_fci", self.lib)
+        check(self.lib.qemb_frag_fci_residual(self.h, C.byref(resid)), "qemb_frag_fci_residual", self.lib)
+        out.update(e_frag=e_frag, e_fci=efci.value, e_corr_mo=efci.value - escf.value, e_scf=escf.value, ebe_hf=ebehf.value, n_iter=nit.value,
+                   scf_cycles=ncyc.value, lambda_iters=0, residual=resid.value)
+        return out
+
+    def set_fci_mem_limit(self, nbytes):
+        """device bytes `solve_fci` of this fragment may take (qemb_frag_fci_mem_limit); negative: whatever is free"""
+        check(self.lib.qemb_frag_fci_mem_limit(self.h, int(nbytes)), "qemb_frag_fci_mem_limit", self.lib)
+
     def make_rdm2(self, kind="CCSD", with_dm1=True):
         """Frags.rdm2__ (molbe/solver.py:528) of the last solve of this fragment in the fragment-MO basis, (n, n, n, n): qemb_frag_rdm2.
         kind="CCSD": make_rdm2_urlx(t1, t2, with_dm1) (shared/external/ccsd_rdm.py:23-55) from the amplitudes `solve` left on the device;
         kind="MP2": PySCF's mp2.make_rdm2 (with_dm1=False: its dovov part) after `solve_mp2`.  One kernel writes the n^4 tensor on the device.
+        kind="FCI-hip": make_rdm2 of the vector `solve_fci` left on the device (with_dm1=False: minus the mean-field part of molbe/solver.py:513-527).
         Relaxed (Lambda) 2-RDMs are not implemented: after a solve with relax_density this raises NotImplementedError."""
         if kind not in RDM2_KINDS:
             raise ValueError("Solver not implemented")
@@ -229,7 +278,8 @@ class DeviceFragment:
             pass
 
 
-RDM2_KINDS = {"CCSD": 0, "MP2": 1}      # QEMB_RDM2_CCSD, QEMB_RDM2_MP2 (include/qemb_hip.h)
+RDM2_KINDS = {"CCSD": 0, "MP2": 1, "FCI-hip": 2}      # QEMB_RDM2_CCSD, QEMB_RDM2_MP2, QEMB_RDM2_FCI (include/qemb_hip.h)
+SOLVERS = ("CCSD", "MP2", "FCI-hip")                   # the solver literals of be_func; everything else (the bare "FCI" included) is refused
 
 
 def rdm2_from_amplitudes(t1, t2, dm1=None, kind="CCSD", lib=None):
@@ -237,7 +287,7 @@ def rdm2_from_amplitudes(t1, t2, dm1=None, kind="CCSD", lib=None):
     kind="MP2" --, t2 (o, o, v, v); dm1 (n, n): the 1-RDM whose products with the HF determinant are added (with_dm1=True of the reference; for CCSD
     make_rdm1_ccsd_t1(t1)), None for with_dm1=False.  Returns (n, n, n, n)."""
     from ._lib import DeviceBuffer
-    if kind not in RDM2_KINDS:
+    if kind not in ("CCSD", "MP2"):      # (an FCI 2-RDM comes from a vector, not from amplitudes: fci_rdm12)
         raise ValueError("Solver not implemented")
     lib = lib or _lib.init()
     t2 = np.ascontiguousarray(t2, dtype=np.float64)
@@ -266,6 +316,47 @@ def rdm2_from_amplitudes(t1, t2, dm1=None, kind="CCSD", lib=None):
     finally:
         for b in bufs:
             b.free()
+
+
+def fci_sigma(h, V, c, nsocc, lib=None):
+    """sigma = H c of the determinant-space Hamiltonian (qemb_op_fci_sigma): h (n, n), V (n, n, n, n) = (pq|rs), c (ns, ns); returns (ns, ns)"""
+    from ._lib import DeviceBuffer
+    lib = lib or _lib.init()
+    h = np.ascontiguousarray(h, dtype=np.float64)
+    n = h.shape[0]
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    bufs = [DeviceBuffer.from_numpy(np.asarray(V).reshape(n * n, n * n), lib=lib), DeviceBuffer.from_numpy(c, lib=lib), DeviceBuffer(c.size, lib=lib)]
+    try:
+        check(lib.qemb_op_fci_sigma(n, int(nsocc), h.ctypes.data, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr), "qemb_op_fci_sigma", lib)
+        return bufs[2].numpy(c.shape)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def fci_rdm12(c, n, nsocc, cumulant=False, lib=None):
+    """(dm1, dm2) of the vector c (ns, ns) in PySCF's conventions (qemb_op_fci_rdm12); cumulant: dm2 minus the mean-field part of molbe/solver.py:513-527"""
+    from ._lib import DeviceBuffer
+    lib = lib or _lib.init()
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    dm1 = np.empty((n, n))
+    bufs = [DeviceBuffer.from_numpy(c, lib=lib), DeviceBuffer(n ** 4, lib=lib)]
+    try:
+        check(lib.qemb_op_fci_rdm12(int(n), int(nsocc), bufs[0].ptr, int(bool(cumulant)), dm1.ctypes.data, bufs[1].ptr), "qemb_op_fci_rdm12", lib)
+        return dm1, bufs[1].numpy((n, n, n, n))
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def fci_links(n, nsocc, lib=None):
+    """(strings, links) of one spin as the library built them (qemb_op_fci_links): strings (ns,) bit patterns, links (nlink, ns) words (J << 9) | (pq << 1) | neg"""
+    lib = lib or _lib.init()
+    ns, nl = C.c_int64(), C.c_int()
+    check(lib.qemb_op_fci_links(int(n), int(nsocc), C.byref(ns), C.byref(nl), None, None), "qemb_op_fci_links", lib)
+    strings = np.empty(ns.value, dtype=np.int32); links = np.empty((nl.value, ns.value), dtype=np.int32)
+    check(lib.qemb_op_fci_links(int(n), int(nsocc), C.byref(ns), C.byref(nl), strings.ctypes.data, links.ctypes.data), "qemb_op_fci_links", lib)
+    return strings, links
 
 
 def solve_batch(frags, nsoccs, hs, dm0s=None, opts: SolverOpts | None = None, eeval=True, want_t2=False, stats=None, solver="CCSD"):

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import eri_transform as et
 from .be_parallel import be_func_parallel, fragment_cost, partition_fragments, world, all_reduce_sum
-from .fragsolver import default_opts
+from .fragsolver import SOLVERS, default_opts
 from .pfrag import Frags
 from .solver import ErrorMap, be_func
 
@@ -524,8 +524,8 @@ class BE:
         return be_func(pot, self.Fobjs, self.Nocc, solver, self.enuc, opts=self.opts, stats=self.stats, nstreams=self.nstreams, lockstep=self.lockstep, **kw)
 
     def oneshot(self, solver="CCSD", use_cumulant=True, nproc=1, ompnum=1, solver_args=None):
-        """mbe.py:1240-1310.  solver: "CCSD" or "MP2"."""
-        if solver not in ("CCSD", "MP2"):
+        """mbe.py:1240-1310.  solver: "CCSD", "MP2" or "FCI-hip" (determinant-space FCI per fragment on the device, n <= 16 embedding orbitals)."""
+        if solver not in SOLVERS:
             raise ValueError("Solver not implemented")
         rets = self._sweep(None, solver=solver, eeval=True, use_cumulant=use_cumulant, return_vec=False)
         self.ebe_tot = rets[0] + self.ebe_hf
@@ -542,10 +542,11 @@ class BE:
         """mbe.py:841-977.  `warm_start` (addition): every sweep after the first starts each fragment's CCSD from the
         amplitudes of the previous sweep, which stay resident on the device (the reference restarts from MP2 at every
         objective evaluation, solver.py:894-907); the converged amplitudes, hence all results, are the same.  solver="MP2": MP2 has no
-        iterations, `warm_start` changes nothing, and relax_density is not read (as in the reference's MP2 branch)."""
+        iterations, `warm_start` changes nothing, and relax_density is not read (as in the reference's MP2 branch).  solver="FCI-hip": every sweep starts its Davidson
+        iteration anew; relax_density is not read (as in the reference's FCI branch)."""
         from .opt import BEOPT
         from .jacobian import get_be_error_jacobian
-        if solver not in ("CCSD", "MP2"):
+        if solver not in SOLVERS:
             raise ValueError("Solver not implemented")
         if method != "QN":
             raise ValueError("This optimization method for BE is not supported")

@@ -13,7 +13,7 @@ import numpy as np
 
 from ._lib import SolverOpts
 from .be_parallel import all_reduce_sum
-from .fragsolver import default_opts
+from .fragsolver import SOLVERS, default_opts
 from .solver import ErrorMap
 
 
@@ -46,7 +46,7 @@ class _Delta:
 
 
 def compute_numerical_jacobian(beobj, solver="CCSD", only_chem=False, nproc=1, step_size=1e-6):
-    if solver not in ("CCSD", "MP2"):
+    if solver not in SOLVERS:
         raise ValueError("Solver not implemented")
     pot = np.asarray(beobj.pot if not only_chem else beobj.pot[-1:], dtype=float)
     npot = len(pot)
@@ -73,7 +73,7 @@ def compute_numerical_jacobian(beobj, solver="CCSD", only_chem=False, nproc=1, s
                 rd = []
                 for sgn in (+1.0, -1.0):
                     x = pot.copy(); x[idx] += sgn * step_size
-                    solve = f.dev.solve_mp2 if solver == "MP2" else f.dev.solve
+                    solve = {"MP2": f.dev.solve_mp2, "FCI-hip": f.dev.solve_fci}.get(solver, f.dev.solve)
                     out = solve(f.nsocc, f.fock + calc_heff(f, x, only_chem), f.dm0, opts=opts, eeval=False)
                     rd.append(out["rdm1_emb"])
                 view = [None] * len(beobj.Fobjs)

@@ -16,7 +16,7 @@ from typing import Sequence
 import numpy as np
 
 from . import eri_transform as et
-from .fragsolver import DeviceFragment, default_opts
+from .fragsolver import SOLVERS, DeviceFragment, default_opts
 
 
 class Frags:
@@ -62,7 +62,7 @@ class Frags:
         self.dm0 = None
         self.unitcell_nkpt = 1.0
         self._hf_jk = None
-        self._solver = None      # the solver of the last solve ("CCSD" / "MP2"): what make_rdm2 assembles
+        self._solver = None      # the solver of the last solve ("CCSD" / "MP2" / "FCI-hip"): what make_rdm2 assembles
 
     # ------------------------------------------------------------------ Schmidt (pfrag.py:146-180)
     def sd(self, lao, lmo, nocc, thr_bath, norb=None, method="eigh"):
@@ -165,12 +165,17 @@ class Frags:
         return None
 
     # ------------------------------------------------------------------ the sweep body
-    def solve(self, opts=None, eeval=True, use_cumulant=True, want_t2=False, relax_density=False, solver="CCSD"):
+    def solve(self, opts=None, eeval=True, use_cumulant=True, want_t2=False, relax_density=False, solver="CCSD", fci_opts=None):
         """update_heff -> scf -> solve_ccsd -> rdm1 -> get_frag_energy for this fragment (solver.py:301-547).
         relax_density: solve_ccsd(relax=True) (solver.py:925-939) -- Lambda equations on the device, response densities.
-        solver="MP2": the MP2 branch (solver.py:313-317) -- solve_mp2, unrelaxed MP2 1-RDM; relax_density is not read, as in the reference."""
-        if solver not in ("CCSD", "MP2"):
+        solver="MP2": the MP2 branch (solver.py:313-317) -- solve_mp2, unrelaxed MP2 1-RDM; relax_density is not read, as in the reference.
+        solver="FCI-hip": the FCI branch (solver.py:339-342) on the device; `fci_opts` (qemb_fci_opts, None: defaults), want_t2 asks for the CI vector (out["civec"])."""
+        if solver not in SOLVERS:
             raise ValueError("Solver not implemented")
+        if solver == "FCI-hip":      # the FCI branch (solver.py:339-342): exact in the embedding space; relax_density is not read
+            opts = self._solve_inputs(opts, eeval, False)
+            out = self.dev.solve_fci(self.nsocc, self.fock + self.heff, self.dm0, opts=opts, fci_opts=fci_opts, eeval=eeval, want_civec=want_t2)
+            return self._solve_outputs(out, eeval, use_cumulant, solver)
         if solver == "MP2":
             opts = self._solve_inputs(opts, eeval, False)
             out = self.dev.solve_mp2(self.nsocc, self.fock + self.heff, self.dm0, opts=opts, eeval=eeval, want_t2=want_t2)
@@ -181,7 +186,7 @@ class Frags:
 
     def make_rdm2(self, with_dm1=True):
         """fills `rdm2__` (molbe/solver.py:528) from the last solve of this fragment, in the fragment-MO basis: make_rdm2_urlx(t1, t2, with_dm1) after a
-        CCSD solve, mp2.make_rdm2 after an MP2 solve; assembled on the device (DeviceFragment.make_rdm2).  Unrelaxed only: after a solve with
+        CCSD solve, mp2.make_rdm2 after an MP2 solve, make_rdm2 of the CI vector after an FCI-hip solve (with_dm1=False: minus its mean-field part); assembled on the device (DeviceFragment.make_rdm2).  Unrelaxed only: after a solve with
         relax_density this raises NotImplementedError."""
         if self._solver is None:
             raise RuntimeError("make_rdm2: solve the fragment first")
@@ -218,7 +223,7 @@ class Frags:
         """get_frag_energy(use_cumulant=False) (helper.py:292-339): the 2-RDM then carries the mean-field pieces
         (make_rdm2_urlx(with_dm1=True), ccsd_rdm.py:40-53).  They are bilinear in D0 = C_o C_o^T and the first-order
         change D' = C [[0,t1],[t1^T,0]] C^T (MP2: the oo and vv blocks of make_rdm1 -- the expression is bilinear in D0 and
-        D' = 2 (rdm1_emb - D0) whatever blocks D' has), so their contraction with the fragment ERIs reduces to J/K builds on the
+        D' = 2 (rdm1_emb - D0) whatever blocks D' has; FCI-hip: the mean-field part nc of solver.py:513-527 is the same bilinear form of hf_dm and del_rdm1), so their contraction with the fragment ERIs reduces to J/K builds on the
         device:  e2_P += sum_Q D0_PQ (J[D'] - K[D']/2 + 2 J[D0] - K[D0])_PQ + D'_PQ (J[D0] - K[D0]/2)_PQ."""
         nf, o = self.n_frag, self.nsocc
         C = out["mo_coeff"]

@@ -1,9 +1,9 @@
 """be_func / solve_error / solve_ccsd -- host mirror of molbe/solver.py over the device fragment solver.
 
-`be_func` keeps the reference's signature (molbe/solver.py:244-257) for solver == "CCSD" and solver == "MP2"
-(:313-317); every other solver string of the reference (FCI, SCI, DMRG, ...) is a different code path of QuEmb
-that this package does not replace and raises ValueError("Solver not implemented") exactly like the reference's
-final else (:490-491).
+`be_func` keeps the reference's signature (molbe/solver.py:244-257) for solver == "CCSD", solver == "MP2"
+(:313-317) and solver == "FCI-hip" -- the reference's FCI branch (:339-342, :507-528) as a determinant-space solver on
+the device; every other solver string of the reference (the bare "FCI", SCI, DMRG, ...) raises
+ValueError("Solver not implemented") exactly like the reference's final else (:490-491).
 """
 
 from __future__ import annotations
@@ -11,7 +11,7 @@ from __future__ import annotations
 import numpy as np
 
 from ._lib import SolverOpts
-from .fragsolver import DeviceFragment, default_opts
+from .fragsolver import SOLVERS, DeviceFragment, default_opts
 
 
 class ErrorMap:
@@ -134,15 +134,48 @@ def solve_mp2(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_re
     return (out["e_corr_mo"], out["t2"], rdm2) if rdm2_return else (out["e_corr_mo"], out["t2"])
 
 
+def solve_fci(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, use_cumulant=True, df_factor=None, opts=None, fci_opts=None, lib=None):
+    """Device counterpart of the reference's FCI branch (molbe/solver.py:339-342: fci.FCI(mf, mo_coeff).kernel(), make_rdm1, make_rdm2) with the inputs of
+    `solve_mp2` above.  Returns (e_fci, civec) -- the eigenvalue of h = fock + heff with the fragment ERIs and the (ns, ns) vector -- or
+    (e_fci, civec, rdm1_mo, mo_coeff) with rdm_return; rdm2_return: make_rdm2 (minus its mean-field part with use_cumulant) in the place `solve_ccsd` gives it."""
+    n = h.shape[0]
+    fr = DeviceFragment(n, n_frag, lib=lib)
+    try:
+        if eri_s4 is not None:
+            fr.set_eri_s4(eri_s4)
+            if df_factor is not None:
+                fr.set_df_factor(df_factor)
+        elif df_factor is not None:
+            fr.set_df_only(df_factor)
+        else:
+            raise ValueError("solve_fci needs the fragment ERIs or their 3-index factor")
+        out = fr.solve_fci(nsocc, h, dm0, opts=opts, fci_opts=fci_opts, eeval=False, want_civec=True)
+        rdm2 = fr.make_rdm2("FCI-hip", with_dm1=not use_cumulant) if rdm2_return else None
+    finally:
+        fr.free()
+    if rdm_return and rdm2_return:
+        return out["e_fci"], out["civec"], out["rdm1_mo"], rdm2
+    if rdm_return:
+        return out["e_fci"], out["civec"], out["rdm1_mo"], out["mo_coeff"]
+    return (out["e_fci"], out["civec"], rdm2) if rdm2_return else (out["e_fci"], out["civec"])
+
+
 def fragment_work_bytes(n, o=None, solver="CCSD", naux=None):
     """Device memory ONE fragment in flight takes beside its resident ERIs: the two n^2 x npair buffers of the
     embedding->MO transformation (rows at a stride of whole 128-byte lines), the (+/-) pair-packed ladder operands, the ovvv block with its
     packed images, and ~30 tensors of the size of t2.  Without n_occ the worst split (n_occ = n / 4) is assumed.
+    solver="FCI-hip" (csrc/fci.cpp; qemb_frag_fci_bytes with the default max_space = 12): D and G (2 x 8 n^2 N_det), 28 vectors of N_det, the tables and the n^4
+    pieces; without n_occ the worst split (n_occ = n / 2) is assumed.
     solver="MP2" (factor route, csrc/mp2.cpp): the unpacked factor and its half-rotated virtual columns while Lov is formed (naux n^2 + naux n v), then
     Lov, Y and its transpose (naux o v each) and three o^2 v^2 tensors (ovov, t2, G); naux = 3 n when not given."""
-    if solver not in ("CCSD", "MP2"):
+    if solver not in SOLVERS:
         raise ValueError("Solver not implemented")
     n = int(n)
+    if solver == "FCI-hip":
+        from math import comb
+        o = max(1, n // 2) if o is None else int(o)
+        ns = comb(n, o)
+        return 8.0 * (2.0 * n * n * ns * ns + 28.0 * ns * ns + 8.0 * n ** 4) + 4.0 * ns * (o * (n - o + 1) + 1)
     o = max(1, n // 4) if o is None else int(o)
     v = max(n - o, 1)
     if solver == "MP2":
@@ -280,13 +313,15 @@ def solve_fragments(pot, frags, only_chem=False, opts=None, eeval=False, use_cum
     nstreams > 1: that many fragments in flight on separate streams (map_fragments).  lockstep: ALL fragments in one library call
     (qemb_frag_solve_batch) -- their CCSD iterations advance together, every operation one grouped launch; the small-fragment regime
     (octane BE2 / BE3), where a fragment alone is bound by its ~110 dependent launches per iteration.  Same results, bit for bit.
-    solver="MP2": the MP2 branch of the loop body (solver.py:313-317); `lockstep` then takes qemb_frag_solve_mp2_batch and relax_density is not read."""
-    if solver not in ("CCSD", "MP2"):
+    solver="MP2": the MP2 branch of the loop body (solver.py:313-317); `lockstep` then takes qemb_frag_solve_mp2_batch and relax_density is not read.
+    solver="FCI-hip": the FCI branch (solver.py:339-342); there is no batched entry -- with `lockstep` the fragments run one by one, or on `nstreams` streams;
+    relax_density is not read."""
+    if solver not in SOLVERS:
         raise ValueError("Solver not implemented")
-    if solver == "MP2":
+    if solver != "CCSD":
         relax_density = False
     frags = list(frags)
-    if lockstep and len(frags) > 1:
+    if lockstep and len(frags) > 1 and solver != "FCI-hip":
         from .fragsolver import solve_batch
         o_list = []
         for f in frags:
@@ -309,10 +344,10 @@ def solve_fragments(pot, frags, only_chem=False, opts=None, eeval=False, use_cum
 
 def be_func(pot, Fobjs, Nocc, solver, enuc, solver_args=None, scratch_dir=None, only_chem=False, eeval=False,
             relax_density=False, return_vec=False, use_cumulant=True, *, opts=None, stats=None, nstreams=1, lockstep=False):
-    """molbe/solver.py:244-562 for solver == 'CCSD' and solver == 'MP2' (relax_density is ignored for MP2: the reference's MP2 branch never reads it).  `opts` (qemb_solver_opts), `stats` (dict collecting per-sweep
+    """molbe/solver.py:244-562 for solver == 'CCSD', 'MP2' and 'FCI-hip' (relax_density is ignored for MP2 and FCI-hip: those branches of the reference never read it).  `opts` (qemb_solver_opts), `stats` (dict collecting per-sweep
     counters), `nstreams` (fragments in flight at once, see map_fragments) and `lockstep` (all fragments in one batched call, see
     solve_fragments) are additions; everything else has the reference's meaning."""
-    if solver not in ("CCSD", "MP2"):
+    if solver not in SOLVERS:
         raise ValueError("Solver not implemented")
     total_e = [0.0, 0.0, 0.0]
     n_iter = 0

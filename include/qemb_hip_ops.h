@@ -160,6 +160,18 @@ int qemb_op_extract_pf(int64_t n, const double* Mp, int64_t p0, int64_t q0, int6
 int qemb_op_extract_pf_t(int64_t n, const double* T, int64_t x0, int64_t r0, int64_t s0, int64_t c0, int64_t sx, int64_t sr,
                          int64_t ss, int64_t sc, double* out);
 int qemb_op_ladder_pack_vvvv_pf(int64_t n, int64_t o, const double* Mp, double* Vp, int64_t ldp, double* Vm, int64_t ldm);
+/* ... and the same gathers from the pair product S[P(p,q)][P(r,s)] (npair x npair, both triangles) without its pair-first image; T restricted to the
+ * requested pairs (slab (r,s) at row r * ss + s); the pair columns of a packed factor as a dense operand; the pair product itself (out = bb^T bb). */
+int qemb_op_extract_pf_t_compact(int64_t n, const double* T, int64_t x0, int64_t c0, int64_t sx, int64_t sr, int64_t ss, int64_t sc,
+                                 double* out, int64_t slab);
+int qemb_op_gather_pair_cols(int64_t rows, int64_t n, const double* in, int64_t r0, int64_t s0, int64_t sr, int64_t ss, double* out);
+int qemb_op_extract_ps(int64_t n, const double* S, int64_t p0, int64_t q0, int64_t r0, int64_t s0, int64_t sp, int64_t sq,
+                       int64_t sr, int64_t ss, double* out);
+int qemb_op_extract_ps_packed(int64_t n, const double* S, int64_t p0, int64_t q0, int64_t r0, int64_t sp, int64_t sq, int64_t sr, double* out);
+int qemb_op_unpack_pair_block(int64_t n, int64_t o, const double* S, double* Mv, int64_t ld);
+int qemb_op_ladder_pack_vvvv_pf_ld(int64_t n, int64_t o, const double* Mp, int64_t ld, double* Vp, int64_t ldp, double* Vm, int64_t ldm);
+int qemb_op_pack_pm_ovvv(int64_t o, int64_t v, const double* ovvv, double* Op, int64_t ldp, double* Om, int64_t ldm);
+int qemb_op_df_pair_product(int64_t np, int64_t naux, const double* bb, double* out);
 int qemb_op_unpack_tril_rows(int64_t rows, int64_t n, const double* packed, double* full);
 int qemb_op_pack_tril_rows(int64_t rows, int64_t n, const double* full, double* packed);
 int qemb_op_jacobi_eigh(int64_t n, double* A, double* w, double* V, int* sweeps);

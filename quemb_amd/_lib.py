@@ -142,6 +142,14 @@ def _declare(lib):
     f("qemb_op_extract_pf", I, L, P, L, L, L, L, L, L, L, L, P)
     f("qemb_op_extract_pf_t", I, L, P, L, L, L, L, L, L, L, L, P)
     f("qemb_op_ladder_pack_vvvv_pf", I, L, L, P, P, L, P, L)
+    f("qemb_op_extract_pf_t_compact", I, L, P, L, L, L, L, L, L, P, L)
+    f("qemb_op_gather_pair_cols", I, L, L, P, L, L, L, L, P)
+    f("qemb_op_extract_ps", I, L, P, L, L, L, L, L, L, L, L, P)
+    f("qemb_op_extract_ps_packed", I, L, P, L, L, L, L, L, L, P)
+    f("qemb_op_unpack_pair_block", I, L, L, P, P, L)
+    f("qemb_op_ladder_pack_vvvv_pf_ld", I, L, L, P, L, P, L, P, L)
+    f("qemb_op_pack_pm_ovvv", I, L, L, P, P, L, P, L)
+    f("qemb_op_df_pair_product", I, L, L, P, P)
     f("qemb_op_pack_tril_rows", I, L, L, P, P)
     f("qemb_op_jacobi_eigh", I, L, P, P, P, C.POINTER(I))
     f("qemb_op_scf_fused_max", I)

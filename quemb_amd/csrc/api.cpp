@@ -241,6 +241,24 @@ int qemb_op_extract_pf_t(int64_t n, const double* T, int64_t x0, int64_t r0, int
   return dev_extract_pf_t(n, T, x0, r0, s0, c0, sx, sr, ss, sc, out);
 }
 int qemb_op_ladder_pack_vvvv_pf(int64_t n, int64_t o, const double* Mp, double* Vp, int64_t ldp, double* Vm, int64_t ldm) { return dev_ladder_pack_vvvv_pf(n, o, Mp, Vp, ldp, Vm, ldm); }
+int qemb_op_extract_pf_t_compact(int64_t n, const double* T, int64_t x0, int64_t c0, int64_t sx, int64_t sr, int64_t ss, int64_t sc, double* out, int64_t slab) {
+  return dev_extract_pf_t_compact(n, T, x0, c0, sx, sr, ss, sc, out, slab);
+}
+int qemb_op_gather_pair_cols(int64_t rows, int64_t n, const double* in, int64_t r0, int64_t s0, int64_t sr, int64_t ss, double* out) {
+  return dev_gather_pair_cols(rows, n, in, r0, s0, sr, ss, out);
+}
+int qemb_op_extract_ps(int64_t n, const double* S, int64_t p0, int64_t q0, int64_t r0, int64_t s0, int64_t sp, int64_t sq, int64_t sr, int64_t ss, double* out) {
+  return dev_extract_ps(n, S, p0, q0, r0, s0, sp, sq, sr, ss, out);
+}
+int qemb_op_extract_ps_packed(int64_t n, const double* S, int64_t p0, int64_t q0, int64_t r0, int64_t sp, int64_t sq, int64_t sr, double* out) {
+  return dev_extract_ps_packed(n, S, p0, q0, r0, sp, sq, sr, out);
+}
+int qemb_op_unpack_pair_block(int64_t n, int64_t o, const double* S, double* Mv, int64_t ld) { return dev_unpack_pair_block(n, o, S, Mv, ld); }
+int qemb_op_ladder_pack_vvvv_pf_ld(int64_t n, int64_t o, const double* Mp, int64_t ld, double* Vp, int64_t ldp, double* Vm, int64_t ldm) {
+  return dev_ladder_pack_vvvv_pf_ld(n, o, Mp, ld, Vp, ldp, Vm, ldm);
+}
+int qemb_op_pack_pm_ovvv(int64_t o, int64_t v, const double* ovvv, double* Op, int64_t ldp, double* Om, int64_t ldm) { return dev_pack_pm_ovvv(o, v, ovvv, Op, ldp, Om, ldm); }
+int qemb_op_df_pair_product(int64_t np, int64_t naux, const double* bb, double* out) { return df_pair_product(np, naux, bb, out); }
 int qemb_op_unpack_tril_pair_rows(int64_t nr, int64_t n, const double* in, double* full) { return dev_unpack_tril_pair_rows(nr, n, in, full); }
 int qemb_op_unpack_tril_rows(int64_t rows, int64_t n, const double* p, double* f) { return dev_unpack_tril_rows(rows, n, p, f); }
 int qemb_op_pack_tril_rows(int64_t rows, int64_t n, const double* f, double* p) { return dev_pack_tril_rows(rows, n, f, p); }

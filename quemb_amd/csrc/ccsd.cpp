@@ -58,6 +58,48 @@ static int mo_three_quarter_blocks(int n, int o, int nf, const double* T, int64_
   return 0;
 }
 
+// the same two blocks when T holds only the rows of the (j,b) pairs, T[j * v + b][P][q'] (the factor route forms no other row of it)
+static int mo_three_quarter_blocks_ov(int n, int o, int nf, const double* T, int64_t slab, MoIntegrals& out) {
+  const int v = n - o;
+  QTRY(out.A1.alloc((int64_t)v * o * v * nf));
+  QTRY(out.A2.alloc((int64_t)o * o * v * nf));
+  QTRY(dev_extract_pf_t_compact(n, T, o, 0, v, o, v, nf, out.A1, slab));
+  QTRY(dev_extract_pf_t_compact(n, T, 0, 0, o, o, v, nf, out.A2, slab));
+  return 0;
+}
+
+// every block of the amplitude equations straight from the pair product S[P(r',s')][P(p',q')] = (r's'|p'q') (npair x npair, both triangles): the pair-first
+// image of S (twice its size, a write of 9.4 GB at n = 220) is formed for the vv|vv part alone (`work`: npair(v) * v * mo_slab_ld(v) doubles).  ovvv comes as rows of S with the pair (a,c) still packed -- the layout setup()
+// wants for the ZC pass anyway -- and is unpacked from there.
+static int mo_blocks_from_pair_product(int n, int o, const double* S, double* work, MoIntegrals& out) {
+  const int v = n - o;
+  const int64_t npv = (int64_t)v * (v + 1) / 2, nm = (int64_t)v * (v - 1) / 2;
+  QTRY(out.oooo.alloc((int64_t)o * o * o * o));
+  QTRY(out.ovoo.alloc((int64_t)o * v * o * o));
+  QTRY(out.ovov.alloc((int64_t)o * v * o * v));
+  QTRY(out.oovv.alloc((int64_t)o * o * v * v));
+  QTRY(out.ovvo.alloc((int64_t)o * v * v * o));
+  QTRY(out.ovvv.alloc((int64_t)o * v * v * v));
+  QTRY(out.ovvv_pk.alloc((int64_t)o * v * npv));
+  QTRY(dev_extract_ps(n, S, 0, 0, 0, 0, o, o, o, o, out.oooo));
+  QTRY(dev_extract_ps(n, S, 0, o, 0, 0, o, v, o, o, out.ovoo));
+  QTRY(dev_extract_ps(n, S, 0, o, 0, o, o, v, o, v, out.ovov));
+  QTRY(dev_extract_ps(n, S, 0, 0, o, o, o, o, v, v, out.oovv));
+  QTRY(dev_extract_ps(n, S, 0, o, o, 0, o, v, v, o, out.ovvo));
+  QTRY(dev_extract_ps_packed(n, S, 0, o, o, o, v, v, out.ovvv_pk));
+  QTRY(dev_unpack_tril_rows((int64_t)o * v, v, out.ovvv_pk, out.ovvv));
+  out.ldp = npv + (npv & 1); out.ldm = nm + (nm & 1);
+  if (out.ldm == 0) out.ldm = 2;
+  QTRY(out.Vp.alloc(npv * out.ldp));
+  QTRY(out.Vm.alloc(std::max<int64_t>(nm, 1) * out.ldm));
+  // the (+/-) ladder operands pair two entries of S whose column pairs run along different indices: gathered from S itself every other read walks down a
+  // column of the packed triangle (6.6 ms at n = 220 against 3.0).  They keep the pair-first image -- of the vv|vv part alone, in `work`
+  const int64_t ldv = mo_slab_ld(v);
+  QTRY(dev_unpack_pair_block(n, o, S, work, ldv));
+  QTRY(dev_ladder_pack_vvvv_pf_ld(v, 0, work, ldv, out.Vp, out.ldp, out.Vm, out.ldm));
+  return 0;
+}
+
 // every block of the amplitude equations from the pair-first MO tensor Mp[P(r',s')][p'][q'] = (r's'|p'q') (slabs of n x n); `scratch` holds v^4 doubles or is null
 static int mo_blocks_from_pair_first(int n, int o, const double* Mp, double* scratch, int64_t scratch_elems, MoIntegrals& out, bool build_Vl) {
   const int v = n - o;
@@ -160,6 +202,20 @@ int mo_transform_factor(int n, int o, int nf, int naux, const double* Bf, double
   QTRY(dev_pack_tril_rows(naux, n, Lu, Lpk));
   Lu.release();
   QTRY(df_pair_product(np, naux, Lpk, X1));                                                         // S in X1 (npair x npair)
+  if (!build_Vl && !build_T34) {
+    // CCSD alone reads S entry by entry and T only in its rows P(j,b), j occupied and b virtual (o v of the npair: 4000 of 24310 at n = 220)
+    if (nf > 0) {
+      DBuf Lov;
+      QTRY(Lov.alloc((int64_t)naux * o * v));
+      QTRY(dev_gather_pair_cols(naux, n, Lpk, 0, o, o, v, Lov));                                    // Lov[L][(j,b)] = Lpk[L][P(j,o+b)]
+      QTRY(gemm((int64_t)o * v, (int64_t)nf * n, naux, 1.0, Lov, (int64_t)o * v, false, Lh, n2, false, 0.0, X0, (int64_t)nf * n));
+      QTRY(mo_three_quarter_blocks_ov(n, o, nf, X0, (int64_t)nf * n, out));
+    }
+    Lh.release(); Lpk.release();
+    QTRY(mo_blocks_from_pair_product(n, o, X1, X0, out));                                            // (X0: T has been gathered from; free again)
+    QTRY(lap_AO2MO.close());
+    return 0;
+  }
   QTRY(dev_unpack_tril_rows(np, n, X1, X0));                                                        // Mp in X0
   if (nf > 0) {
     // T[P(r's')][(P,q')] for the first nf rows P of every slab of Lh: A(m,k) = Lpk[k][m], B(k,col) = Lh[k][col], col < nf n
@@ -205,18 +261,22 @@ int CcsdSolver::setup(MoIntegrals&& ints, const double* mo_energy_dev) {
   QTRY(axpby(N2, 2.0, W1base_, -1.0, Lph1_));                            // Lph1 = 2 W1base - W2base
   {  // OVl[k,a,c,d] = ovvv[k,d,a,c], kept only as its (+/-) pair-packed images over (c,d): the tau-side dressing of
      // Wvvvv then contracts the SAME packed tau rows as the ladder, at half the flops of the dense o^2 x ov x v^2 product
-    DBuf OVl;
-    QTRY(OVl.alloc(o * v * vv));
-    QTRY(perm4(OVl, I_.ovvv, o, v, v, v, 0, 2, 3, 1));
     QTRY(OVp_.alloc(nov * I_.ldp)); QTRY(OVm_.alloc(nov * I_.ldm));
-    QTRY(dev_pack_pm_cols(nov, v, OVl, OVp_, I_.ldp, OVm_, I_.ldm));
+    if (v >= 32) QTRY(dev_pack_pm_ovvv(o, v, I_.ovvv, OVp_, I_.ldp, OVm_, I_.ldm));     // the tiled pass reads ovvv in place: no permuted copy
+    else {
+      DBuf OVl;
+      QTRY(OVl.alloc(o * v * vv));
+      QTRY(perm4(OVl, I_.ovvv, o, v, v, v, 0, 2, 3, 1));
+      QTRY(dev_pack_pm_cols(nov, v, OVl, OVp_, I_.ldp, OVm_, I_.ldm));
+    }
   }
   // (kd|ac) is symmetric in (a,c): the pass ZC[k,i,a,c] = t1[id] ovvv[kdac] reads the block packed over that pair -- half the bytes of an
   // HBM-bound pass -- and its result is unpacked afterwards (a tenth of the bytes)
   {
     const int64_t npv = v * (v + 1) / 2;
-    QTRY(ovvv_pk_.alloc(o * v * npv)); QTRY(ZCp_.alloc(oo * npv));
-    QTRY(dev_pack_tril_rows(o * v, v, I_.ovvv, ovvv_pk_));
+    QTRY(ZCp_.alloc(oo * npv));
+    if (I_.ovvv_pk.p) ovvv_pk_ = std::move(I_.ovvv_pk);                // (the factor route hands the packed block over: it is rows of the pair product)
+    else { QTRY(ovvv_pk_.alloc(o * v * npv)); QTRY(dev_pack_tril_rows(o * v, v, I_.ovvv, ovvv_pk_)); }
   }
   // G+-[(k,l)][P/Q(c,d)] = ovov[kcld] +- ovov[kdlc]: Woooo += ovov[kcld] tau[ijcd] then runs over the packed (c,d) pairs against the
   // packed tau rows the ladder builds anyway -- half the flops of the dense (oo) x (oo) x (vv) product

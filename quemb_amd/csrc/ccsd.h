@@ -20,6 +20,7 @@ struct CcsdOptions {
 struct MoIntegrals {
   int n = 0, o = 0, v = 0, nf = 0;
   DBuf oooo, ovoo, ovov, oovv, ovvo, ovvv;
+  DBuf ovvv_pk;     // ovvv[k,d,P(a,c)] packed over its symmetric pair, where the transformation has it anyway (the factor route); else empty
   DBuf Vl;          // Vl[a,b,c,d] = (ac|bd)   (dense ladder operand; only built on request: export / measurement)
   // (+/-) packed ladder operands: Vp[P(a,b),P(c,d)] = (ac|bd)+(ad|bc), Vm[Q(a,b),Q(c,d)] = (ac|bd)-(ad|bc)
   DBuf Vp, Vm;

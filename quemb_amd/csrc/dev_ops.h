@@ -215,6 +215,20 @@ int dev_extract_pf_t(int64_t n, const double* T, int64_t x0, int64_t r0, int64_t
                      int64_t ss, int64_t sc, double* out, int64_t slab = 0);
 // (+/-) ladder operands: Vp[P(ab),P(cd)] = Mp[P(va,vc)][vb][vd] + Mp[P(vb,vc)][va][vd]  (v* = o + *), Vm with the minus sign
 int dev_ladder_pack_vvvv_pf(int64_t n, int64_t o, const double* Mp, double* Vp, int64_t ldp, double* Vm, int64_t ldm);
+// the same slabs when T holds ONLY the sr x ss requested pairs, slab (r,s) at row r * ss + s:  out[sx][sr][ss][sc] = T[r * ss + s][c0+c][x0+x]
+int dev_extract_pf_t_compact(int64_t n, const double* T, int64_t x0, int64_t c0, int64_t sx, int64_t sr, int64_t ss, int64_t sc, double* out, int64_t slab = 0);
+// ---- the same gathers from the pair product S[P(p,q)][P(r,s)] = (pq|rs) (npair(n) x npair(n), both triangles filled): no pair-first image of S
+// out[L][r * ss + s] = in[L][P(r0+r, s0+s)]  (in: rows x npair(n)): the columns of the chosen pairs of a packed factor as one dense operand
+int dev_gather_pair_cols(int64_t rows, int64_t n, const double* in, int64_t r0, int64_t s0, int64_t sr, int64_t ss, double* out);
+// out (contiguous sp x sq x sr x ss) = S[P(p0+p, q0+q)][P(r0+r, s0+s)]
+int dev_extract_ps(int64_t n, const double* S, int64_t p0, int64_t q0, int64_t r0, int64_t s0, int64_t sp, int64_t sq, int64_t sr, int64_t ss, double* out);
+// out[sp][sq][P(r,s)] = S[P(p0+p, q0+q)][P(r0+r, r0+s)], r >= s, r < sr: the block with its (equal-range) column pair left packed -- runs of S rows
+int dev_extract_ps_packed(int64_t n, const double* S, int64_t p0, int64_t q0, int64_t r0, int64_t sp, int64_t sq, int64_t sr, double* out);
+// Mv[P(a,c)][b][d] = S[P(o+a,o+c)][P(o+b,o+d)], slabs of v = n - o rows, ld >= v apart: the pair-first image of the vv|vv part of S alone (the ladder
+// operands are gathered from it in contiguous runs: dev_ladder_pack_vvvv_pf_ld(v, 0, Mv, ld, ...))
+int dev_unpack_pair_block(int64_t n, int64_t o, const double* S, double* Mv, int64_t ld);
+// dev_ladder_pack_vvvv_pf on slabs whose n rows are ld >= n doubles apart
+int dev_ladder_pack_vvvv_pf_ld(int64_t n, int64_t o, const double* Mp, int64_t ld, double* Vp, int64_t ldp, double* Vm, int64_t ldm);
 
 // ---- (+/-) packed pp-ladder: R_ijab = sum_cd (ac|bd) tau_ijcd through symmetric / antisymmetric pair combinations ------
 // pairs: P(x,y) = x(x+1)/2 + y for x >= y ("plus" blocks), Q(x,y) = x(x-1)/2 + y for x > y ("minus" blocks).
@@ -228,6 +242,9 @@ int dev_ladder_pack_tau(int64_t o, int64_t v, const double* tau, double* Tp, int
 // Generic (+/-) pair packing of the last two (equal, size v) indices of in[rows][v][v]:
 //   Op[r, P(c,d)] = in[r,c,d] + in[r,d,c] (c >= d),  Om[r, Q(c,d)] = in[r,c,d] - in[r,d,c] (c > d); rows padded with zeros to ldp / ldm
 int dev_pack_pm_cols(int64_t rows, int64_t v, const double* in, double* Op, int64_t ldp, double* Om, int64_t ldm);
+// the same images of the permuted block in[k,a,c,d] <- ovvv[k,d,a,c] without forming it (v >= 32):
+//   Op[(k,a), P(c,d)] = ovvv[k,d,a,c] + ovvv[k,c,a,d],  Om[(k,a), Q(c,d)] = ovvv[k,d,a,c] - ovvv[k,c,a,d]
+int dev_pack_pm_ovvv(int64_t o, int64_t v, const double* ovvv, double* Op, int64_t ldp, double* Om, int64_t ldm);
 // out[i,j,:] = Xp[P(i,j),:] + Xm[Q(i,j),:],  out[j,i,:] = Xp[P(i,j),:] - Xm[Q(i,j),:]  (i > j),  out[i,i,:] = Xp[P(i,i),:]
 // add (laid out like out): out = scatter + add.  Sp / Sm > 1: Xp / Xm are split-K slabs (stride strideP / strideM apart) that are added up on the way, in slab order
 int dev_scatter_pm_rows(int64_t o, int64_t ncols, const double* Xp, const double* Xm, double* out, const double* add = nullptr, int Sp = 1, int64_t strideP = 0,

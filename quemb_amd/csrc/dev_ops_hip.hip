@@ -1549,10 +1549,12 @@ int dev_extract_pf(int64_t n, const double* Mp, int64_t p0, int64_t q0, int64_t 
 }
 // out[x][r][s][c] = T[P(r0+r,s0+s)][c0+c][x0+x]: one workgroup per (r,s) slab reads the sc x sx corner (rows of sx contiguous doubles)
 __global__ void __launch_bounds__(256) extract_pf_t_kernel(long long n, const double* __restrict__ T, long long x0, long long r0, long long s0, long long c0,
-                                                          long long sx, long long sr, long long ss, long long sc, double* __restrict__ out, long long slab) {
+                                                          long long sx, long long sr, long long ss, long long sc, double* __restrict__ out, long long slab,
+                                                          int compact) {
   for (long long rs = blockIdx.x; rs < sr * ss; rs += gridDim.x) {
     const long long r = rs / ss, s = rs - r * ss;
-    const double* src = T + pair_idx(r0 + r, s0 + s) * slab + c0 * n + x0;
+    // compact: T holds only the sr x ss requested pairs, slab (r, s) at row r * ss + s (the factor route forms no other row)
+    const double* src = T + (compact ? rs : pair_idx(r0 + r, s0 + s)) * slab + c0 * n + x0;
     for (long long t = threadIdx.x; t < sc * sx; t += blockDim.x) {
       const long long c = t / sx, x = t - c * sx;
       out[(x * sr * ss + rs) * sc + c] = src[c * n + x];
@@ -1565,13 +1567,130 @@ int dev_extract_pf_t(int64_t n, const double* T, int64_t x0, int64_t r0, int64_t
   if (slab <= 0) slab = n * n;          // (a pair's slab holds all n rows; the factor route of mo_transform keeps only the first nf)
   if (c0 + sc > slab / n) { set_error("dev_extract_pf_t: rows beyond the slab"); return QEMB_ERR_ARG; }
   return launch("dev_extract_pf_t", extract_pf_t_kernel, dim3((unsigned)std::min<int64_t>(sr * ss, 1 << 20)), dim3(256), 0, g_stream, n, T, x0, r0,
-                s0, c0, sx, sr, ss, sc, out, slab);
+                s0, c0, sx, sr, ss, sc, out, slab, 0);
+}
+int dev_extract_pf_t_compact(int64_t n, const double* T, int64_t x0, int64_t c0, int64_t sx, int64_t sr, int64_t ss, int64_t sc, double* out, int64_t slab) {
+  REQUIRE_INIT();
+  if (sx <= 0 || sr <= 0 || ss <= 0 || sc <= 0) return QEMB_OK;
+  if (slab <= 0) slab = n * n;
+  if (c0 + sc > slab / n || x0 + sx > n) { set_error("dev_extract_pf_t_compact: rows beyond the slab"); return QEMB_ERR_ARG; }
+  return launch("dev_extract_pf_t_compact", extract_pf_t_kernel, dim3((unsigned)std::min<int64_t>(sr * ss, 1 << 20)), dim3(256), 0, g_stream, n, T, x0,
+                (long long)0, (long long)0, c0, sx, sr, ss, sc, out, slab, 1);
+}
+// ---- the same gathers from the pair product S[P(p,q)][P(r,s)] = (pq|rs) itself (npair(n) x npair(n), BOTH triangles filled) ---------------
+// out[L][r * ss + s] = in[L][P(r0+r, s0+s)]: the columns of the chosen pairs of a packed factor, as one dense operand
+__global__ void __launch_bounds__(256) gather_pair_cols_kernel(long long rows, long long np, const double* __restrict__ in, long long r0, long long s0,
+                                                              long long sr, long long ss, double* __restrict__ out) {
+  const long long nc = sr * ss;
+  for (long long L = blockIdx.y; L < rows; L += gridDim.y)
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < nc; t += (long long)gridDim.x * blockDim.x) {
+      const long long r = t / ss, s = t - r * ss;
+      out[L * nc + t] = in[L * np + pair_idx(r0 + r, s0 + s)];
+    }
+}
+int dev_gather_pair_cols(int64_t rows, int64_t n, const double* in, int64_t r0, int64_t s0, int64_t sr, int64_t ss, double* out) {
+  REQUIRE_INIT();
+  if (rows <= 0 || sr <= 0 || ss <= 0) return QEMB_OK;
+  if (r0 < 0 || s0 < 0 || r0 + sr > n || s0 + ss > n) { set_error("dev_gather_pair_cols: pairs beyond n"); return QEMB_ERR_ARG; }
+  return launch("dev_gather_pair_cols", gather_pair_cols_kernel, dim3((unsigned)std::min<int64_t>((sr * ss + 255) / 256, 1024), (unsigned)std::min<int64_t>(rows, 65535)),
+                dim3(256), 0, g_stream, rows, n * (n + 1) / 2, in, r0, s0, sr, ss, out);
+}
+// out (contiguous sp x sq x sr x ss) = S[P(p0+p, q0+q)][P(r0+r, s0+s)]
+__global__ void __launch_bounds__(256) extract_ps_kernel(long long np, const double* __restrict__ S, long long p0, long long q0, long long r0, long long s0,
+                                                        long long sp, long long sq, long long sr, long long ss, double* __restrict__ out) {
+  const long long nrs = sr * ss;
+  for (long long pq = blockIdx.x; pq < sp * sq; pq += gridDim.x) {
+    const long long p = pq / sq, q = pq - p * sq;
+    const double* src = S + pair_idx(p0 + p, q0 + q) * np;
+    double* dst = out + pq * nrs;
+    for (long long t = threadIdx.x; t < nrs; t += blockDim.x) {
+      const long long r = t / ss, s = t - r * ss;
+      dst[t] = src[pair_idx(r0 + r, s0 + s)];
+    }
+  }
+}
+int dev_extract_ps(int64_t n, const double* S, int64_t p0, int64_t q0, int64_t r0, int64_t s0, int64_t sp, int64_t sq, int64_t sr, int64_t ss, double* out) {
+  REQUIRE_INIT();
+  if (sp <= 0 || sq <= 0 || sr <= 0 || ss <= 0) return QEMB_OK;
+  if (p0 < 0 || q0 < 0 || r0 < 0 || s0 < 0 || p0 + sp > n || q0 + sq > n || r0 + sr > n || s0 + ss > n) { set_error("dev_extract_ps: block beyond n"); return QEMB_ERR_ARG; }
+  return launch("dev_extract_ps", extract_ps_kernel, dim3((unsigned)std::min<int64_t>(sp * sq, 1 << 20)), dim3(256), 0, g_stream, n * (n + 1) / 2, S, p0, q0,
+                r0, s0, sp, sq, sr, ss, out);
+}
+// out[(p,q)][P(r,s)] = S[P(p0+p, q0+q)][P(r0+r, r0+s)], r >= s < sr: a block whose column pair stays packed is, row by row r, one contiguous run of
+// r + 1 doubles of S.  One wave per run (no pair index to invert), four runs of a source row in flight per workgroup.
+__global__ void __launch_bounds__(256) extract_ps_packed_kernel(long long np, const double* __restrict__ S, long long p0, long long q0, long long r0,
+                                                               long long sp, long long sq, long long sr, double* __restrict__ out) {
+  const long long npr = sr * (sr + 1) / 2;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (long long pq = blockIdx.x; pq < sp * sq; pq += gridDim.x) {
+    const long long p = pq / sq, q = pq - p * sq;
+    const double* src = S + pair_idx(p0 + p, q0 + q) * np;
+    double* dst = out + pq * npr;
+    for (long long r = wave; r < sr; r += 4) {
+      const double* run = src + (r0 + r) * (r0 + r + 1) / 2 + r0;
+      double* o = dst + r * (r + 1) / 2;
+      for (long long s = lane; s <= r; s += 64) o[s] = run[s];
+    }
+  }
+}
+int dev_extract_ps_packed(int64_t n, const double* S, int64_t p0, int64_t q0, int64_t r0, int64_t sp, int64_t sq, int64_t sr, double* out) {
+  REQUIRE_INIT();
+  if (sp <= 0 || sq <= 0 || sr <= 0) return QEMB_OK;
+  if (p0 < 0 || q0 < 0 || r0 < 0 || p0 + sp > n || q0 + sq > n || r0 + sr > n) { set_error("dev_extract_ps_packed: block beyond n"); return QEMB_ERR_ARG; }
+  return launch("dev_extract_ps_packed", extract_ps_packed_kernel, dim3((unsigned)std::min<int64_t>(sp * sq, 1 << 20)), dim3(256), 0, g_stream, n * (n + 1) / 2, S,
+                p0, q0, r0, sp, sq, sr, out);
+}
+// Mv[P(a,c)][b][d] = S[P(va,vc)][P(vb,vd)] (v* = o + *; slabs of v rows, ld apart): the pair-first image of the vv|vv part of S alone -- all the (+/-) ladder
+// operands are gathered from (every other block reads S entry by entry).  The tiles of unpack_tril_tiled_kernel, on the runs of the virtual pairs in a row of S.
+__global__ void __launch_bounds__(256) unpack_pair_block_kernel(long long n, long long o, const double* __restrict__ S, double* __restrict__ Mv, long long ld) {
+  __shared__ double tile[32][33];
+  const long long v = n - o, npn = n * (n + 1) / 2, npv = v * (v + 1) / 2, slab = v * ld;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const uint3 LB = xcd_logical_block(block_id(), grid_dim());
+  long long tk, tl; unpair_ge((long long)LB.x, tk, tl);
+  for (long long r = LB.y; r < npv; r += gridDim.y) {
+    long long a, c; unpair_ge(r, a, c);
+    const double* src = S + pair_idx(o + a, o + c) * npn;
+    double* dst = Mv + r * slab;
+    double xr[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int kk = ty + 8 * i;
+      const long long k = tk * 32 + kk, l = tl * 32 + tx;
+      xr[i] = (k < v && l <= k) ? src[(o + k) * (o + k + 1) / 2 + o + l] : 0.0;
+      tile[kk][tx] = xr[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int kk = ty + 8 * i;
+      const long long k = tk * 32 + kk, l = tl * 32 + tx;
+      if (k < v && l <= k) dst[k * ld + l] = xr[i];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int kk = ty + 8 * i;
+      const long long lr = tl * 32 + kk, kc = tk * 32 + tx;
+      if (kc < v && lr < kc) dst[lr * ld + kc] = tile[tx][kk];
+    }
+    __syncthreads();
+  }
+}
+static int64_t unpack_walkers(int64_t rows, int64_t ntiles);
+int dev_unpack_pair_block(int64_t n, int64_t o, const double* S, double* Mv, int64_t ld) {
+  REQUIRE_INIT();
+  const int64_t v = n - o, npv = v * (v + 1) / 2;
+  if (npv <= 0) return QEMB_OK;
+  if (o < 0 || ld < v) { set_error("dev_unpack_pair_block: need 0 <= o < n and ld >= n - o"); return QEMB_ERR_ARG; }
+  const int64_t nt = (v + 31) / 32;
+  return launch("dev_unpack_pair_block", unpack_pair_block_kernel, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)unpack_walkers(npv, nt * (nt + 1) / 2)), dim3(256), 0, g_stream,
+                n, o, S, Mv, ld);
 }
 // one workgroup per output row P(a,b); for every c the two source runs (d = 0..c) are contiguous:
 //   (ac|bd) = Mp[P(va,vc)][vb][vd],   (ad|bc) = (bc|ad) = Mp[P(vb,vc)][va][vd]
-__global__ void __launch_bounds__(256) ladder_pack_vvvv_pf_kernel(long long n, long long o, const double* __restrict__ Mp,
+__global__ void __launch_bounds__(256) ladder_pack_vvvv_pf_kernel(long long n, long long o, const double* __restrict__ Mp, long long ld,
                                                                  double* __restrict__ Vp, long long ldp, double* __restrict__ Vm, long long ldm) {
-  const long long v = n - o, np = v * (v + 1) / 2, nm = v * (v - 1) / 2, n2 = n * n;
+  const long long v = n - o, np = v * (v + 1) / 2, nm = v * (v - 1) / 2, n2 = n * ld;      // (ld: row stride inside a slab of n rows)
   for (long long ab = blockIdx.x; ab < np; ab += gridDim.x) {
     long long a, b; unpair_ge(ab, a, b);
     double* vp = Vp + ab * ldp;
@@ -1587,8 +1706,8 @@ __global__ void __launch_bounds__(256) ladder_pack_vvvv_pf_kernel(long long n, l
         long long c = 0, d = 0;
         if (in[u]) unpair_ge(cd, c, d);
         cc[u] = c; dd[u] = d;
-        x[u] = in[u] ? Mp[pair_idx(o + a, o + c) * n2 + (o + b) * n + (o + d)] : 0.0;
-        y[u] = in[u] ? Mp[pair_idx(o + b, o + c) * n2 + (o + a) * n + (o + d)] : 0.0;
+        x[u] = in[u] ? Mp[pair_idx(o + a, o + c) * n2 + (o + b) * ld + (o + d)] : 0.0;
+        y[u] = in[u] ? Mp[pair_idx(o + b, o + c) * n2 + (o + a) * ld + (o + d)] : 0.0;
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -1602,12 +1721,14 @@ __global__ void __launch_bounds__(256) ladder_pack_vvvv_pf_kernel(long long n, l
     if (vm) for (long long q = nm + threadIdx.x; q < ldm; q += blockDim.x) vm[q] = 0.0;
   }
 }
-int dev_ladder_pack_vvvv_pf(int64_t n, int64_t o, const double* Mp, double* Vp, int64_t ldp, double* Vm, int64_t ldm) {
+int dev_ladder_pack_vvvv_pf_ld(int64_t n, int64_t o, const double* Mp, int64_t ld, double* Vp, int64_t ldp, double* Vm, int64_t ldm) {
   REQUIRE_INIT();
   const long long v = n - o, np = v * (v + 1) / 2;
   if (np <= 0) return QEMB_OK;
-  return launch("dev_ladder_pack_vvvv_pf", ladder_pack_vvvv_pf_kernel, dim3((unsigned)std::min<long long>(np, 1 << 20)), dim3(256), 0, g_stream, n, o, Mp, Vp, ldp, Vm, ldm);
+  if (ld < n) { set_error("dev_ladder_pack_vvvv_pf_ld: ld < n"); return QEMB_ERR_ARG; }
+  return launch("dev_ladder_pack_vvvv_pf", ladder_pack_vvvv_pf_kernel, dim3((unsigned)std::min<long long>(np, 1 << 20)), dim3(256), 0, g_stream, n, o, Mp, (long long)ld, Vp, ldp, Vm, ldm);
 }
+int dev_ladder_pack_vvvv_pf(int64_t n, int64_t o, const double* Mp, double* Vp, int64_t ldp, double* Vm, int64_t ldm) { return dev_ladder_pack_vvvv_pf_ld(n, o, Mp, n, Vp, ldp, Vm, ldm); }
 
 // ---- (+/-) packed ladder ------------------------------------------------------------------------------------
 // one block row per (a >= b); threads run over P(c,d).  Reads M[a,c,b,d] (d contiguous) and M[a,d,b,c].
@@ -1640,7 +1761,9 @@ int dev_ladder_pack_vvvv(int64_t n, int64_t o, const double* M, double* Vp, int6
 // index: 2.6 TB/s (pack_pm_cols), 3.8 TB/s (ladder_pack_tau).  Here a workgroup takes one pair of 32 x 32 tiles (tc >= td) of a slab: tile
 // (tc, td) and its mirror (td, tc) are both read along rows, the mirror is read transposed out of LDS, and each thread row writes 32
 // consecutive packed entries c(c+1)/2 + d.  MODE 0: Op = x + y, Om = x - y for every row.  MODE 1 (tau): the slab of packed row ij is
-// (i*o + j), Op = w (x + y) with w = 1/2 (1/4 on c = d), Om = (x - y)/2 only for i > j (row Q(i,j)).
+// (i*o + j), Op = w (x + y) with w = 1/2 (1/4 on c = d), Om = (x - y)/2 only for i > j (row Q(i,j)).  MODE 2: row r = (k,a) packs the TRANSPOSED
+// image x[c][d] = in[k][d][a][c] of an [o][v][v][v] block (rows of the image v * v apart): Op[(k,a)][P(c,d)] = in[k,d,a,c] + in[k,c,a,d], Om the difference
+// -- what MODE 0 gives on the permuted copy in[k,a,c,d] <- in[k,d,a,c], without that copy.
 template <int MODE>
 __global__ void __launch_bounds__(256) pack_pm_tiled_kernel(long long rows, long long o, long long v, const double* __restrict__ in, double* __restrict__ Op,
                                                             long long ldp, double* __restrict__ Om, long long ldm) {
@@ -1656,18 +1779,22 @@ __global__ void __launch_bounds__(256) pack_pm_tiled_kernel(long long rows, long
       long long i, j; unpair_ge(r, i, j);
       t = in + (i * o + j) * v * v;
       tm = (i > j) ? Om + (i * (i - 1) / 2 + j) * ldm : nullptr;
+    } else if (MODE == 2) {
+      const long long k = r / v, a = r - k * v;
+      t = in + k * v * v * v + a * v; tm = Om + r * ldm;
     } else {
       t = in + r * v * v; tm = Om + r * ldm;
     }
+    const long long rs = (MODE == 2) ? v * v : v;     // distance between the rows of the v x v image that is packed
     double xa[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int rr = ty + 8 * k;
       const long long c = tc * 32 + rr, d = td * 32 + tx;
-      xa[k] = (c < v && d < v) ? t[c * v + d] : 0.0;
+      xa[k] = (c < v && d < v) ? t[c * rs + d] : 0.0;
       if (!diag) {
         const long long d2 = td * 32 + rr, c2 = tc * 32 + tx;
-        tB[rr][tx] = (d2 < v && c2 < v) ? t[d2 * v + c2] : 0.0;
+        tB[rr][tx] = (d2 < v && c2 < v) ? t[d2 * rs + c2] : 0.0;
       } else {
         tB[rr][tx] = xa[k];
       }
@@ -1678,7 +1805,7 @@ __global__ void __launch_bounds__(256) pack_pm_tiled_kernel(long long rows, long
       const int cc = ty + 8 * k;
       const long long c = tc * 32 + cc, d = td * 32 + tx;
       if (c < v && d <= c) {
-        const double x = xa[k], y = tB[tx][cc];
+        const double x = (MODE == 2) ? tB[tx][cc] : xa[k], y = (MODE == 2) ? xa[k] : tB[tx][cc];
         if (MODE == 1) {
           tp[c * (c + 1) / 2 + d] = (c == d) ? 0.25 * (x + y) : 0.5 * (x + y);
           if (tm && c > d) tm[c * (c - 1) / 2 + d] = 0.5 * (x - y);
@@ -1754,6 +1881,14 @@ int dev_pack_pm_cols(int64_t rows, int64_t v, const double* in, double* Op, int6
                   rows, 0LL, v, in, Op, ldp, Om, ldm);
   }
   return launch("dev_pack_pm_cols", pack_pm_cols_kernel, dim3((unsigned)std::min<int64_t>(rows, 1 << 20)), dim3(256), 0, g_stream, rows, v, in, Op, ldp, Om, ldm);
+}
+int dev_pack_pm_ovvv(int64_t o, int64_t v, const double* ovvv, double* Op, int64_t ldp, double* Om, int64_t ldm) {
+  REQUIRE_INIT();
+  if (o <= 0 || v <= 0) return QEMB_OK;
+  if (v < 32) { set_error("dev_pack_pm_ovvv: tiled pass only (v >= 32)"); return QEMB_ERR_ARG; }
+  const long long nt = (v + 31) / 32;
+  return launch("dev_pack_pm_ovvv", pack_pm_tiled_kernel<2>, dim3((unsigned)(nt * (nt + 1) / 2), (unsigned)std::min<int64_t>(o * v, 16384)), dim3(256), 0, g_stream,
+                o * v, 0LL, v, ovvv, Op, ldp, Om, ldm);
 }
 __device__ __forceinline__ void scatter_pm_rows_kernel_body(const uint3 BID, const uint3 GDIM, long long o, long long ncols, const double* __restrict__ Xp, const double* __restrict__ Xm, double* __restrict__ out, const double* __restrict__ add,
                                                             int Sp, long long strideP, int Sm, long long strideM) {

@@ -431,6 +431,33 @@ int qemb_int_cholesky_bytes(qemb_int_basis_t basis, int64_t panel_pairs, int64_t
 int qemb_int_cholesky_stats(qemb_int_basis_t basis, double* out4);
 int qemb_df_set_ints_from_cholesky(qemb_df_t df, qemb_int_basis_t basis, double tol, double span, int64_t panel_pairs, int64_t max_rank);
 
+/* ---- one-electron integrals of an uploaded basis on the device (csrc/int3c.cpp: int1e_fill; kernel csrc/int1e_ops.hip) ----
+ * S (overlap), T (kinetic energy) and V = sum_C -Z_C <a|1/r_C|b> (nuclear attraction) of the contracted real-spherical functions of `basis`: normalisation, component
+ * order and Cartesian -> spherical matrices are those of the uploaded records, i.e. of Mole.one_electron().  natm nuclei at xyz (3 natm doubles, Bohr) with charges Z.
+ * S_out, T_out, V_out: host arrays, N x N row-major; a NULL one is not computed.  Only shell pairs A >= B are evaluated and every element is stored once with its
+ * mirror image: the matrices are symmetric to the bit and two calls give the same bits (no atomics).  natm < 0, or V_out with natm > 0 and NULL xyz / Z: QEMB_ERR_ARG;
+ * an orbital shell with l > 2: QEMB_ERR_UNSUPPORTED naming the shell and its l. */
+int qemb_int1e(qemb_int_basis_t basis, int natm, const double* xyz, const double* Z, double* S_out, double* T_out, double* V_out);
+
+/* ---- J and K of the AO-level mean field from the resident dense 3-index tensor of a DF context (csrc/ao2mo.cpp: DfContext::jk) ----
+ * With T = (P|mu nu) resident as [naux][N][N] and the inverse metric factor Linv (B = Linv T):  J[mu,nu] = sum_P B[P,mu nu] sum_{la si} B[P,la si] D[la,si],
+ * K[mu,la] = sum_P sum_{nu si} B[P,mu nu] B[P,la si] D[nu,si].  The density enters K through a factor Cw (N x (npos + nneg), host, row-major): D = sum_k s_k c_k c_k^T,
+ * the columns scaled by sqrt|w_k|, the npos columns with s_k = +1 first, then the nneg columns with s_k = -1 (an indefinite density is legal).  dm (N x N, host,
+ * symmetric) feeds J; NULL: D is formed from Cw on the device.  J_out / K_out: host, N x N; either may be NULL, not both.  N must be the N of the context.
+ *   J: rho = T D, c = Linv^T (Linv rho), J = sum_P c_P T_P: two passes over the tensor, 4 naux N^2 flop.
+ *   K: per slab of occ_block columns of one sign Y[mu,P,k] = sum_nu T[P,mu,nu] Cw[nu,k], Z[mu] = Linv Y[mu], K +/-= Z Z^T over (P, k); 2 naux N k (2 N + naux) flop.
+ *      The lower triangle is mirrored at the end: K is symmetric to the bit.
+ * A context with an identity metric (qemb_df_set_ints_from_cholesky) skips both products with Linv.  occ_block <= 0: all columns if they fit, else the largest slab
+ * (halving) that fits.  No atomics and a fixed slab order: the same bits from call to call at a given occ_block.
+ * qemb_df_jk_bytes(ctx, ncol, occ_block, &bytes): 8 (f naux N kb + N ncol + (3 + s) N^2 + 3 naux), kb = occ_block > 0 ? min(occ_block, ncol) : ncol, f = 2 with a metric,
+ *   1 with the identity; s N^2 doubles are the split-K slices the last product (K = naux kb) may leave in the GEMM's work space: s = 0 when naux kb < 1024 or
+ *   t = ceil(N / 256)^2 >= 256, else min(ceil(768 / t), naux kb / 256) (0 when that is 1).  The other products of the call are never split.  qemb_df_jk compares its figure with min(free device memory, the limit of qemb_df_jk_mem_limit; < 0: none) before anything is allocated:
+ *   QEMB_ERR_ALLOC with N, naux, the slab and the bytes in the message.
+ * A semi-sparse context and a periodic one (planar re / im tensor: qemb_df_create_pbc + qemb_df_alloc_ints): QEMB_ERR_UNSUPPORTED naming the layout. */
+int qemb_df_jk(qemb_df_t ctx, int N, const double* dm, const double* Cw, int npos, int nneg, int occ_block, double* J_out, double* K_out);
+int qemb_df_jk_bytes(qemb_df_t ctx, int ncol, int occ_block, int64_t* bytes);
+int qemb_df_jk_mem_limit(qemb_df_t ctx, int64_t bytes);
+
 /* the resident 3-index factor of a fragment (qemb_frag_mo_route_used gives its naux), naux x npair(n) to the host; QEMB_ERR_ARG without one */
 int qemb_frag_get_df_factor(qemb_frag_t f, double* B_host);
 

@@ -259,6 +259,10 @@ def _declare(lib):
     f("qemb_op_cd_diag_update", I, L, I, P, P, P, L, P, P, P, P)
     f("qemb_op_cd_permute", I, L, L, P, P, I, P)
     f("qemb_op_df_get_ints", I, V, P, C.POINTER(I))
+    f("qemb_int1e", I, V, I, P, P, P, P, P)
+    f("qemb_df_jk", I, V, I, P, P, I, I, I, P, P)
+    f("qemb_df_jk_bytes", I, V, I, I, C.POINTER(L))
+    f("qemb_df_jk_mem_limit", I, V, L)
     f("qemb_op_int4c_class", I, I, I, I, I, P, P, P, P, P, P)
     f("qemb_op_boys", I, I, L, P, P)
     f("qemb_op_int3c_class", I, I, I, I, P, P, P, P, P)

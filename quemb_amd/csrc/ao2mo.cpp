@@ -425,6 +425,107 @@ int DfContext::transform(const double* TA, int n, double* out_s4, const double* 
   return 0;
 }
 
+// ---- J and K of the AO-level mean field from the resident tensor ------------------------------------------------------------------------------
+int DfContext::jk_check(const char* who) const {
+  if (Usp.p) { set_error(std::string(who) + ": a semi-sparse context holds no dense tensor; J / K from it are not supported"); return QEMB_ERR_UNSUPPORTED; }
+  if (Lpq_im.p) { set_error(std::string(who) + ": a periodic context (planar re / im tensor) is not supported"); return QEMB_ERR_UNSUPPORTED; }
+  if ((!Linv.p && !identity_metric) || !Lpq.p || N <= 0 || naux <= 0) { set_error(std::string(who) + ": metric and 3-index integrals must be set"); return QEMB_ERR_ARG; }
+  return 0;
+}
+// The most split-K slices (N x N partial products in the GEMM's work space) the last product K +/-= F F^T (M = N = nao, K = naux kb) may leave: dev_gemm splits a
+// product of K >= 1024 with fewer than 256 output tiles into at most ceil(768 / tiles) and at most K / 256 slices; no tile is larger than 256 x 256.  The other
+// products of the call are issued with ksplit < 0 (never split) and take no work space.
+static int64_t jk_splitk_slices(int64_t N, int64_t K) {
+  const int64_t t = ((N + 255) / 256) * ((N + 255) / 256);
+  if (K < 1024 || t >= 256) return 0;
+  const int64_t S = std::min<int64_t>((768 + t - 1) / t, K / 256);
+  return S > 1 ? S : 0;
+}
+static int64_t jk_words(int64_t naux, int64_t N, bool identity, int64_t ncol, int64_t kb) {
+  return (identity ? 1 : 2) * naux * N * kb + N * ncol + (3 + jk_splitk_slices(N, naux * kb)) * N * N + 3 * naux;
+}
+int DfContext::jk_bytes(int ncol, int occ_block, int64_t* bytes) const {
+  QTRY(jk_check("qemb_df_jk_bytes"));
+  if (ncol < 0 || occ_block < 0 || !bytes) { set_error("qemb_df_jk_bytes: bad arguments"); return QEMB_ERR_ARG; }
+  const int64_t kb = occ_block > 0 ? std::min(occ_block, ncol) : ncol;
+  *bytes = 8 * jk_words(naux, N, identity_metric, ncol, kb);
+  return QEMB_OK;
+}
+int DfContext::jk(const double* dm_host, const double* Cw_host, int npos, int nneg, int occ_block, double* J_host, double* K_host) const {
+  QTRY(jk_check("qemb_df_jk"));
+  if (npos < 0 || nneg < 0 || occ_block < 0 || (!J_host && !K_host)) { set_error("qemb_df_jk: bad arguments"); return QEMB_ERR_ARG; }
+  const int64_t ncol = (int64_t)npos + nneg, n2 = (int64_t)N * N;
+  if (ncol > 0 && !Cw_host) { set_error("qemb_df_jk: the density factor is null"); return QEMB_ERR_ARG; }
+  const bool need_cw = K_host || !dm_host;
+  // the slab and the memory guard, before anything is allocated
+  size_t free_b = 0, total_b = 0;
+  QTRY(dev_mem_info(&free_b, &total_b));
+  double room = (double)free_b;
+  if (jk_mem_limit >= 0 && (double)jk_mem_limit < room) room = (double)jk_mem_limit;
+  int64_t kb = K_host ? (occ_block > 0 ? std::min<int64_t>(occ_block, ncol) : ncol) : 0;
+  if (occ_block <= 0)
+    while (kb > 1 && 8.0 * (double)jk_words(naux, N, identity_metric, ncol, kb) > room) kb = (kb + 1) / 2;
+  const double need = 8.0 * (double)jk_words(naux, N, identity_metric, ncol, kb);
+  if (need > room) {
+    auto bytes = [](double b) { const std::string t = std::to_string(b); return t.substr(0, t.find('.')) + " bytes"; };
+    set_error("qemb_df_jk: with N = " + std::to_string(N) + ", naux = " + std::to_string(naux) + " and slabs of " + std::to_string(kb) + " columns the J / K work space takes " +
+              bytes(need) + ", more than the " + bytes(room) + " of device memory it may take");
+    return QEMB_ERR_ALLOC;
+  }
+  constexpr int64_t kBatchMax = 32768;      // products per batched launch (the batch is a grid dimension)
+  DBuf D, Cw, J, K, vec, Y, Z;
+  if (need_cw && ncol > 0) { QTRY(Cw.alloc((int64_t)N * ncol)); QTRY(dev_h2d(Cw, Cw_host, sizeof(double) * N * ncol)); }
+  TimerScope lap_DF(TIMER_DF);
+  if (J_host) {
+    QTRY(D.alloc(n2)); QTRY(J.alloc(n2)); QTRY(vec.alloc(3 * (int64_t)naux));
+    if (dm_host) QTRY(dev_h2d(D, dm_host, sizeof(double) * n2));
+    else {      // D = Cw+ Cw+^T - Cw- Cw-^T
+      QTRY(dev_fill(D, n2, 0.0));
+      if (npos > 0) QTRY(gemm(N, N, npos, 1.0, Cw, ncol, true, Cw, ncol, true, 0.0, D, N, 1, 0, 0, 0, -1, -1));
+      if (nneg > 0) QTRY(gemm(N, N, nneg, -1.0, Cw.p + npos, ncol, true, Cw.p + npos, ncol, true, 1.0, D, N, 1, 0, 0, 0, -1, -1));
+    }
+    double *rho = vec.p, *t = vec.p + naux, *c = vec.p + 2 * (int64_t)naux;
+    QTRY(dev_gemv_rows(naux, n2, Lpq, n2, D, rho, 1.0, 0.0));                                  // rho_P = sum T[P,mu nu] D[mu nu]
+    if (identity_metric) c = rho;
+    else {
+      QTRY(dev_gemv_rows(naux, naux, Linv, naux, rho, t, 1.0, 0.0));                           // t = Linv rho
+      QTRY(dev_contract_mid(1, naux, naux, Linv, t, c, naux, 1.0, 0.0));                       // c = Linv^T t
+    }
+    QTRY(dev_contract_mid(1, naux, n2, Lpq, c, J, n2, 1.0, 0.0));                              // J = sum_P c_P T_P
+  }
+  if (K_host) {
+    QTRY(K.alloc(n2));
+    QTRY(dev_fill(K, n2, 0.0));
+    if (kb > 0) {
+      QTRY(Y.alloc((int64_t)naux * N * kb));
+      if (!identity_metric) QTRY(Z.alloc((int64_t)naux * N * kb));
+    }
+    bool first = true;
+    for (int sign = 0; sign < 2; ++sign) {      // the positive columns, then the negative ones: a slab has one sign
+      const int64_t c0 = sign ? npos : 0, c1 = sign ? ncol : npos;
+      for (int64_t k0 = c0; k0 < c1; k0 += kb) {
+        const int64_t w = std::min(kb, c1 - k0), ld = (int64_t)naux * w;
+        // Y[mu][P][k] = sum_nu T[P][mu][nu] Cw[nu][k0 + k]: one product per P, written into its column block
+        for (int64_t P0 = 0; P0 < naux; P0 += kBatchMax)
+          QTRY(gemm(N, w, N, 1.0, Lpq.p + P0 * n2, N, true, Cw.p + k0, ncol, false, 0.0, Y.p + P0 * w, ld, std::min<int64_t>(kBatchMax, naux - P0), n2, 0, w, -1, -1));
+        const double* F = Y;
+        if (!identity_metric) {                 // Z[mu] = Linv Y[mu]
+          for (int64_t m0 = 0; m0 < N; m0 += kBatchMax)
+            QTRY(gemm(naux, w, naux, 1.0, Linv, naux, true, Y.p + m0 * ld, w, false, 0.0, Z.p + m0 * ld, w, std::min<int64_t>(kBatchMax, N - m0), 0, ld, ld, -1, -1));
+          F = Z;
+        }
+        QTRY(gemm(N, N, ld, sign ? -1.0 : 1.0, F, ld, true, F, ld, true, first ? 0.0 : 1.0, K, N));      // K +/-= F F^T over (P, k)
+        first = false;
+      }
+    }
+    QTRY(dev_mirror_lower(N, K, N));
+  }
+  QTRY(lap_DF.close());
+  if (J_host) QTRY(dev_d2h(J_host, J, sizeof(double) * n2));
+  if (K_host) QTRY(dev_d2h(K_host, K, sizeof(double) * n2));
+  return dev_sync();
+}
+
 // out[P1][P2] = sum_L bb[L,P1] bb[L,P2] (np x np, symmetric) from the packed factor bb[naux][np].  Only block columns at and below
 // the diagonal are computed (9/16 of the flops with 8 blocks), then mirrored.
 int df_pair_product(int64_t np, int64_t naux, const double* bb, double* out) {

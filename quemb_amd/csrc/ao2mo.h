@@ -70,6 +70,19 @@ class DfContext {
   // keep_bb (nullable): receives the fitted factor B_{ij}^{L} = bb[naux][npair(n)] (eri_onthefly.py:141) the block was formed from
   int transform(const double* TA_dev, int n, double* out_s4_dev, const double* S_abs_dev = nullptr, double eps = 0.0, DBuf* keep_bb = nullptr) const;
 
+  // J[mu,nu] = sum (mu nu|la si) D[la,si] and K[mu,la] = sum (mu nu|la si) D[nu,si] of the fitted integrals from the resident dense tensor T = (P|mu nu):
+  //   J: rho = T D, c = Linv^T (Linv rho), J = sum_P c_P T_P -- two passes over the tensor.
+  //   K: D = sum_k s_k c_k c_k^T through Cw (N x (npos + nneg), columns scaled by sqrt|w_k|, the npos positive ones first); per slab of occ_block columns of one
+  //      sign Y[mu,P,k] = sum_nu T[P,mu,nu] Cw[nu,k], Z[mu] = Linv Y[mu], K +/-= Z Z^T over the joint index (P, k); the lower triangle is mirrored at the end.
+  // An identity metric skips both Linv products.  dm_host (N x N, symmetric) may be null: D is then formed from Cw.  J_host / K_host: null = not wanted.
+  // occ_block <= 0: all columns if they fit, else the largest slab that fits.  No atomics and a fixed slab order: the same bits at a given occ_block.
+  // Semi-sparse and periodic (planar re / im) contexts: QEMB_ERR_UNSUPPORTED.  jk_bytes: what a call takes, checked against min(free memory, jk_mem_limit)
+  // before anything is allocated (QEMB_ERR_ALLOC):  8 (f naux N occ_block + N ncol + (3 + s) N^2 + 3 naux) bytes, f = 2 with a metric and 1 without,
+  // s the most split-K slices the last product may leave in the GEMM's work space (ao2mo.cpp: jk_splitk_slices).
+  int jk(const double* dm_host, const double* Cw_host, int npos, int nneg, int occ_block, double* J_host, double* K_host) const;
+  int jk_bytes(int ncol, int occ_block, int64_t* bytes) const;
+  int64_t jk_mem_limit = -1;             // device bytes a jk call may take (< 0: the free memory)
+
   DBuf Usp;                              // semi-sparse storage: [n_unique][naux]
   int64_t n_unique = 0;
   std::vector<int64_t> reach_ptr, reach_off;
@@ -77,6 +90,7 @@ class DfContext {
  private:
   int transform_semisparse(const double* TA_dev, int n, double* out_s4_dev, const double* S_abs_dev, double eps, DBuf* keep_bb) const;
   int finish_from_pair_rows(int n, const double* bpT, double* out_s4, DBuf* keep_bb) const;
+  int jk_check(const char* who) const;
 };
 
 // out[np][np] = bb^T bb for the packed factor bb[naux][np] (lower block columns + mirror)

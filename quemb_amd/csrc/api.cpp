@@ -726,6 +726,21 @@ int qemb_df_pw_select(qemb_df_t df, int part) {
   if (!df) { set_error("qemb_df_pw_select: null handle"); return QEMB_ERR_ARG; }
   return reinterpret_cast<DfContext*>(df)->select_part(part);
 }
+int qemb_df_jk(qemb_df_t ctx, int N, const double* dm, const double* Cw, int npos, int nneg, int occ_block, double* J_out, double* K_out) {
+  if (!ctx) { set_error("qemb_df_jk: null handle"); return QEMB_ERR_ARG; }
+  const DfContext* d = reinterpret_cast<const DfContext*>(ctx);
+  if (d->N > 0 && N != d->N) { set_error("qemb_df_jk: N = " + std::to_string(N) + ", the context holds N = " + std::to_string(d->N)); return QEMB_ERR_ARG; }
+  return d->jk(dm, Cw, npos, nneg, occ_block, J_out, K_out);
+}
+int qemb_df_jk_bytes(qemb_df_t ctx, int ncol, int occ_block, int64_t* bytes) {
+  if (!ctx) { set_error("qemb_df_jk_bytes: null handle"); return QEMB_ERR_ARG; }
+  return reinterpret_cast<const DfContext*>(ctx)->jk_bytes(ncol, occ_block, bytes);
+}
+int qemb_df_jk_mem_limit(qemb_df_t ctx, int64_t bytes) {
+  if (!ctx) { set_error("qemb_df_jk_mem_limit: null handle"); return QEMB_ERR_ARG; }
+  reinterpret_cast<DfContext*>(ctx)->jk_mem_limit = bytes;
+  return QEMB_OK;
+}
 int qemb_df_free(qemb_df_t df) { delete reinterpret_cast<DfContext*>(df); return QEMB_OK; }
 
 // ---- DF integrals from the basis (int3c.cpp) ----
@@ -775,6 +790,10 @@ int qemb_int2c2e(qemb_int_basis_t auxbasis, double* out, int out_on_device) {
   QTRY(d.alloc((int64_t)a->nao * a->nao));
   QTRY(int2c_fill(*a, d));
   return dev_d2h(out, d, sizeof(double) * a->nao * a->nao);
+}
+int qemb_int1e(qemb_int_basis_t basis, int natm, const double* xyz, const double* Z, double* S_out, double* T_out, double* V_out) {
+  IntBasis* o = live_basis(basis, "qemb_int1e"); if (!o) return QEMB_ERR_ARG;
+  return int1e_fill(*o, natm, xyz, Z, S_out, T_out, V_out);
 }
 // ---- four-centre AO integrals from the basis (int4c.cpp) ----
 int qemb_int4c2e(qemb_int_basis_t basis, int sym, double thresh, double* out, int out_on_device) {

@@ -397,6 +397,12 @@ int dev_boys(int m_max, int64_t n, const double* x, double* out);
 namespace int3c { struct ClassArgs; }
 int dev_int3c_class(int la, int lb, int lp, const int3c::ClassArgs& args);
 
+// ---- one-electron integrals from the basis (int3c.cpp: int1e_fill; kernel in int1e_ops.hip, scalar restatement in int1e_ops_hostcheck.cpp; arithmetic in int1e_core.h) ----
+// One launch per orbital pair class (la >= lb <= 2), one wavefront per shell pair: the blocks of S, T and V = sum_C -Z_C <a|1/r_C|b> (whichever of args.out is not null)
+// and their mirror images, every element stored once by plain stores.
+namespace int1e { struct Args; }
+int dev_int1e_class(int la, int lb, const int1e::Args& args);
+
 // ---- four-centre AO integrals from the basis (int4c.cpp; kernels in int4c_ops.hip, scalar restatement in int4c_ops_hostcheck.cpp; arithmetic in int4c_core.h) ----
 // pairs: per (shell pair, primitive pair) of one pair class la >= lb <= 2 the exponent sum, the centre and the Hermite expansion of the spherical products.
 // class: one launch per canonical class (la >= lb | lc >= ld), pair class of the bra >= that of the ket: every quartet of the two lists, each output element stored once.

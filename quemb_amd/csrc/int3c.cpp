@@ -1,6 +1,8 @@
 // int3c.cpp -- driver of the DF integrals on the device (see int3c.h): shells from the uploaded records, work lists per angular class, one launch per class;
+// the one-electron integrals of the same basis (int1e_fill);
 // and the refusals and the record -> shell copy it shares with the four-centre driver (int4c.cpp).
 #include "int3c.h"
+#include "int1e_core.h"
 #include <algorithm>
 #include <cstring>
 #include <map>
@@ -203,6 +205,48 @@ int int2c_fill(const IntBasis& aux, double* out) {
       if (int rc = dev_int3c_class(la, 0, lp, g)) { dev_sync(); return rc; }
     }
   return dev_sync();
+}
+
+// S, T and V of the basis: shell pairs I >= J grouped by pair class, one launch per class (one wavefront per shell pair), the matrices assembled on the device
+// and copied out.  A null output is not computed.
+int int1e_fill(const IntBasis& orb, int natm, const double* xyz_host, const double* Z_host, double* S_host, double* T_host, double* V_host) {
+  if (natm < 0 || (V_host && natm > 0 && (!xyz_host || !Z_host))) { set_error("qemb_int1e: the nuclear attraction needs natm >= 0 centres and charges"); return QEMB_ERR_ARG; }
+  QTRY(check_orbital(orb, "qemb_int1e"));
+  double* host[3] = {S_host, T_host, V_host};
+  if (!S_host && !T_host && !V_host) return QEMB_OK;
+  std::map<int, PairClass> cls;      // key la * 8 + lb
+  for (int I = 0; I < orb.nshell; ++I)
+    for (int J = 0; J <= I; ++J) {
+      const bool sw = orb.shells[I].l < orb.shells[J].l;
+      PairClass& c = cls[orb.shells[sw ? J : I].l * 8 + orb.shells[sw ? I : J].l];
+      c.pa.push_back(sw ? J : I); c.pb.push_back(sw ? I : J);
+    }
+  IndexPool pool;
+  for (auto& kv : cls) {
+    PairClass& c = kv.second;
+    c.o_pa = pool.i32.size(); pool.i32.insert(pool.i32.end(), c.pa.begin(), c.pa.end());
+    c.o_pb = pool.i32.size(); pool.i32.insert(pool.i32.end(), c.pb.begin(), c.pb.end());
+  }
+  QTRY(pool.upload());
+  const int64_t n2 = (int64_t)orb.nao * orb.nao;
+  DBuf nuc, out[3];
+  if (V_host && natm > 0) {
+    QTRY(nuc.alloc(4 * (int64_t)natm));
+    QTRY(dev_h2d(nuc, xyz_host, sizeof(double) * 3 * natm));
+    QTRY(dev_h2d(nuc.p + 3 * natm, Z_host, sizeof(double) * natm));
+  }
+  int1e::Args g{};
+  g.sh = orb.dev(); g.c2s = orb.dc2s; g.natm = natm; g.xyz = nuc.p; g.Z = nuc.p ? nuc.p + 3 * natm : nullptr; g.N = orb.nao;
+  for (int k = 0; k < 3; ++k)
+    if (host[k]) { QTRY(out[k].alloc(n2)); g.out[k] = out[k]; }
+  for (auto& kv : cls) {
+    const PairClass& c = kv.second;
+    g.pa = pool.p32(c.o_pa); g.pb = pool.p32(c.o_pb); g.npair = (int64_t)c.pa.size();
+    if (int rc = dev_int1e_class(kv.first / 8, kv.first % 8, g)) { dev_sync(); return rc; }      // earlier launches still read the index lists
+  }
+  for (int k = 0; k < 3; ++k)
+    if (host[k]) QTRY(dev_d2h(host[k], out[k], sizeof(double) * n2));
+  return dev_sync();      // the index lists are released on return
 }
 
 int int3c_block(int la, int lb, int lp, const BfRecord* A, const BfRecord* B, const BfRecord* P, const double* c2s_host, double* out_host) {

@@ -162,7 +162,12 @@ def _reach_csr(exch_reachable_with_offsets):
 
 
 class DFContext:
-    """Density-fitting context: metric factor and (P|mu nu) resident on the device."""
+    """Density-fitting context: metric factor and (P|mu nu) resident on the device.  `layout`: what the context holds -- None (no integrals yet), "dense" (the
+    [naux][N][N] tensor: `get_jk` and the mean field read it), "semisparse" or "periodic" (planar re / im accumulation); `identity_metric`: the tensor is a Cholesky
+    factor of the integrals themselves (`from_cholesky`; `cd_tol` its tolerance)."""
+    layout = None
+    identity_metric = False
+    cd_tol = None
 
     def __init__(self, j2c=None, L_PQ=None, lib=None):
         self.lib = lib or _lib.init()
@@ -230,6 +235,7 @@ class DFContext:
             if basis is None:
                 b.free()
         self.naux, self.nao = self.cd_stats["rank"], mol.nao
+        self.layout, self.identity_metric, self.cd_tol = "dense", True, float(tol)
         return self
 
     def set_ints_from_mol(self, mol, auxmol, int_P_mu_nu=None):
@@ -253,11 +259,12 @@ class DFContext:
         finally:
             b.free(); a.free()
         self.naux, self.nao = auxmol.nao, mol.nao
+        self.layout, self.identity_metric, self.cd_tol = ("dense" if int_P_mu_nu is None else "semisparse"), False, None
 
     def alloc_ints(self, nao: int):
         """zeroed fitted tensor (L|mu nu) (real and imaginary part) for `add_pw_block` / `add_rs_block`"""
         check(self.lib.qemb_df_alloc_ints(self.h, int(nao)), "qemb_df_alloc_ints", self.lib)
-        self.nao = int(nao)
+        self.nao, self.layout = int(nao), "periodic"
 
     def add_pw_block(self, F, pw):
         """(L|mu nu) += sum_G F[L,G] (G|mu nu): F = ft_ao(chgcell, Gv_block).conj().T (naux, nG), pw = ft_aopair(cell, Gv_block) * coulG.conj()
@@ -293,7 +300,7 @@ class DFContext:
         if ints.size != want:
             raise ValueError("DFContext.set_ints: array size does not match layout")
         check(self.lib.qemb_df_set_ints(self.h, int(nao), ints.ctypes.data, code), "qemb_df_set_ints", self.lib)
-        self.nao = int(nao)
+        self.nao, self.layout = int(nao), "dense"
 
     def set_ints_semisparse(self, int_P_mu_nu):
         """Upload a SemiSparseSym3DTensor (this module's or the reference's pybind object: `unique_dense_data` (naux, n_unique) and
@@ -308,7 +315,7 @@ class DFContext:
         nao = len(ptr) - 1
         check(self.lib.qemb_df_set_ints_semisparse(self.h, nao, rows.shape[0], rows.ctypes.data, ptr.ctypes.data, nu.ctypes.data,
                                                    off.ctypes.data), "qemb_df_set_ints_semisparse", self.lib)
-        self.nao = nao
+        self.nao, self.layout = nao, "semisparse"
 
     def transform(self, TA, frag=None, want_host=True, S_abs=None, MO_coeff_epsilon=None, factor_only=False):
         """(ij|kl) 4-fold packed.  With `S_abs` and `MO_coeff_epsilon` the reference's semi-sparse screening is applied
@@ -342,6 +349,58 @@ class DFContext:
         else:
             check(self.lib.qemb_df_transform(self.h, TA.ctypes.data, n, op, fh), "qemb_df_transform", self.lib)
         return out
+
+    # ---- J and K of the AO-level mean field from the resident dense tensor (qemb_df_jk) ---------------------------------------------------------------
+    def _jk(self, dm, Cw, npos, nneg, with_j, with_k, occ_block):
+        if not (with_j or with_k):
+            raise ValueError("get_jk: with_j and with_k are both False")
+        N = self.nao
+        J = np.empty((N, N)) if with_j else None
+        K = np.empty((N, N)) if with_k else None
+        check(self.lib.qemb_df_jk(self.h, N, None if dm is None else dm.ctypes.data, Cw.ctypes.data if Cw.size else None, npos, nneg, int(occ_block or 0),
+                                  J.ctypes.data if with_j else None, K.ctypes.data if with_k else None), "qemb_df_jk", self.lib)
+        return J, K
+
+    def get_jk(self, dm, with_j=True, with_k=True, occ_block=None):
+        """(J, K) of the fitted integrals for a symmetric density `dm` (symmetrised like integrals.DeviceBasis.get_jk; ValueError when it is not symmetric).  For K
+        the density is factored on the host, dm = sum_k w_k v_k v_k^T (eigh); |w_k| < 1e-14 max|w| is dropped and the columns sqrt|w_k| v_k are handed over with
+        the positive ones first -- an indefinite density is legal, its negative columns are subtracted.  occ_block: columns per slab (None: all that fit).
+        A matrix that was not asked for is None.  No atomics: the same bits from call to call at a given occ_block; K is symmetric to the bit."""
+        from .integrals import _symmetric_density
+        if self.nao is None:
+            raise ValueError("DFContext.get_jk: set the integrals first")
+        dm = _symmetric_density(dm, self.nao)
+        Cw, npos, nneg = np.zeros((self.nao, 0)), 0, 0
+        if with_k:
+            w, v = np.linalg.eigh(dm)
+            top = np.abs(w).max()
+            keep = np.abs(w) >= 1e-14 * top if top > 0.0 else np.zeros(len(w), dtype=bool)
+            pos, neg = np.nonzero(keep & (w > 0))[0][::-1], np.nonzero(keep & (w < 0))[0]
+            Cw = np.ascontiguousarray(np.hstack([v[:, pos] * np.sqrt(w[pos]), v[:, neg] * np.sqrt(-w[neg])]))
+            npos, nneg = len(pos), len(neg)
+        return self._jk(dm, Cw, npos, nneg, with_j, with_k, occ_block)
+
+    def get_jk_orbitals(self, C_occ, occ=2.0, with_j=True, with_k=True, occ_block=None):
+        """(J, K) of the density occ * C_occ C_occ^T straight from the occupied orbitals (N x n_occ): no eigen-decomposition, the density itself is formed on the
+        device.  What the cycles of RHF(density_fit=...).kernel() call."""
+        if self.nao is None:
+            raise ValueError("DFContext.get_jk_orbitals: set the integrals first")
+        C_occ = np.asarray(C_occ, dtype=float)
+        if C_occ.ndim != 2 or C_occ.shape[0] != self.nao or occ < 0:
+            raise ValueError(f"get_jk_orbitals: C_occ must be {self.nao} x n_occ and occ >= 0")
+        Cw = np.ascontiguousarray(C_occ * np.sqrt(occ))
+        return self._jk(None, Cw, Cw.shape[1], 0, with_j, with_k, occ_block)
+
+    def jk_bytes(self, ncol, occ_block=None):
+        """device bytes a get_jk call with `ncol` density columns takes at this slab size (qemb_df_jk_bytes):
+        8 (f naux N kb + N ncol + (3 + s) N^2 + 3 naux), f = 2 with a metric and 1 without, s the most split-K slices the last product may leave (include/qemb_hip.h)"""
+        b = C.c_int64()
+        check(self.lib.qemb_df_jk_bytes(self.h, int(ncol), int(occ_block or 0), C.byref(b)), "qemb_df_jk_bytes", self.lib)
+        return b.value
+
+    def jk_mem_limit(self, nbytes):
+        """device bytes a get_jk call may take (qemb_df_jk_mem_limit); None or < 0: whatever is free"""
+        check(self.lib.qemb_df_jk_mem_limit(self.h, -1 if nbytes is None else int(nbytes)), "qemb_df_jk_mem_limit", self.lib)
 
     def free(self):
         if getattr(self, "h", None):

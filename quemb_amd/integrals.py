@@ -311,6 +311,17 @@ class DeviceBasis:
         arr, tab = mol._arr(), c2s_table()
         _lib.check(self.lib.qemb_int_basis_create(mol.ncart, C.addressof(arr), C.sizeof(_BF), tab.ctypes.data, C.byref(h)), "qemb_int_basis_create", self.lib)
         self.h, self.nao = h, mol.nao
+        self._xyz = np.ascontiguousarray([a[1] for a in mol.atom], dtype=float).reshape(-1, 3)
+        self._Z = np.ascontiguousarray([_Z[a[0]] for a in mol.atom], dtype=float)
+
+    def one_electron(self):
+        """(S, T, V) of the basis from the device kernel (qemb_int1e): overlap, kinetic energy and nuclear attraction sum_C -Z_C <a|1/r_C|b> over the atoms of the
+        molecule the basis was made from -- the arrays of `Mole.one_electron()`.  Symmetric to the bit; two calls return the same bits."""
+        from . import _lib
+        N = self.nao
+        S, T, V = np.empty((N, N)), np.empty((N, N)), np.empty((N, N))
+        _lib.check(self.lib.qemb_int1e(self.h, len(self._Z), self._xyz.ctypes.data, self._Z.ctypes.data, S.ctypes.data, T.ctypes.data, V.ctypes.data), "qemb_int1e", self.lib)
+        return S, T, V
 
     def eri(self, sym=8, thresh=0.0, out_dev=None):
         """(mu nu|la si) from the device kernels (qemb_int4c2e) in form `sym`: 8 (1-D, PySCF's 8-fold packed form), 4 ([npair][npair]) or 1 ([N]^4).  out_dev: a
@@ -539,6 +550,17 @@ def aux_e2_pairs(mol: Mole, auxmol: Mole, pairs, backend="host", lib=None):
     return res
 
 
+def one_electron(mol: Mole, backend="host", lib=None):
+    """(S, T, V) of `mol`.  backend="host": Mole.one_electron() (libqemb_gto); backend="hip": the device kernel (DeviceBasis.one_electron)."""
+    if _backend(backend):
+        b = DeviceBasis(mol, lib)
+        try:
+            return b.one_electron()
+        finally:
+            b.free()
+    return mol.one_electron()
+
+
 def pack_eri(eri_s1, sym):
     """The full [N]^4 tensor in PySCF's 4-fold ([npair][npair]) or 8-fold (1-D npair (npair + 1) / 2) packed form (pair index ij = i (i + 1) / 2 + j, i >= j)."""
     if sym == 1:
@@ -598,13 +620,30 @@ class RHF:
     """Closed-shell RHF with DIIS in the AO basis (generalised eigenproblem through S^-1/2).  integral_backend="hip": `_eri` comes from the device kernels in the
     8-fold packed form (PySCF's own form of mf._eri); J and K are then contracted from the packed integrals.  direct=True (with integral_backend="hip"): direct
     SCF -- `_eri` stays None, every J and K of kernel() and get_veff() is formed integral-direct on the device (DeviceBasis.get_jk, screened at direct_thresh)
-    from one DeviceBasis kept on the object; those sums are accumulated with atomic adds, so energies agree from run to run to rounding, not to the bit."""
+    from one DeviceBasis kept on the object; those sums are accumulated with atomic adds, so energies agree from run to run to rounding, not to the bit.
+    density_fit=X (with integral_backend="hip", not with direct=True): the mean field of the fitted integrals from ONE resident 3-index tensor, exposed as
+    `with_df` (eri_transform.DFContext).  X: an auxiliary-basis spec of `make_auxmol` (DFContext.from_mol), "cholesky" / ("cholesky", tol) (DFContext.from_cholesky:
+    the Cholesky factor of the AO integrals, no auxiliary basis), or a ready dense DFContext, which is borrowed -- `free()` leaves it alone.  `_eri` stays None;
+    S and hcore come from the device (DeviceBasis.one_electron); kernel() forms J and K from the occupied orbitals (DFContext.get_jk_orbitals), get_veff(dm) from
+    any symmetric density (DFContext.get_jk).  No atomics on this route: energies repeat to the bit."""
 
-    def __init__(self, mol: Mole, conv_tol=1e-12, max_cycle=100, integral_backend="host", lib=None, direct=False, direct_thresh=0.0):
+    def __init__(self, mol: Mole, conv_tol=1e-12, max_cycle=100, integral_backend="host", lib=None, direct=False, direct_thresh=0.0, density_fit=None):
         self.integral_backend, self._lib = ("hip" if _backend(integral_backend) else "host"), lib
         self.direct, self.direct_thresh = bool(direct), float(direct_thresh)
         if self.direct and self.integral_backend != "hip":
             raise ValueError("RHF: direct=True forms J and K on the device; it needs integral_backend='hip'")
+        self.density_fit, self.with_df, self._owns_df = density_fit, None, False
+        if density_fit is not None:
+            if self.integral_backend != "hip":
+                raise ValueError("RHF: density_fit keeps the 3-index tensor on the device; it needs integral_backend='hip'")
+            if self.direct:
+                raise ValueError("RHF: density_fit and direct=True are two sources of J and K; choose one")
+            from .eri_transform import DFContext
+            if isinstance(density_fit, DFContext):
+                if getattr(density_fit, "layout", None) != "dense" or density_fit.nao != mol.nao or getattr(density_fit, "h", None) is None:
+                    raise ValueError("RHF: the DFContext given as density_fit must hold the dense [naux][N][N] tensor of this molecule "
+                                     f"(its layout is {getattr(density_fit, 'layout', None)!r}; semi-sparse and periodic contexts are not supported)")
+                self.with_df = density_fit      # borrowed
         self._basis = None
         self._pk = None
         self.mol = mol
@@ -615,9 +654,22 @@ class RHF:
         self._eri = None
         self._S = self._h = None
 
+    def _ensure_df(self):
+        """the DF context of a density-fitted mean field, built at the first need (and again after free())"""
+        if self.with_df is None:
+            from .eri_transform import DFContext
+            from . import _lib
+            X, lib = self.density_fit, self._lib or _lib.init()
+            if X == "cholesky" or (isinstance(X, tuple) and len(X) > 0 and X[0] == "cholesky"):
+                self.with_df = DFContext.from_cholesky(self.mol, *(X[1:] if isinstance(X, tuple) else ()), lib=lib)
+            else:
+                self.with_df = DFContext.from_mol(self.mol, make_auxmol(self.mol, X), lib=lib)
+            self._owns_df = True
+        return self.with_df
+
     def get_ovlp(self):
         if self._S is None:
-            S, T, V = self.mol.one_electron()
+            S, T, V = one_electron(self.mol, "hip", self._lib) if self.density_fit is not None else self.mol.one_electron()
             self._S, self._h = S, T + V
         return self._S
 
@@ -633,6 +685,9 @@ class RHF:
         b, self._basis = getattr(self, "_basis", None), None
         if b is not None:
             b.free()
+        if getattr(self, "_owns_df", False) and self.with_df is not None:      # a borrowed context is the caller's
+            self.with_df.free()
+            self.with_df, self._owns_df = None, False
 
     def __del__(self):
         try:
@@ -640,7 +695,10 @@ class RHF:
         except Exception:
             pass
 
-    def _jk(self, dm):
+    def _jk(self, dm, C_occ=None):
+        if self.density_fit is not None:
+            df = self._ensure_df()
+            return df.get_jk_orbitals(C_occ, 2.0) if C_occ is not None else df.get_jk(dm)
         if self.direct:
             if self._basis is None:
                 self._basis = DeviceBasis(self.mol, self._lib)
@@ -693,7 +751,7 @@ class RHF:
 
     def kernel(self):
         S = self.get_ovlp(); h = self._h
-        if self._eri is None and not self.direct:
+        if self._eri is None and not self.direct and self.density_fit is None:
             self._eri = eri(self.mol, 8, "hip", lib=self._lib) if self.integral_backend == "hip" else self.mol.eri_s1()
         no = self.mol.nelectron // 2
         w, U = np.linalg.eigh(S)
@@ -701,10 +759,12 @@ class RHF:
         e, c = np.linalg.eigh(X @ h @ X)
         Cm = X @ c
         dm = 2.0 * Cm[:, :no] @ Cm[:, :no].T
+        # the density-fitted route forms J and K from the occupied orbitals; every other route keeps its one-argument call
+        jk = (lambda d, Cm: self._jk(d, Cm[:, :no])) if self.density_fit is not None else (lambda d, Cm: self._jk(d))
         fs, es = [], []
         e_old = None
         for cyc in range(self.max_cycle):
-            J, K = self._jk(dm)
+            J, K = jk(dm, Cm)
             F = h + J - 0.5 * K
             e_el = 0.5 * np.sum((h + F) * dm)
             err = X @ (F @ dm @ S - S @ dm @ F) @ X
@@ -729,7 +789,7 @@ class RHF:
             e, c = np.linalg.eigh(X @ Fd @ X)
             Cm = X @ c
             dm = 2.0 * Cm[:, :no] @ Cm[:, :no].T
-        J, K = self._jk(dm)
+        J, K = jk(dm, Cm)
         F = h + J - 0.5 * K
         e, c = np.linalg.eigh(X @ F @ X)
         self.mo_energy, self.mo_coeff = e, X @ c

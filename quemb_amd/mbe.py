@@ -33,7 +33,7 @@ class BE:
     def __init__(self, mf, fobj, *, lo_method="lowdin", thr_bath=1.0e-10, int_transform="in-core-hip", auxbasis=None,
                  df_ints=None, nproc=1, ompnum=1, initialize_fragment_idx=None, solver_opts=None, lib=None, distribute=True, nstreams=None, lockstep=None,
                  eri_file=None, scratch_dir=None, restart=False, schmidt_method="subspace", MO_coeff_epsilon=1e-5, AO_coeff_epsilon=1e-10, df_resident="factor",
-                 integral_backend="host", int_direct_tile=None, int_direct_thresh=0.0, cd_tol=1e-8, cd_span=0.01, cd_panel=None):
+                 integral_backend="host", int_direct_tile=None, int_direct_thresh=0.0, cd_tol=1e-8, cd_span=0.01, cd_panel=None, reuse_mf_df=False):
         if lo_method != "lowdin":
             raise NotImplementedError("only lo_method='lowdin' is mirrored (localisation is upstream of the hot path)")
         if restart:
@@ -70,6 +70,20 @@ class BE:
                 raise ValueError("int_transform='cholesky-hip' decomposes the integrals on the device: it needs integral_backend='hip'")
             if getattr(mf, "mol", None) is None:
                 raise ValueError("int_transform='cholesky-hip' evaluates the integrals from the geometry: the mean field needs `mol`")
+        # reuse_mf_df: on "int-direct-DF-hip" and "cholesky-hip" the fragments are transformed from the dense 3-index tensor the mean field already holds
+        # (mf.with_df, RHF(density_fit=...)): no second tensor is filled, `auxbasis` is not needed and the context stays the mean field's
+        self.reuse_mf_df = bool(reuse_mf_df)
+        if self.reuse_mf_df:
+            df, mol = getattr(mf, "with_df", None), getattr(mf, "mol", None)
+            if mol is None or not isinstance(df, et.DFContext) or df.layout != "dense" or df.nao != mol.nao or getattr(df, "h", None) is None:
+                raise ValueError("reuse_mf_df=True needs a mean field whose `with_df` is a dense DFContext of its molecule (RHF(..., density_fit=...) after kernel())")
+            if int_transform not in ("int-direct-DF-hip", "cholesky-hip"):
+                raise ValueError("reuse_mf_df=True goes with int_transform='int-direct-DF-hip' or 'cholesky-hip'")
+            if (int_transform == "cholesky-hip") != bool(df.identity_metric):      # the tensor must be the one the branch would have filled
+                raise ValueError("reuse_mf_df=True: int_transform='cholesky-hip' reads a Cholesky factor (density_fit='cholesky'), "
+                                 "'int-direct-DF-hip' a fitted tensor (density_fit=<auxiliary basis>); the mean field holds the other kind")
+            if int_transform == "cholesky-hip" and df.cd_tol is not None:
+                cd_tol = df.cd_tol      # the factor exists already: its tolerance is the one that holds
         self.cd_tol, self.cd_span, self.cd_panel = float(cd_tol), float(cd_span), None if cd_panel is None else int(cd_panel)
         self.int_direct_tile = None if int_direct_tile is None else int(int_direct_tile)
         self.int_direct_thresh = float(int_direct_thresh)
@@ -185,6 +199,14 @@ class BE:
                     ao.transform(self.Fobjs[I].TA, frag=self.Fobjs[I].dev, want_host=False)
             finally:
                 ao.free()
+        elif self.reuse_mf_df and it in ("int-direct-DF-hip", "cholesky-hip"):
+            # the tensor of the mean field serves the fragments too: borrowed, not freed here
+            df = self.mf.with_df
+            if it == "cholesky-hip":
+                self.cd_stats = dict(getattr(df, "cd_stats", {}))
+            for I in idx:
+                df.transform(self.Fobjs[I].TA, frag=self.Fobjs[I].dev, want_host=False, factor_only=self.df_resident == "factor")
+            self._eri_from_geometry = True
         elif it == "int-direct-hip":
             # integral-direct: one pass over the AO integrals, tile by tile, serves every fragment of `idx` (csrc/int4c.cpp: int4c_ao2mo_direct); nothing of size
             # N^4 exists on the host or the device.  `eri_` (mf._eri) is ignored: the integrals come from mf.mol

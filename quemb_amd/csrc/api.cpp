@@ -399,51 +399,55 @@ int qemb_frag_set_energy_data(qemb_frag_t f, const double* h1, const double* vef
   return QEMB_OK;
 }
 int qemb_frag_jk(qemb_frag_t f, const double* P, double* J, double* K) { CHECK_FRAG(f); return FRAG(f)->hf_veff_from_dm(P, J, K); }
+// What a solve entry hands back through its nullable out-pointers, for fragment f of the call (0 of a single solve): the counters always, the energies of a call
+// that did not fail.  e_total: the entry reports e_scf + e_corr_mo (the FCI eigenvalue) where the others report e_corr_mo.
+static void store_result(Fragment* fr, const FragmentResult& r, int rc, int f, bool e_total, double* e_frag, double* e, double* e_scf, double* ebe_hf, int* n_iter, int* scf_cycles) {
+  if (n_iter) n_iter[f] = r.n_iter;
+  if (scf_cycles) scf_cycles[f] = r.scf_cycles;
+  fr->last_lambda_iters = r.lambda_iters;
+  if (rc < 0) return;
+  if (e_frag) for (int k = 0; k < 3; ++k) e_frag[3 * f + k] = r.e_frag[k];
+  if (e) e[f] = e_total ? r.e_scf + r.e_corr_mo : r.e_corr_mo;
+  if (e_scf) e_scf[f] = r.e_scf;
+  if (ebe_hf) ebe_hf[f] = r.ebe_hf;
+}
+// The handles, nsocc, h, dm0 and output pointers of a batched entry `name` as the Fragment batch calls take them; a foreign opts struct and null or repeated handles are refused
+static int gather_batch(const char* name, int nfrag, const qemb_frag_t* frags, const int* nsocc, const double* const* h, const double* const* dm0, const qemb_solver_opts* opts,
+                        double* const* mo_coeff, double* const* mo_energy, double* const* rdm1_emb, double* const* rdm1_mo, double* const* t1, double* const* t2,
+                        std::vector<Fragment*>& frs, std::vector<int>& o, std::vector<const double*>& hs, std::vector<const double*>& dms, std::vector<Fragment::BatchOutputs>& outs) {
+  if (nfrag < 0 || (nfrag > 0 && (!frags || !nsocc || !h))) { set_error(std::string(name) + ": bad arguments"); return QEMB_ERR_ARG; }
+  CHECK_OPTS(opts);
+  outs.assign(nfrag > 0 ? nfrag : 0, Fragment::BatchOutputs());
+  for (int f = 0; f < nfrag; ++f) {
+    if (!frags[f] || !h[f]) { set_error(std::string(name) + ": null fragment handle or h"); return QEMB_ERR_ARG; }
+    for (int g = 0; g < f; ++g) if (frags[g] == frags[f]) { set_error(std::string(name) + ": the same fragment twice"); return QEMB_ERR_ARG; }
+    frs.push_back(FRAG(frags[f])); o.push_back(nsocc[f]); hs.push_back(h[f]); dms.push_back(dm0 ? dm0[f] : nullptr);
+    auto pick = [&](double* const* arr) { return arr ? arr[f] : nullptr; };
+    outs[f].mo_coeff = pick(mo_coeff); outs[f].mo_energy = pick(mo_energy); outs[f].rdm1_emb = pick(rdm1_emb);
+    outs[f].rdm1_mo = pick(rdm1_mo); outs[f].t1 = pick(t1); outs[f].t2 = pick(t2);
+  }
+  return QEMB_OK;
+}
 int qemb_frag_solve(qemb_frag_t f, int nsocc, const double* h, const double* dm0, const qemb_solver_opts* opts, int eeval,
                     double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* t1, double* t2,
                     double* e_frag, double* e_corr_mo, double* e_scf, double* ebe_hf, int* n_iter, int* scf_cycles) {
   CHECK_FRAG(f); CHECK_OPTS(opts);
   if (!h) { set_error("qemb_frag_solve: h is NULL"); return QEMB_ERR_ARG; }
   FragmentResult r;
-  int rc = FRAG(f)->solve(nsocc, h, dm0, to_opts(opts), eeval, &r, mo_coeff, mo_energy, rdm1_emb, rdm1_mo, t1, t2);
-  if (n_iter) *n_iter = r.n_iter;
-  if (scf_cycles) *scf_cycles = r.scf_cycles;
-  FRAG(f)->last_lambda_iters = r.lambda_iters;
-  if (rc < 0) return rc;
-  if (e_frag) { e_frag[0] = r.e_frag[0]; e_frag[1] = r.e_frag[1]; e_frag[2] = r.e_frag[2]; }
-  if (e_corr_mo) *e_corr_mo = r.e_corr_mo;
-  if (e_scf) *e_scf = r.e_scf;
-  if (ebe_hf) *ebe_hf = r.ebe_hf;
+  const int rc = FRAG(f)->solve(nsocc, h, dm0, to_opts(opts), eeval, &r, mo_coeff, mo_energy, rdm1_emb, rdm1_mo, t1, t2);
+  store_result(FRAG(f), r, rc, 0, false, e_frag, e_corr_mo, e_scf, ebe_hf, n_iter, scf_cycles);
   return rc;        // QEMB_OK, or QEMB_WARN_NOCONV with strict_convergence = 0
 }
 int qemb_frag_solve_batch(int nfrag, const qemb_frag_t* frags, const int* nsocc, const double* const* h, const double* const* dm0,
                           const qemb_solver_opts* opts, int eeval, double* const* mo_coeff, double* const* mo_energy,
                           double* const* rdm1_emb, double* const* rdm1_mo, double* const* t1, double* const* t2, double* e_frag,
                           double* e_corr_mo, double* e_scf, double* ebe_hf, int* n_iter, int* scf_cycles, int64_t* stats) {
-  if (nfrag < 0 || (nfrag > 0 && (!frags || !nsocc || !h))) { set_error("qemb_frag_solve_batch: bad arguments"); return QEMB_ERR_ARG; }
-  CHECK_OPTS(opts);
-  std::vector<Fragment*> frs; std::vector<int> o; std::vector<const double*> hs, dms; std::vector<Fragment::BatchOutputs> outs(nfrag);
-  for (int f = 0; f < nfrag; ++f) {
-    if (!frags[f] || !h[f]) { set_error("qemb_frag_solve_batch: null fragment handle or h"); return QEMB_ERR_ARG; }
-    for (int g = 0; g < f; ++g) if (frags[g] == frags[f]) { set_error("qemb_frag_solve_batch: the same fragment twice"); return QEMB_ERR_ARG; }
-    frs.push_back(FRAG(frags[f])); o.push_back(nsocc[f]); hs.push_back(h[f]); dms.push_back(dm0 ? dm0[f] : nullptr);
-    auto pick = [&](double* const* arr) { return arr ? arr[f] : nullptr; };
-    outs[f].mo_coeff = pick(mo_coeff); outs[f].mo_energy = pick(mo_energy); outs[f].rdm1_emb = pick(rdm1_emb);
-    outs[f].rdm1_mo = pick(rdm1_mo); outs[f].t1 = pick(t1); outs[f].t2 = pick(t2);
-  }
+  std::vector<Fragment*> frs; std::vector<int> o; std::vector<const double*> hs, dms; std::vector<Fragment::BatchOutputs> outs;
+  QTRY(gather_batch("qemb_frag_solve_batch", nfrag, frags, nsocc, h, dm0, opts, mo_coeff, mo_energy, rdm1_emb, rdm1_mo, t1, t2, frs, o, hs, dms, outs));
   std::vector<FragmentResult> res;
   LockstepStats st;
   const int rc = Fragment::solve_batch(frs, o, hs, dms, to_opts(opts), eeval, res, outs, &st);
-  for (int f = 0; f < nfrag && f < (int)res.size(); ++f) {
-    if (n_iter) n_iter[f] = res[f].n_iter;
-    if (scf_cycles) scf_cycles[f] = res[f].scf_cycles;
-    frs[f]->last_lambda_iters = res[f].lambda_iters;
-    if (rc < 0) continue;
-    if (e_frag) for (int k = 0; k < 3; ++k) e_frag[3 * f + k] = res[f].e_frag[k];
-    if (e_corr_mo) e_corr_mo[f] = res[f].e_corr_mo;
-    if (e_scf) e_scf[f] = res[f].e_scf;
-    if (ebe_hf) ebe_hf[f] = res[f].ebe_hf;
-  }
+  for (int f = 0; f < (int)res.size(); ++f) store_result(frs[f], res[f], rc, f, false, e_frag, e_corr_mo, e_scf, ebe_hf, n_iter, scf_cycles);
   if (stats) { stats[0] = st.merged_runs; stats[1] = st.launches; stats[2] = st.grouped; stats[3] = st.operations; stats[4] = st.max_group; }
   return rc;
 }
@@ -453,42 +457,19 @@ int qemb_frag_solve_mp2(qemb_frag_t f, int nsocc, const double* h, const double*
   CHECK_FRAG(f); CHECK_OPTS(opts);
   if (!h) { set_error("qemb_frag_solve_mp2: h is NULL"); return QEMB_ERR_ARG; }
   FragmentResult r;
-  int rc = FRAG(f)->solve_mp2(nsocc, h, dm0, to_opts(opts), eeval, &r, mo_coeff, mo_energy, rdm1_emb, rdm1_mo, t2);
-  if (scf_cycles) *scf_cycles = r.scf_cycles;
-  FRAG(f)->last_lambda_iters = 0;
-  if (rc < 0) return rc;
-  if (e_frag) { e_frag[0] = r.e_frag[0]; e_frag[1] = r.e_frag[1]; e_frag[2] = r.e_frag[2]; }
-  if (e_corr_mo) *e_corr_mo = r.e_corr_mo;
-  if (e_scf) *e_scf = r.e_scf;
-  if (ebe_hf) *ebe_hf = r.ebe_hf;
+  const int rc = FRAG(f)->solve_mp2(nsocc, h, dm0, to_opts(opts), eeval, &r, mo_coeff, mo_energy, rdm1_emb, rdm1_mo, t2);
+  store_result(FRAG(f), r, rc, 0, false, e_frag, e_corr_mo, e_scf, ebe_hf, nullptr, scf_cycles);
   return rc;        // QEMB_OK, or QEMB_WARN_NOCONV with strict_convergence = 0
 }
 int qemb_frag_solve_mp2_batch(int nfrag, const qemb_frag_t* frags, const int* nsocc, const double* const* h, const double* const* dm0,
                               const qemb_solver_opts* opts, int eeval, double* const* mo_coeff, double* const* mo_energy,
                               double* const* rdm1_emb, double* const* rdm1_mo, double* const* t2, double* e_frag, double* e_corr_mo,
                               double* e_scf, double* ebe_hf, int* scf_cycles) {
-  if (nfrag < 0 || (nfrag > 0 && (!frags || !nsocc || !h))) { set_error("qemb_frag_solve_mp2_batch: bad arguments"); return QEMB_ERR_ARG; }
-  CHECK_OPTS(opts);
-  std::vector<Fragment*> frs; std::vector<int> o; std::vector<const double*> hs, dms; std::vector<Fragment::BatchOutputs> outs(nfrag);
-  for (int f = 0; f < nfrag; ++f) {
-    if (!frags[f] || !h[f]) { set_error("qemb_frag_solve_mp2_batch: null fragment handle or h"); return QEMB_ERR_ARG; }
-    for (int g = 0; g < f; ++g) if (frags[g] == frags[f]) { set_error("qemb_frag_solve_mp2_batch: the same fragment twice"); return QEMB_ERR_ARG; }
-    frs.push_back(FRAG(frags[f])); o.push_back(nsocc[f]); hs.push_back(h[f]); dms.push_back(dm0 ? dm0[f] : nullptr);
-    auto pick = [&](double* const* arr) { return arr ? arr[f] : nullptr; };
-    outs[f].mo_coeff = pick(mo_coeff); outs[f].mo_energy = pick(mo_energy); outs[f].rdm1_emb = pick(rdm1_emb);
-    outs[f].rdm1_mo = pick(rdm1_mo); outs[f].t2 = pick(t2);
-  }
+  std::vector<Fragment*> frs; std::vector<int> o; std::vector<const double*> hs, dms; std::vector<Fragment::BatchOutputs> outs;
+  QTRY(gather_batch("qemb_frag_solve_mp2_batch", nfrag, frags, nsocc, h, dm0, opts, mo_coeff, mo_energy, rdm1_emb, rdm1_mo, nullptr, t2, frs, o, hs, dms, outs));
   std::vector<FragmentResult> res;
   const int rc = Fragment::solve_mp2_batch(frs, o, hs, dms, to_opts(opts), eeval, res, outs);
-  for (int f = 0; f < nfrag && f < (int)res.size(); ++f) {
-    if (scf_cycles) scf_cycles[f] = res[f].scf_cycles;
-    frs[f]->last_lambda_iters = 0;
-    if (rc < 0) continue;
-    if (e_frag) for (int k = 0; k < 3; ++k) e_frag[3 * f + k] = res[f].e_frag[k];
-    if (e_corr_mo) e_corr_mo[f] = res[f].e_corr_mo;
-    if (e_scf) e_scf[f] = res[f].e_scf;
-    if (ebe_hf) ebe_hf[f] = res[f].ebe_hf;
-  }
+  for (int f = 0; f < (int)res.size(); ++f) store_result(frs[f], res[f], rc, f, false, e_frag, e_corr_mo, e_scf, ebe_hf, nullptr, scf_cycles);
   return rc;
 }
 // ---- solver == "FCI-hip"
@@ -511,15 +492,8 @@ int qemb_frag_solve_fci(qemb_frag_t f, int nsocc, const double* h, const double*
   FciOptions fo;
   if (fci_opts) { fo.conv_tol = fci_opts->conv_tol; fo.max_cycle = fci_opts->max_cycle; fo.max_space = fci_opts->max_space; fo.lindep = fci_opts->lindep; }
   FragmentResult r;
-  int rc = FRAG(f)->solve_fci(nsocc, h, dm0, to_opts(opts), fo, eeval, &r, mo_coeff, mo_energy, rdm1_emb, rdm1_mo, civec);
-  if (n_iter) *n_iter = r.n_iter;
-  if (scf_cycles) *scf_cycles = r.scf_cycles;
-  FRAG(f)->last_lambda_iters = 0;
-  if (rc < 0) return rc;
-  if (e_frag) { e_frag[0] = r.e_frag[0]; e_frag[1] = r.e_frag[1]; e_frag[2] = r.e_frag[2]; }
-  if (e_fci) *e_fci = r.e_scf + r.e_corr_mo;
-  if (e_scf) *e_scf = r.e_scf;
-  if (ebe_hf) *ebe_hf = r.ebe_hf;
+  const int rc = FRAG(f)->solve_fci(nsocc, h, dm0, to_opts(opts), fo, eeval, &r, mo_coeff, mo_energy, rdm1_emb, rdm1_mo, civec);
+  store_result(FRAG(f), r, rc, 0, true, e_frag, e_fci, e_scf, ebe_hf, n_iter, scf_cycles);
   return rc;        // QEMB_OK, or QEMB_WARN_NOCONV with strict_convergence = 0
 }
 int qemb_frag_fci_bytes(int n, int nsocc, int max_space, int64_t* bytes) {

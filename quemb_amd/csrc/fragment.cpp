@@ -425,10 +425,21 @@ class PhasePool {
   int active_ = 0, pending_ = 0, nworkers_ = 0;
   unsigned long long gen_ = 0;
 };
-// fn(f) for every fragment of a batched call: each on the worker thread of fragment f bound to execution context f + 1 (threaded), or one after the other; the
-// first failure (in fragment order) is the call's status and error text
+// A batched call: its execution contexts, whether the fragments run side by side, the worker pool and the per-fragment statuses.  per_fragment(fn) runs fn(f) for
+// every fragment -- each on the worker thread of fragment f bound to execution context f + 1 (threaded), or one after the other -- and folds what they return:
+// the first failure (in fragment order) is the call's status and error text, else the last warning
 struct Fanout {
-  int F; bool threaded; PhasePool* pool; std::vector<int>& rc; std::vector<std::string>& msg;
+  int F; bool threaded = false; PhasePool* pool = nullptr; std::vector<int> rc; std::vector<std::string> msg;
+  explicit Fanout(int F_) : F(F_), rc(F_, 0), msg(F_) {}
+  ~Fanout() { if (pool) pool->release(); }
+  int init(bool use_pool) {
+    const int have = dev_ctx_count(F + 1);
+    if (have < 0) return have;
+    // a backend with a single execution context (the scalar mock of tests/hostcheck) runs the per-fragment phases one after the other
+    threaded = have >= F + 1 && F > 1;
+    if (threaded && use_pool) pool = PhasePool::acquire(F);
+    return 0;
+  }
   template <class Fn> int operator()(Fn fn) {
     if (threaded) {
       auto body = [&](int f) {
@@ -445,9 +456,10 @@ struct Fanout {
     } else {
       for (int f = 0; f < F; ++f) { rc[f] = fn(f); if (rc[f] != 0) msg[f] = last_error(); }
     }
-    int worst = 0;
-    for (int f = 0; f < F; ++f) if (rc[f] < 0 && worst == 0) { worst = rc[f]; set_error("fragment " + std::to_string(f) + ": " + msg[f]); }
-    return worst;
+    int status = 0;
+    for (int f = 0; f < F; ++f) if (rc[f] < 0) { set_error("fragment " + std::to_string(f) + ": " + msg[f]); return rc[f]; }
+    for (int f = 0; f < F; ++f) if (rc[f] > 0) { status = rc[f]; set_error("fragment " + std::to_string(f) + ": " + msg[f]); }
+    return status;
   }
 };
 }  // namespace
@@ -461,16 +473,10 @@ int Fragment::solve_batch(const std::vector<Fragment*>& frs, const std::vector<i
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_start = now();
   res.assign(F, FragmentResult());
-  const int have = dev_ctx_count(F + 1);
-  if (have < 0) return have;
-  // a backend with a single execution context (the scalar mock of tests/hostcheck) runs the per-fragment phases one after the other
-  const bool threaded = have >= F + 1 && F > 1;
-  std::vector<int> rc(F, 0);
-  std::vector<std::string> msg(F);
   static const bool pool_on = !(std::getenv("QEMB_PHASE_POOL") && std::atoi(std::getenv("QEMB_PHASE_POOL")) == 0);      // (0: a std::thread per fragment and phase, for A/B runs)
-  PhasePool* pool = (threaded && pool_on) ? PhasePool::acquire(F) : nullptr;
-  struct PoolRelease { PhasePool* p; ~PoolRelease() { if (p) p->release(); } } pool_guard{pool};
-  Fanout per_fragment{F, threaded, pool, rc, msg};
+  Fanout per_fragment(F);
+  QTRY(per_fragment.init(pool_on));
+  const bool threaded = per_fragment.threaded;
   // Before the iterations: the fragment RHF per fragment (host round trips inside), then MO integrals + CCSD set-up + starting amplitudes.  The latter is a pure
   // launch sequence (~60 launches per small fragment) and CAN be recorded as a tape per fragment and run merged on the home stream like the iterations
   // (QEMB_TAPE_PREPHASE=1).  Measured in round 5 and left off: recording the sequence anew every sweep (stream capture + node queries) and running the merged
@@ -527,30 +533,31 @@ int Fragment::solve_batch(const std::vector<Fragment*>& frs, const std::vector<i
     for (size_t k = 0; k < idx.size(); ++k) { res[idx[k]].e_corr_mo = e[k]; res[idx[k]].n_iter = nit[k]; res[idx[k]].ccsd_converged = conv[k] != 0; }
   }
   const double t_lock_done = now();
-  int warn = 0;
-  std::vector<int> rc_end(F, 0);
-  const int worst = per_fragment([&](int f) {
-    rc_end[f] = frs[f]->solve_end(outs[f].mo_coeff, outs[f].mo_energy, outs[f].rdm1_emb, outs[f].rdm1_mo, outs[f].t1, outs[f].t2);
-    return rc_end[f];
-  });
+  const int rc = per_fragment([&](int f) { return frs[f]->solve_end(outs[f].mo_coeff, outs[f].mo_energy, outs[f].rdm1_emb, outs[f].rdm1_mo, outs[f].t1, outs[f].t2); });
   if (trace) std::fprintf(stderr, "[qemb batch] %d fragments: begin %.2f ms (RHF <= %.2f, integrals + set-up <= %.2f, recording <= %.2f), lock-step iterations %.2f ms (tapes %.2f, post %.2f), end %.2f ms\n", F,
                           t_begin_done - t_start, *std::max_element(ms_scf.begin(), ms_scf.end()), *std::max_element(ms_cc.begin(), ms_cc.end()), *std::max_element(ms_capture.begin(), ms_capture.end()),
                           t_lock_done - t_begin_done, stats ? stats->ms_tapes : 0.0, stats ? stats->ms_post : 0.0, now() - t_lock_done);
-  if (worst) return worst;
-  for (int f = 0; f < F; ++f) if (rc_end[f] > 0) { warn = rc_end[f]; set_error("fragment " + std::to_string(f) + ": " + msg[f]); }
-  return warn;
+  return rc;
 }
 
 int Fragment::solve_begin(int o, const double* h, const double* dm0, const FragmentOptions& opt, int eeval, FragmentResult* res) {
   QTRY(solve_begin_scf(o, h, dm0, opt, eeval, res));
   return solve_begin_cc(false);
 }
+// every solver refuses an energy evaluation without the static data before its fragment RHF
+int Fragment::check_energy_data(int eeval) const {
+  if (eeval && (h1_.empty() || veff0_.empty())) { set_error("Fragment: set_energy_data(h1, veff0, ...) before an energy evaluation"); return QEMB_ERR_ARG; }
+  return 0;
+}
+// what a solver reports when it has no correlated step to run (no virtual orbitals), and until its own step fills them in
+static void mean_field_result(FragmentResult* res) { res->e_corr_mo = 0.0; res->n_iter = 0; res->ccsd_converged = true; res->lambda_iters = 0; }
 int Fragment::solve_begin_scf(int o, const double* h, const double* dm0, const FragmentOptions& opt, int eeval, FragmentResult* res) {
   sp_ = SolvePending();
   sp_.o = o; sp_.opt = opt; sp_.eeval = eeval; sp_.res = res;
   last_route_factor_ = false;
   if (!has_eris()) { set_error("Fragment: ERIs not set"); return QEMB_ERR_ARG; }
   if (o <= 0 || o > n_) { set_error("Fragment: need 0 < nsocc <= n"); return QEMB_ERR_ARG; }
+  QTRY(check_energy_data(eeval));
   const int n = n_, v = n - o;
   // nsocc == n: an embedding space without virtual orbitals.  PySCF's CCSD then has empty amplitude arrays and returns E_corr = 0; the
   // sweep body needs the mean-field results only (density = 2 I in any orthonormal basis, no correlation contribution to the energies).
@@ -585,7 +592,7 @@ int Fragment::solve_begin_cc(bool defer_energy) {
   FragmentResult* res = sp_.res;
   if (sp_.no_virtuals) {
     sp_.X1.release();
-    res->e_corr_mo = 0.0; res->n_iter = 0; res->ccsd_converged = true; res->lambda_iters = 0;
+    mean_field_result(res);
     return 0;
   }
   dev_alloc_trace_begin();
@@ -646,14 +653,42 @@ void Fragment::retire_solver() {
   cc_.reset();
 }
 
-// get_frag_energy (helper.py:286-339) from the embedding-basis density and the contracted two-body pieces -- Z1, Z2 (energy_intermediates of the CCSD or the MP2
-// solver), or Imat of the relaxed path -- and update_ebe_hf: the host tail every correlated solve of a fragment shares
-int Fragment::frag_energies(int o, const std::vector<double>& C, const std::vector<double>& rdm, const std::vector<double>& hfdm, const std::vector<double>& Z1,
-                            const std::vector<double>& Z2, const std::vector<double>* Imat, FragmentResult* res, const std::vector<double>* e2_sites) {
-  const int n = n_, v = n - o;
+// ---- the tail every correlated solve of a fragment shares: the solver hands finish_solve its MO-basis 1-RDM and its per-site two-body energies
+// hf_dm = Co Co^T
+static std::vector<double> hf_density(int n, int o, const std::vector<double>& C) {
+  std::vector<double> hfdm((size_t)n * n, 0.0);
+  for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int i = 0; i < o; ++i) s += C[(size_t)p * n + i] * C[(size_t)q * n + i]; hfdm[(size_t)p * n + q] = s; }
+  return hfdm;
+}
+// The per-site two-body energies e2_P of get_frag_energy (helper.py:286-339), P < nf, from what each solver contracts on the device:
+// Z1, Z2 (energy_intermediates of the CCSD or the MP2 solver): e2_P = 1/2 (sum_i C[P,i] Z1[i,P] + sum_a C[P,o+a] Z2[a,P])
+static std::vector<double> e2_from_Z(int n, int o, int nf, const std::vector<double>& C, const std::vector<double>& Z1, const std::vector<double>& Z2) {
+  std::vector<double> e2((size_t)nf, 0.0);
+  for (int P = 0; P < nf; ++P) {
+    double s2 = 0;
+    for (int i = 0; i < o; ++i) s2 += C[(size_t)P * n + i] * Z1[(size_t)i * nf + P];
+    for (int a = 0; a < n - o; ++a) s2 += C[(size_t)P * n + o + a] * Z2[(size_t)a * nf + P];
+    e2[P] = 0.5 * s2;
+  }
+  return e2;
+}
+// Imat of the relaxed CCSD path: e2_P = 1/4 sum_p' C[P,p'] I[p',P]  (cc_lambda.h)
+static std::vector<double> e2_from_Imat(int n, int nf, const std::vector<double>& C, const std::vector<double>& Imat) {
+  std::vector<double> e2((size_t)nf, 0.0);
+  for (int P = 0; P < nf; ++P) {
+    double s2 = 0;
+    for (int q = 0; q < n; ++q) s2 += C[(size_t)P * n + q] * Imat[(size_t)q * nf + P];
+    e2[P] = 0.25 * s2;
+  }
+  return e2;
+}
+
+// get_frag_energy (helper.py:286-339) from the embedding-basis density and the per-site two-body energies, and update_ebe_hf
+int Fragment::frag_energies(const std::vector<double>& rdm, const std::vector<double>& hfdm, const std::vector<double>& e2, FragmentResult* res) {
+  const int n = n_;
   const int64_t n2 = (int64_t)n * n;
   std::vector<double> J((size_t)n2), K((size_t)n2);
-  std::vector<double> e1((size_t)nf_, 0.0), e2((size_t)nf_, 0.0), ec((size_t)nf_, 0.0);
+  std::vector<double> e1((size_t)nf_, 0.0), ec((size_t)nf_, 0.0);
   for (int P = 0; P < nf_; ++P) {
     double s1 = 0, sc = 0;
     for (int Q = 0; Q < n; ++Q) {
@@ -661,16 +696,6 @@ int Fragment::frag_energies(int o, const std::vector<double>& C, const std::vect
       s1 += h1_[(size_t)P * n + Q] * d; sc += veff0_[(size_t)P * n + Q] * d;
     }
     e1[P] = s1; ec[P] = sc;
-    double s2 = 0;
-    if (e2_sites) { e2[P] = (*e2_sites)[(size_t)P]; continue; }      // (the FCI path contracts its 2-RDM on the device: one value per fragment site)
-    if (Imat) {   // e2_P = 1/4 sum_p' C[P,p'] I[p',P]  (cc_lambda.h)
-      for (int q = 0; q < n; ++q) s2 += C[(size_t)P * n + q] * (*Imat)[(size_t)q * nf_ + P];
-      e2[P] = 0.25 * s2;
-      continue;
-    }
-    for (int i = 0; i < o; ++i) s2 += C[(size_t)P * n + i] * Z1[(size_t)i * nf_ + P];
-    for (int a = 0; a < v; ++a) s2 += C[(size_t)P * n + o + a] * Z2[(size_t)a * nf_ + P];
-    e2[P] = 0.5 * s2;
   }
   res->e_frag[0] = res->e_frag[1] = res->e_frag[2] = 0.0;
   for (int c : centers_) { res->e_frag[0] += weight_ * e1[c]; res->e_frag[1] += weight_ * e2[c]; res->e_frag[2] += weight_ * ec[c]; }
@@ -692,6 +717,46 @@ int Fragment::frag_energies(int o, const std::vector<double>& C, const std::vect
   return 0;
 }
 
+// After a solver's correlated step: rdm_emb = C rdm1_mo C^T / 2 (solver.py:496-505), the outputs, the energies, and what rdm2() needs of this solve.
+// dm is the solver's MO-basis 1-RDM (n x n, host); e2 its per-site two-body energies (read with eeval only).  The back-rotation has two forms:
+//   t1 given (o x v, host; dm = [[2 I, t1], [t1^T, 0]]): Co Co^T + (Co t1 Cv^T + Cv t1^T Co^T)/2 on the host -- no device call in the end phase of a lock-step sweep;
+//   otherwise: two products with the resident orbitals on the device, symmetrised on the host.
+int Fragment::finish_solve(const std::vector<double>* t1, const std::vector<double>& dm, const std::vector<double>& e2, int kind, bool relaxed, bool unconverged,
+                           double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo) {
+  const int o = sp_.o, n = n_, v = n - o;
+  const int64_t n2 = (int64_t)n * n;
+  const std::vector<double>& C = sp_.C;
+  const std::vector<double> hfdm = hf_density(n, o, C);
+  std::vector<double> rdm((size_t)n2, 0.0);
+  if (t1) {
+    std::vector<double> X((size_t)n * v, 0.0);
+    for (int p = 0; p < n; ++p) for (int a = 0; a < v; ++a) { double s = 0; for (int i = 0; i < o; ++i) s += C[(size_t)p * n + i] * (*t1)[(size_t)i * v + a]; X[(size_t)p * v + a] = s; }
+    for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int a = 0; a < v; ++a) s += X[(size_t)p * v + a] * C[(size_t)q * n + o + a]; rdm[(size_t)p * n + q] = s; }
+    for (int p = 0; p < n; ++p) for (int q = 0; q <= p; ++q) {
+      const double sym = 0.5 * (rdm[(size_t)p * n + q] + rdm[(size_t)q * n + p]);
+      rdm[(size_t)p * n + q] = rdm[(size_t)q * n + p] = hfdm[(size_t)p * n + q] + sym;
+    }
+  } else if (v > 0) {
+    DBuf D, T, R;
+    QTRY(D.alloc(n2)); QTRY(T.alloc(n2)); QTRY(R.alloc(n2));
+    QTRY(dev_h2d(D, dm.data(), sizeof(double) * n2));
+    QTRY(gemm_nn(n, n, n, 1.0, C_, D, 0.0, T));
+    QTRY(gemm_nt(n, n, n, 0.5, T, C_, 0.0, R));
+    QTRY(dev_d2h(rdm.data(), R, sizeof(double) * n2));
+    for (int p = 0; p < n; ++p) for (int q = 0; q < p; ++q) { const double sym = 0.5 * (rdm[(size_t)p * n + q] + rdm[(size_t)q * n + p]); rdm[(size_t)p * n + q] = rdm[(size_t)q * n + p] = sym; }
+  } else rdm = hfdm;      // no virtual orbitals: dm = 2 I
+  if (rdm1_mo) std::memcpy(rdm1_mo, dm.data(), sizeof(double) * n2);
+  if (rdm1_emb) std::memcpy(rdm1_emb, rdm.data(), sizeof(double) * n2);
+  if (mo_coeff) std::memcpy(mo_coeff, C.data(), sizeof(double) * n2);
+  if (mo_energy) std::memcpy(mo_energy, sp_.eps.data(), sizeof(double) * n);
+  if (sp_.eeval) QTRY(frag_energies(rdm, hfdm, e2, sp_.res));
+  // the next sweep may drive this fragment from a host thread bound to ANOTHER execution context (stream): the kept amplitudes,
+  // multipliers and orbitals must be complete before this call returns (no inter-stream ordering exists otherwise)
+  QTRY(dev_sync());
+  last_kind_ = kind; last_o_ = o; last_relaxed_ = relaxed;
+  return unconverged ? QEMB_WARN_NOCONV : 0;
+}
+
 int Fragment::solve_end(double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* t1_out, double* t2_out) {
   const int o = sp_.o, n = n_, v = n - o, eeval = sp_.eeval;
   const FragmentOptions& opt = sp_.opt;
@@ -699,24 +764,22 @@ int Fragment::solve_end(double* mo_coeff, double* mo_energy, double* rdm1_emb, d
   const bool no_virtuals = sp_.no_virtuals;
   bool unconverged = sp_.unconverged;
   const int64_t n2 = (int64_t)n * n;
-  const std::vector<double>& C = sp_.C; const std::vector<double>& eps = sp_.eps;
   if (!no_virtuals && !res->ccsd_converged) {
     set_error("CCSD did not converge in max_cycle iterations");
     if (opt.strict) return QEMB_ERR_NOCONV;
     unconverged = true;
   }
-  // ---- amplitudes to the host as requested; unrelaxed 1-RDM (depends on t1 only)
+  // ---- amplitudes to the host as requested
   std::vector<double> t1((size_t)o * v);
   if (!no_virtuals) QTRY(dev_d2h(t1.data(), cc_->t1(), sizeof(double) * o * v));
   if (t1_out && !t1.empty()) std::memcpy(t1_out, t1.data(), sizeof(double) * o * v);
   if (t2_out && !no_virtuals) QTRY(dev_d2h(t2_out, cc_->t2(), sizeof(double) * (int64_t)o * o * v * v));
-  // ---- relax_density: Lambda equations, response 1-RDM and the contraction of the response 2-RDM with the fragment ERIs
-  std::vector<double> dm1r, Imat;
+  std::vector<double> dm((size_t)n2, 0.0), e2;
   if (opt.relax_density && no_virtuals) {
-    dm1r.assign((size_t)n2, 0.0);
-    for (int i = 0; i < n; ++i) dm1r[(size_t)i * n + i] = 2.0;
-    if (eeval) Imat.assign((size_t)n * nf_, 0.0);
+    for (int i = 0; i < n; ++i) dm[(size_t)i * n + i] = 2.0;
+    if (eeval) e2.assign((size_t)nf_, 0.0);
   } else if (opt.relax_density) {
+    // ---- Lambda equations, response 1-RDM and the contraction of the response 2-RDM with the fragment ERIs
     CcLambda lam(*cc_);
     QTRY(lam.setup());
     if (opt.warm_start && z_prev_.p && z_prev_o_ == o) QTRY(lam.set_guess(z_prev_));
@@ -727,47 +790,24 @@ int Fragment::solve_end(double* mo_coeff, double* mo_energy, double* rdm1_emb, d
       if (opt.strict) return QEMB_ERR_NOCONV;
       unconverged = true;
     }
-    dm1r.assign((size_t)n2, 0.0);
+    std::vector<double> Imat;
     if (eeval) Imat.assign((size_t)n * nf_, 0.0);
-    QTRY(lam.densities(dm1r.data(), eeval ? cc_->integrals().T34.p : nullptr, nf_, eeval ? Imat.data() : nullptr));
+    QTRY(lam.densities(dm.data(), eeval ? cc_->integrals().T34.p : nullptr, nf_, eeval ? Imat.data() : nullptr));
+    if (eeval) e2 = e2_from_Imat(n, nf_, sp_.C, Imat);
     if (opt.keep_amplitudes || opt.warm_start) {
       QTRY(z_prev_.alloc(lam.n_amp()));
       QTRY(dcopy(lam.n_amp(), lam.z(), z_prev_));
       z_prev_o_ = o;
     }
-  }
-  // rdm1_mo = [[2 I, t1], [t1^T, 0]]  (shared/external/ccsd_rdm.py:10-20)
-  if (rdm1_mo && opt.relax_density) {
-    std::memcpy(rdm1_mo, dm1r.data(), sizeof(double) * n2);
-  } else if (rdm1_mo) {
-    std::memset(rdm1_mo, 0, sizeof(double) * n2);
-    for (int i = 0; i < o; ++i) rdm1_mo[(size_t)i * n + i] = 2.0;
-    for (int i = 0; i < o; ++i) for (int a = 0; a < v; ++a) { rdm1_mo[(size_t)i * n + o + a] = t1[(size_t)i * v + a]; rdm1_mo[(size_t)(o + a) * n + i] = t1[(size_t)i * v + a]; }
-  }
-  // rdm_emb = C rdm1 C^T / 2 = Co Co^T + (Co t1 Cv^T + Cv t1^T Co^T)/2   (solver.py:496-505)
-  std::vector<double> rdm((size_t)n2, 0.0), hfdm((size_t)n2, 0.0), X((size_t)n * v, 0.0);
-  for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int i = 0; i < o; ++i) s += C[(size_t)p * n + i] * C[(size_t)q * n + i]; hfdm[(size_t)p * n + q] = s; }
-  for (int p = 0; p < n; ++p) for (int a = 0; a < v; ++a) { double s = 0; for (int i = 0; i < o; ++i) s += C[(size_t)p * n + i] * t1[(size_t)i * v + a]; X[(size_t)p * v + a] = s; }
-  for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int a = 0; a < v; ++a) s += X[(size_t)p * v + a] * C[(size_t)q * n + o + a]; rdm[(size_t)p * n + q] = s; }
-  for (int p = 0; p < n; ++p) for (int q = 0; q <= p; ++q) {
-    const double sym = 0.5 * (rdm[(size_t)p * n + q] + rdm[(size_t)q * n + p]);
-    rdm[(size_t)p * n + q] = rdm[(size_t)q * n + p] = hfdm[(size_t)p * n + q] + sym;
-  }
-  if (opt.relax_density) {   // rdm_emb = C dm1 C^T / 2 with the full response density
-    std::vector<double> Y((size_t)n2, 0.0);
-    for (int p = 0; p < n; ++p) for (int r = 0; r < n; ++r) { const double c = C[(size_t)p * n + r]; for (int q = 0; q < n; ++q) Y[(size_t)p * n + q] += c * dm1r[(size_t)r * n + q]; }
-    for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double t = 0; for (int r = 0; r < n; ++r) t += Y[(size_t)p * n + r] * C[(size_t)q * n + r]; rdm[(size_t)p * n + q] = 0.5 * t; }
-  }
-  if (rdm1_emb) std::memcpy(rdm1_emb, rdm.data(), sizeof(double) * n2);
-  if (mo_coeff) std::memcpy(mo_coeff, C.data(), sizeof(double) * n2);
-  if (mo_energy) std::memcpy(mo_energy, eps.data(), sizeof(double) * n);
-  // ---- energies
-  if (eeval) {
-    if (h1_.empty() || veff0_.empty()) { set_error("Fragment: set_energy_data(h1, veff0, ...) before an energy evaluation"); return QEMB_ERR_ARG; }
-    std::vector<double> Z1, Z2;
-    if (!opt.relax_density && !no_virtuals) QTRY(cc_->energy_intermediates(Z1, Z2));
-    if (no_virtuals) { Z1.assign((size_t)o * nf_, 0.0); Z2.clear(); }
-    QTRY(frag_energies(o, C, rdm, hfdm, Z1, Z2, opt.relax_density ? &Imat : nullptr, res));
+  } else {
+    // unrelaxed: rdm1_mo = [[2 I, t1], [t1^T, 0]]  (shared/external/ccsd_rdm.py:10-20)
+    for (int i = 0; i < o; ++i) dm[(size_t)i * n + i] = 2.0;
+    for (int i = 0; i < o; ++i) for (int a = 0; a < v; ++a) { dm[(size_t)i * n + o + a] = t1[(size_t)i * v + a]; dm[(size_t)(o + a) * n + i] = t1[(size_t)i * v + a]; }
+    if (eeval) {
+      std::vector<double> Z1((size_t)o * nf_, 0.0), Z2;
+      if (!no_virtuals) QTRY(cc_->energy_intermediates(Z1, Z2));
+      e2 = e2_from_Z(n, o, nf_, sp_.C, Z1, Z2);
+    }
   }
   // ---- keep amplitudes for a warm start of the next sweep
   if ((opt.keep_amplitudes || opt.warm_start) && !no_virtuals) {
@@ -776,12 +816,9 @@ int Fragment::solve_end(double* mo_coeff, double* mo_energy, double* rdm1_emb, d
     QTRY(dcopy(na, cc_->t1(), t_prev_));
     t_prev_o_ = o;
   }
-  // the next sweep may drive this fragment from a host thread bound to ANOTHER execution context (stream): the kept amplitudes,
-  // multipliers and orbitals must be complete before this call returns (no inter-stream ordering exists otherwise)
-  QTRY(dev_sync());
+  const int rc = finish_solve(opt.relax_density ? nullptr : &t1, dm, e2, QEMB_RDM2_CCSD, opt.relax_density != 0, unconverged, mo_coeff, mo_energy, rdm1_emb, rdm1_mo);
   retire_solver();
-  last_kind_ = QEMB_RDM2_CCSD; last_o_ = o; last_relaxed_ = opt.relax_density != 0;
-  return unconverged ? QEMB_WARN_NOCONV : 0;
+  return rc;
 }
 
 // ---- solver == "MP2": everything after the fragment RHF is a handful of products with the factor and one pass over o^2 v^2 (mp2.cpp)
@@ -789,11 +826,8 @@ int Fragment::solve_mp2(int o, const double* h, const double* dm0, const Fragmen
                         double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* t2_out) {
   QTRY(solve_begin_scf(o, h, dm0, opt, eeval, res));
   const int n = n_, v = n - o;
-  const int64_t n2 = (int64_t)n * n;
-  const std::vector<double>& C = sp_.C;
-  if (eeval && (h1_.empty() || veff0_.empty())) { set_error("Fragment: set_energy_data(h1, veff0, ...) before an energy evaluation"); return QEMB_ERR_ARG; }
-  res->e_corr_mo = 0.0; res->n_iter = 0; res->ccsd_converged = true; res->lambda_iters = 0;
-  std::vector<double> doo((size_t)o * o, 0.0), dvv, Z1, Z2;
+  mean_field_result(res);
+  std::vector<double> doo((size_t)o * o, 0.0), dvv, Z1((size_t)o * nf_, 0.0), Z2;
   if (v > 0) {
     Mp2Solver mp;
     if (use_factor_route()) {
@@ -810,34 +844,14 @@ int Fragment::solve_mp2(int o, const double* h, const double* dm0, const Fragmen
     if (t2_out) QTRY(dev_d2h(t2_out, mp.t2(), sizeof(double) * (int64_t)o * o * v * v));
     QTRY(mp.rdm1_blocks(doo, dvv));
     if (eeval) QTRY(mp.energy_intermediates(Z1, Z2));
-  } else {      // no virtual orbitals: the mean-field results, as the CCSD path
-    sp_.X1.release();
-    if (eeval) Z1.assign((size_t)o * nf_, 0.0);
-  }
-  // rdm1_mo = [[2 I + doo + doo^T, 0], [0, dvv + dvv^T]]   (PySCF mp2.make_rdm1)
-  std::vector<double> dm((size_t)n2, 0.0);
-  for (int i = 0; i < o; ++i) for (int j = 0; j < o; ++j) dm[(size_t)i * n + j] = doo[(size_t)i * o + j] + doo[(size_t)j * o + i] + (i == j ? 2.0 : 0.0);
-  for (int a = 0; a < v; ++a) for (int b = 0; b < v; ++b) dm[(size_t)(o + a) * n + o + b] = dvv[(size_t)a * v + b] + dvv[(size_t)b * v + a];
-  if (rdm1_mo) std::memcpy(rdm1_mo, dm.data(), sizeof(double) * n2);
-  // rdm_emb = C rdm1_mo C^T / 2   (solver.py:496-505); hf_dm = Co Co^T
-  std::vector<double> rdm((size_t)n2, 0.0), hfdm((size_t)n2, 0.0);
-  for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int i = 0; i < o; ++i) s += C[(size_t)p * n + i] * C[(size_t)q * n + i]; hfdm[(size_t)p * n + q] = s; }
-  if (v > 0) {
-    DBuf D, T, R;
-    QTRY(D.alloc(n2)); QTRY(T.alloc(n2)); QTRY(R.alloc(n2));
-    QTRY(dev_h2d(D, dm.data(), sizeof(double) * n2));
-    QTRY(gemm_nn(n, n, n, 1.0, C_, D, 0.0, T));
-    QTRY(gemm_nt(n, n, n, 0.5, T, C_, 0.0, R));
-    QTRY(dev_d2h(rdm.data(), R, sizeof(double) * n2));
-    for (int p = 0; p < n; ++p) for (int q = 0; q < p; ++q) { const double sym = 0.5 * (rdm[(size_t)p * n + q] + rdm[(size_t)q * n + p]); rdm[(size_t)p * n + q] = rdm[(size_t)q * n + p] = sym; }
-  } else rdm = hfdm;
-  if (rdm1_emb) std::memcpy(rdm1_emb, rdm.data(), sizeof(double) * n2);
-  if (mo_coeff) std::memcpy(mo_coeff, C.data(), sizeof(double) * n2);
-  if (mo_energy) std::memcpy(mo_energy, sp_.eps.data(), sizeof(double) * n);
-  if (eeval) QTRY(frag_energies(o, C, rdm, hfdm, Z1, Z2, nullptr, res));
-  QTRY(dev_sync());      // (the next sweep may drive this fragment from another execution context, as after solve_end)
-  mp2_dm1_ = std::move(dm); last_kind_ = QEMB_RDM2_MP2; last_o_ = o; last_relaxed_ = false;
-  return sp_.unconverged ? QEMB_WARN_NOCONV : 0;
+  } else sp_.X1.release();      // no virtual orbitals: the mean-field results, as the CCSD path
+  // rdm1_mo = [[2 I + doo + doo^T, 0], [0, dvv + dvv^T]]   (PySCF mp2.make_rdm1); kept for rdm2(): an MP2 solve keeps no amplitudes to form it from
+  // (written before finish_solve can fail: rdm2() reads it only once finish_solve has set last_kind_, which run_scf cleared through forget_solve())
+  mp2_dm1_.assign((size_t)n * n, 0.0);
+  for (int i = 0; i < o; ++i) for (int j = 0; j < o; ++j) mp2_dm1_[(size_t)i * n + j] = doo[(size_t)i * o + j] + doo[(size_t)j * o + i] + (i == j ? 2.0 : 0.0);
+  for (int a = 0; a < v; ++a) for (int b = 0; b < v; ++b) mp2_dm1_[(size_t)(o + a) * n + o + b] = dvv[(size_t)a * v + b] + dvv[(size_t)b * v + a];
+  const std::vector<double> e2 = eeval ? e2_from_Z(n, o, nf_, sp_.C, Z1, Z2) : std::vector<double>();
+  return finish_solve(nullptr, mp2_dm1_, e2, QEMB_RDM2_MP2, false, sp_.unconverged, mo_coeff, mo_energy, rdm1_emb, rdm1_mo);
 }
 
 // ---- solver == "FCI-hip": the fragment RHF, then the exact ground state of the embedding Hamiltonian in the determinant basis (fci.cpp)
@@ -861,13 +875,26 @@ int Fragment::fci_mo_integrals(const std::vector<double>& C, DBuf& Vao, DBuf& CC
   return dev_sync();      // (Tm and a transient block go back to the pool on return)
 }
 
+// e2_P = 1/2 sum_qrs Gamma_emb[P,q,r,s] (Pq|rs), Gamma_emb = (C x C) Gamma (C x C)^T the cumulant in the embedding basis; rows P < n_f only
+int Fragment::fci_e2_sites(const double* CC, const double* G2, const double* Vao, std::vector<double>& e2) {
+  const int64_t n2 = (int64_t)n_ * n_, n3 = n2 * n_;
+  DBuf Tm, Ge, ed;
+  QTRY(Tm.alloc(n2 * n2)); QTRY(Ge.alloc(n2 * n2)); QTRY(ed.alloc(nf_));
+  QTRY(gemm_nn(n2, n2, n2, 1.0, CC, G2, 0.0, Tm));
+  QTRY(gemm_nt(n2, n2, n2, 1.0, Tm, CC, 0.0, Ge));
+  for (int P = 0; P < nf_; ++P) QTRY(dev_dot(n3, Ge.p + P * n3, Vao + P * n3, ed.p + P));
+  QTRY(dev_d2h(e2.data(), ed, sizeof(double) * nf_));
+  for (double& e : e2) e *= 0.5;
+  return 0;
+}
+
 int Fragment::solve_fci(int o, const double* h, const double* dm0, const FragmentOptions& opt, const FciOptions& fopt, int eeval, FragmentResult* res,
                         double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* civec) {
   const int n = n_, v = n - o;
   const int64_t n2 = (int64_t)n * n;
   if (n > kFciMaxOrb) { set_error("Fragment::solve_fci: n = " + std::to_string(n) + " embedding orbitals; the determinant-space solver takes at most " + std::to_string(kFciMaxOrb)); return QEMB_ERR_UNSUPPORTED; }
   if (o <= 0 || o > n) { set_error("Fragment: need 0 < nsocc <= n"); return QEMB_ERR_ARG; }
-  if (eeval && (h1_.empty() || veff0_.empty())) { set_error("Fragment: set_energy_data(h1, veff0, ...) before an energy evaluation"); return QEMB_ERR_ARG; }
+  QTRY(check_energy_data(eeval));      // (solve_begin_scf has the check for every solver; here it also keeps its place before the guard)
   {      // the guard: D, G, the Davidson vectors, the tables and the n^4 pieces against what is free (or the fragment's limit), before anything is allocated
     size_t free_b = 0, total_b = 0;
     QTRY(dev_mem_info(&free_b, &total_b));
@@ -885,9 +912,9 @@ int Fragment::solve_fci(int o, const double* h, const double* dm0, const Fragmen
   sp_.X1.release();
   const std::vector<double>& C = sp_.C;
   bool unconverged = sp_.unconverged;
-  res->e_corr_mo = 0.0; res->n_iter = 0; res->ccsd_converged = true; res->lambda_iters = 0;
+  mean_field_result(res);
   fci_c_.release(); fci_residual_ = 0.0;
-  std::vector<double> dm((size_t)n2, 0.0), e2_sites((size_t)nf_, 0.0);
+  std::vector<double> dm((size_t)n2, 0.0), e2((size_t)nf_, 0.0);
   if (v > 0) {
     const FciTables* T = nullptr;
     QTRY(fci_tables(n, o, &T));
@@ -911,39 +938,12 @@ int Fragment::solve_fci(int o, const double* h, const double* dm0, const Fragmen
     DBuf G2;
     if (eeval) QTRY(G2.alloc(n2 * n2));
     QTRY(fci_rdm12(*T, fci_c_, o, dm.data(), eeval ? G2.p : nullptr));
-    if (eeval && nf_ > 0) {      // e2_P = 1/2 sum_qrs Gamma_emb[P,q,r,s] (Pq|rs), Gamma_emb = (C x C) Gamma (C x C)^T the cumulant in the embedding basis; rows P < n_f only
-      DBuf Tm, Ge, ed;
-      QTRY(Tm.alloc(n2 * n2)); QTRY(Ge.alloc(n2 * n2)); QTRY(ed.alloc(nf_));
-      QTRY(gemm_nn(n2, n2, n2, 1.0, CC, G2, 0.0, Tm));
-      QTRY(gemm_nt(n2, n2, n2, 1.0, Tm, CC, 0.0, Ge));
-      const int64_t n3 = n2 * n;
-      for (int P = 0; P < nf_; ++P) QTRY(dev_dot(n3, Ge.p + P * n3, Vao.p + P * n3, ed.p + P));
-      QTRY(dev_d2h(e2_sites.data(), ed, sizeof(double) * nf_));
-      for (double& e : e2_sites) e *= 0.5;
-    }
+    if (eeval && nf_ > 0) QTRY(fci_e2_sites(CC, G2, Vao, e2));
   } else {      // a single determinant: the mean-field results, as the other solvers
     for (int i = 0; i < n; ++i) dm[(size_t)i * n + i] = 2.0;
     if (civec) civec[0] = 1.0;
   }
-  if (rdm1_mo) std::memcpy(rdm1_mo, dm.data(), sizeof(double) * n2);
-  // rdm_emb = C rdm1 C^T / 2 (solver.py:496-505); hf_dm = Co Co^T
-  std::vector<double> rdm((size_t)n2, 0.0), hfdm((size_t)n2, 0.0), Y((size_t)n2, 0.0);
-  for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int i = 0; i < o; ++i) s += C[(size_t)p * n + i] * C[(size_t)q * n + i]; hfdm[(size_t)p * n + q] = s; }
-  if (v > 0) {
-    for (int p = 0; p < n; ++p) for (int r = 0; r < n; ++r) { const double c = C[(size_t)p * n + r]; for (int q = 0; q < n; ++q) Y[(size_t)p * n + q] += c * dm[(size_t)r * n + q]; }
-    for (int p = 0; p < n; ++p) for (int q = 0; q <= p; ++q) {
-      double t = 0, u = 0;
-      for (int r = 0; r < n; ++r) { t += Y[(size_t)p * n + r] * C[(size_t)q * n + r]; u += Y[(size_t)q * n + r] * C[(size_t)p * n + r]; }
-      rdm[(size_t)p * n + q] = rdm[(size_t)q * n + p] = 0.25 * (t + u);
-    }
-  } else rdm = hfdm;
-  if (rdm1_emb) std::memcpy(rdm1_emb, rdm.data(), sizeof(double) * n2);
-  if (mo_coeff) std::memcpy(mo_coeff, C.data(), sizeof(double) * n2);
-  if (mo_energy) std::memcpy(mo_energy, sp_.eps.data(), sizeof(double) * n);
-  if (eeval) QTRY(frag_energies(o, C, rdm, hfdm, std::vector<double>(), std::vector<double>(), nullptr, res, &e2_sites));
-  QTRY(dev_sync());      // (the next sweep may drive this fragment from another execution context, as after solve_end)
-  fci_dm1_ = std::move(dm); last_kind_ = QEMB_RDM2_FCI; last_o_ = o; last_relaxed_ = false;
-  return unconverged ? QEMB_WARN_NOCONV : 0;
+  return finish_solve(nullptr, dm, e2, QEMB_RDM2_FCI, false, unconverged, mo_coeff, mo_energy, rdm1_emb, rdm1_mo);
 }
 
 // ---- Frags.rdm2__ (molbe/solver.py:528): the n^4 tensor of the last solve, written once by one kernel (rdm2_ops.hip)
@@ -1046,22 +1046,11 @@ int Fragment::solve_mp2_batch(const std::vector<Fragment*>& frs, const std::vect
   const int F = (int)frs.size();
   if (F == 0) return 0;
   res.assign(F, FragmentResult());
-  const int have = dev_ctx_count(F + 1);
-  if (have < 0) return have;
-  const bool threaded = have >= F + 1 && F > 1;      // (the scalar mock has one execution context: one fragment after the other)
-  std::vector<int> rc(F, 0), rc_solve(F, 0);
-  std::vector<std::string> msg(F);
-  PhasePool* pool = threaded ? PhasePool::acquire(F) : nullptr;
-  struct PoolRelease { PhasePool* p; ~PoolRelease() { if (p) p->release(); } } pool_guard{pool};
-  Fanout per_fragment{F, threaded, pool, rc, msg};
-  const int worst = per_fragment([&](int f) {
-    rc_solve[f] = frs[f]->solve_mp2(o[f], h[f], dm0[f], opt, eeval, &res[f], outs[f].mo_coeff, outs[f].mo_energy, outs[f].rdm1_emb, outs[f].rdm1_mo, outs[f].t2);
-    return rc_solve[f];
+  Fanout per_fragment(F);
+  QTRY(per_fragment.init(true));
+  return per_fragment([&](int f) {
+    return frs[f]->solve_mp2(o[f], h[f], dm0[f], opt, eeval, &res[f], outs[f].mo_coeff, outs[f].mo_energy, outs[f].rdm1_emb, outs[f].rdm1_mo, outs[f].t2);
   });
-  if (worst) return worst;
-  int warn = 0;
-  for (int f = 0; f < F; ++f) if (rc_solve[f] > 0) { warn = rc_solve[f]; set_error("fragment " + std::to_string(f) + ": " + msg[f]); }
-  return warn;
 }
 
 }  // namespace qemb

@@ -73,7 +73,8 @@ class Fragment {
   int solve(int o, const double* h, const double* dm0, const FragmentOptions& opt, int eeval, FragmentResult* res,
             double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* t1, double* t2);
   // The same in three steps -- everything before the CCSD iterations, (the iterations: cc_->kernel or the lock-step loop of solve_batch),
-  // everything after -- so that several fragments can share the middle step.
+  // everything after -- so that several fragments can share the middle step.  solve_end keeps what belongs to CCSD (amplitudes, Lambda equations, the 1-RDM, the
+  // per-site two-body energies) and ends in finish_solve, the tail it shares with solve_mp2 and solve_fci.
   int solve_begin(int o, const double* h, const double* dm0, const FragmentOptions& opt, int eeval, FragmentResult* res);
   // ... and solve_begin itself in two halves: the fragment RHF (host round trips inside), then MO integrals + CCSD set-up + starting amplitudes -- a pure launch
   // sequence, which solve_batch records as a tape per fragment and runs merged for all fragments (defer_energy: the guess's energy is fetched afterwards)
@@ -138,8 +139,14 @@ class Fragment {
   int scf_operand(DBuf& X1, bool* unpacked);
   int check_df_factor();
   int mo_integrals(int o, int nf, DBuf& X1, bool x1_unpacked, MoIntegrals& ints, bool build_Vl, bool build_T34);
-  int frag_energies(int o, const std::vector<double>& C, const std::vector<double>& rdm, const std::vector<double>& hfdm, const std::vector<double>& Z1,
-                    const std::vector<double>& Z2, const std::vector<double>* Imat, FragmentResult* res, const std::vector<double>* e2_sites = nullptr);
+  // The tail every solver shares (fragment.cpp): after its correlated step a solver hands finish_solve its MO-basis 1-RDM (the rdm1_mo output), its per-site two-body
+  // energies and what rdm2() has to know of the solve; finish_solve forms hf_dm = Co Co^T and rdm1_emb = C rdm1_mo C^T / 2 -- from t1 on the host where the density is
+  // [[2 I, t1], [t1^T, 0]] (unrelaxed CCSD), else by two products on the device --, copies the four outputs, evaluates the energies (frag_energies), waits for the
+  // device and returns the solve's status (QEMB_WARN_NOCONV for an unconverged one)
+  int finish_solve(const std::vector<double>* t1, const std::vector<double>& dm, const std::vector<double>& e2, int kind, bool relaxed, bool unconverged,
+                   double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo);
+  int frag_energies(const std::vector<double>& rdm, const std::vector<double>& hfdm, const std::vector<double>& e2, FragmentResult* res);
+  int check_energy_data(int eeval) const;           // QEMB_ERR_ARG for an energy evaluation without set_energy_data; from solve_begin_scf, which every solver passes
   DBuf df_factor_; int df_naux_ = 0; int mo_route_ = -1; bool last_route_factor_ = false;
   bool have_C_ = false; int c_nocc_ = -1;    // C_ holds the orbitals of a converged earlier solve with c_nocc_ occupied orbitals (the Jacobi eigensolver starts in that basis)
   int n_, nf_, o_ = -1;
@@ -147,7 +154,7 @@ class Fragment {
   std::vector<double> h1_, veff0_, veff_;
   double weight_ = 1.0;
   std::vector<int> centers_;
-  // what solve_begin hands to solve_end
+  // what solve_begin_scf hands to the solver's own step and to finish_solve
   struct SolvePending {
     int o = 0, eeval = 0; FragmentOptions opt; FragmentResult* res = nullptr;
     bool unconverged = false, no_virtuals = false;
@@ -172,12 +179,12 @@ class Fragment {
   int last_kind_ = -1, last_o_ = 0; bool last_relaxed_ = false;
   std::vector<double> mp2_dm1_;
   int64_t rdm2_mem_limit_ = -1;
-  // after an FCI solve: the CI vector (device, ns * ns) and the symmetrised 1-RDM (host)
+  // after an FCI solve: the CI vector (device, ns * ns)
   DBuf fci_c_;
-  std::vector<double> fci_dm1_;
   double fci_residual_ = 0.0;
   int64_t fci_mem_limit_ = -1;
   int fci_mo_integrals(const std::vector<double>& C, DBuf& Vao, DBuf& CC, DBuf& Vmo);
+  int fci_e2_sites(const double* CC, const double* G2, const double* Vao, std::vector<double>& e2);      // the cumulant contracted with the integrals, per fragment site
   void forget_solve() { last_kind_ = -1; }
 };
 

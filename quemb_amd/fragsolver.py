@@ -128,73 +128,42 @@ class DeviceFragment:
 
     # ---- the sweep body -------------------------------------------------------------------------
     def solve(self, nsocc, h, dm0=None, opts: SolverOpts | None = None, eeval=True, want_t2=False):
-        n, o = self.n, int(nsocc)
-        v = n - o
-        h = np.ascontiguousarray(h, dtype=np.float64)
-        dm0 = None if dm0 is None else np.ascontiguousarray(dm0, dtype=np.float64)
-        opts = opts or default_opts(self.lib)
-        out = dict(mo_coeff=np.empty((n, n)), mo_energy=np.empty(n), rdm1_emb=np.empty((n, n)), rdm1_mo=np.empty((n, n)),
-                   t1=np.empty((o, v)), t2=np.empty((o, o, v, v)) if want_t2 else None)
-        e_frag = np.zeros(3)
-        ecorr, escf, ebehf = C.c_double(), C.c_double(), C.c_double()
-        nit, ncyc = C.c_int(), C.c_int()
-        check(self.lib.qemb_frag_solve(self.h, o, h.ctypes.data, _p(dm0), C.byref(opts), int(bool(eeval)),
-                                       out["mo_coeff"].ctypes.data, out["mo_energy"].ctypes.data, out["rdm1_emb"].ctypes.data,
-                                       out["rdm1_mo"].ctypes.data, out["t1"].ctypes.data, _p(out["t2"]), e_frag.ctypes.data,
-                                       C.byref(ecorr), C.byref(escf), C.byref(ebehf), C.byref(nit), C.byref(ncyc)),
-              "qemb_frag_solve", self.lib)
-        nlam = C.c_int()
-        check(self.lib.qemb_frag_lambda_iters(self.h, C.byref(nlam)), "qemb_frag_lambda_iters", self.lib)
-        out.update(e_frag=e_frag, e_corr_mo=ecorr.value, e_scf=escf.value, ebe_hf=ebehf.value, n_iter=nit.value,
-                   scf_cycles=ncyc.value, lambda_iters=nlam.value)
-        return out
+        c = _SolveCall([self], [nsocc], [h], [dm0], opts, eeval, batch=False, t1=True, t2=want_t2)
+        c.call("qemb_frag_solve", ("t1", "t2"))
+        return c.results(lambda_iters=True)[0]
 
     def solve_mp2(self, nsocc, h, dm0=None, opts: SolverOpts | None = None, eeval=True, want_t2=False):
         """solver == "MP2" of be_func (qemb_frag_solve_mp2): fragment RHF -> density-fitted MP2 -> unrelaxed MP2 1-RDM -> fragment energies.
         The dict `solve` returns, with t1 = None and n_iter = 0; of `opts` only scf_*, verbose and strict_convergence are read."""
-        n, o = self.n, int(nsocc)
-        v = n - o
-        h = np.ascontiguousarray(h, dtype=np.float64)
-        dm0 = None if dm0 is None else np.ascontiguousarray(dm0, dtype=np.float64)
-        opts = opts or default_opts(self.lib)
-        out = dict(mo_coeff=np.empty((n, n)), mo_energy=np.empty(n), rdm1_emb=np.empty((n, n)), rdm1_mo=np.empty((n, n)),
-                   t1=None, t2=np.empty((o, o, v, v)) if want_t2 else None)
-        e_frag = np.zeros(3)
-        ecorr, escf, ebehf = C.c_double(), C.c_double(), C.c_double()
-        ncyc = C.c_int()
-        check(self.lib.qemb_frag_solve_mp2(self.h, o, h.ctypes.data, _p(dm0), C.byref(opts), int(bool(eeval)),
-                                           out["mo_coeff"].ctypes.data, out["mo_energy"].ctypes.data, out["rdm1_emb"].ctypes.data,
-                                           out["rdm1_mo"].ctypes.data, _p(out["t2"]), e_frag.ctypes.data,
-                                           C.byref(ecorr), C.byref(escf), C.byref(ebehf), C.byref(ncyc)),
-              "qemb_frag_solve_mp2", self.lib)
-        out.update(e_frag=e_frag, e_corr_mo=ecorr.value, e_scf=escf.value, ebe_hf=ebehf.value, n_iter=0, scf_cycles=ncyc.value, lambda_iters=0)
-        return out
+        c = _SolveCall([self], [nsocc], [h], [dm0], opts, eeval, batch=False, t2=want_t2)
+        c.call("qemb_frag_solve_mp2", ("t2",), n_iter=False)
+        return c.results()[0]
 
     def solve_fci(self, nsocc, h, dm0=None, opts: SolverOpts | None = None, fci_opts: FciOpts | None = None, eeval=True, want_civec=False):
         """solver == "FCI-hip" of be_func (qemb_frag_solve_fci): fragment RHF -> determinant-space FCI on the device -> make_rdm1 -> fragment energies from the cumulant
         of make_rdm2.  The dict `solve` returns with t1 = t2 = None, plus e_fci (the eigenvalue; e_corr_mo = e_fci - e_scf), residual (||H c - E c||_2), n_iter (the
         applications of H) and civec ((ns, ns), row = alpha string; None unless want_civec).  Of `opts` only scf_*, verbose and strict_convergence are read;
         fci_opts None: the defaults of `default_fci_opts`."""
-        n, o = self.n, int(nsocc)
-        h = np.ascontiguousarray(h, dtype=np.float64)
-        dm0 = None if dm0 is None else np.ascontiguousarray(dm0, dtype=np.float64)
-        opts = opts or default_opts(self.lib)
         from math import comb
+        n, o = self.n, int(nsocc)
         ns = comb(n, o) if 0 < o <= n else 1
-        out = dict(mo_coeff=np.empty((n, n)), mo_energy=np.empty(n), rdm1_emb=np.empty((n, n)), rdm1_mo=np.empty((n, n)), t1=None, t2=None,
-                   civec=np.empty((ns, ns)) if want_civec and n <= 16 else None)
-        e_frag = np.zeros(3)
-        efci, escf, ebehf, resid = C.c_double(), C.c_double(), C.c_double(), C.c_double()
-        nit, ncyc = C.c_int(), C.c_int()
-        check(self.lib.qemb_frag_solve_fci(self.h, o, h.ctypes.data, _p(dm0), C.byref(opts), None if fci_opts is None else C.byref(fci_opts), int(bool(eeval)),
-                                           out["mo_coeff"].ctypes.data, out["mo_energy"].ctypes.data, out["rdm1_emb"].ctypes.data,
-                                           out["rdm1_mo"].ctypes.data, _p(out["civec"]), e_frag.ctypes.data,
-                                           C.byref(efci), C.byref(escf), C.byref(ebehf), C.byref(nit), C.byref(ncyc)),
-              "qemb_frag_solve_fci", self.lib)
+        c = _SolveCall([self], [nsocc], [h], [dm0], opts, eeval, batch=False)
+        c.outs[0]["civec"] = np.empty((ns, ns)) if want_civec and n <= 16 else None
+        c.call("qemb_frag_solve_fci", ("civec",), after_opts=(None if fci_opts is None else C.byref(fci_opts),))
+        resid = C.c_double()
         check(self.lib.qemb_frag_fci_residual(self.h, C.byref(resid)), "qemb_frag_fci_residual", self.lib)
-        out.update(e_frag=e_frag, e_fci=efci.value, e_corr_mo=efci.value - escf.value, e_scf=escf.value, ebe_hf=ebehf.value, n_iter=nit.value,
-                   scf_cycles=ncyc.value, lambda_iters=0, residual=resid.value)
+        out = c.results()[0]
+        out.update(e_fci=c.e[0], e_corr_mo=c.e[0] - c.e_scf[0], residual=resid.value)      # (this entry reports the eigenvalue where the others report e_corr_mo)
         return out
+
+    def solve_as(self, solver, nsocc, h, dm0=None, opts=None, eeval=True, want_amplitudes=False, fci_opts=None):
+        """the solve of be_func's solver literal (one of SOLVERS): `solve`, `solve_mp2` or `solve_fci`.  want_amplitudes asks for t2 (the CI vector of "FCI-hip");
+        fci_opts is read by "FCI-hip" alone"""
+        if solver not in SOLVERS:
+            raise ValueError("Solver not implemented")
+        if solver == "FCI-hip":
+            return self.solve_fci(nsocc, h, dm0, opts=opts, fci_opts=fci_opts, eeval=eeval, want_civec=want_amplitudes)
+        return (self.solve_mp2 if solver == "MP2" else self.solve)(nsocc, h, dm0, opts=opts, eeval=eeval, want_t2=want_amplitudes)
 
     def set_fci_mem_limit(self, nbytes):
         """device bytes `solve_fci` of this fragment may take (qemb_frag_fci_mem_limit); negative: whatever is free"""
@@ -359,6 +328,52 @@ def fci_links(n, nsocc, lib=None):
     return strings, links
 
 
+class _SolveCall:
+    """What the solve entries of the library share on this side: h / dm0 / opts as they are handed over, the output dict of every fragment, the result scalars
+    (__init__), the call itself (call) and the dicts filled from it (results).  batch: the entry takes arrays over the fragments (qemb_frag_solve_batch,
+    _mp2_batch) where the single entries take one fragment's pointers; the result scalars are arrays of the call's length either way.  t1 / t2: whether the
+    dicts carry those amplitudes."""
+
+    def __init__(self, frags, nsoccs, hs, dm0s, opts, eeval, batch, t1=False, t2=False):
+        F = len(frags)
+        self.frags, self.batch, self.lib = frags, batch, frags[0].lib
+        self.opts = opts or default_opts(self.lib)
+        self.eeval = int(bool(eeval))
+        self.ns = [int(o) for o in nsoccs]
+        self.hs = [np.ascontiguousarray(h, dtype=np.float64) for h in hs]
+        self.dm0s = [None if d is None else np.ascontiguousarray(d, dtype=np.float64) for d in (dm0s if dm0s is not None else [None] * F)]
+        self.outs = []
+        for fr, o in zip(frags, self.ns):
+            n, v = fr.n, fr.n - o
+            self.outs.append(dict(mo_coeff=np.empty((n, n)), mo_energy=np.empty(n), rdm1_emb=np.empty((n, n)), rdm1_mo=np.empty((n, n)),
+                                  t1=np.empty((o, v)) if t1 else None, t2=np.empty((o, o, v, v)) if t2 else None))
+        self.e_frag = np.zeros((F, 3))
+        self.e, self.e_scf, self.ebe_hf = (C.c_double * F)(), (C.c_double * F)(), (C.c_double * F)()
+        self.n_iter, self.scf_cycles = (C.c_int * F)(), (C.c_int * F)()
+
+    def _ptr(self, xs):
+        return (C.c_void_p * len(xs))(*[_p(x) for x in xs]) if self.batch else _p(xs[0])
+
+    def call(self, name, amplitudes, n_iter=True, after_opts=(), last=()):
+        """the entry `name`: the inputs up to opts (after_opts: what an entry takes next), eeval, the four arrays every solver returns, the entry's own
+        `amplitudes` (keys of the dicts), the energies, n_iter where the entry has it, scf_cycles and what comes `last`"""
+        F = len(self.frags)
+        head = (F, (C.c_void_p * F)(*[fr.h for fr in self.frags]), (C.c_int * F)(*self.ns)) if self.batch else (self.frags[0].h, self.ns[0])
+        arrays = [self._ptr([o_[k] for o_ in self.outs]) for k in ("mo_coeff", "mo_energy", "rdm1_emb", "rdm1_mo") + tuple(amplitudes)]
+        check(getattr(self.lib, name)(*head, self._ptr(self.hs), self._ptr(self.dm0s), C.byref(self.opts), *after_opts, self.eeval, *arrays,
+                                      self.e_frag.ctypes.data, self.e, self.e_scf, self.ebe_hf, *((self.n_iter,) if n_iter else ()), self.scf_cycles, *last), name, self.lib)
+
+    def results(self, lambda_iters=False):
+        """the dicts, filled after the call; lambda_iters: asked of the library (a CCSD solve), else 0"""
+        for f, (fr, o_) in enumerate(zip(self.frags, self.outs)):
+            nlam = C.c_int()
+            if lambda_iters:
+                check(self.lib.qemb_frag_lambda_iters(fr.h, C.byref(nlam)), "qemb_frag_lambda_iters", self.lib)
+            o_.update(e_frag=self.e_frag[f].copy(), e_corr_mo=float(self.e[f]), e_scf=float(self.e_scf[f]), ebe_hf=float(self.ebe_hf[f]), n_iter=int(self.n_iter[f]),
+                      scf_cycles=int(self.scf_cycles[f]), lambda_iters=nlam.value)
+        return self.outs
+
+
 def solve_batch(frags, nsoccs, hs, dm0s=None, opts: SolverOpts | None = None, eeval=True, want_t2=False, stats=None, solver="CCSD"):
     """qemb_frag_solve_batch: every fragment of `frags` (DeviceFragment objects of one library) in one call -- fragment RHF, MO transformation
     and the density / energy evaluation per fragment on its own stream, the CCSD iterations of all fragments in lock step (one grouped
@@ -368,46 +383,15 @@ def solve_batch(frags, nsoccs, hs, dm0s=None, opts: SolverOpts | None = None, ee
     step); the dicts DeviceFragment.solve_mp2 would return, bit for bit."""
     if solver not in ("CCSD", "MP2"):
         raise ValueError("Solver not implemented")
-    F = len(frags)
-    if F == 0:
+    if len(frags) == 0:
         return []
-    lib = frags[0].lib
-    opts = opts or default_opts(lib)
-    ns = [int(o) for o in nsoccs]
-    hs = [np.ascontiguousarray(h, dtype=np.float64) for h in hs]
-    dm0s = [None] * F if dm0s is None else [None if d is None else np.ascontiguousarray(d, dtype=np.float64) for d in dm0s]
-    outs = []
-    for fr, o in zip(frags, ns):
-        n, v = fr.n, fr.n - o
-        outs.append(dict(mo_coeff=np.empty((n, n)), mo_energy=np.empty(n), rdm1_emb=np.empty((n, n)), rdm1_mo=np.empty((n, n)),
-                         t1=np.empty((o, v)) if solver == "CCSD" else None, t2=np.empty((o, o, v, v)) if want_t2 else None))
-    VP = C.c_void_p * F
-    arr = lambda xs: VP(*[None if x is None else x.ctypes.data for x in xs])
-    handles = VP(*[fr.h for fr in frags])
-    nso = (C.c_int * F)(*ns)
-    e_frag = np.zeros((F, 3)); ecorr = np.zeros(F); escf = np.zeros(F); ebehf = np.zeros(F)
-    nit = (C.c_int * F)(); ncyc = (C.c_int * F)(); st = (C.c_int64 * 5)()
+    c = _SolveCall(frags, nsoccs, hs, dm0s, opts, eeval, batch=True, t1=solver == "CCSD", t2=want_t2)
     if solver == "MP2":
-        check(lib.qemb_frag_solve_mp2_batch(F, handles, nso, arr(hs), arr(dm0s), C.byref(opts), int(bool(eeval)),
-                                            arr([o_["mo_coeff"] for o_ in outs]), arr([o_["mo_energy"] for o_ in outs]), arr([o_["rdm1_emb"] for o_ in outs]),
-                                            arr([o_["rdm1_mo"] for o_ in outs]), arr([o_["t2"] for o_ in outs]),
-                                            e_frag.ctypes.data, ecorr.ctypes.data, escf.ctypes.data, ebehf.ctypes.data, ncyc),
-              "qemb_frag_solve_mp2_batch", lib)
-        for f, o_ in enumerate(outs):
-            o_.update(e_frag=e_frag[f].copy(), e_corr_mo=float(ecorr[f]), e_scf=float(escf[f]), ebe_hf=float(ebehf[f]), n_iter=0,
-                      scf_cycles=int(ncyc[f]), lambda_iters=0)
-        return outs
-    check(lib.qemb_frag_solve_batch(F, handles, nso, arr(hs), arr(dm0s), C.byref(opts), int(bool(eeval)),
-                                    arr([o_["mo_coeff"] for o_ in outs]), arr([o_["mo_energy"] for o_ in outs]), arr([o_["rdm1_emb"] for o_ in outs]),
-                                    arr([o_["rdm1_mo"] for o_ in outs]), arr([o_["t1"] for o_ in outs]), arr([o_["t2"] for o_ in outs]),
-                                    e_frag.ctypes.data, ecorr.ctypes.data, escf.ctypes.data, ebehf.ctypes.data, nit, ncyc, st),
-          "qemb_frag_solve_batch", lib)
-    for f, (fr, o_) in enumerate(zip(frags, outs)):
-        nlam = C.c_int()
-        check(lib.qemb_frag_lambda_iters(fr.h, C.byref(nlam)), "qemb_frag_lambda_iters", lib)
-        o_.update(e_frag=e_frag[f].copy(), e_corr_mo=float(ecorr[f]), e_scf=float(escf[f]), ebe_hf=float(ebehf[f]), n_iter=int(nit[f]),
-                  scf_cycles=int(ncyc[f]), lambda_iters=nlam.value)
+        c.call("qemb_frag_solve_mp2_batch", ("t2",), n_iter=False)
+        return c.results()
+    st = (C.c_int64 * 5)()
+    c.call("qemb_frag_solve_batch", ("t1", "t2"), last=(st,))
     if stats is not None:
         for k, name in enumerate(("merged_runs", "launches", "grouped_launches", "operations", "max_group")):
             stats[name] = stats.get(name, 0) + int(st[k]) if name != "max_group" else max(stats.get(name, 0), int(st[k]))
-    return outs
+    return c.results(lambda_iters=True)

@@ -73,8 +73,7 @@ def compute_numerical_jacobian(beobj, solver="CCSD", only_chem=False, nproc=1, s
                 rd = []
                 for sgn in (+1.0, -1.0):
                     x = pot.copy(); x[idx] += sgn * step_size
-                    solve = {"MP2": f.dev.solve_mp2, "FCI-hip": f.dev.solve_fci}.get(solver, f.dev.solve)
-                    out = solve(f.nsocc, f.fock + calc_heff(f, x, only_chem), f.dm0, opts=opts, eeval=False)
+                    out = f.dev.solve_as(solver, f.nsocc, f.fock + calc_heff(f, x, only_chem), f.dm0, opts=opts, eeval=False)
                     rd.append(out["rdm1_emb"])
                 view = [None] * len(beobj.Fobjs)
                 view[I] = _Delta(rd[0] - rd[1])

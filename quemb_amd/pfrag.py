@@ -172,16 +172,8 @@ class Frags:
         solver="FCI-hip": the FCI branch (solver.py:339-342) on the device; `fci_opts` (qemb_fci_opts, None: defaults), want_t2 asks for the CI vector (out["civec"])."""
         if solver not in SOLVERS:
             raise ValueError("Solver not implemented")
-        if solver == "FCI-hip":      # the FCI branch (solver.py:339-342): exact in the embedding space; relax_density is not read
-            opts = self._solve_inputs(opts, eeval, False)
-            out = self.dev.solve_fci(self.nsocc, self.fock + self.heff, self.dm0, opts=opts, fci_opts=fci_opts, eeval=eeval, want_civec=want_t2)
-            return self._solve_outputs(out, eeval, use_cumulant, solver)
-        if solver == "MP2":
-            opts = self._solve_inputs(opts, eeval, False)
-            out = self.dev.solve_mp2(self.nsocc, self.fock + self.heff, self.dm0, opts=opts, eeval=eeval, want_t2=want_t2)
-            return self._solve_outputs(out, eeval, use_cumulant, solver)
-        opts = self._solve_inputs(opts, eeval, relax_density)
-        out = self.dev.solve(self.nsocc, self.fock + self.heff, self.dm0, opts=opts, eeval=eeval, want_t2=want_t2)
+        opts = self._solve_inputs(opts, eeval, relax_density and solver == "CCSD")      # (the MP2 and FCI branches do not read relax_density)
+        out = self.dev.solve_as(solver, self.nsocc, self.fock + self.heff, self.dm0, opts=opts, eeval=eeval, want_amplitudes=want_t2, fci_opts=fci_opts)
         return self._solve_outputs(out, eeval, use_cumulant, solver)
 
     def make_rdm2(self, with_dm1=True):

@@ -81,6 +81,30 @@ def solve_error(Fobjs, Nocc, only_chem=False, rdm1_list=None):
     return float(np.mean(err_vec * err_vec) ** 0.5), err_vec
 
 
+def _solve_fragment(name, solver, keys, h, eri_s4, nsocc, dm0, *, n_frag, rdm_return, rdm2_return, use_cumulant, opts, lib, df_factor=None, fci_opts=None):
+    """What solve_ccsd / solve_mp2 / solve_fci share: a fragment with its ERIs (or living on its 3-index factor) is created, solved without energies and freed.
+    Returns (out[keys[0]], out[keys[1]]), then rdm1_mo and mo_coeff with rdm_return; rdm2_return: the 2-RDM of the solve takes the place of mo_coeff
+    (solver.py:940-942), or is appended without rdm_return."""
+    fr = DeviceFragment(h.shape[0], n_frag, lib=lib)
+    try:
+        if eri_s4 is not None:
+            fr.set_eri_s4(eri_s4)
+            if df_factor is not None:
+                fr.set_df_factor(df_factor)
+        elif df_factor is not None:
+            fr.set_df_only(df_factor)
+        else:
+            raise ValueError(f"{name} needs the fragment ERIs or their 3-index factor")
+        out = fr.solve_as(solver, nsocc, h, dm0, opts=opts, eeval=False, want_amplitudes=True, fci_opts=fci_opts)
+        rdm2 = fr.make_rdm2(solver, with_dm1=not use_cumulant) if rdm2_return else None
+    finally:
+        fr.free()
+    head = (out[keys[0]], out[keys[1]])
+    if rdm_return:
+        return (*head, out["rdm1_mo"], rdm2 if rdm2_return else out["mo_coeff"])
+    return (*head, rdm2) if rdm2_return else head
+
+
 def solve_ccsd(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, relax=False, use_cumulant=True,
                opts=None, lib=None):
     """Device counterpart of solve_ccsd (molbe/solver.py:829-946).  The reference takes a PySCF mean-field object;
@@ -92,19 +116,8 @@ def solve_ccsd(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_r
     if relax:
         opts = SolverOpts.from_buffer_copy(opts) if opts is not None else default_opts(lib)
         opts.relax_density = 1
-    n = h.shape[0]
-    fr = DeviceFragment(n, n_frag, lib=lib)
-    try:
-        fr.set_eri_s4(eri_s4)
-        out = fr.solve(nsocc, h, dm0, opts=opts, eeval=False, want_t2=True)
-        rdm2 = fr.make_rdm2("CCSD", with_dm1=not use_cumulant) if rdm2_return else None
-    finally:
-        fr.free()
-    if rdm_return and rdm2_return:
-        return out["t1"], out["t2"], out["rdm1_mo"], rdm2          # solver.py:942
-    if rdm_return:
-        return out["t1"], out["t2"], out["rdm1_mo"], out["mo_coeff"]
-    return (out["t1"], out["t2"], rdm2) if rdm2_return else (out["t1"], out["t2"])
+    return _solve_fragment("solve_ccsd", "CCSD", ("t1", "t2"), h, eri_s4, nsocc, dm0, n_frag=n_frag, rdm_return=rdm_return, rdm2_return=rdm2_return,
+                           use_cumulant=use_cumulant, opts=opts, lib=lib)
 
 
 def solve_mp2(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, use_cumulant=True, df_factor=None, opts=None, lib=None):
@@ -112,52 +125,16 @@ def solve_mp2(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_re
     fragment ERIs (or None with `df_factor`, the 3-index factor (naux, npair(n)) the fragment then lives on), nsocc and dm0.
     Returns (e_corr, t2) or (e_corr, t2, rdm1_mo, mo_coeff) with rdm_return; rdm1_mo is PySCF's unrelaxed mp2.make_rdm1.  rdm2_return: the
     fragment 2-RDM in the MO basis (mp2.make_rdm2, or its dovov part alone with use_cumulant) in the place `solve_ccsd` gives it."""
-    n = h.shape[0]
-    fr = DeviceFragment(n, n_frag, lib=lib)
-    try:
-        if eri_s4 is not None:
-            fr.set_eri_s4(eri_s4)
-            if df_factor is not None:
-                fr.set_df_factor(df_factor)
-        elif df_factor is not None:
-            fr.set_df_only(df_factor)
-        else:
-            raise ValueError("solve_mp2 needs the fragment ERIs or their 3-index factor")
-        out = fr.solve_mp2(nsocc, h, dm0, opts=opts, eeval=False, want_t2=True)
-        rdm2 = fr.make_rdm2("MP2", with_dm1=not use_cumulant) if rdm2_return else None
-    finally:
-        fr.free()
-    if rdm_return and rdm2_return:
-        return out["e_corr_mo"], out["t2"], out["rdm1_mo"], rdm2
-    if rdm_return:
-        return out["e_corr_mo"], out["t2"], out["rdm1_mo"], out["mo_coeff"]
-    return (out["e_corr_mo"], out["t2"], rdm2) if rdm2_return else (out["e_corr_mo"], out["t2"])
+    return _solve_fragment("solve_mp2", "MP2", ("e_corr_mo", "t2"), h, eri_s4, nsocc, dm0, n_frag=n_frag, rdm_return=rdm_return, rdm2_return=rdm2_return,
+                           use_cumulant=use_cumulant, opts=opts, lib=lib, df_factor=df_factor)
 
 
 def solve_fci(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, use_cumulant=True, df_factor=None, opts=None, fci_opts=None, lib=None):
     """Device counterpart of the reference's FCI branch (molbe/solver.py:339-342: fci.FCI(mf, mo_coeff).kernel(), make_rdm1, make_rdm2) with the inputs of
     `solve_mp2` above.  Returns (e_fci, civec) -- the eigenvalue of h = fock + heff with the fragment ERIs and the (ns, ns) vector -- or
     (e_fci, civec, rdm1_mo, mo_coeff) with rdm_return; rdm2_return: make_rdm2 (minus its mean-field part with use_cumulant) in the place `solve_ccsd` gives it."""
-    n = h.shape[0]
-    fr = DeviceFragment(n, n_frag, lib=lib)
-    try:
-        if eri_s4 is not None:
-            fr.set_eri_s4(eri_s4)
-            if df_factor is not None:
-                fr.set_df_factor(df_factor)
-        elif df_factor is not None:
-            fr.set_df_only(df_factor)
-        else:
-            raise ValueError("solve_fci needs the fragment ERIs or their 3-index factor")
-        out = fr.solve_fci(nsocc, h, dm0, opts=opts, fci_opts=fci_opts, eeval=False, want_civec=True)
-        rdm2 = fr.make_rdm2("FCI-hip", with_dm1=not use_cumulant) if rdm2_return else None
-    finally:
-        fr.free()
-    if rdm_return and rdm2_return:
-        return out["e_fci"], out["civec"], out["rdm1_mo"], rdm2
-    if rdm_return:
-        return out["e_fci"], out["civec"], out["rdm1_mo"], out["mo_coeff"]
-    return (out["e_fci"], out["civec"], rdm2) if rdm2_return else (out["e_fci"], out["civec"])
+    return _solve_fragment("solve_fci", "FCI-hip", ("e_fci", "civec"), h, eri_s4, nsocc, dm0, n_frag=n_frag, rdm_return=rdm_return, rdm2_return=rdm2_return,
+                           use_cumulant=use_cumulant, opts=opts, lib=lib, df_factor=df_factor, fci_opts=fci_opts)
 
 
 def fragment_work_bytes(n, o=None, solver="CCSD", naux=None):

@@ -65,6 +65,10 @@ int qemb_op_gemm_stamps(int64_t M, int64_t N, int64_t K, const double* A, int64_
 /* the tile configuration and split-K factor the CCSD driver picks for a product of `rows` packed pair rows by `cols` columns (pp-ladder,
  * tau-side dressing): introspection for tests and tools, no device call */
 int qemb_pair_gemm_choice(int64_t rows, int64_t cols, int* cfg, int* ksplit);
+/* the plans of the nine CCSD products whose split-K slabs the consumer adds up, for a fragment of o occupied and v virtual orbitals -- the plans the
+ * solver sizes its slab buffers and launches from: out[9][6] = (M, N, K, cfg, ksplit, slabs) for Fvv', the two long-K T1 terms, ladder +/-, Xw +/-,
+ * tau-side X +/-.  Introspection for tests and tools, no device call */
+int qemb_ccsd_gemm_plans(int o, int v, int64_t* out);
 int qemb_set_gemm_ksplit(int ksplit);      /* explicit split-K factor for qemb_op_gemm (0 = automatic) */
 /* out[sum ik*so[k]] = alpha*in[sum ik*si[k]] + beta*out[...], 0<=ik<dim[k], 4 dims                  */
 int qemb_op_copy4(const int64_t dim[4], const double* in, const int64_t si[4], double* out,

@@ -57,7 +57,7 @@ int ao2mo_dense(const AoEri& ao, const double* TA, int n, double* out_s4) {
   QTRY(W1.alloc(std::max<int64_t>(npN * N * N, (int64_t)n * n * npN)));
   QTRY(W2.alloc(std::max<int64_t>((int64_t)n * npN * N, npn * N * N)));
   TimerScope lap_AO2MO(TIMER_AO2MO);
-  const int tcfg = (n > 192 && n <= 224) ? 13 : -1;   // one 224 x 128 tile instead of two padded 128-row tiles
+  const int tcfg = fits_one_224_tile(n) ? GEMM_224x128 : -1;   // one 224 x 128 tile instead of two padded 128-row tiles
   QTRY(dev_unpack_tril_rows(npN, N, ao.s4, W1));                                                   // [mn][k][l]
   QTRY(gemm(n, npN * N, N, 1.0, TA, n, false, W1, N, true, 0.0, W2, npN * N, 1, 0, 0, 0, tcfg));                     // [l'][mn][k]
   QTRY(gemm_quarter_lower_rows(n, npN, N, TA, W2, W1));                                            // [k'][l'][mn], rows k' >= l' only

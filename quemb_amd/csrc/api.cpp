@@ -96,10 +96,16 @@ int qemb_mfma_f64_peak(int iters, int blocks_per_cu, double* tflops) { return de
 int qemb_mfma_f64_peak(int, int, double*) { set_error("not available in the hostcheck build"); return QEMB_ERR_DEVICE; }
 #endif
 int qemb_pair_gemm_choice(int64_t rows, int64_t cols, int* cfg, int* ksplit) {
-  int c = -1, k = 0;
-  pick_pair_gemm(rows, cols, c, k);
-  if (cfg) *cfg = c;
-  if (ksplit) *ksplit = k;
+  const GemmPlan p = pick_pair_gemm(rows, cols);
+  if (cfg) *cfg = p.cfg;
+  if (ksplit) *ksplit = p.ks;
+  return QEMB_OK;
+}
+int qemb_ccsd_gemm_plans(int o, int v, int64_t* out) {
+  if (o < 1 || v < 0 || !out) { set_error("qemb_ccsd_gemm_plans: bad arguments"); return QEMB_ERR_ARG; }
+  const CcsdGemmPlans p = ccsd_gemm_plans(o, v);
+  for (const GemmPlan* g : {&p.fvv, &p.pa, &p.pb, &p.ladder_p, &p.ladder_m, &p.xw_p, &p.xw_m, &p.x_p, &p.x_m})
+    for (const int64_t x : {g->M, g->N, g->K, (int64_t)g->cfg, (int64_t)g->ks, (int64_t)g->S}) *out++ = x;
   return QEMB_OK;
 }
 int qemb_set_gemm_splitk(int enabled) { dev_gemm_set_auto_splitk(enabled); return QEMB_OK; }

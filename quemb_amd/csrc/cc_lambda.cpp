@@ -124,7 +124,7 @@ int CcLambda::contract(int dst, double coef, std::string sa, std::string sb, con
                           (long long)M, (long long)N, (long long)K, (int)a_kc, (int)b_kc, (int)(sA.p != nullptr), (int)(sB.p != nullptr), (int)(so != Mord + Nord));
   // products with an n_occ-sized side: 32 x 128 / 128 x 32 tiles instead of padding that side to 64 (these are HBM-bound passes
   // over ovvv-sized operands; ccsd.cpp uses the same tiles for the t1 contractions)
-  const int cfg = (M <= 32 && N >= 64) ? 21 : (N <= 32 && M >= 64) ? 20 : -1;
+  const int cfg = (M <= 32 && N >= 64) ? GEMM_32x128 : (N <= 32 && M >= 64) ? GEMM_128x32 : -1;
   if (so == Mord + Nord) return gemm(M, N, K, coef, A, lda, a_kc, B, ldb, b_kc, take_beta(dst), ptr_[dst], N, 1, 0, 0, 0, cfg);
   QTRY(sC.alloc(M * N));
   QTRY(gemm(M, N, K, 1.0, A, lda, a_kc, B, ldb, b_kc, 0.0, sC, N, 1, 0, 0, 0, cfg));

@@ -68,6 +68,13 @@ static int mo_three_quarter_blocks_ov(int n, int o, int nf, const double* T, int
   return 0;
 }
 
+// row strides of the (+/-) pair-packed ladder operands over the virtual pairs (even, so that their rows stay 16-byte aligned)
+static void packed_pair_lds(int64_t v, int64_t& ldp, int64_t& ldm) {
+  const int64_t npv = v * (v + 1) / 2, nm = v * (v - 1) / 2;
+  ldp = npv + (npv & 1);
+  ldm = nm > 0 ? nm + (nm & 1) : 2;
+}
+
 // every block of the amplitude equations straight from the pair product S[P(r',s')][P(p',q')] = (r's'|p'q') (npair x npair, both triangles): the pair-first
 // image of S (twice its size, a write of 9.4 GB at n = 220) is formed for the vv|vv part alone (`work`: npair(v) * v * mo_slab_ld(v) doubles).  ovvv comes as rows of S with the pair (a,c) still packed -- the layout setup()
 // wants for the ZC pass anyway -- and is unpacked from there.
@@ -88,8 +95,7 @@ static int mo_blocks_from_pair_product(int n, int o, const double* S, double* wo
   QTRY(dev_extract_ps(n, S, 0, o, o, 0, o, v, v, o, out.ovvo));
   QTRY(dev_extract_ps_packed(n, S, 0, o, o, o, v, v, out.ovvv_pk));
   QTRY(dev_unpack_tril_rows((int64_t)o * v, v, out.ovvv_pk, out.ovvv));
-  out.ldp = npv + (npv & 1); out.ldm = nm + (nm & 1);
-  if (out.ldm == 0) out.ldm = 2;
+  packed_pair_lds(v, out.ldp, out.ldm);
   QTRY(out.Vp.alloc(npv * out.ldp));
   QTRY(out.Vm.alloc(std::max<int64_t>(nm, 1) * out.ldm));
   // the (+/-) ladder operands pair two entries of S whose column pairs run along different indices: gathered from S itself every other read walks down a
@@ -117,8 +123,7 @@ static int mo_blocks_from_pair_first(int n, int o, const double* Mp, double* scr
   QTRY(dev_extract_pf(n, Mp, 0, o, o, o, o, v, v, v, out.ovvv));
   {  // (+/-) pair-packed ladder operands (6.4 GB instead of the 12.8 GB dense v^4 block at v = 200)
     const int64_t npv = (int64_t)v * (v + 1) / 2, nm = (int64_t)v * (v - 1) / 2;
-    out.ldp = npv + (npv & 1); out.ldm = nm + (nm & 1);
-    if (out.ldm == 0) out.ldm = 2;
+    packed_pair_lds(v, out.ldp, out.ldm);
     QTRY(out.Vp.alloc(npv * out.ldp));
     QTRY(out.Vm.alloc(std::max<int64_t>(nm, 1) * out.ldm));
     QTRY(dev_ladder_pack_vvvv_pf(n, o, Mp, out.Vp, out.ldp, out.Vm, out.ldm));
@@ -143,8 +148,8 @@ int mo_transform(int n, int o, int nf, const double* eri_s4, double* X0, double*
   TimerScope lap_AO2MO(TIMER_AO2MO);
   const int64_t nl = mo_slab_ld(n);                   // row stride of the unpacked n x n images (X1 here, X0 after the second unpack)
   if (!x1_is_unpacked) QTRY(dev_unpack_tril_rows_ld(np, n, nl, eri_s4, X1));   // (the caller of solve_begin has done it already)
-  // 193..224 rows fit ONE 224 x 128 tile (1.8 % padding instead of the 14 % of two 128-row tiles at n = 220)
-  const int tcfg = (n > 192 && n <= 224) ? 13 : -1;
+  const bool one_tile = fits_one_224_tile(n);      // 1.8 % padding instead of the 14 % of two 128-row tiles at n = 220
+  const int tcfg = one_tile ? GEMM_224x128 : -1;
   QTRY(gemm(n, ncol, n, 1.0, C, n, false, X1, nl, true, 0.0, X0, ncol, 1, 0, 0, 0, tcfg));
   QTRY(gemm_quarter_lower_rows(n, np, n, C, X0, X1));     // X1[r'][s'][pq], only the rows r' >= s' (all that is read below)
   QTRY(dev_unpack_tril_pair_rows_ld(n, n, nl, X1, X0));   // keep r' >= s' rows AND unpack pq, one pass: X0 = [(r's')][p][q], rows nl apart
@@ -153,7 +158,7 @@ int mo_transform(int n, int o, int nf, const double* eri_s4, double* X0, double*
   const int64_t n2 = (int64_t)n * n;
   // X1[(r's')][P][q'] = sum_q X0[..][P][q] C[q,q']: the slabs are contiguous, so this is ONE tall product over the np * n rows ((r's'),P) with
   // all n columns in a 128 x 224 tile (as a batch of n x n x n products on the 224 x 128 tile the second column tile is 72 % padding at n = 220)
-  if (n > 192 && n <= 224) { QTRY(gemm(np * n, n, n, 1.0, X0, nl, true, C, n, false, 0.0, X1, n, 1, 0, 0, 0, 34)); }
+  if (one_tile) { QTRY(gemm(np * n, n, n, 1.0, X0, nl, true, C, n, false, 0.0, X1, n, 1, 0, 0, 0, GEMM_128x224)); }
   else QTRY(gemm(n, n, n, 1.0, X0, nl, true, C, n, false, 0.0, X1, n, np, (int64_t)n * nl, 0, n2, tcfg));
   QTRY(mo_three_quarter_blocks(n, o, nf, X1, 0, out, build_T34));
   // X0[(r's')][p'][q'] = sum_p C[p,p'] X1[..][p][q'].  As a batch of n x n x n products on the 224 x 128 tile the second column tile is 72 % padding at n = 220
@@ -161,12 +166,12 @@ int mo_transform(int n, int o, int nf, const double* eri_s4, double* X0, double*
   //   X0[(r's')][q'][p'] = sum_p X1[(r's')][p][q'] C[p,p']
   // and that is ONE tall product over the rows ((r's'), q') -- the rows of a stack of slabs read through the slab-aware loader (GemmDesc::a_slab) -- with all n
   // columns in a 128 x 224 tile, like the third quarter transform above (round 5).  Other sizes keep the batched form.
-  if (n > 192 && n <= 224 && n % 2 == 0) {
+  if (one_tile && n % 2 == 0) {
     GemmDesc g{};
     g.M = np * n; g.N = n; g.K = n; g.alpha = 1.0; g.beta = 0.0;
     g.A = X1; g.lda = n; g.a_kcontig = 0; g.strideA = 0; g.a_slab = n; g.a_slab_skip = n2 - n;
     g.B = C; g.ldb = n; g.b_kcontig = 0; g.strideB = 0;
-    g.C = X0; g.ldc = n; g.strideC = 0; g.batch = 1; g.cfg = 34; g.ksplit = 0;
+    g.C = X0; g.ldc = n; g.strideC = 0; g.batch = 1; g.cfg = GEMM_128x224; g.ksplit = 0;
     QTRY(dev_gemm(g));
   } else QTRY(gemm(n, n, n, 1.0, C, n, false, X1, n, false, 0.0, X0, n, np, 0, n2, n2, tcfg));
   // pair-first MO tensor Mp[P(r',s')][p'][q'] = (r's'|p'q') in X0 (X1 is free now)
@@ -229,8 +234,6 @@ int mo_transform_factor(int n, int o, int nf, int naux, const double* Bf, double
 }
 
 // ------------------------------------------------------------------------------------------------------------
-static void pick_xw_split(int64_t rows, int64_t oo, int64_t K, int& cfg, int& ks);
-static void pick_long_k(int64_t M, int64_t N, int64_t K, int tile_m, int tile_n, int cfg_in, int& cfg, int& ks, bool many_slices);
 int CcsdSolver::setup(MoIntegrals&& ints, const double* mo_energy_dev) {
   I_ = std::move(ints);
   o_ = I_.o; v_ = I_.v; nf_ = I_.nf;
@@ -292,30 +295,21 @@ int CcsdSolver::setup(MoIntegrals&& ints, const double* mo_energy_dev) {
   for (DBuf* b : {&tau_, &T_, &Tp_, &S_, &W1_, &W2_, &W12_, &W12b_, &R_, &U_}) QTRY(b->alloc(N2));
   const int64_t NG = std::max<int64_t>(N2, oo * o * v);   // scratch also holds (o,o,v,o)-shaped temporaries
   QTRY(G2_.alloc(NG));
-  {  // split-K slabs of the few-output, long-K products stay where the slices wrote them (added up by y_traces / t1_assemble)
-    int cfg, ks;
-    pick_long_k(v, v, oo * v, 64, 64, (v <= 256) ? 1 : -1, cfg, ks, false);
-    QTRY(Fvv_.alloc((int64_t)gemm_slab_count(oo * v, ks) * vv));
-    const int cw = (o <= 32) ? 21 : -1;
-    pick_long_k(o, v, o * vv, 32, 128, cw, cfg, ks, true);
-    const int64_t sa = gemm_slab_count(o * vv, ks);
-    pick_long_k(o, v, o * v * o, 32, 128, cw, cfg, ks, true);
-    const int64_t sb = gemm_slab_count(o * v * o, ks);
-    QTRY(T1P_.alloc((sa + sb) * nov));
-  }
+  // split-K slabs of the few-output, long-K products stay where the slices wrote them (added up by y_traces / t1_assemble, the scatter passes): every such
+  // product is planned here, once; its buffer is sized and -- in update_amps / apply_ladder -- its launch made from the same plan
+  plans_ = ccsd_gemm_plans(o, v);
+  QTRY(Fvv_.alloc(plans_.fvv.elems()));
+  QTRY(T1P_.alloc(plans_.pa.elems() + plans_.pb.elems()));
   QTRY(Foo_.alloc(oo)); QTRY(Fov_.alloc(nov)); QTRY(Z_.alloc(oo)); QTRY(Y_.alloc(vv));
   QTRY(Ytmp_.alloc(vv)); QTRY(Loo_.alloc(oo)); QTRY(Lvv_.alloc(vv)); QTRY(Q_.alloc(oo)); QTRY(Wo_.alloc(oo * oo));
   QTRY(O1_.alloc(oo * oo)); QTRY(X_.alloc(oo * nov)); QTRY(scal_.alloc(8));
   {
     const int64_t npo = o * (o + 1) / 2, nmo = std::max<int64_t>(o * (o - 1) / 2, 1);
     // (results of the split-K products keep one slab per K slice: the consumers add them up)
-    const int64_t npv = v * (v + 1) / 2, nmv = v * (v - 1) / 2;
-    auto slabs_pair = [&](int64_t rows, int64_t cols, int64_t K, bool k_aware = false) { int cfg, ks; pick_pair_gemm(rows, cols, cfg, ks, k_aware ? K : 0); return (int64_t)gemm_slab_count(K, ks); };
-    auto slabs_xw = [&](int64_t rows, int64_t K) { int cfg, ks; pick_xw_split(rows, oo, K, cfg, ks); return (int64_t)gemm_slab_count(K, ks); };
-    QTRY(LTp_.alloc(npo * I_.ldp)); QTRY(LRp_.alloc(std::max(npo * I_.ldp, slabs_pair(npo, npv, I_.ldp) * npo * npv)));
-    QTRY(LTm_.alloc(nmo * I_.ldm)); QTRY(LRm_.alloc(std::max(nmo * I_.ldm, slabs_pair(nmo, std::max<int64_t>(nmv, 1), I_.ldm) * nmo * std::max<int64_t>(nmv, 1))));
-    QTRY(Xp_.alloc(slabs_pair(npo, nov, I_.ldp, true) * npo * nov)); QTRY(Xm_.alloc(slabs_pair(nmo, nov, I_.ldm, true) * nmo * nov));
-    QTRY(Xwp_.alloc(slabs_xw(npo, I_.ldp) * npo * oo)); QTRY(Xwm_.alloc(slabs_xw(nmo, I_.ldm) * nmo * oo)); QTRY(Xw_.alloc(oo * oo));
+    QTRY(LTp_.alloc(npo * I_.ldp)); QTRY(LRp_.alloc(std::max(npo * I_.ldp, plans_.ladder_p.elems())));
+    QTRY(LTm_.alloc(nmo * I_.ldm)); QTRY(LRm_.alloc(std::max(nmo * I_.ldm, plans_.ladder_m.elems())));
+    QTRY(Xp_.alloc(plans_.x_p.elems())); QTRY(Xm_.alloc(plans_.x_m.elems()));
+    QTRY(Xwp_.alloc(plans_.xw_p.elems())); QTRY(Xwm_.alloc(plans_.xw_m.elems())); QTRY(Xw_.alloc(oo * oo));
     lwp_ = npo + (npo & 1); lwm_ = std::max<int64_t>(2, nmo + (nmo & 1));
     QTRY(WAp_.alloc(npo * lwp_)); QTRY(WAm_.alloc(nmo * lwm_)); QTRY(HRp_.alloc(npo * I_.ldp)); QTRY(HRm_.alloc(nmo * I_.ldm));
     QTRY(ZB_.alloc(N2)); QTRY(ZC_.alloc(N2));
@@ -362,24 +356,24 @@ int CcsdSolver::set_amps(const double* t1d, const double* t2d, bool defer_energy
 }
 
 // tile configuration and K split for the "few packed pair rows x many columns" GEMMs (ladder, tau-side dressing)
-void pick_pair_gemm(int64_t rows, int64_t cols, int& cfg, int& ks, int64_t K) {
-  cfg = -1; ks = 0;
-  if (cols < 1024) return;
+GemmPlan pick_pair_gemm(int64_t rows, int64_t cols, int64_t K, bool k_aware) {
+  int cfg = -1, ks = 0;
+  if (cols < 1024) return GemmPlan(rows, cols, K, cfg, ks);
   // the row-tile height with the least ESTIMATED TIME among the configurations that exist: padded rows weighted by what a row costs on
   // that tile relative to the 7 x 2 / 6 x 2 wave tiles (the single-column wave tiles 11 / 12 read 8 / 5 LDS fragments per 7 / 4 MFMAs and
   // run at ~0.8 / ~0.6 of their rate on these long-K products; profiles/r01_gemm_microbench_ladder_tiles.jsonl).  n_occ = 20 gets the
   // 224-row tile for its 210 symmetric and the 192-row tile for its 190 antisymmetric pairs; n_occ = 30 three 160-row tiles for 465;
   // n_occ = 40 (820 rows) four 224-row tiles, not thirteen 64-row ones.  (The dispatcher's own choice for "few tiles" would be the
   // 64 x 64 tile, a quarter of the rate.)
-  static const struct { int rows, cfg, cols; double cost; } cand[] = {{224, 13, 128, 1.0}, {192, 15, 128, 1.0}, {160, 35, 128, 1.03}, {128, 4, 256, 1.0},
-                                                                      {112, 11, 128, 1.25}, {80, 36, 128, 1.08}, {64, 12, 128, 1.6}, {48, 38, 128, 1.12}};
+  static const struct { int cfg; double cost; } cand[] = {{GEMM_224x128, 1.0}, {GEMM_192x128, 1.0}, {GEMM_160x128, 1.03}, {GEMM_128x256, 1.0},
+                                                          {GEMM_112x128_COL, 1.25}, {GEMM_80x128, 1.08}, {GEMM_64x128_COL, 1.6}, {GEMM_48x128, 1.12}};
   double best_cost = -1.0;
   int64_t tiles = 0;
   for (const auto& c : cand) {
-    const int64_t mt = (rows + c.rows - 1) / c.rows;
-    if (c.cfg == 38 && mt > 1) continue;      // (the 48-row tile only where it holds all rows: n_occ <= 9)
-    const double cost = (double)(mt * c.rows) * c.cost;
-    if (best_cost < 0 || cost < best_cost - 1e-9) { best_cost = cost; cfg = c.cfg; tiles = mt * ((cols + c.cols - 1) / c.cols); }
+    const int64_t tile_rows = gemm_tile_rows(c.cfg), mt = (rows + tile_rows - 1) / tile_rows;
+    if (c.cfg == GEMM_48x128 && mt > 1) continue;      // (the 48-row tile only where it holds all rows: n_occ <= 9)
+    const double cost = (double)(mt * tile_rows) * c.cost;
+    if (best_cost < 0 || cost < best_cost - 1e-9) { best_cost = cost; cfg = c.cfg; tiles = gemm_tile_count(c.cfg, rows, cols); }
   }
   double best = 0.0;
   for (int c = 1; c <= 8; ++c) {
@@ -389,49 +383,65 @@ void pick_pair_gemm(int64_t rows, int64_t cols, int& cfg, int& ks, int64_t K) {
   }
   if (ks == 0) ks = (int)std::max<int64_t>(1, std::min<int64_t>(8, (1024 + tiles - 1) / tiles));
   // a product whose eight slices still leave most CUs without a workgroup and whose K is long (the tau-side dressing of mid-size fragments: 12 column tiles x 8 at
-  // n = 132, K = 7260 -- 85 us at 19 TFLOP/s): more, shorter slices, down to ~256 k each (K = 0: the caller did not say, the rule above stands)
-  if (K > 0 && tiles * ks < 256) ks = (int)std::max<int64_t>(ks, std::min<int64_t>(std::min<int64_t>(32, K / 256), (512 + tiles - 1) / tiles));
+  // n = 132, K = 7260 -- 85 us at 19 TFLOP/s): more, shorter slices, down to ~256 k each (k_aware; else the rule above stands)
+  if (k_aware && K > 0 && tiles * ks < 256) ks = (int)std::max<int64_t>(ks, std::min<int64_t>(std::min<int64_t>(32, K / 256), (512 + tiles - 1) / tiles));
+  return GemmPlan(rows, cols, K, cfg, ks);
 }
 
-// C = A B^T (both operands K-contiguous) whose consumer adds the split-K slabs itself: with ks > 1 the slices' partial products stay in slabs
-// [S][M][N] at C (no reduction pass), else C is the plain product with leading dimension ldc
+// The product `p` (planned in setup) as C = A B^T (both operands K-contiguous by default), whose consumer adds the split-K slabs itself: with S > 1 the slices'
+// partial products stay in slabs [S][M][N] at C (no reduction pass), else C is the plain product with leading dimension ldc
 struct SlabGemm { int S = 1; int64_t stride = 0, ld = 0; };
-static int gemm_slabs(int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, int cfg, int ks, SlabGemm& out,
-                      bool a_kc = true, bool b_kc = true) {
+static int gemm_slabs(const GemmPlan& p, const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, SlabGemm& out, bool a_kc = true, bool b_kc = true) {
   GemmDesc g{};
-  g.M = M; g.N = N; g.K = K; g.alpha = 1.0; g.beta = 0.0;
+  g.M = p.M; g.N = p.N; g.K = p.K; g.alpha = 1.0; g.beta = 0.0;
   g.A = A; g.lda = lda; g.a_kcontig = a_kc ? 1 : 0; g.B = B; g.ldb = ldb; g.b_kcontig = b_kc ? 1 : 0;
-  g.C = C; g.ldc = ldc; g.batch = 1; g.cfg = cfg; g.ksplit = ks;
-  out.S = gemm_slab_count(K, ks);
-  if (out.S > 1) { g.keep_slabs = 1; out.stride = M * N; out.ld = N; }
+  g.C = C; g.ldc = ldc; g.batch = 1; g.cfg = p.cfg; g.ksplit = p.ks;
+  out.S = p.S;
+  if (out.S > 1) { g.keep_slabs = 1; out.stride = p.M * p.N; out.ld = p.N; }
   else { out.stride = 0; out.ld = ldc; }
   return dev_gemm(g);
 }
 // tile configuration and K split of the Xw products (output only npair(o) x o^2, K = packed virtual pairs): 64 x 64 tiles and enough K slices for
 // ~2 workgroups per CU
-static void pick_xw_split(int64_t rows, int64_t oo, int64_t K, int& cfg, int& ks) {
-  cfg = -1; ks = 0;
-  if (K < 2048) return;
-  const int64_t tiles = ((rows + 63) / 64) * ((oo + 63) / 64);
-  cfg = 1;
-  ks = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(64, K / 256), (512 + tiles - 1) / tiles));
+static GemmPlan pick_xw_split(int64_t rows, int64_t oo, int64_t K) {
+  if (K < 2048) return GemmPlan(rows, oo, K, -1, 0);
+  const int cfg = GEMM_64x64;
+  const int64_t tiles = gemm_tile_count(cfg, rows, oo);
+  return GemmPlan(rows, oo, K, cfg, (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(64, K / 256), (512 + tiles - 1) / tiles)));
 }
-// The K split dev_gemm would pick by itself for a product with `tiles` output tiles (gemm_f64.hip launch_cfg), spelled out so that the caller can keep the slabs
-static int auto_ksplit(int64_t tiles, int64_t K) {
-  if (tiles >= 256 || K < 1024) return 0;
-  int64_t S = (768 + tiles - 1) / tiles;
-  if (S > K / 256) S = K / 256;
-  return S > 1 ? (int)S : 0;
-}
-// few-output, long-K products (Fvv', the two ovvv / ovoo terms of the T1 equation): tile configuration and K split; cfg < 0: the dispatcher's own choice, no slabs
-static void pick_long_k(int64_t M, int64_t N, int64_t K, int tile_m, int tile_n, int cfg_in, int& cfg, int& ks, bool many_slices = false) {
-  cfg = cfg_in; ks = 0;
-  if (cfg_in < 0) return;
-  ks = auto_ksplit(((M + tile_m - 1) / tile_m) * ((N + tile_n - 1) / tile_n), K);
+// few-output, long-K products (Fvv', the two ovvv / ovoo terms of the T1 equation) on the tile `cfg`, split over K as dev_gemm would split them by itself
+// (gemm_auto_ksplit) -- spelled out so that the caller can keep the slabs; cfg < 0: the dispatcher's own choice, no slabs
+static GemmPlan pick_long_k(int64_t M, int64_t N, int64_t K, int cfg, bool many_slices = false) {
+  if (cfg < 0) return GemmPlan(M, N, K, cfg, 0);
+  int ks = gemm_auto_ksplit(gemm_tile_count(cfg, M, N), K);
   // a result of one tile (small fragments) whose consumer adds the slabs with all its threads (ccsd_t1_assemble): slices of ~64-96 k instead of ~288 -- a
   // workgroup then runs 4-6 k-steps instead of 18, and there are hundreds of them (octane: 20 + 31 -> ~10 us each for the two T1 products).  (A scalar-FMA
   // kernel for these shapes -- one workgroup per slice out of LDS, no padded MFMA tile -- was measured slower than the tiled kernel on the same slices.)
   if (many_slices && ks > 1 && M <= 32 && N <= 32) ks = (int)std::min<int64_t>(512, K / 64);
+  return GemmPlan(M, N, K, cfg, ks);
+}
+// n_occ <= 32 columns / rows: 128 x 32 and 32 x 128 tiles instead of padding n_occ to a 64-wide tile
+static int tile_tall(int64_t o) { return (o <= 32) ? GEMM_128x32 : -1; }
+static int tile_wide(int64_t o) { return (o <= 32) ? GEMM_32x128 : -1; }
+
+// Every product of the CCSD update whose split-K slabs the consumer adds up itself, for a fragment of o occupied and v virtual orbitals (K of the packed
+// products: the row strides of the packed virtual pairs).  The (-) products of a fragment without antisymmetric pairs are planned with one row / column: they are never launched.
+CcsdGemmPlans ccsd_gemm_plans(int64_t o, int64_t v) {
+  int64_t ldp, ldm;
+  packed_pair_lds(v, ldp, ldm);
+  const int64_t oo = o * o, vv = v * v, nov = o * v;
+  const int64_t npo = o * (o + 1) / 2, nmo = std::max<int64_t>(o * (o - 1) / 2, 1), npv = v * (v + 1) / 2, nmv = std::max<int64_t>(v * (v - 1) / 2, 1);
+  CcsdGemmPlans p;
+  p.fvv = pick_long_k(v, v, oo * v, (v <= 256) ? GEMM_64x64 : -1);
+  p.pa = pick_long_k(o, v, o * vv, tile_wide(o), true);
+  p.pb = pick_long_k(o, v, o * v * o, tile_wide(o), true);
+  p.ladder_p = pick_pair_gemm(npo, npv, ldp);
+  p.ladder_m = pick_pair_gemm(nmo, nmv, ldm);
+  p.xw_p = pick_xw_split(npo, oo, ldp);
+  p.xw_m = pick_xw_split(nmo, oo, ldm);
+  p.x_p = pick_pair_gemm(npo, nov, ldp, true);      // (k_aware: their long K may ask for more slices)
+  p.x_m = pick_pair_gemm(nmo, nov, ldm, true);
+  return p;
 }
 // pp-ladder through the (+/-) pair-packed operands (see the comment in update_amps)
 int CcsdSolver::apply_ladder(const double* x, double* out, bool rows_packed, bool hh) {
@@ -440,20 +450,15 @@ int CcsdSolver::apply_ladder(const double* x, double* out, bool rows_packed, boo
     const int64_t npo = o * (o + 1) / 2, nmo = o * (o - 1) / 2, npv = v * (v + 1) / 2, nmv = v * (v - 1) / 2;
     const int64_t ldp = I_.ldp, ldm = I_.ldm;
     if (!rows_packed) QTRY(dev_ladder_pack_tau(o, v, x, LTp_, ldp, LTm_, ldm));
-    int cfg, ks;
     TimerScope lap_LADDER(TIMER_LADDER);
     // (split over K, the slices' partial products stay in slabs that the scatter below adds up: no reduction pass over the packed results)
     SlabGemm sp, sm;
-    pick_pair_gemm(npo, npv, cfg, ks);
-    if (cfg == 13 || cfg == 15) cfg += 10;      // same tiles under the ladder's own kernel symbol (profiles)
+    GemmPlan lp = plans_.ladder_p, lm = plans_.ladder_m;
+    lp.cfg = gemm_tile_ladder_symbol(lp.cfg); lm.cfg = gemm_tile_ladder_symbol(lm.cfg);      // same tiles under the ladder's own kernel symbol (profiles)
     QTRY(dev_region_begin());
-    QTRY(gemm_slabs(npo, npv, ldp, LTp_, ldp, I_.Vp, ldp, LRp_, ldp, cfg, ks, sp));
+    QTRY(gemm_slabs(lp, LTp_, ldp, I_.Vp, ldp, LRp_, ldp, sp));
     QTRY(dev_region_chain());
-    if (nmo > 0 && nmv > 0) {
-      pick_pair_gemm(nmo, nmv, cfg, ks);
-      if (cfg == 13 || cfg == 15) cfg += 10;
-      QTRY(gemm_slabs(nmo, nmv, ldm, LTm_, ldm, I_.Vm, ldm, LRm_, ldm, cfg, ks, sm));
-    }
+    if (nmo > 0 && nmv > 0) QTRY(gemm_slabs(lm, LTm_, ldm, I_.Vm, ldm, LRm_, ldm, sm));
     QTRY(dev_region_end());
     QTRY(lap_LADDER.close());
     if (hh) {
@@ -461,8 +466,8 @@ int CcsdSolver::apply_ladder(const double* x, double* out, bool rows_packed, boo
       //   HR+[P(ij),P(ab)] = sum_{k>=l} WA+[P(ij),P(kl)] LTp[P(kl),P(ab)],   HR-[Q(ij),Q(ab)] = sum_{k>l} WA-[Q(ij),Q(kl)] LTm[Q(kl),Q(ab)]
       // -- a quarter of the flops of the dense o^2 x v^2 x o^2 product; the scatter adds them to the pp-ladder rows (doubling the a = b
       // columns of HR+: LTp carries 1/2 there) and writes the sum as the first contribution to `out`
-      static const struct { int rows, cfg; } cand[] = {{224, 13}, {192, 15}, {160, 35}, {128, 0}, {64, 1}};
-      auto tile_for = [&](int64_t rows) { int best = -1; int64_t pad = -1; for (const auto& c : cand) { const int64_t q = (rows + c.rows - 1) / c.rows * c.rows; if (pad < 0 || q < pad) { pad = q; best = c.cfg; } } return best; };
+      static const int cand[] = {GEMM_224x128, GEMM_192x128, GEMM_160x128, GEMM_128x128, GEMM_64x64};
+      auto tile_for = [&](int64_t rows) { int best = -1; int64_t pad = -1; for (const int c : cand) { const int64_t r = gemm_tile_rows(c), q = (rows + r - 1) / r * r; if (pad < 0 || q < pad) { pad = q; best = c; } } return best; };
       QTRY(dev_region_begin());
       QTRY(gemm(npo, npv, npo, 1.0, WAp_, lwp_, true, LTp_, ldp, false, 0.0, HRp_, ldp, 1, 0, 0, 0, npv >= 2048 ? tile_for(npo) : -1));
       QTRY(dev_region_chain());
@@ -498,16 +503,13 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
   // ---- one- and two-index intermediates (energy-shifted: Foo - eps, Fvv - eps, ...)
   {  // Xw[i,j,k,l] = ovov[kcld] tau[ijcd] (the quadratic part of Woooo, added to it below) over the (+/-) packed (c,d) pairs:  X[ij] = Xp + Xm, X[ji] = Xp - Xm (i > j),
      //   Xp[P(ij),(kl)] = sum_{c>=d} LTp[P(ij),P(cd)] G+[(kl),P(cd)],  Xm[Q(ij),(kl)] = sum_{c>d} LTm G-   (LTp carries 1/2 on c = d, G+ is doubled there)
-    const int64_t npo = o * (o + 1) / 2, nmo = o * (o - 1) / 2, nmv = v * (v - 1) / 2;
-    auto split = [&](int64_t rows, int64_t K, int& cfg, int& ks) { pick_xw_split(rows, oo, K, cfg, ks); };
-    int cfg, ks;
+    const int64_t nmo = o * (o - 1) / 2, nmv = v * (v - 1) / 2;
     SlabGemm sp, sm;
-    split(npo, I_.ldp, cfg, ks);
     QTRY(dev_region_begin());
-    QTRY(gemm_slabs(npo, oo, I_.ldp, LTp_, I_.ldp, Gp_, I_.ldp, Xwp_, oo, cfg, ks, sp));
+    QTRY(gemm_slabs(plans_.xw_p, LTp_, I_.ldp, Gp_, I_.ldp, Xwp_, oo, sp));
     QTRY(dev_region_chain());
     if (nmo > 0) {
-      if (nmv > 0) { split(nmo, I_.ldm, cfg, ks); QTRY(gemm_slabs(nmo, oo, I_.ldm, LTm_, I_.ldm, Gm_, I_.ldm, Xwm_, oo, cfg, ks, sm)); }
+      if (nmv > 0) QTRY(gemm_slabs(plans_.xw_m, LTm_, I_.ldm, Gm_, I_.ldm, Xwm_, oo, sm));
       else QTRY(dev_fill(Xwm_, nmo * oo, 0.0));
     }
     QTRY(dev_region_end());
@@ -520,19 +522,15 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
   // Fvv'[a,c] = -sum tau[klxa] Loovv[klxc]  (64 x 64 tiles: split-K supplies the blocks; the slabs are added up -- with the sign -- by the pass that forms Lvv' below)
   SlabGemm sfvv;
   double fvv_scale = -1.0;
-  {
-    int cfg, ks;
-    pick_long_k(v, v, oo * v, 64, 64, (v <= 256) ? 1 : -1, cfg, ks);
-    if (ks > 1) QTRY(gemm_slabs(v, v, oo * v, tau_, v, Loovv_, v, Fvv_, v, cfg, ks, sfvv, false, false));
-    else { QTRY(gemm(v, v, oo * v, -1.0, tau_, v, false, Loovv_, v, false, 0.0, Fvv_, v, 1, 0, 0, 0, cfg)); fvv_scale = 1.0; }
-  }
+  if (plans_.fvv.ks > 1) QTRY(gemm_slabs(plans_.fvv, tau_, v, Loovv_, v, Fvv_, v, sfvv, false, false));
+  else { QTRY(gemm(v, v, oo * v, -1.0, tau_, v, false, Loovv_, v, false, 0.0, Fvv_, v, 1, 0, 0, 0, plans_.fvv.cfg)); fvv_scale = 1.0; }
   // Fov[k,c] = Lovov[(kc),:] . t1  and  Loo' = Foo' + Z[k,i], Z = LovooT[(ki),:] . t1: two matrix-vector passes, one launch
   QTRY(dev_gemv_rows_two(nov, nov, Lovov_, nov, t1, Fov_, 1.0, 0.0, oo, nov, LovooT_, nov, t1, Loo_, 1.0, 1.0));
   // The two t1-contractions of ovvv are formed ONCE per iteration (each is one pass over the 1.28 GB block) and serve the
   // ring intermediates, the X1 term and -- through their k = i traces -- the Y intermediate:
   // (n_occ <= 32 columns / rows: 128 x 32 and 32 x 128 tiles instead of padding n_occ to a 64-wide tile, which made these
   //  HBM-bound passes MFMA-bound)
-  const int cfg_tall = (o <= 32) ? 20 : -1, cfg_wide = (o <= 32) ? 21 : -1;
+  const int cfg_tall = tile_tall(o), cfg_wide = tile_wide(o);
   QTRY(dev_region_begin());
   QTRY(gemm(o * vv, o, v, 1.0, I_.ovvv, v, true, t1, v, true, 0.0, ZB_, o, 1, 0, 0, 0, cfg_tall));     // ZB[k,c,a,i] = ovvv[kcad] t1[id]
   QTRY(dev_region_chain());
@@ -550,20 +548,10 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
   SlabGemm spa, spb;
   double* PA = T1P_.p;
   QTRY(dev_region_begin());
-  {
-    int cfg, ks;
-    pick_long_k(o, v, o * vv, 32, 128, cfg_wide, cfg, ks, true);
-    if (ks > 1) QTRY(gemm_slabs(o, v, o * vv, R_, o * vv, I_.ovvv, v, PA, v, cfg, ks, spa, true, false));
-    else { QTRY(gemm(o, v, o * vv, 1.0, R_, o * vv, true, I_.ovvv, v, false, 0.0, PA, v, 1, 0, 0, 0, cfg)); spa.S = 1; }
-  }
+  QTRY(gemm_slabs(plans_.pa, R_, o * vv, I_.ovvv, v, PA, v, spa, true, false));      // (no split: the plain product)
   double* PB = PA + (int64_t)spa.S * nov;
   QTRY(dev_region_chain());
-  {
-    int cfg, ks;
-    pick_long_k(o, v, o * v * o, 32, 128, cfg_wide, cfg, ks, true);
-    if (ks > 1) QTRY(gemm_slabs(o, v, o * v * o, Lovoo_, o, T_, v, PB, v, cfg, ks, spb, false, false));
-    else { QTRY(gemm(o, v, o * v * o, 1.0, Lovoo_, o, false, T_, v, false, 0.0, PB, v, 1, 0, 0, 0, cfg)); spb.S = 1; }
-  }
+  QTRY(gemm_slabs(plans_.pb, Lovoo_, o, T_, v, PB, v, spb, false, false));
   QTRY(dev_region_end());
   // t1n = (Fvv'+Y)_ac t1[ic] - (Foo'+Z)_ki t1[ka] + Fov_kc t1[ic] t1[ka] + Fov_kc (2 t2[kica] - t2[ikca]) + (2 ovvo[kcai] - oovv[kiac]) t1[kc] + PA - PB:
   // the small products, the two passes over o^2 v^2 operands and the slab sums in one launch (a workgroup per element)
@@ -592,17 +580,12 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
   //   t1-dressing of Wvvvv folded on the tau side: -t1[kb] (tau[ijcd] ovvv[kdac])
   {  // X[i,j,k,a] = tau[ijcd] OVl[k,a,c,d] from the packed tau rows LTp/LTm that apply_ladder just built:
      //   X[ij] = Xp + Xm, X[ji] = Xp - Xm (i > j),  Xp = LTp OVp^T (c >= d),  Xm = LTm OVm^T (c > d)
-    const int64_t npo = o * (o + 1) / 2, nmo = o * (o - 1) / 2;
-    int cfg, ks;
+    const int64_t nmo = o * (o - 1) / 2;
     SlabGemm sp, sm;
-    pick_pair_gemm(npo, nov, cfg, ks, I_.ldp);
     QTRY(dev_region_begin());
-    QTRY(gemm_slabs(npo, nov, I_.ldp, LTp_, I_.ldp, OVp_, I_.ldp, Xp_, nov, cfg, ks, sp));
+    QTRY(gemm_slabs(plans_.x_p, LTp_, I_.ldp, OVp_, I_.ldp, Xp_, nov, sp));
     QTRY(dev_region_chain());
-    if (nmo > 0) {
-      pick_pair_gemm(nmo, nov, cfg, ks, I_.ldm);
-      QTRY(gemm_slabs(nmo, nov, I_.ldm, LTm_, I_.ldm, OVm_, I_.ldm, Xm_, nov, cfg, ks, sm));
-    }
+    if (nmo > 0) QTRY(gemm_slabs(plans_.x_m, LTm_, I_.ldm, OVm_, I_.ldm, Xm_, nov, sm));
     QTRY(dev_region_end());
     QTRY(dev_scatter_pm_rows(o, nov, Xp_, Xm_, X_, ovoo_ijka_, sp.S, sp.stride, sm.S, sm.stride));   // ... + ovoo[i,a,j,k]: the second term of A below, added on the way
   }
@@ -636,12 +619,12 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
   // (small fragments in a lock-step sweep, QEMB_LOCKSTEP_PEERS=1: `peers` products of this shape run in ONE grouped launch, enough to fill the chip with
   //  64 x 64 tiles.  Measured on six octane fragments, o v = 441: 294 such workgroups on 256 CUs are SLOWER than the 1176 of the 32 x 32 tile the
   //  dispatcher picks for a lone product -- 11.3 against 11.0 ms per sweep -- so the hint stays off.)
-  const int64_t ring_tiles64 = ((nov + 63) / 64) * ((nov + 63) / 64) * dev_gemm_peers();
+  const int64_t ring_tiles64 = gemm_tile_count(GEMM_64x64, nov, nov) * dev_gemm_peers();
   // (1024 <= o v < 2048, one mid-size fragment on the chip: 96 x 96 tiles with K in two slices -- 15 x 15 x 2 workgroups at o v = 1440, 119 us against the 151 us
   //  of 23 x 23 tiles of 64 x 64; tools/mid_gemm_bench.py.  QEMB_RING96=0: the 64 x 64 tiles, for A/B runs)
   static const bool ring96 = !(std::getenv("QEMB_RING96") && std::getenv("QEMB_RING96")[0] == '0');
   const bool mid_ring = ring96 && nov >= 1024 && nov < 2048 && dev_gemm_peers() == 1;
-  const int cfg_ring = (nov >= 2048) ? 4 : mid_ring ? 37 : (nov >= 256 && ring_tiles64 >= 200) ? 1 : -1;
+  const int cfg_ring = (nov >= 2048) ? GEMM_128x256 : mid_ring ? GEMM_96x96 : (nov >= 256 && ring_tiles64 >= 200) ? GEMM_64x64 : -1;
   auto ring = [&](double al, const double* A, const double* Bsym, double be, double* C) {
     return gemm(nov, nov, nov, al, A, nov, true, Bsym, nov, true, be, C, nov, 1, 0, 0, 0, cfg_ring, mid_ring ? 2 : 0);
   };

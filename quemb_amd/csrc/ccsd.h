@@ -44,6 +44,11 @@ int mo_transform_factor(int n, int o, int nf, int naux, const double* B_packed, 
 // functions against 41 ms for the four quarter transformations -- the times cross near naux = 11 n; 8 n leaves a margin)
 inline bool mo_factor_route_pays(int n, int naux) { return naux > 0 && (int64_t)naux <= 8 * (int64_t)n; }
 
+// the products of the CCSD update whose split-K slabs the consumer adds up: planned once per solver (CcsdSolver::setup), read by the launches
+// (Fvv', the two long-K terms of the T1 equation, then the (+/-) pairs of the pp-ladder, of Xw = ovov . tau and of the tau-side dressing X = tau . ovvv)
+struct CcsdGemmPlans { GemmPlan fvv, pa, pb, ladder_p, ladder_m, xw_p, xw_m, x_p, x_m; };
+CcsdGemmPlans ccsd_gemm_plans(int64_t o, int64_t v);
+
 class CcLambda;
 
 struct LockstepStats { long long merged_runs = 0, launches = 0, grouped = 0, operations = 0, max_group = 0; double ms_tapes = 0.0, ms_post = 0.0; };
@@ -107,6 +112,7 @@ class CcsdSolver {
   DBuf WAp_, WAm_, HRp_, HRm_;   // hole-hole ladder: (+/-) packed images of Woooo and its packed result rows
   int64_t lwp_ = 0, lwm_ = 0;    // leading dimensions of WAp_ / WAm_
   DBuf ZB_, ZC_;                 // ZB[k,c,a,i] = ovvv[kcad] t1[id],  ZC[k,i,a,c] = t1[id] ovvv[kdac]  (one ovvv pass each per iteration)
+  CcsdGemmPlans plans_;          // tile, K split and slab count of every product that keeps its slabs: sizes the buffers in setup(), launches in update_amps / apply_ladder
   DBuf Foo_, Fvv_, Fov_, Z_, Y_, Ytmp_, Loo_, Lvv_, Q_, Wo_, O1_, X_, scal_, LovooT_;
   std::vector<DeviceDIIS> diis_;
   bool first_ = true;
@@ -140,6 +146,6 @@ class CcsdSolver {
   double ecc_ = 0.0;
 };
 
-// tile configuration and split-K factor CcsdSolver picks for a "few packed pair rows x many columns" product (introspection for tests / tools)
-void pick_pair_gemm(int64_t rows, int64_t cols, int& cfg, int& ks, int64_t K = 0);
+// tile configuration and split-K factor CcsdSolver picks for a "few packed pair rows x many columns" product over K (k_aware: a long K may ask for more slices)
+GemmPlan pick_pair_gemm(int64_t rows, int64_t cols, int64_t K = 0, bool k_aware = false);
 }  // namespace qemb

@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <string>
 #include "../../include/qemb_hip_ops.h"
+#include "gemm_tiles.h"
 
 namespace qemb {
 
@@ -136,12 +137,29 @@ struct GemmDesc {
   int64_t a_slab = 0, a_slab_skip = 0;
 };
 inline int gemm_slab_count(int64_t K, int ksplit) {      // the K slices dev_gemm cuts for an explicit ksplit (32-aligned chunks)
-  if (ksplit <= 1) return 1;
+  if (ksplit <= 1 || K <= 0) return 1;
   int64_t chunk = (K + ksplit - 1) / ksplit;
   chunk = (chunk + 31) / 32 * 32;
   const int64_t S = (K + chunk - 1) / chunk;
   return S > 1 ? (int)S : 1;
 }
+// the ksplit dev_gemm asks for by itself when the output has too few tiles to occupy 256 CUs but K is long (the o x v, o x o, v x v shaped CCSD
+// intermediates contract over o*v^2 ... v^2 indices); 0: none.  A caller that keeps the slabs passes it on as its explicit ksplit.
+inline int gemm_auto_ksplit(int64_t tiles, int64_t K) {
+  if (tiles >= 256 || K < 1024) return 0;
+  int64_t S = (768 + tiles - 1) / tiles;
+  if (S > K / 256) S = K / 256;
+  return S > 1 ? (int)S : 0;
+}
+// A product planned ahead of its launch: the tile (cfg < 0: the dispatcher's choice), the K split, and the S = gemm_slab_count(K, ks) slabs of M x N that a
+// keep_slabs launch writes.  The buffer is sized and the product launched from the same plan.
+struct GemmPlan {
+  int64_t M = 0, N = 0, K = 0;
+  int cfg = -1, ks = 0, S = 1;
+  GemmPlan() = default;
+  GemmPlan(int64_t m, int64_t n, int64_t k, int cfg_, int ks_) : M(m), N(n), K(k), cfg(cfg_), ks(ks_), S(gemm_slab_count(k, ks_)) {}
+  int64_t elems() const { return (int64_t)S * M * N; }
+};
 int dev_gemm(const GemmDesc& g);
 // measurement hook: 2 M N K batch of every product issued (or recorded into a capture) by ANY host thread since the last reset -- the executed flops the size
 // sweep of bench.py divides by the iteration time (a captured update replayed k times counts once: read it around eager iterations)

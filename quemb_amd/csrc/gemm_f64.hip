@@ -644,20 +644,13 @@ static int launch_cfg(const GemmDesc& d, hipStream_t s) {
   g.ksplit = 1; g.kchunk = g.K > 0 ? g.K : 1;
   const long long tiles = (long long)g.tiles_m * g.tiles_n * d.batch;
   if (d.keep_slabs && (d.ksplit <= 1 || d.alpha != 1.0 || d.beta != 0.0 || d.batch != 1)) { set_error("dev_gemm: keep_slabs needs ksplit > 1, alpha = 1, beta = 0, batch = 1"); return QEMB_ERR_ARG; }
-  if (d.ksplit > 1) {
-    long long chunk = (d.K + d.ksplit - 1) / d.ksplit;
+  // (ksplit < 0: the caller wants NO split -- its product runs beside others that fill the chip)
+  const int want = d.ksplit > 1 ? d.ksplit : (d.ksplit == 0 && t_gemm_splitk_enabled) ? gemm_auto_ksplit(tiles, d.K) : 0;
+  if (want > 1) {
+    long long chunk = (d.K + want - 1) / want;
     chunk = (chunk + 31) / 32 * 32;
     const long long S = (d.K + chunk - 1) / chunk;
     if (S > 1 && S * d.batch <= 65535) { g.ksplit = (int)S; g.kchunk = (int)chunk; }
-  } else if (d.ksplit == 0 && t_gemm_splitk_enabled && tiles < 256 && d.K >= 1024) {      // (ksplit < 0: the caller wants NO split -- its product runs beside others that fill the chip)
-    long long S = (768 + tiles - 1) / tiles;
-    if (S > d.K / 256) S = d.K / 256;
-    if (S > 1) {
-      long long chunk = (d.K + S - 1) / S;
-      chunk = (chunk + 31) / 32 * 32;
-      S = (d.K + chunk - 1) / chunk;
-      if (S > 1 && S * d.batch <= 65535) { g.ksplit = (int)S; g.kchunk = (int)chunk; }
-    }
   }
   if (d.keep_slabs) {      // the slices' partial products go straight to the caller's slabs (gemm_slab_count(K, ksplit) of them, also when that is one)
     if (g.ksplit != gemm_slab_count(d.K, d.ksplit)) { set_error("dev_gemm: slab count mismatch"); return QEMB_ERR_ARG; }
@@ -704,6 +697,14 @@ static int launch_layout(const GemmDesc& d, hipStream_t s, bool vec2) {
   QEMB_GEMM_CASE(false, false)
 #undef QEMB_GEMM_CASE
   return QEMB_ERR_ARG;
+}
+
+// a tile of gemm_tiles.h by its id: the template arguments come from the table entry
+template <int ID, int TAG, int MODE>
+static int launch_tile(const GemmDesc& d, hipStream_t s, bool vec2) {
+  constexpr GemmTile t = gemm_tile(ID);
+  static_assert(t.wm > 0, "not a tile of gemm_tiles.h");
+  return launch_layout<t.wm, t.wn, t.waves_m, t.waves_n, t.bk, TAG, MODE>(d, s, vec2);
 }
 
 // 16-byte loads of an operand tile: an M/N-contiguous operand needs pairs that are entirely inside or outside the matrix and 16-byte aligned (even extent, ld,
@@ -881,7 +882,7 @@ static int dev_gemm_dispatch(const GemmDesc& d) {
   // tall products with 193..224 columns: ONE 224-wide column tile (128 x 224) instead of two 128-wide ones, 12.5 % of which would be padding
   // (from ~1000 row tiles on: with fewer, two 128 x 128 workgroups per CU overlap their short-K prologues and epilogues better -- U = t2 . Lvv,
   //  625 row tiles, K = 200: 156 us against 163 us)
-  if (vec2 && d.N > 192 && d.N <= 224 && d.M >= 128 * 1024) cfg = 34;
+  if (vec2 && fits_one_224_tile(d.N) && d.M >= 128 * 1024) cfg = GEMM_128x224;
   if (d.cfg >= 0) cfg = d.cfg;
   if (t_gemm_force_cfg >= 0) cfg = t_gemm_force_cfg;
   // 3xx (s_memtime stamps) and 4xx-6xx (ablation: WRONG products by construction) exist for tools/ only: unreachable unless the process
@@ -890,54 +891,32 @@ static int dev_gemm_dispatch(const GemmDesc& d) {
     static const bool diag = std::getenv("QEMB_GEMM_DIAGNOSTICS") != nullptr;
     if (!diag) { set_error("dev_gemm: tile configs >= 300 are diagnostic instantiations (set QEMB_GEMM_DIAGNOSTICS=1 in a measurement run)"); return QEMB_ERR_ARG; }
   }
-  // The large tiles run the MODE 1 main loop (explicit one-k-step-ahead LDS fragment reads, LDS stores spread behind the MFMA rows) when
-  // the operands allow 16-byte loads; their scalar-load variants, the single-column wave tiles and the small / skinny tiles, which are
-  // latency or HBM bound and want the two-tiles-deep register prefetch, keep the classic loop.
+  // every production tile of gemm_tiles.h, its classic-loop twin (+ 200) where the table says one exists, and the ladder-symbol twins
   switch (cfg) {
-    case 0: return launch_layout<4, 4, 2, 2, 16, 0, 1>(d, s, vec2);   // 128 x 128, 4 waves
-    case 1: return launch_layout<2, 2, 2, 2, 16, 0, 1>(d, s, vec2);   //  64 x  64, 4 waves
-    case 2: return launch_layout<1, 1, 2, 2, 32>(d, s, vec2);   //  32 x  32, 4 waves
-    case 4: return launch_layout<4, 4, 2, 4, 16, 0, 1>(d, s, vec2);   // 128 x 256, 8 waves
-    case 10: return launch_layout<14, 1, 1, 8, 16>(d, s, vec2); // 224 x 128, 8 waves: all packed (i>=j) rows of o = 20 in ONE tile
-    case 11: return launch_layout<7, 1, 1, 8, 16>(d, s, vec2);  // 112 x 128, 8 waves
-    case 12: return launch_layout<4, 1, 1, 8, 16>(d, s, vec2);  //  64 x 128, 8 waves
-    case 13: return launch_layout<7, 2, 2, 4, 16, 0, 1>(d, s, vec2);  // 224 x 128, 8 waves as 2 x 4: 9 LDS fragment reads per 14 MFMAs (15 for cfg 10)
-    case 15: return launch_layout<6, 2, 2, 4, 16, 0, 1>(d, s, vec2);  // 192 x 128, 8 waves as 2 x 4 (the 190 antisymmetric pair rows of o = 20)
-    case 33: return launch_layout<7, 2, 1, 4, 16, 0, 1>(d, s, vec2);  // 112 x 128, 4 waves, TWO workgroups per CU (66 KB of LDS each): short-K products
-    case 34: return launch_layout<2, 7, 4, 2, 16, 0, 1>(d, s, vec2);  // 128 x 224, 8 waves as 4 x 2 (2 x 7 MFMA tiles per wave): tall products with 192 < N <= 224
-    case 35: return launch_layout<5, 2, 2, 4, 16, 0, 1>(d, s, vec2);  // 160 x 128, 8 waves as 2 x 4 (5 x 2 MFMA tiles per wave): pair-row counts that 160 divides well (465 = npair(30))
-    case 36: return launch_layout<5, 2, 1, 4, 16, 0, 1>(d, s, vec2);  //  80 x 128, 4 waves as 1 x 4 (5 x 2 per wave), two workgroups per CU: the 66-80 packed pair rows of n_occ = 12 (mid-size fragments, round 5)
-    case 37: return launch_layout<3, 3, 2, 2, 16, 0, 1>(d, s, vec2);  //  96 x  96, 4 waves as 2 x 2 (3 x 3 per wave): square products of 1000-2000 rows and columns (the rings of mid-size fragments: 15 x 15 tiles at o v = 1440 fill 225 of 256 CUs in one round)
-    case 38: return launch_layout<3, 2, 1, 4, 16, 0, 1>(d, s, vec2);  //  48 x 128, 4 waves as 1 x 4 (3 x 2 per wave): the 36-45 packed pair rows of n_occ = 9 (round 5: the 80-row tile spent 44 % of its MFMAs on padding there)
-    case 236: return launch_layout<5, 2, 1, 4, 16>(d, s, vec2);
-    case 237: return launch_layout<3, 3, 2, 2, 16>(d, s, vec2);
-    case 20: return launch_layout<4, 1, 2, 2, 16>(d, s, vec2);   // 128 x  32, 4 waves: tall products with N = n_occ (the t1 contractions of ovvv)
-    case 21: return launch_layout<1, 4, 2, 2, 16>(d, s, vec2);   //  32 x 128, 4 waves: the same with M = n_occ
-    case 23: return launch_layout<7, 2, 2, 4, 16, 1, 1>(d, s, vec2);   // = 13 under its own kernel symbol (pp-ladder, + pairs)
-    case 25: return launch_layout<6, 2, 2, 4, 16, 1, 1>(d, s, vec2);   // = 15 under its own kernel symbol (pp-ladder, - pairs)
-    // the classic (MODE 0) main loop of EVERY tile that runs MODE 1 in production, cfg + 200: kept addressable for A/B measurements
-    // (tools/gemm_modes.py) and for the bit-for-bit comparison tests/test_gpu_ops.py::test_gemm_mode1_equals_classic_loop runs, so that a
-    // toolchain change that breaks the hand-counted LDS waits of MODE 1 is caught (same summation order: results must be identical)
+#define QEMB_IF_0(...)
+#define QEMB_IF_1(...) __VA_ARGS__
+#define QEMB_X(id, name, wm, wn, waves_m, waves_n, bk, mode1, classic) \
+    case id: return launch_tile<id, 0, mode1>(d, s, vec2);             \
+    QEMB_IF_##classic(case GEMM_CLASSIC + id: return launch_tile<id, 0, 0>(d, s, vec2);)
+    QEMB_GEMM_TILES(QEMB_X)
+#undef QEMB_X
+#define QEMB_X(id, name) case id: return launch_tile<GEMM_##name, 1, 1>(d, s, vec2);
+    QEMB_GEMM_LADDER_TWINS(QEMB_X)
+#undef QEMB_X
+#undef QEMB_IF_0
+#undef QEMB_IF_1
     // diagnostic instantiations (TAG 2): per-wave s_memtime stamps around the per-tile barrier, read by qemb_op_gemm_stamps
-    case 313: return launch_layout<7, 2, 2, 4, 16, 2, 1>(d, s, vec2);
-    case 315: return launch_layout<6, 2, 2, 4, 16, 2, 1>(d, s, vec2);
-    case 304: return launch_layout<4, 4, 2, 4, 16, 2, 1>(d, s, vec2);
+    case 313: return launch_tile<GEMM_224x128, 2, 1>(d, s, vec2);
+    case 315: return launch_tile<GEMM_192x128, 2, 1>(d, s, vec2);
+    case 304: return launch_tile<GEMM_128x256, 2, 1>(d, s, vec2);
     // ablation instantiations (WRONG results by construction; tools/gemm_ablation.py): 3 = no global loads in the main loop, 4 = half of the
     // A fragment reads, 5 = both -- what the clock the chip holds under the kernel owes to HBM / L2 traffic and to LDS reads
-    case 413: return launch_layout<7, 2, 2, 4, 16, 3, 1>(d, s, vec2);
-    case 513: return launch_layout<7, 2, 2, 4, 16, 4, 1>(d, s, vec2);
-    case 613: return launch_layout<7, 2, 2, 4, 16, 5, 1>(d, s, vec2);
-    case 404: return launch_layout<4, 4, 2, 4, 16, 3, 1>(d, s, vec2);
-    case 504: return launch_layout<4, 4, 2, 4, 16, 4, 1>(d, s, vec2);
-    case 604: return launch_layout<4, 4, 2, 4, 16, 5, 1>(d, s, vec2);
-    case 200: return launch_layout<4, 4, 2, 2, 16>(d, s, vec2);
-    case 201: return launch_layout<2, 2, 2, 2, 16>(d, s, vec2);
-    case 204: return launch_layout<4, 4, 2, 4, 16>(d, s, vec2);
-    case 213: return launch_layout<7, 2, 2, 4, 16>(d, s, vec2);
-    case 215: return launch_layout<6, 2, 2, 4, 16>(d, s, vec2);
-    case 233: return launch_layout<7, 2, 1, 4, 16>(d, s, vec2);
-    case 234: return launch_layout<2, 7, 4, 2, 16>(d, s, vec2);
-    case 235: return launch_layout<5, 2, 2, 4, 16>(d, s, vec2);
+    case 413: return launch_tile<GEMM_224x128, 3, 1>(d, s, vec2);
+    case 513: return launch_tile<GEMM_224x128, 4, 1>(d, s, vec2);
+    case 613: return launch_tile<GEMM_224x128, 5, 1>(d, s, vec2);
+    case 404: return launch_tile<GEMM_128x256, 3, 1>(d, s, vec2);
+    case 504: return launch_tile<GEMM_128x256, 4, 1>(d, s, vec2);
+    case 604: return launch_tile<GEMM_128x256, 5, 1>(d, s, vec2);
     default: set_error("dev_gemm: unknown tile config"); return QEMB_ERR_ARG;
   }
 }

@@ -123,14 +123,14 @@ inline int gemm_tn(int64_t M, int64_t N, int64_t K, double al, const double* A, 
 // 224-row tile holds all rows) the full product on the dispatcher's tile choice.
 inline int gemm_quarter_lower_rows(int n, int64_t inner, int64_t K, const double* C, const double* In, double* Out) {
   const int64_t ncol = (int64_t)n * inner;
-  if (!(n > 192 && n <= 224)) return gemm(n, ncol, K, 1.0, C, n, false, In, K, true, 0.0, Out, ncol);
-  static const struct { int rows, cfg; } tiles[] = {{224, 13}, {192, 15}, {128, 4}, {112, 33}, {64, 12}};
+  if (!fits_one_224_tile(n)) return gemm(n, ncol, K, 1.0, C, n, false, In, K, true, 0.0, Out, ncol);
+  static const int tiles[] = {GEMM_224x128, GEMM_192x128, GEMM_128x256, GEMM_112x128, GEMM_64x128_COL};
   int s0 = 0;
   for (int t = 0; t < 5 && s0 < n; ++t) {
-    const int s1 = (t + 1 < 5) ? std::min(n, std::max(s0, n - tiles[t + 1].rows)) : n;
+    const int s1 = (t + 1 < 5) ? std::min(n, std::max(s0, n - gemm_tile_rows(tiles[t + 1]))) : n;
     if (s1 > s0) {
       const int rc = gemm(n - s0, (int64_t)(s1 - s0) * inner, K, 1.0, C + s0, n, false, In + (int64_t)s0 * inner * K, K, true, 0.0,
-                          Out + (int64_t)s0 * ncol + (int64_t)s0 * inner, ncol, 1, 0, 0, 0, tiles[t].cfg);
+                          Out + (int64_t)s0 * ncol + (int64_t)s0 * inner, ncol, 1, 0, 0, 0, tiles[t]);
       if (rc) return rc;
     }
     s0 = s1;

@@ -432,6 +432,90 @@ def test_pair_gemm_tile_choice(hlib):
         assert 1 <= ks <= 8
 
 
+# (M, N, K, cfg, ksplit, slabs) of the nine slab-keeping products -- Fvv', PA, PB | ladder +/- | Xw +/- | tau-side X +/- -- per (n_occ, n_virt): recorded from the
+# commit before the plans existed, by calling its pick_* functions with the argument lists its CcsdSolver::setup() used to size the slab buffers
+_CCSD_GEMM_PLANS = {
+    (1, 1): ((1, 1, 1, 1, 0, 1), (1, 1, 1, 21, 0, 1), (1, 1, 1, 21, 0, 1),
+             (1, 1, 2, -1, 0, 1), (1, 1, 2, -1, 0, 1),
+             (1, 1, 2, -1, 0, 1), (1, 1, 2, -1, 0, 1),
+             (1, 1, 2, -1, 0, 1), (1, 1, 2, -1, 0, 1)),
+    (1, 5): ((5, 5, 5, 1, 0, 1), (1, 5, 25, 21, 0, 1), (1, 5, 5, 21, 0, 1),
+             (1, 15, 16, -1, 0, 1), (1, 10, 10, -1, 0, 1),
+             (1, 1, 16, -1, 0, 1), (1, 1, 10, -1, 0, 1),
+             (1, 5, 16, -1, 0, 1), (1, 5, 10, -1, 0, 1)),
+    (5, 1): ((1, 1, 25, 1, 0, 1), (5, 1, 5, 21, 0, 1), (5, 1, 25, 21, 0, 1),
+             (15, 1, 2, -1, 0, 1), (10, 1, 2, -1, 0, 1),
+             (15, 25, 2, -1, 0, 1), (10, 25, 2, -1, 0, 1),
+             (15, 5, 2, -1, 0, 1), (10, 5, 2, -1, 0, 1)),
+    (2, 2): ((2, 2, 8, 1, 0, 1), (2, 2, 8, 21, 0, 1), (2, 2, 8, 21, 0, 1),
+             (3, 3, 4, -1, 0, 1), (1, 1, 2, -1, 0, 1),
+             (3, 4, 4, -1, 0, 1), (1, 4, 2, -1, 0, 1),
+             (3, 4, 4, -1, 0, 1), (1, 4, 2, -1, 0, 1)),
+    (6, 30): ((30, 30, 1080, 1, 4, 4), (6, 30, 5400, 21, 84, 57), (6, 30, 1080, 21, 16, 12),
+              (21, 465, 466, -1, 0, 1), (15, 435, 436, -1, 0, 1),
+              (21, 36, 466, -1, 0, 1), (15, 36, 436, -1, 0, 1),
+              (21, 180, 466, -1, 0, 1), (15, 180, 436, -1, 0, 1)),
+    (9, 40): ((40, 40, 3240, 1, 12, 12), (9, 40, 14400, 21, 56, 50), (9, 40, 3240, 21, 12, 12),
+              (45, 820, 820, -1, 0, 1), (36, 780, 780, -1, 0, 1),
+              (45, 81, 820, -1, 0, 1), (36, 81, 780, -1, 0, 1),
+              (45, 360, 820, -1, 0, 1), (36, 360, 780, -1, 0, 1)),
+    (16, 64): ((64, 64, 16384, 1, 64, 64), (16, 64, 65536, 21, 256, 256), (16, 64, 16384, 21, 64, 64),
+               (136, 2080, 2080, 35, 8, 8), (120, 2016, 2016, 4, 8, 8),
+               (136, 256, 2080, 1, 8, 8), (120, 256, 2016, -1, 0, 1),
+               (136, 1024, 2080, 35, 8, 8), (120, 1024, 2016, 4, 8, 8)),
+    (20, 64): ((64, 64, 25600, 1, 100, 100), (20, 64, 81920, 21, 320, 320), (20, 64, 25600, 21, 100, 100),
+               (210, 2080, 2080, 13, 8, 8), (190, 2016, 2016, 15, 8, 8),
+               (210, 400, 2080, 1, 8, 8), (190, 400, 2016, -1, 0, 1),
+               (210, 1280, 2080, 13, 8, 8), (190, 1280, 2016, 15, 8, 8)),
+    (12, 120): ((120, 120, 17280, 1, 67, 60), (12, 120, 172800, 21, 675, 675), (12, 120, 17280, 21, 67, 60),
+                (78, 7260, 7260, 36, 8, 8), (66, 7140, 7140, 36, 8, 8),
+                (78, 144, 7260, 1, 28, 26), (66, 144, 7140, 1, 27, 25),
+                (78, 1440, 7260, 36, 28, 26), (66, 1440, 7140, 36, 27, 25)),
+    (20, 200): ((200, 200, 80000, 1, 48, 48), (20, 200, 800000, 21, 384, 379), (20, 200, 80000, 21, 312, 278),
+                (210, 20100, 20100, 13, 8, 8), (190, 19900, 19900, 15, 8, 8),
+                (210, 400, 20100, 1, 19, 19), (190, 400, 19900, 1, 25, 25),
+                (210, 4000, 20100, 13, 8, 8), (190, 4000, 19900, 15, 8, 8)),
+    (30, 190): ((190, 190, 171000, 1, 86, 85), (30, 190, 1083000, 21, 384, 381), (30, 190, 171000, 21, 384, 382),
+                (465, 18145, 18146, 35, 3, 3), (435, 17955, 17956, 13, 8, 8),
+                (465, 900, 18146, 1, 5, 5), (435, 900, 17956, 1, 5, 5),
+                (465, 5700, 18146, 35, 7, 7), (435, 5700, 17956, 13, 8, 8)),
+    (40, 180): ((180, 180, 288000, 1, 86, 86), (40, 180, 1296000, -1, 0, 1), (40, 180, 288000, -1, 0, 1),
+                (820, 16290, 16290, 13, 1, 1), (780, 16110, 16110, 35, 2, 2),
+                (820, 1600, 16290, 1, 2, 2), (780, 1600, 16110, 1, 2, 2),
+                (820, 7200, 16290, 13, 3, 3), (780, 7200, 16110, 35, 8, 8)),
+    (33, 70): ((70, 70, 76230, 1, 192, 184), (33, 70, 161700, -1, 0, 1), (33, 70, 76230, -1, 0, 1),
+               (561, 2485, 2486, 15, 8, 8), (528, 2415, 2416, 15, 8, 8),
+               (561, 1089, 2486, 1, 4, 4), (528, 1089, 2416, 1, 4, 4),
+               (561, 2310, 2486, 15, 8, 8), (528, 2310, 2416, 15, 8, 8)),
+    (20, 300): ((300, 300, 120000, -1, 0, 1), (20, 300, 1800000, 21, 256, 256), (20, 300, 120000, 21, 256, 250),
+                (210, 45150, 45150, 13, 5, 5), (190, 44850, 44850, 15, 8, 8),
+                (210, 400, 45150, 1, 19, 19), (190, 400, 44850, 1, 25, 25),
+                (210, 6000, 45150, 13, 8, 8), (190, 6000, 44850, 15, 8, 8)),
+}
+
+
+def _slab_count(K, ks):
+    if ks <= 1:
+        return 1
+    chunk = (-(-K // ks) + 31) // 32 * 32
+    return max(1, -(-K // chunk))
+
+
+def test_ccsd_gemm_plans_match_parent(hlib):
+    """the plans CcsdSolver sizes its slab buffers and launches its split-K products from (qemb_ccsd_gemm_plans: the function setup() calls) are the tiles,
+    K splits and slab counts the solver chose before they became one object -- tiny and degenerate fragments, the three golden fragments, n_occ > 32 (no
+    32-row tiles) and n_virt > 256 (Fvv' left to the dispatcher) included -- and every slab count is the one dev_gemm cuts for that K split."""
+    assert len(_CCSD_GEMM_PLANS) == 14
+    for (o, v), want in _CCSD_GEMM_PLANS.items():
+        buf = (C.c_int64 * 54)()
+        assert hlib.qemb_ccsd_gemm_plans(o, v, buf) == 0
+        got = tuple(tuple(buf[6 * i:6 * i + 6]) for i in range(9))
+        assert got == want, (o, v, got)
+        for M, N, K, cfg, ks, S in got:
+            assert S == _slab_count(K, ks), (o, v, K, ks, S)
+            assert S >= 1 and (ks > 1 or S == 1), (o, v, ks, S)
+
+
 def check_solve_batch_equals_one_by_one(lib, sizes=((8, 3, 3), (10, 4, 4), (7, 2, 2), (9, 3, 3), (6, 6, 2)), expect_grouped=False):
     """qemb_frag_solve_batch (fragment phases per stream, CCSD iterations in lock step) == qemb_frag_solve fragment by fragment, bit for bit:
     fragments of different sizes (they converge in different iterations and drop out of the lock step one by one), one without virtual

@@ -70,6 +70,14 @@ int qemb_pair_gemm_choice(int64_t rows, int64_t cols, int* cfg, int* ksplit);
  * tau-side X +/-.  Introspection for tests and tools, no device call */
 int qemb_ccsd_gemm_plans(int o, int v, int64_t* out);
 int qemb_set_gemm_ksplit(int ksplit);      /* explicit split-K factor for qemb_op_gemm (0 = automatic) */
+/* entry `index` (0, 1, ...) of the table of production tiles (csrc/gemm_tiles.h), in the table's order: its id, tile rows x cols, k-step, whether it runs
+ * the MODE 1 main loop on 16-byte loads, whether id + 200 addresses its classic loop, and the id of its pp-ladder twin (-1: none).  QEMB_ERR_ARG past
+ * the end.  Introspection for tests and tools, no device call */
+int qemb_gemm_tile_table(int index, int* id, int* rows, int* cols, int* bk, int* mode1, int* has_classic, int* ladder_twin);
+/* what the calling host thread's last FP64 MFMA product launched: the tile id, 16-byte (1) or 8-byte (0) operand loads, main loop (1 = MODE 1), K slices,
+ * the super-block walk (0 0: m-tiles fastest) and wide_c = 1 when the epilogue stores every C matrix of the launch in 16-byte pairs (ldc and N even, C
+ * 16-byte aligned; under split-K: of the workspace slabs).  The host-check library reports vec2 and wide_c of the descriptor and zeros for the rest */
+int qemb_gemm_last_launch(int* cfg, int* vec2, int* mode, int* ksplit, int* sb_m, int* sb_n, int* wide_c);
 /* out[sum ik*so[k]] = alpha*in[sum ik*si[k]] + beta*out[...], 0<=ik<dim[k], 4 dims                  */
 int qemb_op_copy4(const int64_t dim[4], const double* in, const int64_t si[4], double* out,
                   const int64_t so[4], double alpha, double beta);

@@ -32,6 +32,11 @@ int nsocc_guess(const double* Cproj, int n, int nocc, double* P_out, int* nsocc,
 }
 
 static thread_local int g_test_ksplit = 0;   // qemb_set_gemm_ksplit: split-K override of qemb_op_gemm (tests / tuning), per calling thread
+#ifdef QEMB_HOSTCHECK
+// The host-check build has no dispatcher: qemb_gemm_last_launch reports the two launch properties that are pure functions of the descriptor, by the rules the
+// real dispatcher uses (dev_ops.h), recorded where qemb_op_gemm builds the descriptor; no tile, loop or split is chosen there, so the rest stays zero
+static thread_local GemmLaunchRecord g_hostcheck_last{};
+#endif
 
 extern "C" {
 
@@ -73,6 +78,11 @@ int qemb_op_gemm(int64_t M, int64_t N, int64_t K, double alpha, const double* A,
                  int64_t strideA, const double* B, int64_t ldb, int b_kcontig, int64_t strideB, double beta,
                  double* C, int64_t ldc, int64_t strideC, int64_t batch) {
   GemmDesc g{M, N, K, alpha, beta, A, lda, a_kcontig, strideA, B, ldb, b_kcontig, strideB, C, ldc, strideC, batch, -1, g_test_ksplit};
+#ifdef QEMB_HOSTCHECK
+  g_hostcheck_last = GemmLaunchRecord{};
+  g_hostcheck_last.vec2 = gemm_desc_vec2(g) ? 1 : 0;
+  g_hostcheck_last.wide_c = gemm_wide_c(C, ldc, N, strideC, batch) ? 1 : 0;
+#endif
   return dev_gemm(g);
 }
 int qemb_op_gemm_probe(int64_t M, int64_t N, int64_t K, const double* A, int64_t lda, int a_kcontig, const double* B, int64_t ldb, int b_kcontig,
@@ -87,6 +97,34 @@ int qemb_op_gemm_stamps(int64_t M, int64_t N, int64_t K, const double* A, int64_
                         double* out7) {
   GemmDesc g{M, N, K, 1.0, 0.0, A, lda, 1, 0, B, ldb, 1, 0, C, ldc, 0, 1, cfg, ksplit};
   return dev_gemm_stamps(g, 8, out7);
+}
+int qemb_gemm_tile_table(int index, int* id, int* rows, int* cols, int* bk, int* mode1, int* has_classic, int* ladder_twin) {
+  GemmTileEntry e;
+  if (!gemm_tile_entry(index, &e)) { set_error("qemb_gemm_tile_table: index past the end of the table"); return QEMB_ERR_ARG; }
+  if (id) *id = e.id;
+  if (rows) *rows = e.rows;
+  if (cols) *cols = e.cols;
+  if (bk) *bk = e.bk;
+  if (mode1) *mode1 = e.mode1;
+  if (has_classic) *has_classic = e.has_classic;
+  if (ladder_twin) *ladder_twin = e.ladder_twin;
+  return QEMB_OK;
+}
+int qemb_gemm_last_launch(int* cfg, int* vec2, int* mode, int* ksplit, int* sb_m, int* sb_n, int* wide_c) {
+#ifdef QEMB_HOSTCHECK
+  const GemmLaunchRecord r = g_hostcheck_last;
+#else
+  GemmLaunchRecord r;
+  dev_gemm_last_launch(&r);
+#endif
+  if (cfg) *cfg = r.cfg;
+  if (vec2) *vec2 = r.vec2;
+  if (mode) *mode = r.mode;
+  if (ksplit) *ksplit = r.ksplit;
+  if (sb_m) *sb_m = r.sb_m;
+  if (sb_n) *sb_n = r.sb_n;
+  if (wide_c) *wide_c = r.wide_c;
+  return QEMB_OK;
 }
 int qemb_set_gemm_ksplit(int ks) { g_test_ksplit = ks; return QEMB_OK; }
 int qemb_set_gemm_config(int cfg) { dev_gemm_set_force_cfg(cfg); return QEMB_OK; }

@@ -161,6 +161,37 @@ struct GemmPlan {
   int64_t elems() const { return (int64_t)S * M * N; }
 };
 int dev_gemm(const GemmDesc& g);
+// What the C ABI refuses before any launch: a leading dimension smaller than the extent it strides over (rows would overlap, and the row clamp of the
+// loaders would read past the operand) and negative batch strides.  nullptr: the descriptor is sound.  (a_slab rows are not plain rows of lda; keep_slabs
+// ignores ldc.)
+inline const char* gemm_desc_error(const GemmDesc& d) {
+  if (d.a_slab <= 0 && d.lda < (d.a_kcontig ? d.K : d.M)) return "dev_gemm: lda is smaller than the contiguous extent of A";
+  if (d.ldb < (d.b_kcontig ? d.K : d.N)) return "dev_gemm: ldb is smaller than the contiguous extent of B";
+  if (!d.keep_slabs && d.ldc < d.N) return "dev_gemm: ldc is smaller than N";
+  if (d.strideA < 0 || d.strideB < 0 || d.strideC < 0) return "dev_gemm: negative batch stride";
+  return nullptr;
+}
+// 16-byte loads of an operand tile: an M/N-contiguous operand needs pairs that are entirely inside or outside the matrix and 16-byte aligned (even extent, ld,
+// batch stride; aligned base); a K-contiguous one takes any K and ld -- its pairs are read at 8-byte alignment and the odd last element of a row alone (round 5:
+// fragments with an odd n_occ n_virt ran the 8-byte kernels, and could not share a grouped launch with their even neighbours of a lock-step sweep).
+// relaxed = false: the round-4 rule (K-contiguous operands as strict as the others).
+inline bool gemm_operand_vec2_ok(const double* p, int64_t ld, int64_t stride, int64_t contig_extent, bool kcontig, bool relaxed = true) {
+  if (kcontig && relaxed) return (reinterpret_cast<uintptr_t>(p) & 7) == 0;
+  return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (ld % 2 == 0) && (stride % 2 == 0) && (contig_extent % 2 == 0);
+}
+inline bool gemm_desc_vec2(const GemmDesc& d, bool relaxed = true) {
+  return gemm_operand_vec2_ok(d.A, d.lda, d.strideA, d.a_kcontig ? d.K : d.M, d.a_kcontig != 0, relaxed) &&
+         gemm_operand_vec2_ok(d.B, d.ldb, d.strideB, d.b_kcontig ? d.K : d.N, d.b_kcontig != 0, relaxed);
+}
+// the epilogue's `wide` predicate (16-byte pair stores of C, gemm_f64.hip) restated on the host: true when EVERY one of the nz matrices C + z * strideC
+// takes the wide path
+inline bool gemm_wide_c(const double* C, int64_t ldc, int64_t N, int64_t strideC, int64_t nz) {
+  return (ldc % 2 == 0) && (N % 2 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0) && (nz <= 1 || strideC % 2 == 0);
+}
+// what the calling host thread's last dev_gemm launched (qemb_gemm_last_launch: lets a test know it ran the variant it was built for).  Kept beside the
+// launch, never inside its kernel arguments.  (The host-check build, which has no dispatcher, answers from the descriptor in api.cpp and does not call this.)
+struct GemmLaunchRecord { int cfg, vec2, mode, ksplit, sb_m, sb_n, wide_c; };
+void dev_gemm_last_launch(GemmLaunchRecord* out);
 // measurement hook: 2 M N K batch of every product issued (or recorded into a capture) by ANY host thread since the last reset -- the executed flops the size
 // sweep of bench.py divides by the iteration time (a captured update replayed k times counts once: read it around eager iterations)
 int dev_gemm_flop_count(double* flops, int reset);

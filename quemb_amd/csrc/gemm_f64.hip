@@ -51,6 +51,8 @@ static thread_local int t_gemm_force_cfg = -1;
 static thread_local int t_gemm_splitk_enabled = 1;
 static thread_local int t_gemm_peers = 1;
 static std::atomic<long long> g_gemm_flops{0};
+static thread_local GemmLaunchRecord t_gemm_last{};      // qemb_gemm_last_launch: written by the dispatcher and launch_cfg, read by tests
+void dev_gemm_last_launch(GemmLaunchRecord* out) { *out = t_gemm_last; }
 int dev_gemm_flop_count(double* flops, int reset) { if (flops) *flops = (double)g_gemm_flops.load(); if (reset) g_gemm_flops = 0; return QEMB_OK; }
 void dev_gemm_set_peers(int n) { t_gemm_peers = n > 1 ? n : 1; }
 int dev_gemm_peers() { return t_gemm_peers; }
@@ -669,6 +671,8 @@ static int launch_cfg(const GemmDesc& d, hipStream_t s) {
   }
   dim3 grid((unsigned)(g.tiles_m * g.tiles_n), (unsigned)(d.batch * g.ksplit), 1);
   dim3 block(WAVES_M * WAVES_N * 64, 1, 1);
+  t_gemm_last.mode = MODE; t_gemm_last.ksplit = g.ksplit; t_gemm_last.sb_m = g.sb_m; t_gemm_last.sb_n = g.sb_n;
+  t_gemm_last.wide_c = gemm_wide_c(g.C, g.ldc, g.N, g.strideC, grid.y) ? 1 : 0;      // of the C this launch writes: the workspace slabs under split-K
   if (g_gemm_cyc_on && g_gemm_cyc && (long long)grid.x * grid.y * (TAG == 2 ? 72 : 1) <= g_gemm_cyc_cap) { g.cyc = g_gemm_cyc; g_gemm_cyc_blocks = (long long)grid.x * grid.y; if (TAG == 2) g.cyc2 = g_gemm_cyc + (long long)grid.x * grid.y * (WAVES_M * WAVES_N) * 5; }
   QTRY(launch("dev_gemm", kern, grid, block, lds, s, g));
   if (g.ksplit > 1 && !d.keep_slabs) {
@@ -707,17 +711,11 @@ static int launch_tile(const GemmDesc& d, hipStream_t s, bool vec2) {
   return launch_layout<t.wm, t.wn, t.waves_m, t.waves_n, t.bk, TAG, MODE>(d, s, vec2);
 }
 
-// 16-byte loads of an operand tile: an M/N-contiguous operand needs pairs that are entirely inside or outside the matrix and 16-byte aligned (even extent, ld,
-// batch stride; aligned base); a K-contiguous one takes any K and ld -- its pairs are read at 8-byte alignment and the odd last element of a row alone (round 5:
-// fragments with an odd n_occ n_virt ran the 8-byte kernels, and could not share a grouped launch with their even neighbours of a lock-step sweep)
-static bool operand_vec2_ok(const double* p, int64_t ld, int64_t stride, int64_t contig_extent, bool kcontig) {
-  static const bool relaxed = !(std::getenv("QEMB_GEMM_VEC2_ODD") && std::atoi(std::getenv("QEMB_GEMM_VEC2_ODD")) == 0);      // (0: the round-4 rule, for A/B runs)
-  if (kcontig && relaxed) return (reinterpret_cast<uintptr_t>(p) & 7) == 0;
-  return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (ld % 2 == 0) && (stride % 2 == 0) &&
-         (contig_extent % 2 == 0);
+// 16-byte loads of an operand tile: the rule is gemm_operand_vec2_ok (dev_ops.h); QEMB_GEMM_VEC2_ODD=0 selects the round-4 rule, for A/B runs
+static bool gemm_vec2_relaxed() {
+  static const bool relaxed = !(std::getenv("QEMB_GEMM_VEC2_ODD") && std::atoi(std::getenv("QEMB_GEMM_VEC2_ODD")) == 0);
+  return relaxed;
 }
-
-
 
 // ---- calibration: v_mfma_f64_16x16x4_f64 issue rate of the whole chip, registers only (no LDS, no memory traffic) -----------
 // An UPPER bound for the tiled GEMMs: 16 independent accumulator chains per wave (the 7 x 2 ladder tile has 14, the 4 x 4 tile 16),
@@ -852,6 +850,7 @@ static int dev_gemm_dispatch(const GemmDesc& d) {
   if (d.M > 0x3fffffff || d.N > 0x3fffffff || d.K > 0x3fffffff) {
     set_error("dev_gemm: dimension too large"); return QEMB_ERR_ARG;
   }
+  if (const char* bad = gemm_desc_error(d)) { set_error(bad); return QEMB_ERR_ARG; }
   hipStream_t s = hip_stream();
   g_gemm_flops += 2ll * d.M * d.N * d.K * d.batch;
   {  // QEMB_GEMM_SHAPELOG=<file>: one line per product in launch order (M N K batch a_kcontig b_kcontig cfg ksplit) -- no timing, no synchronisation; a single-stream
@@ -864,8 +863,7 @@ static int dev_gemm_dispatch(const GemmDesc& d) {
       std::fflush(shapelog);
     }
   }
-  const bool vec2 = operand_vec2_ok(d.A, d.lda, d.strideA, d.a_kcontig ? d.K : d.M, d.a_kcontig != 0) &&
-                    operand_vec2_ok(d.B, d.ldb, d.strideB, d.b_kcontig ? d.K : d.N, d.b_kcontig != 0);
+  const bool vec2 = gemm_desc_vec2(d, gemm_vec2_relaxed());
   // tile choice: biggest tile that still gives the 256 CUs >= ~2 workgroups each; small problems
   // fall to 64x64 / 32x32 tiles so the grid is not a handful of blocks.
   const int64_t t128 = ((d.M + 127) / 128) * ((d.N + 127) / 128) * d.batch;
@@ -891,6 +889,8 @@ static int dev_gemm_dispatch(const GemmDesc& d) {
     static const bool diag = std::getenv("QEMB_GEMM_DIAGNOSTICS") != nullptr;
     if (!diag) { set_error("dev_gemm: tile configs >= 300 are diagnostic instantiations (set QEMB_GEMM_DIAGNOSTICS=1 in a measurement run)"); return QEMB_ERR_ARG; }
   }
+  t_gemm_last = GemmLaunchRecord{};
+  t_gemm_last.cfg = cfg; t_gemm_last.vec2 = vec2 ? 1 : 0;
   // every production tile of gemm_tiles.h, its classic-loop twin (+ 200) where the table says one exists, and the ladder-symbol twins
   switch (cfg) {
 #define QEMB_IF_0(...)

@@ -63,6 +63,24 @@ constexpr int gemm_tile_ladder_symbol(int cfg) {
     default: return cfg;
   }
 }
+// the table itself, entry by entry in the order it is written (qemb_gemm_tile_table: tests and tools enumerate the tiles from here, not from a list of their own)
+struct GemmTileEntry { int id, rows, cols, bk, mode1, has_classic, ladder_twin; };
+constexpr int gemm_tile_entries() {
+#define QEMB_X(id, name, wm, wn, waves_m, waves_n, bk, mode1, classic) +1
+  return 0 QEMB_GEMM_TILES(QEMB_X);
+#undef QEMB_X
+}
+inline bool gemm_tile_entry(int index, GemmTileEntry* e) {
+  static const GemmTileEntry table[] = {
+#define QEMB_X(id, name, wm, wn, waves_m, waves_n, bk, mode1, classic) \
+    {id, gemm_tile_rows(id), gemm_tile_cols(id), bk, mode1, classic, gemm_tile_ladder_symbol(id) != id ? gemm_tile_ladder_symbol(id) : -1},
+    QEMB_GEMM_TILES(QEMB_X)
+#undef QEMB_X
+  };
+  if (index < 0 || index >= gemm_tile_entries()) return false;
+  *e = table[index];
+  return true;
+}
 // 193..224 rows (columns) fit ONE 224-row (224-column) tile: 1.8 % padding at n = 220 instead of the 14 % of two 128-wide tiles
 constexpr bool fits_one_224_tile(int64_t n) { return n > gemm_tile_rows(GEMM_192x128) && n <= gemm_tile_rows(GEMM_224x128); }
 

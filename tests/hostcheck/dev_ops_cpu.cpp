@@ -74,6 +74,9 @@ int dev_gemm_probe(const GemmDesc&, double*, double*, long long*) { set_error("d
 static std::atomic<long long> g_gemm_flops{0};
 int dev_gemm_flop_count(double* flops, int reset) { if (flops) *flops = (double)g_gemm_flops.load(); if (reset) g_gemm_flops = 0; return QEMB_OK; }
 int dev_gemm(const GemmDesc& g0) {
+  if (g0.M <= 0 || g0.N <= 0 || g0.batch <= 0) return QEMB_OK;
+  if (g0.K < 0 || !g0.A || !g0.B || !g0.C) { set_error("dev_gemm: bad arguments"); return QEMB_ERR_ARG; }
+  if (const char* bad = gemm_desc_error(g0)) { set_error(bad); return QEMB_ERR_ARG; }
   g_gemm_flops += 2ll * g0.M * g0.N * g0.K * g0.batch;
   GemmDesc g = g0;
   if (g.keep_slabs) {      // slab form: the first slab receives the whole product, the others zeros (their sum is what the consumer forms)

@@ -317,8 +317,7 @@ int qemb_op_jacobi_eigh_in_basis(int64_t n, const double* F, const double* Cp, d
   QTRY(dev_d2h(&word, st.p, sizeof(double)));
   int sw; std::memcpy(&sw, &word, sizeof(int));
   if (sweeps) *sweeps = sw;
-  if (sw < 0) { set_error("Jacobi sweeps did not converge in 40 sweeps"); return QEMB_ERR_NOCONV; }
-  return QEMB_OK;
+  return jacobi_status_code(sw, "dev_jacobi_eigh_in_basis");
 }
 int qemb_op_scf_fock_small(int64_t n, const double* h, const double* J, const double* K, const double* D, double* F, double* err, double* scal2) { return dev_scf_fock_small(n, h, J, K, D, F, err, scal2); }
 int qemb_op_pack_density_sym(int64_t n, const double* D, double* Dp) { return dev_pack_density_sym(n, D, Dp); }

@@ -569,18 +569,30 @@ int dev_unpack_tril_pair_rows_ld(int64_t nr, int64_t n, int64_t ld, const double
 // ---- symmetric eigen / SVD by wavefront Jacobi (no MFMA) -----------------------------------------
 // A (n x n, symmetric, row-major, overwritten) -> eigenvalues w[n] ascending and eigenvectors in the
 // COLUMNS of V (n x n row-major).  sweeps_out (host int*) may be null.
+// A NaN or an infinity in the input of any routine of this group is QEMB_ERR_NUMERIC (found in the scale the routine computes first, before any sweep), never a
+// "converged" result.  dev_jacobi_eigh sweeps until nothing above the rotation threshold is left (n <= 80: the one-launch kernel measures what is left after a
+// sweep below 1e-10 and saves the confirming sweep; larger n: until a whole sweep rotates nothing).
 int dev_jacobi_eigh(int64_t n, double* A, double* w, double* V, int* sweeps_out);
 // The same with an early stop: the sweeps end once the largest normalised off-diagonal element met during a sweep is below `stop_below`
-// (what is left after that sweep is its square).  dev_jacobi_eigh uses 1e-10 -- nothing above the rotation threshold is left; a caller
+// (what is left after that sweep is its square -- for separated eigenvalues; on a graded spectrum the convergence is not quadratic, which is
+// why the one-launch kernels check what is left (<= max(thr, 1e3 stop_below^2 scale), else they sweep on) and dev_jacobi_eigh passes none to
+// the one-sided sweeps, which cannot check).  A caller
 // that will diagonalise again anyway (the cycles of an SCF before the last) can stop a sweep earlier.
 int dev_jacobi_eigh_until(int64_t n, double* A, double* w, double* V, int* sweeps_out, double stop_below);
+// status word of the one-launch eigensolvers (dev_jacobi_eigh_in_basis hands it back through device memory): sweeps used, or one of these
+enum { JACOBI_STATUS_NOCONV = -1, JACOBI_STATUS_NONFINITE = -2 };
+inline int jacobi_status_code(int st, const char* who) {
+  if (st == JACOBI_STATUS_NONFINITE) { set_error(std::string(who) + ": the matrix holds a NaN or an infinity"); return QEMB_ERR_NUMERIC; }
+  if (st < 0) { set_error(std::string(who) + ": Jacobi sweeps did not converge in 40 sweeps"); return QEMB_ERR_NOCONV; }
+  return QEMB_OK;
+}
 // One-sided Jacobi SVD of G (m x n row-major, m >= n), overwritten by U*diag(s) columns;
 // s[n] descending, V (n x n) right vectors in columns, U (m x n) left vectors in columns.
 // ---- fused steps of the fragment RHF of SMALL fragments (n <= dev_scf_fused_max(); 0: not available / switched off): see linalg_f64.hip
 int dev_scf_fused_max();
 // eigenproblem of F in the basis Cp (nullptr: as given): w ascending, C_out = Cp V (columns in that order), the same to C2_out (nullable; may be Cp), dm_out (nullable) =
-// 2 C_occ C_occ^T of the lowest nocc columns.  Asynchronous: *status_dev (device) receives the number of sweeps, or -1 when 40 sweeps did not converge -- read it at the
-// caller's next transfer.
+// 2 C_occ C_occ^T of the lowest nocc columns.  Asynchronous: *status_dev (device) receives the number of sweeps, or -1 when 40 sweeps did not converge, or -2 when F or Cp
+// holds a NaN or an infinity (nothing is written then) -- read it at the caller's next transfer and pass it through jacobi_status_code.
 int dev_jacobi_eigh_in_basis(int64_t n, const double* F, const double* Cp, double* w, double* C_out, double* C2_out, int nocc, double* dm_out, double stop_below,
                              int* status_dev);
 // F = h + J - K/2, err = F D - D F, scal2[0] = sum (h + F) o D, scal2[1] = sum err^2 (device)

@@ -120,8 +120,7 @@ static int rhf_loop(int n, int o, const double* h, const JkSource& src, double* 
   bool status_pending = false;
   auto check_status = [&](const double* word) {
     int st; std::memcpy(&st, word, sizeof(int));
-    if (st < 0) { set_error("Jacobi sweeps did not converge in 40 sweeps"); return (int)QEMB_ERR_NOCONV; }
-    return 0;
+    return jacobi_status_code(st, "dev_jacobi_eigh_in_basis (fragment SCF)");      // (a NaN Fock matrix -- a diverged DIIS step -- is QEMB_ERR_NUMERIC, not a converged eigensolve)
   };
   static const bool trace = std::getenv("QEMB_SCF_TRACE") != nullptr;
   auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };

@@ -488,8 +488,11 @@ int dev_pack_tril_rows(int64_t rows, int64_t n, const double* f, double* p) {
 // cyclic two-sided Jacobi (independent of the product's one-sided formulation)
 int dev_jacobi_eigh(int64_t n64, double* A, double* w, double* V, int* sweeps_out);
 int dev_jacobi_eigh_until(int64_t n64, double* A, double* w, double* V, int* sweeps_out, double) { return dev_jacobi_eigh(n64, A, w, V, sweeps_out); }
+static bool all_finite(const double* x, size_t count) { for (size_t t = 0; t < count; ++t) if (!std::isfinite(x[t])) return false; return true; }
 int dev_jacobi_eigh(int64_t n64, double* A, double* w, double* V, int* sweeps_out) {
   const int n = (int)n64;
+  // a NaN or an infinity is refused before any sweep, as in linalg_f64.hip (there it is found in the row sums of the scale)
+  if (!all_finite(A, (size_t)n * n)) { if (sweeps_out) *sweeps_out = JACOBI_STATUS_NONFINITE; return jacobi_status_code(JACOBI_STATUS_NONFINITE, "dev_jacobi_eigh"); }
   std::vector<double> a(A, A + (size_t)n * n), v((size_t)n * n, 0.0);
   for (int i = 0; i < n; ++i) v[(size_t)i * n + i] = 1.0;
   int sweep = 0;
@@ -518,6 +521,7 @@ int dev_jacobi_eigh(int64_t n64, double* A, double* w, double* V, int* sweeps_ou
 int dev_scf_fused_max() { return 80; }
 int dev_jacobi_eigh_in_basis(int64_t n64, const double* F, const double* Cp, double* w, double* C_out, double* C2_out, int nocc, double* dm_out, double, int* status_dev) {
   const int n = (int)n64;
+  if (!all_finite(F, (size_t)n * n) || (Cp && !all_finite(Cp, (size_t)n * n))) { *status_dev = JACOBI_STATUS_NONFINITE; return 0; }      // the status word, as the kernel
   std::vector<double> a((size_t)n * n), v((size_t)n * n), c((size_t)n * n);
   for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) {
     double t = 0;
@@ -558,6 +562,7 @@ int dev_pack_density_sym(int64_t n64, const double* D, double* Dp) {
 int dev_jacobi_svd(int64_t m64, int64_t n64, double* G, double* s, double* U, double* V, int* sweeps_out) {
   // via eigh of G^T G (adequate for a mock; the product does a genuine one-sided Jacobi)
   const int m = (int)m64, n = (int)n64;
+  if (!all_finite(G, (size_t)m * n)) { if (sweeps_out) *sweeps_out = JACOBI_STATUS_NONFINITE; return jacobi_status_code(JACOBI_STATUS_NONFINITE, "dev_jacobi_svd"); }
   std::vector<double> gtg((size_t)n * n, 0.0), w(n), vv((size_t)n * n);
   for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) { double t = 0; for (int k = 0; k < m; ++k) t += G[(size_t)k * n + i] * G[(size_t)k * n + j]; gtg[(size_t)i * n + j] = t; }
   dev_jacobi_eigh(n, gtg.data(), w.data(), vv.data(), sweeps_out);
@@ -574,7 +579,7 @@ int dev_cholesky_lower(int64_t n64, double* A) {
   for (int j = 0; j < n; ++j) {
     double d = A[(size_t)j * n + j];
     for (int k = 0; k < j; ++k) d -= A[(size_t)j * n + k] * A[(size_t)j * n + k];
-    if (!(d > 0)) { set_error("Cholesky: matrix is not positive definite"); return QEMB_ERR_NUMERIC; }
+    if (!(d > 0 && std::isfinite(d))) { set_error("dev_cholesky_lower (Cholesky): matrix is not positive definite, or holds a NaN or an infinity"); return QEMB_ERR_NUMERIC; }
     A[(size_t)j * n + j] = std::sqrt(d);
     for (int i = j + 1; i < n; ++i) { double t = A[(size_t)i * n + j]; for (int k = 0; k < j; ++k) t -= A[(size_t)i * n + k] * A[(size_t)j * n + k]; A[(size_t)i * n + j] = t / A[(size_t)j * n + j]; }
     for (int k = j + 1; k < n; ++k) A[(size_t)j * n + k] = 0.0;
@@ -588,6 +593,16 @@ int dev_tri_inverse_lower(int64_t n64, const double* L, double* X) {
     X[(size_t)j * n + j] = 1.0 / L[(size_t)j * n + j];
     for (int i = j + 1; i < n; ++i) { double t = 0; for (int k = j; k < i; ++k) t += L[(size_t)i * n + k] * X[(size_t)k * n + j]; X[(size_t)i * n + j] = -t / L[(size_t)i * n + i]; }
   }
+  // one Newton step X <- X + (I - X L) X with the residual accumulated in extended precision, as linalg_f64.hip (there in double-double): the substitution alone
+  // bounds L X - I, not X L - I
+  std::vector<double> R((size_t)n * n, 0.0), RX((size_t)n * n, 0.0);
+  for (int i = 0; i < n; ++i) for (int j = 0; j <= i; ++j) {
+    long double t = (i == j) ? 1.0L : 0.0L;
+    for (int k = j; k <= i; ++k) t -= (long double)X[(size_t)i * n + k] * L[(size_t)k * n + j];
+    R[(size_t)i * n + j] = (double)t;
+  }
+  for (int i = 0; i < n; ++i) for (int j = 0; j <= i; ++j) { double t = 0; for (int k = j; k <= i; ++k) t += R[(size_t)i * n + k] * X[(size_t)k * n + j]; RX[(size_t)i * n + j] = t; }
+  for (size_t t = 0; t < (size_t)n * n; ++t) X[t] += RX[t];
   return 0;
 }
 

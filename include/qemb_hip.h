@@ -438,6 +438,19 @@ int qemb_df_set_ints_from_cholesky(qemb_df_t df, qemb_int_basis_t basis, double 
  * mirror image: the matrices are symmetric to the bit and two calls give the same bits (no atomics).  natm < 0, or V_out with natm > 0 and NULL xyz / Z: QEMB_ERR_ARG;
  * an orbital shell with l > 2: QEMB_ERR_UNSUPPORTED naming the shell and its l. */
 int qemb_int1e(qemb_int_basis_t basis, int natm, const double* xyz, const double* Z, double* S_out, double* T_out, double* V_out);
+/* ---- Edmiston-Ruedenberg localisation on factorised integrals (csrc/api.cpp, kernels csrc/loc_ops.hip) ----
+ * Rotates the m columns of C (host, N x m row-major, orthonormal under the overlap) so that sum_i (ii|ii) = sum_P sum_i (B^P_ii)^2 is maximal, with B the 3-index factor of
+ * the columns from the dense tensor of `df` (fitted: the metric applied; Cholesky: the vectors themselves) -- the quarter transforms of qemb_df_transform_factor, unpacked
+ * on the device to the stack [naux][m][m], which the joint-diagonalisation sweeps of qemb_hip_ops.h take with K = naux.  The integrals are the factorised ones: exact to the factor's own
+ * error.  U_host (m x m): the rotation, C_loc = C U.  *f_before / *f_after: the functional; *sweeps, *converged as for those sweeps.  The footprint -- stack, U,
+ * workspace and the transform's buffers -- is checked against the limit set there and the free memory before anything is allocated (QEMB_ERR_ALLOC naming
+ * K = naux and m).  A semi-sparse or periodic context, or m > 512 (the limit of the sweeps, named in the message): QEMB_ERR_UNSUPPORTED. */
+int qemb_df_localize_er(qemb_df_t df, const double* C, int m, double stop_angle, int max_sweeps, double* U_host, int* sweeps, double* f_before, double* f_after, int* converged);
+
+/* The dipole integrals <a|r - origin|b> of the same functions: out[3][N][N] (host; x, y, z), origin: 3 doubles (Bohr).  From the 1-D overlaps the overlap already
+ * forms, one order up in the ket: <i|x - o|j> = s_{i,j+1} + (B_x - o) s_ij.  The same shell-pair ownership as qemb_int1e: every element is stored once with its
+ * mirror image (symmetric to the bit, the same bits on every call).  An orbital shell with l > 2: QEMB_ERR_UNSUPPORTED, as there. */
+int qemb_int1e_dipole(qemb_int_basis_t basis, const double* origin, double* out);
 
 /* ---- J and K of the AO-level mean field from the resident dense 3-index tensor of a DF context (csrc/ao2mo.cpp: DfContext::jk) ----
  * With T = (P|mu nu) resident as [naux][N][N] and the inverse metric factor Linv (B = Linv T):  J[mu,nu] = sum_P B[P,mu nu] sum_{la si} B[P,la si] D[la,si],

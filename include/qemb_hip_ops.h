@@ -273,6 +273,18 @@ int qemb_op_fci_rdm12(int n, int nsocc, const double* c_dev, int cumulant, doubl
 int qemb_op_fci_sigma_timed(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev, double* ms3);
 int qemb_op_fci_links(int n, int nsocc, int64_t* ns, int* nlink, int32_t* strings_host, int32_t* links_host);
 
+/* ---- orbital localisation (csrc/loc_ops.hip): joint diagonalisation of a stack of symmetric matrices by Jacobi sweeps -- Boys (K = 3 dipole matrices), Pipek-Mezey
+ * (K = atoms) and Edmiston-Ruedenberg on a 3-index factor (K = naux) are this one problem.  Q_dev [K][m][m] and U_dev [m][m] are device pointers.  On return U is
+ * orthogonal (started from the identity: the orbitals rotate as C U), Q^k = U^T Q^k U, and *f = sum_k sum_i (Q^k_ii)^2 is maximal over plane rotations.  A sweep is
+ * the m - 1 rounds of the circle-method tournament; the pair (p, q) turns by 4 theta = atan2(2 sum_k a_k d_k, sum_k d_k^2 - sum_k a_k^2), a_k = Q^k_pq,
+ * d_k = (Q^k_pp - Q^k_qq) / 2.  Stops after a sweep whose largest |theta| < stop_angle (*converged = 1) or after max_sweeps (max_sweeps = 0: nothing is rotated and
+ * *f is that of the input).  m <= 1 or K = 0: U = 1.  m > 512 (the launch-per-round variant's limit, csrc/loc_core.h): QEMB_ERR_UNSUPPORTED naming it.  All sums run in one fixed order: two calls give the same bits.  Before anything is allocated the footprint
+ * (qemb_op_joint_diag_bytes: 8 (K m^2 + 2 m^2) and the workspace) is checked against the limit of qemb_op_joint_diag_mem_limit (bytes < 0: none; calling host thread)
+ * and the workspace against the free memory: QEMB_ERR_ALLOC naming K and m.  *in_lds (nullable) of _bytes: 1 when the one-workgroup variant (stack in LDS) serves. */
+int qemb_op_joint_diag(int64_t K, int64_t m, double* Q_dev, double* U_dev, double stop_angle, int max_sweeps, int* sweeps, double* f, int* converged);
+int qemb_op_joint_diag_bytes(int64_t K, int64_t m, int64_t* bytes, int* in_lds);
+int qemb_op_joint_diag_mem_limit(int64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

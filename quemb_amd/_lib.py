@@ -161,6 +161,10 @@ def _declare(lib):
     f("qemb_op_pack_density_sym", I, L, P, P)
     f("qemb_op_jacobi_svd", I, L, L, P, P, P, P, C.POINTER(I))
     f("qemb_op_cholesky_lower", I, L, P)
+    f("qemb_op_joint_diag", I, L, L, P, P, D, I, C.POINTER(I), C.POINTER(D), C.POINTER(I))
+    f("qemb_df_localize_er", I, V, P, I, D, I, P, C.POINTER(I), C.POINTER(D), C.POINTER(D), C.POINTER(I))
+    f("qemb_op_joint_diag_bytes", I, L, L, C.POINTER(L), C.POINTER(I))
+    f("qemb_op_joint_diag_mem_limit", I, L)
     f("qemb_op_tri_inverse_lower", I, L, P, P)
     f("qemb_comm_unique_id", I, P)
     f("qemb_comm_init", I, I, I, P)
@@ -263,6 +267,7 @@ def _declare(lib):
     f("qemb_op_cd_permute", I, L, L, P, P, I, P)
     f("qemb_op_df_get_ints", I, V, P, C.POINTER(I))
     f("qemb_int1e", I, V, I, P, P, P, P, P)
+    f("qemb_int1e_dipole", I, V, P, P)
     f("qemb_df_jk", I, V, I, P, P, I, I, I, P, P)
     f("qemb_df_jk_bytes", I, V, I, I, C.POINTER(L))
     f("qemb_df_jk_mem_limit", I, V, L)

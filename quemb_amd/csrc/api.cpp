@@ -16,6 +16,7 @@
 #include "int3c.h"
 #include "int4c.h"
 #include "cd_core.h"
+#include "loc_core.h"
 #include <mutex>
 #include <set>
 
@@ -323,6 +324,60 @@ int qemb_op_scf_fock_small(int64_t n, const double* h, const double* J, const do
 int qemb_op_pack_density_sym(int64_t n, const double* D, double* Dp) { return dev_pack_density_sym(n, D, Dp); }
 int qemb_op_jacobi_svd(int64_t m, int64_t n, double* G, double* s, double* U, double* V, int* sweeps) { return dev_jacobi_svd(m, n, G, s, U, V, sweeps); }
 int qemb_op_cholesky_lower(int64_t n, double* A) { return dev_cholesky_lower(n, A); }
+// orbital localisation: the guard, then the sweeps (loc_ops.hip)
+static thread_local int64_t g_joint_diag_limit = -1;
+int qemb_op_joint_diag_mem_limit(int64_t bytes) { g_joint_diag_limit = bytes; return QEMB_OK; }
+int qemb_op_joint_diag_bytes(int64_t K, int64_t m, int64_t* bytes, int* in_lds) {
+  if (K < 0 || m < 0 || !bytes) { set_error("qemb_op_joint_diag_bytes: bad arguments"); return QEMB_ERR_ARG; }
+  *bytes = (int64_t)loc::footprint_bytes(K, m);
+  if (in_lds) *in_lds = loc::in_lds(K, m) ? 1 : 0;
+  return QEMB_OK;
+}
+// the one guard of the localisation calls: the footprint (stack, U, workspace, and what the caller forms the stack with) against the limit, what is still to be
+// allocated against the free memory
+static int joint_diag_guard(const char* who, int64_t K, int64_t m, double extra_bytes, double to_allocate) {
+  size_t free_b = 0, total_b = 0;
+  QTRY(dev_mem_info(&free_b, &total_b));
+  const double need = loc::footprint_bytes(K, m) + extra_bytes;
+  if ((g_joint_diag_limit >= 0 && need > (double)g_joint_diag_limit) || to_allocate > (double)free_b) {
+    set_error(std::string(who) + ": with K = " + std::to_string(K) + " and m = " + std::to_string(m) + " the stack, U and the workspace take " + std::to_string(need * 1e-9) +
+              " GB (" + std::to_string(to_allocate * 1e-9) + " GB still to allocate), more than the " +
+              std::to_string((g_joint_diag_limit >= 0 && (double)g_joint_diag_limit < (double)free_b ? (double)g_joint_diag_limit : (double)free_b) * 1e-9) + " GB they may take");
+    return QEMB_ERR_ALLOC;
+  }
+  return QEMB_OK;
+}
+int qemb_op_joint_diag(int64_t K, int64_t m, double* Q_dev, double* U_dev, double stop_angle, int max_sweeps, int* sweeps, double* f, int* converged) {
+  QTRY(loc::check_joint_diag("qemb_op_joint_diag", K, m, Q_dev != nullptr, U_dev != nullptr, stop_angle, max_sweeps));
+  QTRY(joint_diag_guard("qemb_op_joint_diag", K, m, 0.0, 8.0 * (double)loc::work_doubles(K, m)));
+  return dev_joint_diag(K, m, Q_dev, U_dev, stop_angle, max_sweeps, sweeps, f, converged);
+}
+// Edmiston-Ruedenberg on the factorised integrals: the 3-index factor of the columns C from the quarter transforms of the DF transform (DfContext::transform with no
+// 4-index product), unpacked to the stack Q[P][i][j] = B^P_ij on the device, then the sweeps with K = naux
+int qemb_df_localize_er(qemb_df_t df, const double* C_host, int m, double stop_angle, int max_sweeps, double* U_host, int* sweeps, double* f_before, double* f_after, int* converged) {
+  if (!df || !C_host || !U_host) { set_error("qemb_df_localize_er: null argument"); return QEMB_ERR_ARG; }
+  const DfContext* d = reinterpret_cast<const DfContext*>(df);
+  if (d->Usp.p || d->Lpq_im.p) { set_error("qemb_df_localize_er: a semi-sparse or periodic context holds no dense real 3-index tensor"); return QEMB_ERR_UNSUPPORTED; }
+  if ((!d->Linv.p && !d->identity_metric) || !d->Lpq.p || d->N <= 0 || d->naux <= 0) { set_error("qemb_df_localize_er: metric and 3-index integrals must be set"); return QEMB_ERR_ARG; }
+  if (m <= 0 || m > d->N) { set_error("qemb_df_localize_er: need 0 < m <= N"); return QEMB_ERR_ARG; }
+  const int64_t K = d->naux, N = d->N, np = (int64_t)m * (m + 1) / 2;
+  QTRY(loc::check_joint_diag("qemb_df_localize_er", K, m, true, true, stop_angle, max_sweeps));      // (the stack and U are this call's own buffers)
+  const double transform_b = 8.0 * ((double)K * m * N + (double)K * m * m + (d->identity_metric ? 1.0 : 2.0) * (double)K * np + (double)N * m);
+  QTRY(joint_diag_guard("qemb_df_localize_er", K, m, transform_b, transform_b + loc::footprint_bytes(K, m)));
+  DBuf dC, bb, Q, U;
+  QTRY(dC.alloc(N * m));
+  QTRY(dev_h2d(dC, C_host, sizeof(double) * N * m));
+  QTRY(d->transform(dC, m, nullptr, nullptr, 0.0, &bb));
+  QTRY(Q.alloc(K * m * m));
+  QTRY(dev_unpack_tril_rows(K, m, bb, Q));
+  bb.release();
+  QTRY(U.alloc((int64_t)m * m));
+  int cv0 = 0;
+  QTRY(dev_joint_diag(K, m, Q, U, stop_angle, 0, nullptr, f_before, &cv0));
+  QTRY(dev_joint_diag(K, m, Q, U, stop_angle, max_sweeps, sweeps, f_after, converged));
+  return dev_d2h(U_host, U, sizeof(double) * m * m);
+}
+
 int qemb_op_tri_inverse_lower(int64_t n, const double* L, double* Linv) { return dev_tri_inverse_lower(n, L, Linv); }
 int qemb_op_boys(int m_max, int64_t n, const double* x, double* out) { QTRY(dev_boys(m_max, n, x, out)); return dev_sync(); }
 int qemb_op_int4c_class(int la, int lb, int lc, int ld, const void* bf_a, const void* bf_b, const void* bf_c, const void* bf_d, const double* c2s, double* out_host) {
@@ -811,6 +866,10 @@ int qemb_int2c2e(qemb_int_basis_t auxbasis, double* out, int out_on_device) {
 int qemb_int1e(qemb_int_basis_t basis, int natm, const double* xyz, const double* Z, double* S_out, double* T_out, double* V_out) {
   IntBasis* o = live_basis(basis, "qemb_int1e"); if (!o) return QEMB_ERR_ARG;
   return int1e_fill(*o, natm, xyz, Z, S_out, T_out, V_out);
+}
+int qemb_int1e_dipole(qemb_int_basis_t basis, const double* origin, double* out) {
+  IntBasis* o = live_basis(basis, "qemb_int1e_dipole"); if (!o) return QEMB_ERR_ARG;
+  return int1e_dipole_fill(*o, origin, out);
 }
 // ---- four-centre AO integrals from the basis (int4c.cpp) ----
 int qemb_int4c2e(qemb_int_basis_t basis, int sym, double thresh, double* out, int out_on_device) {

@@ -484,6 +484,11 @@ int dev_int4c_add_transpose(int64_t m, double* A);
 //                 largest d of shell pair w (rows row0[w] .. + cnt[w]) and dmax[0] = their maximum in two stages (partials: (nsp + 255) / 256 doubles)
 //   unpack:       out[k][mu][nu] = L[k * ld + pos[pair(mu, nu)]]: the [M][N][N] image of a DF context from plan-row order, every element once
 int dev_cd_gather_cols(int64_t rows, int64_t ncols, const double* in, int64_t ldi, const int32_t* idx, double* out, int64_t ldo);
+// Orbital localisation as joint diagonalisation (loc_ops.hip; arithmetic, angle rule and the limits of the two variants: loc_core.h).  Q [K][m][m] symmetric, U [m][m]:
+// on return U is orthogonal (started from the identity), Q^k = U^T Q^k U and f = sum_k sum_i (Q^k_ii)^2 is at a maximum over plane rotations.  Sweeps until the largest
+// |theta| of a sweep is below stop_angle (*converged = 1) or max_sweeps are done (0: nothing is rotated, f is that of the input).  m <= 1 or K = 0: U = 1, converged.
+// A NaN or an infinity in the stack: QEMB_ERR_NUMERIC.  Waits for the result (the outputs are host scalars).
+int dev_joint_diag(int64_t K, int64_t m, double* Q, double* U, double stop_angle, int max_sweeps, int* sweeps, double* f, int* converged);
 int dev_cd_panel_factor(const double* E, int64_t ld, const int32_t* srow, int n, double thr, const double* d, double* T, int32_t* piv, int32_t* rank, double* work);
 int dev_cd_new_rows(int64_t np, int n, int r, const double* E, int64_t ld, const double* T, const int32_t* piv, double* Lnew, int64_t ldl);
 int dev_cd_diag_update(int64_t np, int r, const double* Lnew, int64_t ldl, const int32_t* piv, const int32_t* srow, double* d, int64_t nsp, const int32_t* row0, const int32_t* cnt,

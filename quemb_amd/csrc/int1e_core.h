@@ -4,6 +4,7 @@
 // Mole.one_electron(); it sits on boys / rtable / hermite_e of int3c_core.h the way int4c_core.h does.
 //   S_ab = sum_prim ca cb K_ab sx sy sz,  s_ij the 1-D overlaps by the Obara-Saika recursion from s_00 = sqrt(pi / p)
 //   T_ab = sum_prim ca cb K_ab (tx sy sz + sx ty sz + sx sy tz),  t_ij = -2 b^2 s_{i,j+2} + b (2j + 1) s_ij - j (j - 1) / 2 s_{i,j-2}
+//   <a|x - o_x|b> = sum_prim ca cb K_ab (s_{i,j+1} + (B_x - o_x) s_ij) sy sz  (x - o_x = (x - B_x) + (B_x - o_x)), likewise y and z: the 1-D overlaps S forms, one order up
 //   V_ab = sum_C -Z_C sum_prim ca cb K_ab 2 pi / p sum_{tuv} E^x_t E^y_u E^z_v R_tuv(p, P - C)
 // The work of a shell pair is dealt to kLanes lanes: lane w takes the items w, w + kLanes, .. of the list (primitive pair) for S and T and (primitive pair, atom), the
 // atom fastest, for V, and keeps a private Cartesian block of at most 36 doubles.  The kLanes partial blocks are added up by a binary tree in a fixed order
@@ -22,7 +23,7 @@ using int3c::hidx;
 
 constexpr int kLanes = 64;                 // one gfx950 wavefront
 constexpr int kMaxBlock = 36;              // ncart(2)^2
-enum Kind { kOverlap = 0, kKinetic = 1, kNuclear = 2 };
+enum Kind { kOverlap = 0, kKinetic = 1, kNuclear = 2, kDipoleX = 3, kDipoleY = 4, kDipoleZ = 5, kKinds = 6 };
 
 struct Args {
   const Shell* sh;             // the shells of the basis (device)
@@ -33,7 +34,8 @@ struct Args {
   int natm;
   const double* xyz;           // 3 natm: the nuclei (Bohr)
   const double* Z;             // natm: their charges
-  double* out[3];              // S, T, V (N x N each; a null matrix is not computed)
+  double* out[kKinds];         // S, T, V, then <a|x - o_x|b>, <a|y - o_y|b>, <a|z - o_z|b> (N x N each; a null matrix is not computed)
+  double origin[3];            // o of the dipole integrals (Bohr)
   int64_t N;
 };
 
@@ -52,9 +54,10 @@ QEMB_I3_HD void overlap_1d(double h, double XPA, double XPB, double s00, double*
     }
 }
 
-// lane's share of the Cartesian block acc[ia * ncart(LB) + ib] of S (KIND = kOverlap) or T (kKinetic): the primitive pairs lane, lane + nlanes, ..
+// lane's share of the Cartesian block acc[ia * ncart(LB) + ib] of S (KIND = kOverlap), T (kKinetic) or a dipole component (kDipoleX ..): the primitive pairs lane,
+// lane + nlanes, ..
 template <int LA, int LB, int KIND>
-QEMB_I3_HD void st_partial(const Shell& A, const Shell& B, int lane, int nlanes, double* acc) {
+QEMB_I3_HD void st_partial(const Shell& A, const Shell& B, const double* origin, int lane, int nlanes, double* acc) {
   constexpr int ncB = ncart(LB), W = LB + 3;
   for (int k = 0; k < ncart(LA) * ncB; ++k) acc[k] = 0.0;
   const double AB[3] = {A.r[0] - B.r[0], A.r[1] - B.r[1], A.r[2] - B.r[2]};
@@ -86,6 +89,9 @@ QEMB_I3_HD void st_partial(const Shell& A, const Shell& B, int lane, int nlanes,
             const double sx = s[0][ax * W + bx], sy = s[1][ay * W + by], sz = s[2][az * W + bz];
             double v;
             if (KIND == kKinetic) v = t[0][ax * (LB + 1) + bx] * sy * sz + sx * t[1][ay * (LB + 1) + by] * sz + sx * sy * t[2][az * (LB + 1) + bz];
+            else if (KIND == kDipoleX) v = (s[0][ax * W + bx + 1] + (B.r[0] - origin[0]) * sx) * sy * sz;
+            else if (KIND == kDipoleY) v = sx * (s[1][ay * W + by + 1] + (B.r[1] - origin[1]) * sy) * sz;
+            else if (KIND == kDipoleZ) v = sx * sy * (s[2][az * W + bz + 1] + (B.r[2] - origin[2]) * sz);
             else v = sx * sy * sz;
             acc[ia * ncB + ib] += pref * v;
           }
@@ -148,8 +154,11 @@ template <int LA, int LB>
 QEMB_I3_HD void partial(int kind, const Args& g, int64_t k, int lane, int nlanes, double* acc) {
   const Shell& A = g.sh[g.pa[k]];
   const Shell& B = g.sh[g.pb[k]];
-  if (kind == kOverlap) st_partial<LA, LB, kOverlap>(A, B, lane, nlanes, acc);
-  else if (kind == kKinetic) st_partial<LA, LB, kKinetic>(A, B, lane, nlanes, acc);
+  if (kind == kOverlap) st_partial<LA, LB, kOverlap>(A, B, g.origin, lane, nlanes, acc);
+  else if (kind == kKinetic) st_partial<LA, LB, kKinetic>(A, B, g.origin, lane, nlanes, acc);
+  else if (kind == kDipoleX) st_partial<LA, LB, kDipoleX>(A, B, g.origin, lane, nlanes, acc);
+  else if (kind == kDipoleY) st_partial<LA, LB, kDipoleY>(A, B, g.origin, lane, nlanes, acc);
+  else if (kind == kDipoleZ) st_partial<LA, LB, kDipoleZ>(A, B, g.origin, lane, nlanes, acc);
   else v_partial<LA, LB>(A, B, g.natm, g.xyz, g.Z, lane, nlanes, acc);
 }
 

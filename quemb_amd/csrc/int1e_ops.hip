@@ -3,7 +3,7 @@
 // One kernel instantiation per orbital pair class (l_a >= l_b <= 2); one wavefront (a 64-thread workgroup) per shell pair of the class.  The nuclear attraction
 // is the expensive part -- work per shell pair ~ atoms x primitive pairs -- so the lanes stride over the (primitive pair, atom) items, each keeping a private
 // Cartesian block of at most 36 doubles; the 64 blocks are added by a shuffle tree in a fixed order, lane 0 applies the Cartesian -> spherical matrices and stores
-// the block and its mirror image.  S and T run through the same three steps with the primitive pairs as items.  No atomics: every element is stored once.
+// the block and its mirror image.  S, T and the three dipole components run through the same three steps with the primitive pairs as items.  No atomics: every element is stored once.
 // The compiler's resource report of the six classes is in DESIGN.md section 4, "DF mean field on the device".
 #include "hip_common.h"
 #include "int_dispatch.h"
@@ -19,7 +19,7 @@ __global__ void __launch_bounds__(kLanes) int1e_class_kernel(const Args g) {
   const int64_t k = blockIdx.x;
   const int lane = threadIdx.x;
   double acc[int3c::ncart(LA) * int3c::ncart(LB)];
-  for (int kind = 0; kind < 3; ++kind) {
+  for (int kind = 0; kind < kKinds; ++kind) {
     double* out = g.out[kind];
     if (!out) continue;      // uniform over the grid
     partial<LA, LB>(kind, g, k, lane, kLanes, acc);

@@ -15,7 +15,7 @@ int dev_int1e_class(int la, int lb, const int1e::Args& g) {
     constexpr int nb = int3c::ncart(A()) * int3c::ncart(B());
     double part[kLanes][kMaxBlock];
     for (int64_t k = 0; k < g.npair; ++k)
-      for (int kind = 0; kind < 3; ++kind) {
+      for (int kind = 0; kind < kKinds; ++kind) {
         if (!g.out[kind]) continue;
         for (int lane = 0; lane < kLanes; ++lane) partial<A(), B()>(kind, g, k, lane, kLanes, part[lane]);
         for (int off = kLanes / 2; off > 0; off >>= 1)

@@ -207,13 +207,13 @@ int int2c_fill(const IntBasis& aux, double* out) {
   return dev_sync();
 }
 
-// S, T and V of the basis: shell pairs I >= J grouped by pair class, one launch per class (one wavefront per shell pair), the matrices assembled on the device
-// and copied out.  A null output is not computed.
-int int1e_fill(const IntBasis& orb, int natm, const double* xyz_host, const double* Z_host, double* S_host, double* T_host, double* V_host) {
-  if (natm < 0 || (V_host && natm > 0 && (!xyz_host || !Z_host))) { set_error("qemb_int1e: the nuclear attraction needs natm >= 0 centres and charges"); return QEMB_ERR_ARG; }
-  QTRY(check_orbital(orb, "qemb_int1e"));
-  double* host[3] = {S_host, T_host, V_host};
-  if (!S_host && !T_host && !V_host) return QEMB_OK;
+// S, T, V and the dipole matrices of the basis: shell pairs I >= J grouped by pair class, one launch per class (one wavefront per shell pair), the matrices
+// assembled on the device and copied out.  A null output is not computed.  host: the int1e::kKinds matrices in the order of int1e::Kind.
+static int int1e_run(const IntBasis& orb, int natm, const double* xyz_host, const double* Z_host, const double* origin, double* const* host, const char* who) {
+  QTRY(check_orbital(orb, who));
+  bool any = false;
+  for (int k = 0; k < int1e::kKinds; ++k) any = any || host[k];
+  if (!any) return QEMB_OK;
   std::map<int, PairClass> cls;      // key la * 8 + lb
   for (int I = 0; I < orb.nshell; ++I)
     for (int J = 0; J <= I; ++J) {
@@ -229,24 +229,39 @@ int int1e_fill(const IntBasis& orb, int natm, const double* xyz_host, const doub
   }
   QTRY(pool.upload());
   const int64_t n2 = (int64_t)orb.nao * orb.nao;
-  DBuf nuc, out[3];
-  if (V_host && natm > 0) {
+  DBuf nuc, out[int1e::kKinds];
+  if (host[int1e::kNuclear] && natm > 0) {
     QTRY(nuc.alloc(4 * (int64_t)natm));
     QTRY(dev_h2d(nuc, xyz_host, sizeof(double) * 3 * natm));
     QTRY(dev_h2d(nuc.p + 3 * natm, Z_host, sizeof(double) * natm));
   }
   int1e::Args g{};
   g.sh = orb.dev(); g.c2s = orb.dc2s; g.natm = natm; g.xyz = nuc.p; g.Z = nuc.p ? nuc.p + 3 * natm : nullptr; g.N = orb.nao;
-  for (int k = 0; k < 3; ++k)
+  for (int d = 0; d < 3; ++d) g.origin[d] = origin ? origin[d] : 0.0;
+  for (int k = 0; k < int1e::kKinds; ++k)
     if (host[k]) { QTRY(out[k].alloc(n2)); g.out[k] = out[k]; }
   for (auto& kv : cls) {
     const PairClass& c = kv.second;
     g.pa = pool.p32(c.o_pa); g.pb = pool.p32(c.o_pb); g.npair = (int64_t)c.pa.size();
     if (int rc = dev_int1e_class(kv.first / 8, kv.first % 8, g)) { dev_sync(); return rc; }      // earlier launches still read the index lists
   }
-  for (int k = 0; k < 3; ++k)
+  for (int k = 0; k < int1e::kKinds; ++k)
     if (host[k]) QTRY(dev_d2h(host[k], out[k], sizeof(double) * n2));
   return dev_sync();      // the index lists are released on return
+}
+
+int int1e_fill(const IntBasis& orb, int natm, const double* xyz_host, const double* Z_host, double* S_host, double* T_host, double* V_host) {
+  if (natm < 0 || (V_host && natm > 0 && (!xyz_host || !Z_host))) { set_error("qemb_int1e: the nuclear attraction needs natm >= 0 centres and charges"); return QEMB_ERR_ARG; }
+  double* const host[int1e::kKinds] = {S_host, T_host, V_host, nullptr, nullptr, nullptr};
+  return int1e_run(orb, natm, xyz_host, Z_host, nullptr, host, "qemb_int1e");
+}
+
+// <a|r - origin|b>: out_host[3][N][N]
+int int1e_dipole_fill(const IntBasis& orb, const double* origin, double* out_host) {
+  if (!origin || !out_host) { set_error("qemb_int1e_dipole: origin and out are needed"); return QEMB_ERR_ARG; }
+  const int64_t n2 = (int64_t)orb.nao * orb.nao;
+  double* const host[int1e::kKinds] = {nullptr, nullptr, nullptr, out_host, out_host + n2, out_host + 2 * n2};
+  return int1e_run(orb, 0, nullptr, nullptr, origin, host, "qemb_int1e_dipole");
 }
 
 int int3c_block(int la, int lb, int lp, const BfRecord* A, const BfRecord* B, const BfRecord* P, const double* c2s_host, double* out_host) {

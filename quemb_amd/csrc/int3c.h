@@ -62,6 +62,8 @@ int int2c_fill(const IntBasis& aux, double* out_dev);
 // S, T and V = sum_C -Z_C <a|1/r_C|b> of the orbital basis into host arrays (N x N each; a null one is skipped): same normalisation, component order and
 // Cartesian -> spherical matrices as Mole.one_electron().  natm nuclei at xyz_host (3 natm, Bohr) with charges Z_host.  Orbital shells beyond d: QEMB_ERR_UNSUPPORTED.
 int int1e_fill(const IntBasis& orb, int natm, const double* xyz_host, const double* Z_host, double* S_host, double* T_host, double* V_host);
+// the dipole integrals <a|r - origin|b> of the same basis, out_host[3][N][N]: the same shell-pair ownership, every element stored once with its mirror image
+int int1e_dipole_fill(const IntBasis& orb, const double* origin, double* out_host);
 // one explicit block (qemb_op_int3c_class): out_host[(a * (2 lb + 1) + b) * (2 lP + 1) + m]
 int int3c_block(int la, int lb, int lp, const BfRecord* A, const BfRecord* B, const BfRecord* P, const double* c2s_host, double* out_host);
 

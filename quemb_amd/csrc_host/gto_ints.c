@@ -149,6 +149,36 @@ void gto_one_electron(int nbf, const bf_t* bf, int natm, const double* atm_xyz, 
     }
 }
 
+/* dipole integrals <a|r_d - origin_d|b>, d = x, y, z: with r_d = (r_d - P_d) + P_d the direction d takes the Hermite terms E_1 + (P_d - origin_d) E_0, the
+ * other two their overlap term E_0.  out[3][nbf][nbf], every element stored once with its mirror. */
+static void prim_dipole(const double A[3], const int la[3], double a, const double B[3], const int lb[3], double b, const double origin[3], double out[3]) {
+  const double p = a + b, pre = pow(M_PI / p, 1.5);
+  double e0[3], e1[3];
+  for (int d = 0; d < 3; ++d) {
+    e0[d] = Ecoef(la[d], lb[d], 0, A[d] - B[d], a, b);
+    e1[d] = Ecoef(la[d], lb[d], 1, A[d] - B[d], a, b) + ((a * A[d] + b * B[d]) / p - origin[d]) * e0[d];
+  }
+  out[0] = pre * e1[0] * e0[1] * e0[2];
+  out[1] = pre * e0[0] * e1[1] * e0[2];
+  out[2] = pre * e0[0] * e0[1] * e1[2];
+}
+
+void gto_dipole(int nbf, const bf_t* bf, const double* origin, double* out) {
+#pragma omp parallel for schedule(dynamic)
+  for (int i = 0; i < nbf; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double r[3] = {0, 0, 0};
+      for (int pa = 0; pa < bf[i].nprim; ++pa)
+        for (int pb = 0; pb < bf[j].nprim; ++pb) {
+          double w[3];
+          prim_dipole(bf[i].ctr, bf[i].lmn, bf[i].ex[pa], bf[j].ctr, bf[j].lmn, bf[j].ex[pb], origin, w);
+          const double c = bf[i].co[pa] * bf[j].co[pb];
+          for (int d = 0; d < 3; ++d) r[d] += c * w[d];
+        }
+      for (int d = 0; d < 3; ++d) out[((size_t)d * nbf + i) * nbf + j] = out[((size_t)d * nbf + j) * nbf + i] = r[d];
+    }
+}
+
 /* primitive-pair data: exponent sum, centre, Hermite coefficients per direction (t <= MAXLPAIR) times the contraction coefs */
 typedef struct { double p, P[3], Ex[MAXLPAIR + 1], Ey[MAXLPAIR + 1], Ez[MAXLPAIR + 1], c; int tx, ty, tz; } ppair_t;
 

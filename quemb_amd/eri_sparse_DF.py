@@ -131,18 +131,26 @@ def transform_sparse_DF_integral_hip(mf, Fobjs, auxbasis, AO_coeff_epsilon: floa
     return S_abs
 
 
+def dense_df_context(mol, auxbasis, lib=None, integral_backend: str = "host"):
+    """The dense fitted context of `mol` in `auxbasis`: metric and (P|mu nu) from the device kernels (integral_backend="hip": written into the resident tensor) or
+    from the host source.  The caller frees it."""
+    auxmol = make_auxmol(mol, auxbasis)
+    if _int_backend(integral_backend):
+        return et.DFContext.from_mol(mol, auxmol, lib=lib)
+    df = et.DFContext(j2c=int2c2e(auxmol), lib=lib)
+    try:
+        df.set_ints(aux_e2(mol, auxmol), mol.nao, "pqL")
+    except Exception:
+        df.free()
+        raise
+    return df
+
+
 def integral_direct_DF_hip(mf, Fobjs, auxbasis, lib=None, factor_only: bool = False, integral_backend: str = "host"):
     """molbe/eri_onthefly.py:45-145 (`int-direct-DF`): dense (mu nu|P), fragment transform, fit with the Cholesky factor of (P|Q).  No
     auxiliary-index blocking: the blocks of :18-42 exist to stay inside host RAM; naux N^2 doubles fit in HBM."""
-    mol = mf.mol
-    auxmol = make_auxmol(mol, auxbasis)
-    if _int_backend(integral_backend):      # metric and (P|mu nu) from the device kernels, written into the resident tensor
-        df = et.DFContext.from_mol(mol, auxmol, lib=lib)
-    else:
-        df = et.DFContext(j2c=int2c2e(auxmol), lib=lib)
+    df = dense_df_context(mf.mol, auxbasis, lib=lib, integral_backend=integral_backend)
     try:
-        if not _int_backend(integral_backend):
-            df.set_ints(aux_e2(mol, auxmol), mol.nao, "pqL")
         for f in Fobjs:
             df.transform(f.TA, frag=f.dev, want_host=False, factor_only=factor_only)
     finally:

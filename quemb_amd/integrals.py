@@ -233,6 +233,18 @@ class Mole:
                              S.ctypes.data_as(C.c_void_p), T.ctypes.data_as(C.c_void_p), V.ctypes.data_as(C.c_void_p))
         return self._sph2(S), self._sph2(T), self._sph2(V)
 
+    def dipole(self, origin=(0.0, 0.0, 0.0)):
+        """<a|r - origin|b>: (3, nao, nao), from the host library (gto_dipole)"""
+        lib = _load()
+        n = self.ncart
+        out = np.zeros((3, n, n))
+        o = np.ascontiguousarray(origin, dtype=float)
+        if o.shape != (3,):
+            raise ValueError("origin: three Cartesian coordinates (Bohr)")
+        lib.gto_dipole(n, self._arr(), o.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+        out = np.array([self._sph2(x) for x in out])
+        return 0.5 * (out + out.transpose(0, 2, 1))      # the Cartesian blocks are symmetric to the bit; the product with c2s is made so again
+
     def eri_s1(self):
         lib = _load()
         n = self.ncart
@@ -322,6 +334,16 @@ class DeviceBasis:
         S, T, V = np.empty((N, N)), np.empty((N, N)), np.empty((N, N))
         _lib.check(self.lib.qemb_int1e(self.h, len(self._Z), self._xyz.ctypes.data, self._Z.ctypes.data, S.ctypes.data, T.ctypes.data, V.ctypes.data), "qemb_int1e", self.lib)
         return S, T, V
+
+    def dipole(self, origin=(0.0, 0.0, 0.0)):
+        """<a|r - origin|b> from the device kernel (qemb_int1e_dipole): (3, N, N), the arrays of `Mole.dipole()`.  Symmetric to the bit."""
+        from . import _lib
+        o = np.ascontiguousarray(origin, dtype=float)
+        if o.shape != (3,):
+            raise ValueError("origin: three Cartesian coordinates (Bohr)")
+        out = np.empty((3, self.nao, self.nao))
+        _lib.check(self.lib.qemb_int1e_dipole(self.h, o.ctypes.data, out.ctypes.data), "qemb_int1e_dipole", self.lib)
+        return out
 
     def eri(self, sym=8, thresh=0.0, out_dev=None):
         """(mu nu|la si) from the device kernels (qemb_int4c2e) in form `sym`: 8 (1-D, PySCF's 8-fold packed form), 4 ([npair][npair]) or 1 ([N]^4).  out_dev: a
@@ -559,6 +581,18 @@ def one_electron(mol: Mole, backend="host", lib=None):
         finally:
             b.free()
     return mol.one_electron()
+
+
+def dipole(mol: Mole, origin=(0.0, 0.0, 0.0), backend="host", lib=None):
+    """The dipole integrals <a|r - origin|b> of `mol`, (3, nao, nao), origin in Bohr.  backend="host": libqemb_gto (Mole.dipole); backend="hip": the device kernel
+    (DeviceBasis.dipole)."""
+    if _backend(backend):
+        b = DeviceBasis(mol, lib)
+        try:
+            return b.dipole(origin)
+        finally:
+            b.free()
+    return mol.dipole(origin)
 
 
 def pack_eri(eri_s1, sym):

@@ -5,7 +5,7 @@
 make_rdm1(), get_veff() -- a real `pyscf.scf.RHF` or `quemb_amd.integrals.RHF`.  What runs where:
   host (NumPy, once per system, out of scope per SURVEY 2): Loewdin localisation W = S^-1/2 (mbe.py:1395-1398);
   device (libqemb_hip): Schmidt decomposition, AO->fragment ERI transform, fragment Fock / SCF, CCSD, energies.
-Only lo_method="lowdin", restricted is mirrored (the configurations of SURVEY section 8); frozen core as in mbe.py:397-419.
+lo_method "lowdin", "boys", "PM" and "ER" and lo_bath_post_schmidt (lo.py: the rotations run on the device), restricted, are mirrored; frozen core as in mbe.py:397-419.
 """
 
 from __future__ import annotations
@@ -33,9 +33,27 @@ class BE:
     def __init__(self, mf, fobj, *, lo_method="lowdin", thr_bath=1.0e-10, int_transform="in-core-hip", auxbasis=None,
                  df_ints=None, nproc=1, ompnum=1, initialize_fragment_idx=None, solver_opts=None, lib=None, distribute=True, nstreams=None, lockstep=None,
                  eri_file=None, scratch_dir=None, restart=False, schmidt_method="subspace", MO_coeff_epsilon=1e-5, AO_coeff_epsilon=1e-10, df_resident="factor",
-                 integral_backend="host", int_direct_tile=None, int_direct_thresh=0.0, cd_tol=1e-8, cd_span=0.01, cd_panel=None, reuse_mf_df=False):
-        if lo_method != "lowdin":
-            raise NotImplementedError("only lo_method='lowdin' is mirrored (localisation is upstream of the hot path)")
+                 integral_backend="host", int_direct_tile=None, int_direct_thresh=0.0, cd_tol=1e-8, cd_span=0.01, cd_panel=None, reuse_mf_df=False,
+                 pop_method=None, init_guess="atomic", lo_bath_post_schmidt=None):
+        # lo_method "boys" / "PM": the Loewdin orbitals rotated by get_loc (lo.py: Jacobi sweeps on the device; mbe.py:1451-1481), pop_method / init_guess as there.
+        # lo_bath_post_schmidt: the bath columns TA[:, n_f:] of every fragment localised after the Schmidt decomposition (mbe.py:1217-1223) -- a rotation inside
+        # the embedding space, the fragment columns are not touched.  "ER" (either keyword) is defined on the factorised integrals and needs a dense 3-index context
+        # before the fragments are transformed: int_transform "int-direct-DF-hip" from the geometry (`auxbasis`), "cholesky-hip", or reuse_mf_df=True (_loc_df);
+        # the context is made once and serves the transform too.  "IAO" stays refused.
+        if lo_method not in ("lowdin", "boys", "PM", "ER"):
+            raise NotImplementedError("lo_method 'lowdin', 'boys', 'PM' and 'ER' are mirrored ('IAO' is not)")
+        if lo_bath_post_schmidt not in (None, "cholesky", "ER", "PM", "boys"):
+            raise ValueError("lo_bath_post_schmidt must be None, 'cholesky', 'ER', 'PM' or 'boys'")
+        if (lo_method == "ER" or lo_bath_post_schmidt == "ER") and not (
+                reuse_mf_df or int_transform == "cholesky-hip" or (int_transform == "int-direct-DF-hip" and df_ints is None and auxbasis)):
+            raise ValueError("Edmiston-Ruedenberg localisation reads a dense 3-index context: int_transform='int-direct-DF-hip' with `auxbasis`, "
+                             "int_transform='cholesky-hip', or reuse_mf_df=True")
+        self._lo_cache = {}       # what get_loc needs of the molecule alone (dipole integrals, S^1/2): formed once for all fragments
+        self._loc_ctx = None      # (context, owned): made by _loc_df for ER, used and released by _eri_transform
+        if (lo_method != "lowdin" or lo_bath_post_schmidt is not None) and getattr(mf, "mol", None) is None:
+            raise ValueError("orbital localisation evaluates its integrals from the geometry: the mean field needs `mol`")
+        self.lo_method, self.pop_method, self.init_guess, self.lo_bath_post_schmidt = lo_method, pop_method, init_guess, lo_bath_post_schmidt
+        self.lo_stats = {}      # what get_loc reports: "W" for lo_method, the fragment index for the bath of each fragment
         if restart:
             raise NotImplementedError("restart files are outside the hot path")
         self.mf, self.fobj, self.lib = mf, fobj, lib
@@ -132,9 +150,12 @@ class BE:
         self.stats = {}
         # fragment ownership over ranks (all fragments on this rank when not distributed)
         self.rank, self.world = world() if distribute else (0, 1)
-        self.localize()
         self._df_ints = df_ints
-        self.initialize(getattr(mf, "_eri", None), initialize_fragment_idx)
+        try:
+            self.localize()
+            self.initialize(getattr(mf, "_eri", None), initialize_fragment_idx)
+        finally:
+            self._release_loc_df()      # (a context made for Edmiston-Ruedenberg that a failure kept from reaching the transform)
 
     # ------------------------------------------------------------------ localisation (host; mbe.py:1395-1449)
     def localize(self):
@@ -142,14 +163,52 @@ class BE:
         edx = es_ > 1.0e-15
         self.W = (vs_[:, edx] / np.sqrt(es_[edx])) @ vs_[:, edx].T
         if self.frozen_core:
-            # mbe.py:1418-1431: project the core out of the Loewdin orbitals, keep the columns that stay populated (> 0.7),
-            # re-orthonormalise symmetrically -- N - ncore valence LOs in the order of the valence AOs
+            # mbe.py:1418-1431: project the core out of the Loewdin orbitals, keep the columns that stay populated (> 0.7; > 0.55 on the boys / PM branch,
+            # mbe.py:1456-1468), re-orthonormalise symmetrically -- N - ncore valence LOs in the order of the valence AOs
             C_ = (np.eye(self.W.shape[0]) - self.P_core @ self.S) @ self.W
             Cpop = np.diag(C_.T @ self.S @ C_)
-            C_ = C_[:, np.where(Cpop > 0.7)[0]]
+            C_ = C_[:, np.where(Cpop > (0.7 if self.lo_method == "lowdin" else 0.55))[0]]
             es_, vs_ = np.linalg.eigh(C_.T @ self.S @ C_)
             self.W = C_ @ ((vs_ / np.sqrt(es_)) @ vs_.T)
+        if self.lo_method != "lowdin":
+            from .lo import get_loc
+            st = self.lo_stats["W"] = {}
+            self.W = get_loc(self.mf.mol, self.W, self.lo_method, pop_method=self.pop_method, init_guess=self.init_guess, lib=self.lib, stats=st, cache=self._lo_cache,
+                             df=self._loc_df() if self.lo_method == "ER" else None)      # mbe.py:1470-1476
         self.lmo_coeff = self.W.T @ self.S @ self.C[:, self.ncore:]
+
+    def _dense_route(self):
+        """whether the fragments are transformed from ONE dense 3-index context the driver makes or borrows: the mean field's (reuse_mf_df), the Cholesky factor of
+        "cholesky-hip", the fitted tensor of "int-direct-DF-hip" from the geometry"""
+        it = self.int_transform
+        return (self.reuse_mf_df and it in ("int-direct-DF-hip", "cholesky-hip")) or it == "cholesky-hip" or (it == "int-direct-DF-hip" and self._df_ints is None)
+
+    def _route_context(self):
+        """-> (context, owned) of a dense route (_dense_route): the one place the driver makes it, for the transform and for Edmiston-Ruedenberg alike"""
+        from . import _lib
+        it = self.int_transform
+        if self.reuse_mf_df:
+            return self.mf.with_df, False      # the tensor of the mean field serves the fragments too: borrowed, not freed here
+        if it == "cholesky-hip":
+            # the Cholesky factor of the AO integrals, decomposed once on the device (csrc/int4c.cpp: int4c_cholesky), is the 3-index tensor of a DF context with an
+            # identity metric.  `mf._eri` is ignored: the integrals come from mf.mol
+            return et.DFContext.from_cholesky(self.mf.mol, tol=self.cd_tol, span=self.cd_span, panel_pairs=self.cd_panel, lib=self.lib or _lib.init()), True
+        from . import eri_sparse_DF as sdf
+        if not self.auxbasis:
+            raise ValueError("`auxbasis` has to be defined.")                # mbe.py:1050
+        return sdf.dense_df_context(self.mf.mol, self.auxbasis, lib=self.lib, integral_backend=self.integral_backend), True
+
+    def _loc_df(self):
+        """The dense 3-index context Edmiston-Ruedenberg reads, before the fragments are transformed: made once here (_route_context) and handed on to
+        `_eri_transform`, which releases it."""
+        if self._loc_ctx is None:
+            self._loc_ctx = self._route_context()
+        return self._loc_ctx[0]
+
+    def _release_loc_df(self):
+        if self._loc_ctx is not None and self._loc_ctx[1]:
+            self._loc_ctx[0].free()
+        self._loc_ctx = None
 
     # ------------------------------------------------------------------ initialisation (mbe.py:1183-1237)
     def initialize(self, eri_, initialize_fragment_idx=None):
@@ -167,6 +226,17 @@ class BE:
         # Schmidt decomposition of every fragment this rank may own (cheap; sizes decide the partition)
         for f in self.Fobjs:
             f.sd(self.W, self.lmo_coeff, self.Nocc, thr_bath=self.thr_bath, method=self.schmidt_method)
+        if self.lo_bath_post_schmidt is not None:
+            # mbe.py:1217-1223: after the Schmidt decomposition of every fragment, before anything reads TA.  Beyond the reference, TA_lo_eo is rewritten too, so
+            # that TA = W TA_lo_eo keeps holding
+            from .lo import get_loc
+            df = self._loc_df() if self.lo_bath_post_schmidt == "ER" else None
+            for f in self.Fobjs:
+                if f.TA.shape[1] > f.n_f:
+                    st = self.lo_stats[f.ifrag] = {}
+                    f.TA[:, f.n_f:] = get_loc(self.mf.mol, f.TA[:, f.n_f:], method=self.lo_bath_post_schmidt, lib=self.lib, stats=st, df=df, cache=self._lo_cache)
+                    f.TA_lo_eo[:, f.n_f:] = self.W.T @ self.S @ f.TA[:, f.n_f:]
+        for f in self.Fobjs:
             f.get_nsocc(self.S, self.C, self.Nocc, ncore=self.ncore)
         costs = [fragment_cost(f.nao, f.nsocc) for f in self.Fobjs]
         self.owner = partition_fragments(costs, self.world)
@@ -179,7 +249,20 @@ class BE:
     def _eri_transform(self, eri_, idx):
         """BE._eri_transform (mbe.py:1004-1113) with the device literals of eri_transform.HIP_INT_TRANSFORMS."""
         it = self.int_transform
-        if it in ("in-core-hip", "in-core"):
+        if self._dense_route():
+            # one dense context serves every fragment: the one Edmiston-Ruedenberg was localised on, if there was one, else made now; an owned one is released
+            df, owned = self._loc_ctx if self._loc_ctx is not None else self._route_context()
+            self._loc_ctx = (df, owned)
+            try:
+                if it == "cholesky-hip":
+                    self.cd_stats = dict(getattr(df, "cd_stats", {}))
+                for I in idx:
+                    df.transform(self.Fobjs[I].TA, frag=self.Fobjs[I].dev, want_host=False, factor_only=self.df_resident == "factor")
+            finally:
+                self._release_loc_df()
+            if self.reuse_mf_df or it == "cholesky-hip":
+                self._eri_from_geometry = True
+        elif it in ("in-core-hip", "in-core"):
             if eri_ is None and self.integral_backend != "hip":
                 raise ValueError("ERIs have to be available in memory.")      # mbe.py:1036
             if eri_ is None:
@@ -199,14 +282,6 @@ class BE:
                     ao.transform(self.Fobjs[I].TA, frag=self.Fobjs[I].dev, want_host=False)
             finally:
                 ao.free()
-        elif self.reuse_mf_df and it in ("int-direct-DF-hip", "cholesky-hip"):
-            # the tensor of the mean field serves the fragments too: borrowed, not freed here
-            df = self.mf.with_df
-            if it == "cholesky-hip":
-                self.cd_stats = dict(getattr(df, "cd_stats", {}))
-            for I in idx:
-                df.transform(self.Fobjs[I].TA, frag=self.Fobjs[I].dev, want_host=False, factor_only=self.df_resident == "factor")
-            self._eri_from_geometry = True
         elif it == "int-direct-hip":
             # integral-direct: one pass over the AO integrals, tile by tile, serves every fragment of `idx` (csrc/int4c.cpp: int4c_ao2mo_direct); nothing of size
             # N^4 exists on the host or the device.  `eri_` (mf._eri) is ignored: the integrals come from mf.mol
@@ -221,34 +296,18 @@ class BE:
             finally:
                 basis.free()
             self._eri_from_geometry = True
-        elif it == "cholesky-hip":
-            # the Cholesky factor of the AO integrals, decomposed once on the device (csrc/int4c.cpp: int4c_cholesky), is the 3-index tensor of a DF context with an
-            # identity metric: every fragment is transformed from it like on "int-direct-DF-hip".  `eri_` (mf._eri) is ignored: the integrals come from mf.mol
-            from . import _lib
-            df = et.DFContext.from_cholesky(self.mf.mol, tol=self.cd_tol, span=self.cd_span, panel_pairs=self.cd_panel, lib=self.lib or _lib.init())
-            try:
-                self.cd_stats = dict(df.cd_stats)
-                for I in idx:
-                    df.transform(self.Fobjs[I].TA, frag=self.Fobjs[I].dev, want_host=False, factor_only=self.df_resident == "factor")
-            finally:
-                df.free()
-            self._eri_from_geometry = True
-        elif it in ("int-direct-DF-hip", "sparse-DF-hip", "on-fly-sparse-DF-hip") and self._df_ints is None:
-            # from the geometry alone, like the reference's "int-direct-DF" / "sparse-DF(-gpu)" / "on-fly-sparse-DF(-gpu)" branches
-            # (mbe.py:1049-1110): auxiliary molecule, (P|Q), (mu nu|P) from the integral source, AO screening, device transform
+        elif it in ("sparse-DF-hip", "on-fly-sparse-DF-hip") and self._df_ints is None:
+            # from the geometry alone, like the reference's "sparse-DF(-gpu)" / "on-fly-sparse-DF(-gpu)" branches (mbe.py:1049-1110; "int-direct-DF" is the dense
+            # route above): auxiliary molecule, (P|Q), (mu nu|P) from the integral source, AO screening, device transform
             from . import eri_sparse_DF as sdf
             if not self.auxbasis:
                 raise ValueError("`auxbasis` has to be defined.")                # mbe.py:1050
             frs = [self.Fobjs[I] for I in idx]
-            if it == "int-direct-DF-hip":
-                sdf.integral_direct_DF_hip(self.mf, frs, self.auxbasis, lib=self.lib, factor_only=self.df_resident == "factor",
-                                           integral_backend=self.integral_backend)
-            else:
-                self.df_stats = {}
-                self.S_abs = sdf.transform_sparse_DF_integral_hip(self.mf, frs, self.auxbasis, AO_coeff_epsilon=self.AO_coeff_epsilon,
-                                                                  MO_coeff_epsilon=self.MO_coeff_epsilon, lib=self.lib,
-                                                                  precompute_P_mu_nu=(it == "sparse-DF-hip"), stats=self.df_stats,
-                                                                  factor_only=self.df_resident == "factor", integral_backend=self.integral_backend)
+            self.df_stats = {}
+            self.S_abs = sdf.transform_sparse_DF_integral_hip(self.mf, frs, self.auxbasis, AO_coeff_epsilon=self.AO_coeff_epsilon,
+                                                              MO_coeff_epsilon=self.MO_coeff_epsilon, lib=self.lib,
+                                                              precompute_P_mu_nu=(it == "sparse-DF-hip"), stats=self.df_stats,
+                                                              factor_only=self.df_resident == "factor", integral_backend=self.integral_backend)
         elif it in ("int-direct-DF-hip", "sparse-DF-hip"):
             # df_ints: (ints, j2c, layout) or a dict(ints=, layout= | int_P_mu_nu=, j2c= | L_PQ=, S_abs=, MO_coeff_epsilon=).
             # "sparse-DF-hip" applies the MO-coefficient screening of the reference's semi-sparse transform

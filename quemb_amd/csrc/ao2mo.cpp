@@ -331,7 +331,7 @@ int DfContext::transform_semisparse(const double* TA, int n, double* out_s4, con
   {
     // blocks of (active) AOs whose gathered operands stay under ~1 GiB
     int64_t budget = (int64_t)1 << 27;
-    if (const char* e = std::getenv("QEMB_DF_GATHER_BUDGET")) budget = std::max<int64_t>(1, std::atoll(e));   // doubles; tests force several blocks
+    budget = std::max<int64_t>(1, env_int("QEMB_DF_GATHER_BUDGET", budget));   // doubles; tests force several blocks
     int64_t a0 = 0;
     std::vector<int64_t> idxD, idxT;
     DBuf Dg, TAg;

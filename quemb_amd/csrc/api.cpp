@@ -52,7 +52,7 @@ static void qemb_fault_handler(int sig) {
   raise(sig);
 }
 int qemb_init(int device) {
-  static const bool bt = [] { const char* e = std::getenv("QEMB_BACKTRACE"); if (e && e[0] != '0') { signal(SIGSEGV, qemb_fault_handler); signal(SIGABRT, qemb_fault_handler); } return true; }();
+  static const bool bt = [] { if (env_flag("QEMB_BACKTRACE", false)) { signal(SIGSEGV, qemb_fault_handler); signal(SIGABRT, qemb_fault_handler); } return true; }();
   (void)bt;
   return dev_init(device);
 }

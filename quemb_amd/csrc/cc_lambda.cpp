@@ -119,7 +119,7 @@ int CcLambda::contract(int dst, double coef, std::string sa, std::string sb, con
   else if (sb == Nord + Kord) { B = ptr_[b]; b_kc = true; }
   else { QTRY(operand(b, sb, Kord + Nord, &B, sB)); b_kc = false; }
   const int64_t lda = a_kc ? K : M, ldb = b_kc ? K : N;
-  static const bool trace = std::getenv("QEMB_LAMBDA_TRACE") != nullptr;
+  static const bool trace = env_flag("QEMB_LAMBDA_TRACE", false);
   if (trace) std::fprintf(stderr, "[qemb lambda] %s,%s->%s  M=%lld N=%lld K=%lld a_kc=%d b_kc=%d permA=%d permB=%d permC=%d\n", sa.c_str(), sb.c_str(), so.c_str(),
                           (long long)M, (long long)N, (long long)K, (int)a_kc, (int)b_kc, (int)(sA.p != nullptr), (int)(sB.p != nullptr), (int)(so != Mord + Nord));
   // products with an n_occ-sized side: 32 x 128 / 128 x 32 tiles instead of padding that side to 64 (these are HBM-bound passes

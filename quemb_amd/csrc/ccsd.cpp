@@ -332,27 +332,25 @@ int CcsdSolver::energy(const double* t1, const double* t2, double* e) {
   // E = sum (2 ovov[iajb] - ovov[ibja]) tau[ijab] = <Loovv, tau>   (f_ov = 0)
   QTRY(make_tau(t1, t2, tau_));
   QTRY(dev_dot((int64_t)o_ * o_ * v_ * v_, Loovv_, tau_, scal_));
-  if (e) QTRY(dev_d2h(e, scal_, sizeof(double)));      // (null: the value stays in scal_[0] -- fetch_energy)
-  return 0;
+  return dev_d2h(e, scal_, sizeof(double));
 }
-int CcsdSolver::fetch_energy() { return dev_d2h(&ecc_, scal_, sizeof(double)); }
 
-int CcsdSolver::init_amps(bool defer_energy) {
+int CcsdSolver::init_amps() {
   const int64_t o = o_, v = v_;
   QTRY(dev_fill(t1(), o * v, 0.0));                                      // t1 = f_ov / e_ia = 0
   QTRY(dcopy(o * o * v * v, OVoovv_, t2()));                             // t2 = ovov[i,a,j,b] / e_ijab
   QTRY(dev_div_denom(t2(), o, o, v, v, eo_, eo_, ev_, ev_));
   first_ = true;
   diis_.clear();
-  return energy(t1(), t2(), defer_energy ? nullptr : &ecc_);
+  return energy(t1(), t2(), &ecc_);
 }
 
-int CcsdSolver::set_amps(const double* t1d, const double* t2d, bool defer_energy) {
+int CcsdSolver::set_amps(const double* t1d, const double* t2d) {
   QTRY(dev_d2d(t1(), t1d, sizeof(double) * o_ * v_));
   QTRY(dev_d2d(t2(), t2d, sizeof(double) * (int64_t)o_ * o_ * v_ * v_));
   first_ = true;
   diis_.clear();
-  return energy(t1(), t2(), defer_energy ? nullptr : &ecc_);
+  return energy(t1(), t2(), &ecc_);
 }
 
 // tile configuration and K split for the "few packed pair rows x many columns" GEMMs (ladder, tau-side dressing)
@@ -616,14 +614,12 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
   // The right-hand operands of all four (ov)^3 products are symmetric matrices over (kc),(ld) -- L and ovov_t by the integral symmetry
   // (kc|ld) = (ld|kc), T' and u by t2[k,j,c,b] = t2[j,k,b,c] -- so each is passed in its K-contiguous (transposed) reading: both operands
   // of the GEMM are then staged through the conflict-free [row][BK+2] LDS image, on the 128 x 256 tile (512 tiles at ov = 4000: two per CU).
-  // (small fragments in a lock-step sweep, QEMB_LOCKSTEP_PEERS=1: `peers` products of this shape run in ONE grouped launch, enough to fill the chip with
-  //  64 x 64 tiles.  Measured on six octane fragments, o v = 441: 294 such workgroups on 256 CUs are SLOWER than the 1176 of the 32 x 32 tile the
-  //  dispatcher picks for a lone product -- 11.3 against 11.0 ms per sweep -- so the hint stays off.)
-  const int64_t ring_tiles64 = gemm_tile_count(GEMM_64x64, nov, nov) * dev_gemm_peers();
+  // (below o v = 1024: 64 x 64 tiles once there are 200 of them, else the dispatcher's choice -- 32 x 32 at the o v = 441 of an octane fragment)
+  const int64_t ring_tiles64 = gemm_tile_count(GEMM_64x64, nov, nov);
   // (1024 <= o v < 2048, one mid-size fragment on the chip: 96 x 96 tiles with K in two slices -- 15 x 15 x 2 workgroups at o v = 1440, 119 us against the 151 us
   //  of 23 x 23 tiles of 64 x 64; tools/mid_gemm_bench.py.  QEMB_RING96=0: the 64 x 64 tiles, for A/B runs)
-  static const bool ring96 = !(std::getenv("QEMB_RING96") && std::getenv("QEMB_RING96")[0] == '0');
-  const bool mid_ring = ring96 && nov >= 1024 && nov < 2048 && dev_gemm_peers() == 1;
+  static const bool ring96 = env_flag("QEMB_RING96", true);
+  const bool mid_ring = ring96 && nov >= 1024 && nov < 2048;
   const int cfg_ring = (nov >= 2048) ? GEMM_128x256 : mid_ring ? GEMM_96x96 : (nov >= 256 && ring_tiles64 >= 200) ? GEMM_64x64 : -1;
   auto ring = [&](double al, const double* A, const double* Bsym, double be, double* C) {
     return gemm(nov, nov, nov, al, A, nov, true, Bsym, nov, true, be, C, nov, 1, 0, 0, 0, cfg_ring, mid_ring ? 2 : 0);
@@ -670,26 +666,47 @@ int CcsdSolver::iterate(double* e_corr, double* normt) {
   return 0;
 }
 
-// The amplitude update of one iteration.  Launch-bound regime (small fragments): update_amps is recorded once (after one eager pass has
-// settled every workspace) and replayed -- as an executable hipGraph, or, in the lock-step sweep over several fragments (prefer_tape), as
-// a TAPE that dev_tape_run executes together with the other fragments' tapes.  defer_tape: when the tape exists, do not run it -- the
-// caller runs it grouped (*deferred = true).  Large fragments are GEMM bound and keep the eager path with its per-kernel timers.
-// (hipGraph replay under rocprofv3's kernel tracing aborts inside the profiler on this ROCm: fall back to eager launches there)
+// ---- the replay rule.  Launch-bound regime (small fragments): update_amps is recorded once and replayed -- as an executable hipGraph, or, in the lock-step
+// sweep over several fragments, as a TAPE that dev_tape_run executes together with the other fragments' tapes.  Large fragments are GEMM bound and keep the
+// eager path with its per-kernel timers.  A fragment replays when graphs_allowed() && replay_regime().
+// Whether this process records at all: QEMB_GRAPH says so; left unset, a profiled run does not (hipGraph replay under rocprofv3's kernel tracing aborts inside the
+// profiler on this ROCm: eager launches there).
+static bool graphs_allowed() {
+  static const bool on = env_flag("QEMB_GRAPH", !profiled_run());
+  return on;
+}
+// ... and whether this fragment does: small enough to be launch bound, and no recording of its update has failed
+bool CcsdSolver::replay_regime() const { return (int64_t)o_ * o_ * v_ * v_ <= (int64_t)1 << 22 && graph_ok_; }
+
+// One update_amps recorded into the staging buffer, as a tape (tape_) or as an executable graph (graph_).  A capture executes nothing.  Returns
+//   0    recorded;
+//   > 0  cannot record (the backend does not capture, or the captured sequence cannot be a tape): nothing is wrong, the caller runs eagerly;
+//   < 0  an error: of dev_graph_begin (*began stays false), else of update_amps under capture, else of the end of the capture.
+// Nothing is kept unless 0 comes back.  The callers clear graph_ok_ (prepare_tape not before its second attempt) and decide which errors they pass on.
+int CcsdSolver::record_update(bool as_tape, bool* began) {
+  *began = false;
+  const int rc = dev_graph_begin(as_tape ? 1 : 0);
+  if (rc != 0) return rc;
+  *began = true;
+  const int rc2 = update_amps(ampn_.p, ampn_.p + (int64_t)o_ * v_);
+  dev_tape_t t = nullptr;
+  dev_graph_t g = nullptr;
+  const int rc3 = as_tape ? dev_tape_end(&t) : dev_graph_end(&g);
+  if (!rc2 && !rc3) { if (as_tape) tape_ = t; else graph_ = g; return 0; }
+  if (t) dev_tape_destroy(t);
+  if (g) dev_graph_destroy(g);
+  return rc2 ? rc2 : rc3;
+}
+
+// The amplitude update of one iteration.  In the replay regime update_amps is recorded after one eager pass has settled every workspace -- as a tape in the
+// lock-step sweep (prefer_tape), else as a graph -- and replayed from then on.  defer_tape: when the tape exists, do not run it -- the caller runs it grouped
+// (*deferred = true).
 int CcsdSolver::iterate_update(bool prefer_tape, bool defer_tape, bool* deferred) {
-  static const bool graphs_enabled = [] {
-    const char* e = std::getenv("QEMB_GRAPH");
-    if (e) return e[0] != '0';
-    const char* pre = std::getenv("LD_PRELOAD");
-    if (std::getenv("ROCP_TOOL_LIBRARIES") || (pre && std::strstr(pre, "rocprofiler"))) return false;
-    return true;
-  }();
-  static const bool tape_replay = std::getenv("QEMB_TAPE") != nullptr;      // diagnostic: replay the captured sequence through dev_tape_run (one tape)
   if (deferred) *deferred = false;
-  const bool small = (int64_t)o_ * o_ * v_ * v_ <= (int64_t)1 << 22;
   // With DIIS the new amplitudes and their error vector go straight into the storage of the next DIIS slot (no staging copies);
   // the replay of small fragments has its output address baked in and keeps the staging buffer.
   const bool use_diis = !first_ && !diis_.empty();
-  const bool replayable = graphs_enabled && small && graph_ok_;
+  const bool replayable = graphs_allowed() && replay_regime();
   double* out = (use_diis && !replayable) ? diis_[0].next_x() : ampn_.p;
   last_out_ = out; last_use_diis_ = use_diis; last_replayable_ = replayable;
   if (replayable && tape_) {
@@ -698,21 +715,13 @@ int CcsdSolver::iterate_update(bool prefer_tape, bool defer_tape, bool* deferred
   } else if (replayable && graph_) {
     QTRY(dev_graph_launch(graph_));
   } else if (replayable && eager_iters_ >= 1) {
-    const int rc = dev_graph_begin((prefer_tape || tape_replay) ? 1 : 0);
-    if (rc == 0 && (prefer_tape || tape_replay)) {
-      const int rc2 = update_amps(ampn_.p, ampn_.p + (int64_t)o_ * v_);
-      dev_tape_t t = nullptr;
-      const int rc3 = dev_tape_end(&t);
-      if (rc2 || rc3) { graph_ok_ = false; if (t) dev_tape_destroy(t); if (rc2) return rc2; if (rc3 < 0) return rc3; QTRY(update_amps(ampn_.p, ampn_.p + (int64_t)o_ * v_)); }
-      else { tape_ = t; QTRY(dev_tape_run(&tape_, 1)); }
-    } else if (rc == 0) {
-      const int rc2 = update_amps(ampn_.p, ampn_.p + (int64_t)o_ * v_);
-      dev_graph_t g = nullptr;
-      const int rc3 = dev_graph_end(&g);
-      if (rc2 || rc3) { graph_ok_ = false; if (g) dev_graph_destroy(g); QTRY(update_amps(ampn_.p, ampn_.p + (int64_t)o_ * v_)); }
-      else { graph_ = g; QTRY(dev_graph_launch(graph_)); }
-    } else {
-      graph_ok_ = false;   // backend cannot capture
+    bool began = false;
+    const int rc = record_update(prefer_tape, &began);
+    if (rc == 0) QTRY(prefer_tape ? dev_tape_run(&tape_, 1) : dev_graph_launch(graph_));
+    else {
+      graph_ok_ = false;
+      // (a tape that failed while being captured is this call's error; a refused capture, and any failure of a graph capture, shows again in the eager pass)
+      if (prefer_tape && began && rc < 0) return rc;
       QTRY(update_amps(ampn_.p, ampn_.p + (int64_t)o_ * v_));
     }
   } else {
@@ -723,43 +732,21 @@ int CcsdSolver::iterate_update(bool prefer_tape, bool defer_tape, bool* deferred
 }
 
 // Lock-step sweeps: record the tape BEFORE the first iteration, on the fragment's own thread and stream (so that the fragments do this side
-// by side).  One eager update_amps into the staging buffer settles the workspaces -- it reads the amplitudes and writes only scratch, the
-// solver's state is what it was -- and the capture that follows records the launch sequence without executing it.  Every iteration of the
-// solve, the first included, then runs from the tape.  A fragment that is not in the replay regime (large, or graphs disabled) is left alone.
-int CcsdSolver::prepare_tape(int peers) {
-  static const bool peer_hint = [] { const char* e = std::getenv("QEMB_LOCKSTEP_PEERS"); return e && e[0] != '0'; }();      // off: measured slower (below)
-  struct Peers { bool on; ~Peers() { if (on) dev_gemm_set_peers(1); } } guard{peer_hint && peers > 1};
-  if (guard.on) dev_gemm_set_peers(peers);
-  const bool use_diis = false;
-  (void)use_diis;
-  bool deferred = false;
-  if (tape_ || !graph_ok_) return 0;
-  // same predicate as iterate_update
-  const bool small = (int64_t)o_ * o_ * v_ * v_ <= (int64_t)1 << 22;
-  static const bool graphs_enabled = [] {
-    const char* e = std::getenv("QEMB_GRAPH");
-    if (e) return e[0] != '0';
-    const char* pre = std::getenv("LD_PRELOAD");
-    if (std::getenv("ROCP_TOOL_LIBRARIES") || (pre && std::strstr(pre, "rocprofiler"))) return false;
-    return true;
-  }();
-  if (!(graphs_enabled && small)) return 0;
-  (void)deferred;
-  // Record straight away: a capture executes nothing, it only must not allocate -- and in the small-fragment regime update_amps works in buffers that setup() sized
-  // (slabs included).  Should a workspace have to grow after all, the capture fails on that allocation: then one eager pass into the staging buffer settles the
-  // workspaces -- it reads the amplitudes and writes only scratch -- and the recording is repeated.  (The unconditional eager pass cost every fragment of every sweep
-  // ~46 launches.)
-  static const bool dry_first = std::getenv("QEMB_TAPE_DRY_PASS") != nullptr;
-  for (int attempt = dry_first ? 1 : 0; attempt < 2; ++attempt) {
+// by side).  Every iteration of the solve, the first included, then runs from the tape.  A fragment that is not in the replay regime (large, or
+// graphs disabled) is left alone.
+// Record straight away: a capture executes nothing, it only must not allocate -- and in the small-fragment regime update_amps works in buffers that setup() sized
+// (slabs included).  Should a workspace have to grow after all, the capture fails on that allocation: then one eager pass into the staging buffer settles the
+// workspaces -- it reads the amplitudes and writes only scratch, the solver's state is what it was -- and the recording is repeated.  (The unconditional eager
+// pass cost every fragment of every sweep ~46 launches.)
+int CcsdSolver::prepare_tape() {
+  if (tape_ || !(graphs_allowed() && replay_regime())) return 0;
+  for (int attempt = 0; attempt < 2; ++attempt) {
     if (attempt == 1) { QTRY(update_amps(ampn_.p, ampn_.p + (int64_t)o_ * v_)); ++eager_iters_; }
-    const int rc = dev_graph_begin(1);
-    if (rc != 0) { graph_ok_ = false; return rc < 0 ? rc : 0; }
-    const int rc2 = update_amps(ampn_.p, ampn_.p + (int64_t)o_ * v_);
-    dev_tape_t t = nullptr;
-    const int rc3 = dev_tape_end(&t);
-    if (!rc2 && !rc3) { tape_ = t; return 0; }
-    if (t) dev_tape_destroy(t);
-    if (attempt == 1) { graph_ok_ = false; if (rc2) return rc2; return (rc3 < 0) ? rc3 : 0; }      // (a failed first attempt: whatever went wrong shows again in the eager pass)
+    bool began = false;
+    const int rc = record_update(true, &began);
+    if (rc == 0) return 0;
+    // (a failed first attempt: whatever went wrong shows again in the eager pass)
+    if (!began || attempt == 1) { graph_ok_ = false; return rc < 0 ? rc : 0; }
   }
   return 0;
 }
@@ -784,7 +771,7 @@ int CcsdSolver::post_wait(int step) {
 }
 // (the fused launches take up to eight stored vectors and o^2 <= 16384 tiles; QEMB_POST_FUSED=0: the pass-by-pass form, for A/B runs)
 bool CcsdSolver::fused_post() const {
-  static const bool on = [] { const char* e = std::getenv("QEMB_POST_FUSED"); return !e || e[0] != '0'; }();
+  static const bool on = env_flag("QEMB_POST_FUSED", true);
   return on && !(last_use_diis_ && diis_[0].space() > 8) && (int64_t)o_ * o_ <= 16384 && v_ <= 4096;
 }
 // step 1: diff = t_new - t (also the DIIS error vector: trial minus previously returned vector) and its Gram row -- one launch whose last
@@ -840,6 +827,34 @@ int CcsdSolver::post_energy(double* e_corr) {
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// The convergence loop of one fragment, stated once for kernel() and for the lock step: begin() sets up DIIS, verdict(it) judges iteration `it` from the
+// energy and |dt| its post steps left in e / normt (and says in `active` whether another iteration follows), end() tears down.
+struct CcsdSolver::Convergence {
+  CcsdSolver* s; CcsdOptions opt; int frag;      // frag >= 0: the fragment's number in a lock-step sweep (the verbose line names it)
+  double eold = 0.0, e = 0.0, normt = 0.0;
+  int n_iter = 0;
+  bool converged = false, active = true;
+  int begin() {
+    s->diis_.clear();
+    if (opt.diis_space > 1) { s->diis_.emplace_back(opt.diis_space, s->n_amp()); QTRY(s->diis_[0].init()); }
+    eold = e = s->ecc_;
+    return 0;
+  }
+  int verdict(int it) {
+    n_iter = it;
+    if (opt.verbose > 0) {
+      if (frag < 0) std::fprintf(stderr, "[qemb ccsd] cycle %3d  E(corr) = %.12f  dE = %.3e  |dt| = %.3e\n", it, e, e - eold, normt);
+      else std::fprintf(stderr, "[qemb ccsd lockstep] frag %d cycle %3d  E(corr) = %.12f  dE = %.3e  |dt| = %.3e\n", frag, it, e, e - eold, normt);
+    }
+    if (!std::isfinite(e)) { set_error("CCSD diverged (non-finite energy)"); return QEMB_ERR_NUMERIC; }
+    if (std::fabs(e - eold) < opt.conv_tol && normt < opt.conv_tol_normt) { converged = true; active = false; }
+    else if (it >= opt.max_cycle) active = false;
+    eold = e;
+    return 0;
+  }
+  double end() { s->diis_.clear(); return e; }
+};
+
 // Several fragments in LOCK STEP (the small-fragment regime: octane BE2 has six fragments of ~40 orbitals whose iterations are ~110
 // dependent launches of 4-5 us each, whatever the fragment count).  Control flow of CcsdSolver::kernel for every solver at once; per
 // iteration the update_amps launch sequences of all still-iterating fragments run as ONE merged sequence (dev_tape_run: the same kernel of
@@ -851,120 +866,91 @@ int ccsd_kernel_lockstep(const std::vector<CcsdSolver*>& s, const std::vector<Cc
                          std::vector<double>& e_corr, std::vector<int>& n_iter, std::vector<char>& converged, LockstepStats* stats) {
   const int F = (int)s.size();
   e_corr.assign(F, 0.0); n_iter.assign(F, 0); converged.assign(F, 0);
-  std::vector<double> eold(F), e(F), normt(F, 0.0);
-  std::vector<char> active(F, 1);
+  std::vector<CcsdSolver::Convergence> c;
   struct Rebind { int home; ~Rebind() { (void)dev_ctx_bind(home); } } rebind{home_ctx};
+  int max_cycle = 0;
   for (int f = 0; f < F; ++f) {
     QTRY(dev_ctx_bind(ctx[f]));
-    s[f]->diis_.clear();
-    if (opt[f].diis_space > 1) { s[f]->diis_.emplace_back(opt[f].diis_space, s[f]->n_amp()); QTRY(s[f]->diis_[0].init()); }
-    eold[f] = e[f] = s[f]->ecc_;
+    c.push_back({s[f], opt[f], f});
+    QTRY(c[f].begin());
+    max_cycle = std::max(max_cycle, opt[f].max_cycle);
   }
-  int max_cycle = 0;
-  for (int f = 0; f < F; ++f) max_cycle = std::max(max_cycle, opt[f].max_cycle);
   for (int it = 1; it <= max_cycle; ++it) {
     std::vector<dev_tape_t> tapes;
-    std::vector<int> tape_ctx;
-    bool any = false;
+    int nactive = 0;
     for (int f = 0; f < F; ++f) {
-      if (!active[f]) continue;
-      any = true;
+      if (!c[f].active) continue;
+      ++nactive;
       QTRY(dev_ctx_bind(ctx[f]));
       bool deferred = false;
       QTRY(s[f]->iterate_update(true, true, &deferred));
-      if (deferred) { tapes.push_back(s[f]->tape_); tape_ctx.push_back(ctx[f]); }
+      if (deferred) tapes.push_back(s[f]->tape());
     }
-    if (!any) break;
+    if (nactive == 0) break;
     // the fragments' own streams must have finished what the tapes read (the previous post steps end with a host sync; an eager or
     // capturing update above is followed by its own post step below, which syncs too) -- and the merged run must finish before the post steps
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
     bool batched_post = false;
-    int nactive = 0;
-    for (int f = 0; f < F; ++f) nactive += active[f] ? 1 : 0;
     if (!tapes.empty()) {
-      // The merged sequence is issued as `nsplit` sequences of tapes.size() / nsplit members each, on the streams of the first nsplit
-      // fragments' contexts: grouped launches of six small fragments are bound by workgroup dispatch (8-15 us each), two sequences of three
-      // members overlap on the device (QEMB_LOCKSTEP_SPLIT; measured: 13.2 ms per octane sweep in one sequence, 14.8 in two, 16.0 in three -- the default stays one).
-      static const int want_split = std::getenv("QEMB_LOCKSTEP_SPLIT") ? std::max(1, std::atoi(std::getenv("QEMB_LOCKSTEP_SPLIT"))) : 1;
       const int nt = (int)tapes.size();
-      const int nsplit = (nt >= 4) ? std::min(want_split, nt / 2) : 1;
-      std::vector<int> run_ctx;
-      for (int k = 0; k < nsplit; ++k) {
-        const int a = (int)((long long)nt * k / nsplit), b = (int)((long long)nt * (k + 1) / nsplit);
-        const int c = (nsplit == 1) ? home_ctx : tape_ctx[a];
-        QTRY(dev_ctx_bind(c));
-        QTRY(dev_tape_run(tapes.data() + a, b - a));
-        run_ctx.push_back(c);
-        if (stats) {
-          long long l = 0, g = 0, ops = 0;
-          (void)dev_tape_last_stats(&l, &g, &ops);
-          stats->launches += l; stats->grouped += g; stats->operations += ops;
-          stats->max_group = std::max<long long>(stats->max_group, (long long)(b - a));
-        }
+      QTRY(dev_ctx_bind(home_ctx));
+      QTRY(dev_tape_run(tapes.data(), nt));      // ONE merged sequence on the home stream
+      if (stats) {
+        long long l = 0, g = 0, ops = 0;
+        (void)dev_tape_last_stats(&l, &g, &ops);
+        stats->launches += l; stats->grouped += g; stats->operations += ops;
+        stats->max_group = std::max<long long>(stats->max_group, (long long)nt);
+        stats->merged_runs += 1;
       }
-      if (stats) stats->merged_runs += 1;
-      // Every active fragment ran in ONE merged sequence on the home stream and ends its iteration with the fused launches: those are collected and issued -- grouped,
-      // four launches for all fragments -- on the same stream, behind the merged run: no wait in between, and the host words tell when each fragment is through.
-      batched_post = (nsplit == 1 && nt == nactive);
-      for (int f = 0; f < F && batched_post; ++f) if (active[f] && !s[f]->fused_post()) batched_post = false;
-      if (!batched_post) for (int c : run_ctx) { QTRY(dev_ctx_bind(c)); QTRY(dev_sync()); }
+      // Every active fragment had a tape and ends its iteration with the fused launches: those are collected and issued -- grouped, four launches for all
+      // fragments -- on the same stream, behind the merged run: no wait in between, and the host words tell when each fragment is through.
+      batched_post = (nt == nactive);
+      for (int f = 0; f < F && batched_post; ++f) if (c[f].active && !s[f]->fused_post()) batched_post = false;
+      if (!batched_post) QTRY(dev_sync());
     }
     const double t1 = now();
     if (stats) stats->ms_tapes += t1 - t0;
     // QEMB_BATCH_TRACE=2: iterations that take longer than 5 ms are reported with their parts (where did a slow sweep spend its time?)
-    static const bool trace_iters = std::getenv("QEMB_BATCH_TRACE") && std::atoi(std::getenv("QEMB_BATCH_TRACE")) >= 2;
+    static const bool trace_iters = env_int("QEMB_BATCH_TRACE", 0) >= 2;
     struct IterTrace { bool on; int it; double t0, t1; double (*now)(); ~IterTrace() { const double t = now(); if (on && t - t0 > 5.0) std::fprintf(stderr, "[qemb lockstep] iteration %d took %.2f ms: tape issue %.2f, post steps %.2f\n", it, t - t0, t1 - t0, t - t1); } } iter_trace{trace_iters, it, t0, t1, +now};
     struct PostTime { LockstepStats* st; double t1; double (*now)(); ~PostTime() { if (st) st->ms_post += now() - t1; } } post_time{stats, t1, +now};
     if (batched_post) {
       struct Flush { bool open = false; ~Flush() { if (open) (void)dev_batch_flush(); } } guard;      // (an error exit must not leave the collector open)
       QTRY(dev_ctx_bind(home_ctx));
       QTRY(dev_batch_begin()); guard.open = true;
-      for (int f = 0; f < F; ++f) if (active[f]) QTRY(s[f]->post_issue());
+      for (int f = 0; f < F; ++f) if (c[f].active) QTRY(s[f]->post_issue());
       guard.open = false; QTRY(dev_batch_flush());
       QTRY(dev_batch_begin()); guard.open = true;
-      for (int f = 0; f < F; ++f) if (active[f]) { QTRY(s[f]->post_wait(1)); QTRY(s[f]->post_extrapolate(&normt[f])); }
+      for (int f = 0; f < F; ++f) if (c[f].active) { QTRY(s[f]->post_wait(1)); QTRY(s[f]->post_extrapolate(&c[f].normt)); }
       guard.open = false; QTRY(dev_batch_flush());
     } else {
-      for (int f = 0; f < F; ++f) if (active[f]) { QTRY(dev_ctx_bind(ctx[f])); QTRY(s[f]->post_issue()); }
-      for (int f = 0; f < F; ++f) if (active[f]) { QTRY(dev_ctx_bind(ctx[f])); QTRY(s[f]->post_wait(1)); QTRY(s[f]->post_extrapolate(&normt[f])); }
+      for (int f = 0; f < F; ++f) if (c[f].active) { QTRY(dev_ctx_bind(ctx[f])); QTRY(s[f]->post_issue()); }
+      for (int f = 0; f < F; ++f) if (c[f].active) { QTRY(dev_ctx_bind(ctx[f])); QTRY(s[f]->post_wait(1)); QTRY(s[f]->post_extrapolate(&c[f].normt)); }
     }
     for (int f = 0; f < F; ++f) {
-      if (!active[f]) continue;
+      if (!c[f].active) continue;
       if (!batched_post) QTRY(dev_ctx_bind(ctx[f]));
       QTRY(s[f]->post_wait(2));
-      QTRY(s[f]->post_energy(&e[f]));
-      n_iter[f] = it;
-      if (opt[f].verbose > 0) std::fprintf(stderr, "[qemb ccsd lockstep] frag %d cycle %3d  E(corr) = %.12f  dE = %.3e  |dt| = %.3e\n", f, it, e[f], e[f] - eold[f], normt[f]);
-      if (!std::isfinite(e[f])) { set_error("CCSD diverged (non-finite energy)"); return QEMB_ERR_NUMERIC; }
-      if (std::fabs(e[f] - eold[f]) < opt[f].conv_tol && normt[f] < opt[f].conv_tol_normt) { converged[f] = 1; active[f] = 0; }
-      else if (it >= opt[f].max_cycle) active[f] = 0;
-      eold[f] = e[f];
+      QTRY(s[f]->post_energy(&c[f].e));
+      QTRY(c[f].verdict(it));
     }
   }
-  for (int f = 0; f < F; ++f) { e_corr[f] = e[f]; s[f]->diis_.clear(); }
+  for (int f = 0; f < F; ++f) { e_corr[f] = c[f].end(); n_iter[f] = c[f].n_iter; converged[f] = c[f].converged ? 1 : 0; }
   return 0;
 }
 
 int CcsdSolver::kernel(const CcsdOptions& opt, double* e_corr, int* n_iter, bool* converged) {
-  diis_.clear();
-  if (opt.diis_space > 1) {
-    diis_.emplace_back(opt.diis_space, n_amp());
-    QTRY(diis_[0].init());
-  }
-  double eold = ecc_, e = ecc_, normt = 0.0;
+  Convergence c{this, opt, -1};
   *converged = false;
-  int it = 0;
-  for (it = 1; it <= opt.max_cycle; ++it) {
-    QTRY(iterate(&e, &normt));
-    if (opt.verbose > 0) std::fprintf(stderr, "[qemb ccsd] cycle %3d  E(corr) = %.12f  dE = %.3e  |dt| = %.3e\n", it, e, e - eold, normt);
-    if (!std::isfinite(e)) { set_error("CCSD diverged (non-finite energy)"); return QEMB_ERR_NUMERIC; }
-    if (std::fabs(e - eold) < opt.conv_tol && normt < opt.conv_tol_normt) { *converged = true; break; }
-    eold = e;
+  QTRY(c.begin());
+  for (int it = 1; c.active && it <= opt.max_cycle; ++it) {
+    QTRY(iterate(&c.e, &c.normt));
+    QTRY(c.verdict(it));
   }
-  *e_corr = e;
-  *n_iter = it > opt.max_cycle ? opt.max_cycle : it;
-  diis_.clear();
+  *e_corr = c.end();
+  *n_iter = c.n_iter;
+  *converged = c.converged;
   return 0;
 }
 

@@ -53,19 +53,16 @@ class CcLambda;
 
 struct LockstepStats { long long merged_runs = 0, launches = 0, grouped = 0, operations = 0, max_group = 0; double ms_tapes = 0.0, ms_post = 0.0; };
 class CcsdSolver;
+// kernel() of several solvers in lock step (ccsd.cpp): it drives them through the public steps below
 int ccsd_kernel_lockstep(const std::vector<CcsdSolver*>& s, const std::vector<CcsdOptions>& opt, const std::vector<int>& ctx, int home_ctx,
                          std::vector<double>& e_corr, std::vector<int>& n_iter, std::vector<char>& converged, LockstepStats* stats);
 
 class CcsdSolver {
   friend class CcLambda;
-  friend int ccsd_kernel_lockstep(const std::vector<CcsdSolver*>&, const std::vector<CcsdOptions>&, const std::vector<int>&, int,
-                                  std::vector<double>&, std::vector<int>&, std::vector<char>&, LockstepStats*);
  public:
   int setup(MoIntegrals&& ints, const double* mo_energy_dev);
-  // defer_energy: the energy of the guess stays on the device (the launches may be captured for a tape); fetch_energy() reads it back afterwards
-  int init_amps(bool defer_energy = false);         // MP2 guess (t1 = 0 for the diagonal Fock)
-  int set_amps(const double* t1_dev, const double* t2_dev, bool defer_energy = false);   // warm start
-  int fetch_energy();
+  int init_amps();                                  // MP2 guess (t1 = 0 for the diagonal Fock)
+  int set_amps(const double* t1_dev, const double* t2_dev);   // warm start
   int iterate(double* e_corr, double* normt);       // one update_amps + DIIS + energy
   int iterate_update(bool prefer_tape, bool defer_tape, bool* deferred);   // the two halves of iterate(), for the lock-step sweep
   int iterate_post(double* e_corr, double* normt);
@@ -74,7 +71,8 @@ class CcsdSolver {
   int post_issue();                                 // iterate_post in three steps (a wait of this context's stream between them)
   int post_extrapolate(double* normt);
   int post_energy(double* e_corr);
-  int prepare_tape(int peers = 1);                               // record the update as a tape before the first iteration (lock-step sweeps)
+  int prepare_tape();                               // record the update as a tape before the first iteration (lock-step sweeps)
+  struct Convergence;                               // the convergence loop of one fragment: begin, verdict(it), end (kernel and the lock step share it)
   int kernel(const CcsdOptions& opt, double* e_corr, int* n_iter, bool* converged);
   // energy pieces of get_frag_energy that need t1,t2: Z1[i,P], Z2[a,P] (host outputs o*nf and v*nf)
   int energy_intermediates(std::vector<double>& Z1, std::vector<double>& Z2);
@@ -93,6 +91,8 @@ class CcsdSolver {
 
  private:
   int update_amps(double* t1n, double* t2n);
+  bool replay_regime() const;                       // small enough to be launch bound, and no recording has failed
+  int record_update(bool as_tape, bool* began);     // one update_amps recorded into ampn_: 0 recorded, > 0 cannot record (run eagerly), < 0 error
   int energy(const double* t1, const double* t2, double* e);
   int make_tau(const double* t1, const double* t2, double* tau);
 

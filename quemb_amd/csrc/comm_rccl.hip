@@ -91,16 +91,14 @@ int load_rccl() {
 // QEMB_COMM_TIMEOUT_S=<seconds> tightens it (tests), QEMB_COMM_TIMEOUT_S=0 removes it.
 constexpr double COMM_TIMEOUT_DEFAULT_S = 21600.0;
 double comm_timeout_s() {
-  const char* e = std::getenv("QEMB_COMM_TIMEOUT_S");
-  if (!e) return COMM_TIMEOUT_DEFAULT_S;
-  const double v = std::atof(e);
+  const double v = env_real("QEMB_COMM_TIMEOUT_S", COMM_TIMEOUT_DEFAULT_S);
   return v > 0 ? v : 0.0;      // 0: no wall-clock bound
 }
 // the rendezvous waits for processes that are still starting (a cold container pages the image in for minutes, and not at the same pace for
 // every rank): its own bound, QEMB_COMM_INIT_TIMEOUT_S; unset, an explicit QEMB_COMM_TIMEOUT_S holds for it too, else 300 s
 double comm_init_timeout_s() {
-  if (const char* e = std::getenv("QEMB_COMM_INIT_TIMEOUT_S")) { const double v = std::atof(e); if (v > 0) return v; }
-  if (std::getenv("QEMB_COMM_TIMEOUT_S") && comm_timeout_s() > 0) return comm_timeout_s();
+  if (const double v = env_real("QEMB_COMM_INIT_TIMEOUT_S", 0.0); v > 0) return v;
+  if (env_str("QEMB_COMM_TIMEOUT_S") && comm_timeout_s() > 0) return comm_timeout_s();
   return 300.0;
 }
 

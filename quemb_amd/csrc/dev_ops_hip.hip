@@ -75,7 +75,7 @@ static int g_device = -1;
 static DevCtx g_default_ctx;
 static std::vector<DevCtx*> g_extra_ctx;          // created by dev_ctx_count(n); index k >= 1
 static std::mutex g_ctx_mutex;
-static int g_ctx_parts = [] { const char* e = std::getenv("QEMB_CU_SPLIT"); return e ? std::atoi(e) : 0; }();      // dev_ctx_partition
+static int g_ctx_parts = (int)env_int("QEMB_CU_SPLIT", 0);      // dev_ctx_partition
 static thread_local DevCtx* t_ctx = nullptr;
 static inline DevCtx& ctx() { return t_ctx ? *t_ctx : g_default_ctx; }
 #define g_stream (ctx().stream)
@@ -120,11 +120,7 @@ static hipError_t create_ctx_stream(hipStream_t* stream, int j) {
   hipError_t e = hipErrorUnknown;
   // (under rocprofv3 the process crashed in its exit handlers when CU-masked streams existed -- and hung when they were destroyed from an atexit handler --, so a
   //  profiled run keeps plain streams, as it keeps eager launches instead of graph replay)
-  static const bool profiled = [] {
-    const char* pre = std::getenv("LD_PRELOAD");
-    return std::getenv("ROCP_TOOL_LIBRARIES") != nullptr || (pre && std::strstr(pre, "rocprofiler"));
-  }();
-  if (g_ctx_parts >= 2 && !profiled) {
+  if (g_ctx_parts >= 2 && !profiled_run()) {
     hipDeviceProp_t prop;
     int ncu = 256;
     if (hipGetDeviceProperties(&prop, g_device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
@@ -234,8 +230,8 @@ static int trim_all_contexts() {
 // released block goes back to the driver.  An allocation that fails trims every context's parked blocks and retries (dev_alloc).
 static size_t pool_cap_bytes() {
   static const size_t cap = [] {
-    const char* e = std::getenv("QEMB_POOL_CAP_GB");
-    if (e) return (size_t)(std::atof(e) * (double)(1ull << 30));
+    const double gb = env_real("QEMB_POOL_CAP_GB", -1.0);
+    if (gb >= 0) return (size_t)(gb * (double)(1ull << 30));
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) return (size_t)96 << 30;
     return total_b / 2;
@@ -346,7 +342,7 @@ int dev_free(void* p) {
 // one stream wait, slot -> destination.  QEMB_STAGED_COPIES=0: the plain calls, for A/B runs.
 static constexpr size_t STAGE_SLOT = 256 * 1024;      // (n x n doubles up to n = 181)
 static bool stage_ready(DevCtx& c) {
-  static const bool on = !(std::getenv("QEMB_STAGED_COPIES") && std::atoi(std::getenv("QEMB_STAGED_COPIES")) == 0);
+  static const bool on = env_flag("QEMB_STAGED_COPIES", true);
   if (!on || c.capturing) return false;
   if (c.stage) return true;
   void* q = nullptr;
@@ -497,7 +493,7 @@ int dev_graph_begin(int for_tape) {
 // ~16 levels deep.  The assertion of independence is the caller's; the lock-step tests compare bit for bit with the one-by-one solves.
 enum { MARK_REGION_BEGIN = 0xA1, MARK_CHAIN = 0xA2, MARK_REGION_END = 0xA3 };
 static bool regions_enabled() {      // QEMB_TAPE_REGIONS=0: no markers are recorded, the tape is the plain sequence (A/B runs)
-  static const bool on = !(std::getenv("QEMB_TAPE_REGIONS") && std::atoi(std::getenv("QEMB_TAPE_REGIONS")) == 0);
+  static const bool on = env_flag("QEMB_TAPE_REGIONS", true);
   return on;
 }
 static int region_mark(int value) {
@@ -538,7 +534,7 @@ int dev_graph_destroy(dev_graph_t g) { if (g) (void)hipGraphExecDestroy((hipGrap
 // with its block index inside that member.  Kernels are registered by the address of their wrapper, which is what a captured graph node
 // carries; the registrars run when the library is loaded, so the map below is complete before anything reads it (grouped_launch.h).
 std::map<const void*, GroupInfo>& groupable() { static std::map<const void*, GroupInfo> m; return m; }
-bool group_xcd_mode() { static const bool on = [] { const char* e = std::getenv("QEMB_GROUP_XCD"); return e && e[0] != '0'; }(); return on; }
+bool group_xcd_mode() { static const bool on = env_flag("QEMB_GROUP_XCD", false); return on; }
 
 // ---- tapes: captured launch sequences executed together -------------------------------------------------------------------------------
 // A tape keeps the captured hipGraph alive (it owns the argument storage of its nodes) and lists the nodes in execution order.
@@ -753,7 +749,7 @@ static std::vector<TapeSegment> tape_segments(const Tape* t) {
 }
 
 static int build_plan(const dev_tape_t* tapes, int n, TapePlan** out) {
-  static const bool grouping = !(std::getenv("QEMB_TAPE_GROUP") && std::atoi(std::getenv("QEMB_TAPE_GROUP")) == 0);
+  static const bool grouping = env_flag("QEMB_TAPE_GROUP", true);
   const bool regions_on = regions_enabled();
   TapePlan* plan = new TapePlan();
   for (int f = 0; f < n; ++f) plan->key.push_back(tapes[f]);
@@ -849,7 +845,7 @@ int dev_tape_last_stats(long long* launches, long long* grouped, long long* oper
 
 // ---- timers -----------------------------------------------------------------------------------
 static bool timers_enabled() {
-  static const bool on = [] { const char* e = std::getenv("QEMB_TIMERS"); return !(e && e[0] == '0'); }();
+  static const bool on = env_flag("QEMB_TIMERS", true);
   return on;
 }
 // fold every lap whose stop event has completed into the totals (oldest first; stops at the first one still in flight unless `wait`)
@@ -2283,7 +2279,7 @@ __device__ __forceinline__ void publish_flag(unsigned long long* flag_host, unsi
   __hip_atomic_store(flag_host, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 static int post_finish_mode() {
-  static const int m = [] { const char* e = std::getenv("QEMB_POST_FINISH"); return (e && e[0] == '2') ? 2 : 0; }();
+  static const int m = env_int("QEMB_POST_FINISH", 0) == 2 ? 2 : 0;
   return m;
 }
 // second kernel of the QEMB_POST_FINISH=0 form: out[j] = sum of the np partials of reduction j, j < m, to device and pinned host memory
@@ -3109,8 +3105,8 @@ int dev_jk_from_packed(int64_t n, const double* S4, const double* D, const doubl
   if (rc) return rc;
   double* P1 = g_ws; double* P2 = g_ws + np * n;
   hipError_t attr_err = hipSuccess;
-  static const bool old_kernel = std::getenv("QEMB_JK_V1") != nullptr;      // A/B measurements (tools/hbm_kernels.py)
-  static const int gl = std::getenv("QEMB_JK_GL") ? std::atoi(std::getenv("QEMB_JK_GL")) : 16;      // 16: 1.28 ms, 32: 1.32 ms at n = 220
+  static const bool old_kernel = env_flag("QEMB_JK_V1", false);      // A/B measurements (tools/hbm_kernels.py)
+  static const int gl = (int)env_int("QEMB_JK_GL", 16);      // 16: 1.28 ms, 32: 1.32 ms at n = 220
   if (n >= 2 && n <= 448 && !old_kernel) {
     // 32-lane row groups (two rows per wave step): 8 partial vectors; 16-lane groups (four rows): 16
     const int nslot = gl == 16 ? 16 : 8;
@@ -3165,7 +3161,7 @@ __device__ __forceinline__ long long pair_idx(long long i, long long j) { return
 
 // row walkers per tile of the tiled unpack: enough blocks for 8 per CU and some slack for the tail (QEMB_UNPACK_WALKERS overrides: A/B runs)
 static int64_t unpack_walkers(int64_t rows, int64_t ntiles) {
-  static const int64_t forced = std::getenv("QEMB_UNPACK_WALKERS") ? std::atoll(std::getenv("QEMB_UNPACK_WALKERS")) : 0;
+  static const int64_t forced = env_int("QEMB_UNPACK_WALKERS", 0);
   const int64_t want = forced > 0 ? forced : 65535;      // one row per block measured best (profiles/r03_hbm_kernels.jsonl)
   return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(rows, 65535), want));
 }

@@ -148,7 +148,7 @@ int Fragment::set_mo_route(int route) {
   return 0;
 }
 bool Fragment::use_factor_route() const {
-  static const bool off = std::getenv("QEMB_MO_FROM_FACTOR") && std::atoi(std::getenv("QEMB_MO_FROM_FACTOR")) == 0;      // A/B measurements
+  static const bool off = !env_flag("QEMB_MO_FROM_FACTOR", true);      // A/B measurements
   if (!df_factor_.p || mo_route_ == 0 || off) return false;
   if (!eri_s4_.p) return true;      // a fragment that lives on its factor: forming the block first would cost what the factor's own product costs
   return mo_route_ == 1 || mo_factor_route_pays(n_, df_naux_);
@@ -469,45 +469,26 @@ int Fragment::solve_batch(const std::vector<Fragment*>& frs, const std::vector<i
                           const std::vector<BatchOutputs>& outs, LockstepStats* stats) {
   const int F = (int)frs.size();
   if (F == 0) return 0;
-  static const bool trace = std::getenv("QEMB_BATCH_TRACE") != nullptr;
+  static const bool trace = env_flag("QEMB_BATCH_TRACE", false);
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_start = now();
   res.assign(F, FragmentResult());
-  static const bool pool_on = !(std::getenv("QEMB_PHASE_POOL") && std::atoi(std::getenv("QEMB_PHASE_POOL")) == 0);      // (0: a std::thread per fragment and phase, for A/B runs)
+  static const bool pool_on = env_flag("QEMB_PHASE_POOL", true);      // (0: a std::thread per fragment and phase, for A/B runs)
   Fanout per_fragment(F);
   QTRY(per_fragment.init(pool_on));
   const bool threaded = per_fragment.threaded;
-  // Before the iterations: the fragment RHF per fragment (host round trips inside), then MO integrals + CCSD set-up + starting amplitudes.  The latter is a pure
-  // launch sequence (~60 launches per small fragment) and CAN be recorded as a tape per fragment and run merged on the home stream like the iterations
-  // (QEMB_TAPE_PREPHASE=1).  Measured in round 5 and left off: recording the sequence anew every sweep (stream capture + node queries) and running the merged
-  // sequence serially costs more than six streams issuing it side by side -- octane BE2 begin phase 3.1 -> 3.9 ms, BE3 sweep 26.9 -> 27.8 ms.
-  static const bool tape_pre = std::getenv("QEMB_TAPE_PREPHASE") && std::atoi(std::getenv("QEMB_TAPE_PREPHASE")) != 0;
-  // (one pass of the host threads for both halves of the begin phase since round 5: a fragment goes on to its integrals as soon as ITS RHF is through instead of
-  //  waiting for the slowest RHF of the sweep)
+  // Before the iterations: the fragment RHF per fragment (host round trips inside), then MO integrals + CCSD set-up + starting amplitudes, each fragment on its own
+  // stream.  (One pass of the host threads for both halves of the begin phase: a fragment goes on to its integrals as soon as ITS RHF is through instead of
+  //  waiting for the slowest RHF of the sweep.)
   std::vector<double> ms_scf(F, 0.0);
   std::vector<double> ms_cc(F, 0.0), ms_capture(F, 0.0);      // (trace: the slowest fragment's share of the second half of the begin phase)
-  std::vector<dev_tape_t> pre(F, nullptr);
-  std::vector<char> taped(F, 0);
-  struct PreTapes { std::vector<dev_tape_t>& t; ~PreTapes() { for (dev_tape_t x : t) if (x) (void)dev_tape_destroy(x); } } pre_guard{pre};
-  const bool small_all = [&] { for (int f = 0; f < F; ++f) { const int64_t oo = o[f], vv = frs[f]->n_ - o[f]; if (oo * oo * vv * vv > ((int64_t)1 << 22)) return false; } return true; }();
-  const bool try_tape = tape_pre && threaded && small_all && opt.relax_density == 0;
   QTRY(per_fragment([&](int f) {
-    int r = 0;
-    {
-      const double ts = now();
-      r = frs[f]->solve_begin_scf(o[f], h[f], dm0[f], opt, eeval, &res[f]);
-      ms_scf[f] = now() - ts;
-      if (r != 0) return r;
-    }
-    if (try_tape && !frs[f]->sp_.no_virtuals && dev_graph_begin(1) == 0) {
-      const int rc_cc = frs[f]->solve_begin_cc(true);
-      dev_tape_t t = nullptr;
-      const int rc_end = dev_tape_end(&t);
-      if (rc_cc == 0 && rc_end == 0 && t) { pre[f] = t; taped[f] = 1; }
-      else { if (t) (void)dev_tape_destroy(t); frs[f]->retire_solver(); }      // (what failed shows again in the eager pass below)
-    }
+    const double ts = now();
+    int r = frs[f]->solve_begin_scf(o[f], h[f], dm0[f], opt, eeval, &res[f]);
+    ms_scf[f] = now() - ts;
+    if (r != 0) return r;
     const double t0 = now();
-    if (!taped[f]) r = frs[f]->solve_begin_cc(false);
+    r = frs[f]->solve_begin_cc();
     const double t1 = now();
     if (r == 0 && frs[f]->cc_ && F > 1) r = frs[f]->tape_for_lockstep(F);      // recorded side by side (or kept from the last sweep); a lone fragment keeps its executable graph
     const double t2 = now();
@@ -515,15 +496,6 @@ int Fragment::solve_batch(const std::vector<Fragment*>& frs, const std::vector<i
     ms_cc[f] = (t1 - t0) + (now() - t2); ms_capture[f] = t2 - t1;
     return r;
   }));
-  {
-    std::vector<dev_tape_t> run;
-    for (int f = 0; f < F; ++f) if (taped[f]) run.push_back(pre[f]);
-    if (!run.empty()) {
-      QTRY(dev_tape_run(run.data(), (int)run.size()));      // on the calling thread's (home) stream
-      QTRY(dev_sync());
-      for (int f = 0; f < F; ++f) if (taped[f]) QTRY(frs[f]->cc_->fetch_energy());
-    }
-  }
   const double t_begin_done = now();
   std::vector<CcsdSolver*> solvers; std::vector<int> idx, ctx; std::vector<CcsdOptions> copt;
   for (int f = 0; f < F; ++f) if (!frs[f]->sp_.no_virtuals) { solvers.push_back(frs[f]->cc_.get()); idx.push_back(f); ctx.push_back(threaded ? f + 1 : 0); copt.push_back(opt.cc); }
@@ -542,7 +514,7 @@ int Fragment::solve_batch(const std::vector<Fragment*>& frs, const std::vector<i
 
 int Fragment::solve_begin(int o, const double* h, const double* dm0, const FragmentOptions& opt, int eeval, FragmentResult* res) {
   QTRY(solve_begin_scf(o, h, dm0, opt, eeval, res));
-  return solve_begin_cc(false);
+  return solve_begin_cc();
 }
 // every solver refuses an energy evaluation without the static data before its fragment RHF
 int Fragment::check_energy_data(int eeval) const {
@@ -562,7 +534,7 @@ int Fragment::solve_begin_scf(int o, const double* h, const double* dm0, const F
   // nsocc == n: an embedding space without virtual orbitals.  PySCF's CCSD then has empty amplitude arrays and returns E_corr = 0; the
   // sweep body needs the mean-field results only (density = 2 I in any orthonormal basis, no correlation contribution to the energies).
   const int64_t n2 = (int64_t)n * n;
-  static const bool trace = std::getenv("QEMB_SCF_TRACE") != nullptr;      // host time of the steps of this phase on stderr (a measuring aid)
+  static const bool trace = env_flag("QEMB_SCF_TRACE", false);      // host time of the steps of this phase on stderr (a measuring aid)
   auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t0 = trace ? now() : 0.0;
   retire_solver();
@@ -586,7 +558,7 @@ int Fragment::solve_begin_scf(int o, const double* h, const double* dm0, const F
   return 0;
 }
 // ---- integrals + CCSD set-up + starting amplitudes: launches only (allocations come from the context's pool once a sweep has run)
-int Fragment::solve_begin_cc(bool defer_energy) {
+int Fragment::solve_begin_cc() {
   const int o = sp_.o, v = n_ - o;
   const FragmentOptions& opt = sp_.opt;
   FragmentResult* res = sp_.res;
@@ -603,9 +575,9 @@ int Fragment::solve_begin_cc(bool defer_energy) {
   cc_.reset(new CcsdSolver());
   QTRY(cc_->setup(std::move(ints), eps_));
   if (opt.warm_start && t_prev_.p && t_prev_o_ == o) {
-    QTRY(cc_->set_amps(t_prev_.p, t_prev_.p + (int64_t)o * v, defer_energy));
+    QTRY(cc_->set_amps(t_prev_.p, t_prev_.p + (int64_t)o * v));
   } else {
-    QTRY(cc_->init_amps(defer_energy));
+    QTRY(cc_->init_amps());
   }
   sp_.alloc_hash = dev_alloc_trace_end();
   return 0;
@@ -621,16 +593,17 @@ void tape_cache_counters(long long* reused, long long* recorded, int reset) {
   if (recorded) *recorded = g_tape_recorded.load();
   if (reset) { g_tape_reused = 0; g_tape_recorded = 0; }
 }
+// (peers: the fragment count of the sweep; it only enters the key)
 int Fragment::tape_for_lockstep(int peers) {
-  static const bool cache_on = !(std::getenv("QEMB_TAPE_CACHE") && std::atoi(std::getenv("QEMB_TAPE_CACHE")) == 0);
-  const bool check = std::getenv("QEMB_TAPE_CACHE_CHECK") && std::atoi(std::getenv("QEMB_TAPE_CACHE_CHECK")) != 0;
+  static const bool cache_on = env_flag("QEMB_TAPE_CACHE", true);
+  const bool check = env_flag("QEMB_TAPE_CACHE_CHECK", false);
   unsigned long long key = sp_.alloc_hash ^ (0x9e3779b97f4a7c15ull * (unsigned long long)(peers + 1)) ^ ((unsigned long long)sp_.o << 40) ^ ((unsigned long long)n_ << 20);
   if (key == 0) key = 1;
   tape_key_ = key;
-  if (std::getenv("QEMB_TAPE_CACHE_TRACE")) std::fprintf(stderr, "[qemb tape cache] fragment %p n %d: key %016llx, kept %016llx\n", (void*)this, n_, key, tape_cache_.tape ? tape_cache_.key : 0ull);
+  if (env_flag("QEMB_TAPE_CACHE_TRACE", false)) std::fprintf(stderr, "[qemb tape cache] fragment %p n %d: key %016llx, kept %016llx\n", (void*)this, n_, key, tape_cache_.tape ? tape_cache_.key : 0ull);
   if (cache_on && tape_cache_.tape && tape_cache_.key == key) {
     if (check) {
-      QTRY(cc_->prepare_tape(peers));
+      QTRY(cc_->prepare_tape());
       if (cc_->tape() && !dev_tape_equal(cc_->tape(), tape_cache_.tape)) { set_error(std::string("the kept tape differs from a fresh recording at the same buffer layout: ") + last_error()); return QEMB_ERR_DEVICE; }
     }
     cc_->adopt_tape(tape_cache_.tape);
@@ -639,7 +612,7 @@ int Fragment::tape_for_lockstep(int peers) {
     return 0;
   }
   g_tape_recorded += 1;
-  return cc_->prepare_tape(peers);
+  return cc_->prepare_tape();
 }
 void Fragment::retire_solver() {
   if (cc_) {

@@ -76,10 +76,9 @@ class Fragment {
   // everything after -- so that several fragments can share the middle step.  solve_end keeps what belongs to CCSD (amplitudes, Lambda equations, the 1-RDM, the
   // per-site two-body energies) and ends in finish_solve, the tail it shares with solve_mp2 and solve_fci.
   int solve_begin(int o, const double* h, const double* dm0, const FragmentOptions& opt, int eeval, FragmentResult* res);
-  // ... and solve_begin itself in two halves: the fragment RHF (host round trips inside), then MO integrals + CCSD set-up + starting amplitudes -- a pure launch
-  // sequence, which solve_batch records as a tape per fragment and runs merged for all fragments (defer_energy: the guess's energy is fetched afterwards)
+  // ... and solve_begin itself in two halves: the fragment RHF (host round trips inside), then MO integrals + CCSD set-up + starting amplitudes (launches only)
   int solve_begin_scf(int o, const double* h, const double* dm0, const FragmentOptions& opt, int eeval, FragmentResult* res);
-  int solve_begin_cc(bool defer_energy);
+  int solve_begin_cc();
   int solve_end(double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* t1, double* t2);
   struct BatchOutputs { double *mo_coeff = nullptr, *mo_energy = nullptr, *rdm1_emb = nullptr, *rdm1_mo = nullptr, *t1 = nullptr, *t2 = nullptr; };
   // every fragment of a sweep in one call: solve_begin / solve_end per fragment on its own execution context (host thread + stream),

@@ -49,13 +49,10 @@ typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));      // a pa
 // (stream), so a setter cannot change the tile choice of GEMMs dispatched -- or being captured into a hipGraph -- by another thread.
 static thread_local int t_gemm_force_cfg = -1;
 static thread_local int t_gemm_splitk_enabled = 1;
-static thread_local int t_gemm_peers = 1;
 static std::atomic<long long> g_gemm_flops{0};
 static thread_local GemmLaunchRecord t_gemm_last{};      // qemb_gemm_last_launch: written by the dispatcher and launch_cfg, read by tests
 void dev_gemm_last_launch(GemmLaunchRecord* out) { *out = t_gemm_last; }
 int dev_gemm_flop_count(double* flops, int reset) { if (flops) *flops = (double)g_gemm_flops.load(); if (reset) g_gemm_flops = 0; return QEMB_OK; }
-void dev_gemm_set_peers(int n) { t_gemm_peers = n > 1 ? n : 1; }
-int dev_gemm_peers() { return t_gemm_peers; }
 void dev_gemm_set_force_cfg(int cfg) { t_gemm_force_cfg = cfg; }
 void dev_gemm_set_auto_splitk(int enabled) { t_gemm_splitk_enabled = enabled; }
 
@@ -629,7 +626,7 @@ static int launch_cfg(const GemmDesc& d, hipStream_t s) {
   {
     // super-blocks of 32 tiles (the workgroups one XCD runs at a time at one workgroup per CU): the shape that moves the fewest operand bytes
     // per k-step, sb_m x |A tile| + sb_n x |B tile|, among the shapes that divide the tile grid (QEMB_GEMM_SB=0: the m-fastest walk, for A/B runs)
-    static const bool sb_on = !(std::getenv("QEMB_GEMM_SB") && std::atoi(std::getenv("QEMB_GEMM_SB")) == 0);
+    static const bool sb_on = env_flag("QEMB_GEMM_SB", true);
     if (sb_on && d.batch == 1 && d.ksplit <= 1 && g.tiles_m >= 8 && g.tiles_n >= 4 && ((long long)g.tiles_m * g.tiles_n) % 256 == 0) {
       long long best = -1;
       for (int sm = 1; sm <= 32; sm *= 2) {
@@ -713,7 +710,7 @@ static int launch_tile(const GemmDesc& d, hipStream_t s, bool vec2) {
 
 // 16-byte loads of an operand tile: the rule is gemm_operand_vec2_ok (dev_ops.h); QEMB_GEMM_VEC2_ODD=0 selects the round-4 rule, for A/B runs
 static bool gemm_vec2_relaxed() {
-  static const bool relaxed = !(std::getenv("QEMB_GEMM_VEC2_ODD") && std::atoi(std::getenv("QEMB_GEMM_VEC2_ODD")) == 0);
+  static const bool relaxed = env_flag("QEMB_GEMM_VEC2_ODD", true);
   return relaxed;
 }
 
@@ -834,7 +831,7 @@ int dev_gemm_stamps(const GemmDesc& d, int waves_per_wg, double* out) {
 
 // QEMB_GEMM_TRACE=1: every product goes through dev_gemm_probe and is logged -- a debugging aid, not a mode to run in
 int dev_gemm(const GemmDesc& d) {
-  static const bool trace = std::getenv("QEMB_GEMM_TRACE") != nullptr;
+  static const bool trace = env_flag("QEMB_GEMM_TRACE", false);
   if (!trace || dev_capturing()) return dev_gemm_dispatch(d);
   double ms = 0.0, ghz = 0.0; long long wg = 0;
   const int rc = dev_gemm_probe(d, &ms, &ghz, &wg);
@@ -855,7 +852,7 @@ static int dev_gemm_dispatch(const GemmDesc& d) {
   g_gemm_flops += 2ll * d.M * d.N * d.K * d.batch;
   {  // QEMB_GEMM_SHAPELOG=<file>: one line per product in launch order (M N K batch a_kcontig b_kcontig cfg ksplit) -- no timing, no synchronisation; a single-stream
      // run under rocprofv3 --kernel-trace then pairs the i-th dgemm_mfma_kernel dispatch of the trace with the i-th line (tools/kernel_roofline.py: products by shape)
-    static FILE* shapelog = [] { const char* e = std::getenv("QEMB_GEMM_SHAPELOG"); return (e && e[0]) ? std::fopen(e, "w") : (FILE*)nullptr; }();
+    static FILE* shapelog = [] { const char* e = env_str("QEMB_GEMM_SHAPELOG"); return e ? std::fopen(e, "w") : (FILE*)nullptr; }();
     if (shapelog) {
       static std::mutex mu;
       std::lock_guard<std::mutex> lock(mu);
@@ -886,7 +883,7 @@ static int dev_gemm_dispatch(const GemmDesc& d) {
   // 3xx (s_memtime stamps) and 4xx-6xx (ablation: WRONG products by construction) exist for tools/ only: unreachable unless the process
   // says it is a measurement run
   if (cfg >= 300) {
-    static const bool diag = std::getenv("QEMB_GEMM_DIAGNOSTICS") != nullptr;
+    static const bool diag = env_flag("QEMB_GEMM_DIAGNOSTICS", false);
     if (!diag) { set_error("dev_gemm: tile configs >= 300 are diagnostic instantiations (set QEMB_GEMM_DIAGNOSTICS=1 in a measurement run)"); return QEMB_ERR_ARG; }
   }
   t_gemm_last = GemmLaunchRecord{};

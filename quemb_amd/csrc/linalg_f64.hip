@@ -673,7 +673,7 @@ static int jacobi_rows(int nvec, int64_t len, double* W, int64_t ldw, double* Vt
   const int np = (nvec % 2 == 0) ? nvec : nvec + 1;
   // (64 < nvec <= 96 take the block rounds below since round 5: n = 96 cold 3.2-3.4 -> 1.35 ms, warm 1.28 -> 0.60 ms; n = 80 2.1 -> 1.34 / 0.89 -> 0.60 ms -- one
   //  workgroup is bound by the LDS bandwidth of its CU there; at n = 57 the single workgroup is still the faster one, 0.86 vs 0.92 ms.  QEMB_JACOBI_ROWS_SMALL_MAX=96: as before)
-  static const int rows_small_max = [] { const char* e = std::getenv("QEMB_JACOBI_ROWS_SMALL_MAX"); return e ? std::atoi(e) : 64; }();
+  static const int rows_small_max = (int)env_int("QEMB_JACOBI_ROWS_SMALL_MAX", 64);
   if (Vt && nvec <= JS_MAX && len <= JS_MAX && nvec <= rows_small_max) {   // LDS-resident single-workgroup path
     int* d_sw = nullptr;
     QTRY_ALLOC(d_sw, sizeof(int));
@@ -695,7 +695,7 @@ static int jacobi_rows(int nvec, int64_t len, double* W, int64_t ldw, double* Vt
   const double tol = std::max(1.0e-15, std::sqrt((double)len) * 2.22e-16);   // LAPACK dgesvj-style
   const int max_sweeps = 40;
   // block rounds when two blocks of 16 vectors fit registers + LDS (QEMB_JACOBI_BLOCK=0: per-pair rounds, A/B runs)
-  static const bool blocks_enabled = !(std::getenv("QEMB_JACOBI_BLOCK") && std::atoi(std::getenv("QEMB_JACOBI_BLOCK")) == 0);
+  static const bool blocks_enabled = env_flag("QEMB_JACOBI_BLOCK", true);
   int B = 0;
   if (Vt && blocks_enabled && len < (1 << 20)) {
     // two blocks of 16 vectors, [W row | Vt row] <= 600 doubles (10 register slots per lane): eigh for 96 < n <= 300 (the fragment Fock matrices).  (Instantiations with 8 / 4 vectors per block and up to 38 slots were built and measured: an
@@ -766,10 +766,10 @@ static int jacobi_eigh_impl(int64_t n64, double* A, double* w, double* V, int* s
   const int n = (int)n64;
   if (n <= 0) return QEMB_OK;
   // small matrices: the whole eigensolve in one launch (two-sided Jacobi in LDS; QEMB_JACOBI_TWOSIDED=0: the one-sided path below, for A/B runs)
-  static const bool two_sided = !(std::getenv("QEMB_JACOBI_TWOSIDED") && std::atoi(std::getenv("QEMB_JACOBI_TWOSIDED")) == 0);
+  static const bool two_sided = env_flag("QEMB_JACOBI_TWOSIDED", true);
   // (n <= 80: the one-barrier kernel; 80 < n <= 96 went through the three-barrier kernel until round 5 -- 1.28 ms warm, bound by the LDS bandwidth of its one CU -- and take
   //  the block rounds of jacobi_rows now, 0.60 ms; QEMB_JACOBI_SMALL_MAX=96: as before)
-  static const int small_max = [] { const char* e = std::getenv("QEMB_JACOBI_SMALL_MAX"); return e ? std::min(std::atoi(e), JE_MAX) : JE_DB_MAX; }();
+  static const int small_max = std::min((int)env_int("QEMB_JACOBI_SMALL_MAX", JE_DB_MAX), JE_MAX);
   if (two_sided && n <= small_max) {
     int* d_st = nullptr;
     QTRY_ALLOC(d_st, sizeof(int));
@@ -778,7 +778,7 @@ static int jacobi_eigh_impl(int64_t n64, double* A, double* w, double* V, int* s
     static std::atomic<bool> attr_set{false};
     if (!attr_set) { HIP_TRY(hipFuncSetAttribute((const void*)jacobi_eigh_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64)); attr_set = true; }
     const double tol = std::max(1.0e-15, std::sqrt((double)n) * 2.22e-16);
-    static const bool one_barrier = !(std::getenv("QEMB_JACOBI_DB") && std::atoi(std::getenv("QEMB_JACOBI_DB")) == 0);
+    static const bool one_barrier = env_flag("QEMB_JACOBI_DB", true);
     if (one_barrier && n <= JE_DB_MAX) {
       const size_t lds_db = sizeof(double) * ((size_t)3 * n * ld + n) + sizeof(int) * (size_t)n + 16;
       static std::atomic<bool> attr_db{false};
@@ -840,7 +840,7 @@ static int jacobi_eigh_impl(int64_t n64, double* A, double* w, double* V, int* s
 
 // ---- fused steps of the fragment RHF of small fragments (scf.cpp)
 int dev_scf_fused_max() {
-  static const int m = [] { const char* e = std::getenv("QEMB_SCF_FUSED"); return (e && std::atoi(e) == 0) ? 0 : JE_DB_MAX; }();      // (QEMB_SCF_FUSED=0: the launch-by-launch cycle, for A/B runs)
+  static const int m = env_flag("QEMB_SCF_FUSED", true) ? JE_DB_MAX : 0;      // (QEMB_SCF_FUSED=0: the launch-by-launch cycle, for A/B runs)
   return m;
 }
 int dev_jacobi_eigh_in_basis(int64_t n64, const double* F, const double* Cp, double* w, double* C_out, double* C2_out, int nocc, double* dm_out, double stop_below,

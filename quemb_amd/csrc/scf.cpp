@@ -122,7 +122,7 @@ static int rhf_loop(int n, int o, const double* h, const JkSource& src, double* 
     int st; std::memcpy(&st, word, sizeof(int));
     return jacobi_status_code(st, "dev_jacobi_eigh_in_basis (fragment SCF)");      // (a NaN Fock matrix -- a diverged DIIS step -- is QEMB_ERR_NUMERIC, not a converged eigensolve)
   };
-  static const bool trace = std::getenv("QEMB_SCF_TRACE") != nullptr;
+  static const bool trace = env_flag("QEMB_SCF_TRACE", false);
   auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   for (cyc = 0; cyc < opt.max_cycle; ++cyc) {
     const double tc0 = trace ? now() : 0.0;

@@ -121,3 +121,23 @@ def test_readme_ladder_agreement_lines_follow_their_csv():
             assert len(hit) == 1
             return float(hit[0]["AverageNs"]) * 1e-6
         assert abs(avg("7, 2, 2, 4, 16, true, true, 2, 1, 1") - float(a)) < 5e-4 and abs(avg("6, 2, 2, 4, 16, true, true, 2, 1, 1") - float(b)) < 5e-4, (name, a, b)
+
+
+def test_every_switch_is_read_through_the_helpers_and_listed_once():
+    """Every QEMB_* switch of the library is read through env_flag / env_int / env_real / env_str (quemb_amd/csrc/env.h) with its name as a literal, and the
+    switch table of DESIGN.md section 5 lists exactly those names, each once; no getenv("QEMB_...") is left beside the helpers."""
+    csrc = ROOT / "quemb_amd" / "csrc"
+    srcs = [f for f in sorted(csrc.iterdir()) if f.suffix in (".cpp", ".hip", ".h", ".inc")]
+    read = set()
+    for f in srcs:
+        txt = f.read_text()
+        assert 'getenv("QEMB_' not in txt, f"{f.name} reads a switch beside the helpers of env.h"
+        read |= set(re.findall(r'\benv_(?:flag|int|real|str)\(\s*"(QEMB_\w+)"', txt))
+    design = (ROOT / "DESIGN.md").read_text()
+    m = re.search(r"<!-- switches -->\n(.*?)\n<!-- /switches -->", design, flags=re.S)
+    assert m, "DESIGN.md carries no switch table"
+    rows = [ln for ln in m.group(1).splitlines()[2:] if ln.strip()]
+    listed = [re.match(r"\| `(QEMB_\w+)` \|", ln).group(1) for ln in rows]
+    assert all(ln.count("|") == 5 for ln in rows)            # switch, default, what the other value does, who sets it
+    assert len(listed) == len(set(listed)), "a switch is listed twice"
+    assert read and set(listed) == read, (sorted(read - set(listed)), sorted(set(listed) - read))

@@ -508,3 +508,34 @@ def test_solve_batch_lockstep_equals_one_by_one(qlib):
     """qemb_frag_solve_batch on the HIP library: grouped launches of the lock-step CCSD iterations, results identical bit for bit"""
     from test_hostlogic_fragment import check_solve_batch_equals_one_by_one
     check_solve_batch_equals_one_by_one(qlib, sizes=((12, 4, 4), (16, 5, 5), (10, 3, 3), (14, 6, 4), (9, 9, 2), (20, 7, 6)), expect_grouped=True)
+
+
+def test_graph_replay_equals_eager_in_fresh_processes(qlib, tmp_path):
+    """The graph branch of the update recorder: a lone n = 12, n_occ = 4 fragment (the first Hamiltonian of check_solve_batch_equals_one_by_one) solved in a fresh
+    child process with the default settings -- one eager iteration, one capture into an executable graph, replays from there on -- and in a second fresh child
+    with QEMB_GRAPH=0 (every iteration eager), each with the default DIIS space and with cc_diis_space = 1 (the eager update then writes to another place).
+    n_iter >= 4: the eager pass, the capture and at least two replays.  The two modes launch the same kernels on the same operands in the same order, and on
+    the commit before the recorder was factored out they agree bit for bit in all five results of both cases: hence array_equal."""
+    import os
+    import subprocess
+    import sys
+    import replay_child as rc
+    got = {}
+    for mode, setting in (("graph", None), ("eager", "0")):
+        env = dict(os.environ)
+        env.pop("QEMB_GRAPH", None)
+        if setting is not None:
+            env["QEMB_GRAPH"] = setting
+        path = tmp_path / f"{mode}.npz"
+        r = subprocess.run([sys.executable, str(rc.__file__), str(path)], env=env, cwd=str(os.path.dirname(os.path.dirname(os.path.abspath(rc.__file__)))), timeout=120,
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        print(r.stdout[-4000:])
+        assert r.returncode == 0, f"{mode}: exit {r.returncode}\n{r.stdout[-4000:]}"
+        assert "replay child ok" in r.stdout
+        got[mode] = dict(np.load(path))
+    for case in rc.CASES:
+        assert int(got["graph"][f"{case}.n_iter"]) >= 4, case
+        for k in rc.KEYS:
+            a, b = got["graph"][f"{case}.{k}"], got["eager"][f"{case}.{k}"]
+            print(case, k, "max |graph - eager| =", float(np.abs(a - b).max()))
+            assert np.array_equal(a, b), (case, k)

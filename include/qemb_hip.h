@@ -193,6 +193,39 @@ int qemb_frag_solve_fci(qemb_frag_t f, int nsocc, const double* h, const double*
 int qemb_frag_fci_bytes(int n, int nsocc, int max_space, int64_t* bytes);
 int qemb_frag_fci_mem_limit(qemb_frag_t f, int64_t bytes);
 int qemb_frag_fci_residual(qemb_frag_t f, double* residual);
+/* solver == "SCI-hip": the selected-CI branch of be_func (molbe/solver.py:412-462, SHCI_ArgsUser(hci_cutoff)) as a heat-bath selection on the device, for fragments
+ * beyond the determinant-space limit of qemb_frag_solve_fci (n <= 64).  Fragment RHF, h1 and the ERIs in the fragment-MO basis as for FCI; then, from the HF
+ * determinant: every determinant outside the space V that a single or double excitation connects to some i in V with |H_ai c_i| >= eps_var joins, with its
+ * spin-swapped partner; the lowest eigenpair of H in the new V (CSR matrix over the sorted 2 x 64-bit keys, Davidson from the old vector padded with zeros, residual
+ * <= conv_tol); stop when a round adds nothing.  Energy, vector and RDMs are those of the last diagonalisation; no perturbative correction.  The determinant set,
+ * the matrix and the vector are the same bits on every call; the RDMs are accumulated with FP64 atomic adds and reproducible to rounding only.
+ * qemb_sci_opts: always start from qemb_default_sci_opts (eps_var 1e-3, conv_tol 1e-9, max_cycle 100, max_space 12, max_round 30, max_det 2^20); NULL means these
+ *   defaults; another struct_size or eps_var <= 0 is QEMB_ERR_ARG.  Reaching max_round before a round adds nothing, or a diagonalisation that misses conv_tol, is
+ *   non-convergence and follows strict_convergence (QEMB_ERR_NOCONV, or results and QEMB_WARN_NOCONV).
+ * Outputs as qemb_frag_solve_fci without the vector; e_sci the eigenvalue, n_iter the applications of H over all rounds.  nsocc == n is a single determinant.
+ * Limits: n > 64 is QEMB_ERR_UNSUPPORTED naming the limit.  Before anything is allocated the part of the working set that max_det fixes (qemb_frag_sci_bytes: three
+ * key lists and vectors, the candidate buffer of one slab, the Davidson vectors, row pointers, the n^4 pieces) is compared with min(free device memory, the limit of
+ * qemb_frag_sci_mem_limit): QEMB_ERR_ALLOC naming n, eps_var and the bytes.  Each round the count is checked against max_det and the CSR arrays (12 bytes per stored
+ * element, known once counted) against what is left: QEMB_ERR_ALLOC naming n, eps_var, the round, the count reached and the energy so far.
+ * qemb_frag_sci_stats: determinants, rounds, stored matrix elements and ||H c - E c||_2 of the last SCI solve (each nullable).
+ * qemb_frag_sci_dets: the final space, alpha[ndet], beta[ndet] (bit p = fragment MO p occupied, sorted by (alpha, beta)) and c[ndet] (each nullable). */
+typedef struct {
+  uint32_t struct_size;      /* sizeof(qemb_sci_opts); set by qemb_default_sci_opts, checked by every entry point that takes the struct */
+  double eps_var;            /* threshold on |H_ai c_i|   default 1e-3 (the reference's hci_cutoff) */
+  double conv_tol;           /* ||H c - E c||_2           default 1e-9 */
+  int max_cycle;             /* applications of H per diagonalisation   default 100 */
+  int max_space;             /* basis vectors             default 12 */
+  int max_round;             /* selection rounds          default 30 */
+  int64_t max_det;           /* determinants              default 2^20 */
+} qemb_sci_opts;
+void qemb_default_sci_opts(qemb_sci_opts* opts);
+int qemb_frag_solve_sci(qemb_frag_t f, int nsocc, const double* h, const double* dm0, const qemb_solver_opts* opts, const qemb_sci_opts* sci_opts, int eeval,
+                        double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* e_frag, double* e_sci, double* e_scf,
+                        double* ebe_hf, int* n_iter, int* scf_cycles);
+int qemb_frag_sci_stats(qemb_frag_t f, int64_t* ndet, int* rounds, int64_t* nnz, double* residual);
+int qemb_frag_sci_dets(qemb_frag_t f, uint64_t* alpha, uint64_t* beta, double* c);
+int qemb_frag_sci_bytes(int n, int nsocc, int64_t max_det, int max_space, int64_t* bytes);
+int qemb_frag_sci_mem_limit(qemb_frag_t f, int64_t bytes);
 /* The fragment 2-RDM in the fragment-MO basis, Frags.rdm2__ (molbe/solver.py:528): out[n^4] (host, [p][q][r][s]) from what the LAST solve of this fragment
  * left on the device.  kind names that solve and must agree with it:
  *   QEMB_RDM2_CCSD  make_rdm2_urlx(t1, t2, with_dm1) of shared/external/ccsd_rdm.py:23-55 (unrelaxed), from the kept t1 / t2 of qemb_frag_solve[_batch];
@@ -204,10 +237,13 @@ int qemb_frag_fci_residual(qemb_frag_t f, double* residual);
  * solve with relax_density the call returns QEMB_ERR_UNSUPPORTED.  Without a preceding solve of that kind, or after new ERIs / another SCF: QEMB_ERR_ARG.
  *   QEMB_RDM2_FCI   make_rdm2 of the vector qemb_frag_solve_fci left on the device, in PySCF's convention dm2[p,q,r,s] = <p+ r+ s q> (E = sum h dm1 + 1/2 sum (pq|rs) dm2);
  *                   with_dm1 = 0: minus the mean-field part of solver.py:513-527, what rdm2__ holds with use_cumulant.  D is formed once more and multiplied with itself
- *                   (8 n^2 N_det bytes of work space beside two n^4 tensors). */
+ *                   (8 n^2 N_det bytes of work space beside two n^4 tensors).
+ *   QEMB_RDM2_SCI   the same tensor of the selected vector qemb_frag_solve_sci left on the device with its determinants (24 bytes each; the matrix is not kept: its
+ *                   pattern, 4 bytes per stored element, is formed again for the call), accumulated over the stored pairs with FP64 atomic adds. */
 #define QEMB_RDM2_CCSD 0
 #define QEMB_RDM2_MP2 1
 #define QEMB_RDM2_FCI 2
+#define QEMB_RDM2_SCI 3
 int qemb_frag_rdm2(qemb_frag_t f, int kind, int with_dm1, double* out);
 /* The device memory qemb_frag_rdm2 of THIS fragment may take: before anything is allocated the call compares 8 n^4 bytes plus its workspace (the 1-RDM; for MP2 the
  * three o^2 v^2 tensors and the integral work space of forming t2 again) with min(free device memory, bytes) and fails with QEMB_ERR_ALLOC and n in the message when

@@ -272,6 +272,24 @@ int qemb_op_fci_rdm12(int n, int nsocc, const double* c_dev, int cumulant, doubl
 /* measurement hook (tools/fci_bench.py): one untimed application of H, then one whose three steps are bracketed by device timers; ms3 = D gather, G = V D, sigma gather */
 int qemb_op_fci_sigma_timed(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev, double* ms3);
 int qemb_op_fci_links(int n, int nsocc, int64_t* ns, int* nlink, int32_t* strings_host, int32_t* links_host);
+/* ---- selected CI (csrc/sci.cpp, kernels csrc/sci_ops.hip): the operations behind qemb_frag_solve_sci on handed-in data.  A space is ndet keys alpha[k], beta[k]
+ * (64-bit occupation words, bit p = orbital p occupied) sorted by (alpha, beta); every array but V_dev ([n^2][n^2] = (pq|rs)) is a host array.
+ * qemb_op_sci_screen: the determinants outside the space that pass |H_ai c_i| >= eps for some member i, spin partners included, sorted; slab / cap: determinants per
+ *   pass and keys of the candidate buffer (0: the defaults); *njoined always, the keys when njoined <= max_out.
+ * qemb_op_sci_merge: the space merged with sorted keys outside it, the vector padded with zeros (outputs: ndet + njoined).
+ * qemb_op_sci_matrix: the CSR matrix of H over the space (both triangles, columns ascending, the diagonal included): *nnz and rowptr[ndet + 1] always, col / val when
+ *   nnz <= max_nnz.   qemb_op_sci_spmv: y = H x.   qemb_op_sci_rdm12: dm1 [n][n] (symmetrised) and dm2 [n]^4 of the vector c; cumulant != 0: minus the mean-field part.
+ * qemb_frag_sci_stage_ms: host wall time (ms) of the five stages of the fragment's last SCI solve: screen, sort / merge, matrix, Davidson, RDMs (tools/sci_bench.py). */
+int qemb_op_sci_screen(int n, int nsocc, const double* h_host, const double* V_dev, int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, double eps,
+                       int64_t slab, int64_t cap, int64_t max_out, int64_t* njoined, uint64_t* out_alpha, uint64_t* out_beta);
+int qemb_op_sci_merge(int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, int64_t njoined, const uint64_t* jalpha, const uint64_t* jbeta,
+                      uint64_t* out_alpha, uint64_t* out_beta, double* out_c);
+int qemb_op_sci_matrix(int n, const double* h_host, const double* V_dev, int64_t ndet, const uint64_t* alpha, const uint64_t* beta, int64_t max_nnz, int64_t* nnz,
+                       int64_t* rowptr, int32_t* col, double* val);
+int qemb_op_sci_spmv(int n, const double* h_host, const double* V_dev, int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* x, double* y);
+int qemb_op_sci_rdm12(int n, int nsocc, const double* h_host, const double* V_dev, int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, int cumulant,
+                      double* dm1, double* dm2);
+int qemb_frag_sci_stage_ms(qemb_frag_t f, double* ms5);
 
 /* ---- orbital localisation (csrc/loc_ops.hip): joint diagonalisation of a stack of symmetric matrices by Jacobi sweeps -- Boys (K = 3 dipole matrices), Pipek-Mezey
  * (K = atoms) and Edmiston-Ruedenberg on a 3-index factor (K = naux) are this one problem.  Q_dev [K][m][m] and U_dev [m][m] are device pointers.  On return U is

@@ -46,6 +46,12 @@ class FciOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("conv_tol", C.c_double), ("max_cycle", C.c_int), ("max_space", C.c_int), ("lindep", C.c_double)]
 
 
+class SciOpts(C.Structure):
+    """qemb_sci_opts (include/qemb_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("eps_var", C.c_double), ("conv_tol", C.c_double), ("max_cycle", C.c_int), ("max_space", C.c_int),
+                ("max_round", C.c_int), ("max_det", C.c_int64)]
+
+
 _lib = None
 _initialised_device = None
 
@@ -202,6 +208,18 @@ def _declare(lib):
     f("qemb_op_fci_rdm12", I, I, I, P, I, P, P)
     f("qemb_op_fci_sigma_timed", I, I, I, P, P, P, P, P)
     f("qemb_op_fci_links", I, I, I, C.POINTER(L), IP, P, P)
+    f("qemb_default_sci_opts", None, C.POINTER(SciOpts))
+    f("qemb_frag_solve_sci", I, V, I, P, P, OP, C.POINTER(SciOpts), I, P, P, P, P, P, DP, DP, DP, IP, IP)
+    f("qemb_frag_sci_stats", I, V, C.POINTER(L), IP, C.POINTER(L), DP)
+    f("qemb_frag_sci_stage_ms", I, V, P)
+    f("qemb_frag_sci_dets", I, V, P, P, P)
+    f("qemb_frag_sci_bytes", I, I, I, L, I, C.POINTER(L))
+    f("qemb_frag_sci_mem_limit", I, V, L)
+    f("qemb_op_sci_screen", I, I, I, P, P, L, P, P, P, D, L, L, L, C.POINTER(L), P, P)
+    f("qemb_op_sci_merge", I, L, P, P, P, L, P, P, P, P, P)
+    f("qemb_op_sci_matrix", I, I, P, P, L, P, P, L, C.POINTER(L), P, P, P)
+    f("qemb_op_sci_spmv", I, I, P, P, L, P, P, P, P)
+    f("qemb_op_sci_rdm12", I, I, I, P, P, L, P, P, P, I, P, P)
     f("qemb_frag_rdm2", I, V, I, I, P)
     f("qemb_frag_rdm2_mem_limit", I, V, L)
     f("qemb_frag_rdm2_dev", I, V, I, I, P)

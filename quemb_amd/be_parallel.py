@@ -130,10 +130,11 @@ def be_func_parallel(pot, Fobjs, Nocc, solver, enuc, solver_args=None, scratch_d
     emap = emap or ErrorMap(Fobjs)
     nm = emap.n_match
     buf = np.zeros(2 * nm + 5)
-    from .solver import solve_fragments
+    from .solver import sci_opts_from_args, solve_fragments
+    sci_opts_from_args(solver, solver_args)      # (refused on every rank alike, before the collective)
     err = None
     try:
-        for out in solve_fragments(pot, [Fobjs[i] for i in mine], only_chem, opts, eeval, use_cumulant, relax_density, nstreams, lockstep, stats, solver):
+        for out in solve_fragments(pot, [Fobjs[i] for i in mine], only_chem, opts, eeval, use_cumulant, relax_density, nstreams, lockstep, stats, solver, solver_args):
             buf[2 * nm + 4] += out["n_iter"]
             if eeval:
                 buf[2 * nm + 1: 2 * nm + 4] += out["e_frag"]

@@ -17,6 +17,9 @@
 #include "int4c.h"
 #include "cd_core.h"
 #include "loc_core.h"
+#include "sci_core.h"
+#include <algorithm>
+#include <cmath>
 #include <mutex>
 #include <set>
 
@@ -651,6 +654,147 @@ int qemb_op_fci_rdm12(int n, int nsocc, const double* c_dev, int cumulant, doubl
   const FciTables* T = nullptr;
   QTRY(fci_tables(n, nsocc, &T));
   return fci_rdm12(*T, c_dev, cumulant ? nsocc : -1, dm1_host, dm2_dev);
+}
+// ---- solver == "SCI-hip"
+void qemb_default_sci_opts(qemb_sci_opts* o) {
+  SciOptions d;
+  memset(o, 0, sizeof *o);
+  o->struct_size = (uint32_t)sizeof(qemb_sci_opts);
+  o->eps_var = d.eps_var; o->conv_tol = d.conv_tol; o->max_cycle = d.max_cycle; o->max_space = d.max_space; o->max_round = d.max_round; o->max_det = d.max_det;
+}
+int qemb_frag_solve_sci(qemb_frag_t f, int nsocc, const double* h, const double* dm0, const qemb_solver_opts* opts, const qemb_sci_opts* sci_opts, int eeval,
+                        double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* e_frag, double* e_sci, double* e_scf,
+                        double* ebe_hf, int* n_iter, int* scf_cycles) {
+  CHECK_FRAG(f); CHECK_OPTS(opts);
+  if (sci_opts && sci_opts->struct_size != (uint32_t)sizeof(qemb_sci_opts)) {
+    set_error("qemb_sci_opts.struct_size is " + std::to_string(sci_opts->struct_size) + ", this library expects " + std::to_string(sizeof(qemb_sci_opts)) +
+              ": initialise the struct with qemb_default_sci_opts()");
+    return QEMB_ERR_ARG;
+  }
+  if (!h) { set_error("qemb_frag_solve_sci: h is NULL"); return QEMB_ERR_ARG; }
+  SciOptions so;
+  if (sci_opts) {
+    so.eps_var = sci_opts->eps_var; so.conv_tol = sci_opts->conv_tol; so.max_cycle = sci_opts->max_cycle; so.max_space = sci_opts->max_space;
+    so.max_round = sci_opts->max_round; so.max_det = sci_opts->max_det;
+  }
+  FragmentResult r;
+  const int rc = FRAG(f)->solve_sci(nsocc, h, dm0, to_opts(opts), so, eeval, &r, mo_coeff, mo_energy, rdm1_emb, rdm1_mo);
+  store_result(FRAG(f), r, rc, 0, true, e_frag, e_sci, e_scf, ebe_hf, n_iter, scf_cycles);
+  return rc;        // QEMB_OK, or QEMB_WARN_NOCONV with strict_convergence = 0
+}
+int qemb_frag_sci_stats(qemb_frag_t f, int64_t* ndet, int* rounds, int64_t* nnz, double* residual) {
+  CHECK_FRAG(f);
+  const SciResult& r = FRAG(f)->sci_result();
+  if (ndet) *ndet = r.ndet;
+  if (rounds) *rounds = r.rounds;
+  if (nnz) *nnz = r.nnz;
+  if (residual) *residual = r.residual;
+  return QEMB_OK;
+}
+int qemb_frag_sci_stage_ms(qemb_frag_t f, double* ms5) {
+  CHECK_FRAG(f);
+  if (!ms5) { set_error("qemb_frag_sci_stage_ms: null argument"); return QEMB_ERR_ARG; }
+  for (int k = 0; k < SCI_T_COUNT; ++k) ms5[k] = FRAG(f)->sci_result().ms[k];
+  return QEMB_OK;
+}
+int qemb_frag_sci_dets(qemb_frag_t f, uint64_t* alpha, uint64_t* beta, double* c) { CHECK_FRAG(f); return FRAG(f)->sci_dets(alpha, beta, c); }
+int qemb_frag_sci_bytes(int n, int nsocc, int64_t max_det, int max_space, int64_t* bytes) {
+  if (n <= 0 || nsocc <= 0 || nsocc > n || max_det < 1 || max_space < 2 || !bytes) { set_error("qemb_frag_sci_bytes: bad arguments"); return QEMB_ERR_ARG; }
+  if (n > kSciMaxOrb) { set_error("qemb_frag_sci_bytes: n = " + std::to_string(n) + " embedding orbitals; the selected CI takes at most " + std::to_string(kSciMaxOrb)); return QEMB_ERR_UNSUPPORTED; }
+  *bytes = sci_bytes(n, nsocc, max_det, max_space);
+  return QEMB_OK;
+}
+int qemb_frag_sci_mem_limit(qemb_frag_t f, int64_t bytes) { CHECK_FRAG(f); FRAG(f)->set_sci_mem_limit(bytes); return QEMB_OK; }
+// ---- the operations of the selected CI on handed-in data (host arrays but V_dev); a space: ndet sorted keys alpha[k], beta[k]
+namespace {
+int sci_upload(int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, SciSpace& V) {
+  if (ndet <= 0 || !alpha || !beta) { set_error("qemb_op_sci: a space needs ndet > 0 keys"); return QEMB_ERR_ARG; }
+  std::vector<uint64_t> k((size_t)(2 * ndet));
+  for (int64_t i = 0; i < ndet; ++i) {
+    k[(size_t)(2 * i)] = alpha[i]; k[(size_t)(2 * i + 1)] = beta[i];
+    if (i > 0 && !sci_key_less(alpha[i - 1], beta[i - 1], alpha[i], beta[i])) { set_error("qemb_op_sci: the keys must be sorted by (alpha, beta) and distinct"); return QEMB_ERR_ARG; }
+  }
+  QTRY(V.keys.alloc(2 * ndet)); QTRY(V.c.alloc(ndet));
+  QTRY(dev_h2d(V.keys, k.data(), sizeof(uint64_t) * 2 * ndet));
+  if (c) QTRY(dev_h2d(V.c, c, sizeof(double) * ndet)); else QTRY(dev_fill(V.c, ndet, 0.0));
+  V.N = ndet;
+  return 0;
+}
+int sci_download(const uint64_t* keys_dev, int64_t N, uint64_t* alpha, uint64_t* beta) {
+  std::vector<uint64_t> k((size_t)(2 * N));
+  if (N > 0) QTRY(dev_d2h(k.data(), keys_dev, sizeof(uint64_t) * 2 * N));
+  for (int64_t i = 0; i < N; ++i) { alpha[i] = k[(size_t)(2 * i)]; beta[i] = k[(size_t)(2 * i + 1)]; }
+  return 0;
+}
+int sci_op_integrals(int n, const double* h_host, const double* V_dev, DBuf& hd, double* dbl_bound) {
+  const int64_t n2 = (int64_t)n * n;
+  if (n <= 0 || n > kSciMaxOrb || !h_host || !V_dev) { set_error("qemb_op_sci: need 0 < n <= 64, h and V"); return QEMB_ERR_ARG; }
+  QTRY(hd.alloc(n2));
+  QTRY(dev_h2d(hd, h_host, sizeof(double) * n2));
+  if (dbl_bound) {
+    std::vector<double> Vh((size_t)(n2 * n2));
+    QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
+    double m = 0.0;
+    for (double x : Vh) m = std::max(m, std::fabs(x));
+    *dbl_bound = 2.0 * m;
+  }
+  return 0;
+}
+}  // namespace
+int qemb_op_sci_screen(int n, int nsocc, const double* h_host, const double* V_dev, int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, double eps,
+                       int64_t slab, int64_t cap, int64_t max_out, int64_t* njoined, uint64_t* out_alpha, uint64_t* out_beta) {
+  if (!c || !njoined || max_out < 0 || (max_out > 0 && (!out_alpha || !out_beta)) || !(eps > 0.0) || nsocc <= 0 || nsocc >= n) { set_error("qemb_op_sci_screen: bad arguments"); return QEMB_ERR_ARG; }
+  DBuf hd, joined; SciSpace V; double bound = 0.0;
+  QTRY(sci_op_integrals(n, h_host, V_dev, hd, &bound));
+  QTRY(sci_upload(ndet, alpha, beta, c, V));
+  QTRY(sci_screen(n, nsocc, hd, V_dev, bound, V, eps, slab, cap, (int64_t)1 << 40, joined, njoined));
+  if (*njoined > max_out) return QEMB_OK;      // the count alone: call again with room
+  return sci_download((const uint64_t*)joined.p, *njoined, out_alpha, out_beta);
+}
+int qemb_op_sci_merge(int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, int64_t njoined, const uint64_t* jalpha, const uint64_t* jbeta,
+                      uint64_t* out_alpha, uint64_t* out_beta, double* out_c) {
+  if (!c || !out_alpha || !out_beta || !out_c) { set_error("qemb_op_sci_merge: null argument"); return QEMB_ERR_ARG; }
+  SciSpace V, J, W;
+  QTRY(sci_upload(ndet, alpha, beta, c, V));
+  QTRY(sci_upload(njoined, jalpha, jbeta, nullptr, J));
+  QTRY(sci_merge(V, J.k(), J.N, W));
+  QTRY(sci_download(W.k(), W.N, out_alpha, out_beta));
+  return dev_d2h(out_c, W.c, sizeof(double) * W.N);
+}
+int qemb_op_sci_matrix(int n, const double* h_host, const double* V_dev, int64_t ndet, const uint64_t* alpha, const uint64_t* beta, int64_t max_nnz, int64_t* nnz,
+                       int64_t* rowptr, int32_t* col, double* val) {
+  if (!nnz || !rowptr) { set_error("qemb_op_sci_matrix: null argument"); return QEMB_ERR_ARG; }
+  DBuf hd; SciSpace V; SciMatrix H;
+  QTRY(sci_op_integrals(n, h_host, V_dev, hd, nullptr));
+  QTRY(sci_upload(ndet, alpha, beta, nullptr, V));
+  QTRY(sci_build(n, hd, V_dev, V.k(), V.N, -1, "qemb_op_sci_matrix", H));
+  *nnz = H.nnz;
+  QTRY(dev_d2h(rowptr, H.rowptr, sizeof(int64_t) * (ndet + 1)));
+  if (H.nnz > max_nnz || !col || !val) return QEMB_OK;      // the counts alone: call again with room
+  QTRY(dev_d2h(col, H.col, sizeof(int32_t) * H.nnz));
+  return dev_d2h(val, H.val, sizeof(double) * H.nnz);
+}
+int qemb_op_sci_spmv(int n, const double* h_host, const double* V_dev, int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* x, double* y) {
+  if (!x || !y) { set_error("qemb_op_sci_spmv: null argument"); return QEMB_ERR_ARG; }
+  DBuf hd, yd; SciSpace V; SciMatrix H;
+  QTRY(sci_op_integrals(n, h_host, V_dev, hd, nullptr));
+  QTRY(sci_upload(ndet, alpha, beta, x, V));
+  QTRY(sci_build(n, hd, V_dev, V.k(), V.N, -1, "qemb_op_sci_spmv", H));
+  QTRY(yd.alloc(ndet));
+  QTRY(dev_sci_spmv(ndet, H.rp(), H.ci(), H.val, V.c, yd));
+  return dev_d2h(y, yd, sizeof(double) * ndet);
+}
+int qemb_op_sci_rdm12(int n, int nsocc, const double* h_host, const double* V_dev, int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, int cumulant,
+                      double* dm1, double* dm2) {
+  if (!c || !dm1 || !dm2) { set_error("qemb_op_sci_rdm12: null argument"); return QEMB_ERR_ARG; }
+  const int64_t n2 = (int64_t)n * n;
+  DBuf hd, G; SciSpace V; SciMatrix H;
+  QTRY(sci_op_integrals(n, h_host, V_dev, hd, nullptr));
+  QTRY(sci_upload(ndet, alpha, beta, c, V));
+  QTRY(sci_build(n, hd, V_dev, V.k(), V.N, -1, "qemb_op_sci_rdm12", H));
+  QTRY(G.alloc(n2 * n2));
+  QTRY(sci_rdm12(n, V.k(), V.N, H.rp(), H.ci(), V.c, cumulant ? nsocc : -1, dm1, G));
+  return dev_d2h(dm2, G, sizeof(double) * n2 * n2);
 }
 int qemb_frag_rdm2(qemb_frag_t f, int kind, int with_dm1, double* out) {
   CHECK_FRAG(f);

@@ -411,6 +411,34 @@ int dev_fci_diag(int n, int64_t ns, const int32_t* strings, const double* h, con
 int dev_fci_precond(int64_t N, const double* r, const double* hdiag, double theta, double* out);
 int dev_fci_dm2(int n, int o_cum, const double* A, const double* dm1, double* out);
 
+// ---- selected CI (sci.cpp; kernels in sci_ops.hip, scalar restatement for the mock in sci_ops_hostcheck.cpp; the arithmetic of both in sci_core.h) ------------
+// A determinant is a key of two uint64 (alpha, beta occupation words, n <= 64), keys[2 k], keys[2 k + 1]; a space is sorted by (alpha, beta).
+//   screen:  for the nd determinants of a slab, every single and double excitation with |H_ai c_i| >= eps.  One workgroup of kSciScreenLanes lanes per determinant:
+//            the count pass writes counts[d * lanes + lane], dev_sci_scan turns them into offsets (exclusive, offsets[m] = the total), the emit pass writes the key and
+//            its spin-swapped partner at out[2 (2 offsets[..] + 2 k)]: dense, in one fixed order, no atomic cursor.  dbl_bound >= every |double-excitation element|.
+//   sort:    bitonic sort of m keys in a buffer of mpad = 2^k >= m keys (the tail is filled with the all-ones key, which no determinant has)
+//   flag_new: flags[k] = cand[k] is a determinant, differs from cand[k - 1] and is in neither sorted list A nor B;  compact: out[offsets[k]] = cand[k] where flagged
+//   merge:   two sorted lists without a common key -> one; cA (nullable) travels with A, the members of B get 0
+//   csr_count / csr_fill: row r of H over the space -- for every run of equal alpha (seg[s] .. seg[s + 1]) at most two excitations from alpha_r, the betas of the run
+//            with at most two excitations in all; columns ascending, both triangles, the diagonal included (also written to hdiag); fill with h = V = val = hdiag = null: the columns alone
+//   spmv:    y = H x, one wavefront per row, a fixed shuffle tree: the same bits on every call
+//   rdm:     dm1[p,q] += <q+ p>, dm2[p,q,r,s] += <p+ r+ s q> over the stored pairs with FP64 atomic adds (zeroed by the caller; reproducible to rounding only)
+//   dm2_finish: dm2 -= the mean-field part of molbe/solver.py:513-527 with o_cum occupied orbitals (the form of dev_fci_dm2)
+constexpr int kSciMaxOrb = 64;
+constexpr int kSciScreenLanes = 256;
+int dev_sci_screen_count(int n, const double* h, const double* V, int64_t nd, const uint64_t* keys, const double* c, double eps, double dbl_bound, int32_t* counts);
+int dev_sci_screen_emit(int n, const double* h, const double* V, int64_t nd, const uint64_t* keys, const double* c, double eps, double dbl_bound, const int64_t* offsets, uint64_t* out);
+int dev_sci_scan(int64_t m, const int32_t* in, int64_t* out);
+int dev_sci_sort(int64_t m, int64_t mpad, uint64_t* keys);
+int dev_sci_flag_new(int64_t m, const uint64_t* cand, int64_t nA, const uint64_t* A, int64_t nB, const uint64_t* B, int32_t* flags);
+int dev_sci_compact(int64_t m, const uint64_t* cand, const int32_t* flags, const int64_t* offsets, uint64_t* out);
+int dev_sci_merge(int64_t nA, const uint64_t* A, const double* cA, int64_t nB, const uint64_t* B, uint64_t* out, double* cout);
+int dev_sci_csr_count(int64_t N, const uint64_t* keys, int64_t nseg, const int64_t* seg, int32_t* counts);
+int dev_sci_csr_fill(int n, const double* h, const double* V, int64_t N, const uint64_t* keys, int64_t nseg, const int64_t* seg, const int64_t* rowptr, int32_t* col, double* val, double* hdiag);
+int dev_sci_spmv(int64_t N, const int64_t* rowptr, const int32_t* col, const double* val, const double* x, double* y);
+int dev_sci_rdm(int n, int64_t N, const uint64_t* keys, const int64_t* rowptr, const int32_t* col, const double* c, double* dm1, double* dm2);
+int dev_sci_dm2_finish(int n, int o_cum, const double* dm1, double* dm2);
+
 // ---- k-point density fitting (kdf.cpp; kernels in kdf_ops.hip, scalar restatement for the mock in kdf_ops_hostcheck.cpp) -------------------------
 // Three HBM passes around the two quarter transforms of KdfContext::transform; no atomics, every output element written once.
 // Row stride of the planar images of a pair block: whole 128-byte lines.

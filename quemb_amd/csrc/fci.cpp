@@ -78,7 +78,7 @@ int fci_apply(const FciTables& T, const double* k_dev, const double* V_dev, cons
   return dev_fci_sigma(T.n, T.ns, T.nlink, T.links_dev, k_dev, D, G, sigma);
 }
 
-namespace {
+namespace fci_detail {      // (declared in fci.h: the selected-CI iteration of sci.cpp shares them)
 // eigenvalues (ascending) and eigenvectors (columns of V) of a small symmetric matrix by cyclic Jacobi; A [m][m] is overwritten
 void small_eigh(int m, std::vector<double>& A, std::vector<double>& w, std::vector<double>& V) {
   V.assign((size_t)m * m, 0.0);
@@ -133,7 +133,8 @@ int combine(int64_t N, const std::vector<double>& coef, const std::vector<const 
     QTRY(dev_lincomb(N, std::min(8, m - j0), coef.data() + j0, xs.data() + j0, (j0 == 0 && !accumulate) ? 0.0 : 1.0, out));
   return 0;
 }
-}  // namespace
+}  // namespace fci_detail
+using namespace fci_detail;
 
 int fci_davidson(const FciTables& T, const double* h_host, const double* V_dev, const FciOptions& opt, double* c, FciResult* res) {
   const int n = T.n;

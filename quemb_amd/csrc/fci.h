@@ -43,6 +43,14 @@ struct FciResult { double e = 0.0, residual = 0.0; int n_iter = 0; bool converge
 // positive.  h_host: [n][n]; V_dev: [n^2][n^2] on the device.
 int fci_davidson(const FciTables& T, const double* h_host, const double* V_dev, const FciOptions& opt, double* c, FciResult* res);
 
+// the host side of the Davidson iteration, shared with sci.cpp: the small symmetric eigenproblem (cyclic Jacobi; A [m][m] is overwritten, w ascending, eigenvectors
+// in the columns of V), host[j] = <x, ys[j]> and out = sum_j coef[j] xs[j] (+ out) eight vectors per pass (scratch: >= 8 doubles on the device)
+namespace fci_detail {
+void small_eigh(int m, std::vector<double>& A, std::vector<double>& w, std::vector<double>& V);
+int dots(int64_t N, const double* x, const std::vector<const double*>& ys, double* scratch, double* host);
+int combine(int64_t N, const std::vector<double>& coef, const std::vector<const double*>& xs, bool accumulate, double* out);
+}  // namespace fci_detail
+
 // dm1[p,q] = sum_I c_I D[pq][I] (host, symmetrised) and, when dm2_dev != null, dm2[p,q,r,s] = <p+ r+ s q> (n^4 doubles, device); o_cum >= 0: minus the mean-field part
 int fci_rdm12(const FciTables& T, const double* c, int o_cum, double* dm1_host, double* dm2_dev);
 

@@ -131,7 +131,7 @@ int Fragment::export_eri_s4(double* s4_host) {
   return dev_d2h(s4_host, tmp, sizeof(double) * np * np);
 }
 int64_t Fragment::resident_bytes() const {
-  int64_t words = eri_s4_.n + df_factor_.n + C_.n + eps_.n + dm_.n + J_.n + K_.n + t_prev_.n + z_prev_.n;
+  int64_t words = eri_s4_.n + df_factor_.n + C_.n + eps_.n + dm_.n + J_.n + K_.n + t_prev_.n + z_prev_.n + sci_V_.keys.n + sci_V_.c.n;
   return 8 * words;
 }
 int Fragment::adopt_df_factor(DBuf&& B, int naux) {
@@ -919,12 +919,101 @@ int Fragment::solve_fci(int o, const double* h, const double* dm0, const Fragmen
   return finish_solve(nullptr, dm, e2, QEMB_RDM2_FCI, false, unconverged, mo_coeff, mo_energy, rdm1_emb, rdm1_mo);
 }
 
+// ---- solver == "SCI-hip": the fragment RHF, then the heat-bath selection of sci.cpp on the integrals of solve_fci; the tail is solve_fci's
+int Fragment::solve_sci(int o, const double* h, const double* dm0, const FragmentOptions& opt, const SciOptions& sopt, int eeval, FragmentResult* res,
+                        double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo) {
+  const int n = n_, v = n - o;
+  const int64_t n2 = (int64_t)n * n;
+  char eps_txt[32];
+  snprintf(eps_txt, sizeof eps_txt, "%.3g", sopt.eps_var);
+  if (n > kSciMaxOrb) { set_error("Fragment::solve_sci: n = " + std::to_string(n) + " embedding orbitals; the selected CI takes at most " + std::to_string(kSciMaxOrb) + " (one 64-bit word per spin)"); return QEMB_ERR_UNSUPPORTED; }
+  if (o <= 0 || o > n) { set_error("Fragment: need 0 < nsocc <= n"); return QEMB_ERR_ARG; }
+  if (!(sopt.eps_var > 0.0)) { set_error("Fragment::solve_sci: eps_var must be positive"); return QEMB_ERR_ARG; }
+  if (sopt.max_round < 1 || sopt.max_det < 1) { set_error("Fragment::solve_sci: need max_round >= 1 and max_det >= 1"); return QEMB_ERR_ARG; }
+  QTRY(check_energy_data(eeval));
+  int64_t room_left = -1;
+  {      // the guard: what max_det fixes against what is free (or the fragment's limit), before anything is allocated; the CSR arrays get what is left
+    size_t free_b = 0, total_b = 0;
+    QTRY(dev_mem_info(&free_b, &total_b));
+    double room = (double)free_b;
+    if (sci_mem_limit_ >= 0 && (double)sci_mem_limit_ < room) room = (double)sci_mem_limit_;
+    const double need = (double)sci_bytes(n, o, sopt.max_det, sopt.max_space);
+    if (v > 0 && need > room) {
+      set_error("Fragment::solve_sci: n = " + std::to_string(n) + ", eps_var = " + eps_txt + ", max_det = " + std::to_string(sopt.max_det) + " give a working set of " +
+                std::to_string((int64_t)need) + " bytes (" + std::to_string(need * 1e-9) + " GB) before the matrix, more than the " + std::to_string(room * 1e-9) + " GB of device memory it may take");
+      return QEMB_ERR_ALLOC;
+    }
+    room_left = (int64_t)(room - need);
+  }
+  QTRY(solve_begin_scf(o, h, dm0, opt, eeval, res));
+  sp_.X1.release();
+  const std::vector<double>& C = sp_.C;
+  bool unconverged = sp_.unconverged;
+  mean_field_result(res);
+  std::vector<double> dm((size_t)n2, 0.0), e2((size_t)nf_, 0.0);
+  if (v > 0) {
+    DBuf Vao, CC, Vmo;
+    QTRY(fci_mo_integrals(C, Vao, CC, Vmo));
+    std::vector<double> hmo((size_t)n2, 0.0), tmp((size_t)n2, 0.0);      // h in the fragment-MO basis: C^T h C
+    for (int p = 0; p < n; ++p) for (int nu = 0; nu < n; ++nu) { double s = 0; for (int mu = 0; mu < n; ++mu) s += C[(size_t)mu * n + p] * h[(size_t)mu * n + nu]; tmp[(size_t)p * n + nu] = s; }
+    for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int nu = 0; nu < n; ++nu) s += tmp[(size_t)p * n + nu] * C[(size_t)nu * n + q]; hmo[(size_t)p * n + q] = s; }
+    SciSpace V; SciMatrix H; SciResult sr;
+    QTRY(sci_solve(n, o, hmo.data(), Vmo, sopt, room_left, V, H, &sr));
+    res->n_iter = sr.n_apply; res->ccsd_converged = sr.converged && sr.diag_converged;
+    res->e_corr_mo = sr.e - res->e_scf;
+    if (!res->ccsd_converged) {
+      char b[200];
+      snprintf(b, sizeof b, "SCI (n = %d, eps_var = %s): %s (%lld determinants, energy %.10f, residual %.3g)", n, eps_txt,
+               sr.converged ? "a diagonalisation did not converge in max_cycle applications of H" : "the selection was still adding determinants after max_round rounds",
+               (long long)sr.ndet, sr.e, sr.residual);
+      set_error(b);
+      if (opt.strict) return QEMB_ERR_NOCONV;
+      unconverged = true;
+    }
+    DBuf G2;
+    if (eeval) QTRY(G2.alloc(n2 * n2));
+    {
+      const auto t0 = std::chrono::steady_clock::now();
+      QTRY(sci_rdm12(n, V.k(), V.N, H.rp(), H.ci(), V.c, o, dm.data(), eeval ? G2.p : nullptr));
+      sr.ms[SCI_T_RDM] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if (eeval && nf_ > 0) QTRY(fci_e2_sites(CC, G2, Vao, e2));
+    H = SciMatrix();      // the matrix goes: 12 bytes per stored element (GBs at 10^9) would stay with every fragment of a sweep; rdm2() forms the pattern again
+    const int rc = finish_solve(nullptr, dm, e2, QEMB_RDM2_SCI, false, unconverged, mo_coeff, mo_energy, rdm1_emb, rdm1_mo);
+    if (rc >= 0) { sci_V_ = std::move(V); sci_res_ = sr; }      // 24 bytes per determinant stay (run_scf dropped the last solve's through forget_solve)
+    return rc;
+  }
+  // a single determinant: the mean-field results, as the other solvers
+  for (int i = 0; i < n; ++i) dm[(size_t)i * n + i] = 2.0;
+  const int rc = finish_solve(nullptr, dm, e2, QEMB_RDM2_SCI, false, unconverged, mo_coeff, mo_energy, rdm1_emb, rdm1_mo);
+  if (rc >= 0) { sci_res_ = SciResult(); sci_res_.ndet = 1; sci_res_.nnz = 1; sci_res_.converged = true; sci_res_.e = res->e_scf; }
+  return rc;
+}
+int Fragment::sci_dets(uint64_t* alpha, uint64_t* beta, double* c) const {
+  if (last_kind_ != QEMB_RDM2_SCI) { set_error("Fragment::sci_dets: the last solve of this fragment was not an SCI solve"); return QEMB_ERR_ARG; }
+  if (sci_V_.N == 0) {      // the single determinant of nsocc == n
+    const uint64_t hf = last_o_ >= 64 ? ~(uint64_t)0 : (((uint64_t)1 << last_o_) - 1);
+    if (alpha) alpha[0] = hf;
+    if (beta) beta[0] = hf;
+    if (c) c[0] = 1.0;
+    return 0;
+  }
+  const int64_t N = sci_V_.N;
+  std::vector<uint64_t> k((size_t)(2 * N));
+  QTRY(dev_d2h(k.data(), sci_V_.keys, sizeof(uint64_t) * 2 * N));
+  for (int64_t i = 0; i < N; ++i) { if (alpha) alpha[i] = k[(size_t)(2 * i)]; if (beta) beta[i] = k[(size_t)(2 * i + 1)]; }
+  if (c) QTRY(dev_d2h(c, sci_V_.c, sizeof(double) * N));
+  return 0;
+}
+
 // ---- Frags.rdm2__ (molbe/solver.py:528): the n^4 tensor of the last solve, written once by one kernel (rdm2_ops.hip)
 // Device bytes of one call: the tensor, the 1-RDM, and for MP2 what forming t2 again takes -- ovov, t2, G and the larger of the two integral routes' work space
 // (factor: the unpacked factor, its half-rotated virtual columns and Lov, mp2.cpp; block: the two buffers of mo_transform and the ovov block it leaves).
 int64_t Fragment::rdm2_bytes(int kind, int o, int with_dm1) const {
   const int64_t n = n_, v = n - o, n2 = n * n, ov2 = (int64_t)o * v * o * v;
   int64_t words = n2 * n2 + (with_dm1 ? n2 : 0);
+  // the tensor and the 1-RDM (sci_rdm12) and the pattern of the matrix, formed again from the resident keys: row pointers, counts, run offsets and 4 bytes per stored element
+  if (kind == QEMB_RDM2_SCI) return 8 * (n2 * n2 + 2 * n2) + 20 * sci_V_.N + 4 * sci_res_.nnz;
   if (kind == QEMB_RDM2_FCI) {      // the tensor, A = D D^T, the 1-RDM and D itself (fci_rdm12)
     const int64_t ns = fci_string_count(n_, o);
     return 8 * (2 * n2 * n2 + n2 + (v > 0 ? n2 * ns * ns : 0));
@@ -936,9 +1025,9 @@ int64_t Fragment::rdm2_bytes(int kind, int o, int with_dm1) const {
   return 8 * words;
 }
 int Fragment::rdm2(int kind, int with_dm1, double* out, bool out_on_device) {
-  if (kind != QEMB_RDM2_CCSD && kind != QEMB_RDM2_MP2 && kind != QEMB_RDM2_FCI) { set_error("Fragment::rdm2: kind must be QEMB_RDM2_CCSD, QEMB_RDM2_MP2 or QEMB_RDM2_FCI"); return QEMB_ERR_ARG; }
+  if (kind != QEMB_RDM2_CCSD && kind != QEMB_RDM2_MP2 && kind != QEMB_RDM2_FCI && kind != QEMB_RDM2_SCI) { set_error("Fragment::rdm2: kind must be QEMB_RDM2_CCSD, QEMB_RDM2_MP2, QEMB_RDM2_FCI or QEMB_RDM2_SCI"); return QEMB_ERR_ARG; }
   if (last_kind_ < 0) { set_error("Fragment::rdm2: no solve has run on this fragment since its ERIs or orbitals were last set"); return QEMB_ERR_ARG; }
-  if (kind != last_kind_) { set_error(std::string("Fragment::rdm2: the last solve of this fragment was ") + (last_kind_ == QEMB_RDM2_MP2 ? "MP2" : last_kind_ == QEMB_RDM2_FCI ? "FCI" : "CCSD") + ", not the kind asked for"); return QEMB_ERR_ARG; }
+  if (kind != last_kind_) { set_error(std::string("Fragment::rdm2: the last solve of this fragment was ") + (last_kind_ == QEMB_RDM2_MP2 ? "MP2" : last_kind_ == QEMB_RDM2_FCI ? "FCI" : last_kind_ == QEMB_RDM2_SCI ? "SCI" : "CCSD") + ", not the kind asked for"); return QEMB_ERR_ARG; }
   if (last_relaxed_) { set_error("Fragment::rdm2: relaxed (Lambda) 2-RDMs are not implemented; solve without relax_density"); return QEMB_ERR_UNSUPPORTED; }
   const int n = n_, o = last_o_, v = n - o;
   const int64_t n2 = (int64_t)n * n;
@@ -953,7 +1042,7 @@ int Fragment::rdm2(int kind, int with_dm1, double* out, bool out_on_device) {
               std::to_string((double)(rdm2_bytes(kind, o, with_dm1) - 8 * n2 * n2) * 1e-9) + " GB of workspace, more than the " + std::to_string(room * 1e-9) + " GB of device memory it may take");
     return QEMB_ERR_ALLOC;
   }
-  if (kind == QEMB_RDM2_FCI) {      // make_rdm2 of the kept vector; with_dm1 = 0: minus the mean-field part (what rdm2__ holds with use_cumulant)
+  if (kind == QEMB_RDM2_FCI || kind == QEMB_RDM2_SCI) {      // make_rdm2 of the kept vector; with_dm1 = 0: minus the mean-field part (what rdm2__ holds with use_cumulant)
     DBuf R;
     double* target = out;
     if (!out_on_device) { QTRY(R.alloc(n2 * n2)); target = R; }
@@ -961,6 +1050,12 @@ int Fragment::rdm2(int kind, int with_dm1, double* out, bool out_on_device) {
       std::vector<double> d2((size_t)(n2 * n2), 0.0);
       if (with_dm1) for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { d2[(size_t)((p * n + p) * n2 + q * n + q)] += 4.0; d2[(size_t)((p * n + q) * n2 + q * n + p)] -= 2.0; }
       QTRY(dev_h2d(target, d2.data(), sizeof(double) * n2 * n2));
+    } else if (kind == QEMB_RDM2_SCI) {
+      if (sci_V_.N == 0) { set_error("Fragment::rdm2: the determinants of the last SCI solve were not kept"); return QEMB_ERR_ARG; }
+      std::vector<double> d1((size_t)n2);
+      SciMatrix P;
+      QTRY(sci_build(n, nullptr, nullptr, sci_V_.k(), sci_V_.N, -1, "Fragment::rdm2", P));
+      QTRY(sci_rdm12(n, sci_V_.k(), sci_V_.N, P.rp(), P.ci(), sci_V_.c, with_dm1 ? -1 : o, d1.data(), target));
     } else {
       if (!fci_c_.p) { set_error("Fragment::rdm2: the vector of the last FCI solve was not kept"); return QEMB_ERR_ARG; }
       const FciTables* T = nullptr;

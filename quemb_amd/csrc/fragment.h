@@ -9,6 +9,7 @@
 #include "cc_lambda.h"
 #include "scf.h"
 #include "fci.h"
+#include "sci.h"
 
 namespace qemb {
 
@@ -100,6 +101,15 @@ class Fragment {
   int solve_fci(int o, const double* h, const double* dm0, const FragmentOptions& opt, const FciOptions& fopt, int eeval, FragmentResult* res,
                 double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* civec);
   void set_fci_mem_limit(int64_t bytes) { fci_mem_limit_ = bytes; }
+  // solver == "SCI-hip": the selected-CI branch of be_func (molbe/solver.py:412-462) as the heat-bath selection of sci.h on the integrals solve_fci forms, for
+  // n <= 64; everything after the vector is the tail of solve_fci (make_rdm1, cumulant of the 2-RDM on the device, fci_e2_sites, finish_solve).  The guard compares
+  // sci_bytes with the free device memory (or set_sci_mem_limit) before anything is allocated; the determinants and the vector stay on the device for a later
+  // rdm2(QEMB_RDM2_SCI) and sci_dets(); the matrix does not.
+  int solve_sci(int o, const double* h, const double* dm0, const FragmentOptions& opt, const SciOptions& sopt, int eeval, FragmentResult* res,
+                double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo);
+  void set_sci_mem_limit(int64_t bytes) { sci_mem_limit_ = bytes; }
+  const SciResult& sci_result() const { return sci_res_; }
+  int sci_dets(uint64_t* alpha, uint64_t* beta, double* c) const;
   double fci_residual() const { return fci_residual_; }
   // Frags.rdm2__ (molbe/solver.py:528) of the last solve in the fragment-MO basis, out: n^4 (host).  kind QEMB_RDM2_CCSD: make_rdm2_urlx from the kept t1 / t2;
   // QEMB_RDM2_MP2: mp2.make_rdm2, t2 formed again from the resident orbitals (an MP2 solve keeps no amplitudes).  One kernel writes the tensor (rdm2_ops.hip).
@@ -184,7 +194,11 @@ class Fragment {
   int64_t fci_mem_limit_ = -1;
   int fci_mo_integrals(const std::vector<double>& C, DBuf& Vao, DBuf& CC, DBuf& Vmo);
   int fci_e2_sites(const double* CC, const double* G2, const double* Vao, std::vector<double>& e2);      // the cumulant contracted with the integrals, per fragment site
-  void forget_solve() { last_kind_ = -1; }
+  // after an SCI solve: the sorted determinants with the vector (device, 24 bytes per determinant); rdm2() forms the pattern of the matrix over them again
+  SciSpace sci_V_;
+  SciResult sci_res_;
+  int64_t sci_mem_limit_ = -1;
+  void forget_solve() { last_kind_ = -1; sci_V_ = SciSpace(); sci_res_ = SciResult(); }
 };
 
 // lock-step tapes kept from an earlier solve / recorded anew since the last reset (all fragments of the process)

@@ -1,0 +1,295 @@
+// sci.cpp -- the selected CI on the device (sci.h): screen in slabs, sort / unique / difference / merge, the CSR matrix, Davidson on it, the RDMs, the round loop.
+#include "sci.h"
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+
+namespace qemb {
+using namespace fci_detail;
+
+namespace {
+int64_t pow2_at_least(int64_t m) { int64_t p = 1; while (p < m) p <<= 1; return p; }
+int64_t pairs(int64_t m) { return m * (m - 1) / 2; }
+int64_t words_for_int32(int64_t count) { return (count + 1) / 2; }      // doubles that hold `count` int32
+struct StageClock {      // host wall time of a stage, the device drained at both ends
+  double* slot; std::chrono::steady_clock::time_point t0;
+  explicit StageClock(double* s) : slot(s) { (void)dev_sync(); t0 = std::chrono::steady_clock::now(); }
+  ~StageClock() { (void)dev_sync(); *slot += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
+}  // namespace
+
+int64_t sci_excitations(int n, int nsocc) {
+  const int64_t o = nsocc, v = n - nsocc, s = o * v;
+  return 2 * s + 2 * pairs(o) * pairs(v) + s * s;
+}
+int64_t sci_candidate_capacity(int n, int nsocc) { return pow2_at_least(std::max<int64_t>(2 * sci_excitations(n, nsocc), (int64_t)1 << 20)); }
+int64_t sci_bytes(int n, int nsocc, int64_t max_det, int max_space) {
+  const int64_t n2 = (int64_t)n * n, cap = sci_candidate_capacity(n, nsocc);
+  const int64_t spaces = 3 * (16 + 8) * max_det;                                   // V, the joined list (two copies while it grows), the merged space; keys and vectors
+  const int64_t cand = cap * (16 + 4 + 8) + kSciSlab * kSciScreenLanes * (4 + 8);    // candidate keys, flags, offsets; lane counts and offsets of a slab
+  const int64_t davidson = 8 * (2 * (int64_t)max_space + 4) * max_det;             // basis, images, residual, correction, diagonal, the kept vector
+  const int64_t rows = (8 + 4 + 8) * max_det;                                      // row pointers, row counts, run offsets
+  return spaces + cand + davidson + rows + 8 * (4 * n2 * n2 + 2 * n2);             // Vao, CC, Vmo and the 2-RDM; h and the 1-RDM
+}
+
+int sci_screen(int n, int nsocc, const double* h_dev, const double* V_dev, double dbl_bound, const SciSpace& V, double eps, int64_t slab, int64_t cap, int64_t max_new,
+               DBuf& joined, int64_t* njoined, double* ms) {
+  double unclocked[SCI_T_COUNT] = {0, 0, 0, 0, 0};
+  if (!ms) ms = unclocked;
+  if (slab <= 0) slab = kSciSlab;
+  if (cap <= 0) cap = sci_candidate_capacity(n, nsocc);
+  if ((cap & (cap - 1)) || cap < 2 * sci_excitations(n, nsocc)) { set_error("sci_screen: the candidate buffer must be a power of two that holds the excitations of one determinant twice"); return QEMB_ERR_ARG; }
+  const int64_t N = V.N;
+  const int64_t slab_max = std::min(slab, N);
+  slab = slab_max;
+  DBuf cand, counts, offs, flags, foffs, Q, P2;
+  QTRY(cand.alloc(2 * cap)); QTRY(counts.alloc(words_for_int32(slab * kSciScreenLanes))); QTRY(offs.alloc(slab * kSciScreenLanes + 1));
+  QTRY(flags.alloc(words_for_int32(cap))); QTRY(foffs.alloc(cap + 1));
+  joined.release();
+  int64_t nP = 0, pos = 0;
+  while (pos < N && nP <= max_new) {
+    const int64_t nd = std::min(slab, N - pos), lanes = nd * kSciScreenLanes;
+    int64_t total = 0;
+    {
+      StageClock clk(&ms[SCI_T_SCREEN]);
+      QTRY(dev_sci_screen_count(n, h_dev, V_dev, nd, V.k() + 2 * pos, V.c.p + pos, eps, dbl_bound, (int32_t*)counts.p));
+      QTRY(dev_sci_scan(lanes, (const int32_t*)counts.p, (int64_t*)offs.p));
+      QTRY(dev_d2h(&total, offs.p + lanes, sizeof(int64_t)));
+    }
+    // the next slab from this one's yield: as many determinants as fill 3/4 of the buffer at the same rate (the vector is not sorted by magnitude, so the
+    // rate drifts: a slab that overflows all the same is counted again at the size its own count gives; one determinant always fits)
+    const int64_t fit = total > 0 ? std::max<int64_t>(1, (int64_t)(0.75 * (double)cap * (double)nd / (2.0 * (double)total))) : slab_max;
+    if (2 * total > cap) {
+      if (nd == 1) { set_error("sci_screen: one determinant emitted more keys than the candidate buffer holds"); return QEMB_ERR_ARG; }
+      slab = std::min(fit, nd - 1);
+      continue;
+    }
+    slab = std::min(slab_max, fit);
+    if (total > 0) {
+      const int64_t m = 2 * total;
+      int64_t K = 0;
+      { StageClock clk(&ms[SCI_T_SCREEN]); QTRY(dev_sci_screen_emit(n, h_dev, V_dev, nd, V.k() + 2 * pos, V.c.p + pos, eps, dbl_bound, (const int64_t*)offs.p, (uint64_t*)cand.p)); }
+      StageClock clk(&ms[SCI_T_MERGE]);      // sort, unique, difference and the growth of the joined list
+      QTRY(dev_sci_sort(m, pow2_at_least(m), (uint64_t*)cand.p));
+      QTRY(dev_sci_flag_new(m, (const uint64_t*)cand.p, N, V.k(), nP, (const uint64_t*)joined.p, (int32_t*)flags.p));
+      QTRY(dev_sci_scan(m, (const int32_t*)flags.p, (int64_t*)foffs.p));
+      QTRY(dev_d2h(&K, foffs.p + m, sizeof(int64_t)));
+      if (K > 0) {
+        QTRY(Q.alloc(2 * K));
+        QTRY(dev_sci_compact(m, (const uint64_t*)cand.p, (const int32_t*)flags.p, (const int64_t*)foffs.p, (uint64_t*)Q.p));
+        if (nP == 0) joined = std::move(Q);
+        else {
+          QTRY(P2.alloc(2 * (nP + K)));
+          QTRY(dev_sci_merge(nP, (const uint64_t*)joined.p, nullptr, K, (const uint64_t*)Q.p, (uint64_t*)P2.p, nullptr));
+          QTRY(dev_sync());      // (the lists that go back to the pool below are still being read)
+          joined = std::move(P2);
+        }
+        nP += K;
+      }
+    }
+    pos += nd;
+  }
+  *njoined = nP;
+  return dev_sync();
+}
+
+int sci_merge(const SciSpace& V, const uint64_t* joined, int64_t njoined, SciSpace& out) {
+  const int64_t N = V.N + njoined;
+  QTRY(out.keys.alloc(2 * N)); QTRY(out.c.alloc(N));
+  QTRY(dev_sci_merge(V.N, V.k(), V.c.p, njoined, joined, (uint64_t*)out.keys.p, out.c.p));
+  out.N = N;
+  return 0;
+}
+
+int sci_build(int n, const double* h_dev, const double* V_dev, const uint64_t* keys, int64_t N, int64_t max_bytes, const std::string& who, SciMatrix& H) {
+  // runs of equal alpha, on the host: one pass over the downloaded keys
+  std::vector<uint64_t> kh((size_t)(2 * N));
+  QTRY(dev_d2h(kh.data(), keys, sizeof(uint64_t) * 2 * N));
+  std::vector<int64_t> seg;
+  for (int64_t k = 0; k < N; ++k) if (k == 0 || kh[(size_t)(2 * k)] != kh[(size_t)(2 * k - 2)]) seg.push_back(k);
+  const int64_t nseg = (int64_t)seg.size();
+  seg.push_back(N);
+  DBuf segd, counts;
+  QTRY(segd.alloc(nseg + 1)); QTRY(counts.alloc(words_for_int32(N)));
+  QTRY(dev_h2d(segd, seg.data(), sizeof(int64_t) * (nseg + 1)));
+  const bool values = h_dev != nullptr;      // (without integrals: row pointers and columns alone, what the RDM pass reads)
+  QTRY(H.rowptr.alloc(N + 1));
+  if (values) QTRY(H.hdiag.alloc(N));
+  QTRY(dev_sci_csr_count(N, keys, nseg, (const int64_t*)segd.p, (int32_t*)counts.p));
+  QTRY(dev_sci_scan(N, (const int32_t*)counts.p, (int64_t*)H.rowptr.p));
+  int64_t nnz = 0;
+  QTRY(dev_d2h(&nnz, H.rowptr.p + N, sizeof(int64_t)));
+  H.N = N; H.nnz = nnz;
+  if (max_bytes >= 0 && (values ? 12 : 4) * nnz > max_bytes) {
+    set_error(who + ": the matrix over " + std::to_string(N) + " determinants stores " + std::to_string(nnz) + " elements, " + std::to_string(12e-9 * (double)nnz) +
+              " GB, more than the " + std::to_string(1e-9 * (double)max_bytes) + " GB of device memory left for it");
+    return QEMB_ERR_ALLOC;
+  }
+  QTRY(H.col.alloc(words_for_int32(nnz)));
+  if (values) QTRY(H.val.alloc(nnz));
+  QTRY(dev_sci_csr_fill(n, h_dev, V_dev, N, keys, nseg, (const int64_t*)segd.p, H.rp(), (int32_t*)H.col.p, values ? H.val.p : nullptr, values ? H.hdiag.p : nullptr));
+  return dev_sync();      // (the run offsets and counts go back to the pool on return)
+}
+
+// fci_davidson over the CSR product: the same small eigenproblem, orthogonalisation, collapse and sign rule; the start vector is handed in
+int sci_davidson(const SciMatrix& H, const SciOptions& opt, double* c, FciResult* res) {
+  const int64_t N = H.N;
+  if (opt.max_space < 2 || opt.max_cycle < 1 || !(opt.conv_tol > 0.0) || !(opt.lindep >= 0.0)) {
+    set_error("sci: need max_space >= 2, max_cycle >= 1, conv_tol > 0 and lindep >= 0"); return QEMB_ERR_ARG;
+  }
+  const int ms = (int)std::min<int64_t>(opt.max_space, N);
+  *res = FciResult();
+  auto apply = [&](const double* x, double* y) { return dev_sci_spmv(N, H.rp(), H.ci(), H.val, x, y); };
+  DBuf r, t, u, scal;
+  QTRY(r.alloc(N)); QTRY(t.alloc(N)); QTRY(u.alloc(N)); QTRY(scal.alloc(8));
+  std::vector<DBuf> B((size_t)ms), S((size_t)ms);
+  for (int j = 0; j < ms; ++j) { QTRY(B[j].alloc(N)); QTRY(S[j].alloc(N)); }
+  auto ptrs = [&](const std::vector<DBuf>& X, int cnt) { std::vector<const double*> p((size_t)cnt); for (int j = 0; j < cnt; ++j) p[j] = X[j].p; return p; };
+  std::vector<double> Hs((size_t)ms * ms, 0.0), row((size_t)ms), y, w, A;
+  double cc = 0.0;
+  { std::vector<const double*> self(1, c); QTRY(dots(N, c, self, scal, &cc)); }
+  if (!(cc > 0.0)) { set_error("sci_davidson: the start vector is zero"); return QEMB_ERR_ARG; }
+  QTRY(axpby(N, 1.0 / std::sqrt(cc), c, 0.0, B[0]));
+  QTRY(apply(B[0], S[0]));
+  res->n_iter = 1;
+  int m = 1;
+  QTRY(dots(N, S[0], ptrs(B, 1), scal, row.data()));
+  Hs[0] = row[0];
+  for (;;) {
+    A.assign((size_t)m * m, 0.0);
+    for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) A[(size_t)i * m + j] = Hs[(size_t)i * ms + j];
+    std::vector<double> Vv;
+    small_eigh(m, A, w, Vv);
+    y.assign((size_t)m, 0.0);
+    for (int j = 0; j < m; ++j) y[j] = Vv[(size_t)j * m];
+    const double theta = w[0];
+    std::vector<double> cy(y), cb((size_t)m);
+    for (int j = 0; j < m; ++j) cb[j] = -theta * y[j];
+    QTRY(combine(N, cy, ptrs(S, m), false, r));
+    QTRY(combine(N, cb, ptrs(B, m), true, r));
+    double rr = 0.0;
+    { std::vector<const double*> self(1, r.p); QTRY(dots(N, r, self, scal, &rr)); }
+    res->e = theta; res->residual = std::sqrt(rr > 0.0 ? rr : 0.0);
+    res->converged = res->residual <= opt.conv_tol;
+    bool stop = res->converged || res->n_iter >= opt.max_cycle;
+    if (!stop) {
+      if (m == ms) {      // collapse to the current Ritz vector (and its image)
+        QTRY(combine(N, y, ptrs(B, m), false, t));
+        QTRY(combine(N, y, ptrs(S, m), false, u));
+        QTRY(dcopy(N, t, B[0])); QTRY(dcopy(N, u, S[0]));
+        m = 1; Hs[0] = theta; y.assign(1, 1.0);
+      }
+      QTRY(dev_fci_precond(N, r, H.hdiag, theta, t));
+      for (int pass = 0; pass < 2; ++pass) {
+        QTRY(dots(N, t, ptrs(B, m), scal, row.data()));
+        std::vector<double> neg((size_t)m);
+        for (int j = 0; j < m; ++j) neg[j] = -row[j];
+        QTRY(combine(N, neg, ptrs(B, m), true, t));
+      }
+      double tt = 0.0;
+      { std::vector<const double*> self(1, t.p); QTRY(dots(N, t, self, scal, &tt)); }
+      const double tn = std::sqrt(tt > 0.0 ? tt : 0.0);
+      if (!(tn > opt.lindep) || m == ms) stop = true;      // nothing left to add (m == ms: the space itself has one dimension)
+      else {
+        QTRY(axpby(N, 1.0 / tn, t, 0.0, B[m]));
+        QTRY(apply(B[m], S[m]));
+        res->n_iter += 1;
+        QTRY(dots(N, S[m], ptrs(B, m + 1), scal, row.data()));
+        for (int j = 0; j <= m; ++j) Hs[(size_t)m * ms + j] = Hs[(size_t)j * ms + m] = row[j];
+        ++m;
+        continue;
+      }
+    }
+    QTRY(combine(N, y, ptrs(B, m), false, c));
+    std::vector<double> ch((size_t)N);
+    QTRY(dev_d2h(ch.data(), c, sizeof(double) * N));
+    double nrm = 0.0; int64_t big = 0;
+    for (int64_t I = 0; I < N; ++I) { nrm += ch[(size_t)I] * ch[(size_t)I]; if (std::fabs(ch[(size_t)I]) > std::fabs(ch[(size_t)big])) big = I; }
+    const double scale = (ch[(size_t)big] < 0.0 ? -1.0 : 1.0) / std::sqrt(nrm);
+    if (scale != 1.0) QTRY(axpby(N, scale, c, 0.0, c));
+    return dev_sync();
+  }
+}
+
+int sci_rdm12(int n, const uint64_t* keys, int64_t N, const int64_t* rowptr, const int32_t* col, const double* c, int o_cum, double* dm1_host, double* dm2_dev) {
+  const int64_t n2 = (int64_t)n * n;
+  DBuf d1, tmp;
+  QTRY(d1.alloc(n2));
+  if (!dm2_dev) { QTRY(tmp.alloc(n2 * n2)); dm2_dev = tmp; }
+  QTRY(dev_fill(d1, n2, 0.0)); QTRY(dev_fill(dm2_dev, n2 * n2, 0.0));
+  QTRY(dev_sci_rdm(n, N, keys, rowptr, col, c, d1, dm2_dev));
+  QTRY(dev_d2h(dm1_host, d1, sizeof(double) * n2));
+  for (int p = 0; p < n; ++p) for (int q = 0; q < p; ++q) { const double s = 0.5 * (dm1_host[p * n + q] + dm1_host[q * n + p]); dm1_host[p * n + q] = dm1_host[q * n + p] = s; }
+  if (o_cum >= 0) {
+    QTRY(dev_h2d(d1, dm1_host, sizeof(double) * n2));
+    QTRY(dev_sci_dm2_finish(n, o_cum, d1, dm2_dev));
+  }
+  return dev_sync();
+}
+
+int sci_solve(int n, int nsocc, const double* h_host, const double* V_dev, const SciOptions& opt, int64_t room, SciSpace& V, SciMatrix& H, SciResult* res) {
+  const int64_t n2 = (int64_t)n * n;
+  *res = SciResult();
+  if (n <= 0 || n > kSciMaxOrb || nsocc <= 0 || nsocc >= n) { set_error("sci_solve: need 0 < nsocc < n <= " + std::to_string(kSciMaxOrb)); return QEMB_ERR_ARG; }
+  if (!(opt.eps_var > 0.0) || opt.max_round < 1 || opt.max_det < 1) { set_error("sci: need eps_var > 0, max_round >= 1 and max_det >= 1"); return QEMB_ERR_ARG; }
+  char head[96];
+  snprintf(head, sizeof head, "SCI (n = %d, eps_var = %.3g)", n, opt.eps_var);
+  const std::string who = head;
+  // ---- h on the device; the bound on every double-excitation element: |(ai|bj) - (aj|bi)| <= 2 max |V|
+  DBuf hd;
+  QTRY(hd.alloc(n2));
+  QTRY(dev_h2d(hd, h_host, sizeof(double) * n2));
+  double dbl_bound = 0.0;
+  {
+    std::vector<double> Vh((size_t)(n2 * n2));
+    QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
+    for (double x : Vh) dbl_bound = std::max(dbl_bound, std::fabs(x));
+    dbl_bound *= 2.0;
+  }
+  // ---- V0 = {HF}
+  {
+    const uint64_t hf = nsocc == 64 ? ~(uint64_t)0 : (((uint64_t)1 << nsocc) - 1);
+    const uint64_t key[2] = {hf, hf};
+    const double one = 1.0;
+    QTRY(V.keys.alloc(2)); QTRY(V.c.alloc(1));
+    QTRY(dev_h2d(V.keys, key, sizeof key)); QTRY(dev_h2d(V.c, &one, sizeof one));
+    V.N = 1;
+  }
+  auto state = [&](int round) {
+    char b[160];
+    snprintf(b, sizeof b, " in round %d: %lld determinants, energy so far %.10f", round, (long long)V.N, res->e);
+    return std::string(b);
+  };
+  { StageClock clk(&res->ms[SCI_T_BUILD]); QTRY(sci_build(n, hd, V_dev, V.k(), V.N, room, who, H)); }
+  QTRY(dev_d2h(&res->e, H.hdiag, sizeof(double)));
+  res->ndet = 1; res->nnz = H.nnz;
+  for (int round = 1; round <= opt.max_round; ++round) {
+    DBuf joined;
+    int64_t njoined = 0;
+    QTRY(sci_screen(n, nsocc, hd, V_dev, dbl_bound, V, opt.eps_var, 0, 0, opt.max_det - V.N, joined, &njoined, res->ms));
+    if (njoined == 0) { res->converged = true; break; }
+    if (V.N + njoined > opt.max_det) {
+      set_error(who + state(round) + " and at least " + std::to_string(njoined) + " more to join, beyond max_det = " + std::to_string(opt.max_det));
+      return QEMB_ERR_ALLOC;
+    }
+    SciSpace W;
+    { StageClock clk(&res->ms[SCI_T_MERGE]); QTRY(sci_merge(V, (const uint64_t*)joined.p, njoined, W)); QTRY(dev_sync()); }
+    V = std::move(W);
+    joined.release();
+    H = SciMatrix();
+    {
+      StageClock clk(&res->ms[SCI_T_BUILD]);
+      const int rc = sci_build(n, hd, V_dev, V.k(), V.N, room, who + state(round), H);
+      if (rc) return rc;
+    }
+    FciResult fr;
+    { StageClock clk(&res->ms[SCI_T_DAVIDSON]); QTRY(sci_davidson(H, opt, V.c, &fr)); }
+    res->e = fr.e; res->residual = fr.residual; res->n_apply += fr.n_iter; res->rounds = round;
+    res->ndet = V.N; res->nnz = H.nnz;
+    if (!fr.converged) res->diag_converged = false;
+  }
+  return 0;
+}
+
+}  // namespace qemb

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FciOpts, SolverOpts, c_vp, check
+from ._lib import FciOpts, SciOpts, SolverOpts, c_vp, check
 
 
 def _p(a):
@@ -38,6 +38,18 @@ def default_fci_opts(lib=None, **kw) -> FciOpts:
     for k, v in kw.items():
         if not hasattr(o, k):
             raise TypeError(f"unknown FCI option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def default_sci_opts(lib=None, **kw) -> SciOpts:
+    """qemb_sci_opts with the library's defaults (eps_var 1e-3, conv_tol 1e-9, max_cycle 100, max_space 12, max_round 30, max_det 2^20), single fields changed by keyword"""
+    lib = lib or _lib.init()
+    o = SciOpts()
+    lib.qemb_default_sci_opts(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError(f"unknown SCI option {k!r}")
         setattr(o, k, v)
     return o
 
@@ -156,11 +168,40 @@ class DeviceFragment:
         out.update(e_fci=c.e[0], e_corr_mo=c.e[0] - c.e_scf[0], residual=resid.value)      # (this entry reports the eigenvalue where the others report e_corr_mo)
         return out
 
-    def solve_as(self, solver, nsocc, h, dm0=None, opts=None, eeval=True, want_amplitudes=False, fci_opts=None):
-        """the solve of be_func's solver literal (one of SOLVERS): `solve`, `solve_mp2` or `solve_fci`.  want_amplitudes asks for t2 (the CI vector of "FCI-hip");
-        fci_opts is read by "FCI-hip" alone"""
+    def solve_sci(self, nsocc, h, dm0=None, opts: SolverOpts | None = None, sci_opts: SciOpts | None = None, eeval=True, want_dets=False):
+        """solver == "SCI-hip" of be_func (qemb_frag_solve_sci): fragment RHF -> heat-bath selected CI on the device -> 1-RDM -> fragment energies from the cumulant of
+        the 2-RDM.  The dict `solve` returns with t1 = t2 = None, plus e_sci (the eigenvalue; e_corr_mo = e_sci - e_scf), ndet, rounds, nnz (stored elements of H),
+        residual (||H c - E c||_2 of the last diagonalisation), n_iter (applications of H over all rounds) and, with want_dets, dets = (alpha, beta, c): the final
+        space as uint64 occupation words sorted by (alpha, beta) and its vector.  sci_opts None: the defaults of `default_sci_opts`."""
+        c = _SolveCall([self], [nsocc], [h], [dm0], opts, eeval, batch=False)
+        c.call("qemb_frag_solve_sci", (), after_opts=(None if sci_opts is None else C.byref(sci_opts),))
+        ndet, rounds, nnz, resid = C.c_int64(), C.c_int(), C.c_int64(), C.c_double()
+        check(self.lib.qemb_frag_sci_stats(self.h, C.byref(ndet), C.byref(rounds), C.byref(nnz), C.byref(resid)), "qemb_frag_sci_stats", self.lib)
+        out = c.results()[0]
+        out.update(e_sci=c.e[0], e_corr_mo=c.e[0] - c.e_scf[0], ndet=int(ndet.value), rounds=int(rounds.value), nnz=int(nnz.value), residual=resid.value)
+        if want_dets:
+            a, b, v = np.empty(out["ndet"], dtype=np.uint64), np.empty(out["ndet"], dtype=np.uint64), np.empty(out["ndet"])
+            check(self.lib.qemb_frag_sci_dets(self.h, a.ctypes.data, b.ctypes.data, v.ctypes.data), "qemb_frag_sci_dets", self.lib)
+            out["dets"] = (a, b, v)
+        return out
+
+    def sci_stage_ms(self):
+        """host wall time (ms) of the stages of the last `solve_sci`: dict(screen, merge, build, davidson, rdm)"""
+        ms = (C.c_double * 5)()
+        check(self.lib.qemb_frag_sci_stage_ms(self.h, ms), "qemb_frag_sci_stage_ms", self.lib)
+        return dict(zip(("screen", "merge", "build", "davidson", "rdm"), (float(x) for x in ms)))
+
+    def set_sci_mem_limit(self, nbytes):
+        """device bytes `solve_sci` of this fragment may take (qemb_frag_sci_mem_limit); negative: whatever is free"""
+        check(self.lib.qemb_frag_sci_mem_limit(self.h, int(nbytes)), "qemb_frag_sci_mem_limit", self.lib)
+
+    def solve_as(self, solver, nsocc, h, dm0=None, opts=None, eeval=True, want_amplitudes=False, fci_opts=None, sci_opts=None):
+        """the solve of be_func's solver literal (one of SOLVERS): `solve`, `solve_mp2`, `solve_fci` or `solve_sci`.  want_amplitudes asks for t2 (the CI vector of
+        "FCI-hip", the determinants and vector of "SCI-hip"); fci_opts is read by "FCI-hip" alone, sci_opts by "SCI-hip" alone"""
         if solver not in SOLVERS:
             raise ValueError("Solver not implemented")
+        if solver == "SCI-hip":
+            return self.solve_sci(nsocc, h, dm0, opts=opts, sci_opts=sci_opts, eeval=eeval, want_dets=want_amplitudes)
         if solver == "FCI-hip":
             return self.solve_fci(nsocc, h, dm0, opts=opts, fci_opts=fci_opts, eeval=eeval, want_civec=want_amplitudes)
         return (self.solve_mp2 if solver == "MP2" else self.solve)(nsocc, h, dm0, opts=opts, eeval=eeval, want_t2=want_amplitudes)
@@ -174,6 +215,7 @@ class DeviceFragment:
         kind="CCSD": make_rdm2_urlx(t1, t2, with_dm1) (shared/external/ccsd_rdm.py:23-55) from the amplitudes `solve` left on the device;
         kind="MP2": PySCF's mp2.make_rdm2 (with_dm1=False: its dovov part) after `solve_mp2`.  One kernel writes the n^4 tensor on the device.
         kind="FCI-hip": make_rdm2 of the vector `solve_fci` left on the device (with_dm1=False: minus the mean-field part of molbe/solver.py:513-527).
+        kind="SCI-hip": the same of the selected vector `solve_sci` left on the device.
         Relaxed (Lambda) 2-RDMs are not implemented: after a solve with relax_density this raises NotImplementedError."""
         if kind not in RDM2_KINDS:
             raise ValueError("Solver not implemented")
@@ -247,8 +289,8 @@ class DeviceFragment:
             pass
 
 
-RDM2_KINDS = {"CCSD": 0, "MP2": 1, "FCI-hip": 2}      # QEMB_RDM2_CCSD, QEMB_RDM2_MP2, QEMB_RDM2_FCI (include/qemb_hip.h)
-SOLVERS = ("CCSD", "MP2", "FCI-hip")                   # the solver literals of be_func; everything else (the bare "FCI" included) is refused
+RDM2_KINDS = {"CCSD": 0, "MP2": 1, "FCI-hip": 2, "SCI-hip": 3}      # QEMB_RDM2_CCSD, _MP2, _FCI, _SCI (include/qemb_hip.h)
+SOLVERS = ("CCSD", "MP2", "FCI-hip", "SCI-hip")                      # the solver literals of be_func; everything else (the bare "FCI" and "SCI" included) is refused
 
 
 def rdm2_from_amplitudes(t1, t2, dm1=None, kind="CCSD", lib=None):
@@ -316,6 +358,97 @@ def fci_rdm12(c, n, nsocc, cumulant=False, lib=None):
     finally:
         for b in bufs:
             b.free()
+
+
+def _sci_space(alpha, beta):
+    a, b = np.ascontiguousarray(alpha, dtype=np.uint64), np.ascontiguousarray(beta, dtype=np.uint64)
+    if a.ndim != 1 or a.shape != b.shape or a.size == 0:
+        raise ValueError("a determinant space is two equally long 1-D arrays of occupation words")
+    return a, b
+
+
+def _sci_integrals(h, V, lib):
+    from ._lib import DeviceBuffer
+    h = np.ascontiguousarray(h, dtype=np.float64)
+    n = h.shape[0]
+    return h, n, DeviceBuffer.from_numpy(np.ascontiguousarray(V, dtype=np.float64).reshape(n * n, n * n), lib=lib)
+
+
+def sci_screen(h, V, nsocc, alpha, beta, c, eps, slab=0, cap=0, lib=None):
+    """the determinants outside the sorted space (alpha, beta) that pass |H_ai c_i| >= eps for some member, spin partners included (qemb_op_sci_screen): (alpha, beta),
+    sorted.  slab / cap: determinants per pass and keys of the candidate buffer (0: the library's)"""
+    lib = lib or _lib.init()
+    a, b = _sci_space(alpha, beta)
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    h, n, Vd = _sci_integrals(h, V, lib)
+    try:
+        nj = C.c_int64()
+        args = (n, int(nsocc), h.ctypes.data, Vd.ptr, a.size, a.ctypes.data, b.ctypes.data, c.ctypes.data, float(eps), int(slab), int(cap))
+        check(lib.qemb_op_sci_screen(*args, 0, C.byref(nj), None, None), "qemb_op_sci_screen", lib)
+        oa, ob = np.empty(nj.value, dtype=np.uint64), np.empty(nj.value, dtype=np.uint64)
+        if nj.value:
+            check(lib.qemb_op_sci_screen(*args, nj.value, C.byref(nj), oa.ctypes.data, ob.ctypes.data), "qemb_op_sci_screen", lib)
+        return oa, ob
+    finally:
+        Vd.free()
+
+
+def sci_merge(alpha, beta, c, jalpha, jbeta, lib=None):
+    """the sorted space merged with sorted keys outside it, the vector padded with zeros (qemb_op_sci_merge): (alpha, beta, c)"""
+    lib = lib or _lib.init()
+    a, b = _sci_space(alpha, beta)
+    ja, jb = _sci_space(jalpha, jbeta)
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    N = a.size + ja.size
+    oa, ob, oc = np.empty(N, dtype=np.uint64), np.empty(N, dtype=np.uint64), np.empty(N)
+    check(lib.qemb_op_sci_merge(a.size, a.ctypes.data, b.ctypes.data, c.ctypes.data, ja.size, ja.ctypes.data, jb.ctypes.data, oa.ctypes.data, ob.ctypes.data, oc.ctypes.data),
+          "qemb_op_sci_merge", lib)
+    return oa, ob, oc
+
+
+def sci_matrix(h, V, alpha, beta, lib=None):
+    """the CSR matrix of H over the sorted space (qemb_op_sci_matrix): (rowptr int64 (N + 1), col int32 (nnz), val (nnz))"""
+    lib = lib or _lib.init()
+    a, b = _sci_space(alpha, beta)
+    h, n, Vd = _sci_integrals(h, V, lib)
+    try:
+        nnz, rp = C.c_int64(), np.empty(a.size + 1, dtype=np.int64)
+        args = (n, h.ctypes.data, Vd.ptr, a.size, a.ctypes.data, b.ctypes.data)
+        check(lib.qemb_op_sci_matrix(*args, 0, C.byref(nnz), rp.ctypes.data, None, None), "qemb_op_sci_matrix", lib)
+        col, val = np.empty(nnz.value, dtype=np.int32), np.empty(nnz.value)
+        check(lib.qemb_op_sci_matrix(*args, nnz.value, C.byref(nnz), rp.ctypes.data, col.ctypes.data, val.ctypes.data), "qemb_op_sci_matrix", lib)
+        return rp, col, val
+    finally:
+        Vd.free()
+
+
+def sci_spmv(h, V, alpha, beta, x, lib=None):
+    """y = H x over the sorted space (qemb_op_sci_spmv)"""
+    lib = lib or _lib.init()
+    a, b = _sci_space(alpha, beta)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    h, n, Vd = _sci_integrals(h, V, lib)
+    try:
+        y = np.empty(a.size)
+        check(lib.qemb_op_sci_spmv(n, h.ctypes.data, Vd.ptr, a.size, a.ctypes.data, b.ctypes.data, x.ctypes.data, y.ctypes.data), "qemb_op_sci_spmv", lib)
+        return y
+    finally:
+        Vd.free()
+
+
+def sci_rdm12(h, V, nsocc, alpha, beta, c, cumulant=False, lib=None):
+    """(dm1, dm2) of the vector c over the sorted space in PySCF's conventions (qemb_op_sci_rdm12); cumulant: dm2 minus the mean-field part"""
+    lib = lib or _lib.init()
+    a, b = _sci_space(alpha, beta)
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    h, n, Vd = _sci_integrals(h, V, lib)
+    try:
+        dm1, dm2 = np.empty((n, n)), np.empty((n, n, n, n))
+        check(lib.qemb_op_sci_rdm12(n, int(nsocc), h.ctypes.data, Vd.ptr, a.size, a.ctypes.data, b.ctypes.data, c.ctypes.data, int(bool(cumulant)), dm1.ctypes.data,
+                                    dm2.ctypes.data), "qemb_op_sci_rdm12", lib)
+        return dm1, dm2
+    finally:
+        Vd.free()
 
 
 def fci_links(n, nsocc, lib=None):

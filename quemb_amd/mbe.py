@@ -589,9 +589,9 @@ class BE:
         if return_rdm:
             return (rdm1f, RDM2_full)
 
-    def compute_numerical_jacobian(self, solver="CCSD", only_chem=False, nproc=1, step_size=1e-6):
+    def compute_numerical_jacobian(self, solver="CCSD", only_chem=False, nproc=1, step_size=1e-6, solver_args=None):
         from .numerical_jac import compute_numerical_jacobian
-        return compute_numerical_jacobian(self, solver, only_chem, nproc, step_size=step_size)
+        return compute_numerical_jacobian(self, solver, only_chem, nproc, step_size=step_size, solver_args=solver_args)
 
     # ------------------------------------------------------------------ sweeps
     def _sweep(self, pot, solver="CCSD", **kw):
@@ -605,10 +605,11 @@ class BE:
         return be_func(pot, self.Fobjs, self.Nocc, solver, self.enuc, opts=self.opts, stats=self.stats, nstreams=self.nstreams, lockstep=self.lockstep, **kw)
 
     def oneshot(self, solver="CCSD", use_cumulant=True, nproc=1, ompnum=1, solver_args=None):
-        """mbe.py:1240-1310.  solver: "CCSD", "MP2" or "FCI-hip" (determinant-space FCI per fragment on the device, n <= 16 embedding orbitals)."""
+        """mbe.py:1240-1310.  solver: "CCSD", "MP2" or "FCI-hip" (determinant-space FCI per fragment on the device, n <= 16 embedding orbitals) or "SCI-hip"
+        (heat-bath selected CI per fragment on the device, n <= 64; `solver_args`: a solver.SHCI_ArgsUser with its cutoff, None for the defaults -- read by "SCI-hip" alone)."""
         if solver not in SOLVERS:
             raise ValueError("Solver not implemented")
-        rets = self._sweep(None, solver=solver, eeval=True, use_cumulant=use_cumulant, return_vec=False)
+        rets = self._sweep(None, solver=solver, eeval=True, use_cumulant=use_cumulant, return_vec=False, solver_args=solver_args)
         self.ebe_tot = rets[0] + self.ebe_hf
         self.e_corr = rets[0]
         self.e_components = rets[1]
@@ -624,7 +625,8 @@ class BE:
         amplitudes of the previous sweep, which stay resident on the device (the reference restarts from MP2 at every
         objective evaluation, solver.py:894-907); the converged amplitudes, hence all results, are the same.  solver="MP2": MP2 has no
         iterations, `warm_start` changes nothing, and relax_density is not read (as in the reference's MP2 branch).  solver="FCI-hip": every sweep starts its Davidson
-        iteration anew; relax_density is not read (as in the reference's FCI branch)."""
+        iteration anew; relax_density is not read (as in the reference's FCI branch).  solver="SCI-hip": as "FCI-hip", every sweep
+        selecting anew from the HF determinant with the cutoff of `solver_args` (SHCI_ArgsUser)."""
         from .opt import BEOPT
         from .jacobian import get_be_error_jacobian
         if solver not in SOLVERS:
@@ -638,10 +640,10 @@ class BE:
         else:
             pot = [0.0]
         be_ = BEOPT(pot, self.Fobjs, self.Nocc, self.enuc, solver=solver, only_chem=only_chem, use_cumulant=use_cumulant,
-                    max_space=max_iter, conv_tol=conv_tol, relax_density=relax_density, ebe_hf=self.ebe_hf,
+                    max_space=max_iter, conv_tol=conv_tol, relax_density=relax_density, ebe_hf=self.ebe_hf, solver_args=solver_args,
                     sweep=lambda p, **kw: self._sweep(p, solver=solver, **kw), verbose=self.rank == 0)
         if jac_solver == "Numerical":
-            J0 = self.compute_numerical_jacobian(solver, only_chem, nproc, step_size=step_size)      # mbe.py:942-945
+            J0 = self.compute_numerical_jacobian(solver, only_chem, nproc, step_size=step_size, solver_args=solver_args)      # mbe.py:942-945
         else:
             J0 = get_be_error_jacobian(self.fobj.n_frag, self.Fobjs, jac_solver=jac_solver, owner=self.owner, rank=self.rank,
                                        world=self.world, opts=self.opts)

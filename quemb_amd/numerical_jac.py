@@ -45,7 +45,7 @@ class _Delta:
         self._rdm1 = rdm1
 
 
-def compute_numerical_jacobian(beobj, solver="CCSD", only_chem=False, nproc=1, step_size=1e-6):
+def compute_numerical_jacobian(beobj, solver="CCSD", only_chem=False, nproc=1, step_size=1e-6, solver_args=None):
     if solver not in SOLVERS:
         raise ValueError("Solver not implemented")
     pot = np.asarray(beobj.pot if not only_chem else beobj.pot[-1:], dtype=float)
@@ -53,15 +53,17 @@ def compute_numerical_jacobian(beobj, solver="CCSD", only_chem=False, nproc=1, s
     J0 = np.zeros((npot, npot))
     # chemical potential: +-h sweeps over all fragments
     x = pot.copy(); x[-1] += step_size
-    J0[:, -1] = beobj._sweep(list(x), solver=solver, only_chem=only_chem, eeval=False, return_vec=True)[1]
+    J0[:, -1] = beobj._sweep(list(x), solver=solver, only_chem=only_chem, eeval=False, return_vec=True, solver_args=solver_args)[1]
     x[-1] -= 2 * step_size
-    J0[:, -1] -= beobj._sweep(list(x), solver=solver, only_chem=only_chem, eeval=False, return_vec=True)[1]
+    J0[:, -1] -= beobj._sweep(list(x), solver=solver, only_chem=only_chem, eeval=False, return_vec=True, solver_args=solver_args)[1]
     J0[:, -1] /= 2 * step_size
     if only_chem:
         return J0
     # the amplitudes of the sweep just done stay on the device: every perturbed solve below starts from them
     opts = SolverOpts.from_buffer_copy(beobj.opts) if beobj.opts is not None else default_opts(beobj.lib)
     opts.warm_start = 1
+    from .solver import sci_opts_from_args
+    sci_opts = sci_opts_from_args(solver, solver_args, beobj.lib)
     emap = beobj.emap if beobj.emap is not None else ErrorMap(beobj.Fobjs)
     nkpt = beobj.Fobjs[0].unitcell_nkpt
     cols = np.zeros((npot, npot))
@@ -73,7 +75,7 @@ def compute_numerical_jacobian(beobj, solver="CCSD", only_chem=False, nproc=1, s
                 rd = []
                 for sgn in (+1.0, -1.0):
                     x = pot.copy(); x[idx] += sgn * step_size
-                    out = f.dev.solve_as(solver, f.nsocc, f.fock + calc_heff(f, x, only_chem), f.dm0, opts=opts, eeval=False)
+                    out = f.dev.solve_as(solver, f.nsocc, f.fock + calc_heff(f, x, only_chem), f.dm0, opts=opts, eeval=False, sci_opts=sci_opts)
                     rd.append(out["rdm1_emb"])
                 view = [None] * len(beobj.Fobjs)
                 view[I] = _Delta(rd[0] - rd[1])

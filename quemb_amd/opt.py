@@ -22,6 +22,7 @@ class BEOPT:
         self.Fobjs, self.Nocc, self.enuc = Fobjs, Nocc, enuc
         self.solver, self.only_chem, self.use_cumulant = solver, only_chem, use_cumulant
         self.max_space, self.conv_tol, self.relax_density, self.ebe_hf = max_space, conv_tol, relax_density, ebe_hf
+        self.solver_args = solver_args      # (read by solver="SCI-hip" alone: handed to every sweep unchanged)
         self.iter = 0
         self.err = 0.0
         self.Ebe = np.array([[0.0]])
@@ -37,7 +38,7 @@ class BEOPT:
     def objfunc(self, xk):
         """molbe/opt.py:89-144: error vector of one sweep; records the RMS error and the BE energies."""
         err_, errvec_, ebe_ = self._sweep(list(xk), only_chem=self.only_chem, use_cumulant=self.use_cumulant, eeval=True,
-                                          return_vec=True, relax_density=self.relax_density)
+                                          return_vec=True, relax_density=self.relax_density, solver_args=self.solver_args)
         self.err = err_
         self.Ebe = ebe_
         self.pot = list(xk)

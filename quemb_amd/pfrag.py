@@ -165,15 +165,19 @@ class Frags:
         return None
 
     # ------------------------------------------------------------------ the sweep body
-    def solve(self, opts=None, eeval=True, use_cumulant=True, want_t2=False, relax_density=False, solver="CCSD", fci_opts=None):
+    def solve(self, opts=None, eeval=True, use_cumulant=True, want_t2=False, relax_density=False, solver="CCSD", fci_opts=None, solver_args=None):
         """update_heff -> scf -> solve_ccsd -> rdm1 -> get_frag_energy for this fragment (solver.py:301-547).
         relax_density: solve_ccsd(relax=True) (solver.py:925-939) -- Lambda equations on the device, response densities.
         solver="MP2": the MP2 branch (solver.py:313-317) -- solve_mp2, unrelaxed MP2 1-RDM; relax_density is not read, as in the reference.
-        solver="FCI-hip": the FCI branch (solver.py:339-342) on the device; `fci_opts` (qemb_fci_opts, None: defaults), want_t2 asks for the CI vector (out["civec"])."""
+        solver="FCI-hip": the FCI branch (solver.py:339-342) on the device; `fci_opts` (qemb_fci_opts, None: defaults), want_t2 asks for the CI vector (out["civec"]).
+        solver="SCI-hip": the selected-CI branch (solver.py:412-462) on the device; `solver_args` (SHCI_ArgsUser, None: defaults) gives its cutoff and is read by
+        this solver alone; want_t2 asks for the determinants and the vector (out["dets"])."""
         if solver not in SOLVERS:
             raise ValueError("Solver not implemented")
+        from .solver import sci_opts_from_args
+        sci_opts = sci_opts_from_args(solver, solver_args, self.dev.lib)
         opts = self._solve_inputs(opts, eeval, relax_density and solver == "CCSD")      # (the MP2 and FCI branches do not read relax_density)
-        out = self.dev.solve_as(solver, self.nsocc, self.fock + self.heff, self.dm0, opts=opts, eeval=eeval, want_amplitudes=want_t2, fci_opts=fci_opts)
+        out = self.dev.solve_as(solver, self.nsocc, self.fock + self.heff, self.dm0, opts=opts, eeval=eeval, want_amplitudes=want_t2, fci_opts=fci_opts, sci_opts=sci_opts)
         return self._solve_outputs(out, eeval, use_cumulant, solver)
 
     def make_rdm2(self, with_dm1=True):

@@ -8,6 +8,8 @@ ValueError("Solver not implemented") exactly like the reference's final else (:4
 
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import numpy as np
 
 from ._lib import SolverOpts
@@ -81,7 +83,34 @@ def solve_error(Fobjs, Nocc, only_chem=False, rdm1_list=None):
     return float(np.mean(err_vec * err_vec) ** 0.5), err_vec
 
 
-def _solve_fragment(name, solver, keys, h, eri_s4, nsocc, dm0, *, n_frag, rdm_return, rdm2_return, use_cumulant, opts, lib, df_factor=None, fci_opts=None):
+@dataclass(frozen=True)
+class SHCI_ArgsUser:
+    """the reference's user arguments of its selected-CI branch (molbe/solver.py), read by solver="SCI-hip": hci_cutoff is the threshold eps_var on |H_ai c_i|.
+    The perturbative correction (hci_pt) and return_frag_data are not built: NotImplementedError."""
+    hci_cutoff: float = 0.001
+    hci_pt: bool = False
+    return_frag_data: bool = False
+
+
+def sci_opts_from_args(solver, solver_args, lib=None):
+    """qemb_sci_opts of a sweep with `solver_args`: None unless solver == "SCI-hip" (the other solvers do not read the argument) or when it is None (the library's
+    defaults); a SHCI_ArgsUser gives eps_var = hci_cutoff; anything else is a TypeError.
+    Without a library only the checks are made."""
+    if solver != "SCI-hip" or solver_args is None:
+        return None
+    if not isinstance(solver_args, SHCI_ArgsUser):
+        raise TypeError(f"solver_args of solver='SCI-hip' must be a SHCI_ArgsUser or None, not {type(solver_args).__name__}")
+    if solver_args.hci_pt:
+        raise NotImplementedError("SCI-hip: the perturbative correction (hci_pt) is not implemented")
+    if solver_args.return_frag_data:
+        raise NotImplementedError("SCI-hip: return_frag_data is not implemented")
+    if lib is None:      # (the checks alone: be_func refuses a bad argument before any fragment is solved)
+        return None
+    from .fragsolver import default_sci_opts
+    return default_sci_opts(lib, eps_var=float(solver_args.hci_cutoff))
+
+
+def _solve_fragment(name, solver, keys, h, eri_s4, nsocc, dm0, *, n_frag, rdm_return, rdm2_return, use_cumulant, opts, lib, df_factor=None, fci_opts=None, sci_opts=None):
     """What solve_ccsd / solve_mp2 / solve_fci share: a fragment with its ERIs (or living on its 3-index factor) is created, solved without energies and freed.
     Returns (out[keys[0]], out[keys[1]]), then rdm1_mo and mo_coeff with rdm_return; rdm2_return: the 2-RDM of the solve takes the place of mo_coeff
     (solver.py:940-942), or is appended without rdm_return."""
@@ -95,7 +124,7 @@ def _solve_fragment(name, solver, keys, h, eri_s4, nsocc, dm0, *, n_frag, rdm_re
             fr.set_df_only(df_factor)
         else:
             raise ValueError(f"{name} needs the fragment ERIs or their 3-index factor")
-        out = fr.solve_as(solver, nsocc, h, dm0, opts=opts, eeval=False, want_amplitudes=True, fci_opts=fci_opts)
+        out = fr.solve_as(solver, nsocc, h, dm0, opts=opts, eeval=False, want_amplitudes=True, fci_opts=fci_opts, sci_opts=sci_opts)
         rdm2 = fr.make_rdm2(solver, with_dm1=not use_cumulant) if rdm2_return else None
     finally:
         fr.free()
@@ -137,6 +166,25 @@ def solve_fci(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_re
                            use_cumulant=use_cumulant, opts=opts, lib=lib, df_factor=df_factor, fci_opts=fci_opts)
 
 
+def solve_sci(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, use_cumulant=True, df_factor=None, opts=None, sci_opts=None, lib=None):
+    """Device counterpart of the reference's selected-CI branch (molbe/solver.py:412-462) with the inputs of `solve_fci` above.  Returns (e_sci, dets) -- the
+    eigenvalue in the selected space and (alpha, beta, c), the occupation words of the final space sorted by (alpha, beta) with the vector -- or
+    (e_sci, dets, rdm1_mo, mo_coeff) with rdm_return; rdm2_return: the 2-RDM (minus its mean-field part with use_cumulant) in the place `solve_ccsd` gives it."""
+    return _solve_fragment("solve_sci", "SCI-hip", ("e_sci", "dets"), h, eri_s4, nsocc, dm0, n_frag=n_frag, rdm_return=rdm_return, rdm2_return=rdm2_return,
+                           use_cumulant=use_cumulant, opts=opts, lib=lib, df_factor=df_factor, sci_opts=sci_opts)
+
+
+def sci_work_bytes(n, o, max_det=1 << 20, max_space=12):
+    """qemb_frag_sci_bytes restated: what max_det fixes of the working set of solver="SCI-hip" (the CSR arrays, 12 bytes per stored element, come on top)"""
+    from math import comb
+    v = n - o
+    nexc = 2 * o * v + 2 * comb(o, 2) * comb(v, 2) + (o * v) ** 2
+    cap = 1 << 20
+    while cap < 2 * nexc:
+        cap <<= 1
+    return float(3 * 24 * max_det + cap * 28 + 4096 * 256 * 12 + 8 * (2 * max_space + 4) * max_det + 20 * max_det + 8 * (4 * n ** 4 + 2 * n * n))
+
+
 def fragment_work_bytes(n, o=None, solver="CCSD", naux=None):
     """Device memory ONE fragment in flight takes beside its resident ERIs: the two n^2 x npair buffers of the
     embedding->MO transformation (rows at a stride of whole 128-byte lines), the (+/-) pair-packed ladder operands, the ovvv block with its
@@ -148,6 +196,8 @@ def fragment_work_bytes(n, o=None, solver="CCSD", naux=None):
     if solver not in SOLVERS:
         raise ValueError("Solver not implemented")
     n = int(n)
+    if solver == "SCI-hip":      # (csrc/sci.cpp; qemb_frag_sci_bytes with the default max_det = 2^20 and max_space = 12; without n_occ: n_occ = n / 2)
+        return sci_work_bytes(n, max(1, n // 2) if o is None else int(o))
     if solver == "FCI-hip":
         from math import comb
         o = max(1, n // 2) if o is None else int(o)
@@ -285,20 +335,21 @@ def map_fragments(fn, frags, nstreams=1):
 
 
 def solve_fragments(pot, frags, only_chem=False, opts=None, eeval=False, use_cumulant=True, relax_density=False, nstreams=1, lockstep=False,
-                    stats=None, solver="CCSD"):
+                    stats=None, solver="CCSD", solver_args=None):
     """The loop body of be_func (molbe/solver.py:301-547) for the fragments `frags`: update_heff, then the device solve of each.
     nstreams > 1: that many fragments in flight on separate streams (map_fragments).  lockstep: ALL fragments in one library call
     (qemb_frag_solve_batch) -- their CCSD iterations advance together, every operation one grouped launch; the small-fragment regime
     (octane BE2 / BE3), where a fragment alone is bound by its ~110 dependent launches per iteration.  Same results, bit for bit.
     solver="MP2": the MP2 branch of the loop body (solver.py:313-317); `lockstep` then takes qemb_frag_solve_mp2_batch and relax_density is not read.
     solver="FCI-hip": the FCI branch (solver.py:339-342); there is no batched entry -- with `lockstep` the fragments run one by one, or on `nstreams` streams;
-    relax_density is not read."""
+    relax_density is not read.
+    solver="SCI-hip": the selected-CI branch (solver.py:412-462) with `solver_args` (SHCI_ArgsUser or None); the fragments run as those of "FCI-hip" do."""
     if solver not in SOLVERS:
         raise ValueError("Solver not implemented")
     if solver != "CCSD":
         relax_density = False
     frags = list(frags)
-    if lockstep and len(frags) > 1 and solver != "FCI-hip":
+    if lockstep and len(frags) > 1 and solver not in ("FCI-hip", "SCI-hip"):
         from .fragsolver import solve_batch
         o_list = []
         for f in frags:
@@ -315,7 +366,7 @@ def solve_fragments(pot, frags, only_chem=False, opts=None, eeval=False, use_cum
         if pot is not None:
             fobj.update_heff(pot, only_chem=only_chem)
         assert fobj.fock is not None and fobj.heff is not None
-        return fobj.solve(opts=opts, eeval=eeval, use_cumulant=use_cumulant, relax_density=relax_density, solver=solver)
+        return fobj.solve(opts=opts, eeval=eeval, use_cumulant=use_cumulant, relax_density=relax_density, solver=solver, solver_args=solver_args)
     return map_fragments(one, frags, nstreams)
 
 
@@ -326,9 +377,10 @@ def be_func(pot, Fobjs, Nocc, solver, enuc, solver_args=None, scratch_dir=None, 
     solve_fragments) are additions; everything else has the reference's meaning."""
     if solver not in SOLVERS:
         raise ValueError("Solver not implemented")
+    sci_opts_from_args(solver, solver_args)      # (a wrong type or an option that is not built is refused before any fragment is solved; read by "SCI-hip" alone)
     total_e = [0.0, 0.0, 0.0]
     n_iter = 0
-    for out in solve_fragments(pot, Fobjs, only_chem, opts, eeval, use_cumulant, relax_density, nstreams, lockstep, stats, solver):
+    for out in solve_fragments(pot, Fobjs, only_chem, opts, eeval, use_cumulant, relax_density, nstreams, lockstep, stats, solver, solver_args):
         n_iter += out["n_iter"]
         if eeval:
             total_e = [a + b for a, b in zip(total_e, out["e_frag"])]

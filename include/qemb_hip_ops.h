@@ -130,6 +130,15 @@ int qemb_op_lincomb2(int64_t n, double a, const double* x, double b, const doubl
 int qemb_op_small_k_update(int64_t batch, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t sA, const double* B, int64_t sB, double* C, int64_t sC);
 int qemb_op_ccsd_ph_layouts(int64_t o, int64_t v, const double* t2, const double* t1, double* T, double* Tp, double* S, double* Ut, double* Tpt, double* Th);
 int qemb_op_ccsd_y_traces(int64_t o, int64_t v, const double* ZC, const double* ZB, double* Y);
+/* One pass over ovvv for two products of the CCSD update (csrc/ccsd_ovvv_ops.hip), device pointers:
+ *   ccsd_ph_layouts_ring: ccsd_ph_layouts writing Tp, S, Ut, Tpt alone (S[k,c,i,d] is Theta in the slab order of ovvv for amplitudes with t2[ikcd] = t2[kidc])
+ *   ccsd_ovvv_slabs:   G > 0, the number of partial slabs ccsd_ovvv_pass writes for this shape; 0: a shape it refuses (n_occ > 32, or n_virt beyond its
+ *                      register / LDS limits)
+ *   ccsd_ovvv_pass:    ZB[k,c,a,i] = sum_d ovvv[k,c,a,d] t1[i,d] ([o][v][v][o]) and PA[g][i][a], G slabs [o][v] whose sum over g (in order) is
+ *                      sum_{k,c,d} Thk[k,c,i,d] ovvv[k,c,a,d]; slab g holds the (k,c) pairs [g o v / G, (g + 1) o v / G).  The same bits on every call. */
+int qemb_op_ccsd_ph_layouts_ring(int64_t o, int64_t v, const double* t2, const double* t1, double* Tp, double* S, double* Ut, double* Tpt);
+int qemb_op_ccsd_ovvv_slabs(int64_t o, int64_t v);
+int qemb_op_ccsd_ovvv_pass(int64_t o, int64_t v, const double* ovvv, const double* t1, const double* Thk, double* ZB, double* PA);
 /* Fused passes of the CCSD amplitude update (csrc/ccsd.cpp update_amps), device pointers:
  *   copy4_two: qemb_op_copy4 with base (NULL: out) and a second output of the same pass, addressed like out: out2 = c2a in2 + c2b (value written to out)
  *   scatter_pm_rows_add / ccsd_y_traces_add: the plain ops with an addend laid out like the result

@@ -125,6 +125,9 @@ def _declare(lib):
     f("qemb_op_lincomb2", I, L, D, P, D, P, D, P)
     f("qemb_op_small_k_update", I, L, L, L, L, D, P, L, P, L, P, L)
     f("qemb_op_ccsd_ph_layouts", I, L, L, P, P, P, P, P, P, P, P)
+    f("qemb_op_ccsd_ph_layouts_ring", I, L, L, P, P, P, P, P, P)
+    f("qemb_op_ccsd_ovvv_slabs", I, L, L)
+    f("qemb_op_ccsd_ovvv_pass", I, L, L, P, P, P, P, P)
     f("qemb_op_ccsd_y_traces", I, L, L, P, P, P)
     f("qemb_op_copy4_two", I, C.POINTER(L), P, C.POINTER(L), P, C.POINTER(L), D, D, P, P, P, D, D)
     f("qemb_op_scatter_pm_rows_add", I, L, L, P, P, P, P)

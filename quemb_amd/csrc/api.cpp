@@ -227,6 +227,13 @@ int qemb_op_small_k_update(int64_t batch, int64_t M, int64_t N, int64_t K, doubl
 int qemb_op_ccsd_ph_layouts(int64_t o, int64_t v, const double* t2, const double* t1, double* T, double* Tp, double* S, double* Ut, double* Tpt, double* Th) {
   return dev_ccsd_ph_layouts(o, v, t2, t1, T, Tp, S, Ut, Tpt, Th);
 }
+int qemb_op_ccsd_ph_layouts_ring(int64_t o, int64_t v, const double* t2, const double* t1, double* Tp, double* S, double* Ut, double* Tpt) {
+  return dev_ccsd_ph_layouts_ring(o, v, t2, t1, Tp, S, Ut, Tpt);
+}
+int qemb_op_ccsd_ovvv_slabs(int64_t o, int64_t v) { return dev_ccsd_ovvv_slabs(o, v); }
+int qemb_op_ccsd_ovvv_pass(int64_t o, int64_t v, const double* ovvv, const double* t1, const double* Thk, double* ZB, double* PA) {
+  return dev_ccsd_ovvv_pass(o, v, ovvv, t1, Thk, ZB, PA);
+}
 int qemb_op_copy4_two(const int64_t dim[4], const double* in, const int64_t si[4], double* out, const int64_t so[4], double alpha, double beta, const double* base,
                       double* out2, const double* in2, double c2a, double c2b) {
   Copy4Desc c{};

@@ -234,6 +234,7 @@ int mo_transform_factor(int n, int o, int nf, int naux, const double* Bf, double
 }
 
 // ------------------------------------------------------------------------------------------------------------
+static bool use_ovvv_pass(int64_t o, int64_t v, bool replay);      // the one-pass ovvv rule, stated next to tile_tall / tile_wide below
 int CcsdSolver::setup(MoIntegrals&& ints, const double* mo_energy_dev) {
   I_ = std::move(ints);
   o_ = I_.o; v_ = I_.v; nf_ = I_.nf;
@@ -299,7 +300,14 @@ int CcsdSolver::setup(MoIntegrals&& ints, const double* mo_energy_dev) {
   // product is planned here, once; its buffer is sized and -- in update_amps / apply_ladder -- its launch made from the same plan
   plans_ = ccsd_gemm_plans(o, v);
   QTRY(Fvv_.alloc(plans_.fvv.elems()));
-  QTRY(T1P_.alloc(plans_.pa.elems() + plans_.pb.elems()));
+  ovvv_pass_ = use_ovvv_pass(o, v, replay_regime());
+  ovvv_G_ = ovvv_pass_ ? dev_ccsd_ovvv_slabs(o, v) : 0;
+  if (ovvv_pass_ && ovvv_G_ <= 0) ovvv_pass_ = false;
+  if (ovvv_pass_) {
+    QTRY(LovooK_.alloc(o * v * oo));
+    QTRY(perm4(LovooK_, Lovoo_, o, v, o, o, 0, 2, 1, 3));                  // Lovoo[l,c,k,i] at [l,k,c,i]: the rows of t2[l,k,c,:], so PB contracts t2 itself
+  }
+  QTRY(T1P_.alloc((ovvv_pass_ ? (int64_t)ovvv_G_ * nov : plans_.pa.elems()) + plans_.pb.elems()));
   QTRY(Foo_.alloc(oo)); QTRY(Fov_.alloc(nov)); QTRY(Z_.alloc(oo)); QTRY(Y_.alloc(vv));
   QTRY(Ytmp_.alloc(vv)); QTRY(Loo_.alloc(oo)); QTRY(Lvv_.alloc(vv)); QTRY(Q_.alloc(oo)); QTRY(Wo_.alloc(oo * oo));
   QTRY(O1_.alloc(oo * oo)); QTRY(X_.alloc(oo * nov)); QTRY(scal_.alloc(8));
@@ -421,6 +429,16 @@ static GemmPlan pick_long_k(int64_t M, int64_t N, int64_t K, int cfg, bool many_
 // n_occ <= 32 columns / rows: 128 x 32 and 32 x 128 tiles instead of padding n_occ to a 64-wide tile
 static int tile_tall(int64_t o) { return (o <= 32) ? GEMM_128x32 : -1; }
 static int tile_wide(int64_t o) { return (o <= 32) ? GEMM_32x128 : -1; }
+// ... and ONE pass over ovvv for ZB and the long-K T1 term PA (dev_ccsd_ovvv_pass) instead of the two skinny products, when all of these hold:
+//   n_occ <= 32 and n_virt within the kernel's register and LDS limits (ccsd_ovvv_shape_ok, dev_ops.h),
+//   the fragment is outside the replay regime (launch-bound fragments keep their recorded sequence: the lock-step tapes do not change).
+// QEMB_OVVV_PASS=0: never (the two products, for A/B runs); =1: wherever the shape allows, the replay regime included (tests).  Read at every set-up of a
+// solver (not once per process), so that one process can solve the same fragment both ways.
+static bool use_ovvv_pass(int64_t o, int64_t v, bool replay) {
+  const long long sw = env_int("QEMB_OVVV_PASS", -1);
+  if (sw == 0 || !ccsd_ovvv_shape_ok(o, v)) return false;
+  return sw > 0 || !replay;
+}
 
 // Every product of the CCSD update whose split-K slabs the consumer adds up itself, for a fragment of o occupied and v virtual orbitals (K of the packed
 // products: the row strides of the packed virtual pairs).  The (-) products of a fragment without antisymmetric pairs are planned with one row / column: they are never launched.
@@ -493,7 +511,8 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
   // T [k,c,j,b] = t2[k,j,c,b], Tp[k,c,j,b] = t2[k,j,b,c], S = u = 2T - Tp (Theta_ph), and the t1-dressed ring operands
   // u~ = u - 2 t1(x)t1 (W12_), Tp~ = Tp + 2 t1(x)t1 (W12b_), t1(x)t1[(ia),(ld)] = t1[id] t1[la] -- one pass over t2
   QTRY(dev_region_begin());
-  QTRY(dev_ccsd_ph_layouts(o, v, t2, t1, T_, Tp_, S_, W12_, W12b_, R_));   // R_: Th[i,k,d,c] = 2 t2[ikcd] - t2[ikdc], scratch until the rings
+  if (ovvv_pass_) QTRY(dev_ccsd_ph_layouts_ring(o, v, t2, t1, Tp_, S_, W12_, W12b_));   // (T and Th are not needed: PB contracts t2, and S is Theta in the slab order of ovvv)
+  else QTRY(dev_ccsd_ph_layouts(o, v, t2, t1, T_, Tp_, S_, W12_, W12b_, R_));   // R_: Th[i,k,d,c] = 2 t2[ikcd] - t2[ikdc], scratch until the rings
   QTRY(dev_region_chain());
   QTRY(dev_ladder_pack_tau(o, v, tau_, LTp_, I_.ldp, LTm_, I_.ldm));     // the packed tau rows: also read by the ladder and by the tau-side dressing below
   QTRY(dev_region_end());
@@ -529,8 +548,11 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
   // (n_occ <= 32 columns / rows: 128 x 32 and 32 x 128 tiles instead of padding n_occ to a 64-wide tile, which made these
   //  HBM-bound passes MFMA-bound)
   const int cfg_tall = tile_tall(o), cfg_wide = tile_wide(o);
+  // (one-pass rule: ZB comes with PA out of ONE read of ovvv -- the block is then read twice per iteration, here and packed for ZC)
+  double* PA = T1P_.p;
   QTRY(dev_region_begin());
-  QTRY(gemm(o * vv, o, v, 1.0, I_.ovvv, v, true, t1, v, true, 0.0, ZB_, o, 1, 0, 0, 0, cfg_tall));     // ZB[k,c,a,i] = ovvv[kcad] t1[id]
+  if (ovvv_pass_) QTRY(dev_ccsd_ovvv_pass(o, v, I_.ovvv, t1, S_, ZB_, PA));                          // ZB[k,c,a,i] = ovvv[kcad] t1[id];  PA slabs [g][i][a] = S[k,c,i,d] ovvv[kcad]
+  else QTRY(gemm(o * vv, o, v, 1.0, I_.ovvv, v, true, t1, v, true, 0.0, ZB_, o, 1, 0, 0, 0, cfg_tall));     // ZB[k,c,a,i] = ovvv[kcad] t1[id]
   QTRY(dev_region_chain());
   {  // ZC[k,i,a,c] = t1[id] ovvv[kdac], symmetric in (a,c): on the pair-packed block, then unpacked
     const int64_t npv = v * (v + 1) / 2;
@@ -544,13 +566,19 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
   // ---- T1 equation
   // The two long-K terms first, as the slabs their K slices leave:  PA[i,a] = (2 ovvv[kdac] - ovvv[kcad]) t2[ikcd],  PB[i,a] = (2 ovoo[lcki] - ovoo[kcli]) t2[klac]
   SlabGemm spa, spb;
-  double* PA = T1P_.p;
-  QTRY(dev_region_begin());
-  QTRY(gemm_slabs(plans_.pa, R_, o * vv, I_.ovvv, v, PA, v, spa, true, false));      // (no split: the plain product)
-  double* PB = PA + (int64_t)spa.S * nov;
-  QTRY(dev_region_chain());
-  QTRY(gemm_slabs(plans_.pb, Lovoo_, o, T_, v, PB, v, spb, false, false));
-  QTRY(dev_region_end());
+  double* PB = nullptr;
+  if (ovvv_pass_) {      // PA: the slabs of the one pass above; PB over the rows (l,k,c) of t2 itself
+    spa.S = ovvv_G_; spa.stride = nov; spa.ld = v;
+    PB = PA + (int64_t)spa.S * nov;
+    QTRY(gemm_slabs(plans_.pb, LovooK_, o, t2, v, PB, v, spb, false, false));
+  } else {
+    QTRY(dev_region_begin());
+    QTRY(gemm_slabs(plans_.pa, R_, o * vv, I_.ovvv, v, PA, v, spa, true, false));      // (no split: the plain product)
+    PB = PA + (int64_t)spa.S * nov;
+    QTRY(dev_region_chain());
+    QTRY(gemm_slabs(plans_.pb, Lovoo_, o, T_, v, PB, v, spb, false, false));
+    QTRY(dev_region_end());
+  }
   // t1n = (Fvv'+Y)_ac t1[ic] - (Foo'+Z)_ki t1[ka] + Fov_kc t1[ic] t1[ka] + Fov_kc (2 t2[kica] - t2[ikca]) + (2 ovvo[kcai] - oovv[kiac]) t1[kc] + PA - PB:
   // the small products, the two passes over o^2 v^2 operands and the slab sums in one launch (a workgroup per element)
   QTRY(dev_ccsd_t1_assemble(o, v, t1, Lvv_, Loo_, Fov_, S_, Lph1_, PA, spa.S, nov, PB, spb.S, nov, t1n));

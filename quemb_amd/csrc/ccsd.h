@@ -104,6 +104,11 @@ class CcsdSolver {
   // amplitudes (t1 then t2, one contiguous vector) and per-iteration work space
   DBuf amp_, ampn_, diff_;
   DBuf tau_, T_, Tp_, S_, W1_, W2_, W12_, W12b_, R_, U_, G2_, T1P_;      // T1P_: slabs of the two long-K products of the T1 equation
+  // the one-pass ovvv rule (ccsd.cpp, next to tile_tall / tile_wide), decided once in setup: ZB and the long-K T1 term PA from one read of ovvv
+  // (dev_ccsd_ovvv_pass, ovvv_G_ partial slabs of PA), and PB contracted with t2 itself through LovooK_[l,k,c,i] = Lovoo[l,c,k,i] (T_ and Th are then not written)
+  bool ovvv_pass_ = false;
+  int ovvv_G_ = 0;
+  DBuf LovooK_;
   DBuf LTp_, LTm_, LRp_, LRm_;   // (+/-) packed ladder: tau combinations and results
   DBuf Xp_, Xm_;                 // (+/-) packed rows of X[i,j,k,a] = tau[ijcd] ovvv[kdac]
   DBuf ovvv_pk_, ZCp_;           // ovvv[k,d,(a>=c)] packed over its symmetric pair, and the packed result of its t1 contraction

@@ -337,6 +337,26 @@ int dev_foo_from_x(int64_t o, const double* X, double* F);
 //   Ut[k,c,j,b] = S  - 2 t1[j,c] t1[k,b]        Tpt[k,c,j,b] = Tp + 2 t1[j,c] t1[k,b]
 // and, in the layout of t2 itself ([o][o][v][v]),  Th[k,j,c,b] = 2 t2[k,j,b,c] - t2[k,j,c,b]
 int dev_ccsd_ph_layouts(int64_t o, int64_t v, const double* t2, const double* t1, double* T, double* Tp, double* S, double* Ut, double* Tpt, double* Th);
+// The same pass writing the four ring operands alone (no T, no Th), for the one-pass ovvv rule of the CCSD update: T's one reader, the PB product, contracts t2
+// itself, and Theta in the slab order of ovvv, Thk[k,c,i,d] = Th[i,k,c,d], IS S: S[k,c,i,d] = 2 t2[k,i,c,d] - t2[k,i,d,c] = 2 t2[i,k,d,c] - t2[i,k,c,d] by
+// t2[i,k,c,d] = t2[k,i,d,c], the symmetry of the amplitudes that the ring operands rely on too.
+int dev_ccsd_ph_layouts_ring(int64_t o, int64_t v, const double* t2, const double* t1, double* Tp, double* S, double* Ut, double* Tpt);
+// ---- one pass over ovvv for ZB and the long-K term of the T1 equation (kernel in ccsd_ovvv_ops.hip, scalar restatement for the mock in ccsd_ovvv_ops_hostcheck.cpp)
+//   ZB[k,c,a,i] = sum_d ovvv[k,c,a,d] t1[i,d]                       ([o][v][v][o])
+//   PA[g][i][a] = sum over the slabs s = k v + c of workgroup g, and d, of Thk[k,c,i,d] ovvv[k,c,a,d]     (Thk: any [o][v][o][v] operand; the update passes S.  G = dev_ccsd_ovvv_slabs(o, v) partial slabs [o][v];
+//                 workgroup g owns the slabs [g o v / G, (g + 1) o v / G) in order, so sum_g PA[g] in slab order is the same bits run to run)
+// Shapes the kernel takes (ccsd_ovvv_shape_ok; others are an error -- the caller keeps the two GEMMs): n_occ <= 32, i.e. NT = ceil(2 o / 16) <= 4 column
+// tiles; RT = ceil(v / 16) row tiles with RT NT <= CCSD_OVVV_MAX_TILES (the accumulator tiles four waves hold in registers) and RT + NT <=
+// CCSD_OVVV_MAX_ROWT (the staged rows: LDS and staging registers).
+constexpr int CCSD_OVVV_MAX_TILES = 48;
+constexpr int CCSD_OVVV_MAX_ROWT = 18;
+inline bool ccsd_ovvv_shape_ok(int64_t o, int64_t v) {
+  if (o < 1 || v < 1 || o > 32) return false;
+  const int64_t rt = (v + 15) / 16, nt = (2 * o + 15) / 16;
+  return rt * nt <= CCSD_OVVV_MAX_TILES && rt + nt <= CCSD_OVVV_MAX_ROWT;
+}
+int dev_ccsd_ovvv_slabs(int64_t o, int64_t v);      // G (> 0), or 0 for a shape the kernel does not take
+int dev_ccsd_ovvv_pass(int64_t o, int64_t v, const double* ovvv, const double* t1, const double* Thk, double* ZB, double* PA);
 // Batched small-K update (K = n_occ): C[z][m][n] += alpha sum_k A[z][k][m] B[z][k][n]   (A: [K][M] per batch, stride sA; B: [K][N] per batch,
 // stride sB; a stride of 0 shares the operand; C: [M][N] per batch, stride sC).  One pass over C -- these products are HBM bound, a
 // tiled GEMM with two k-steps is not.

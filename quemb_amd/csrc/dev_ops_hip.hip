@@ -1240,13 +1240,13 @@ __device__ __forceinline__ void ccsd_ph_layouts_kernel_body(const uint3 BID, con
       const double xp = xt[tx][ty + 8 * r];          // t2[k,j,b,c]
       const double tt = 2.0 * t1[j * v + c] * t1[k * v + b];
       const long long off = ((k * v + c) * o + j) * v + b;
-      T[off] = x;
+      if (T) T[off] = x;
       Tp[off] = xp;
       const double s = 2.0 * x - xp;
       S[off] = s;
       Ut[off] = s - tt;
       Tpt[off] = xp + tt;
-      Th[((k * o + j) * v + c) * v + b] = 2.0 * xp - x;
+      if (Th) Th[((k * o + j) * v + c) * v + b] = 2.0 * xp - x;
     }
   }
 }
@@ -1254,13 +1254,21 @@ __global__ void __launch_bounds__(256) ccsd_ph_layouts_kernel(long long o, long 
                                                               double* __restrict__ T, double* __restrict__ Tp, double* __restrict__ S,
                                                               double* __restrict__ Ut, double* __restrict__ Tpt, double* __restrict__ Th, int tiles) { ccsd_ph_layouts_kernel_body(block_id(), grid_dim(), o, v, t2, t1, T, Tp, S, Ut, Tpt, Th, tiles); }
 static const Groupable<ccsd_ph_layouts_kernel_body, 256> reg_ccsd_ph_layouts(ccsd_ph_layouts_kernel);
-int dev_ccsd_ph_layouts(int64_t o, int64_t v, const double* t2, const double* t1, double* T, double* Tp, double* S, double* Ut, double* Tpt, double* Th) {
+static int ccsd_ph_layouts_launch(int64_t o, int64_t v, const double* t2, const double* t1, double* T, double* Tp, double* S, double* Ut, double* Tpt, double* Th) {
   REQUIRE_INIT();
   if (o <= 0 || v <= 0) return QEMB_OK;
   if (o > 65535) { set_error("dev_ccsd_ph_layouts: too many occupied orbitals"); return QEMB_ERR_ARG; }
   const long long tiles_c = (v + 31) / 32, tiles = (v + 15 + 31) / 32;      // b-tiles: one more may be needed for the line-aligning shift (<= 15)
   return launch("dev_ccsd_ph_layouts", ccsd_ph_layouts_kernel, dim3((unsigned)(tiles_c * tiles), (unsigned)o, (unsigned)o), dim3(256), 0, g_stream, o, v, t2, t1,
                 T, Tp, S, Ut, Tpt, Th, (int)tiles);
+}
+int dev_ccsd_ph_layouts(int64_t o, int64_t v, const double* t2, const double* t1, double* T, double* Tp, double* S, double* Ut, double* Tpt, double* Th) {
+  if (!T || !Th) { set_error("dev_ccsd_ph_layouts: null output"); return QEMB_ERR_ARG; }
+  return ccsd_ph_layouts_launch(o, v, t2, t1, T, Tp, S, Ut, Tpt, Th);
+}
+// (the four ring operands alone: T and Th are not written)
+int dev_ccsd_ph_layouts_ring(int64_t o, int64_t v, const double* t2, const double* t1, double* Tp, double* S, double* Ut, double* Tpt) {
+  return ccsd_ph_layouts_launch(o, v, t2, t1, nullptr, Tp, S, Ut, Tpt, nullptr);
 }
 
 __device__ __forceinline__ void small_k_update_kernel_body(const uint3 BID, const uint3 GDIM, long long M, long long N, long long K, double alpha, const double* __restrict__ A, long long sA,

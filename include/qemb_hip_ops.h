@@ -139,6 +139,19 @@ int qemb_op_ccsd_y_traces(int64_t o, int64_t v, const double* ZC, const double* 
 int qemb_op_ccsd_ph_layouts_ring(int64_t o, int64_t v, const double* t2, const double* t1, double* Tp, double* S, double* Ut, double* Tpt);
 int qemb_op_ccsd_ovvv_slabs(int64_t o, int64_t v);
 int qemb_op_ccsd_ovvv_pass(int64_t o, int64_t v, const double* ovvv, const double* t1, const double* Thk, double* ZB, double* PA);
+/* The t1-dependent parts of both ring intermediates of the CCSD update in one pass (csrc/ccsd_ring_prep_ops.hip), device pointers:
+ *   ccsd_ring_prep:      W2[i,a,k,c] = W2base[i,a,k,c] + ZC[k,i,a,c] - sum_l t1[l,a] OC[k,i,l,c],
+ *                        R[i,a,k,c] = P1[i,a,k,c] + W1base[i,a,k,c] + ZB[k,c,a,i] - sum_l t1[l,a] OB[k,i,l,c] - W2[i,a,k,c] / 2
+ *                        (ZB [o][v][v][o] and ZC [o][o][v][v] are only read; OB[k,i,l,c] = ovoo[k,c,l,i], OC[k,i,l,c] = ovoo[l,c,k,i], [o][o][o][v]; the rest
+ *                        [o][v][o][v]).  The same bits on every call; a shape outside n_occ <= 32, n_virt <= 4096 is an error.
+ *   ccsd_u_update:       U[i,j,a,b] = (U[i,j,a,b] + Z[i,a,b,j]) - sum_k A[i,j,k,a] t1[k,b]: the rank-n_occ update of U ([o][o][v][v], in place) with its
+ *                        transposed addend Z ([o][v][v][o]) in the same sweep; A: [o][o][o][v].  Same shape limits.
+ *   ccsd_ring_prep_rule: 1 when a CCSD solver of this shape takes the pass (replay != 0: a fragment small enough to replay its recorded update), else 0;
+ *                        QEMB_RING_PREP=0 / 1 forces it off / on wherever the shape allows */
+int qemb_op_ccsd_ring_prep(int64_t o, int64_t v, const double* t1, const double* P1, const double* W1base, const double* W2base, const double* ZB, const double* ZC,
+                           const double* OB, const double* OC, double* R, double* W2);
+int qemb_op_ccsd_ring_prep_rule(int64_t o, int64_t v, int replay);
+int qemb_op_ccsd_u_update(int64_t o, int64_t v, const double* A, const double* t1, const double* Z, double* U);
 /* Fused passes of the CCSD amplitude update (csrc/ccsd.cpp update_amps), device pointers:
  *   copy4_two: qemb_op_copy4 with base (NULL: out) and a second output of the same pass, addressed like out: out2 = c2a in2 + c2b (value written to out)
  *   scatter_pm_rows_add / ccsd_y_traces_add: the plain ops with an addend laid out like the result

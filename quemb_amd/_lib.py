@@ -126,6 +126,9 @@ def _declare(lib):
     f("qemb_op_small_k_update", I, L, L, L, L, D, P, L, P, L, P, L)
     f("qemb_op_ccsd_ph_layouts", I, L, L, P, P, P, P, P, P, P, P)
     f("qemb_op_ccsd_ph_layouts_ring", I, L, L, P, P, P, P, P, P)
+    f("qemb_op_ccsd_ring_prep", I, L, L, P, P, P, P, P, P, P, P, P, P)
+    f("qemb_op_ccsd_ring_prep_rule", I, L, L, I)
+    f("qemb_op_ccsd_u_update", I, L, L, P, P, P, P)
     f("qemb_op_ccsd_ovvv_slabs", I, L, L)
     f("qemb_op_ccsd_ovvv_pass", I, L, L, P, P, P, P, P)
     f("qemb_op_ccsd_y_traces", I, L, L, P, P, P)

@@ -230,6 +230,12 @@ int qemb_op_ccsd_ph_layouts(int64_t o, int64_t v, const double* t2, const double
 int qemb_op_ccsd_ph_layouts_ring(int64_t o, int64_t v, const double* t2, const double* t1, double* Tp, double* S, double* Ut, double* Tpt) {
   return dev_ccsd_ph_layouts_ring(o, v, t2, t1, Tp, S, Ut, Tpt);
 }
+int qemb_op_ccsd_ring_prep(int64_t o, int64_t v, const double* t1, const double* P1, const double* W1base, const double* W2base, const double* ZB, const double* ZC,
+                           const double* OB, const double* OC, double* R, double* W2) {
+  return dev_ccsd_ring_prep(o, v, t1, P1, W1base, W2base, ZB, ZC, OB, OC, R, W2);
+}
+int qemb_op_ccsd_u_update(int64_t o, int64_t v, const double* A, const double* t1, const double* Z, double* U) { return dev_ccsd_u_update(o, v, A, t1, Z, U); }
+int qemb_op_ccsd_ring_prep_rule(int64_t o, int64_t v, int replay) { return ccsd_use_ring_prep(o, v, replay != 0) ? 1 : 0; }
 int qemb_op_ccsd_ovvv_slabs(int64_t o, int64_t v) { return dev_ccsd_ovvv_slabs(o, v); }
 int qemb_op_ccsd_ovvv_pass(int64_t o, int64_t v, const double* ovvv, const double* t1, const double* Thk, double* ZB, double* PA) {
   return dev_ccsd_ovvv_pass(o, v, ovvv, t1, Thk, ZB, PA);

@@ -307,6 +307,11 @@ int CcsdSolver::setup(MoIntegrals&& ints, const double* mo_energy_dev) {
     QTRY(LovooK_.alloc(o * v * oo));
     QTRY(perm4(LovooK_, Lovoo_, o, v, o, o, 0, 2, 1, 3));                  // Lovoo[l,c,k,i] at [l,k,c,i]: the rows of t2[l,k,c,:], so PB contracts t2 itself
   }
+  ring_prep_ = ccsd_use_ring_prep(o, v, replay_regime());
+  if (ring_prep_) {
+    QTRY(ovoo_kicl_.alloc(o * v * oo));
+    QTRY(perm4(ovoo_kicl_, I_.ovoo, o, v, o, o, 0, 3, 2, 1));               // ovoo[k,c,l,i] at [k,i,l,c]
+  }
   QTRY(T1P_.alloc((ovvv_pass_ ? (int64_t)ovvv_G_ * nov : plans_.pa.elems()) + plans_.pb.elems()));
   QTRY(Foo_.alloc(oo)); QTRY(Fov_.alloc(nov)); QTRY(Z_.alloc(oo)); QTRY(Y_.alloc(vv));
   QTRY(Ytmp_.alloc(vv)); QTRY(Loo_.alloc(oo)); QTRY(Lvv_.alloc(vv)); QTRY(Q_.alloc(oo)); QTRY(Wo_.alloc(oo * oo));
@@ -437,6 +442,16 @@ static int tile_wide(int64_t o) { return (o <= 32) ? GEMM_32x128 : -1; }
 static bool use_ovvv_pass(int64_t o, int64_t v, bool replay) {
   const long long sw = env_int("QEMB_OVVV_PASS", -1);
   if (sw == 0 || !ccsd_ovvv_shape_ok(o, v)) return false;
+  return sw > 0 || !replay;
+}
+// ... and ONE pass for the t1-dependent parts of both ring intermediates (dev_ccsd_ring_prep) instead of the two rank-n_occ updates of ZB and ZC and the two
+// transposing passes behind them, under the same two conditions: the shape is one the kernel takes (ccsd_ring_prep_shape_ok, dev_ops.h) and the fragment is
+// outside the replay regime; under the same rule U += ZB^T is added inside the rank-n_occ update of U (dev_ccsd_u_update) instead of by a pass of its own.
+// Independent of the one-pass ovvv rule.  QEMB_RING_PREP=0: never (the four passes, for A/B runs); =1: wherever the shape allows.
+// Read at every set-up of a solver.
+bool ccsd_use_ring_prep(int64_t o, int64_t v, bool replay) {
+  const long long sw = env_int("QEMB_RING_PREP", -1);
+  if (sw == 0 || !ccsd_ring_prep_shape_ok(o, v)) return false;
   return sw > 0 || !replay;
 }
 
@@ -616,17 +631,21 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
     QTRY(dev_scatter_pm_rows(o, nov, Xp_, Xm_, X_, ovoo_ijka_, sp.S, sp.stride, sm.S, sm.stride));   // ... + ovoo[i,a,j,k]: the second term of A below, added on the way
   }
   //   X1 = (ovvv[iacb] - oovv[kibc] t1[ka]) t1[jc],   X2 = (ovvo[kcai] t1[jc] + ovoo[iajk]) t1[kb] (enters with a minus sign)
-  QTRY(dev_region_begin());
-  QTRY(perm4(U_, ZB_, o, v, v, o, 0, 3, 1, 2, 1.0, 1.0));                          // U[i,j,a,b] += t1[jc] ovvv[i,a,b,c] = ZB[i,a,b,j]
-  QTRY(dev_region_chain());
+  // (one-pass ring preparation: U += ZB^T is not a pass of its own -- the rank-n_occ update below adds it in its sweep over U)
+  if (!ring_prep_) {
+    QTRY(dev_region_begin());
+    QTRY(perm4(U_, ZB_, o, v, v, o, 0, 3, 1, 2, 1.0, 1.0));                          // U[i,j,a,b] += t1[jc] ovvv[i,a,b,c] = ZB[i,a,b,j]
+    QTRY(dev_region_chain());
+  }
   // Every other t1-dressing term has the form U[i,j,a,b] -= sum_k A[i,j,k,a] t1[k,b] (the oovv one through its P-partner), with
   // A only o^3 v large: the A's are summed first and ONE rank-n_occ update passes over U.
   //   A = X[i,j,k,a] + ovoo[i,a,j,k] + (oovv[(k,j,a),c] t1[i,c]) + (t1[j,c] ovvo[k,c,a,i])
   QTRY(gemm(oo * v, o, v, 1.0, I_.oovv, v, true, t1, v, true, 0.0, G2_, o, 1, 0, 0, 0, cfg_tall));                                   // G2[k,j,a,i] = oovv[(kja),c] t1[ic]
   QTRY(gemm(o, v * o, v, 1.0, t1, v, true, I_.ovvo, v * o, false, 1.0, G2_, v * o, o, 0, v * v * o, o * v * o, cfg_wide));          //          += t1[jc] ovvo[k,c,a,i]
-  QTRY(dev_region_end());
+  if (!ring_prep_) QTRY(dev_region_end());
   QTRY(perm4(X_, G2_, o, o, v, o, 3, 1, 0, 2, 1.0, 1.0));                          // A[i,j,k,a] += G2[k,j,a,i]
-  QTRY(dev_small_k_update(oo, v, v, o, -1.0, X_, nov, t1, 0, U_, vv));                 // U[ij][a][b] -= sum_k A[ij][k][a] t1[k][b]
+  if (ring_prep_) QTRY(dev_ccsd_u_update(o, v, X_, t1, ZB_, U_));                      // U[ij][a][b] = (U + ZB[i,a,b,j]) - sum_k A[ij][k][a] t1[k][b]
+  else QTRY(dev_small_k_update(oo, v, v, o, -1.0, X_, nov, t1, 0, U_, vv));            // U[ij][a][b] -= sum_k A[ij][k][a] t1[k][b]
   // ---- ph rings
   TimerScope lap_RINGS(TIMER_RINGS);
   // The t2-dependent parts of both ring intermediates come from TWO (ov)^3 products instead of three: with
@@ -637,8 +656,11 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
   // (S = u, W12_ = u~ and W12b_ = Tp~ were formed by dev_ccsd_ph_layouts at the top of the update)
   // the rank-n_occ pieces -ovoo[kcli] t1[la] (Wvoov) and -t1[la] ovoo[lcki] (Wvovo) are subtracted from ZB / ZC in place (their last
   // readers -- the Y traces and the X1 term -- are done), so ONE transposing pass per intermediate carries both pieces
-  QTRY(dev_small_k_update(nov, v, o, o, -1.0, t1, 0, I_.ovoo, oo, ZB_, v * o));    // ZB[k,c,a,i] -= sum_l t1[l,a] ovoo[k,c,l,i]
-  QTRY(perm4(W1_, ZB_, o, v, v, o, 3, 2, 0, 1, 1.0, 1.0, W1base_));                // W1 = W1base + ovvv[kcad] t1[id] - ovoo[kcli] t1[la]
+  // (one-pass ring preparation, ring_prep_: none of this -- ZB and ZC stay raw and dev_ccsd_ring_prep below forms both intermediates from them)
+  if (!ring_prep_) {
+    QTRY(dev_small_k_update(nov, v, o, o, -1.0, t1, 0, I_.ovoo, oo, ZB_, v * o));    // ZB[k,c,a,i] -= sum_l t1[l,a] ovoo[k,c,l,i]
+    QTRY(perm4(W1_, ZB_, o, v, v, o, 3, 2, 0, 1, 1.0, 1.0, W1base_));                // W1 = W1base + ovvv[kcad] t1[id] - ovoo[kcli] t1[la]
+  }
   // The right-hand operands of all four (ov)^3 products are symmetric matrices over (kc),(ld) -- L and ovov_t by the integral symmetry
   // (kc|ld) = (ld|kc), T' and u by t2[k,j,c,b] = t2[j,k,b,c] -- so each is passed in its K-contiguous (transposed) reading: both operands
   // of the GEMM are then staged through the conflict-free [row][BK+2] LDS image, on the 128 x 256 tile (512 tiles at ov = 4000: two per CU).
@@ -652,24 +674,32 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
   auto ring = [&](double al, const double* A, const double* Bsym, double be, double* C) {
     return gemm(nov, nov, nov, al, A, nov, true, Bsym, nov, true, be, C, nov, 1, 0, 0, 0, cfg_ring, mid_ring ? 2 : 0);
   };
-  QTRY(ring(0.25, W12_, Lovov_, 1.0, W1_));                                        // + 1/4 u~ L
-  //   W2[(ia),(kc)] = Wvovo[a,k,c,i]
-  QTRY(dev_small_k_update(oo, v, v, o, -1.0, t1, 0, ovoo_kilc_, nov, ZC_, vv));     // ZC[k,i,a,c] -= sum_l t1[l,a] ovoo[l,c,k,i]
-  // W2 = W2base + t1[id] ovvv[kdac] - t1[la] ovoo[lcki].  The Tp~ ovov_t product enters Wvoov with -1/4 and Wvovo with -1/2, so it cancels in
-  // Wvoov - Wvovo/2: that combination (R) is formed first -- as a second output of the pass that writes W2 -- then the GEMM accumulates the product
-  // straight into Wvovo.
-  {
-    Copy4Desc c{};
-    const int64_t d[4] = {o, o, v, v};       // ZC[k,i,a,c] -> [i,a,k,c]
-    const int perm[4] = {1, 2, 0, 3};
-    int64_t od[4], ostr[4];
-    for (int k = 0; k < 4; ++k) od[k] = d[perm[k]];
-    ostr[3] = 1; ostr[2] = od[3]; ostr[1] = od[3] * od[2]; ostr[0] = od[3] * od[2] * od[1];
-    c.in = ZC_; c.out = W2_; c.alpha = 1.0; c.beta = 1.0; c.base = W2base_;
-    c.si[3] = 1; c.si[2] = d[3]; c.si[1] = d[3] * d[2]; c.si[0] = d[3] * d[2] * d[1];
-    for (int k = 0; k < 4; ++k) { c.dim[k] = d[k]; c.so[perm[k]] = ostr[k]; }
-    c.out2 = R_; c.in2 = W1_; c.c2a = 1.0; c.c2b = -0.5;                            // R = Wvoov - Wvovo/2
-    QTRY(dev_copy4(c));
+  if (ring_prep_) {
+    // Wvoov itself is never read -- only R = Wvoov - Wvovo/2 and Wvovo go on -- so the first product is written on its own (P1 = 1/4 u~ L, beta = 0: no read of
+    // its output) and ONE pass adds the bases, the raw ZB (transposed) and ZC and the two rank-n_occ pieces, and writes R and W2: ZB and ZC are not written
+    // back, W1 is neither written by a pass nor read again by the product
+    QTRY(ring(0.25, W12_, Lovov_, 0.0, W1_));                                        // P1 = 1/4 u~ L
+    QTRY(dev_ccsd_ring_prep(o, v, t1, W1_, W1base_, W2base_, ZB_, ZC_, ovoo_kicl_, ovoo_kilc_, R_, W2_));
+  } else {
+    QTRY(ring(0.25, W12_, Lovov_, 1.0, W1_));                                        // + 1/4 u~ L
+    //   W2[(ia),(kc)] = Wvovo[a,k,c,i]
+    QTRY(dev_small_k_update(oo, v, v, o, -1.0, t1, 0, ovoo_kilc_, nov, ZC_, vv));     // ZC[k,i,a,c] -= sum_l t1[l,a] ovoo[l,c,k,i]
+    // W2 = W2base + t1[id] ovvv[kdac] - t1[la] ovoo[lcki].  The Tp~ ovov_t product enters Wvoov with -1/4 and Wvovo with -1/2, so it cancels in
+    // Wvoov - Wvovo/2: that combination (R) is formed first -- as a second output of the pass that writes W2 -- then the GEMM accumulates the product
+    // straight into Wvovo.
+    {
+      Copy4Desc c{};
+      const int64_t d[4] = {o, o, v, v};       // ZC[k,i,a,c] -> [i,a,k,c]
+      const int perm[4] = {1, 2, 0, 3};
+      int64_t od[4], ostr[4];
+      for (int k = 0; k < 4; ++k) od[k] = d[perm[k]];
+      ostr[3] = 1; ostr[2] = od[3]; ostr[1] = od[3] * od[2]; ostr[0] = od[3] * od[2] * od[1];
+      c.in = ZC_; c.out = W2_; c.alpha = 1.0; c.beta = 1.0; c.base = W2base_;
+      c.si[3] = 1; c.si[2] = d[3]; c.si[1] = d[3] * d[2]; c.si[0] = d[3] * d[2] * d[1];
+      for (int k = 0; k < 4; ++k) { c.dim[k] = d[k]; c.so[perm[k]] = ostr[k]; }
+      c.out2 = R_; c.in2 = W1_; c.c2a = 1.0; c.c2b = -0.5;                            // R = Wvoov - Wvovo/2
+      QTRY(dev_copy4(c));
+    }
   }
   QTRY(ring(-0.5, W12b_, ovov_t_, 1.0, W2_));                                       // Wvovo -= 1/2 Tp~ ovov_t
   // Update, also two products:  (2 Wvoov - Wvovo) T - Wvoov Tp = (Wvoov - Wvovo/2) u - (Wvovo Tp)/2  with T = (u + Tp)/2

@@ -48,6 +48,8 @@ inline bool mo_factor_route_pays(int n, int naux) { return naux > 0 && (int64_t)
 // (Fvv', the two long-K terms of the T1 equation, then the (+/-) pairs of the pp-ladder, of Xw = ovov . tau and of the tau-side dressing X = tau . ovvv)
 struct CcsdGemmPlans { GemmPlan fvv, pa, pb, ladder_p, ladder_m, xw_p, xw_m, x_p, x_m; };
 CcsdGemmPlans ccsd_gemm_plans(int64_t o, int64_t v);
+// the one-pass ring preparation rule (ccsd.cpp, next to the tile rules): whether a solver of this shape replaces the four passes by dev_ccsd_ring_prep
+bool ccsd_use_ring_prep(int64_t o, int64_t v, bool replay);
 
 class CcLambda;
 
@@ -109,6 +111,10 @@ class CcsdSolver {
   bool ovvv_pass_ = false;
   int ovvv_G_ = 0;
   DBuf LovooK_;
+  // one-pass ring preparation (ccsd_use_ring_prep): the first ring product goes first (P1, beta = 0) and ONE pass forms R and W2 from the raw ZB and ZC
+  // (dev_ccsd_ring_prep); ovoo_kicl_[k,i,l,c] = ovoo[k,c,l,i] is the slab image of its ZB-side correction (the ZC side reads ovoo_kilc_)
+  bool ring_prep_ = false;
+  DBuf ovoo_kicl_;
   DBuf LTp_, LTm_, LRp_, LRm_;   // (+/-) packed ladder: tau combinations and results
   DBuf Xp_, Xm_;                 // (+/-) packed rows of X[i,j,k,a] = tau[ijcd] ovvv[kdac]
   DBuf ovvv_pk_, ZCp_;           // ovvv[k,d,(a>=c)] packed over its symmetric pair, and the packed result of its t1 contraction

@@ -357,6 +357,20 @@ inline bool ccsd_ovvv_shape_ok(int64_t o, int64_t v) {
 }
 int dev_ccsd_ovvv_slabs(int64_t o, int64_t v);      // G (> 0), or 0 for a shape the kernel does not take
 int dev_ccsd_ovvv_pass(int64_t o, int64_t v, const double* ovvv, const double* t1, const double* Thk, double* ZB, double* PA);
+// ---- the t1-dependent parts of both ring intermediates in one pass (kernel in ccsd_ring_prep_ops.hip, scalar restatement for the mock in ccsd_ring_prep_ops_hostcheck.cpp)
+//   W2[i,a,k,c] = W2base[i,a,k,c] + ZC[k,i,a,c] - sum_l t1[l,a] OC[k,i,l,c]                                   (OC[k,i,l,c] = ovoo[l,c,k,i])
+//   R [i,a,k,c] = P1[i,a,k,c] + W1base[i,a,k,c] + ZB[k,c,a,i] - sum_l t1[l,a] OB[k,i,l,c] - 1/2 W2[i,a,k,c]   (OB[k,i,l,c] = ovoo[k,c,l,i])
+// ZB: [o][v][v][o] and ZC: [o][o][v][v], both only read; OB, OC: [o][o][o][v]; t1: [o][v]; the rest [o][v][o][v].  The outputs must not overlap the inputs.
+// Order: W2 = (W2base + ZC) - sC,  R = (((P1 + W1base) + ZB) - sB) - W2 / 2, with sB, sC summed from zero in ascending l.
+// Shapes the kernel takes (ccsd_ring_prep_shape_ok; others are an error -- the caller keeps the four passes): n_occ <= 32 (the LDS image of a workgroup's
+// ZB tile is 16 x 16 n_occ doubles) and n_virt <= 4096 (the grid).
+constexpr int CCSD_RING_PREP_MAX_O = 32;
+inline bool ccsd_ring_prep_shape_ok(int64_t o, int64_t v) { return o >= 1 && o <= CCSD_RING_PREP_MAX_O && v >= 1 && v <= 4096; }
+int dev_ccsd_ring_prep(int64_t o, int64_t v, const double* t1, const double* P1, const double* W1base, const double* W2base, const double* ZB, const double* ZC,
+                       const double* OB, const double* OC, double* R, double* W2);
+// The rank-n_occ update of U with its transposed addend in the same sweep (same units, same shape rule):
+//   U[i,j,a,b] = (U[i,j,a,b] + Z[i,a,b,j]) - sum_k A[i,j,k,a] t1[k,b]      (U: [o][o][v][v] in place; Z: [o][v][v][o] and A: [o][o][o][v], only read; k ascending from zero)
+int dev_ccsd_u_update(int64_t o, int64_t v, const double* A, const double* t1, const double* Z, double* U);
 // Batched small-K update (K = n_occ): C[z][m][n] += alpha sum_k A[z][k][m] B[z][k][n]   (A: [K][M] per batch, stride sA; B: [K][N] per batch,
 // stride sB; a stride of 0 shares the operand; C: [M][N] per batch, stride sC).  One pass over C -- these products are HBM bound, a
 // tiled GEMM with two k-steps is not.

@@ -177,7 +177,15 @@ int qemb_frag_solve_mp2_batch(int nfrag, const qemb_frag_t* frags, const int* ns
  * mean-field results.
  * Limits: n > 16 is QEMB_ERR_UNSUPPORTED naming n.  Before anything is allocated the working set -- D and G (2 x 8 n^2 N_det bytes), (2 max_space + 4) vectors of
  * N_det, the tables and the n^4 pieces; qemb_frag_fci_bytes reports it -- is compared with min(free device memory, the limit of qemb_frag_fci_mem_limit):
- * QEMB_ERR_ALLOC naming n, nsocc and N_det.  In practice n <= 14 (7 alpha, 7 beta: 11.8 M determinants, 18.5 GB each for D and G).
+ * QEMB_ERR_ALLOC naming n, nsocc and N_det.  Without slabs that is n <= 14 (7 alpha, 7 beta: 11.8 M determinants, 18.5 GB each for D and G); in slabs (15, 7) and
+ * (16, 8) -- 165.6 M determinants -- run under a limit of 140 GB.
+ * qemb_frag_fci_slab: D and G -- all but (2 max_space + 4) vectors of the working set -- in slabs of `rows` alpha strings (all beta strings: rows * ns determinant
+ *   columns), one application of H and the RDM build walking the ceil(ns / rows) slabs in ascending order.  rows = 0 (the default): off, the path and the guard
+ *   above, bit for bit.  rows = k > 0: the slab kernels with k rows (k >= ns: one slab); for one k two calls return the same bits, between different k and against
+ *   rows = 0 the results agree to rounding.  rows = -1: unslabbed when that fits min(free, limit), else the largest rows that does.  Any other negative value:
+ *   QEMB_ERR_ARG.  The guard of a slabbed solve compares qemb_frag_fci_bytes_slab (qemb_frag_fci_bytes with D and G at 2 x 8 n^2 min(rows, ns) ns bytes; rows = 0:
+ *   the whole space) with the same room: QEMB_ERR_ALLOC naming n, nsocc, N_det, rows and the slab count.  qemb_frag_rdm2(QEMB_RDM2_FCI) follows the setting with
+ *   its own limit.  qemb_frag_fci_slab_used: rows and slab count of the last FCI solve or FCI 2-RDM call of the fragment (unslabbed: rows 0, n_slab 1).
  * qemb_frag_fci_residual: ||H c - E c||_2 of the last FCI solve of the fragment. */
 typedef struct {
   uint32_t struct_size;      /* sizeof(qemb_fci_opts); set by qemb_default_fci_opts, checked by every entry point that takes the struct */
@@ -192,6 +200,9 @@ int qemb_frag_solve_fci(qemb_frag_t f, int nsocc, const double* h, const double*
                         double* ebe_hf, int* n_iter, int* scf_cycles);
 int qemb_frag_fci_bytes(int n, int nsocc, int max_space, int64_t* bytes);
 int qemb_frag_fci_mem_limit(qemb_frag_t f, int64_t bytes);
+int qemb_frag_fci_slab(qemb_frag_t f, int64_t rows);
+int qemb_frag_fci_bytes_slab(int n, int nsocc, int max_space, int64_t rows, int64_t* bytes);
+int qemb_frag_fci_slab_used(qemb_frag_t f, int64_t* rows, int64_t* n_slab);
 int qemb_frag_fci_residual(qemb_frag_t f, double* residual);
 /* solver == "SCI-hip": the selected-CI branch of be_func (molbe/solver.py:412-462, SHCI_ArgsUser(hci_cutoff)) as a heat-bath selection on the device, for fragments
  * beyond the determinant-space limit of qemb_frag_solve_fci (n <= 64).  Fragment RHF, h1 and the ERIs in the fragment-MO basis as for FCI; then, from the HF

@@ -293,6 +293,9 @@ int qemb_op_fci_sigma(int n, int nsocc, const double* h_host, const double* V_de
 int qemb_op_fci_rdm12(int n, int nsocc, const double* c_dev, int cumulant, double* dm1_host, double* dm2_dev);
 /* measurement hook (tools/fci_bench.py): one untimed application of H, then one whose three steps are bracketed by device timers; ms3 = D gather, G = V D, sigma gather */
 int qemb_op_fci_sigma_timed(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev, double* ms3);
+/* the same two operations in slabs of `rows` > 0 alpha rows (qemb_frag_fci_slab; rows >= ns: one slab); ms3 nullable: the three steps timed, summed over the slabs */
+int qemb_op_fci_sigma_slab(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev, int64_t rows, double* ms3);
+int qemb_op_fci_rdm12_slab(int n, int nsocc, const double* c_dev, int cumulant, int64_t rows, double* dm1_host, double* dm2_dev);
 int qemb_op_fci_links(int n, int nsocc, int64_t* ns, int* nlink, int32_t* strings_host, int32_t* links_host);
 /* ---- selected CI (csrc/sci.cpp, kernels csrc/sci_ops.hip): the operations behind qemb_frag_solve_sci on handed-in data.  A space is ndet keys alpha[k], beta[k]
  * (64-bit occupation words, bit p = orbital p occupied) sorted by (alpha, beta); every array but V_dev ([n^2][n^2] = (pq|rs)) is a host array.

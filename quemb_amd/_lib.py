@@ -210,6 +210,11 @@ def _declare(lib):
     f("qemb_frag_fci_bytes", I, I, I, I, C.POINTER(L))
     f("qemb_frag_fci_mem_limit", I, V, L)
     f("qemb_frag_fci_residual", I, V, DP)
+    f("qemb_frag_fci_slab", I, V, L)
+    f("qemb_frag_fci_bytes_slab", I, I, I, I, L, C.POINTER(L))
+    f("qemb_frag_fci_slab_used", I, V, C.POINTER(L), C.POINTER(L))
+    f("qemb_op_fci_sigma_slab", I, I, I, P, P, P, P, L, P)
+    f("qemb_op_fci_rdm12_slab", I, I, I, P, I, L, P, P)
     f("qemb_op_fci_sigma", I, I, I, P, P, P, P)
     f("qemb_op_fci_rdm12", I, I, I, P, I, P, P)
     f("qemb_op_fci_sigma_timed", I, I, I, P, P, P, P, P)

@@ -616,6 +616,14 @@ int qemb_frag_fci_bytes(int n, int nsocc, int max_space, int64_t* bytes) {
   *bytes = fci_bytes(n, nsocc, max_space);
   return QEMB_OK;
 }
+int qemb_frag_fci_bytes_slab(int n, int nsocc, int max_space, int64_t rows, int64_t* bytes) {
+  if (n <= 0 || nsocc <= 0 || nsocc > n || max_space < 2 || rows < 0 || !bytes) { set_error("qemb_frag_fci_bytes_slab: bad arguments"); return QEMB_ERR_ARG; }
+  if (n > kFciMaxOrb) { set_error("qemb_frag_fci_bytes_slab: n = " + std::to_string(n) + " embedding orbitals; the determinant-space solver takes at most " + std::to_string(kFciMaxOrb)); return QEMB_ERR_UNSUPPORTED; }
+  *bytes = fci_bytes_slab(n, nsocc, max_space, rows);
+  return QEMB_OK;
+}
+int qemb_frag_fci_slab(qemb_frag_t f, int64_t rows) { CHECK_FRAG(f); return FRAG(f)->set_fci_slab(rows); }
+int qemb_frag_fci_slab_used(qemb_frag_t f, int64_t* rows, int64_t* n_slab) { CHECK_FRAG(f); FRAG(f)->fci_slab_used(rows, n_slab); return QEMB_OK; }
 int qemb_frag_fci_mem_limit(qemb_frag_t f, int64_t bytes) { CHECK_FRAG(f); FRAG(f)->set_fci_mem_limit(bytes); return QEMB_OK; }
 int qemb_frag_fci_residual(qemb_frag_t f, double* residual) { CHECK_FRAG(f); if (residual) *residual = FRAG(f)->fci_residual(); return QEMB_OK; }
 int qemb_op_fci_links(int n, int nsocc, int64_t* ns, int* nlink, int32_t* strings_host, int32_t* links_host) {
@@ -661,6 +669,40 @@ int qemb_op_fci_sigma_timed(int n, int nsocc, const double* h_host, const double
   { TimerScope t(slot[2]); QTRY(dev_fci_sigma(n, T->ns, T->nlink, T->links_dev, kd, D, G, sigma_dev)); QTRY(t.close()); }
   for (int k = 0; k < 3; ++k) { int64_t cnt = 0; QTRY(dev_timer_read(slot[k], &ms3[k], &cnt)); }
   return QEMB_OK;
+}
+// sigma = H c in slabs of `rows` alpha rows (fci_apply); ms3 (nullable): after one untimed application, one whose three steps are bracketed by device timers,
+// summed over the slabs -- the slabbed counterpart of qemb_op_fci_sigma_timed
+int qemb_op_fci_sigma_slab(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev, int64_t rows, double* ms3) {
+  if (!h_host || !V_dev || !c_dev || !sigma_dev) { set_error("qemb_op_fci_sigma_slab: null argument"); return QEMB_ERR_ARG; }
+  if (rows <= 0) { set_error("qemb_op_fci_sigma_slab: rows must be positive"); return QEMB_ERR_ARG; }
+  const FciTables* T = nullptr;
+  QTRY(fci_tables(n, nsocc, &T));
+  const int64_t n2 = (int64_t)n * n, ns = T->ns, R = std::min(rows, ns);
+  std::vector<double> Vh((size_t)(n2 * n2)), kh((size_t)n2);
+  QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
+  fci_one_body(n, h_host, Vh.data(), kh.data());
+  DBuf kd, D, G;
+  QTRY(kd.alloc(n2)); QTRY(D.alloc(n2 * R * ns)); QTRY(G.alloc(n2 * R * ns));
+  QTRY(dev_h2d(kd, kh.data(), sizeof(double) * n2));
+  QTRY(fci_apply(*T, kd, V_dev, c_dev, D, G, sigma_dev, R));
+  if (!ms3) return dev_sync();
+  const int slot[3] = {10, 11, 12};
+  for (int s : slot) QTRY(dev_timer_reset(s));
+  for (int64_t a0 = 0; a0 < ns; a0 += R) {
+    const int64_t a1 = std::min(ns, a0 + R), Ns = (a1 - a0) * ns;
+    { TimerScope t(slot[0]); QTRY(dev_fci_gather_slab(n, ns, T->nlink, T->links_dev, c_dev, a0, a1, D)); QTRY(t.close()); }
+    { TimerScope t(slot[1]); QTRY(gemm(n2, Ns, n2, 1.0, V_dev, n2, true, D, Ns, false, 0.0, G, Ns)); QTRY(t.close()); }
+    { TimerScope t(slot[2]); QTRY(dev_fci_sigma_slab(n, ns, T->nlink, T->links_dev, kd, a0, a1, D, G, sigma_dev)); QTRY(t.close()); }
+  }
+  for (int k = 0; k < 3; ++k) { int64_t cnt = 0; QTRY(dev_timer_read(slot[k], &ms3[k], &cnt)); }
+  return QEMB_OK;
+}
+int qemb_op_fci_rdm12_slab(int n, int nsocc, const double* c_dev, int cumulant, int64_t rows, double* dm1_host, double* dm2_dev) {
+  if (!c_dev || !dm1_host) { set_error("qemb_op_fci_rdm12_slab: null argument"); return QEMB_ERR_ARG; }
+  if (rows <= 0) { set_error("qemb_op_fci_rdm12_slab: rows must be positive"); return QEMB_ERR_ARG; }
+  const FciTables* T = nullptr;
+  QTRY(fci_tables(n, nsocc, &T));
+  return fci_rdm12(*T, c_dev, cumulant ? nsocc : -1, dm1_host, dm2_dev, rows);
 }
 int qemb_op_fci_rdm12(int n, int nsocc, const double* c_dev, int cumulant, double* dm1_host, double* dm2_dev) {
   if (!c_dev || !dm1_host) { set_error("qemb_op_fci_rdm12: null argument"); return QEMB_ERR_ARG; }

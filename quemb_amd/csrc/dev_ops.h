@@ -441,6 +441,16 @@ inline int fci_check_args(const char* who, int n, int64_t ns, int nlink, const v
 }
 int dev_fci_gather(int n, int64_t ns, int nlink, const int32_t* links, const double* c, double* D);
 int dev_fci_sigma(int n, int64_t ns, int nlink, const int32_t* links, const double* k, const double* D, const double* G, double* sigma);
+// The two passes over a slab of alpha rows [a0, a1), all beta strings (Ns = (a1 - a0) ns determinants, contiguous in c): what lets n = 15, 16 fit (fci_apply)
+//   gather_slab: Ds[pq * Ns + I - a0 ns] = the column of D of every determinant I of the slab, from the whole vector c
+//   sigma_slab:  for every I of the whole space, sigma[I] (=, when a0 == 0; += otherwise) the one-body term when I lies in the slab plus 1/2 sum of
+//                +-Gs[pq * Ns + J - a0 ns] over the links (pq, J) of I with J in the slab  (Gs = V Ds); slabs in ascending order give sigma = H c
+inline int fci_check_slab(const char* who, int64_t ns, int64_t a0, int64_t a1) {
+  if (a0 < 0 || a1 <= a0 || a1 > ns) { set_error(std::string(who) + ": bad slab [" + std::to_string(a0) + ", " + std::to_string(a1) + ") of " + std::to_string(ns) + " alpha rows"); return QEMB_ERR_ARG; }
+  return 0;
+}
+int dev_fci_gather_slab(int n, int64_t ns, int nlink, const int32_t* links, const double* c, int64_t a0, int64_t a1, double* Ds);
+int dev_fci_sigma_slab(int n, int64_t ns, int nlink, const int32_t* links, const double* k, int64_t a0, int64_t a1, const double* Ds, const double* Gs, double* sigma);
 int dev_fci_diag(int n, int64_t ns, const int32_t* strings, const double* h, const double* V, double* hdiag);
 int dev_fci_precond(int64_t N, const double* r, const double* hdiag, double theta, double* out);
 int dev_fci_dm2(int n, int o_cum, const double* A, const double* dm1, double* out);

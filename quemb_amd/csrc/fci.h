@@ -31,17 +31,25 @@ int fci_tables(int n, int nsocc, const FciTables** out);
 int64_t fci_string_count(int n, int nsocc);
 // device bytes of a solve: D and G (2 x 8 n^2 N_det), the Davidson basis, its images and four work vectors ((2 max_space + 4) x 8 N_det), the tables and the n^4 pieces
 int64_t fci_bytes(int n, int nsocc, int max_space);
+// Slabs: D and G hold the columns of `rows` alpha strings at a time (all beta strings: rows * ns determinants, contiguous in c), and one application of H, or
+// one RDM build, walks the ceil(ns / rows) slabs in ascending order.  rows <= 0 (and rows >= ns in the byte count) is the whole space.
+//   fci_bytes_slab: fci_bytes with D and G at 2 x 8 n^2 min(rows, ns) ns;  fci_slab_count: ceil(ns / rows), 1 when rows <= 0
+//   fci_rows_that_fit: the largest rows <= ns whose fci_bytes_slab is at most `room` bytes; 0 when not even one row fits
+int64_t fci_bytes_slab(int n, int nsocc, int max_space, int64_t rows);
+int64_t fci_slab_count(int64_t ns, int64_t rows);
+int64_t fci_rows_that_fit(int n, int nsocc, int max_space, double room);
 
 // k_pq = h_pq - 1/2 sum_r (pr|rq) on the host (h, V: [n][n] and [n^2][n^2] host arrays)
 void fci_one_body(int n, const double* h, const double* V, double* k);
 
-// one application of H: sigma = H c.  k_dev [n^2], V_dev [n^2][n^2]; D, G: n^2 N_det doubles of work space each
-int fci_apply(const FciTables& T, const double* k_dev, const double* V_dev, const double* c, double* D, double* G, double* sigma);
+// one application of H: sigma = H c.  k_dev [n^2], V_dev [n^2][n^2]; D, G: n^2 N_det doubles of work space each.  rows > 0: in slabs of that many alpha rows
+// through the slab kernels (rows >= ns: one slab), D and G n^2 min(rows, ns) ns doubles each; for a given rows two calls give the same bits
+int fci_apply(const FciTables& T, const double* k_dev, const double* V_dev, const double* c, double* D, double* G, double* sigma, int64_t rows = 0);
 
 struct FciResult { double e = 0.0, residual = 0.0; int n_iter = 0; bool converged = false; };
 // lowest state of the M_s = 0 space of H(h, V) with nelec = (nsocc, nsocc); c (N_det doubles, device) receives the normalised vector, largest-magnitude component
-// positive.  h_host: [n][n]; V_dev: [n^2][n^2] on the device.
-int fci_davidson(const FciTables& T, const double* h_host, const double* V_dev, const FciOptions& opt, double* c, FciResult* res);
+// positive.  h_host: [n][n]; V_dev: [n^2][n^2] on the device.  rows: the slab height of every application of H (0: none); the working set is fci_bytes_slab.
+int fci_davidson(const FciTables& T, const double* h_host, const double* V_dev, const FciOptions& opt, double* c, FciResult* res, int64_t rows = 0);
 
 // the host side of the Davidson iteration, shared with sci.cpp: the small symmetric eigenproblem (cyclic Jacobi; A [m][m] is overwritten, w ascending, eigenvectors
 // in the columns of V), host[j] = <x, ys[j]> and out = sum_j coef[j] xs[j] (+ out) eight vectors per pass (scratch: >= 8 doubles on the device)
@@ -51,7 +59,8 @@ int dots(int64_t N, const double* x, const std::vector<const double*>& ys, doubl
 int combine(int64_t N, const std::vector<double>& coef, const std::vector<const double*>& xs, bool accumulate, double* out);
 }  // namespace fci_detail
 
-// dm1[p,q] = sum_I c_I D[pq][I] (host, symmetrised) and, when dm2_dev != null, dm2[p,q,r,s] = <p+ r+ s q> (n^4 doubles, device); o_cum >= 0: minus the mean-field part
-int fci_rdm12(const FciTables& T, const double* c, int o_cum, double* dm1_host, double* dm2_dev);
+// dm1[p,q] = sum_I c_I D[pq][I] (host, symmetrised) and, when dm2_dev != null, dm2[p,q,r,s] = <p+ r+ s q> (n^4 doubles, device); o_cum >= 0: minus the mean-field part.
+// rows > 0: slab by slab (dm1 += D_s c_s, A += D_s D_s^T), D at n^2 min(rows, ns) ns doubles
+int fci_rdm12(const FciTables& T, const double* c, int o_cum, double* dm1_host, double* dm2_dev, int64_t rows = 0);
 
 }  // namespace qemb

@@ -55,6 +55,66 @@ __global__ void __launch_bounds__(256) fci_sigma_kernel(int n, long long ns, int
   sigma[I] = one + 0.5 * two;
 }
 
+// The same two passes over a slab of alpha rows [a0, a1) (all beta strings: the determinants a0 ns <= I < a1 ns, contiguous in c[Ia][Ib]); Ns = (a1 - a0) ns columns.
+// gather: D_s[pq][I - a0 ns] for the determinants of the slab from the whole vector c -- the owner, the stores and the order of additions of fci_gather_kernel.
+__global__ void __launch_bounds__(256) fci_gather_slab_kernel(int n, long long ns, int nlink, const int* __restrict__ links, const double* __restrict__ c,
+                                                              long long a0, long long a1, double* Ds) {
+  const long long Ns = (a1 - a0) * ns;
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;      // the column of D_s
+  if (t >= Ns) return;
+  const long long Ia = a0 + t / ns, Ib = t - (Ia - a0) * ns;
+  const int n2 = n * n;
+  for (int pq = 0; pq < n2; ++pq) Ds[(long long)pq * Ns + t] = 0.0;
+  for (int l = 0; l < nlink; ++l) {
+    const int w = links[(long long)l * ns + Ia];
+    const double x = c[(long long)(w >> 9) * ns + Ib];
+    Ds[(long long)((w >> 1) & 255) * Ns + t] = (w & 1) ? -x : x;
+  }
+  for (int l = 0; l < nlink; ++l) {
+    const int w = links[(long long)l * ns + Ib];
+    const double x = c[Ia * ns + (w >> 9)];
+    double* d = Ds + (long long)((w >> 1) & 255) * Ns + t;
+    *d += (w & 1) ? -x : x;
+  }
+}
+
+// sigma: every determinant I of the WHOLE space takes what the slab holds for it -- the one-body term when I lies in the slab, and 1/2 G_s[pq][J - a0 ns] over
+// those links (pq, J) of I whose J lies in the slab: an alpha link when a0 <= Ja < a1, a beta link (Ja = Ia) when I's own row is in range.  Still a gather: one
+// thread per I, no atomics; the slab at a0 = 0 starts sigma, every later one adds to it, so ascending slabs give one fixed order of additions per slab height.
+// Ib is the fast thread index: Ia, the words links[l ns + Ia] and both range tests are uniform over the threads of a row, so a wave (but for the one that straddles
+// two rows) takes each branch whole, and the alpha reads of G_s stay contiguous.  Outside the slab's rows a thread reads its nlink alpha words and the few G_s rows
+// they select: the link table is rescanned once per slab.
+__global__ void __launch_bounds__(256) fci_sigma_slab_kernel(int n, long long ns, int nlink, const int* __restrict__ links, const double* __restrict__ k,
+                                                             long long a0, long long a1, const double* __restrict__ Ds, const double* __restrict__ Gs, double* sigma) {
+  const long long N = ns * ns, Ns = (a1 - a0) * ns;
+  const long long I = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (I >= N) return;
+  const long long Ia = I / ns, Ib = I - Ia * ns;
+  const bool mine = Ia >= a0 && Ia < a1;
+  const int n2 = n * n;
+  double one = 0.0, two = 0.0;
+  if (mine) {
+    const long long t = I - a0 * ns;
+    for (int pq = 0; pq < n2; ++pq) one += k[pq] * Ds[(long long)pq * Ns + t];
+  }
+  for (int l = 0; l < nlink; ++l) {
+    const int w = links[(long long)l * ns + Ia];
+    const long long Ja = w >> 9;
+    if (Ja < a0 || Ja >= a1) continue;
+    const double x = Gs[(long long)((w >> 1) & 255) * Ns + (Ja - a0) * ns + Ib];
+    two += (w & 1) ? -x : x;
+  }
+  if (mine) {
+    for (int l = 0; l < nlink; ++l) {
+      const int w = links[(long long)l * ns + Ib];
+      const double x = Gs[(long long)((w >> 1) & 255) * Ns + (Ia - a0) * ns + (w >> 9)];
+      two += (w & 1) ? -x : x;
+    }
+  }
+  const double add = one + 0.5 * two;
+  sigma[I] = a0 == 0 ? add : sigma[I] + add;
+}
+
 // H_II from the occupations: sum_i (na_i + nb_i) h_ii + 1/2 sum_ij [(na_i na_j + nb_i nb_j)(J_ij - K_ij) + 2 na_i nb_j J_ij], J_ij = (ii|jj), K_ij = (ij|ji)
 __global__ void __launch_bounds__(256) fci_diag_kernel(int n, long long ns, const int* __restrict__ strings, const double* __restrict__ h, const double* __restrict__ V,
                                                        double* __restrict__ hdiag) {
@@ -126,6 +186,23 @@ int dev_fci_sigma(int n, int64_t ns, int nlink, const int32_t* links, const doub
   if (int rc = fci_check_args("dev_fci_sigma", n, ns, nlink, links, D, sigma)) return rc;
   if (!k || !G) { set_error("dev_fci_sigma: bad arguments"); return QEMB_ERR_ARG; }
   return launch("dev_fci_sigma", fci_sigma_kernel, dim3(det_grid(ns * ns)), dim3(256), 0, st, n, ns, nlink, links, k, D, G, sigma);
+}
+
+int dev_fci_gather_slab(int n, int64_t ns, int nlink, const int32_t* links, const double* c, int64_t a0, int64_t a1, double* Ds) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (int rc = fci_check_args("dev_fci_gather_slab", n, ns, nlink, links, c, Ds)) return rc;
+  if (int rc = fci_check_slab("dev_fci_gather_slab", ns, a0, a1)) return rc;
+  return launch("dev_fci_gather_slab", fci_gather_slab_kernel, dim3(det_grid((a1 - a0) * ns)), dim3(256), 0, st, n, ns, nlink, links, c, a0, a1, Ds);
+}
+
+int dev_fci_sigma_slab(int n, int64_t ns, int nlink, const int32_t* links, const double* k, int64_t a0, int64_t a1, const double* Ds, const double* Gs, double* sigma) {
+  hipStream_t st = hip_stream();
+  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
+  if (int rc = fci_check_args("dev_fci_sigma_slab", n, ns, nlink, links, Ds, sigma)) return rc;
+  if (int rc = fci_check_slab("dev_fci_sigma_slab", ns, a0, a1)) return rc;
+  if (!k || !Gs) { set_error("dev_fci_sigma_slab: bad arguments"); return QEMB_ERR_ARG; }
+  return launch("dev_fci_sigma_slab", fci_sigma_slab_kernel, dim3(det_grid(ns * ns)), dim3(256), 0, st, n, ns, nlink, links, k, a0, a1, Ds, Gs, sigma);
 }
 
 int dev_fci_diag(int n, int64_t ns, const int32_t* strings, const double* h, const double* V, double* hdiag) {

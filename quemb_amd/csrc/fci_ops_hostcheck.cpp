@@ -41,6 +41,38 @@ int dev_fci_sigma(int n, int64_t ns, int nlink, const int32_t* links, const doub
   return 0;
 }
 
+int dev_fci_gather_slab(int n, int64_t ns, int nlink, const int32_t* links, const double* c, int64_t a0, int64_t a1, double* Ds) {
+  if (int rc = fci_check_args("dev_fci_gather_slab", n, ns, nlink, links, c, Ds)) return rc;
+  if (int rc = fci_check_slab("dev_fci_gather_slab", ns, a0, a1)) return rc;
+  const int64_t Ns = (a1 - a0) * ns, n2 = (int64_t)n * n;
+  for (int64_t k = 0; k < n2 * Ns; ++k) Ds[k] = 0.0;
+  for (int l = 0; l < nlink; ++l) for (int64_t I = 0; I < ns; ++I) {
+    const int32_t w = links[(int64_t)l * ns + I];
+    const int64_t J = w >> 9, pq = (w >> 1) & 255;
+    const double sg = (w & 1) ? -1.0 : 1.0;
+    if (I >= a0 && I < a1) for (int64_t K = 0; K < ns; ++K) Ds[pq * Ns + (I - a0) * ns + K] += sg * c[J * ns + K];      // alpha: the link's own string is the row
+    for (int64_t K = a0; K < a1; ++K) Ds[pq * Ns + (K - a0) * ns + I] += sg * c[K * ns + J];                              // beta: every row of the slab
+  }
+  return 0;
+}
+
+int dev_fci_sigma_slab(int n, int64_t ns, int nlink, const int32_t* links, const double* k, int64_t a0, int64_t a1, const double* Ds, const double* Gs, double* sigma) {
+  if (int rc = fci_check_args("dev_fci_sigma_slab", n, ns, nlink, links, Ds, sigma)) return rc;
+  if (int rc = fci_check_slab("dev_fci_sigma_slab", ns, a0, a1)) return rc;
+  if (!k || !Gs) { set_error("dev_fci_sigma_slab: bad arguments"); return QEMB_ERR_ARG; }
+  const int64_t N = ns * ns, Ns = (a1 - a0) * ns, n2 = (int64_t)n * n;
+  if (a0 == 0) for (int64_t I = 0; I < N; ++I) sigma[I] = 0.0;
+  for (int64_t pq = 0; pq < n2; ++pq) for (int64_t t = 0; t < Ns; ++t) sigma[a0 * ns + t] += k[pq] * Ds[pq * Ns + t];
+  for (int l = 0; l < nlink; ++l) for (int64_t I = 0; I < ns; ++I) {
+    const int32_t w = links[(int64_t)l * ns + I];
+    const int64_t J = w >> 9, pq = (w >> 1) & 255;
+    const double sg = (w & 1) ? -0.5 : 0.5;
+    if (J >= a0 && J < a1) for (int64_t K = 0; K < ns; ++K) sigma[I * ns + K] += sg * Gs[pq * Ns + (J - a0) * ns + K];      // alpha: the source row lies in the slab
+    for (int64_t K = a0; K < a1; ++K) sigma[K * ns + I] += sg * Gs[pq * Ns + (K - a0) * ns + J];                             // beta: the row is its own source row
+  }
+  return 0;
+}
+
 int dev_fci_diag(int n, int64_t ns, const int32_t* strings, const double* h, const double* V, double* hdiag) {
   if (int rc = fci_check_args("dev_fci_diag", n, ns, 1, strings, h, hdiag)) return rc;
   if (!V) { set_error("dev_fci_diag: bad arguments"); return QEMB_ERR_ARG; }

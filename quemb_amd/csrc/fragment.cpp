@@ -868,6 +868,7 @@ int Fragment::solve_fci(int o, const double* h, const double* dm0, const Fragmen
   if (n > kFciMaxOrb) { set_error("Fragment::solve_fci: n = " + std::to_string(n) + " embedding orbitals; the determinant-space solver takes at most " + std::to_string(kFciMaxOrb)); return QEMB_ERR_UNSUPPORTED; }
   if (o <= 0 || o > n) { set_error("Fragment: need 0 < nsocc <= n"); return QEMB_ERR_ARG; }
   QTRY(check_energy_data(eeval));      // (solve_begin_scf has the check for every solver; here it also keeps its place before the guard)
+  int64_t rows = 0;      // the slab height this solve runs with (0: unslabbed), settled by the guard
   {      // the guard: D, G, the Davidson vectors, the tables and the n^4 pieces against what is free (or the fragment's limit), before anything is allocated
     size_t free_b = 0, total_b = 0;
     QTRY(dev_mem_info(&free_b, &total_b));
@@ -875,7 +876,17 @@ int Fragment::solve_fci(int o, const double* h, const double* dm0, const Fragmen
     if (fci_mem_limit_ >= 0 && (double)fci_mem_limit_ < room) room = (double)fci_mem_limit_;
     const int64_t ns = fci_string_count(n, o);
     const double need = (double)fci_bytes(n, o, fopt.max_space);
-    if (v > 0 && need > room) {
+    if (v > 0 && fci_slab_ != 0 && !(fci_slab_ < 0 && need <= room)) {      // a slabbed solve: its own figure against the same room
+      rows = fci_slab_ > 0 ? std::min(fci_slab_, ns) : fci_rows_that_fit(n, o, fopt.max_space, room);
+      const int64_t r1 = rows > 0 ? rows : 1;
+      const double need_s = (double)fci_bytes_slab(n, o, fopt.max_space, r1);
+      if (need_s > room) {
+        set_error("Fragment::solve_fci: n = " + std::to_string(n) + ", nsocc = " + std::to_string(o) + " gives N_det = " + std::to_string(ns * ns) + " determinants; with rows = " +
+                  std::to_string(r1) + " alpha rows of D and G at a time (" + std::to_string(fci_slab_count(ns, r1)) + " slabs) the working set is " + std::to_string(need_s * 1e-9) +
+                  " GB, more than the " + std::to_string(room * 1e-9) + " GB of device memory it may take");
+        return QEMB_ERR_ALLOC;
+      }
+    } else if (v > 0 && need > room) {
       set_error("Fragment::solve_fci: n = " + std::to_string(n) + ", nsocc = " + std::to_string(o) + " gives N_det = " + std::to_string(ns * ns) + " determinants and a working set of " +
                 std::to_string(need * 1e-9) + " GB, more than the " + std::to_string(room * 1e-9) + " GB of device memory it may take");
       return QEMB_ERR_ALLOC;
@@ -887,6 +898,7 @@ int Fragment::solve_fci(int o, const double* h, const double* dm0, const Fragmen
   bool unconverged = sp_.unconverged;
   mean_field_result(res);
   fci_c_.release(); fci_residual_ = 0.0;
+  fci_rows_used_ = rows; fci_nslab_used_ = fci_slab_count(fci_string_count(n, o), rows);
   std::vector<double> dm((size_t)n2, 0.0), e2((size_t)nf_, 0.0);
   if (v > 0) {
     const FciTables* T = nullptr;
@@ -899,7 +911,7 @@ int Fragment::solve_fci(int o, const double* h, const double* dm0, const Fragmen
     for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int nu = 0; nu < n; ++nu) s += tmp[(size_t)p * n + nu] * C[(size_t)nu * n + q]; hmo[(size_t)p * n + q] = s; }
     QTRY(fci_c_.alloc(N));
     FciResult fr;
-    QTRY(fci_davidson(*T, hmo.data(), Vmo, fopt, fci_c_, &fr));
+    QTRY(fci_davidson(*T, hmo.data(), Vmo, fopt, fci_c_, &fr, rows));
     res->n_iter = fr.n_iter; res->ccsd_converged = fr.converged; fci_residual_ = fr.residual;
     res->e_corr_mo = fr.e - res->e_scf;
     if (!fr.converged) {
@@ -910,7 +922,7 @@ int Fragment::solve_fci(int o, const double* h, const double* dm0, const Fragmen
     if (civec) QTRY(dev_d2h(civec, fci_c_, sizeof(double) * N));
     DBuf G2;
     if (eeval) QTRY(G2.alloc(n2 * n2));
-    QTRY(fci_rdm12(*T, fci_c_, o, dm.data(), eeval ? G2.p : nullptr));
+    QTRY(fci_rdm12(*T, fci_c_, o, dm.data(), eeval ? G2.p : nullptr, rows));
     if (eeval && nf_ > 0) QTRY(fci_e2_sites(CC, G2, Vao, e2));
   } else {      // a single determinant: the mean-field results, as the other solvers
     for (int i = 0; i < n; ++i) dm[(size_t)i * n + i] = 2.0;
@@ -1009,14 +1021,14 @@ int Fragment::sci_dets(uint64_t* alpha, uint64_t* beta, double* c) const {
 // ---- Frags.rdm2__ (molbe/solver.py:528): the n^4 tensor of the last solve, written once by one kernel (rdm2_ops.hip)
 // Device bytes of one call: the tensor, the 1-RDM, and for MP2 what forming t2 again takes -- ovov, t2, G and the larger of the two integral routes' work space
 // (factor: the unpacked factor, its half-rotated virtual columns and Lov, mp2.cpp; block: the two buffers of mo_transform and the ovov block it leaves).
-int64_t Fragment::rdm2_bytes(int kind, int o, int with_dm1) const {
+int64_t Fragment::rdm2_bytes(int kind, int o, int with_dm1, int64_t fci_rows) const {
   const int64_t n = n_, v = n - o, n2 = n * n, ov2 = (int64_t)o * v * o * v;
   int64_t words = n2 * n2 + (with_dm1 ? n2 : 0);
   // the tensor and the 1-RDM (sci_rdm12) and the pattern of the matrix, formed again from the resident keys: row pointers, counts, run offsets and 4 bytes per stored element
   if (kind == QEMB_RDM2_SCI) return 8 * (n2 * n2 + 2 * n2) + 20 * sci_V_.N + 4 * sci_res_.nnz;
-  if (kind == QEMB_RDM2_FCI) {      // the tensor, A = D D^T, the 1-RDM and D itself (fci_rdm12)
+  if (kind == QEMB_RDM2_FCI) {      // the tensor, A = D D^T, the 1-RDM and D itself, or fci_rows alpha rows of it (fci_rdm12)
     const int64_t ns = fci_string_count(n_, o);
-    return 8 * (2 * n2 * n2 + n2 + (v > 0 ? n2 * ns * ns : 0));
+    return 8 * (2 * n2 * n2 + n2 + (v > 0 ? n2 * (fci_rows > 0 && fci_rows < ns ? fci_rows : ns) * ns : 0));
   }
   if (kind == QEMB_RDM2_MP2 && v > 0) {
     const int64_t factor = (int64_t)df_naux_ * (n2 + n * v + (int64_t)o * v), block = 2 * mo_transform_work(n_) + ov2;
@@ -1036,10 +1048,17 @@ int Fragment::rdm2(int kind, int with_dm1, double* out, bool out_on_device) {
   QTRY(dev_mem_info(&free_b, &total_b));
   double room = (double)free_b;
   if (rdm2_mem_limit_ >= 0 && (double)rdm2_mem_limit_ < room) room = (double)rdm2_mem_limit_;
-  const int64_t need = rdm2_bytes(kind, o, with_dm1) - (out_on_device ? 8 * n2 * n2 : 0);
+  int64_t fci_rows = 0;      // the slab height of an FCI 2-RDM (set_fci_slab): given, or under -1 the largest that fits when the whole D does not
+  if (kind == QEMB_RDM2_FCI && v > 0 && fci_slab_ != 0) {
+    const int64_t ns = fci_string_count(n, o), per_row = 8 * n2 * ns;
+    const int64_t whole = rdm2_bytes(kind, o, with_dm1) - (out_on_device ? 8 * n2 * n2 : 0);
+    if (fci_slab_ > 0) fci_rows = std::min(fci_slab_, ns);
+    else if ((double)whole > room) fci_rows = std::max<int64_t>(1, std::min<int64_t>(ns, (int64_t)std::floor((room - (double)(whole - per_row * ns)) / (double)per_row)));
+  }
+  const int64_t need = rdm2_bytes(kind, o, with_dm1, fci_rows) - (out_on_device ? 8 * n2 * n2 : 0);
   if ((double)need > room) {
     set_error("Fragment::rdm2: the 2-RDM of a fragment with n = " + std::to_string(n) + " takes " + std::to_string((double)n2 * (double)n2 * 8e-9) + " GB and " +
-              std::to_string((double)(rdm2_bytes(kind, o, with_dm1) - 8 * n2 * n2) * 1e-9) + " GB of workspace, more than the " + std::to_string(room * 1e-9) + " GB of device memory it may take");
+              std::to_string((double)(rdm2_bytes(kind, o, with_dm1, fci_rows) - 8 * n2 * n2) * 1e-9) + " GB of workspace, more than the " + std::to_string(room * 1e-9) + " GB of device memory it may take");
     return QEMB_ERR_ALLOC;
   }
   if (kind == QEMB_RDM2_FCI || kind == QEMB_RDM2_SCI) {      // make_rdm2 of the kept vector; with_dm1 = 0: minus the mean-field part (what rdm2__ holds with use_cumulant)
@@ -1061,7 +1080,8 @@ int Fragment::rdm2(int kind, int with_dm1, double* out, bool out_on_device) {
       const FciTables* T = nullptr;
       QTRY(fci_tables(n, o, &T));
       std::vector<double> d1((size_t)n2);
-      QTRY(fci_rdm12(*T, fci_c_, with_dm1 ? -1 : o, d1.data(), target));
+      fci_rows_used_ = fci_rows; fci_nslab_used_ = fci_slab_count(T->ns, fci_rows);
+      QTRY(fci_rdm12(*T, fci_c_, with_dm1 ? -1 : o, d1.data(), target, fci_rows));
     }
     return out_on_device ? dev_sync() : dev_d2h(out, R, sizeof(double) * n2 * n2);
   }

@@ -101,6 +101,11 @@ class Fragment {
   int solve_fci(int o, const double* h, const double* dm0, const FragmentOptions& opt, const FciOptions& fopt, int eeval, FragmentResult* res,
                 double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* civec);
   void set_fci_mem_limit(int64_t bytes) { fci_mem_limit_ = bytes; }
+  // The slab height of solve_fci and rdm2(QEMB_RDM2_FCI): 0 (default) the whole space in one piece -- the path and the guard above --, k > 0 the slab kernels with
+  // k alpha rows of D and G at a time (fci.h; k >= ns: one slab), -1 unslabbed when that fits the room, else the largest height that does.  The guard of a slabbed
+  // solve compares fci_bytes_slab with the same room.  fci_slab_used: what the last FCI solve or FCI 2-RDM call ran with (rows 0, one slab: unslabbed).
+  int set_fci_slab(int64_t rows) { if (rows < -1) { set_error("Fragment::set_fci_slab: rows = " + std::to_string(rows) + "; need 0 (off), a positive slab height or -1 (automatic)"); return QEMB_ERR_ARG; } fci_slab_ = rows; return 0; }
+  void fci_slab_used(int64_t* rows, int64_t* n_slab) const { if (rows) *rows = fci_rows_used_; if (n_slab) *n_slab = fci_nslab_used_; }
   // solver == "SCI-hip": the selected-CI branch of be_func (molbe/solver.py:412-462) as the heat-bath selection of sci.h on the integrals solve_fci forms, for
   // n <= 64; everything after the vector is the tail of solve_fci (make_rdm1, cumulant of the 2-RDM on the device, fci_e2_sites, finish_solve).  The guard compares
   // sci_bytes with the free device memory (or set_sci_mem_limit) before anything is allocated; the determinants and the vector stay on the device for a later
@@ -118,7 +123,7 @@ class Fragment {
   int rdm2(int kind, int with_dm1, double* out, bool out_on_device = false);
   // device bytes rdm2() may take (tensor + workspace); < 0: whatever is free
   void set_rdm2_mem_limit(int64_t bytes) { rdm2_mem_limit_ = bytes; }
-  int64_t rdm2_bytes(int kind, int o, int with_dm1) const;      // 8 n^4 + the workspace of the call
+  int64_t rdm2_bytes(int kind, int o, int with_dm1, int64_t fci_rows = 0) const;      // 8 n^4 + the workspace of the call (fci_rows > 0: D of an FCI 2-RDM in slabs of that height)
   // Bench hooks: set up the CCSD problem once (SCF + transform), then time single iterations.
   int prepare_ccsd(int o, const double* h, const double* dm0, const FragmentOptions& opt);
   int ccsd_iterate(int niter, double* e_corr, double* normt);
@@ -192,6 +197,7 @@ class Fragment {
   DBuf fci_c_;
   double fci_residual_ = 0.0;
   int64_t fci_mem_limit_ = -1;
+  int64_t fci_slab_ = 0, fci_rows_used_ = 0, fci_nslab_used_ = 1;
   int fci_mo_integrals(const std::vector<double>& C, DBuf& Vao, DBuf& CC, DBuf& Vmo);
   int fci_e2_sites(const double* CC, const double* G2, const double* Vao, std::vector<double>& e2);      // the cumulant contracted with the integrals, per fragment site
   // after an SCI solve: the sorted determinants with the vector (device, 24 bytes per determinant); rdm2() forms the pattern of the matrix over them again

@@ -210,6 +210,17 @@ class DeviceFragment:
         """device bytes `solve_fci` of this fragment may take (qemb_frag_fci_mem_limit); negative: whatever is free"""
         check(self.lib.qemb_frag_fci_mem_limit(self.h, int(nbytes)), "qemb_frag_fci_mem_limit", self.lib)
 
+    def set_fci_slab(self, rows):
+        """the slab height of `solve_fci` and of make_rdm2("FCI-hip") of this fragment (qemb_frag_fci_slab): 0 (default) off, k > 0 the work matrices D and G in
+        slabs of k alpha strings (k >= ns: one slab), -1 unslabbed when that fits the memory limit, else the largest height that does"""
+        check(self.lib.qemb_frag_fci_slab(self.h, int(rows)), "qemb_frag_fci_slab", self.lib)
+
+    def fci_slab_used(self):
+        """(rows, n_slab) of the last FCI solve or FCI 2-RDM call of this fragment (qemb_frag_fci_slab_used); unslabbed: (0, 1)"""
+        rows, n_slab = C.c_int64(), C.c_int64()
+        check(self.lib.qemb_frag_fci_slab_used(self.h, C.byref(rows), C.byref(n_slab)), "qemb_frag_fci_slab_used", self.lib)
+        return int(rows.value), int(n_slab.value)
+
     def make_rdm2(self, kind="CCSD", with_dm1=True):
         """Frags.rdm2__ (molbe/solver.py:528) of the last solve of this fragment in the fragment-MO basis, (n, n, n, n): qemb_frag_rdm2.
         kind="CCSD": make_rdm2_urlx(t1, t2, with_dm1) (shared/external/ccsd_rdm.py:23-55) from the amplitudes `solve` left on the device;
@@ -329,8 +340,9 @@ def rdm2_from_amplitudes(t1, t2, dm1=None, kind="CCSD", lib=None):
             b.free()
 
 
-def fci_sigma(h, V, c, nsocc, lib=None):
-    """sigma = H c of the determinant-space Hamiltonian (qemb_op_fci_sigma): h (n, n), V (n, n, n, n) = (pq|rs), c (ns, ns); returns (ns, ns)"""
+def fci_sigma(h, V, c, nsocc, lib=None, slab_rows=0):
+    """sigma = H c of the determinant-space Hamiltonian (qemb_op_fci_sigma): h (n, n), V (n, n, n, n) = (pq|rs), c (ns, ns); returns (ns, ns).
+    slab_rows > 0: in slabs of that many alpha strings (qemb_op_fci_sigma_slab)"""
     from ._lib import DeviceBuffer
     lib = lib or _lib.init()
     h = np.ascontiguousarray(h, dtype=np.float64)
@@ -338,22 +350,29 @@ def fci_sigma(h, V, c, nsocc, lib=None):
     c = np.ascontiguousarray(c, dtype=np.float64)
     bufs = [DeviceBuffer.from_numpy(np.asarray(V).reshape(n * n, n * n), lib=lib), DeviceBuffer.from_numpy(c, lib=lib), DeviceBuffer(c.size, lib=lib)]
     try:
-        check(lib.qemb_op_fci_sigma(n, int(nsocc), h.ctypes.data, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr), "qemb_op_fci_sigma", lib)
+        if slab_rows:
+            check(lib.qemb_op_fci_sigma_slab(n, int(nsocc), h.ctypes.data, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, int(slab_rows), None), "qemb_op_fci_sigma_slab", lib)
+        else:
+            check(lib.qemb_op_fci_sigma(n, int(nsocc), h.ctypes.data, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr), "qemb_op_fci_sigma", lib)
         return bufs[2].numpy(c.shape)
     finally:
         for b in bufs:
             b.free()
 
 
-def fci_rdm12(c, n, nsocc, cumulant=False, lib=None):
-    """(dm1, dm2) of the vector c (ns, ns) in PySCF's conventions (qemb_op_fci_rdm12); cumulant: dm2 minus the mean-field part of molbe/solver.py:513-527"""
+def fci_rdm12(c, n, nsocc, cumulant=False, lib=None, slab_rows=0):
+    """(dm1, dm2) of the vector c (ns, ns) in PySCF's conventions (qemb_op_fci_rdm12); cumulant: dm2 minus the mean-field part of molbe/solver.py:513-527.
+    slab_rows > 0: in slabs of that many alpha strings (qemb_op_fci_rdm12_slab)"""
     from ._lib import DeviceBuffer
     lib = lib or _lib.init()
     c = np.ascontiguousarray(c, dtype=np.float64)
     dm1 = np.empty((n, n))
     bufs = [DeviceBuffer.from_numpy(c, lib=lib), DeviceBuffer(n ** 4, lib=lib)]
     try:
-        check(lib.qemb_op_fci_rdm12(int(n), int(nsocc), bufs[0].ptr, int(bool(cumulant)), dm1.ctypes.data, bufs[1].ptr), "qemb_op_fci_rdm12", lib)
+        if slab_rows:
+            check(lib.qemb_op_fci_rdm12_slab(int(n), int(nsocc), bufs[0].ptr, int(bool(cumulant)), int(slab_rows), dm1.ctypes.data, bufs[1].ptr), "qemb_op_fci_rdm12_slab", lib)
+        else:
+            check(lib.qemb_op_fci_rdm12(int(n), int(nsocc), bufs[0].ptr, int(bool(cumulant)), dm1.ctypes.data, bufs[1].ptr), "qemb_op_fci_rdm12", lib)
         return dm1, bufs[1].numpy((n, n, n, n))
     finally:
         for b in bufs:

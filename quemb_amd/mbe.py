@@ -34,7 +34,7 @@ class BE:
                  df_ints=None, nproc=1, ompnum=1, initialize_fragment_idx=None, solver_opts=None, lib=None, distribute=True, nstreams=None, lockstep=None,
                  eri_file=None, scratch_dir=None, restart=False, schmidt_method="subspace", MO_coeff_epsilon=1e-5, AO_coeff_epsilon=1e-10, df_resident="factor",
                  integral_backend="host", int_direct_tile=None, int_direct_thresh=0.0, cd_tol=1e-8, cd_span=0.01, cd_panel=None, reuse_mf_df=False,
-                 pop_method=None, init_guess="atomic", lo_bath_post_schmidt=None):
+                 pop_method=None, init_guess="atomic", lo_bath_post_schmidt=None, fci_slab_rows=0):
         # lo_method "boys" / "PM": the Loewdin orbitals rotated by get_loc (lo.py: Jacobi sweeps on the device; mbe.py:1451-1481), pop_method / init_guess as there.
         # lo_bath_post_schmidt: the bath columns TA[:, n_f:] of every fragment localised after the Schmidt decomposition (mbe.py:1217-1223) -- a rotation inside
         # the embedding space, the fragment columns are not touched.  "ER" (either keyword) is defined on the factorised integrals and needs a dense 3-index context
@@ -48,6 +48,11 @@ class BE:
                 reuse_mf_df or int_transform == "cholesky-hip" or (int_transform == "int-direct-DF-hip" and df_ints is None and auxbasis)):
             raise ValueError("Edmiston-Ruedenberg localisation reads a dense 3-index context: int_transform='int-direct-DF-hip' with `auxbasis`, "
                              "int_transform='cholesky-hip', or reuse_mf_df=True")
+        # fci_slab_rows: the slab height of solver="FCI-hip" on every fragment (DeviceFragment.set_fci_slab: 0 off, k > 0 rows, -1 automatic) -- what lets fragments
+        # of 15 and 16 embedding orbitals fit; read wherever a sweep or a 2-RDM runs that solver, ignored by the other solvers
+        if int(fci_slab_rows) < -1:
+            raise ValueError("fci_slab_rows must be 0 (off), a positive slab height or -1 (automatic)")
+        self.fci_slab_rows = int(fci_slab_rows)
         self._lo_cache = {}       # what get_loc needs of the molecule alone (dipole integrals, S^1/2): formed once for all fragments
         self._loc_ctx = None      # (context, owned): made by _loc_df for ER, used and released by _eri_transform
         if (lo_method != "lowdin" or lo_bath_post_schmidt is not None) and getattr(mf, "mol", None) is None:
@@ -217,6 +222,7 @@ class BE:
             f = Frags(fo.AO_per_frag[I], I, fo.AO_per_edge_per_frag[I], fo.ref_frag_idx_per_edge_per_frag[I],
                       fo.relAO_per_edge_per_frag[I], fo.relAO_in_ref_per_edge_per_frag[I],
                       fo.weight_and_relAO_per_center_per_frag[I], fo.relAO_per_origin_per_frag[I], lib=self.lib)
+            f.fci_slab_rows = self.fci_slab_rows
             self.Fobjs.append(f)
         couti = 0
         for f in self.Fobjs:

@@ -62,6 +62,7 @@ class Frags:
         self.dm0 = None
         self.unitcell_nkpt = 1.0
         self._hf_jk = None
+        self.fci_slab_rows = 0   # slab height of solver="FCI-hip" on this fragment (DeviceFragment.set_fci_slab; BE(fci_slab_rows=...)); the other solvers do not read it
         self._solver = None      # the solver of the last solve ("CCSD" / "MP2" / "FCI-hip"): what make_rdm2 assembles
 
     # ------------------------------------------------------------------ Schmidt (pfrag.py:146-180)
@@ -169,7 +170,8 @@ class Frags:
         """update_heff -> scf -> solve_ccsd -> rdm1 -> get_frag_energy for this fragment (solver.py:301-547).
         relax_density: solve_ccsd(relax=True) (solver.py:925-939) -- Lambda equations on the device, response densities.
         solver="MP2": the MP2 branch (solver.py:313-317) -- solve_mp2, unrelaxed MP2 1-RDM; relax_density is not read, as in the reference.
-        solver="FCI-hip": the FCI branch (solver.py:339-342) on the device; `fci_opts` (qemb_fci_opts, None: defaults), want_t2 asks for the CI vector (out["civec"]).
+        solver="FCI-hip": the FCI branch (solver.py:339-342) on the device; `fci_opts` (qemb_fci_opts, None: defaults), want_t2 asks for the CI vector (out["civec"]);
+        the work matrices go in slabs of `self.fci_slab_rows` alpha strings (0: off, -1: automatic).
         solver="SCI-hip": the selected-CI branch (solver.py:412-462) on the device; `solver_args` (SHCI_ArgsUser, None: defaults) gives its cutoff and is read by
         this solver alone; want_t2 asks for the determinants and the vector (out["dets"])."""
         if solver not in SOLVERS:
@@ -177,6 +179,8 @@ class Frags:
         from .solver import sci_opts_from_args
         sci_opts = sci_opts_from_args(solver, solver_args, self.dev.lib)
         opts = self._solve_inputs(opts, eeval, relax_density and solver == "CCSD")      # (the MP2 and FCI branches do not read relax_density)
+        if solver == "FCI-hip":
+            self.dev.set_fci_slab(self.fci_slab_rows)      # (kept by the device fragment: a later make_rdm2 follows it too)
         out = self.dev.solve_as(solver, self.nsocc, self.fock + self.heff, self.dm0, opts=opts, eeval=eeval, want_amplitudes=want_t2, fci_opts=fci_opts, sci_opts=sci_opts)
         return self._solve_outputs(out, eeval, use_cumulant, solver)
 

@@ -110,7 +110,8 @@ def sci_opts_from_args(solver, solver_args, lib=None):
     return default_sci_opts(lib, eps_var=float(solver_args.hci_cutoff))
 
 
-def _solve_fragment(name, solver, keys, h, eri_s4, nsocc, dm0, *, n_frag, rdm_return, rdm2_return, use_cumulant, opts, lib, df_factor=None, fci_opts=None, sci_opts=None):
+def _solve_fragment(name, solver, keys, h, eri_s4, nsocc, dm0, *, n_frag, rdm_return, rdm2_return, use_cumulant, opts, lib, df_factor=None, fci_opts=None, sci_opts=None,
+                    slab_rows=0):
     """What solve_ccsd / solve_mp2 / solve_fci share: a fragment with its ERIs (or living on its 3-index factor) is created, solved without energies and freed.
     Returns (out[keys[0]], out[keys[1]]), then rdm1_mo and mo_coeff with rdm_return; rdm2_return: the 2-RDM of the solve takes the place of mo_coeff
     (solver.py:940-942), or is appended without rdm_return."""
@@ -124,6 +125,8 @@ def _solve_fragment(name, solver, keys, h, eri_s4, nsocc, dm0, *, n_frag, rdm_re
             fr.set_df_only(df_factor)
         else:
             raise ValueError(f"{name} needs the fragment ERIs or their 3-index factor")
+        if slab_rows:
+            fr.set_fci_slab(slab_rows)
         out = fr.solve_as(solver, nsocc, h, dm0, opts=opts, eeval=False, want_amplitudes=True, fci_opts=fci_opts, sci_opts=sci_opts)
         rdm2 = fr.make_rdm2(solver, with_dm1=not use_cumulant) if rdm2_return else None
     finally:
@@ -158,12 +161,14 @@ def solve_mp2(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_re
                            use_cumulant=use_cumulant, opts=opts, lib=lib, df_factor=df_factor)
 
 
-def solve_fci(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, use_cumulant=True, df_factor=None, opts=None, fci_opts=None, lib=None):
+def solve_fci(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, use_cumulant=True, df_factor=None, opts=None, fci_opts=None, lib=None,
+              slab_rows=0):
     """Device counterpart of the reference's FCI branch (molbe/solver.py:339-342: fci.FCI(mf, mo_coeff).kernel(), make_rdm1, make_rdm2) with the inputs of
     `solve_mp2` above.  Returns (e_fci, civec) -- the eigenvalue of h = fock + heff with the fragment ERIs and the (ns, ns) vector -- or
-    (e_fci, civec, rdm1_mo, mo_coeff) with rdm_return; rdm2_return: make_rdm2 (minus its mean-field part with use_cumulant) in the place `solve_ccsd` gives it."""
+    (e_fci, civec, rdm1_mo, mo_coeff) with rdm_return; rdm2_return: make_rdm2 (minus its mean-field part with use_cumulant) in the place `solve_ccsd` gives it.
+    slab_rows: the work matrices D and G in slabs of that many alpha strings (DeviceFragment.set_fci_slab: 0 off, -1 automatic)."""
     return _solve_fragment("solve_fci", "FCI-hip", ("e_fci", "civec"), h, eri_s4, nsocc, dm0, n_frag=n_frag, rdm_return=rdm_return, rdm2_return=rdm2_return,
-                           use_cumulant=use_cumulant, opts=opts, lib=lib, df_factor=df_factor, fci_opts=fci_opts)
+                           use_cumulant=use_cumulant, opts=opts, lib=lib, df_factor=df_factor, fci_opts=fci_opts, slab_rows=slab_rows)
 
 
 def solve_sci(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, use_cumulant=True, df_factor=None, opts=None, sci_opts=None, lib=None):
@@ -185,12 +190,13 @@ def sci_work_bytes(n, o, max_det=1 << 20, max_space=12):
     return float(3 * 24 * max_det + cap * 28 + 4096 * 256 * 12 + 8 * (2 * max_space + 4) * max_det + 20 * max_det + 8 * (4 * n ** 4 + 2 * n * n))
 
 
-def fragment_work_bytes(n, o=None, solver="CCSD", naux=None):
+def fragment_work_bytes(n, o=None, solver="CCSD", naux=None, slab_rows=0):
     """Device memory ONE fragment in flight takes beside its resident ERIs: the two n^2 x npair buffers of the
     embedding->MO transformation (rows at a stride of whole 128-byte lines), the (+/-) pair-packed ladder operands, the ovvv block with its
     packed images, and ~30 tensors of the size of t2.  Without n_occ the worst split (n_occ = n / 4) is assumed.
     solver="FCI-hip" (csrc/fci.cpp; qemb_frag_fci_bytes with the default max_space = 12): D and G (2 x 8 n^2 N_det), 28 vectors of N_det, the tables and the n^4
-    pieces; without n_occ the worst split (n_occ = n / 2) is assumed.
+    pieces; without n_occ the worst split (n_occ = n / 2) is assumed.  slab_rows > 0 (read by this solver alone; qemb_frag_fci_bytes_slab): D and G at
+    2 x 8 n^2 min(slab_rows, ns) ns.
     solver="MP2" (factor route, csrc/mp2.cpp): the unpacked factor and its half-rotated virtual columns while Lov is formed (naux n^2 + naux n v), then
     Lov, Y and its transpose (naux o v each) and three o^2 v^2 tensors (ovov, t2, G); naux = 3 n when not given."""
     if solver not in SOLVERS:
@@ -202,7 +208,8 @@ def fragment_work_bytes(n, o=None, solver="CCSD", naux=None):
         from math import comb
         o = max(1, n // 2) if o is None else int(o)
         ns = comb(n, o)
-        return 8.0 * (2.0 * n * n * ns * ns + 28.0 * ns * ns + 8.0 * n ** 4) + 4.0 * ns * (o * (n - o + 1) + 1)
+        rows = ns if int(slab_rows) <= 0 else min(int(slab_rows), ns)
+        return 8.0 * (2.0 * n * n * rows * ns + 28.0 * ns * ns + 8.0 * n ** 4) + 4.0 * ns * (o * (n - o + 1) + 1)
     o = max(1, n // 4) if o is None else int(o)
     v = max(n - o, 1)
     if solver == "MP2":

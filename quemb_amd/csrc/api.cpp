@@ -613,7 +613,7 @@ int qemb_frag_solve_fci(qemb_frag_t f, int nsocc, const double* h, const double*
 int qemb_frag_fci_bytes(int n, int nsocc, int max_space, int64_t* bytes) {
   if (n <= 0 || nsocc <= 0 || nsocc > n || max_space < 2 || !bytes) { set_error("qemb_frag_fci_bytes: bad arguments"); return QEMB_ERR_ARG; }
   if (n > kFciMaxOrb) { set_error("qemb_frag_fci_bytes: n = " + std::to_string(n) + " embedding orbitals; the determinant-space solver takes at most " + std::to_string(kFciMaxOrb)); return QEMB_ERR_UNSUPPORTED; }
-  *bytes = fci_bytes(n, nsocc, max_space);
+  *bytes = fci_bytes_slab(n, nsocc, max_space, 0);
   return QEMB_OK;
 }
 int qemb_frag_fci_bytes_slab(int n, int nsocc, int max_space, int64_t rows, int64_t* bytes) {
@@ -635,49 +635,14 @@ int qemb_op_fci_links(int n, int nsocc, int64_t* ns, int* nlink, int32_t* string
   if (links_host) std::memcpy(links_host, T->links.data(), sizeof(int32_t) * T->links.size());
   return QEMB_OK;
 }
-int qemb_op_fci_sigma(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev) {
-  if (!h_host || !V_dev || !c_dev || !sigma_dev) { set_error("qemb_op_fci_sigma: null argument"); return QEMB_ERR_ARG; }
+namespace {
+// sigma = H c on handed-in data in slabs of `rows` alpha rows (fci_apply; 0: the whole space): k on the device, D and G, one untimed application; ms3 (nullable):
+// then one more whose three steps are bracketed by device timers, summed over the slabs: ms3 = gather, product, sigma gather (tools/fci_bench.py)
+int fci_sigma_op(const std::string& who, int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev, int64_t rows, double* ms3) {
+  if (!h_host || !V_dev || !c_dev || !sigma_dev) { set_error(who + ": null argument"); return QEMB_ERR_ARG; }
   const FciTables* T = nullptr;
   QTRY(fci_tables(n, nsocc, &T));
-  const int64_t n2 = (int64_t)n * n, N = T->ndet();
-  std::vector<double> Vh((size_t)(n2 * n2)), kh((size_t)n2);
-  QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
-  fci_one_body(n, h_host, Vh.data(), kh.data());
-  DBuf kd, D, G;
-  QTRY(kd.alloc(n2)); QTRY(D.alloc(n2 * N)); QTRY(G.alloc(n2 * N));
-  QTRY(dev_h2d(kd, kh.data(), sizeof(double) * n2));
-  QTRY(fci_apply(*T, kd, V_dev, c_dev, D, G, sigma_dev));
-  return dev_sync();
-}
-// measurement hook (tools/fci_bench.py): one untimed application, then one with the three steps bracketed by device timers; ms3 = gather, product, sigma gather
-int qemb_op_fci_sigma_timed(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev, double* ms3) {
-  if (!h_host || !V_dev || !c_dev || !sigma_dev || !ms3) { set_error("qemb_op_fci_sigma_timed: null argument"); return QEMB_ERR_ARG; }
-  const FciTables* T = nullptr;
-  QTRY(fci_tables(n, nsocc, &T));
-  const int64_t n2 = (int64_t)n * n, N = T->ndet();
-  std::vector<double> Vh((size_t)(n2 * n2)), kh((size_t)n2);
-  QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
-  fci_one_body(n, h_host, Vh.data(), kh.data());
-  DBuf kd, D, G;
-  QTRY(kd.alloc(n2)); QTRY(D.alloc(n2 * N)); QTRY(G.alloc(n2 * N));
-  QTRY(dev_h2d(kd, kh.data(), sizeof(double) * n2));
-  QTRY(fci_apply(*T, kd, V_dev, c_dev, D, G, sigma_dev));
-  const int slot[3] = {10, 11, 12};
-  for (int s : slot) QTRY(dev_timer_reset(s));
-  { TimerScope t(slot[0]); QTRY(dev_fci_gather(n, T->ns, T->nlink, T->links_dev, c_dev, D)); QTRY(t.close()); }
-  { TimerScope t(slot[1]); QTRY(gemm(n2, N, n2, 1.0, V_dev, n2, true, D, N, false, 0.0, G, N)); QTRY(t.close()); }
-  { TimerScope t(slot[2]); QTRY(dev_fci_sigma(n, T->ns, T->nlink, T->links_dev, kd, D, G, sigma_dev)); QTRY(t.close()); }
-  for (int k = 0; k < 3; ++k) { int64_t cnt = 0; QTRY(dev_timer_read(slot[k], &ms3[k], &cnt)); }
-  return QEMB_OK;
-}
-// sigma = H c in slabs of `rows` alpha rows (fci_apply); ms3 (nullable): after one untimed application, one whose three steps are bracketed by device timers,
-// summed over the slabs -- the slabbed counterpart of qemb_op_fci_sigma_timed
-int qemb_op_fci_sigma_slab(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev, int64_t rows, double* ms3) {
-  if (!h_host || !V_dev || !c_dev || !sigma_dev) { set_error("qemb_op_fci_sigma_slab: null argument"); return QEMB_ERR_ARG; }
-  if (rows <= 0) { set_error("qemb_op_fci_sigma_slab: rows must be positive"); return QEMB_ERR_ARG; }
-  const FciTables* T = nullptr;
-  QTRY(fci_tables(n, nsocc, &T));
-  const int64_t n2 = (int64_t)n * n, ns = T->ns, R = std::min(rows, ns);
+  const int64_t n2 = (int64_t)n * n, ns = T->ns, R = rows > 0 ? std::min(rows, ns) : ns;
   std::vector<double> Vh((size_t)(n2 * n2)), kh((size_t)n2);
   QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
   fci_one_body(n, h_host, Vh.data(), kh.data());
@@ -697,18 +662,30 @@ int qemb_op_fci_sigma_slab(int n, int nsocc, const double* h_host, const double*
   for (int k = 0; k < 3; ++k) { int64_t cnt = 0; QTRY(dev_timer_read(slot[k], &ms3[k], &cnt)); }
   return QEMB_OK;
 }
-int qemb_op_fci_rdm12_slab(int n, int nsocc, const double* c_dev, int cumulant, int64_t rows, double* dm1_host, double* dm2_dev) {
-  if (!c_dev || !dm1_host) { set_error("qemb_op_fci_rdm12_slab: null argument"); return QEMB_ERR_ARG; }
-  if (rows <= 0) { set_error("qemb_op_fci_rdm12_slab: rows must be positive"); return QEMB_ERR_ARG; }
+int fci_rdm12_op(const std::string& who, int n, int nsocc, const double* c_dev, int cumulant, int64_t rows, double* dm1_host, double* dm2_dev) {
+  if (!c_dev || !dm1_host) { set_error(who + ": null argument"); return QEMB_ERR_ARG; }
   const FciTables* T = nullptr;
   QTRY(fci_tables(n, nsocc, &T));
   return fci_rdm12(*T, c_dev, cumulant ? nsocc : -1, dm1_host, dm2_dev, rows);
 }
+}  // namespace
+int qemb_op_fci_sigma(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev) {
+  return fci_sigma_op("qemb_op_fci_sigma", n, nsocc, h_host, V_dev, c_dev, sigma_dev, 0, nullptr);
+}
+int qemb_op_fci_sigma_timed(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev, double* ms3) {
+  if (!ms3) { set_error("qemb_op_fci_sigma_timed: null argument"); return QEMB_ERR_ARG; }
+  return fci_sigma_op("qemb_op_fci_sigma_timed", n, nsocc, h_host, V_dev, c_dev, sigma_dev, 0, ms3);
+}
+int qemb_op_fci_sigma_slab(int n, int nsocc, const double* h_host, const double* V_dev, const double* c_dev, double* sigma_dev, int64_t rows, double* ms3) {
+  if (h_host && V_dev && c_dev && sigma_dev && rows <= 0) { set_error("qemb_op_fci_sigma_slab: rows must be positive"); return QEMB_ERR_ARG; }
+  return fci_sigma_op("qemb_op_fci_sigma_slab", n, nsocc, h_host, V_dev, c_dev, sigma_dev, rows, ms3);
+}
 int qemb_op_fci_rdm12(int n, int nsocc, const double* c_dev, int cumulant, double* dm1_host, double* dm2_dev) {
-  if (!c_dev || !dm1_host) { set_error("qemb_op_fci_rdm12: null argument"); return QEMB_ERR_ARG; }
-  const FciTables* T = nullptr;
-  QTRY(fci_tables(n, nsocc, &T));
-  return fci_rdm12(*T, c_dev, cumulant ? nsocc : -1, dm1_host, dm2_dev);
+  return fci_rdm12_op("qemb_op_fci_rdm12", n, nsocc, c_dev, cumulant, 0, dm1_host, dm2_dev);
+}
+int qemb_op_fci_rdm12_slab(int n, int nsocc, const double* c_dev, int cumulant, int64_t rows, double* dm1_host, double* dm2_dev) {
+  if (c_dev && dm1_host && rows <= 0) { set_error("qemb_op_fci_rdm12_slab: rows must be positive"); return QEMB_ERR_ARG; }
+  return fci_rdm12_op("qemb_op_fci_rdm12_slab", n, nsocc, c_dev, cumulant, rows, dm1_host, dm2_dev);
 }
 // ---- solver == "SCI-hip"
 void qemb_default_sci_opts(qemb_sci_opts* o) {

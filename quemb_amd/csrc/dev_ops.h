@@ -424,11 +424,15 @@ int dev_rdm2_eri_dot(int64_t m, int sym, const double* eri, const double* K, dou
 // ---- determinant-space FCI (fci.cpp; kernels in fci_ops.hip, scalar restatement for the mock in fci_ops_hostcheck.cpp) ----------------------------------------
 // Determinants I = Ia * ns + Ib over the ns = C(n, nsocc) occupation strings of one spin (lexical order), c[Ia][Ib] row-major.  links: one spin's table,
 // links[l * ns + I] = (J << 9) | (pq << 1) | neg with <I|E_pq|J> = neg ? -1 : +1, nlink = nsocc (n - nsocc + 1) words per string; strings[I]: the bit pattern.
-//   gather:  D[pq * N + I] = sum_J <I|E^a_pq + E^b_pq|J> c[J]   (N = ns^2; every entry written by the thread that owns I, zeros included)
-//   sigma:   sigma[I] = sum_pq k[pq] D[pq * N + I] + 1/2 sum_pq sum_J <I|E_pq|J> G[pq * N + J]      (G = V D, formed by dev_gemm in between)
+// The two passes around the product work on a slab of alpha rows [a0, a1), all beta strings (Ns = (a1 - a0) ns determinants, contiguous in c); (0, ns) is the
+// whole space, shorter slabs are what lets n = 15, 16 fit (fci_apply):
+//   gather_slab: Ds[pq * Ns + I - a0 ns] = sum_J <I|E^a_pq + E^b_pq|J> c[J] for every determinant I of the slab, from the whole vector c (every entry written by
+//                the thread that owns I, zeros included)
+//   sigma_slab:  for every I of the whole space, sigma[I] (=, when a0 == 0; += otherwise) sum_pq k[pq] Ds[pq * Ns + I - a0 ns] when I lies in the slab plus 1/2 sum of
+//                +-Gs[pq * Ns + J - a0 ns] over the links (pq, J) of I with J in the slab  (Gs = V Ds, formed by dev_gemm in between); slabs in ascending order give sigma = H c
 //   diag:    hdiag[I] = <I|H|I> from the occupations, h [n][n], V [n^2][n^2] = (pq|rs)
 //   precond: out[I] = r[I] / (hdiag[I] - theta), |denominator| >= 1e-8
-//   dm2:     out[p,q,r,s] = A[qp][rs] - delta_qr dm1[p,s]  (A = D D^T), o_cum >= 0: minus the mean-field part of molbe/solver.py:513-527 with o_cum occupied orbitals
+//   dm2:     out[p,q,r,s] = A[qp][rs] - delta_qr dm1[p,s]  (A = D D^T), o_cum >= 0: minus the mean-field part of molbe/solver.py:513-527 with o_cum occupied orbitals (cumulant_core.h)
 // No atomics, one owner per output element: the same bits on every run.
 constexpr int kFciMaxOrb = 16;
 constexpr int64_t kFciMaxDet = (int64_t)12870 * 12870;      // C(16, 8)^2
@@ -439,12 +443,6 @@ inline int fci_check_args(const char* who, int n, int64_t ns, int nlink, const v
   }
   return 0;
 }
-int dev_fci_gather(int n, int64_t ns, int nlink, const int32_t* links, const double* c, double* D);
-int dev_fci_sigma(int n, int64_t ns, int nlink, const int32_t* links, const double* k, const double* D, const double* G, double* sigma);
-// The two passes over a slab of alpha rows [a0, a1), all beta strings (Ns = (a1 - a0) ns determinants, contiguous in c): what lets n = 15, 16 fit (fci_apply)
-//   gather_slab: Ds[pq * Ns + I - a0 ns] = the column of D of every determinant I of the slab, from the whole vector c
-//   sigma_slab:  for every I of the whole space, sigma[I] (=, when a0 == 0; += otherwise) the one-body term when I lies in the slab plus 1/2 sum of
-//                +-Gs[pq * Ns + J - a0 ns] over the links (pq, J) of I with J in the slab  (Gs = V Ds); slabs in ascending order give sigma = H c
 inline int fci_check_slab(const char* who, int64_t ns, int64_t a0, int64_t a1) {
   if (a0 < 0 || a1 <= a0 || a1 > ns) { set_error(std::string(who) + ": bad slab [" + std::to_string(a0) + ", " + std::to_string(a1) + ") of " + std::to_string(ns) + " alpha rows"); return QEMB_ERR_ARG; }
   return 0;

@@ -1,5 +1,6 @@
 // fci.cpp -- determinant-space FCI on the device (fci.h): tables, one application of H, Davidson-Liu, RDMs.
 #include "fci.h"
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -12,12 +13,6 @@ int64_t fci_string_count(int n, int nsocc) {
   int64_t c = 1;
   for (int k = 1; k <= nsocc; ++k) c = c * (n - nsocc + k) / k;
   return c;
-}
-
-int64_t fci_bytes(int n, int nsocc, int max_space) {
-  const int64_t ns = fci_string_count(n, nsocc), N = ns * ns, n2 = (int64_t)n * n;
-  const int64_t nlink = (int64_t)nsocc * (n - nsocc + 1);
-  return 8 * (2 * n2 * N + (2 * (int64_t)max_space + 4) * N + 8 * n2 * n2) + 4 * ns * (nlink + 1);
 }
 
 int64_t fci_slab_count(int64_t ns, int64_t rows) { return rows <= 0 || rows >= ns ? 1 : (ns + rows - 1) / rows; }
@@ -89,19 +84,15 @@ void fci_one_body(int n, const double* h, const double* V, double* k) {
 }
 
 int fci_apply(const FciTables& T, const double* k_dev, const double* V_dev, const double* c, double* D, double* G, double* sigma, int64_t rows) {
-  const int64_t n2 = (int64_t)T.n * T.n, N = T.ndet();
-  if (rows > 0) {      // slab by slab, ascending: D_s, G_s = V D_s, then every determinant takes what the slab holds for it (the links are scanned once per slab)
-    for (int64_t a0 = 0; a0 < T.ns; a0 += rows) {
-      const int64_t a1 = std::min(T.ns, a0 + rows), Ns = (a1 - a0) * T.ns;
-      QTRY(dev_fci_gather_slab(T.n, T.ns, T.nlink, T.links_dev, c, a0, a1, D));
-      QTRY(gemm(n2, Ns, n2, 1.0, V_dev, n2, true, D, Ns, false, 0.0, G, Ns));
-      QTRY(dev_fci_sigma_slab(T.n, T.ns, T.nlink, T.links_dev, k_dev, a0, a1, D, G, sigma));
-    }
-    return 0;
+  const int64_t n2 = (int64_t)T.n * T.n, R = rows > 0 ? std::min(rows, T.ns) : T.ns;
+  // slab by slab, ascending: D_s, G_s = V D_s, then every determinant takes what the slab holds for it (the links are scanned once per slab)
+  for (int64_t a0 = 0; a0 < T.ns; a0 += R) {
+    const int64_t a1 = std::min(T.ns, a0 + R), Ns = (a1 - a0) * T.ns;
+    QTRY(dev_fci_gather_slab(T.n, T.ns, T.nlink, T.links_dev, c, a0, a1, D));
+    QTRY(gemm(n2, Ns, n2, 1.0, V_dev, n2, true, D, Ns, false, 0.0, G, Ns));      // G_s = V D_s
+    QTRY(dev_fci_sigma_slab(T.n, T.ns, T.nlink, T.links_dev, k_dev, a0, a1, D, G, sigma));
   }
-  QTRY(dev_fci_gather(T.n, T.ns, T.nlink, T.links_dev, c, D));
-  QTRY(gemm(n2, N, n2, 1.0, V_dev, n2, true, D, N, false, 0.0, G, N));      // G = V D
-  return dev_fci_sigma(T.n, T.ns, T.nlink, T.links_dev, k_dev, D, G, sigma);
+  return 0;
 }
 
 namespace fci_detail {      // (declared in fci.h: the selected-CI iteration of sci.cpp shares them)
@@ -159,44 +150,48 @@ int combine(int64_t N, const std::vector<double>& coef, const std::vector<const 
     QTRY(dev_lincomb(N, std::min(8, m - j0), coef.data() + j0, xs.data() + j0, (j0 == 0 && !accumulate) ? 0.0 : 1.0, out));
   return 0;
 }
-}  // namespace fci_detail
-using namespace fci_detail;
+void symmetrise_dm1(int n, double* dm1) {
+  for (int p = 0; p < n; ++p) for (int q = 0; q < p; ++q) { const double s = 0.5 * (dm1[p * n + q] + dm1[q * n + p]); dm1[p * n + q] = dm1[q * n + p] = s; }
+}
 
-int fci_davidson(const FciTables& T, const double* h_host, const double* V_dev, const FciOptions& opt, double* c, FciResult* res, int64_t rows) {
-  const int n = T.n;
-  const int64_t n2 = (int64_t)n * n, N = T.ndet();
-  if (opt.max_space < 2 || opt.max_cycle < 1 || !(opt.conv_tol > 0.0) || !(opt.lindep >= 0.0)) {
-    set_error("fci: need max_space >= 2, max_cycle >= 1, conv_tol > 0 and lindep >= 0"); return QEMB_ERR_ARG;
+// c / |c|, largest-magnitude component positive (ties: the lowest index)
+static int normalise_signed(int64_t N, double* c, bool compensated) {
+  std::vector<double> ch((size_t)N);
+  QTRY(dev_d2h(ch.data(), c, sizeof(double) * N));
+  double nrm = 0.0; int64_t big = 0;
+  for (int64_t I = 0; I < N; ++I) { nrm += ch[(size_t)I] * ch[(size_t)I]; if (std::fabs(ch[(size_t)I]) > std::fabs(ch[(size_t)big])) big = I; }
+  if (compensated) {
+    // The plain sum above absorbs every c_I^2 below half an ulp of the running sum once the leading determinant is in: at (14, 7) that tail is 2.2e-11 of the norm,
+    // at (16, 8) 1.2e-10 (measured), and Tr dm1 and the energy from the RDMs are off by as much.  The slabbed FCI solve, which is the one that reaches those sizes,
+    // sums with compensation (Neumaier); the unslabbed solve and the selected CI keep the plain sum and their bits.
+    double s = 0.0, comp = 0.0;
+    for (int64_t I = 0; I < N; ++I) {
+      const double x = ch[(size_t)I] * ch[(size_t)I], t2 = s + x;
+      comp += std::fabs(s) >= x ? (s - t2) + x : (x - t2) + s;
+      s = t2;
+    }
+    nrm = s + comp;
   }
-  const int ms = (int)std::min<int64_t>(opt.max_space, N);
+  const double scale = (ch[(size_t)big] < 0.0 ? -1.0 : 1.0) / std::sqrt(nrm);
+  if (scale != 1.0) QTRY(axpby(N, scale, c, 0.0, c));
+  return 0;
+}
+
+int davidson(int64_t N, const std::function<int(const double*, double*)>& apply, const double* hdiag, double conv_tol, int max_cycle, int max_space, double lindep,
+             bool compensated, double* c, FciResult* res) {
+  const int ms = (int)std::min<int64_t>(max_space, N);
   *res = FciResult();
-  // ---- k, the diagonal and the start vector (the unit vector at the lowest diagonal; ties: the lowest index)
-  std::vector<double> Vh((size_t)(n2 * n2)), kh((size_t)n2);
-  QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
-  fci_one_body(n, h_host, Vh.data(), kh.data());
-  DBuf kd, hd, hdiag, D, G, r, t, scal;
-  QTRY(kd.alloc(n2)); QTRY(hd.alloc(n2)); QTRY(hdiag.alloc(N));
-  const int64_t ncol = rows > 0 ? std::min(rows, T.ns) * T.ns : N;      // columns of D and G: one slab of alpha rows, or the whole space
-  QTRY(D.alloc(n2 * ncol)); QTRY(G.alloc(n2 * ncol)); QTRY(r.alloc(N)); QTRY(t.alloc(N)); QTRY(scal.alloc(8));
-  QTRY(dev_h2d(kd, kh.data(), sizeof(double) * n2));
-  QTRY(dev_h2d(hd, h_host, sizeof(double) * n2));
-  QTRY(dev_fci_diag(n, T.ns, T.strings_dev, hd, V_dev, hdiag));
-  int64_t start = 0;
-  {
-    std::vector<double> dh((size_t)N);
-    QTRY(dev_d2h(dh.data(), hdiag, sizeof(double) * N));
-    for (int64_t I = 1; I < N; ++I) if (dh[(size_t)I] < dh[(size_t)start]) start = I;
-  }
+  DBuf r, t, scal;
+  QTRY(r.alloc(N)); QTRY(t.alloc(N)); QTRY(scal.alloc(8));
   std::vector<DBuf> B((size_t)ms), S((size_t)ms);
   for (int j = 0; j < ms; ++j) { QTRY(B[j].alloc(N)); QTRY(S[j].alloc(N)); }
-  QTRY(dev_fill(B[0], N, 0.0));
-  const double one = 1.0;
-  QTRY(dev_h2d(B[0].p + start, &one, sizeof(double)));
-  QTRY(fci_apply(T, kd, V_dev, B[0], D, G, S[0], rows));
+  auto ptrs = [&](const std::vector<DBuf>& X, int cnt) { std::vector<const double*> p((size_t)cnt); for (int j = 0; j < cnt; ++j) p[j] = X[j].p; return p; };
+  auto norm2 = [&](const double* x, double* out) { std::vector<const double*> self(1, x); return dots(N, x, self, scal, out); };
+  QTRY(dcopy(N, c, B[0]));
+  QTRY(apply(B[0], S[0]));
   res->n_iter = 1;
   int m = 1;
   std::vector<double> Hs((size_t)ms * ms, 0.0), row((size_t)ms), y, w, A;
-  auto ptrs = [&](const std::vector<DBuf>& X, int cnt) { std::vector<const double*> p((size_t)cnt); for (int j = 0; j < cnt; ++j) p[j] = X[j].p; return p; };
   QTRY(dots(N, S[0], ptrs(B, 1), scal, row.data()));
   Hs[0] = row[0];
   for (;;) {
@@ -214,21 +209,16 @@ int fci_davidson(const FciTables& T, const double* h_host, const double* V_dev, 
     QTRY(combine(N, cy, ptrs(S, m), false, r));
     QTRY(combine(N, cb, ptrs(B, m), true, r));
     double rr = 0.0;
-    { std::vector<const double*> self(1, r.p); QTRY(dots(N, r, self, scal, &rr)); }
+    QTRY(norm2(r, &rr));
     res->e = theta; res->residual = std::sqrt(rr > 0.0 ? rr : 0.0);
-    res->converged = res->residual <= opt.conv_tol;
-    bool stop = res->converged || res->n_iter >= opt.max_cycle;
+    res->converged = res->residual <= conv_tol;
+    bool stop = res->converged || res->n_iter >= max_cycle;
     if (!stop) {
-      if (m == ms) {      // collapse to the current Ritz vector (and its image)
+      if (m == ms) {      // collapse to the current Ritz vector and its image (t serves twice: no further vector)
         QTRY(combine(N, y, ptrs(B, m), false, t));
-        if (rows > 0) {      // (a slab of D may be shorter than a vector: t serves twice)
-          QTRY(dcopy(N, t, B[0]));
-          QTRY(combine(N, y, ptrs(S, m), false, t));
-          QTRY(dcopy(N, t, S[0]));
-        } else {
-          QTRY(combine(N, y, ptrs(S, m), false, D));      // (D is free between applications)
-          QTRY(dcopy(N, t, B[0])); QTRY(dcopy(N, D, S[0]));
-        }
+        QTRY(dcopy(N, t, B[0]));
+        QTRY(combine(N, y, ptrs(S, m), false, t));
+        QTRY(dcopy(N, t, S[0]));
         m = 1; Hs[0] = theta; y.assign(1, 1.0);
       }
       // ---- correction: (H_II - theta)^-1 r, orthogonalised twice against the basis
@@ -240,12 +230,12 @@ int fci_davidson(const FciTables& T, const double* h_host, const double* V_dev, 
         QTRY(combine(N, neg, ptrs(B, m), true, t));
       }
       double tt = 0.0;
-      { std::vector<const double*> self(1, t.p); QTRY(dots(N, t, self, scal, &tt)); }
+      QTRY(norm2(t, &tt));
       const double tn = std::sqrt(tt > 0.0 ? tt : 0.0);
-      if (!(tn > opt.lindep)) stop = true;      // nothing left to add: the space is exhausted
+      if (!(tn > lindep) || m == ms) stop = true;      // nothing left to add: the space is exhausted (m == ms after the collapse: the space itself has one dimension)
       else {
         QTRY(axpby(N, 1.0 / tn, t, 0.0, B[m]));
-        QTRY(fci_apply(T, kd, V_dev, B[m], D, G, S[m], rows));
+        QTRY(apply(B[m], S[m]));
         res->n_iter += 1;
         QTRY(dots(N, S[m], ptrs(B, m + 1), scal, row.data()));
         for (int j = 0; j <= m; ++j) Hs[(size_t)m * ms + j] = Hs[(size_t)j * ms + m] = row[j];
@@ -253,61 +243,60 @@ int fci_davidson(const FciTables& T, const double* h_host, const double* V_dev, 
         continue;
       }
     }
-    // ---- the Ritz vector, normalised, largest-magnitude component positive (ties: the lowest index)
-    QTRY(combine(N, y, ptrs(B, m), false, c));
-    std::vector<double> ch((size_t)N);
-    QTRY(dev_d2h(ch.data(), c, sizeof(double) * N));
-    double nrm = 0.0; int64_t big = 0;
-    for (int64_t I = 0; I < N; ++I) { nrm += ch[(size_t)I] * ch[(size_t)I]; if (std::fabs(ch[(size_t)I]) > std::fabs(ch[(size_t)big])) big = I; }
-    if (rows > 0) {
-      // The plain sum above absorbs every c_I^2 below half an ulp of the running sum once the leading determinant is in: at (14, 7) that tail is 2.2e-11 of the norm,
-      // at (16, 8) 1.2e-10 (measured), and Tr dm1 and the energy from the RDMs are off by as much.  The slabbed solve, which is the one that reaches those sizes,
-      // sums with compensation (Neumaier); the unslabbed path keeps its sum and its bits.
-      double s = 0.0, comp = 0.0;
-      for (int64_t I = 0; I < N; ++I) {
-        const double x = ch[(size_t)I] * ch[(size_t)I], t2 = s + x;
-        comp += std::fabs(s) >= x ? (s - t2) + x : (x - t2) + s;
-        s = t2;
-      }
-      nrm = s + comp;
-    }
-    const double scale = (ch[(size_t)big] < 0.0 ? -1.0 : 1.0) / std::sqrt(nrm);
-    if (scale != 1.0) QTRY(axpby(N, scale, c, 0.0, c));
-    return 0;
+    QTRY(combine(N, y, ptrs(B, m), false, c));      // the Ritz vector
+    return normalise_signed(N, c, compensated);
   }
+}
+}  // namespace fci_detail
+using namespace fci_detail;
+
+int fci_davidson(const FciTables& T, const double* h_host, const double* V_dev, const FciOptions& opt, double* c, FciResult* res, int64_t rows) {
+  const int n = T.n;
+  const int64_t n2 = (int64_t)n * n, N = T.ndet();
+  if (opt.max_space < 2 || opt.max_cycle < 1 || !(opt.conv_tol > 0.0) || !(opt.lindep >= 0.0)) {
+    set_error("fci: need max_space >= 2, max_cycle >= 1, conv_tol > 0 and lindep >= 0"); return QEMB_ERR_ARG;
+  }
+  // ---- k, the diagonal and the start vector (the unit vector at the lowest diagonal; ties: the lowest index)
+  std::vector<double> Vh((size_t)(n2 * n2)), kh((size_t)n2);
+  QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
+  fci_one_body(n, h_host, Vh.data(), kh.data());
+  DBuf kd, hd, hdiag, D, G;
+  QTRY(kd.alloc(n2)); QTRY(hd.alloc(n2)); QTRY(hdiag.alloc(N));
+  const int64_t ncol = (rows > 0 ? std::min(rows, T.ns) : T.ns) * T.ns;      // columns of D and G: one slab of alpha rows, or the whole space
+  QTRY(D.alloc(n2 * ncol)); QTRY(G.alloc(n2 * ncol));
+  QTRY(dev_h2d(kd, kh.data(), sizeof(double) * n2));
+  QTRY(dev_h2d(hd, h_host, sizeof(double) * n2));
+  QTRY(dev_fci_diag(n, T.ns, T.strings_dev, hd, V_dev, hdiag));
+  int64_t start = 0;
+  {
+    std::vector<double> dh((size_t)N);
+    QTRY(dev_d2h(dh.data(), hdiag, sizeof(double) * N));
+    for (int64_t I = 1; I < N; ++I) if (dh[(size_t)I] < dh[(size_t)start]) start = I;
+  }
+  QTRY(dev_fill(c, N, 0.0));
+  const double one = 1.0;
+  QTRY(dev_h2d(c + start, &one, sizeof(double)));
+  auto apply = [&](const double* x, double* y) { return fci_apply(T, kd, V_dev, x, D, G, y, rows); };
+  return davidson(N, apply, hdiag, opt.conv_tol, opt.max_cycle, opt.max_space, opt.lindep, rows > 0, c, res);
 }
 
 int fci_rdm12(const FciTables& T, const double* c, int o_cum, double* dm1_host, double* dm2_dev, int64_t rows) {
   const int n = T.n;
-  const int64_t n2 = (int64_t)n * n, N = T.ndet();
+  const int64_t n2 = (int64_t)n * n, R = rows > 0 ? std::min(rows, T.ns) : T.ns;
   DBuf D, d1, A;
-  if (rows > 0) {      // slab by slab: dm1 += D_s c_s and A += D_s D_s^T (the products accumulate, beta = 1 after the first slab); the tail is the one below
-    const int64_t R = std::min(rows, T.ns);
-    QTRY(D.alloc(n2 * R * T.ns)); QTRY(d1.alloc(n2));
-    if (dm2_dev) QTRY(A.alloc(n2 * n2));
-    for (int64_t a0 = 0; a0 < T.ns; a0 += R) {
-      const int64_t a1 = std::min(T.ns, a0 + R), Ns = (a1 - a0) * T.ns;
-      const double beta = a0 == 0 ? 0.0 : 1.0;
-      QTRY(dev_fci_gather_slab(n, T.ns, T.nlink, T.links_dev, c, a0, a1, D));
-      QTRY(dev_gemv_rows(n2, Ns, D, Ns, c + a0 * T.ns, d1, 1.0, beta));
-      if (dm2_dev) QTRY(gemm(n2, n2, Ns, 1.0, D, Ns, true, D, Ns, true, beta, A, n2));
-    }
-    QTRY(dev_d2h(dm1_host, d1, sizeof(double) * n2));
-    for (int p = 0; p < n; ++p) for (int q = 0; q < p; ++q) { const double s = 0.5 * (dm1_host[p * n + q] + dm1_host[q * n + p]); dm1_host[p * n + q] = dm1_host[q * n + p] = s; }
-    if (!dm2_dev) return 0;
-    QTRY(dev_h2d(d1, dm1_host, sizeof(double) * n2));
-    QTRY(dev_fci_dm2(n, o_cum, A, d1, dm2_dev));
-    return dev_sync();
+  QTRY(D.alloc(n2 * R * T.ns)); QTRY(d1.alloc(n2));
+  if (dm2_dev) QTRY(A.alloc(n2 * n2));
+  for (int64_t a0 = 0; a0 < T.ns; a0 += R) {      // slab by slab: dm1 += D_s c_s and A += D_s D_s^T (the products accumulate, beta = 1 after the first slab)
+    const int64_t a1 = std::min(T.ns, a0 + R), Ns = (a1 - a0) * T.ns;
+    const double beta = a0 == 0 ? 0.0 : 1.0;
+    QTRY(dev_fci_gather_slab(n, T.ns, T.nlink, T.links_dev, c, a0, a1, D));
+    QTRY(dev_gemv_rows(n2, Ns, D, Ns, c + a0 * T.ns, d1, 1.0, beta));
+    if (dm2_dev) QTRY(gemm(n2, n2, Ns, 1.0, D, Ns, true, D, Ns, true, beta, A, n2));      // A[pq][rs] = sum_I D[pq][I] D[rs][I]
   }
-  QTRY(D.alloc(n2 * N)); QTRY(d1.alloc(n2));
-  QTRY(dev_fci_gather(n, T.ns, T.nlink, T.links_dev, c, D));
-  QTRY(dev_gemv_rows(n2, N, D, N, c, d1, 1.0, 0.0));
   QTRY(dev_d2h(dm1_host, d1, sizeof(double) * n2));
-  for (int p = 0; p < n; ++p) for (int q = 0; q < p; ++q) { const double s = 0.5 * (dm1_host[p * n + q] + dm1_host[q * n + p]); dm1_host[p * n + q] = dm1_host[q * n + p] = s; }
+  symmetrise_dm1(n, dm1_host);
   if (!dm2_dev) return 0;
   QTRY(dev_h2d(d1, dm1_host, sizeof(double) * n2));
-  QTRY(A.alloc(n2 * n2));
-  QTRY(gemm(n2, n2, N, 1.0, D, N, true, D, N, true, 0.0, A, n2));      // A[pq][rs] = sum_I D[pq][I] D[rs][I]
   QTRY(dev_fci_dm2(n, o_cum, A, d1, dm2_dev));
   return dev_sync();      // (D, A and d1 go back to the pool on return)
 }

@@ -9,54 +9,15 @@
 // (string fast: the threads of a wave read consecutive words).  Within one spin a string meets every pq at most once.
 // Bytes of one application: D written (zeros, then the links) and read, G written and read: four passes over 8 n^2 N_det.
 #include "hip_common.h"
+#include "cumulant_core.h"
 
 namespace qemb {
 namespace {
 
-__global__ void __launch_bounds__(256) fci_gather_kernel(int n, long long ns, int nlink, const int* __restrict__ links, const double* __restrict__ c, double* D) {
-  const long long N = ns * ns;
-  const long long I = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (I >= N) return;
-  const long long Ia = I / ns, Ib = I - Ia * ns;
-  const int n2 = n * n;
-  for (int pq = 0; pq < n2; ++pq) D[pq * N + I] = 0.0;      // the owner writes every entry of its column: zeros where no link lands
-  for (int l = 0; l < nlink; ++l) {                          // alpha: |Ia Ib> <- E_pq |Ja Ib>
-    const int w = links[(long long)l * ns + Ia];
-    const double x = c[(long long)(w >> 9) * ns + Ib];
-    D[(long long)((w >> 1) & 255) * N + I] = (w & 1) ? -x : x;
-  }
-  for (int l = 0; l < nlink; ++l) {                          // beta: |Ia Ib> <- E_pq |Ia Jb>, added to what this thread stored above
-    const int w = links[(long long)l * ns + Ib];
-    const double x = c[Ia * ns + (w >> 9)];
-    double* d = D + (long long)((w >> 1) & 255) * N + I;
-    *d += (w & 1) ? -x : x;
-  }
-}
-
-__global__ void __launch_bounds__(256) fci_sigma_kernel(int n, long long ns, int nlink, const int* __restrict__ links, const double* __restrict__ k,
-                                                        const double* __restrict__ D, const double* __restrict__ G, double* __restrict__ sigma) {
-  const long long N = ns * ns;
-  const long long I = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (I >= N) return;
-  const long long Ia = I / ns, Ib = I - Ia * ns;
-  const int n2 = n * n;
-  double one = 0.0, two = 0.0;
-  for (int pq = 0; pq < n2; ++pq) one += k[pq] * D[pq * N + I];
-  for (int l = 0; l < nlink; ++l) {
-    const int w = links[(long long)l * ns + Ia];
-    const double x = G[(long long)((w >> 1) & 255) * N + (long long)(w >> 9) * ns + Ib];
-    two += (w & 1) ? -x : x;
-  }
-  for (int l = 0; l < nlink; ++l) {
-    const int w = links[(long long)l * ns + Ib];
-    const double x = G[(long long)((w >> 1) & 255) * N + Ia * ns + (w >> 9)];
-    two += (w & 1) ? -x : x;
-  }
-  sigma[I] = one + 0.5 * two;
-}
-
-// The same two passes over a slab of alpha rows [a0, a1) (all beta strings: the determinants a0 ns <= I < a1 ns, contiguous in c[Ia][Ib]); Ns = (a1 - a0) ns columns.
-// gather: D_s[pq][I - a0 ns] for the determinants of the slab from the whole vector c -- the owner, the stores and the order of additions of fci_gather_kernel.
+// Both passes work on a slab of alpha rows [a0, a1) (all beta strings: the determinants a0 ns <= I < a1 ns, contiguous in c[Ia][Ib]); Ns = (a1 - a0) ns columns.
+// The whole space is the slab (0, ns).
+// gather: D_s[pq][I - a0 ns] for the determinants of the slab from the whole vector c.  The owner writes every entry of its column: zeros where no link lands,
+// then the alpha links |Ia Ib> <- E_pq |Ja Ib>, then the beta links |Ia Ib> <- E_pq |Ia Jb> added to what this thread stored before.
 __global__ void __launch_bounds__(256) fci_gather_slab_kernel(int n, long long ns, int nlink, const int* __restrict__ links, const double* __restrict__ c,
                                                               long long a0, long long a1, double* Ds) {
   const long long Ns = (a1 - a0) * ns;
@@ -150,8 +111,7 @@ __global__ void __launch_bounds__(256) fci_precond_kernel(long long N, const dou
 }
 
 // dm2[p,q,r,s] = A[qp][rs] - delta_qr dm1[p,s]   (A[pq][rs] = sum_I D[pq][I] D[rs][I] = <E_qp E_rs>; PySCF's dm2[p,q,r,s] = <p+ r+ s q>), every element written once;
-// o_cum >= 0: minus the mean-field part nc of the reference (hf = 2 I_occ over the first o_cum orbitals, del = dm1 - hf):
-//   nc[p,q,r,s] = hf_pq hf_rs + hf_pq del_rs + del_pq hf_rs - (hf_ps hf_qr + hf_ps del_qr + del_ps hf_qr) / 2
+// o_cum >= 0: minus the mean-field part nc of the reference (cumulant_core.h)
 __global__ void __launch_bounds__(256) fci_dm2_kernel(int n, int o_cum, const double* __restrict__ A, const double* __restrict__ dm1, double* __restrict__ out) {
   const int n2 = n * n;
   const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -160,33 +120,13 @@ __global__ void __launch_bounds__(256) fci_dm2_kernel(int n, int o_cum, const do
   const int p = pq / n, q = pq - p * n, r = rs / n, s = rs - r * n;
   double x = A[(q * n + p) * n2 + rs];
   if (q == r) x -= dm1[p * n + s];
-  if (o_cum >= 0) {
-    const double hf_pq = (p == q && p < o_cum) ? 2.0 : 0.0, hf_rs = (r == s && r < o_cum) ? 2.0 : 0.0;
-    const double hf_ps = (p == s && p < o_cum) ? 2.0 : 0.0, hf_qr = (q == r && q < o_cum) ? 2.0 : 0.0;
-    const double d_pq = dm1[p * n + q] - hf_pq, d_rs = dm1[r * n + s] - hf_rs, d_ps = dm1[p * n + s] - hf_ps, d_qr = dm1[q * n + r] - hf_qr;
-    x -= hf_pq * hf_rs + hf_pq * d_rs + d_pq * hf_rs - 0.5 * (hf_ps * hf_qr + hf_ps * d_qr + d_ps * hf_qr);
-  }
+  if (o_cum >= 0) x -= cumulant_mean_field(n, o_cum, dm1, p, q, r, s);
   out[idx] = x;
 }
 
 inline unsigned det_grid(int64_t N) { return (unsigned)((N + 255) / 256); }
 
 }  // namespace
-
-int dev_fci_gather(int n, int64_t ns, int nlink, const int32_t* links, const double* c, double* D) {
-  hipStream_t st = hip_stream();
-  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
-  if (int rc = fci_check_args("dev_fci_gather", n, ns, nlink, links, c, D)) return rc;
-  return launch("dev_fci_gather", fci_gather_kernel, dim3(det_grid(ns * ns)), dim3(256), 0, st, n, ns, nlink, links, c, D);
-}
-
-int dev_fci_sigma(int n, int64_t ns, int nlink, const int32_t* links, const double* k, const double* D, const double* G, double* sigma) {
-  hipStream_t st = hip_stream();
-  if (!st) { set_error("libqemb_hip: call qemb_init(device) first"); return QEMB_ERR_DEVICE; }
-  if (int rc = fci_check_args("dev_fci_sigma", n, ns, nlink, links, D, sigma)) return rc;
-  if (!k || !G) { set_error("dev_fci_sigma: bad arguments"); return QEMB_ERR_ARG; }
-  return launch("dev_fci_sigma", fci_sigma_kernel, dim3(det_grid(ns * ns)), dim3(256), 0, st, n, ns, nlink, links, k, D, G, sigma);
-}
 
 int dev_fci_gather_slab(int n, int64_t ns, int nlink, const int32_t* links, const double* c, int64_t a0, int64_t a1, double* Ds) {
   hipStream_t st = hip_stream();

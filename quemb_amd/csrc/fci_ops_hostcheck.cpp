@@ -7,40 +7,6 @@
 
 namespace qemb {
 
-int dev_fci_gather(int n, int64_t ns, int nlink, const int32_t* links, const double* c, double* D) {
-  if (int rc = fci_check_args("dev_fci_gather", n, ns, nlink, links, c, D)) return rc;
-  const int64_t N = ns * ns, n2 = (int64_t)n * n;
-  for (int64_t k = 0; k < n2 * N; ++k) D[k] = 0.0;
-  for (int l = 0; l < nlink; ++l) for (int64_t I = 0; I < ns; ++I) {
-    const int32_t w = links[(int64_t)l * ns + I];
-    const int64_t J = w >> 9, pq = (w >> 1) & 255;
-    const double sg = (w & 1) ? -1.0 : 1.0;
-    for (int64_t K = 0; K < ns; ++K) {
-      D[pq * N + I * ns + K] += sg * c[J * ns + K];      // alpha: the string is the slow index
-      D[pq * N + K * ns + I] += sg * c[K * ns + J];      // beta
-    }
-  }
-  return 0;
-}
-
-int dev_fci_sigma(int n, int64_t ns, int nlink, const int32_t* links, const double* k, const double* D, const double* G, double* sigma) {
-  if (int rc = fci_check_args("dev_fci_sigma", n, ns, nlink, links, D, sigma)) return rc;
-  if (!k || !G) { set_error("dev_fci_sigma: bad arguments"); return QEMB_ERR_ARG; }
-  const int64_t N = ns * ns, n2 = (int64_t)n * n;
-  for (int64_t I = 0; I < N; ++I) sigma[I] = 0.0;
-  for (int64_t pq = 0; pq < n2; ++pq) for (int64_t I = 0; I < N; ++I) sigma[I] += k[pq] * D[pq * N + I];
-  for (int l = 0; l < nlink; ++l) for (int64_t I = 0; I < ns; ++I) {
-    const int32_t w = links[(int64_t)l * ns + I];
-    const int64_t J = w >> 9, pq = (w >> 1) & 255;
-    const double sg = (w & 1) ? -0.5 : 0.5;
-    for (int64_t K = 0; K < ns; ++K) {
-      sigma[I * ns + K] += sg * G[pq * N + J * ns + K];
-      sigma[K * ns + I] += sg * G[pq * N + K * ns + J];
-    }
-  }
-  return 0;
-}
-
 int dev_fci_gather_slab(int n, int64_t ns, int nlink, const int32_t* links, const double* c, int64_t a0, int64_t a1, double* Ds) {
   if (int rc = fci_check_args("dev_fci_gather_slab", n, ns, nlink, links, c, Ds)) return rc;
   if (int rc = fci_check_slab("dev_fci_gather_slab", ns, a0, a1)) return rc;

@@ -861,6 +861,26 @@ int Fragment::fci_e2_sites(const double* CC, const double* G2, const double* Vao
   return 0;
 }
 
+// ---- shared by solve_fci and solve_sci
+// h in the fragment-MO basis: C^T h C (h, C [n][n] on the host)
+static std::vector<double> mo_one_body(int n, const std::vector<double>& C, const double* h) {
+  const int64_t n2 = (int64_t)n * n;
+  std::vector<double> hmo((size_t)n2, 0.0), tmp((size_t)n2, 0.0);
+  for (int p = 0; p < n; ++p) for (int nu = 0; nu < n; ++nu) { double s = 0; for (int mu = 0; mu < n; ++mu) s += C[(size_t)mu * n + p] * h[(size_t)mu * n + nu]; tmp[(size_t)p * n + nu] = s; }
+  for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int nu = 0; nu < n; ++nu) s += tmp[(size_t)p * n + nu] * C[(size_t)nu * n + q]; hmo[(size_t)p * n + q] = s; }
+  return hmo;
+}
+// the device bytes a guard compares with: what is free, or the fragment's limit where that is less (limit < 0: none)
+static int device_room(int64_t limit, double* room) {
+  size_t free_b = 0, total_b = 0;
+  QTRY(dev_mem_info(&free_b, &total_b));
+  *room = (double)free_b;
+  if (limit >= 0 && (double)limit < *room) *room = (double)limit;
+  return 0;
+}
+// a single determinant (nsocc == n): the mean-field density 2 I, as the other solvers
+static void single_determinant_dm(int n, std::vector<double>& dm) { for (int i = 0; i < n; ++i) dm[(size_t)i * n + i] = 2.0; }
+
 int Fragment::solve_fci(int o, const double* h, const double* dm0, const FragmentOptions& opt, const FciOptions& fopt, int eeval, FragmentResult* res,
                         double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo, double* civec) {
   const int n = n_, v = n - o;
@@ -870,12 +890,10 @@ int Fragment::solve_fci(int o, const double* h, const double* dm0, const Fragmen
   QTRY(check_energy_data(eeval));      // (solve_begin_scf has the check for every solver; here it also keeps its place before the guard)
   int64_t rows = 0;      // the slab height this solve runs with (0: unslabbed), settled by the guard
   {      // the guard: D, G, the Davidson vectors, the tables and the n^4 pieces against what is free (or the fragment's limit), before anything is allocated
-    size_t free_b = 0, total_b = 0;
-    QTRY(dev_mem_info(&free_b, &total_b));
-    double room = (double)free_b;
-    if (fci_mem_limit_ >= 0 && (double)fci_mem_limit_ < room) room = (double)fci_mem_limit_;
+    double room = 0.0;
+    QTRY(device_room(fci_mem_limit_, &room));
     const int64_t ns = fci_string_count(n, o);
-    const double need = (double)fci_bytes(n, o, fopt.max_space);
+    const double need = (double)fci_bytes_slab(n, o, fopt.max_space, 0);
     if (v > 0 && fci_slab_ != 0 && !(fci_slab_ < 0 && need <= room)) {      // a slabbed solve: its own figure against the same room
       rows = fci_slab_ > 0 ? std::min(fci_slab_, ns) : fci_rows_that_fit(n, o, fopt.max_space, room);
       const int64_t r1 = rows > 0 ? rows : 1;
@@ -906,9 +924,7 @@ int Fragment::solve_fci(int o, const double* h, const double* dm0, const Fragmen
     const int64_t N = T->ndet();
     DBuf Vao, CC, Vmo;
     QTRY(fci_mo_integrals(C, Vao, CC, Vmo));
-    std::vector<double> hmo((size_t)n2, 0.0), tmp((size_t)n2, 0.0);      // h in the fragment-MO basis: C^T h C
-    for (int p = 0; p < n; ++p) for (int nu = 0; nu < n; ++nu) { double s = 0; for (int mu = 0; mu < n; ++mu) s += C[(size_t)mu * n + p] * h[(size_t)mu * n + nu]; tmp[(size_t)p * n + nu] = s; }
-    for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int nu = 0; nu < n; ++nu) s += tmp[(size_t)p * n + nu] * C[(size_t)nu * n + q]; hmo[(size_t)p * n + q] = s; }
+    const std::vector<double> hmo = mo_one_body(n, C, h);
     QTRY(fci_c_.alloc(N));
     FciResult fr;
     QTRY(fci_davidson(*T, hmo.data(), Vmo, fopt, fci_c_, &fr, rows));
@@ -924,14 +940,14 @@ int Fragment::solve_fci(int o, const double* h, const double* dm0, const Fragmen
     if (eeval) QTRY(G2.alloc(n2 * n2));
     QTRY(fci_rdm12(*T, fci_c_, o, dm.data(), eeval ? G2.p : nullptr, rows));
     if (eeval && nf_ > 0) QTRY(fci_e2_sites(CC, G2, Vao, e2));
-  } else {      // a single determinant: the mean-field results, as the other solvers
-    for (int i = 0; i < n; ++i) dm[(size_t)i * n + i] = 2.0;
+  } else {
+    single_determinant_dm(n, dm);
     if (civec) civec[0] = 1.0;
   }
   return finish_solve(nullptr, dm, e2, QEMB_RDM2_FCI, false, unconverged, mo_coeff, mo_energy, rdm1_emb, rdm1_mo);
 }
 
-// ---- solver == "SCI-hip": the fragment RHF, then the heat-bath selection of sci.cpp on the integrals of solve_fci; the tail is solve_fci's
+// ---- solver == "SCI-hip": the fragment RHF, then the heat-bath selection of sci.cpp on the integrals of solve_fci; front and tail share its helpers
 int Fragment::solve_sci(int o, const double* h, const double* dm0, const FragmentOptions& opt, const SciOptions& sopt, int eeval, FragmentResult* res,
                         double* mo_coeff, double* mo_energy, double* rdm1_emb, double* rdm1_mo) {
   const int n = n_, v = n - o;
@@ -945,10 +961,8 @@ int Fragment::solve_sci(int o, const double* h, const double* dm0, const Fragmen
   QTRY(check_energy_data(eeval));
   int64_t room_left = -1;
   {      // the guard: what max_det fixes against what is free (or the fragment's limit), before anything is allocated; the CSR arrays get what is left
-    size_t free_b = 0, total_b = 0;
-    QTRY(dev_mem_info(&free_b, &total_b));
-    double room = (double)free_b;
-    if (sci_mem_limit_ >= 0 && (double)sci_mem_limit_ < room) room = (double)sci_mem_limit_;
+    double room = 0.0;
+    QTRY(device_room(sci_mem_limit_, &room));
     const double need = (double)sci_bytes(n, o, sopt.max_det, sopt.max_space);
     if (v > 0 && need > room) {
       set_error("Fragment::solve_sci: n = " + std::to_string(n) + ", eps_var = " + eps_txt + ", max_det = " + std::to_string(sopt.max_det) + " give a working set of " +
@@ -966,9 +980,7 @@ int Fragment::solve_sci(int o, const double* h, const double* dm0, const Fragmen
   if (v > 0) {
     DBuf Vao, CC, Vmo;
     QTRY(fci_mo_integrals(C, Vao, CC, Vmo));
-    std::vector<double> hmo((size_t)n2, 0.0), tmp((size_t)n2, 0.0);      // h in the fragment-MO basis: C^T h C
-    for (int p = 0; p < n; ++p) for (int nu = 0; nu < n; ++nu) { double s = 0; for (int mu = 0; mu < n; ++mu) s += C[(size_t)mu * n + p] * h[(size_t)mu * n + nu]; tmp[(size_t)p * n + nu] = s; }
-    for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) { double s = 0; for (int nu = 0; nu < n; ++nu) s += tmp[(size_t)p * n + nu] * C[(size_t)nu * n + q]; hmo[(size_t)p * n + q] = s; }
+    const std::vector<double> hmo = mo_one_body(n, C, h);
     SciSpace V; SciMatrix H; SciResult sr;
     QTRY(sci_solve(n, o, hmo.data(), Vmo, sopt, room_left, V, H, &sr));
     res->n_iter = sr.n_apply; res->ccsd_converged = sr.converged && sr.diag_converged;
@@ -995,8 +1007,7 @@ int Fragment::solve_sci(int o, const double* h, const double* dm0, const Fragmen
     if (rc >= 0) { sci_V_ = std::move(V); sci_res_ = sr; }      // 24 bytes per determinant stay (run_scf dropped the last solve's through forget_solve)
     return rc;
   }
-  // a single determinant: the mean-field results, as the other solvers
-  for (int i = 0; i < n; ++i) dm[(size_t)i * n + i] = 2.0;
+  single_determinant_dm(n, dm);
   const int rc = finish_solve(nullptr, dm, e2, QEMB_RDM2_SCI, false, unconverged, mo_coeff, mo_energy, rdm1_emb, rdm1_mo);
   if (rc >= 0) { sci_res_ = SciResult(); sci_res_.ndet = 1; sci_res_.nnz = 1; sci_res_.converged = true; sci_res_.e = res->e_scf; }
   return rc;
@@ -1044,10 +1055,8 @@ int Fragment::rdm2(int kind, int with_dm1, double* out, bool out_on_device) {
   const int n = n_, o = last_o_, v = n - o;
   const int64_t n2 = (int64_t)n * n;
   // ---- the guard: tensor + workspace against what is free (or the fragment's limit), before anything is allocated
-  size_t free_b = 0, total_b = 0;
-  QTRY(dev_mem_info(&free_b, &total_b));
-  double room = (double)free_b;
-  if (rdm2_mem_limit_ >= 0 && (double)rdm2_mem_limit_ < room) room = (double)rdm2_mem_limit_;
+  double room = 0.0;
+  QTRY(device_room(rdm2_mem_limit_, &room));
   int64_t fci_rows = 0;      // the slab height of an FCI 2-RDM (set_fci_slab): given, or under -1 the largest that fits when the whole D does not
   if (kind == QEMB_RDM2_FCI && v > 0 && fci_slab_ != 0) {
     const int64_t ns = fci_string_count(n, o), per_row = 8 * n2 * ns;

@@ -132,84 +132,24 @@ int sci_build(int n, const double* h_dev, const double* V_dev, const uint64_t* k
   return dev_sync();      // (the run offsets and counts go back to the pool on return)
 }
 
-// fci_davidson over the CSR product: the same small eigenproblem, orthogonalisation, collapse and sign rule; the start vector is handed in
+// fci_detail::davidson over the CSR product, from the handed-in vector
 int sci_davidson(const SciMatrix& H, const SciOptions& opt, double* c, FciResult* res) {
   const int64_t N = H.N;
   if (opt.max_space < 2 || opt.max_cycle < 1 || !(opt.conv_tol > 0.0) || !(opt.lindep >= 0.0)) {
     set_error("sci: need max_space >= 2, max_cycle >= 1, conv_tol > 0 and lindep >= 0"); return QEMB_ERR_ARG;
   }
-  const int ms = (int)std::min<int64_t>(opt.max_space, N);
-  *res = FciResult();
-  auto apply = [&](const double* x, double* y) { return dev_sci_spmv(N, H.rp(), H.ci(), H.val, x, y); };
-  DBuf r, t, u, scal;
-  QTRY(r.alloc(N)); QTRY(t.alloc(N)); QTRY(u.alloc(N)); QTRY(scal.alloc(8));
-  std::vector<DBuf> B((size_t)ms), S((size_t)ms);
-  for (int j = 0; j < ms; ++j) { QTRY(B[j].alloc(N)); QTRY(S[j].alloc(N)); }
-  auto ptrs = [&](const std::vector<DBuf>& X, int cnt) { std::vector<const double*> p((size_t)cnt); for (int j = 0; j < cnt; ++j) p[j] = X[j].p; return p; };
-  std::vector<double> Hs((size_t)ms * ms, 0.0), row((size_t)ms), y, w, A;
   double cc = 0.0;
-  { std::vector<const double*> self(1, c); QTRY(dots(N, c, self, scal, &cc)); }
-  if (!(cc > 0.0)) { set_error("sci_davidson: the start vector is zero"); return QEMB_ERR_ARG; }
-  QTRY(axpby(N, 1.0 / std::sqrt(cc), c, 0.0, B[0]));
-  QTRY(apply(B[0], S[0]));
-  res->n_iter = 1;
-  int m = 1;
-  QTRY(dots(N, S[0], ptrs(B, 1), scal, row.data()));
-  Hs[0] = row[0];
-  for (;;) {
-    A.assign((size_t)m * m, 0.0);
-    for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) A[(size_t)i * m + j] = Hs[(size_t)i * ms + j];
-    std::vector<double> Vv;
-    small_eigh(m, A, w, Vv);
-    y.assign((size_t)m, 0.0);
-    for (int j = 0; j < m; ++j) y[j] = Vv[(size_t)j * m];
-    const double theta = w[0];
-    std::vector<double> cy(y), cb((size_t)m);
-    for (int j = 0; j < m; ++j) cb[j] = -theta * y[j];
-    QTRY(combine(N, cy, ptrs(S, m), false, r));
-    QTRY(combine(N, cb, ptrs(B, m), true, r));
-    double rr = 0.0;
-    { std::vector<const double*> self(1, r.p); QTRY(dots(N, r, self, scal, &rr)); }
-    res->e = theta; res->residual = std::sqrt(rr > 0.0 ? rr : 0.0);
-    res->converged = res->residual <= opt.conv_tol;
-    bool stop = res->converged || res->n_iter >= opt.max_cycle;
-    if (!stop) {
-      if (m == ms) {      // collapse to the current Ritz vector (and its image)
-        QTRY(combine(N, y, ptrs(B, m), false, t));
-        QTRY(combine(N, y, ptrs(S, m), false, u));
-        QTRY(dcopy(N, t, B[0])); QTRY(dcopy(N, u, S[0]));
-        m = 1; Hs[0] = theta; y.assign(1, 1.0);
-      }
-      QTRY(dev_fci_precond(N, r, H.hdiag, theta, t));
-      for (int pass = 0; pass < 2; ++pass) {
-        QTRY(dots(N, t, ptrs(B, m), scal, row.data()));
-        std::vector<double> neg((size_t)m);
-        for (int j = 0; j < m; ++j) neg[j] = -row[j];
-        QTRY(combine(N, neg, ptrs(B, m), true, t));
-      }
-      double tt = 0.0;
-      { std::vector<const double*> self(1, t.p); QTRY(dots(N, t, self, scal, &tt)); }
-      const double tn = std::sqrt(tt > 0.0 ? tt : 0.0);
-      if (!(tn > opt.lindep) || m == ms) stop = true;      // nothing left to add (m == ms: the space itself has one dimension)
-      else {
-        QTRY(axpby(N, 1.0 / tn, t, 0.0, B[m]));
-        QTRY(apply(B[m], S[m]));
-        res->n_iter += 1;
-        QTRY(dots(N, S[m], ptrs(B, m + 1), scal, row.data()));
-        for (int j = 0; j <= m; ++j) Hs[(size_t)m * ms + j] = Hs[(size_t)j * ms + m] = row[j];
-        ++m;
-        continue;
-      }
-    }
-    QTRY(combine(N, y, ptrs(B, m), false, c));
-    std::vector<double> ch((size_t)N);
-    QTRY(dev_d2h(ch.data(), c, sizeof(double) * N));
-    double nrm = 0.0; int64_t big = 0;
-    for (int64_t I = 0; I < N; ++I) { nrm += ch[(size_t)I] * ch[(size_t)I]; if (std::fabs(ch[(size_t)I]) > std::fabs(ch[(size_t)big])) big = I; }
-    const double scale = (ch[(size_t)big] < 0.0 ? -1.0 : 1.0) / std::sqrt(nrm);
-    if (scale != 1.0) QTRY(axpby(N, scale, c, 0.0, c));
-    return dev_sync();
+  {
+    DBuf scal;
+    QTRY(scal.alloc(8));
+    std::vector<const double*> self(1, c);
+    QTRY(dots(N, c, self, scal, &cc));
   }
+  if (!(cc > 0.0)) { set_error("sci_davidson: the start vector is zero"); return QEMB_ERR_ARG; }
+  QTRY(axpby(N, 1.0 / std::sqrt(cc), c, 0.0, c));
+  auto apply = [&](const double* x, double* y) { return dev_sci_spmv(N, H.rp(), H.ci(), H.val, x, y); };
+  QTRY(davidson(N, apply, H.hdiag, opt.conv_tol, opt.max_cycle, opt.max_space, opt.lindep, false, c, res));
+  return dev_sync();
 }
 
 int sci_rdm12(int n, const uint64_t* keys, int64_t N, const int64_t* rowptr, const int32_t* col, const double* c, int o_cum, double* dm1_host, double* dm2_dev) {
@@ -220,7 +160,7 @@ int sci_rdm12(int n, const uint64_t* keys, int64_t N, const int64_t* rowptr, con
   QTRY(dev_fill(d1, n2, 0.0)); QTRY(dev_fill(dm2_dev, n2 * n2, 0.0));
   QTRY(dev_sci_rdm(n, N, keys, rowptr, col, c, d1, dm2_dev));
   QTRY(dev_d2h(dm1_host, d1, sizeof(double) * n2));
-  for (int p = 0; p < n; ++p) for (int q = 0; q < p; ++q) { const double s = 0.5 * (dm1_host[p * n + q] + dm1_host[q * n + p]); dm1_host[p * n + q] = dm1_host[q * n + p] = s; }
+  symmetrise_dm1(n, dm1_host);
   if (o_cum >= 0) {
     QTRY(dev_h2d(d1, dm1_host, sizeof(double) * n2));
     QTRY(dev_sci_dm2_finish(n, o_cum, d1, dm2_dev));

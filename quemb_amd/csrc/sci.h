@@ -42,7 +42,7 @@ struct SciResult {
 // single and double excitations of one determinant with nsocc electrons per spin in n orbitals; keys of the candidate buffer of one slab (a power of two that
 // holds every excitation of one determinant and its partner); device bytes of a solve WITHOUT the CSR arrays, whose size is known only once a round has counted
 // them: three key lists and vectors of max_det, the candidate buffer with its flags and offsets, the slab's lane counts, the Davidson basis with its images and
-// work vectors, the row pointers and the n^4 pieces (V, the 2-RDM).  The CSR arrays (12 bytes per stored element) are checked against what is left each round.
+// four work vectors (residual, correction, diagonal, the kept vector), the row pointers and the n^4 pieces (V, the 2-RDM).  The CSR arrays (12 bytes per stored element) are checked against what is left each round.
 int64_t sci_excitations(int n, int nsocc);
 int64_t sci_candidate_capacity(int n, int nsocc);
 int64_t sci_bytes(int n, int nsocc, int64_t max_det, int max_space);
@@ -58,7 +58,8 @@ int sci_screen(int n, int nsocc, const double* h_dev, const double* V_dev, doubl
 int sci_merge(const SciSpace& V, const uint64_t* joined, int64_t njoined, SciSpace& out);
 // the CSR matrix over the sorted keys (h_dev = V_dev = null: its row pointers and columns alone, 4 bytes per stored element); max_bytes >= 0: QEMB_ERR_ALLOC (message starting with `who`) when the arrays would take more
 int sci_build(int n, const double* h_dev, const double* V_dev, const uint64_t* keys, int64_t N, int64_t max_bytes, const std::string& who, SciMatrix& H);
-// lowest eigenpair of H from the start vector c (device, N, any norm > 0); c receives the normalised vector, largest-magnitude component positive
+// lowest eigenpair of H from the start vector c (device, N, any norm > 0; a zero vector: QEMB_ERR_ARG) by fci_detail::davidson (fci.h) over the CSR product with
+// H.hdiag as the preconditioner's diagonal; c receives the normalised vector (plain sum of c_I^2), largest-magnitude component positive
 int sci_davidson(const SciMatrix& H, const SciOptions& opt, double* c, FciResult* res);
 // dm1 (host, symmetrised) and dm2[p,q,r,s] = <p+ r+ s q> (n^4 doubles, device; may be null) of the vector over the stored pairs; o_cum >= 0: minus the mean-field part
 int sci_rdm12(int n, const uint64_t* keys, int64_t N, const int64_t* rowptr, const int32_t* col, const double* c, int o_cum, double* dm1_host, double* dm2_dev);

@@ -9,6 +9,7 @@
 // rdm        one wavefront per row, one lane per stored pair: the excitation is recomputed from the two keys and its contributions are added with FP64 atomics.
 // Everything but the RDM pass has one owner per output element and a fixed order of additions: the same bits on every call.
 #include "hip_common.h"
+#include "cumulant_core.h"
 #include "sci_core.h"
 
 namespace qemb {
@@ -185,17 +186,14 @@ __global__ void __launch_bounds__(256) sci_rdm_kernel(int n, long long N, const 
   }
 }
 
-// dm2 -= nc, the mean-field part as dev_fci_dm2 states it (hf = 2 I_occ over the first o_cum orbitals, del = dm1 - hf)
+// dm2 -= nc, the mean-field part of cumulant_core.h
 __global__ void __launch_bounds__(256) sci_dm2_finish_kernel(int n, int o_cum, const double* __restrict__ dm1, double* __restrict__ dm2) {
   const long long n2 = (long long)n * n;
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= n2 * n2) return;
   const int pq = (int)(idx / n2), rs = (int)(idx - pq * n2);
   const int p = pq / n, q = pq - p * n, r = rs / n, s = rs - r * n;
-  const double hf_pq = (p == q && p < o_cum) ? 2.0 : 0.0, hf_rs = (r == s && r < o_cum) ? 2.0 : 0.0;
-  const double hf_ps = (p == s && p < o_cum) ? 2.0 : 0.0, hf_qr = (q == r && q < o_cum) ? 2.0 : 0.0;
-  const double d_pq = dm1[p * n + q] - hf_pq, d_rs = dm1[r * n + s] - hf_rs, d_ps = dm1[p * n + s] - hf_ps, d_qr = dm1[q * n + r] - hf_qr;
-  dm2[idx] -= hf_pq * hf_rs + hf_pq * d_rs + d_pq * hf_rs - 0.5 * (hf_ps * hf_qr + hf_ps * d_qr + d_ps * hf_qr);
+  dm2[idx] -= cumulant_mean_field(n, o_cum, dm1, p, q, r, s);
 }
 
 inline bool grid_for(const char* who, long long items, int per_block, unsigned* grid) {

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <utility>
 #include <vector>
+#include "cumulant_core.h"
 #include "sci_core.h"
 
 namespace qemb {
@@ -153,14 +154,8 @@ int dev_sci_rdm(int n, int64_t N, const uint64_t* keys, const int64_t* rowptr, c
 }
 int dev_sci_dm2_finish(int n, int o_cum, const double* dm1, double* dm2) {
   if (n <= 0 || n > kSciMaxOrb || o_cum < 0 || o_cum > n || !dm1 || !dm2) { set_error("dev_sci_dm2_finish: bad arguments"); return QEMB_ERR_ARG; }
-  const int64_t n2 = (int64_t)n * n, n3 = n2 * n;
-  auto hf = [&](int i, int j) { return (i == j && i < o_cum) ? 2.0 : 0.0; };
-  auto del = [&](int i, int j) { return dm1[i * n + j] - hf(i, j); };
-  for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) for (int k = 0; k < n; ++k) for (int l = 0; l < n; ++l) {      // the statements of molbe/solver.py:513-527
-    const double x = hf(i, j) * hf(k, l) + hf(i, j) * del(k, l) + del(i, j) * hf(k, l);
-    dm2[i * n3 + j * n2 + k * n + l] -= x;
-    dm2[i * n3 + k * n2 + l * n + j] += 0.5 * x;
-  }
+  int64_t idx = 0;
+  for (int p = 0; p < n; ++p) for (int q = 0; q < n; ++q) for (int r = 0; r < n; ++r) for (int s = 0; s < n; ++s) dm2[idx++] -= cumulant_mean_field(n, o_cum, dm1, p, q, r, s);
   return 0;
 }
 

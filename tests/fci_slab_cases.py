@@ -29,6 +29,8 @@ def slab_heights(n, o):
 
 
 CASES = [(n, o, r) for n, o in SHAPES for r in slab_heights(n, o)]
+# the collapse of the Davidson basis: unslabbed, two rows per slab, one slab of ns rows
+COLLAPSE = [(n, o, r) for n, o in [(4, 2), (6, 3), (7, 3)] for r in (0, 2, comb(n, o))]
 
 
 def solve(lib, n, o, rows, fci_opts=None):
@@ -107,8 +109,26 @@ def check_slab_equals_unslabbed_and_twin(lib, n, o, rows):
           + " ".join(f"{k}={v:.2e}" for k, v in a.items()) + "; unslabbed: " + " ".join(f"{k}={v:.2e}" for k, v in b.items()))
 
 
+def check_collapse(lib, n, o, rows):
+    """max_space = 2: the basis collapses to the Ritz vector (and its image) after every second application of H -- the default max_space = 12 never gets there,
+    every solve of these files converges in 6 to 8 applications.  The collapsed solve is held to the twin and to the default-options solve at the bars above;
+    n_iter > max_space says the collapse ran."""
+    from quemb_amd.fragsolver import default_fci_opts
+    base, ref = unslabbed(lib, n, o)
+    fo = default_fci_opts(lib, max_space=2, max_cycle=400)
+    out = solve(lib, n, o, rows, fci_opts=fo)      # (strict convergence is the default: a solve that did not converge raises)
+    ns = comb(n, o)
+    assert out["slab_used"] == ((rows, -(-ns // rows)) if rows else (0, 1))
+    assert out["residual"] <= fo.conv_tol and fo.max_space < out["n_iter"] <= fo.max_cycle, (out["residual"], out["n_iter"])
+    a = check_against_twin(out, ref, n, o)
+    b = check_against_unslabbed(out, base)
+    print(f"collapse ({n},{o}) rows = {rows}: n_iter = {out['n_iter']} (max_space = 12: {base['n_iter']}) residual = {out['residual']:.2e}; twin: "
+          + " ".join(f"{k}={v:.2e}" for k, v in a.items()) + "; default options: " + " ".join(f"{k}={v:.2e}" for k, v in b.items()))
+
+
 def check_ops(lib, n, o):
-    """one application of H and the RDM build on handed-in data, slab by slab, at the bars of fc.check_sigma and fc.check_rdm_op"""
+    """one application of H and the RDM build on handed-in data, slab by slab, at the bars of fc.check_sigma and fc.check_rdm_op; one slab (rows >= ns) is the
+    whole space bit for bit: the same code"""
     from quemb_amd.fragsolver import fci_rdm12, fci_sigma
     h, e1 = fc.inputs(n, o)[:2]
     ns = comb(n, o)
@@ -116,6 +136,12 @@ def check_ops(lib, n, o):
     ref = fnp.sigma(h, e1, c, o)
     cn = c / np.linalg.norm(c)
     r1, r2 = fnp.rdm12(cn, n, o)
+    whole = fci_sigma(h, e1, c, o, lib=lib), fci_rdm12(cn, n, o, lib=lib), fci_rdm12(cn, n, o, cumulant=True, lib=lib)
+    for rows in (ns, ns + 5):
+        assert np.array_equal(fci_sigma(h, e1, c, o, lib=lib, slab_rows=rows), whole[0]), rows
+        for cumulant in (False, True):
+            dm1, dm2 = fci_rdm12(cn, n, o, cumulant=cumulant, lib=lib, slab_rows=rows)
+            assert np.array_equal(dm1, whole[1 + cumulant][0]) and np.array_equal(dm2, whole[1 + cumulant][1]), (rows, cumulant)
     for rows in slab_heights(n, o):
         s = fci_sigma(h, e1, c, o, lib=lib, slab_rows=rows)
         print(f"sigma ({n},{o}) rows = {rows}: max |d| = {np.abs(s - ref).max():.2e}, max |sigma| = {np.abs(ref).max():.2e}")

@@ -241,6 +241,27 @@ def check_solve(lib, n, o, family):
     assert abs(np.trace(out["rdm1_mo"]) - 2 * o) < 1e-10
 
 
+def check_collapse(lib, n=10, o=5, family="default", max_space=2):
+    """max_space = 2: the Davidson basis of every diagonalisation collapses to the Ritz vector after its second application of H, which the default max_space = 12
+    never reaches.  The same determinants and rounds as the default-options solve of `solved`, energy, vector, densities and fragment energies at the bars above;
+    more than max_space applications per round on average says that a collapse ran."""
+    from quemb_amd.fragsolver import default_sci_opts
+    base = solved(lib, n, o, family)[0]
+    so = default_sci_opts(lib, eps_var=1e-3, max_space=max_space, max_cycle=400)
+    fr = fragment(lib, n, o, family)
+    out = fr.solve_sci(o, inputs(n, o, family)[0], opts=scf_opts(lib), sci_opts=so, eeval=True, want_dets=True)      # (strict: raises unless every diagonalisation converged)
+    out["dm2"] = fr.make_rdm2("SCI-hip", with_dm1=True)
+    out["dm2_cumulant"] = fr.make_rdm2("SCI-hip", with_dm1=False)
+    fr.free()
+    assert all(np.array_equal(x, y) for x, y in zip(out["dets"][:2], base["dets"][:2])) and out["rounds"] == base["rounds"] and out["nnz"] == base["nnz"]
+    assert out["residual"] <= so.conv_tol and out["n_iter"] > max_space * out["rounds"], (out["residual"], out["n_iter"], out["rounds"])
+    errs = {k: float(np.abs(np.asarray(out[k]) - np.asarray(base[k])).max()) for k in ("e_sci", "rdm1_mo", "rdm1_emb", "dm2", "dm2_cumulant", "e_frag")}
+    errs["c"] = float(np.abs(out["dets"][2] - base["dets"][2]).max())
+    print(f"collapse ({n},{o}) {family}: n_iter = {out['n_iter']} in {out['rounds']} rounds (max_space = 12: {base['n_iter']}) residual = {out['residual']:.2e} "
+          + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
+    assert errs["c"] < 1e-7 and max(v for k, v in errs.items() if k != "c") < TOL, errs
+
+
 def check_frags_energy(lib, n=5, o=2):
     """Frags.solve(solver="SCI-hip") for both values of use_cumulant against the oracle's get_frag_energy fed with the twin's RDMs"""
     from quemb_amd.pfrag import Frags

@@ -31,6 +31,11 @@ def test_slabbed_equals_unslabbed_equals_twin(hlib, n, o, rows):
     sc.check_slab_equals_unslabbed_and_twin(hlib, n, o, rows)
 
 
+@pytest.mark.parametrize("n,o,rows", sc.COLLAPSE)
+def test_collapse_of_the_davidson_basis(hlib, n, o, rows):
+    sc.check_collapse(hlib, n, o, rows)
+
+
 def test_two_slabbed_solves_same_bits(hlib):
     sc.check_deterministic(hlib)
 

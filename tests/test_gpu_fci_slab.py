@@ -43,6 +43,11 @@ def test_mid_size_twelve_orbitals_in_ten_slabs(qlib):
     assert abs(np.trace(outs[1]["rdm1_mo"]) - 2 * o) < 1e-10
 
 
+@pytest.mark.parametrize("n,o,rows", sc.COLLAPSE)
+def test_collapse_of_the_davidson_basis(qlib, n, o, rows):
+    sc.check_collapse(qlib, n, o, rows)
+
+
 def test_two_slabbed_solves_same_bits(qlib):
     sc.check_deterministic(qlib)
 

@@ -42,6 +42,10 @@ def test_solve(qlib, n, o, family):
     sc.check_solve(qlib, n, o, family)
 
 
+def test_collapse_of_the_davidson_basis(qlib):
+    sc.check_collapse(qlib)
+
+
 def test_frags_energy_for_both_values_of_use_cumulant(qlib):
     sc.check_frags_energy(qlib)
 

@@ -118,6 +118,10 @@ def test_solve(hlib, n, o, family):
     sc.check_solve(hlib, n, o, family)
 
 
+def test_collapse_of_the_davidson_basis(hlib):
+    sc.check_collapse(hlib)
+
+
 def test_frags_energy_for_both_values_of_use_cumulant(hlib):
     sc.check_frags_energy(hlib)
 

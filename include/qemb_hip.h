@@ -208,7 +208,7 @@ int qemb_frag_fci_residual(qemb_frag_t f, double* residual);
  * beyond the determinant-space limit of qemb_frag_solve_fci (n <= 64).  Fragment RHF, h1 and the ERIs in the fragment-MO basis as for FCI; then, from the HF
  * determinant: every determinant outside the space V that a single or double excitation connects to some i in V with |H_ai c_i| >= eps_var joins, with its
  * spin-swapped partner; the lowest eigenpair of H in the new V (CSR matrix over the sorted 2 x 64-bit keys, Davidson from the old vector padded with zeros, residual
- * <= conv_tol); stop when a round adds nothing.  Energy, vector and RDMs are those of the last diagonalisation; no perturbative correction.  The determinant set,
+ * <= conv_tol); stop when a round adds nothing.  Energy, vector and RDMs are those of the last diagonalisation; the perturbative correction is a call of its own (qemb_frag_sci_pt2).  The determinant set,
  * the matrix and the vector are the same bits on every call; the RDMs are accumulated with FP64 atomic adds and reproducible to rounding only.
  * qemb_sci_opts: always start from qemb_default_sci_opts (eps_var 1e-3, conv_tol 1e-9, max_cycle 100, max_space 12, max_round 30, max_det 2^20); NULL means these
  *   defaults; another struct_size or eps_var <= 0 is QEMB_ERR_ARG.  Reaching max_round before a round adds nothing, or a diagonalisation that misses conv_tol, is
@@ -219,7 +219,19 @@ int qemb_frag_fci_residual(qemb_frag_t f, double* residual);
  * qemb_frag_sci_mem_limit): QEMB_ERR_ALLOC naming n, eps_var and the bytes.  Each round the count is checked against max_det and the CSR arrays (12 bytes per stored
  * element, known once counted) against what is left: QEMB_ERR_ALLOC naming n, eps_var, the round, the count reached and the energy so far.
  * qemb_frag_sci_stats: determinants, rounds, stored matrix elements and ||H c - E c||_2 of the last SCI solve (each nullable).
- * qemb_frag_sci_dets: the final space, alpha[ndet], beta[ndet] (bit p = fragment MO p occupied, sorted by (alpha, beta)) and c[ndet] (each nullable). */
+ * qemb_frag_sci_dets: the final space, alpha[ndet], beta[ndet] (bit p = fragment MO p occupied, sorted by (alpha, beta)) and c[ndet] (each nullable).
+ * qemb_frag_sci_pt2: the screened Epstein-Nesbet second-order correction of the last SCI solve of this fragment, from the determinants, the vector and e_sci it left
+ *   on the device (h and V in the fragment-MO basis are formed again from the resident ERIs or factor and the kept orbitals):
+ *     S_a = sum over i in V with |H_ai c_i| >= eps_pt of H_ai c_i,   e_pt2 = sum_a S_a^2 / (e_sci - H_aa),
+ *   a over the n_ext determinants outside V with at least one passing product and their spin-swapped partners.  Denominators are not guarded.  After a converged
+ *   solve eps_pt >= eps_var gives exactly 0 and n_ext = 0; eps_pt -> 0 gives the full second-order correction.  A diagnostic of the embedding problem: it enters no
+ *   fragment or BE energy.  The externals are handled in ranges of the alpha word of at most max_ext determinants (batches: how many ranges), summed in ascending
+ *   order: the same bits on every call with the same max_ext.  max_ext <= 0: the largest count that fits.  ms3: host wall time (ms) of the screen passes, the sorts /
+ *   merges and the row passes.  Every output is nullable.  nsocc == n: zeros.
+ *   Errors: eps_pt <= 0, no solve since the ERIs or orbitals were set, or a last solve that was not SCI: QEMB_ERR_ARG.  Before anything is allocated the working set
+ *   (qemb_frag_sci_pt2_bytes: 40 bytes per external, the candidate buffer of the screen, the run starts, the n^4 pieces) is compared with min(free device memory, the
+ *   limit of qemb_frag_sci_mem_limit): QEMB_ERR_ALLOC naming n, eps_pt and the bytes.  One alpha word with more than max_ext externals: QEMB_ERR_ALLOC naming n,
+ *   eps_pt, max_ext and the count reached. */
 typedef struct {
   uint32_t struct_size;      /* sizeof(qemb_sci_opts); set by qemb_default_sci_opts, checked by every entry point that takes the struct */
   double eps_var;            /* threshold on |H_ai c_i|   default 1e-3 (the reference's hci_cutoff) */
@@ -237,6 +249,8 @@ int qemb_frag_sci_stats(qemb_frag_t f, int64_t* ndet, int* rounds, int64_t* nnz,
 int qemb_frag_sci_dets(qemb_frag_t f, uint64_t* alpha, uint64_t* beta, double* c);
 int qemb_frag_sci_bytes(int n, int nsocc, int64_t max_det, int max_space, int64_t* bytes);
 int qemb_frag_sci_mem_limit(qemb_frag_t f, int64_t bytes);
+int qemb_frag_sci_pt2(qemb_frag_t f, double eps_pt, int64_t max_ext, double* e_pt2, int64_t* n_ext, int* batches, double* ms3);
+int qemb_frag_sci_pt2_bytes(int n, int nsocc, int64_t ndet, int64_t max_ext, int64_t* bytes);
 /* The fragment 2-RDM in the fragment-MO basis, Frags.rdm2__ (molbe/solver.py:528): out[n^4] (host, [p][q][r][s]) from what the LAST solve of this fragment
  * left on the device.  kind names that solve and must agree with it:
  *   QEMB_RDM2_CCSD  make_rdm2_urlx(t1, t2, with_dm1) of shared/external/ccsd_rdm.py:23-55 (unrelaxed), from the kept t1 / t2 of qemb_frag_solve[_batch];

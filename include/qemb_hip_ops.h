@@ -301,12 +301,15 @@ int qemb_op_fci_links(int n, int nsocc, int64_t* ns, int* nlink, int32_t* string
  * (64-bit occupation words, bit p = orbital p occupied) sorted by (alpha, beta); every array but V_dev ([n^2][n^2] = (pq|rs)) is a host array.
  * qemb_op_sci_screen: the determinants outside the space that pass |H_ai c_i| >= eps for some member i, spin partners included, sorted; slab / cap: determinants per
  *   pass and keys of the candidate buffer (0: the defaults); *njoined always, the keys when njoined <= max_out.
+ * qemb_op_sci_pt2: the second-order correction of qemb_frag_sci_pt2 for a handed-in space, vector and e_var (max_ext <= 0: no bound; outputs nullable).
  * qemb_op_sci_merge: the space merged with sorted keys outside it, the vector padded with zeros (outputs: ndet + njoined).
  * qemb_op_sci_matrix: the CSR matrix of H over the space (both triangles, columns ascending, the diagonal included): *nnz and rowptr[ndet + 1] always, col / val when
  *   nnz <= max_nnz.   qemb_op_sci_spmv: y = H x.   qemb_op_sci_rdm12: dm1 [n][n] (symmetrised) and dm2 [n]^4 of the vector c; cumulant != 0: minus the mean-field part.
  * qemb_frag_sci_stage_ms: host wall time (ms) of the five stages of the fragment's last SCI solve: screen, sort / merge, matrix, Davidson, RDMs (tools/sci_bench.py). */
 int qemb_op_sci_screen(int n, int nsocc, const double* h_host, const double* V_dev, int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, double eps,
                        int64_t slab, int64_t cap, int64_t max_out, int64_t* njoined, uint64_t* out_alpha, uint64_t* out_beta);
+int qemb_op_sci_pt2(int n, int nsocc, const double* h_host, const double* V_dev, int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, double e_var, double eps_pt,
+                    int64_t max_ext, int64_t slab, int64_t cap, double* e_pt2, int64_t* n_ext, int* batches);
 int qemb_op_sci_merge(int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, int64_t njoined, const uint64_t* jalpha, const uint64_t* jbeta,
                       uint64_t* out_alpha, uint64_t* out_beta, double* out_c);
 int qemb_op_sci_matrix(int n, const double* h_host, const double* V_dev, int64_t ndet, const uint64_t* alpha, const uint64_t* beta, int64_t max_nnz, int64_t* nnz,

@@ -226,6 +226,9 @@ def _declare(lib):
     f("qemb_frag_sci_dets", I, V, P, P, P)
     f("qemb_frag_sci_bytes", I, I, I, L, I, C.POINTER(L))
     f("qemb_frag_sci_mem_limit", I, V, L)
+    f("qemb_frag_sci_pt2", I, V, D, L, DP, C.POINTER(L), IP, P)
+    f("qemb_frag_sci_pt2_bytes", I, I, I, L, L, C.POINTER(L))
+    f("qemb_op_sci_pt2", I, I, I, P, P, L, P, P, P, D, D, L, L, L, DP, C.POINTER(L), IP)
     f("qemb_op_sci_screen", I, I, I, P, P, L, P, P, P, D, L, L, L, C.POINTER(L), P, P)
     f("qemb_op_sci_merge", I, L, P, P, P, L, P, P, P, P, P)
     f("qemb_op_sci_matrix", I, I, P, P, L, P, P, L, C.POINTER(L), P, P, P)

@@ -737,6 +737,16 @@ int qemb_frag_sci_bytes(int n, int nsocc, int64_t max_det, int max_space, int64_
   return QEMB_OK;
 }
 int qemb_frag_sci_mem_limit(qemb_frag_t f, int64_t bytes) { CHECK_FRAG(f); FRAG(f)->set_sci_mem_limit(bytes); return QEMB_OK; }
+int qemb_frag_sci_pt2(qemb_frag_t f, double eps_pt, int64_t max_ext, double* e_pt2, int64_t* n_ext, int* batches, double* ms3) {
+  CHECK_FRAG(f);
+  return FRAG(f)->sci_pt2(eps_pt, max_ext, e_pt2, n_ext, batches, ms3);
+}
+int qemb_frag_sci_pt2_bytes(int n, int nsocc, int64_t ndet, int64_t max_ext, int64_t* bytes) {
+  if (n <= 0 || nsocc <= 0 || nsocc > n || ndet < 1 || max_ext < 1 || !bytes) { set_error("qemb_frag_sci_pt2_bytes: bad arguments"); return QEMB_ERR_ARG; }
+  if (n > kSciMaxOrb) { set_error("qemb_frag_sci_pt2_bytes: n = " + std::to_string(n) + " embedding orbitals; the selected CI takes at most " + std::to_string(kSciMaxOrb)); return QEMB_ERR_UNSUPPORTED; }
+  *bytes = Fragment::sci_pt2_work_bytes(n, nsocc, ndet, max_ext);
+  return QEMB_OK;
+}
 // ---- the operations of the selected CI on handed-in data (host arrays but V_dev); a space: ndet sorted keys alpha[k], beta[k]
 namespace {
 int sci_upload(int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, SciSpace& V) {
@@ -763,13 +773,7 @@ int sci_op_integrals(int n, const double* h_host, const double* V_dev, DBuf& hd,
   if (n <= 0 || n > kSciMaxOrb || !h_host || !V_dev) { set_error("qemb_op_sci: need 0 < n <= 64, h and V"); return QEMB_ERR_ARG; }
   QTRY(hd.alloc(n2));
   QTRY(dev_h2d(hd, h_host, sizeof(double) * n2));
-  if (dbl_bound) {
-    std::vector<double> Vh((size_t)(n2 * n2));
-    QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
-    double m = 0.0;
-    for (double x : Vh) m = std::max(m, std::fabs(x));
-    *dbl_bound = 2.0 * m;
-  }
+  if (dbl_bound) QTRY(sci_double_bound(n, V_dev, dbl_bound));
   return 0;
 }
 }  // namespace
@@ -782,6 +786,18 @@ int qemb_op_sci_screen(int n, int nsocc, const double* h_host, const double* V_d
   QTRY(sci_screen(n, nsocc, hd, V_dev, bound, V, eps, slab, cap, (int64_t)1 << 40, joined, njoined));
   if (*njoined > max_out) return QEMB_OK;      // the count alone: call again with room
   return sci_download((const uint64_t*)joined.p, *njoined, out_alpha, out_beta);
+}
+int qemb_op_sci_pt2(int n, int nsocc, const double* h_host, const double* V_dev, int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, double e_var, double eps_pt,
+                    int64_t max_ext, int64_t slab, int64_t cap, double* e_pt2, int64_t* n_ext, int* batches) {
+  if (!c || !(eps_pt > 0.0) || nsocc <= 0 || nsocc >= n) { set_error("qemb_op_sci_pt2: bad arguments (need c, eps_pt > 0 and 0 < nsocc < n)"); return QEMB_ERR_ARG; }
+  DBuf hd; SciSpace V; double bound = 0.0, e = 0.0; int64_t next = 0; int nb = 0;
+  QTRY(sci_op_integrals(n, h_host, V_dev, hd, &bound));
+  QTRY(sci_upload(ndet, alpha, beta, c, V));
+  const int rc = sci_pt2(n, nsocc, hd, V_dev, bound, V, e_var, eps_pt, max_ext > 0 ? max_ext : (int64_t)1 << 40, slab, cap, &e, &next, &nb);
+  if (e_pt2) *e_pt2 = e;
+  if (n_ext) *n_ext = next;
+  if (batches) *batches = nb;
+  return rc;
 }
 int qemb_op_sci_merge(int64_t ndet, const uint64_t* alpha, const uint64_t* beta, const double* c, int64_t njoined, const uint64_t* jalpha, const uint64_t* jbeta,
                       uint64_t* out_alpha, uint64_t* out_beta, double* out_c) {

@@ -466,10 +466,20 @@ int dev_fci_dm2(int n, int o_cum, const double* A, const double* dm1, double* ou
 //   spmv:    y = H x, one wavefront per row, a fixed shuffle tree: the same bits on every call
 //   rdm:     dm1[p,q] += <q+ p>, dm2[p,q,r,s] += <p+ r+ s q> over the stored pairs with FP64 atomic adds (zeroed by the caller; reproducible to rounding only)
 //   dm2_finish: dm2 -= the mean-field part of molbe/solver.py:513-527 with o_cum occupied orbitals (the form of dev_fci_dm2)
+//   screen_emit with an alpha-word range: a key, and on its own its partner, whose alpha word lies outside [alpha_lo, alpha_hi] is written as the all-ones pad
+//            key (flag_new drops it); the slots stay where they are.  The union over disjoint ranges is the unrestricted output; the defaults cover every word.
+//   pt2_rows: contrib[k] = S^2 / (e_var - H_aa) for the K sorted keys `ext` outside the space, S the sum of the products H_ai c_i with |H_ai c_i| >= eps over the
+//            space (seg: the nseg + 1 run starts of equal alpha, as sci_build forms them).  One wavefront per key, a fixed shuffle tree, no atomics: the same bits
+//            on every call.  The denominator is not guarded.
+//   sum:     out[0] = the sum of m doubles in one fixed order (one workgroup: 1024 strided partial sums, then a tree)
 constexpr int kSciMaxOrb = 64;
 constexpr int kSciScreenLanes = 256;
 int dev_sci_screen_count(int n, const double* h, const double* V, int64_t nd, const uint64_t* keys, const double* c, double eps, double dbl_bound, int32_t* counts);
-int dev_sci_screen_emit(int n, const double* h, const double* V, int64_t nd, const uint64_t* keys, const double* c, double eps, double dbl_bound, const int64_t* offsets, uint64_t* out);
+int dev_sci_screen_emit(int n, const double* h, const double* V, int64_t nd, const uint64_t* keys, const double* c, double eps, double dbl_bound, const int64_t* offsets, uint64_t* out,
+                        uint64_t alpha_lo = 0, uint64_t alpha_hi = ~(uint64_t)0);
+int dev_sci_pt2_rows(int n, const double* h, const double* V, int64_t N, const uint64_t* keys, const double* c, int64_t nseg, const int64_t* seg, int64_t K, const uint64_t* ext,
+                     double e_var, double eps, double dbl_bound, double* contrib);
+int dev_sci_sum(int64_t m, const double* in, double* out);
 int dev_sci_scan(int64_t m, const int32_t* in, int64_t* out);
 int dev_sci_sort(int64_t m, int64_t mpad, uint64_t* keys);
 int dev_sci_flag_new(int64_t m, const uint64_t* cand, int64_t nA, const uint64_t* A, int64_t nB, const uint64_t* B, int32_t* flags);

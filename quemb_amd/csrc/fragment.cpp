@@ -1004,7 +1004,7 @@ int Fragment::solve_sci(int o, const double* h, const double* dm0, const Fragmen
     if (eeval && nf_ > 0) QTRY(fci_e2_sites(CC, G2, Vao, e2));
     H = SciMatrix();      // the matrix goes: 12 bytes per stored element (GBs at 10^9) would stay with every fragment of a sweep; rdm2() forms the pattern again
     const int rc = finish_solve(nullptr, dm, e2, QEMB_RDM2_SCI, false, unconverged, mo_coeff, mo_energy, rdm1_emb, rdm1_mo);
-    if (rc >= 0) { sci_V_ = std::move(V); sci_res_ = sr; }      // 24 bytes per determinant stay (run_scf dropped the last solve's through forget_solve)
+    if (rc >= 0) { sci_V_ = std::move(V); sci_res_ = sr; sci_hmo_ = hmo; sci_C_ = C; }      // 24 bytes per determinant stay (run_scf dropped the last solve's through forget_solve)
     return rc;
   }
   single_determinant_dm(n, dm);
@@ -1027,6 +1027,61 @@ int Fragment::sci_dets(uint64_t* alpha, uint64_t* beta, double* c) const {
   for (int64_t i = 0; i < N; ++i) { if (alpha) alpha[i] = k[(size_t)(2 * i)]; if (beta) beta[i] = k[(size_t)(2 * i + 1)]; }
   if (c) QTRY(dev_d2h(c, sci_V_.c, sizeof(double) * N));
   return 0;
+}
+
+// ---- the second-order correction of the last SCI solve (sci.cpp: sci_pt2), on integrals formed again as rdm2() forms again what it needs
+int64_t Fragment::sci_pt2_work_bytes(int n, int nsocc, int64_t ndet, int64_t max_ext) {
+  const int64_t n2 = (int64_t)n * n;
+  return sci_pt2_bytes(n, nsocc, ndet, max_ext) + 8 * (4 * n2 * n2 + n2);      // Vao, CC, Vmo and the intermediate of fci_mo_integrals; h
+}
+int Fragment::sci_pt2(double eps_pt, int64_t max_ext, double* e_pt2, int64_t* n_ext, int* batches, double* ms3) {
+  double e = 0.0, ms[SCI_PT2_T_COUNT] = {0, 0, 0};
+  int64_t next = 0;
+  int nb = 0;
+  auto hand_out = [&]() {
+    if (e_pt2) *e_pt2 = e;
+    if (n_ext) *n_ext = next;
+    if (batches) *batches = nb;
+    if (ms3) for (int k = 0; k < SCI_PT2_T_COUNT; ++k) ms3[k] = ms[k];
+  };
+  hand_out();
+  if (!(eps_pt > 0.0)) { set_error("Fragment::sci_pt2: eps_pt must be positive"); return QEMB_ERR_ARG; }
+  if (last_kind_ < 0) { set_error("Fragment::sci_pt2: no solve has run on this fragment since its ERIs or orbitals were last set"); return QEMB_ERR_ARG; }
+  if (last_kind_ != QEMB_RDM2_SCI) {
+    set_error(std::string("Fragment::sci_pt2: the last solve of this fragment was ") + (last_kind_ == QEMB_RDM2_MP2 ? "MP2" : last_kind_ == QEMB_RDM2_FCI ? "FCI" : "CCSD") + ", not SCI");
+    return QEMB_ERR_ARG;
+  }
+  const int n = n_, o = last_o_;
+  if (o == n) return 0;      // a single determinant: nothing outside it
+  if (sci_V_.N == 0 || sci_hmo_.empty() || sci_C_.empty()) { set_error("Fragment::sci_pt2: the determinants of the last SCI solve were not kept"); return QEMB_ERR_ARG; }
+  char eps_txt[32];
+  snprintf(eps_txt, sizeof eps_txt, "%.3g", eps_pt);
+  {      // the guard, before anything is allocated
+    double room = 0.0;
+    QTRY(device_room(sci_mem_limit_, &room));
+    if (max_ext <= 0) {      // the largest count that fits beside the integrals (one at the least: the comparison below then refuses)
+      const int64_t integrals = sci_pt2_work_bytes(n, o, sci_V_.N, 0) - sci_pt2_bytes(n, o, sci_V_.N, 0);
+      max_ext = std::max<int64_t>(1, sci_pt2_max_ext(n, o, sci_V_.N, (int64_t)std::min(room, 9e18) - integrals));
+    }
+    const double need = (double)sci_pt2_work_bytes(n, o, sci_V_.N, max_ext);
+    if (need > room) {
+      set_error("Fragment::sci_pt2: n = " + std::to_string(n) + ", eps_pt = " + eps_txt + ", max_ext = " + std::to_string(max_ext) + " over " + std::to_string(sci_V_.N) +
+                " determinants give a working set of " + std::to_string((int64_t)need) + " bytes (" + std::to_string(need * 1e-9) + " GB), more than the " + std::to_string(room * 1e-9) +
+                " GB of device memory it may take");
+      return QEMB_ERR_ALLOC;
+    }
+  }
+  const int64_t n2 = (int64_t)n * n;
+  DBuf Vao, CC, Vmo, hd;
+  QTRY(fci_mo_integrals(sci_C_, Vao, CC, Vmo));
+  Vao.release(); CC.release();
+  QTRY(hd.alloc(n2));
+  QTRY(dev_h2d(hd, sci_hmo_.data(), sizeof(double) * n2));
+  double dbl_bound = 0.0;
+  QTRY(sci_double_bound(n, Vmo, &dbl_bound));
+  const int rc = qemb::sci_pt2(n, o, hd, Vmo, dbl_bound, sci_V_, sci_res_.e, eps_pt, max_ext, 0, 0, &e, &next, &nb, ms);
+  if (rc == 0) hand_out();
+  return rc;
 }
 
 // ---- Frags.rdm2__ (molbe/solver.py:528): the n^4 tensor of the last solve, written once by one kernel (rdm2_ops.hip)

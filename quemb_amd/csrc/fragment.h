@@ -115,6 +115,12 @@ class Fragment {
   void set_sci_mem_limit(int64_t bytes) { sci_mem_limit_ = bytes; }
   const SciResult& sci_result() const { return sci_res_; }
   int sci_dets(uint64_t* alpha, uint64_t* beta, double* c) const;
+  // the screened Epstein-Nesbet correction (sci.h: sci_pt2) of what the last SCI solve left -- the determinants, the vector, e_sci and the kept orbitals, from which
+  // h and V in the fragment-MO basis are formed again (fci_mo_integrals).  A diagnostic of the embedding problem: it is added to no energy.  max_ext <= 0: the
+  // largest count the room (free device memory, or set_sci_mem_limit) allows.  The working set sci_pt2_work_bytes is compared with the room before anything is
+  // allocated.  Outputs nullable; ms3: host wall time of screen, sorts / merges, rows.  nsocc == n: zeros.
+  int sci_pt2(double eps_pt, int64_t max_ext, double* e_pt2, int64_t* n_ext, int* batches, double* ms3);
+  static int64_t sci_pt2_work_bytes(int n, int nsocc, int64_t ndet, int64_t max_ext);      // sci_pt2_bytes and the n^4 pieces of fci_mo_integrals, h
   double fci_residual() const { return fci_residual_; }
   // Frags.rdm2__ (molbe/solver.py:528) of the last solve in the fragment-MO basis, out: n^4 (host).  kind QEMB_RDM2_CCSD: make_rdm2_urlx from the kept t1 / t2;
   // QEMB_RDM2_MP2: mp2.make_rdm2, t2 formed again from the resident orbitals (an MP2 solve keeps no amplitudes).  One kernel writes the tensor (rdm2_ops.hip).
@@ -200,11 +206,13 @@ class Fragment {
   int64_t fci_slab_ = 0, fci_rows_used_ = 0, fci_nslab_used_ = 1;
   int fci_mo_integrals(const std::vector<double>& C, DBuf& Vao, DBuf& CC, DBuf& Vmo);
   int fci_e2_sites(const double* CC, const double* G2, const double* Vao, std::vector<double>& e2);      // the cumulant contracted with the integrals, per fragment site
-  // after an SCI solve: the sorted determinants with the vector (device, 24 bytes per determinant); rdm2() forms the pattern of the matrix over them again
+  // after an SCI solve: the sorted determinants with the vector (device, 24 bytes per determinant); rdm2() forms the pattern of the matrix over them again;
+  // h in the fragment-MO basis and the orbitals (host, n x n each) for sci_pt2()
   SciSpace sci_V_;
   SciResult sci_res_;
+  std::vector<double> sci_hmo_, sci_C_;
   int64_t sci_mem_limit_ = -1;
-  void forget_solve() { last_kind_ = -1; sci_V_ = SciSpace(); sci_res_ = SciResult(); }
+  void forget_solve() { last_kind_ = -1; sci_V_ = SciSpace(); sci_res_ = SciResult(); sci_hmo_.clear(); sci_C_.clear(); }
 };
 
 // lock-step tapes kept from an earlier solve / recorded anew since the last reset (all fragments of the process)

@@ -1,4 +1,4 @@
-// sci.cpp -- the selected CI on the device (sci.h): screen in slabs, sort / unique / difference / merge, the CSR matrix, Davidson on it, the RDMs, the round loop.
+// sci.cpp -- the selected CI on the device (sci.h): screen in slabs, sort / unique / difference / merge, the CSR matrix, Davidson on it, the RDMs, the round loop; the second-order correction over ranges of the alpha word.
 #include "sci.h"
 #include <algorithm>
 #include <chrono>
@@ -33,8 +33,18 @@ int64_t sci_bytes(int n, int nsocc, int64_t max_det, int max_space) {
   return spaces + cand + davidson + rows + 8 * (4 * n2 * n2 + 2 * n2);             // Vao, CC, Vmo and the 2-RDM; h and the 1-RDM
 }
 
+int sci_double_bound(int n, const double* V_dev, double* bound) {
+  const int64_t n2 = (int64_t)n * n;
+  std::vector<double> Vh((size_t)(n2 * n2));
+  QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
+  double m = 0.0;
+  for (double x : Vh) m = std::max(m, std::fabs(x));
+  *bound = 2.0 * m;
+  return 0;
+}
+
 int sci_screen(int n, int nsocc, const double* h_dev, const double* V_dev, double dbl_bound, const SciSpace& V, double eps, int64_t slab, int64_t cap, int64_t max_new,
-               DBuf& joined, int64_t* njoined, double* ms) {
+               DBuf& joined, int64_t* njoined, double* ms, uint64_t alpha_lo, uint64_t alpha_hi) {
   double unclocked[SCI_T_COUNT] = {0, 0, 0, 0, 0};
   if (!ms) ms = unclocked;
   if (slab <= 0) slab = kSciSlab;
@@ -69,7 +79,7 @@ int sci_screen(int n, int nsocc, const double* h_dev, const double* V_dev, doubl
     if (total > 0) {
       const int64_t m = 2 * total;
       int64_t K = 0;
-      { StageClock clk(&ms[SCI_T_SCREEN]); QTRY(dev_sci_screen_emit(n, h_dev, V_dev, nd, V.k() + 2 * pos, V.c.p + pos, eps, dbl_bound, (const int64_t*)offs.p, (uint64_t*)cand.p)); }
+      { StageClock clk(&ms[SCI_T_SCREEN]); QTRY(dev_sci_screen_emit(n, h_dev, V_dev, nd, V.k() + 2 * pos, V.c.p + pos, eps, dbl_bound, (const int64_t*)offs.p, (uint64_t*)cand.p, alpha_lo, alpha_hi)); }
       StageClock clk(&ms[SCI_T_MERGE]);      // sort, unique, difference and the growth of the joined list
       QTRY(dev_sci_sort(m, pow2_at_least(m), (uint64_t*)cand.p));
       QTRY(dev_sci_flag_new(m, (const uint64_t*)cand.p, N, V.k(), nP, (const uint64_t*)joined.p, (int32_t*)flags.p));
@@ -102,17 +112,23 @@ int sci_merge(const SciSpace& V, const uint64_t* joined, int64_t njoined, SciSpa
   return 0;
 }
 
-int sci_build(int n, const double* h_dev, const double* V_dev, const uint64_t* keys, int64_t N, int64_t max_bytes, const std::string& who, SciMatrix& H) {
-  // runs of equal alpha, on the host: one pass over the downloaded keys
+int sci_alpha_runs(const uint64_t* keys, int64_t N, DBuf& segd, int64_t* nseg) {
+  // on the host: one pass over the downloaded keys
   std::vector<uint64_t> kh((size_t)(2 * N));
   QTRY(dev_d2h(kh.data(), keys, sizeof(uint64_t) * 2 * N));
   std::vector<int64_t> seg;
   for (int64_t k = 0; k < N; ++k) if (k == 0 || kh[(size_t)(2 * k)] != kh[(size_t)(2 * k - 2)]) seg.push_back(k);
-  const int64_t nseg = (int64_t)seg.size();
+  *nseg = (int64_t)seg.size();
   seg.push_back(N);
+  QTRY(segd.alloc(*nseg + 1));
+  return dev_h2d(segd, seg.data(), sizeof(int64_t) * (*nseg + 1));
+}
+
+int sci_build(int n, const double* h_dev, const double* V_dev, const uint64_t* keys, int64_t N, int64_t max_bytes, const std::string& who, SciMatrix& H) {
   DBuf segd, counts;
-  QTRY(segd.alloc(nseg + 1)); QTRY(counts.alloc(words_for_int32(N)));
-  QTRY(dev_h2d(segd, seg.data(), sizeof(int64_t) * (nseg + 1)));
+  int64_t nseg = 0;
+  QTRY(sci_alpha_runs(keys, N, segd, &nseg));
+  QTRY(counts.alloc(words_for_int32(N)));
   const bool values = h_dev != nullptr;      // (without integrals: row pointers and columns alone, what the RDM pass reads)
   QTRY(H.rowptr.alloc(N + 1));
   if (values) QTRY(H.hdiag.alloc(N));
@@ -181,12 +197,7 @@ int sci_solve(int n, int nsocc, const double* h_host, const double* V_dev, const
   QTRY(hd.alloc(n2));
   QTRY(dev_h2d(hd, h_host, sizeof(double) * n2));
   double dbl_bound = 0.0;
-  {
-    std::vector<double> Vh((size_t)(n2 * n2));
-    QTRY(dev_d2h(Vh.data(), V_dev, sizeof(double) * n2 * n2));
-    for (double x : Vh) dbl_bound = std::max(dbl_bound, std::fabs(x));
-    dbl_bound *= 2.0;
-  }
+  QTRY(sci_double_bound(n, V_dev, &dbl_bound));
   // ---- V0 = {HF}
   {
     const uint64_t hf = nsocc == 64 ? ~(uint64_t)0 : (((uint64_t)1 << nsocc) - 1);
@@ -230,6 +241,71 @@ int sci_solve(int n, int nsocc, const double* h_host, const double* V_dev, const
     if (!fr.converged) res->diag_converged = false;
   }
   return 0;
+}
+
+// ---- the second-order correction
+int64_t sci_pt2_bytes(int n, int nsocc, int64_t ndet, int64_t max_ext) {
+  const int64_t cap = sci_candidate_capacity(n, nsocc);
+  const int64_t lists = 16 * (2 * max_ext + 2 * cap) + 8 * max_ext;      // joined (<= max_ext when a slab's yield of <= cap keys is merged into the second copy); contributions
+  const int64_t cand = cap * (16 + 4 + 8) + kSciSlab * kSciScreenLanes * (4 + 8);
+  return lists + cand + 8 * (ndet + 1) + 8;                                // run starts; the sum
+}
+int64_t sci_pt2_max_ext(int n, int nsocc, int64_t ndet, int64_t room) {
+  const int64_t fixed = sci_pt2_bytes(n, nsocc, ndet, 0);
+  return room < fixed ? 0 : (room - fixed) / 40;
+}
+
+int sci_pt2(int n, int nsocc, const double* h_dev, const double* V_dev, double dbl_bound, const SciSpace& V, double e_var, double eps_pt, int64_t max_ext, int64_t slab, int64_t cap,
+            double* e_pt2, int64_t* n_ext, int* batches, double* ms) {
+  double unclocked[SCI_PT2_T_COUNT] = {0, 0, 0};
+  if (!ms) ms = unclocked;
+  *e_pt2 = 0.0; *n_ext = 0; *batches = 0;
+  if (n <= 0 || n > kSciMaxOrb || nsocc <= 0 || nsocc >= n || V.N <= 0) { set_error("sci_pt2: need 0 < nsocc < n <= " + std::to_string(kSciMaxOrb) + " and a space"); return QEMB_ERR_ARG; }
+  if (!(eps_pt > 0.0) || max_ext < 1) { set_error("sci_pt2: need eps_pt > 0 and max_ext >= 1"); return QEMB_ERR_ARG; }
+  DBuf segd, sum;
+  int64_t nseg = 0;
+  QTRY(sci_alpha_runs(V.k(), V.N, segd, &nseg));
+  QTRY(sum.alloc(1));
+  // the ranges still to do, the lowest on top: ascending order, and the sums are added in that order
+  std::vector<std::pair<uint64_t, uint64_t>> todo(1, {(uint64_t)0, ~(uint64_t)0});
+  double e = 0.0;
+  int64_t next = 0;
+  int nb = 0;
+  while (!todo.empty()) {
+    const uint64_t lo = todo.back().first, hi = todo.back().second;
+    todo.pop_back();
+    DBuf joined;
+    int64_t nj = 0;
+    double sms[SCI_T_COUNT] = {0, 0, 0, 0, 0};
+    QTRY(sci_screen(n, nsocc, h_dev, V_dev, dbl_bound, V, eps_pt, slab, cap, max_ext, joined, &nj, sms, lo, hi));
+    ms[SCI_PT2_T_SCREEN] += sms[SCI_T_SCREEN]; ms[SCI_PT2_T_MERGE] += sms[SCI_T_MERGE];
+    if (nj > max_ext) {      // too many for one pass: cut at the alpha word in the middle of what joined so far (a word of its own when that is the lowest one)
+      if (lo == hi) {
+        char b[256];
+        snprintf(b, sizeof b, "sci_pt2 (n = %d, eps_pt = %.3g): the alpha word %llx alone has at least %lld determinants outside the space, more than max_ext = %lld; %lld were summed before it",
+                 n, eps_pt, (unsigned long long)lo, (long long)nj, (long long)max_ext, (long long)next);
+        set_error(b);
+        return QEMB_ERR_ALLOC;
+      }
+      uint64_t mid = 0;
+      QTRY(dev_d2h(&mid, joined.p + 2 * (nj / 2), sizeof mid));
+      if (mid == lo) { todo.push_back({lo + 1, hi}); todo.push_back({lo, lo}); }
+      else { todo.push_back({mid, hi}); todo.push_back({lo, mid - 1}); }
+      continue;
+    }
+    ++nb;
+    if (nj == 0) continue;
+    StageClock clk(&ms[SCI_PT2_T_ROWS]);
+    DBuf contrib;
+    double x = 0.0;
+    QTRY(contrib.alloc(nj));
+    QTRY(dev_sci_pt2_rows(n, h_dev, V_dev, V.N, V.k(), V.c, nseg, (const int64_t*)segd.p, nj, (const uint64_t*)joined.p, e_var, eps_pt, dbl_bound, contrib));
+    QTRY(dev_sci_sum(nj, contrib, sum));
+    QTRY(dev_d2h(&x, sum, sizeof x));
+    e += x; next += nj;
+  }
+  *e_pt2 = e; *n_ext = next; *batches = nb;
+  return dev_sync();
 }
 
 }  // namespace qemb

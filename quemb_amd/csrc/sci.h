@@ -47,13 +47,17 @@ int64_t sci_excitations(int n, int nsocc);
 int64_t sci_candidate_capacity(int n, int nsocc);
 int64_t sci_bytes(int n, int nsocc, int64_t max_det, int max_space);
 constexpr int64_t kSciSlab = 4096;      // determinants screened per pass
+// the bound on every double-excitation element: |(ai|bj) - (aj|bi)| <= 2 max |V| (V_dev [n^2][n^2], downloaded once)
+int sci_double_bound(int n, const double* V_dev, double* bound);
 
 // the determinants outside `V` that pass the rule for (V, c), partners included: sorted, unique, in `joined` (2 * njoined uint64).  slab / cap: determinants per
 // pass and keys of the candidate buffer (0: kSciSlab and sci_candidate_capacity); stops early, with njoined > max_new, once more than max_new have joined.
 // The slab follows the yield: after every pass the next one takes as many determinants as would fill 3/4 of the buffer at the rate just seen.  ms (nullable,
 // SCI_T_COUNT slots): the evaluation passes are added to ms[SCI_T_SCREEN], the sorts, the unique / difference passes and the merges to ms[SCI_T_MERGE].
+// alpha_lo / alpha_hi: only keys whose alpha word lies in [alpha_lo, alpha_hi] are emitted, a key and its partner each tested on its own -- the union over
+// disjoint ranges is the unrestricted output, which the defaults give.
 int sci_screen(int n, int nsocc, const double* h_dev, const double* V_dev, double dbl_bound, const SciSpace& V, double eps, int64_t slab, int64_t cap, int64_t max_new,
-               DBuf& joined, int64_t* njoined, double* ms = nullptr);
+               DBuf& joined, int64_t* njoined, double* ms = nullptr, uint64_t alpha_lo = 0, uint64_t alpha_hi = ~(uint64_t)0);
 // out = V merged with the sorted keys `joined` (none of them in V), the vector padded with zeros
 int sci_merge(const SciSpace& V, const uint64_t* joined, int64_t njoined, SciSpace& out);
 // the CSR matrix over the sorted keys (h_dev = V_dev = null: its row pointers and columns alone, 4 bytes per stored element); max_bytes >= 0: QEMB_ERR_ALLOC (message starting with `who`) when the arrays would take more
@@ -66,5 +70,23 @@ int sci_rdm12(int n, const uint64_t* keys, int64_t N, const int64_t* rowptr, con
 // the round loop.  h_host [n][n], V_dev [n^2][n^2]; room: device bytes the CSR arrays may take (< 0: no check).  On QEMB_ERR_ALLOC / QEMB_ERR_NOCONV the message
 // names n, eps, the round, the count reached and the energy so far.  Returns 0 with res->converged = false when max_round was reached.
 int sci_solve(int n, int nsocc, const double* h_host, const double* V_dev, const SciOptions& opt, int64_t room, SciSpace& V, SciMatrix& H, SciResult* res);
+
+// ---- the screened Epstein-Nesbet second-order correction of (V, c, e_var) (DESIGN.md §4 "Selected CI"):
+//   S_a = sum over i in V with |H_ai c_i| >= eps_pt of H_ai c_i (a outside V; each product tested on its own),   E_PT2 = sum_{a in P} S_a^2 / (e_var - H_aa),
+// P what sci_screen returns for (V, c, eps_pt), n_ext = |P|.  The denominators are not guarded.  One alpha-word range at a time, starting with every word: the
+// screen at eps_pt with max_new = max_ext, the row pass (dev_sci_pt2_rows), a fixed-order sum.  A range in which more than max_ext determinants join is cut at
+// the alpha word in the middle of the partial sorted list and both halves are done again; ranges run in ascending order and their sums are added in that order
+// (*batches: the ranges that were summed).  A single alpha word with more than max_ext externals: QEMB_ERR_ALLOC naming n, eps_pt, max_ext and the count reached.
+// ms (nullable, SCI_PT2_T_COUNT slots): host wall time of the screen passes, the sorts / merges and the row passes with their sums.
+enum { SCI_PT2_T_SCREEN = 0, SCI_PT2_T_MERGE = 1, SCI_PT2_T_ROWS = 2, SCI_PT2_T_COUNT = 3 };
+int sci_pt2(int n, int nsocc, const double* h_dev, const double* V_dev, double dbl_bound, const SciSpace& V, double e_var, double eps_pt, int64_t max_ext, int64_t slab, int64_t cap,
+            double* e_pt2, int64_t* n_ext, int* batches, double* ms = nullptr);
+// device bytes of one sci_pt2 call over ndet determinants beside the space itself: the joined list while it grows (two copies of max_ext + one slab's yield, and
+// the slab's own new keys), the contributions, the candidate buffer with its flags and offsets, the slab's lane counts and the run starts
+int64_t sci_pt2_bytes(int n, int nsocc, int64_t ndet, int64_t max_ext);
+// the largest max_ext whose sci_pt2_bytes is at most `room` (< 1: not even one)
+int64_t sci_pt2_max_ext(int n, int nsocc, int64_t ndet, int64_t room);
+// the run starts of equal alpha of sorted keys (device): nseg + 1 offsets in segd, the last one N
+int sci_alpha_runs(const uint64_t* keys, int64_t N, DBuf& segd, int64_t* nseg);
 
 }  // namespace qemb

@@ -174,6 +174,39 @@ QEMB_SCI_HD int sci_screen_lane(int n, const double* h, const double* V, const S
   return cnt;
 }
 
+// ---- the second-order correction: the determinant (a, b) outside the sorted space against its members.  Lane `lane` of `nlanes` takes the runs of equal alpha
+// s = lane, lane + nlanes, ... (seg[s] .. seg[s + 1], as sci_build forms them): a run whose alpha is more than two excitations away is skipped whole, then the
+// betas of the run are compared.  Returns the lane's part of S_a = sum_i H_ai c_i over the products with |H_ai c_i| >= eps, each tested on its own -- the
+// expression the screen tests, bra and ket in the same places, so the two passes decide alike.  A double excitation of a member with |c_i| dbl_bound < eps
+// cannot pass (the screen's own shortcut) and is not evaluated.
+QEMB_SCI_HD double sci_pt2_lane(int n, const double* h, const double* V, const uint64_t* keys, const double* c, long long nseg, const long long* seg, uint64_t a, uint64_t b,
+                                double eps, double dbl_bound, int lane, int nlanes) {
+  double sum = 0.0;
+  for (long long s = lane; s < nseg; s += nlanes) {
+    const long long k0 = seg[s], k1 = seg[s + 1];
+    const uint64_t as = keys[2 * k0];
+    const int da = sci_popc(a ^ as) >> 1;
+    if (da > 2) continue;
+    for (long long k = k0; k < k1; ++k) {
+      const uint64_t bs = keys[2 * k + 1];
+      const int d = da + (sci_popc(b ^ bs) >> 1);
+      if (d > 2 || d == 0) continue;
+      const double ck = c[k];
+      if (ck == 0.0 || (d == 2 && !(fabs(ck) * dbl_bound >= eps))) continue;
+      const double x = sci_hij(n, h, V, a, b, as, bs) * ck;
+      if (fabs(x) >= eps) sum += x;
+    }
+  }
+  return sum;
+}
+// the Epstein-Nesbet term of one determinant; the denominator is not guarded
+QEMB_SCI_HD double sci_pt2_term(double S, double e_var, double haa) { return S * S / (e_var - haa); }
+// a key of the screen's output that lies outside the alpha-word range [lo, hi] becomes the pad key of the sort, which flag_new drops
+QEMB_SCI_HD void sci_put_in_range(uint64_t* o, uint64_t a, uint64_t b, uint64_t lo, uint64_t hi) {
+  const bool in = a >= lo && a <= hi;
+  o[0] = in ? a : ~(uint64_t)0; o[1] = in ? b : ~(uint64_t)0;
+}
+
 // position of the first key of A[0..nA) that is not less than (a, b); keys are interleaved (A[2k], A[2k+1])
 QEMB_SCI_HD long long sci_lower_bound(const uint64_t* A, long long nA, uint64_t a, uint64_t b) {
   long long lo = 0, hi = nA;

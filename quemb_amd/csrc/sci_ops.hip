@@ -1,11 +1,13 @@
 // sci_ops.hip -- the determinant-space passes of the selected CI on 64-bit occupation words (dev_ops.h: dev_sci_*; driver: sci.cpp; arithmetic: sci_core.h).
 //
-// screen     one workgroup per determinant of the slab, its lanes stride the flat list of excitations; count pass, scan, emit pass: dense output in a fixed order.
+// screen     one workgroup per determinant of the slab, its lanes stride the flat list of excitations; count pass, scan, emit pass: dense output in a fixed order
+//            (a key outside the alpha-word range of the call is written as the pad key of the sort: the slots stay where they are).
 // scan       exclusive scan int32 -> int64 by ONE workgroup walking the array in pieces of 8192 (the arrays are counts per lane or per row: a few MB at most).
 // sort       bitonic network on the 128-bit keys in global memory, one launch per (k, j) step; the set is what matters, and the network is deterministic.
 // flag_new / compact / merge   binary searches in sorted lists; every output position has one owner.
 // csr        one thread per row walks the runs of equal alpha: popcount of the alpha words rules out a whole run, then the betas of the run are compared.
 // spmv       one wavefront per row, lanes stride the row, a fixed xor-shuffle tree.
+// pt2_rows   one wavefront per determinant outside the space, lanes stride the runs of equal alpha of the space, a fixed xor-shuffle tree; sum: one workgroup, fixed order.
 // rdm        one wavefront per row, one lane per stored pair: the excitation is recomputed from the two keys and its contributions are added with FP64 atomics.
 // Everything but the RDM pass has one owner per output element and a fixed order of additions: the same bits on every call.
 #include "hip_common.h"
@@ -17,7 +19,7 @@ namespace {
 
 __global__ void __launch_bounds__(kSciScreenLanes) sci_screen_kernel(int n, const double* __restrict__ h, const double* __restrict__ V, const uint64_t* __restrict__ keys,
                                                                      const double* __restrict__ c, double eps, double dbl_bound, const long long* __restrict__ offsets,
-                                                                     int* __restrict__ counts, uint64_t* __restrict__ out) {
+                                                                     int* __restrict__ counts, uint64_t* __restrict__ out, uint64_t lo, uint64_t hi) {
   __shared__ SciLists L;
   const long long d = blockIdx.x;
   const uint64_t a = keys[2 * d], b = keys[2 * d + 1];
@@ -29,7 +31,7 @@ __global__ void __launch_bounds__(kSciScreenLanes) sci_screen_kernel(int n, cons
   } else {
     uint64_t* o = out + 4 * offsets[slot];
     sci_screen_lane(n, h, V, L, a, b, c[d], eps, dbl_bound, (int)threadIdx.x, kSciScreenLanes,
-                    [o](int k, uint64_t na, uint64_t nb) { o[4 * k] = na; o[4 * k + 1] = nb; o[4 * k + 2] = nb; o[4 * k + 3] = na; });
+                    [o, lo, hi](int k, uint64_t na, uint64_t nb) { sci_put_in_range(o + 4 * k, na, nb, lo, hi); sci_put_in_range(o + 4 * k + 2, nb, na, lo, hi); });
   }
 }
 
@@ -186,6 +188,34 @@ __global__ void __launch_bounds__(256) sci_rdm_kernel(int n, long long N, const 
   }
 }
 
+// contrib[k] = S_a^2 / (e_var - H_aa) of external determinant k: one wavefront per determinant, its lanes stride the runs of equal alpha of the space
+// (sci_pt2_lane), a fixed xor-shuffle tree; lane 0 forms the diagonal element and writes.  One owner and one order of additions per output.
+__global__ void __launch_bounds__(256) sci_pt2_rows_kernel(int n, const double* __restrict__ h, const double* __restrict__ V, long long N, const uint64_t* __restrict__ keys,
+                                                           const double* __restrict__ c, long long nseg, const long long* __restrict__ seg, long long K,
+                                                           const uint64_t* __restrict__ ext, double e_var, double eps, double dbl_bound, double* __restrict__ contrib) {
+  const int lane = threadIdx.x & 63;
+  const long long k = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= K) return;      // (a whole wavefront leaves together)
+  const uint64_t a = ext[2 * k], b = ext[2 * k + 1];
+  double s = sci_pt2_lane(n, h, V, keys, c, nseg, seg, a, b, eps, dbl_bound, lane, 64);
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  if (lane == 0) contrib[k] = sci_pt2_term(s, e_var, sci_diag(n, h, V, a, b));
+}
+// out[0] = sum of in[0..m): ONE workgroup, every thread adds its elements tid, tid + 1024, ... in ascending order, then a fixed tree in shared memory
+__global__ void __launch_bounds__(1024) sci_sum_kernel(long long m, const double* __restrict__ in, double* __restrict__ out) {
+  __shared__ double s[1024];
+  const int tid = threadIdx.x;
+  double x = 0.0;
+  for (long long i = tid; i < m; i += 1024) x += in[i];
+  s[tid] = x;
+  __syncthreads();
+  for (int off = 512; off > 0; off >>= 1) {
+    if (tid < off) s[tid] += s[tid + off];
+    __syncthreads();
+  }
+  if (tid == 0) out[0] = s[0];
+}
+
 // dm2 -= nc, the mean-field part of cumulant_core.h
 __global__ void __launch_bounds__(256) sci_dm2_finish_kernel(int n, int o_cum, const double* __restrict__ dm1, double* __restrict__ dm2) {
   const long long n2 = (long long)n * n;
@@ -212,13 +242,15 @@ int dev_sci_screen_count(int n, const double* h, const double* V, int64_t nd, co
   SCI_STREAM(st);
   unsigned grid;
   if (n <= 0 || n > kSciMaxOrb || !h || !V || !keys || !c || !counts || !(eps > 0.0) || !grid_for("dev_sci_screen_count", nd, 1, &grid)) { set_error("dev_sci_screen_count: bad arguments"); return QEMB_ERR_ARG; }
-  return launch("dev_sci_screen_count", sci_screen_kernel, dim3(grid), dim3(kSciScreenLanes), 0, st, n, h, V, keys, c, eps, dbl_bound, (const long long*)nullptr, counts, (uint64_t*)nullptr);
+  return launch("dev_sci_screen_count", sci_screen_kernel, dim3(grid), dim3(kSciScreenLanes), 0, st, n, h, V, keys, c, eps, dbl_bound, (const long long*)nullptr, counts, (uint64_t*)nullptr,
+                (uint64_t)0, ~(uint64_t)0);
 }
-int dev_sci_screen_emit(int n, const double* h, const double* V, int64_t nd, const uint64_t* keys, const double* c, double eps, double dbl_bound, const int64_t* offsets, uint64_t* out) {
+int dev_sci_screen_emit(int n, const double* h, const double* V, int64_t nd, const uint64_t* keys, const double* c, double eps, double dbl_bound, const int64_t* offsets, uint64_t* out,
+                        uint64_t alpha_lo, uint64_t alpha_hi) {
   SCI_STREAM(st);
   unsigned grid;
   if (n <= 0 || n > kSciMaxOrb || !h || !V || !keys || !c || !offsets || !out || !(eps > 0.0) || !grid_for("dev_sci_screen_emit", nd, 1, &grid)) { set_error("dev_sci_screen_emit: bad arguments"); return QEMB_ERR_ARG; }
-  return launch("dev_sci_screen_emit", sci_screen_kernel, dim3(grid), dim3(kSciScreenLanes), 0, st, n, h, V, keys, c, eps, dbl_bound, (const long long*)offsets, (int*)nullptr, out);
+  return launch("dev_sci_screen_emit", sci_screen_kernel, dim3(grid), dim3(kSciScreenLanes), 0, st, n, h, V, keys, c, eps, dbl_bound, (const long long*)offsets, (int*)nullptr, out, alpha_lo, alpha_hi);
 }
 int dev_sci_scan(int64_t m, const int32_t* in, int64_t* out) {
   SCI_STREAM(st);
@@ -282,6 +314,21 @@ int dev_sci_rdm(int n, int64_t N, const uint64_t* keys, const int64_t* rowptr, c
   unsigned grid;
   if (n <= 0 || n > kSciMaxOrb || !keys || !rowptr || !col || !c || !dm1 || !dm2 || !grid_for("dev_sci_rdm", N, 4, &grid)) { set_error("dev_sci_rdm: bad arguments"); return QEMB_ERR_ARG; }
   return launch("dev_sci_rdm", sci_rdm_kernel, dim3(grid), dim3(256), 0, st, n, (long long)N, keys, (const long long*)rowptr, col, c, dm1, dm2);
+}
+int dev_sci_pt2_rows(int n, const double* h, const double* V, int64_t N, const uint64_t* keys, const double* c, int64_t nseg, const int64_t* seg, int64_t K, const uint64_t* ext,
+                     double e_var, double eps, double dbl_bound, double* contrib) {
+  SCI_STREAM(st);
+  unsigned grid;
+  if (n <= 0 || n > kSciMaxOrb || !h || !V || !keys || !c || !seg || !ext || !contrib || N <= 0 || nseg <= 0 || nseg > N || !(eps > 0.0) || !grid_for("dev_sci_pt2_rows", K, 4, &grid)) {
+    set_error("dev_sci_pt2_rows: bad arguments"); return QEMB_ERR_ARG;
+  }
+  return launch("dev_sci_pt2_rows", sci_pt2_rows_kernel, dim3(grid), dim3(256), 0, st, n, h, V, (long long)N, keys, c, (long long)nseg, (const long long*)seg, (long long)K, ext, e_var, eps,
+                dbl_bound, contrib);
+}
+int dev_sci_sum(int64_t m, const double* in, double* out) {
+  SCI_STREAM(st);
+  if (m <= 0 || !in || !out) { set_error("dev_sci_sum: bad arguments"); return QEMB_ERR_ARG; }
+  return launch("dev_sci_sum", sci_sum_kernel, dim3(1), dim3(1024), 0, st, (long long)m, in, out);
 }
 int dev_sci_dm2_finish(int n, int o_cum, const double* dm1, double* dm2) {
   SCI_STREAM(st);

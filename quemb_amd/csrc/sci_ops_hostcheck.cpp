@@ -1,7 +1,7 @@
 // sci_ops_hostcheck.cpp -- scalar restatement of the device operations of the selected CI for the mock device layer of tests/hostcheck.
 // Everything below is compiled only with -DQEMB_HOSTCHECK: in the product build this file is an empty object and sci_ops.hip provides the operations.
 // The screen walks the lanes of sci_core.h one after another (the same output positions as the kernel); the sort is std::sort, the merge a two-finger merge,
-// the matrix the kernel's walk over the runs of equal alpha (the tests hold the pattern to an all-pairs popcount in numpy), the product and the RDMs plain loops over the rows.
+// the matrix the kernel's walk over the runs of equal alpha (the tests hold the pattern to an all-pairs popcount in numpy), the product and the RDMs plain loops over the rows; the second-order rows and their sum keep the kernel's lanes and trees (the same order of additions).
 #ifdef QEMB_HOSTCHECK
 #include <algorithm>
 #include <utility>
@@ -12,7 +12,7 @@
 namespace qemb {
 
 static int screen(const char* who, int n, const double* h, const double* V, int64_t nd, const uint64_t* keys, const double* c, double eps, double dbl_bound,
-                  int32_t* counts, const int64_t* offsets, uint64_t* out) {
+                  int32_t* counts, const int64_t* offsets, uint64_t* out, uint64_t lo, uint64_t hi) {
   if (n <= 0 || n > kSciMaxOrb || !h || !V || !keys || !c || nd <= 0 || !(eps > 0.0) || (!counts && !(offsets && out))) { set_error(std::string(who) + ": bad arguments"); return QEMB_ERR_ARG; }
   for (int64_t d = 0; d < nd; ++d) {
     SciLists L;
@@ -23,7 +23,7 @@ static int screen(const char* who, int n, const double* h, const double* V, int6
       else {
         uint64_t* o = out + 4 * offsets[slot];
         sci_screen_lane(n, h, V, L, keys[2 * d], keys[2 * d + 1], c[d], eps, dbl_bound, lane, kSciScreenLanes,
-                        [o](int k, uint64_t na, uint64_t nb) { o[4 * k] = na; o[4 * k + 1] = nb; o[4 * k + 2] = nb; o[4 * k + 3] = na; });
+                        [o, lo, hi](int k, uint64_t na, uint64_t nb) { sci_put_in_range(o + 4 * k, na, nb, lo, hi); sci_put_in_range(o + 4 * k + 2, nb, na, lo, hi); });
       }
     }
   }
@@ -31,11 +31,12 @@ static int screen(const char* who, int n, const double* h, const double* V, int6
 }
 int dev_sci_screen_count(int n, const double* h, const double* V, int64_t nd, const uint64_t* keys, const double* c, double eps, double dbl_bound, int32_t* counts) {
   if (!counts) { set_error("dev_sci_screen_count: bad arguments"); return QEMB_ERR_ARG; }
-  return screen("dev_sci_screen_count", n, h, V, nd, keys, c, eps, dbl_bound, counts, nullptr, nullptr);
+  return screen("dev_sci_screen_count", n, h, V, nd, keys, c, eps, dbl_bound, counts, nullptr, nullptr, 0, ~(uint64_t)0);
 }
-int dev_sci_screen_emit(int n, const double* h, const double* V, int64_t nd, const uint64_t* keys, const double* c, double eps, double dbl_bound, const int64_t* offsets, uint64_t* out) {
+int dev_sci_screen_emit(int n, const double* h, const double* V, int64_t nd, const uint64_t* keys, const double* c, double eps, double dbl_bound, const int64_t* offsets, uint64_t* out,
+                        uint64_t alpha_lo, uint64_t alpha_hi) {
   if (!offsets || !out) { set_error("dev_sci_screen_emit: bad arguments"); return QEMB_ERR_ARG; }
-  return screen("dev_sci_screen_emit", n, h, V, nd, keys, c, eps, dbl_bound, nullptr, offsets, out);
+  return screen("dev_sci_screen_emit", n, h, V, nd, keys, c, eps, dbl_bound, nullptr, offsets, out, alpha_lo, alpha_hi);
 }
 int dev_sci_scan(int64_t m, const int32_t* in, int64_t* out) {
   if (m <= 0 || !in || !out) { set_error("dev_sci_scan: bad arguments"); return QEMB_ERR_ARG; }
@@ -150,6 +151,33 @@ int dev_sci_rdm(int n, int64_t N, const uint64_t* keys, const int64_t* rowptr, c
       if (e.spin1 == e.spin2) { at(e.a, e.j, e.b, e.i) -= w; at(e.b, e.i, e.a, e.j) -= w; }
     }
   }
+  return 0;
+}
+// the kernel's lanes one after another, then its shuffle tree: lane l takes lane l ^ off at every step, and lane 0 holds the sum
+int dev_sci_pt2_rows(int n, const double* h, const double* V, int64_t N, const uint64_t* keys, const double* c, int64_t nseg, const int64_t* seg, int64_t K, const uint64_t* ext,
+                     double e_var, double eps, double dbl_bound, double* contrib) {
+  if (n <= 0 || n > kSciMaxOrb || !h || !V || !keys || !c || !seg || !ext || !contrib || N <= 0 || nseg <= 0 || nseg > N || K <= 0 || !(eps > 0.0)) {
+    set_error("dev_sci_pt2_rows: bad arguments"); return QEMB_ERR_ARG;
+  }
+  for (int64_t k = 0; k < K; ++k) {
+    const uint64_t a = ext[2 * k], b = ext[2 * k + 1];
+    double s[64], t[64];
+    for (int lane = 0; lane < 64; ++lane) s[lane] = sci_pt2_lane(n, h, V, keys, c, nseg, (const long long*)seg, a, b, eps, dbl_bound, lane, 64);
+    for (int off = 32; off > 0; off >>= 1) {
+      for (int lane = 0; lane < 64; ++lane) t[lane] = s[lane] + s[lane ^ off];
+      std::copy(t, t + 64, s);
+    }
+    contrib[k] = sci_pt2_term(s[0], e_var, sci_diag(n, h, V, a, b));
+  }
+  return 0;
+}
+// the kernel's order: 1024 strided partial sums, then its tree
+int dev_sci_sum(int64_t m, const double* in, double* out) {
+  if (m <= 0 || !in || !out) { set_error("dev_sci_sum: bad arguments"); return QEMB_ERR_ARG; }
+  std::vector<double> s(1024, 0.0);
+  for (int tid = 0; tid < 1024; ++tid) for (int64_t i = tid; i < m; i += 1024) s[(size_t)tid] += in[i];
+  for (int off = 512; off > 0; off >>= 1) for (int tid = 0; tid < off; ++tid) s[(size_t)tid] += s[(size_t)(tid + off)];
+  out[0] = s[0];
   return 0;
 }
 int dev_sci_dm2_finish(int n, int o_cum, const double* dm1, double* dm2) {

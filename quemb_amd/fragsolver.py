@@ -179,6 +179,7 @@ class DeviceFragment:
         check(self.lib.qemb_frag_sci_stats(self.h, C.byref(ndet), C.byref(rounds), C.byref(nnz), C.byref(resid)), "qemb_frag_sci_stats", self.lib)
         out = c.results()[0]
         out.update(e_sci=c.e[0], e_corr_mo=c.e[0] - c.e_scf[0], ndet=int(ndet.value), rounds=int(rounds.value), nnz=int(nnz.value), residual=resid.value)
+        self._sci_e_var = out["e_sci"]      # (what `sci_pt2` reports beside its correction; the library keeps its own copy)
         if want_dets:
             a, b, v = np.empty(out["ndet"], dtype=np.uint64), np.empty(out["ndet"], dtype=np.uint64), np.empty(out["ndet"])
             check(self.lib.qemb_frag_sci_dets(self.h, a.ctypes.data, b.ctypes.data, v.ctypes.data), "qemb_frag_sci_dets", self.lib)
@@ -194,6 +195,17 @@ class DeviceFragment:
     def set_sci_mem_limit(self, nbytes):
         """device bytes `solve_sci` of this fragment may take (qemb_frag_sci_mem_limit); negative: whatever is free"""
         check(self.lib.qemb_frag_sci_mem_limit(self.h, int(nbytes)), "qemb_frag_sci_mem_limit", self.lib)
+
+    def sci_pt2(self, eps_pt, max_ext=0):
+        """the screened Epstein-Nesbet second-order correction of the last `solve_sci` of this fragment (qemb_frag_sci_pt2), from the determinants, the vector and e_sci
+        it left on the device:  S_a = sum of the products H_ai c_i with |H_ai c_i| >= eps_pt,  e_pt2 = sum_a S_a^2 / (e_var - H_aa)  over the n_ext determinants
+        outside the space with a passing product and their spin partners; denominators are not guarded.  Returns dict(e_var, e_pt2, n_ext, batches, ms) -- batches: the
+        ranges of at most max_ext externals the sum ran in (max_ext = 0: the largest count that fits the memory), ms: dict(screen, merge, rows) of host wall time.
+        e_var + e_pt2 tells whether the cutoff of the solve was small enough; it is a diagnostic of the embedding problem and is added to no fragment or BE energy
+        (those come from the variational RDMs, as in the reference)."""
+        e, next_, nb, ms = C.c_double(), C.c_int64(), C.c_int(), (C.c_double * 3)()
+        check(self.lib.qemb_frag_sci_pt2(self.h, float(eps_pt), int(max_ext), C.byref(e), C.byref(next_), C.byref(nb), ms), "qemb_frag_sci_pt2", self.lib)
+        return dict(e_var=self._sci_e_var, e_pt2=e.value, n_ext=int(next_.value), batches=int(nb.value), ms=dict(zip(("screen", "merge", "rows"), (float(x) for x in ms))))
 
     def solve_as(self, solver, nsocc, h, dm0=None, opts=None, eeval=True, want_amplitudes=False, fci_opts=None, sci_opts=None):
         """the solve of be_func's solver literal (one of SOLVERS): `solve`, `solve_mp2`, `solve_fci` or `solve_sci`.  want_amplitudes asks for t2 (the CI vector of
@@ -408,6 +420,23 @@ def sci_screen(h, V, nsocc, alpha, beta, c, eps, slab=0, cap=0, lib=None):
         if nj.value:
             check(lib.qemb_op_sci_screen(*args, nj.value, C.byref(nj), oa.ctypes.data, ob.ctypes.data), "qemb_op_sci_screen", lib)
         return oa, ob
+    finally:
+        Vd.free()
+
+
+def sci_pt2(h, V, nsocc, alpha, beta, c, e_var, eps_pt, max_ext=0, slab=0, cap=0, lib=None):
+    """the screened Epstein-Nesbet second-order correction of the vector c with energy e_var over the sorted space (alpha, beta) (qemb_op_sci_pt2; the definition
+    is in DeviceFragment.sci_pt2): dict(e_pt2, n_ext, batches).  max_ext: externals per range of the alpha word (0: no bound, one range); slab / cap as in
+    `sci_screen`"""
+    lib = lib or _lib.init()
+    a, b = _sci_space(alpha, beta)
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    h, n, Vd = _sci_integrals(h, V, lib)
+    try:
+        e, next_, nb = C.c_double(), C.c_int64(), C.c_int()
+        check(lib.qemb_op_sci_pt2(n, int(nsocc), h.ctypes.data, Vd.ptr, a.size, a.ctypes.data, b.ctypes.data, c.ctypes.data, float(e_var), float(eps_pt), int(max_ext), int(slab), int(cap),
+                                  C.byref(e), C.byref(next_), C.byref(nb)), "qemb_op_sci_pt2", lib)
+        return dict(e_pt2=e.value, n_ext=int(next_.value), batches=int(nb.value))
     finally:
         Vd.free()
 

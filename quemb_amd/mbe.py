@@ -624,6 +624,16 @@ class BE:
                   f"  E_tot = {self.ebe_tot:.10f}", flush=True)
         return rets
 
+    def sci_pt2(self, eps_pt, max_ext=0):
+        """after `oneshot` / `optimize` with solver="SCI-hip": the screened Epstein-Nesbet second-order correction of every fragment's last solve (Frags.sci_pt2), one
+        dict(e_var, e_pt2, n_ext, batches, ms) per fragment in fragment order (None for a fragment another rank owns).  e_var + e_pt2 against e_var tells whether
+        `hci_cutoff` was small enough for that embedding problem.  It is a per-fragment diagnostic and is added to nothing: the BE energies are formed from the
+        variational RDMs, as in the reference, whose hci_pt does not reach them either."""
+        mine = [f for i, f in enumerate(self.Fobjs) if self.world <= 1 or self.owner[i] == self.rank]
+        if not mine or any(f._solver != "SCI-hip" for f in mine):
+            raise RuntimeError("BE.sci_pt2: run oneshot or optimize with solver='SCI-hip' first")
+        return [f.sci_pt2(eps_pt, max_ext) if f in mine else None for f in self.Fobjs]
+
     def optimize(self, solver="CCSD", method="QN", only_chem=False, use_cumulant=True, conv_tol=1.0e-6, relax_density=False,
                  jac_solver="HF", nproc=1, ompnum=1, max_iter=500, trust_region=False, step_size=1e-6, solver_args=None,
                  warm_start=True):

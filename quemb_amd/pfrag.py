@@ -64,6 +64,7 @@ class Frags:
         self._hf_jk = None
         self.fci_slab_rows = 0   # slab height of solver="FCI-hip" on this fragment (DeviceFragment.set_fci_slab; BE(fci_slab_rows=...)); the other solvers do not read it
         self._solver = None      # the solver of the last solve ("CCSD" / "MP2" / "FCI-hip"): what make_rdm2 assembles
+        self.e_pt2 = None        # the second-order correction of the last `sci_pt2` call (a diagnostic, added to nothing)
 
     # ------------------------------------------------------------------ Schmidt (pfrag.py:146-180)
     def sd(self, lao, lmo, nocc, thr_bath, norb=None, method="eigh"):
@@ -183,6 +184,16 @@ class Frags:
             self.dev.set_fci_slab(self.fci_slab_rows)      # (kept by the device fragment: a later make_rdm2 follows it too)
         out = self.dev.solve_as(solver, self.nsocc, self.fock + self.heff, self.dm0, opts=opts, eeval=eeval, want_amplitudes=want_t2, fci_opts=fci_opts, sci_opts=sci_opts)
         return self._solve_outputs(out, eeval, use_cumulant, solver)
+
+    def sci_pt2(self, eps_pt, max_ext=0):
+        """the screened Epstein-Nesbet second-order correction of this fragment's last solve with solver="SCI-hip" (DeviceFragment.sci_pt2):
+        dict(e_var, e_pt2, n_ext, batches, ms); the correction is also kept as `self.e_pt2`.  A diagnostic of the embedding problem -- whether `hci_cutoff` was
+        small enough --, added to no energy: the BE energies come from the variational RDMs, as in the reference."""
+        if self._solver != "SCI-hip":
+            raise RuntimeError("sci_pt2: solve the fragment with solver='SCI-hip' first")
+        out = self.dev.sci_pt2(eps_pt, max_ext)
+        self.e_pt2 = out["e_pt2"]
+        return out
 
     def make_rdm2(self, with_dm1=True):
         """fills `rdm2__` (molbe/solver.py:528) from the last solve of this fragment, in the fragment-MO basis: make_rdm2_urlx(t1, t2, with_dm1) after a

@@ -86,7 +86,7 @@ def solve_error(Fobjs, Nocc, only_chem=False, rdm1_list=None):
 @dataclass(frozen=True)
 class SHCI_ArgsUser:
     """the reference's user arguments of its selected-CI branch (molbe/solver.py), read by solver="SCI-hip": hci_cutoff is the threshold eps_var on |H_ai c_i|.
-    The perturbative correction (hci_pt) and return_frag_data are not built: NotImplementedError."""
+    hci_pt and return_frag_data are not built: NotImplementedError.  The perturbative correction is a call of its own after the sweep, BE.sci_pt2."""
     hci_cutoff: float = 0.001
     hci_pt: bool = False
     return_frag_data: bool = False
@@ -101,7 +101,7 @@ def sci_opts_from_args(solver, solver_args, lib=None):
     if not isinstance(solver_args, SHCI_ArgsUser):
         raise TypeError(f"solver_args of solver='SCI-hip' must be a SHCI_ArgsUser or None, not {type(solver_args).__name__}")
     if solver_args.hci_pt:
-        raise NotImplementedError("SCI-hip: the perturbative correction (hci_pt) is not implemented")
+        raise NotImplementedError("SCI-hip: the perturbative correction inside a sweep (hci_pt) is not implemented; call BE.sci_pt2 after the sweep")
     if solver_args.return_frag_data:
         raise NotImplementedError("SCI-hip: return_frag_data is not implemented")
     if lib is None:      # (the checks alone: be_func refuses a bad argument before any fragment is solved)
@@ -111,10 +111,10 @@ def sci_opts_from_args(solver, solver_args, lib=None):
 
 
 def _solve_fragment(name, solver, keys, h, eri_s4, nsocc, dm0, *, n_frag, rdm_return, rdm2_return, use_cumulant, opts, lib, df_factor=None, fci_opts=None, sci_opts=None,
-                    slab_rows=0):
+                    slab_rows=0, pt2_eps=None):
     """What solve_ccsd / solve_mp2 / solve_fci share: a fragment with its ERIs (or living on its 3-index factor) is created, solved without energies and freed.
     Returns (out[keys[0]], out[keys[1]]), then rdm1_mo and mo_coeff with rdm_return; rdm2_return: the 2-RDM of the solve takes the place of mo_coeff
-    (solver.py:940-942), or is appended without rdm_return."""
+    (solver.py:940-942), or is appended without rdm_return.  pt2_eps (read for "SCI-hip" alone): the second-order correction at that threshold is the last element."""
     fr = DeviceFragment(h.shape[0], n_frag, lib=lib)
     try:
         if eri_s4 is not None:
@@ -129,12 +129,13 @@ def _solve_fragment(name, solver, keys, h, eri_s4, nsocc, dm0, *, n_frag, rdm_re
             fr.set_fci_slab(slab_rows)
         out = fr.solve_as(solver, nsocc, h, dm0, opts=opts, eeval=False, want_amplitudes=True, fci_opts=fci_opts, sci_opts=sci_opts)
         rdm2 = fr.make_rdm2(solver, with_dm1=not use_cumulant) if rdm2_return else None
+        tail = () if pt2_eps is None else (fr.sci_pt2(pt2_eps)["e_pt2"],)
     finally:
         fr.free()
     head = (out[keys[0]], out[keys[1]])
     if rdm_return:
-        return (*head, out["rdm1_mo"], rdm2 if rdm2_return else out["mo_coeff"])
-    return (*head, rdm2) if rdm2_return else head
+        return (*head, out["rdm1_mo"], rdm2 if rdm2_return else out["mo_coeff"], *tail)
+    return (*head, rdm2, *tail) if rdm2_return else (*head, *tail)
 
 
 def solve_ccsd(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, relax=False, use_cumulant=True,
@@ -171,12 +172,15 @@ def solve_fci(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_re
                            use_cumulant=use_cumulant, opts=opts, lib=lib, df_factor=df_factor, fci_opts=fci_opts, slab_rows=slab_rows)
 
 
-def solve_sci(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, use_cumulant=True, df_factor=None, opts=None, sci_opts=None, lib=None):
+def solve_sci(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, use_cumulant=True, df_factor=None, opts=None, sci_opts=None, lib=None,
+              pt2_eps=None):
     """Device counterpart of the reference's selected-CI branch (molbe/solver.py:412-462) with the inputs of `solve_fci` above.  Returns (e_sci, dets) -- the
     eigenvalue in the selected space and (alpha, beta, c), the occupation words of the final space sorted by (alpha, beta) with the vector -- or
-    (e_sci, dets, rdm1_mo, mo_coeff) with rdm_return; rdm2_return: the 2-RDM (minus its mean-field part with use_cumulant) in the place `solve_ccsd` gives it."""
+    (e_sci, dets, rdm1_mo, mo_coeff) with rdm_return; rdm2_return: the 2-RDM (minus its mean-field part with use_cumulant) in the place `solve_ccsd` gives it.
+    pt2_eps: with a value, the screened Epstein-Nesbet second-order correction at that threshold (DeviceFragment.sci_pt2) is appended as the last element -- a
+    diagnostic of the cutoff, contained in none of the other results."""
     return _solve_fragment("solve_sci", "SCI-hip", ("e_sci", "dets"), h, eri_s4, nsocc, dm0, n_frag=n_frag, rdm_return=rdm_return, rdm2_return=rdm2_return,
-                           use_cumulant=use_cumulant, opts=opts, lib=lib, df_factor=df_factor, sci_opts=sci_opts)
+                           use_cumulant=use_cumulant, opts=opts, lib=lib, df_factor=df_factor, sci_opts=sci_opts, pt2_eps=pt2_eps)
 
 
 def sci_work_bytes(n, o, max_det=1 << 20, max_space=12):

@@ -1,6 +1,6 @@
 """Time solver="SCI-hip" per stage: screen, sort / merge, matrix build, Davidson, RDMs.
 
-    python tools/sci_bench.py [out.jsonl] [budget_s] [rows]        (default profiles/sci_bench.jsonl, 600 s per row, rows = synthetic,octane,small)
+    python tools/sci_bench.py [--pt2] [out.jsonl] [budget_s] [rows]        (default profiles/sci_bench.jsonl, 600 s per row, rows = synthetic,octane,small)
 
 Per row one JSON line: eps, ndet, rounds, nnz, the energy beside CCSD's, the time of the whole solve (host clock around DeviceFragment.solve_sci without energies,
 which ends in a synchronisation) and per stage (qemb_frag_sci_stage_ms: host wall time with the device drained at each boundary -- screen: the count and emit
@@ -9,7 +9,11 @@ two warm-ups.  A row whose single solve is so long that eleven of them would pas
 that such a row is not mistaken for a median of nine.  max_det is 2^23 (the default 2^20 refuses the smaller cutoffs at (42, 21)); a row that the limits still
 refuse (max_det, or the memory left for the matrix) is recorded with the library's message.
 Rows: the default synthetic fragment at (n, o) = (42, 21) and the first fragment of octane BE2 / STO-3G (tests/golden) for eps = 1e-3, 3e-4, 1e-4; (12, 6) at
-eps = 1e-12 beside "FCI-hip" on the same fragment."""
+eps = 1e-12 beside "FCI-hip" on the same fragment.
+--pt2: the second-order correction (DeviceFragment.sci_pt2) instead: per row of PT2_CUTOFFS one solve, then one call at eps_pt = eps / 100 and one at eps / 1000 (a
+first call that takes under a tenth of the budget is repeated and the median of up to five taken).  New lines with kind = "pt2": e_pt2, n_ext, batches, the three
+stage times (screen, merge, rows), the time of the call, the time of the solve of the same run and their ratio.  They stand beside the solve rows, which stay as
+they are; an earlier pt2 line of the same (fragment, eps, eps_pt) is replaced."""
 import json
 import statistics
 import sys
@@ -24,6 +28,7 @@ from quemb_amd.fragsolver import DeviceFragment, default_opts, default_sci_opts 
 CUTOFFS = (1e-3, 3e-4, 1e-4)
 WARM, REPS = 2, 9
 MAX_DET = 1 << 23
+PT2_CUTOFFS = {"synthetic(42,21)": (1e-3,), "octane": (1e-3, 3e-4), "synthetic(12,6)": (1e-12,)}      # by the start of the row's name
 
 
 def timed(fn, budget):
@@ -70,12 +75,45 @@ def fragments(lib, which):
         yield ("synthetic(12,6)", *synthetic(12, 6), (1e-12,))
 
 
+def pt2_rows(lib, opts, which, budget):
+    """the lines of --pt2"""
+    rows = []
+    for name, fr, o, h, dm0, _ in fragments(lib, which):
+        for eps in next(v for k, v in PT2_CUTOFFS.items() if name.startswith(k)):
+            so = default_sci_opts(lib, eps_var=eps, max_det=MAX_DET)
+            fr.solve_sci(o, h, dm0, opts=opts, sci_opts=so, eeval=False)      # (warm-up: the pool and the code objects)
+            t0 = time.perf_counter()
+            r = fr.solve_sci(o, h, dm0, opts=opts, sci_opts=so, eeval=False)
+            solve_ms = 1e3 * (time.perf_counter() - t0)
+            for eps_pt in (eps / 100, eps / 1000):
+                ts, res = [], None
+                while len(ts) < 5 and (len(ts) < 1 or ts[0] < 100.0 * budget):
+                    t0 = time.perf_counter()
+                    res = fr.sci_pt2(eps_pt)
+                    ts.append(1e3 * (time.perf_counter() - t0))
+                ms = statistics.median(ts)
+                rows.append(dict(kind="pt2", fragment=name, eps=eps, eps_pt=eps_pt, ndet=r["ndet"], e_corr_sci=r["e_corr_mo"], e_pt2=res["e_pt2"], n_ext=res["n_ext"],
+                                 batches=res["batches"], pt2_ms=ms, stage_ms=res["ms"], solve_ms=solve_ms, pt2_over_solve=ms / solve_ms, repeats=len(ts)))
+                print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def main():
-    out = Path(sys.argv[1]) if len(sys.argv) > 1 else ROOT / "profiles" / "sci_bench.jsonl"
-    budget = float(sys.argv[2]) if len(sys.argv) > 2 else 600.0
-    which = sys.argv[3].split(",") if len(sys.argv) > 3 else ["synthetic", "octane", "small"]
+    argv = [a for a in sys.argv[1:] if a != "--pt2"]
+    pt2 = "--pt2" in sys.argv[1:]
+    out = Path(argv[0]) if len(argv) > 0 else ROOT / "profiles" / "sci_bench.jsonl"
+    budget = float(argv[1]) if len(argv) > 1 else 600.0
+    which = argv[2].split(",") if len(argv) > 2 else ["synthetic", "octane", "small"]
     lib = _lib.init()
     opts = default_opts(lib, strict_convergence=0)
+    if pt2:
+        rows = pt2_rows(lib, opts, which, budget)
+        same = {(r["fragment"], r["eps"], r["eps_pt"]) for r in rows}
+        lines = [ln for ln in (out.read_text().splitlines() if out.exists() else []) if ln.strip()]
+        kept = [ln for ln in lines if not (json.loads(ln).get("kind") == "pt2" and (json.loads(ln)["fragment"], json.loads(ln)["eps"], json.loads(ln)["eps_pt"]) in same)]
+        out.parent.mkdir(parents=True, exist_ok=True)
+        out.write_text("".join(ln + "\n" for ln in kept) + "".join(json.dumps(r) + "\n" for r in rows))
+        return
     rows = []
     for name, fr, o, h, dm0, cutoffs in fragments(lib, which):
         e_ccsd = fr.solve(o, h, dm0, opts=opts, eeval=False)["e_corr_mo"]
@@ -100,7 +138,7 @@ def main():
             print(json.dumps(row), flush=True)
     out.parent.mkdir(parents=True, exist_ok=True)
     # the groups of rows may come from separate runs: rows of the fragments measured now replace those the file had, the others stay
-    kept = [ln for ln in (out.read_text().splitlines() if out.exists() else []) if ln.strip() and json.loads(ln)["fragment"] not in {r["fragment"] for r in rows}]
+    kept = [ln for ln in (out.read_text().splitlines() if out.exists() else []) if ln.strip() and (json.loads(ln).get("kind") == "pt2" or json.loads(ln)["fragment"] not in {r["fragment"] for r in rows})]
     out.write_text("".join(ln + "\n" for ln in kept) + "".join(json.dumps(r) + "\n" for r in rows))
 
 

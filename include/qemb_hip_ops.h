@@ -69,6 +69,10 @@ int qemb_pair_gemm_choice(int64_t rows, int64_t cols, int* cfg, int* ksplit);
  * solver sizes its slab buffers and launches from: out[9][6] = (M, N, K, cfg, ksplit, slabs) for Fvv', the two long-K T1 terms, ladder +/-, Xw +/-,
  * tau-side X +/-.  Introspection for tests and tools, no device call */
 int qemb_ccsd_gemm_plans(int o, int v, int64_t* out);
+/* the ring products of the CCSD update of a fragment of o occupied and v virtual orbitals: out[0] = 1 when the shape is in the replay regime (o^2 v^2 <= 2^22),
+ * out[1] the tile id (-1: the dispatcher's choice), out[2] the K split (0: the dispatcher's), out[3] the bytes of split-K workspace that the parallel region of
+ * the last two products takes inside a tape.  No device call */
+int qemb_ccsd_ring_plan(int o, int v, int64_t* out);
 int qemb_set_gemm_ksplit(int ksplit);      /* explicit split-K factor for qemb_op_gemm (0 = automatic) */
 /* entry `index` (0, 1, ...) of the table of production tiles (csrc/gemm_tiles.h), in the table's order: its id, tile rows x cols, k-step, whether it runs
  * the MODE 1 main loop on 16-byte loads, whether id + 200 addresses its classic loop, and the id of its pp-ladder twin (-1: none).  QEMB_ERR_ARG past

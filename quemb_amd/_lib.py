@@ -91,6 +91,7 @@ def _declare(lib):
     f("qemb_set_gemm_ksplit", I, I)
     f("qemb_pair_gemm_choice", I, L, L, C.POINTER(I), C.POINTER(I))
     f("qemb_ccsd_gemm_plans", I, I, I, C.POINTER(L))
+    f("qemb_ccsd_ring_plan", I, I, I, C.POINTER(L))
     f("qemb_gemm_tile_table", I, I, *([C.POINTER(I)] * 7))
     f("qemb_gemm_last_launch", I, *([C.POINTER(I)] * 7))
     f("qemb_op_ladder_pack_vvvv", I, L, L, P, P, L, P, L)

@@ -150,6 +150,12 @@ int qemb_ccsd_gemm_plans(int o, int v, int64_t* out) {
     for (const int64_t x : {g->M, g->N, g->K, (int64_t)g->cfg, (int64_t)g->ks, (int64_t)g->S}) *out++ = x;
   return QEMB_OK;
 }
+int qemb_ccsd_ring_plan(int o, int v, int64_t* out) {
+  if (o < 1 || v < 0 || !out) { set_error("qemb_ccsd_ring_plan: bad arguments"); return QEMB_ERR_ARG; }
+  const CcsdRingPlan r = ccsd_ring_plan(o, v);
+  out[0] = ((int64_t)o * o * v * v <= (int64_t)1 << 22) ? 1 : 0; out[1] = r.cfg; out[2] = r.ks; out[3] = r.region_ws_bytes;
+  return QEMB_OK;
+}
 int qemb_set_gemm_splitk(int enabled) { dev_gemm_set_auto_splitk(enabled); return QEMB_OK; }
 int qemb_op_copy4(const int64_t dim[4], const double* in, const int64_t si[4], double* out, const int64_t so[4],
                   double alpha, double beta) {

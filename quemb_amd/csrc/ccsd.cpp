@@ -299,6 +299,9 @@ int CcsdSolver::setup(MoIntegrals&& ints, const double* mo_energy_dev) {
   // split-K slabs of the few-output, long-K products stay where the slices wrote them (added up by y_traces / t1_assemble, the scatter passes): every such
   // product is planned here, once; its buffer is sized and -- in update_amps / apply_ladder -- its launch made from the same plan
   plans_ = ccsd_gemm_plans(o, v);
+  // (a tape gives the two ring products of its last region a slice of the split-K workspace each, and the workspace cannot grow under a capture: sized here, where
+  //  the block still enters the key of the tape -- Fragment::solve_begin_cc)
+  if (replay_regime()) QTRY(dev_region_workspace_reserve((size_t)ccsd_ring_plan(o, v).region_ws_bytes));
   QTRY(Fvv_.alloc(plans_.fvv.elems()));
   ovvv_pass_ = use_ovvv_pass(o, v, replay_regime());
   ovvv_G_ = ovvv_pass_ ? dev_ccsd_ovvv_slabs(o, v) : 0;
@@ -473,6 +476,25 @@ CcsdGemmPlans ccsd_gemm_plans(int64_t o, int64_t v) {
   p.x_p = pick_pair_gemm(npo, nov, ldp, true);      // (k_aware: their long K may ask for more slices)
   p.x_m = pick_pair_gemm(nmo, nov, ldm, true);
   return p;
+}
+// The ring products (update_amps has the reasons):
+//   o v >= 2048: the 128 x 256 tile;
+//   1024 <= o v < 2048, one mid-size fragment on the chip: 96 x 96 tiles with K in two slices -- 15 x 15 x 2 workgroups at o v = 1440, 119 us against the 151 us
+//     of 23 x 23 tiles of 64 x 64; tools/mid_gemm_bench.py.  QEMB_RING96=0: the 64 x 64 tiles, for A/B runs;
+//   below: 64 x 64 tiles once there are 200 of them, else the dispatcher's choice -- 32 x 32 at the o v = 441 of an octane fragment.
+// The K slices of a product are summed from the split-K workspace, S (ov)^2 doubles per product -- S = 2 for the mid-size tiles, and the six slices that dev_gemm
+// cuts by itself for the 16 x 8 tiles of o v = 2048 (gemm_auto_ksplit; below o v = 1024 K is too short for a split) -- and the last two products form one
+// parallel region: 32 (ov)^2 bytes for 1024 <= o v < 2048, 403 MB at o v = 2048, the last shape of the replay regime.
+CcsdRingPlan ccsd_ring_plan(int64_t o, int64_t v) {
+  static const bool ring96 = env_flag("QEMB_RING96", true);
+  const int64_t nov = o * v;
+  CcsdRingPlan r;
+  const bool mid_ring = ring96 && nov >= 1024 && nov < 2048;
+  r.cfg = (nov >= 2048) ? GEMM_128x256 : mid_ring ? GEMM_96x96 : (nov >= 256 && gemm_tile_count(GEMM_64x64, nov, nov) >= 200) ? GEMM_64x64 : -1;
+  r.ks = mid_ring ? 2 : 0;
+  const int S = gemm_slab_count(nov, r.ks > 1 ? r.ks : r.cfg >= 0 ? gemm_auto_ksplit(gemm_tile_count(r.cfg, nov, nov), nov) : 0);
+  if (S > 1) r.region_ws_bytes = 2 * (((int64_t)sizeof(double) * S * nov * nov + 255) / 256 * 256);
+  return r;
 }
 // pp-ladder through the (+/-) pair-packed operands (see the comment in update_amps)
 int CcsdSolver::apply_ladder(const double* x, double* out, bool rows_packed, bool hh) {
@@ -664,15 +686,10 @@ int CcsdSolver::update_amps(double* t1n, double* t2n) {
   // The right-hand operands of all four (ov)^3 products are symmetric matrices over (kc),(ld) -- L and ovov_t by the integral symmetry
   // (kc|ld) = (ld|kc), T' and u by t2[k,j,c,b] = t2[j,k,b,c] -- so each is passed in its K-contiguous (transposed) reading: both operands
   // of the GEMM are then staged through the conflict-free [row][BK+2] LDS image, on the 128 x 256 tile (512 tiles at ov = 4000: two per CU).
-  // (below o v = 1024: 64 x 64 tiles once there are 200 of them, else the dispatcher's choice -- 32 x 32 at the o v = 441 of an octane fragment)
-  const int64_t ring_tiles64 = gemm_tile_count(GEMM_64x64, nov, nov);
-  // (1024 <= o v < 2048, one mid-size fragment on the chip: 96 x 96 tiles with K in two slices -- 15 x 15 x 2 workgroups at o v = 1440, 119 us against the 151 us
-  //  of 23 x 23 tiles of 64 x 64; tools/mid_gemm_bench.py.  QEMB_RING96=0: the 64 x 64 tiles, for A/B runs)
-  static const bool ring96 = env_flag("QEMB_RING96", true);
-  const bool mid_ring = ring96 && nov >= 1024 && nov < 2048;
-  const int cfg_ring = (nov >= 2048) ? GEMM_128x256 : mid_ring ? GEMM_96x96 : (nov >= 256 && ring_tiles64 >= 200) ? GEMM_64x64 : -1;
+  // (below o v = 2048 smaller tiles, between 1024 and 2048 with K in two slices: ccsd_ring_plan)
+  const CcsdRingPlan rp = ccsd_ring_plan(o, v);
   auto ring = [&](double al, const double* A, const double* Bsym, double be, double* C) {
-    return gemm(nov, nov, nov, al, A, nov, true, Bsym, nov, true, be, C, nov, 1, 0, 0, 0, cfg_ring, mid_ring ? 2 : 0);
+    return gemm(nov, nov, nov, al, A, nov, true, Bsym, nov, true, be, C, nov, 1, 0, 0, 0, rp.cfg, rp.ks);
   };
   if (ring_prep_) {
     // Wvoov itself is never read -- only R = Wvoov - Wvovo/2 and Wvovo go on -- so the first product is written on its own (P1 = 1/4 u~ L, beta = 0: no read of
@@ -741,9 +758,9 @@ bool CcsdSolver::replay_regime() const { return (int64_t)o_ * o_ * v_ * v_ <= (i
 //   > 0  cannot record (the backend does not capture, or the captured sequence cannot be a tape): nothing is wrong, the caller runs eagerly;
 //   < 0  an error: of dev_graph_begin (*began stays false), else of update_amps under capture, else of the end of the capture.
 // Nothing is kept unless 0 comes back.  The callers clear graph_ok_ (prepare_tape not before its second attempt) and decide which errors they pass on.
-int CcsdSolver::record_update(bool as_tape, bool* began) {
+int CcsdSolver::record_update(bool as_tape, bool* began, bool regions) {
   *began = false;
-  const int rc = dev_graph_begin(as_tape ? 1 : 0);
+  const int rc = dev_graph_begin(as_tape ? (regions ? 1 : 2) : 0);
   if (rc != 0) return rc;
   *began = true;
   const int rc2 = update_amps(ampn_.p, ampn_.p + (int64_t)o_ * v_);
@@ -804,7 +821,13 @@ int CcsdSolver::prepare_tape() {
     const int rc = record_update(true, &began);
     if (rc == 0) return 0;
     // (a failed first attempt: whatever went wrong shows again in the eager pass)
-    if (!began || attempt == 1) { graph_ok_ = false; return rc < 0 ? rc : 0; }
+    if (!began || attempt == 1) {
+      // A region whose split-K slices do not fit the workspace side by side (an eager pass sizes it for one product, setup() for the ring region only) is no
+      // reason to fail: the same update recorded WITHOUT region marks shares one slice, like the executable graph; dev_tape_run then merges this tape
+      // position by position with its peers.
+      if (began && rc == QEMB_ERR_ALLOC && record_update(true, &began, /*regions=*/false) == 0) return 0;
+      graph_ok_ = false; return rc < 0 ? rc : 0;
+    }
   }
   return 0;
 }

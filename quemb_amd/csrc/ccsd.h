@@ -50,6 +50,10 @@ struct CcsdGemmPlans { GemmPlan fvv, pa, pb, ladder_p, ladder_m, xw_p, xw_m, x_p
 CcsdGemmPlans ccsd_gemm_plans(int64_t o, int64_t v);
 // the one-pass ring preparation rule (ccsd.cpp, next to the tile rules): whether a solver of this shape replaces the four passes by dev_ccsd_ring_prep
 bool ccsd_use_ring_prep(int64_t o, int64_t v, bool replay);
+// the four (ov)^3 ring products of the update: their tile (cfg < 0: the dispatcher's choice), their K split (0: the dispatcher's), and the split-K workspace that
+// the parallel region of the last two asks for when it is recorded into a tape (a slice per product; 0: no split)
+struct CcsdRingPlan { int cfg = -1, ks = 0; int64_t region_ws_bytes = 0; };
+CcsdRingPlan ccsd_ring_plan(int64_t o, int64_t v);
 
 class CcLambda;
 
@@ -94,7 +98,7 @@ class CcsdSolver {
  private:
   int update_amps(double* t1n, double* t2n);
   bool replay_regime() const;                       // small enough to be launch bound, and no recording has failed
-  int record_update(bool as_tape, bool* began);     // one update_amps recorded into ampn_: 0 recorded, > 0 cannot record (run eagerly), < 0 error
+  int record_update(bool as_tape, bool* began, bool regions = true);     // one update_amps recorded into ampn_: 0 recorded, > 0 cannot record (run eagerly), < 0 error
   int energy(const double* t1, const double* t2, double* e);
   int make_tau(const double* t1, const double* t2, double* tau);
 

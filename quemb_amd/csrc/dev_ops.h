@@ -63,7 +63,11 @@ const char* dev_backend_name();      // "hip-gfx950" for the product, "hostcheck
 // with one host call.  Only pure launch sequences may be captured (no allocation, no host transfer, no timers).
 // dev_graph_begin returns 1 (not an error) when the backend cannot capture; the caller then simply runs eagerly.
 typedef void* dev_graph_t;
-int dev_graph_begin(int for_tape = 0);       // for_tape: the capture will end as a tape (dev_tape_end): parallel regions leave their markers
+int dev_graph_begin(int for_tape = 0);       // for_tape: the capture will end as a tape (dev_tape_end): parallel regions leave their markers (2: a tape without them)
+// The split-K workspace of the calling context holds at least `bytes` from now on (never inside a capture).  Inside a parallel region of a tape capture every
+// split-K product takes a slice of its own, counted from the start of the workspace in every region; the workspace cannot grow under a capture, so whoever
+// records a tape asks for the bytes of its largest region first (CcsdSolver::setup) -- before the key of the tape is taken (dev_alloc_trace_end names the block).
+int dev_region_workspace_reserve(size_t bytes);
 // Parallel regions inside a tape capture: chains of operations that do not depend on each other (dev_ops_hip.hip has the contract).  No-ops when the calls are
 // executed or captured for an executable graph: program order is always a valid order.
 int dev_region_begin();

@@ -55,7 +55,7 @@ struct DevCtx {
   // parallel regions of a tape capture (dev_region_*): the marks that delimit regions / chains in the captured chain of nodes, and a bump offset so that
   // every split-K product recorded inside a region gets its own slice of gws (the chains of a region may run side by side)
   std::vector<std::pair<hipGraphNode_t, int>> marks;      // (last captured node at the time of the mark, mark)
-  bool tape_capture = false, in_region = false;
+  bool tape_capture = false, tape_regions = true, in_region = false;      // (tape_regions: this tape capture records its regions, dev_graph_begin)
   bool alloc_trace = false; unsigned long long alloc_hash = 0;      // dev_alloc_trace_*
   size_t gws_bump = 0;
   TimerSlot timers[TIMER_NSLOTS];
@@ -448,7 +448,10 @@ int dev_mem_info(size_t* free_b, size_t* total_b) { REQUIRE_INIT(); HIP_TRY(hipM
 double* gemm_workspace(size_t bytes) {
   if (ctx().in_region) {      // recorded inside a parallel region: a slice of its own (the region's chains do not share scratch)
     const size_t need = (bytes + 255) / 256 * 256;
-    if (!g_gws || ctx().gws_bump + need > g_gws_bytes) { set_error("split-K workspace too small for a parallel region"); return nullptr; }
+    // (QEMB_REGION_WS_MB=<n>: the slices of a region may take n MB at the most, whatever the workspace holds -- tests of the recording without region marks)
+    const long long cap_mb = env_int("QEMB_REGION_WS_MB", -1);
+    const size_t room = cap_mb >= 0 ? std::min(g_gws_bytes, (size_t)cap_mb << 20) : g_gws_bytes;
+    if (!g_gws || ctx().gws_bump + need > room) { set_error("split-K workspace too small for a parallel region"); return nullptr; }
     double* p = (double*)((unsigned char*)g_gws + ctx().gws_bump);
     ctx().gws_bump += need;
     return p;
@@ -460,6 +463,12 @@ double* gemm_workspace(size_t bytes) {
   if (hipMalloc((void**)&g_gws, want) != hipSuccess) { set_error("split-K workspace hipMalloc failed"); return nullptr; }
   g_gws_bytes = want;
   return g_gws;
+}
+int dev_region_workspace_reserve(size_t bytes) {
+  REQUIRE_INIT();
+  if (bytes <= g_gws_bytes) return QEMB_OK;
+  if (g_capturing) { set_error("split-K workspace growth inside a captured region"); return QEMB_ERR_ALLOC; }
+  return gemm_workspace(bytes) ? QEMB_OK : QEMB_ERR_ALLOC;
 }
 
 static int ensure_ws(size_t bytes) {
@@ -480,7 +489,7 @@ int dev_graph_begin(int for_tape) {
   if (for_tape && !g_gws) { if (!gemm_workspace(1)) return QEMB_ERR_ALLOC; }      // regions slice the workspace: it must exist before the capture
   HIP_TRY(hipStreamBeginCapture(g_stream, hipStreamCaptureModeThreadLocal));
   g_capturing = true;
-  ctx().tape_capture = for_tape != 0; ctx().in_region = false; ctx().gws_bump = 0; ctx().marks.clear();
+  ctx().tape_capture = for_tape != 0; ctx().tape_regions = for_tape != 2; ctx().in_region = false; ctx().gws_bump = 0; ctx().marks.clear();
   return QEMB_OK;
 }
 // Parallel regions (round 5).  Between dev_region_begin and dev_region_end the caller declares CHAINS of operations -- dev_region_chain starts the next one --
@@ -497,7 +506,7 @@ static bool regions_enabled() {      // QEMB_TAPE_REGIONS=0: no markers are reco
   return on;
 }
 static int region_mark(int value) {
-  if (!g_capturing || !ctx().tape_capture || !regions_enabled()) return QEMB_OK;
+  if (!g_capturing || !ctx().tape_capture || !ctx().tape_regions || !regions_enabled()) return QEMB_OK;
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
   unsigned long long id = 0;
   hipGraph_t graph = nullptr;
@@ -508,7 +517,9 @@ static int region_mark(int value) {
   ctx().marks.emplace_back(ndeps ? deps[0] : nullptr, value);
   return QEMB_OK;
 }
-int dev_region_begin() { if (g_capturing && ctx().tape_capture && regions_enabled()) { ctx().in_region = true; } { const int rc_ = region_mark(MARK_REGION_BEGIN); if (rc_) return rc_; } return region_mark(MARK_CHAIN); }
+// (the slices of a region are counted from the start of the workspace: the regions of a tape run one after the other on one stream, and every split-K product
+//  is followed by its reduction inside its own chain, so no slice outlives its region)
+int dev_region_begin() { if (g_capturing && ctx().tape_capture && ctx().tape_regions && regions_enabled()) { ctx().in_region = true; ctx().gws_bump = 0; } { const int rc_ = region_mark(MARK_REGION_BEGIN); if (rc_) return rc_; } return region_mark(MARK_CHAIN); }
 int dev_region_chain() { return region_mark(MARK_CHAIN); }
 int dev_region_end() { ctx().in_region = false; return region_mark(MARK_REGION_END); }
 int dev_graph_end(dev_graph_t* out) {

@@ -12,6 +12,8 @@ number bench.py's parity field compares) and the DIIS solve to |dE| < 1e-11.  Ab
                                                            -> tests/golden/frag220_f1.npz, frag220_f2.npz)
     python tests/golden/make_golden_frag220.py 132:12     (round 5: the mid-size point of bench.py's size sweep, n = 132, n_occ = 12, same family and seed,
                                                            ERI scale 0.06 (55 / n)^(1/2) as tools/size_sweep.py -> tests/golden/frag132.npz; a minute)
+    python tests/golden/make_golden_frag220.py 85:24:lockstep   (n:o:tag -> tests/golden/frag85_lockstep.npz, results of the converged solve only: the
+                                                           (24, 61) fragment of the lock-step batches, tests/lockstep_cases.py)
 """
 import sys
 import time
@@ -37,11 +39,11 @@ def bench_fragment(n, seed, scale):
     return h, B
 
 
-def main(frag=0, n=N, o=O, scale=SCALE):
+def main(frag=0, n=N, o=O, scale=SCALE, tag=None):
     N, O, SCALE = n, o, scale          # (shadow the module constants: the body below is written in their terms)
     t0 = time.time()
     seed = SEED + frag
-    out = ("frag220.npz" if frag == 0 else f"frag220_f{frag}.npz") if n == 220 else f"frag{n}.npz"
+    out = ("frag220.npz" if frag == 0 else f"frag220_f{frag}.npz") if n == 220 else f"frag{n}.npz" if tag is None else f"frag{n}_{tag}.npz"
     h, B = bench_fragment(N, seed, SCALE)
     naux = B.shape[0]
     Bf = B.reshape(naux, -1)
@@ -58,6 +60,13 @@ def main(frag=0, n=N, o=O, scale=SCALE):
     B_mo = np.einsum("Ppq,pi,qj->Pij", B, C, C, optimize=True)
     er = ccsd_lean.LeanEris(B_mo, O, mf["mo_energy"])
     print(f"MO blocks ({time.time() - t0:.0f} s)", flush=True)
+    if tag is not None:      # results only: the converged solve
+        conv, ecc, t1, t2, nit = ccsd_lean.kernel(er, conv_tol=1e-11, conv_tol_normt=1e-9)
+        assert conv
+        np.savez_compressed(ROOT / "tests" / "golden" / out, n=N, o=O, seed=seed, scale=SCALE, e_scf=mf["e_tot"], mo_energy=mf["mo_energy"],
+                            e_corr=ecc, n_iter=nit, rdm1_emb=C @ rdm.make_rdm1_ccsd_t1(t1) @ C.T * 0.5)
+        print(f"{out}: E_corr {ecc:.12f} in {nit} iterations ({time.time() - t0:.0f} s)", flush=True)
+        return
     t1, t2 = ccsd_lean.init_amps(er)
     e_mp2 = ccsd_lean.energy(t1, t2, er)
     for _ in range(3):
@@ -76,7 +85,8 @@ def main(frag=0, n=N, o=O, scale=SCALE):
 if __name__ == "__main__":
     for a in (sys.argv[1:] or ["0"]):
         if ":" in a:
-            nn, oo = (int(x) for x in a.split(":"))
-            main(0, nn, oo, 0.06 * min(1.0, (55.0 / nn) ** 0.5))
+            nn, oo, *tag = a.split(":")
+            nn, oo = int(nn), int(oo)
+            main(0, nn, oo, 0.06 * min(1.0, (55.0 / nn) ** 0.5), tag[0] if tag else None)
         else:
             main(int(a))

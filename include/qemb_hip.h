@@ -274,6 +274,30 @@ int qemb_frag_rdm2(qemb_frag_t f, int kind, int with_dm1, double* out);
  * three o^2 v^2 tensors and the integral work space of forming t2 again) with min(free device memory, bytes) and fails with QEMB_ERR_ALLOC and n in the message when
  * it does not fit.  bytes < 0 (default): the free device memory alone. */
 int qemb_frag_rdm2_mem_limit(qemb_frag_t f, int64_t bytes);
+/* The perturbative triples correction E_(T) of the last CCSD solve of this fragment, relaxed or not (only t1 and t2 are read), from the amplitudes it left on
+ * the device, the orbital energies, and (ia|bc), (ia|jk), (ia|jb) formed again by the route the fragment takes (3-index factor or packed block).  Closed shell,
+ * Fock = diag(mo_energy), chemists' notation, i j k m occupied, a b c f virtual:
+ *     g[i,j,k,a,b,c] = sum_f (ia|fb) t2[k,j,c,f] - sum_m (ia|mj) t2[m,k,b,c]
+ *     W = the sum of g over the six simultaneous permutations of the pairs (i,a), (j,b), (k,c);   V = W + t1[i,a] (jb|kc) + t1[j,b] (ia|kc) + t1[k,c] (ia|jb)
+ *     E_(T) = 1/3 sum W r3(V) / D,   r3(X)_ijk = 4 X_ijk + X_jki + X_kij - 2 X_kji - 2 X_ikj - 2 X_jik,   D = e_i + e_j + e_k - e_a - e_b - e_c   (not guarded)
+ *   It is the triples energy of the EMBEDDING problem of this fragment, a diagnostic of what CCSD leaves out: it is added to no fragment or BE energy, and a
+ *   centre-projected BE-level (T) energy is not formed.  The virtual orbitals are cut into tiles of *tile (the largest of 16, 8, 4, 2, 1 whose six product
+ *   buffers of 8 tile^3 o^3 bytes stay within 192 MiB and whose working set fits) and *n_tile_triples tile triples A >= B >= C are visited; per triple six batched
+ *   FP64 MFMA products over K = v + o form g (particle and hole term) and one kernel the rest.  No atomics: the same bits on every call.  ms4: device time (ms) of the images, the
+ *   products and the assembly, then host wall time of forming the integrals again.  Every output is nullable.  Fewer than two occupied or two virtual orbitals (no triples): 0.0, tile 0.
+ *   Errors: no solve since the ERIs or orbitals were set, a last solve that was not CCSD, or amplitudes that were released since (qemb_frag_drop_amplitudes): QEMB_ERR_ARG.
+ *   Before anything is allocated the working set with tile 1 (qemb_frag_ccsd_t_bytes) is compared with min(free device memory, the limit of
+ *   qemb_frag_ccsd_t_mem_limit): QEMB_ERR_ALLOC naming n.
+ * qemb_frag_ccsd_t_bytes: the device bytes of the call with that tile for nsocc occupied orbitals (0: as many as the last solve had): the larger of the integral transformation (its work
+ *   buffers and every block it leaves) and of the three kept blocks with the two images (v^2 o + v o^2)(v + o), the six buffers, the partial sums and, beyond 20
+ *   occupied orbitals, the scratch of the kernel.
+ * qemb_frag_ccsd_t_mem_limit: the device bytes qemb_frag_ccsd_t of THIS fragment may take; bytes < 0 (default): the free device memory alone.
+ * qemb_frag_drop_amplitudes: releases the t1 / t2 (and Lambda multipliers) this fragment keeps from its last CCSD solve -- 8 (o v + o^2 v^2) bytes each; the next
+ *   solve starts from the MP2 guess, and qemb_frag_rdm2(QEMB_RDM2_CCSD) and qemb_frag_ccsd_t are refused until it has run. */
+int qemb_frag_ccsd_t(qemb_frag_t f, double* e_t, int* tile, int64_t* n_tile_triples, double* ms4);
+int qemb_frag_ccsd_t_bytes(qemb_frag_t f, int nsocc, int tile, int64_t* bytes);
+int qemb_frag_ccsd_t_mem_limit(qemb_frag_t f, int64_t bytes);
+int qemb_frag_drop_amplitudes(qemb_frag_t f);
 /* The same tensor left ON THE DEVICE in out_dev (n^4 doubles from qemb_malloc): what the full-basis accumulation of BE.rdm12_fullbasis rotates (the guard
  * then counts the workspace of the call alone). */
 int qemb_frag_rdm2_dev(qemb_frag_t f, int kind, int with_dm1, double* out_dev);

@@ -233,6 +233,9 @@ int qemb_op_mp2_amplitudes(int64_t o, int64_t v, const double* ovov, const doubl
 /* The fragment 2-RDM from amplitudes that are handed in (all pointers on the device): kind QEMB_RDM2_CCSD (t1 [o][v], t2 [o][o][v][v]) or QEMB_RDM2_MP2 (t2; t1 is
  * not read), dm1c = dm1 - 2 I_occ ([n][n]) or NULL for with_dm1 = 0, out [n]^4 with n = o + v.  Every element of out is written once.  Returns after the kernel. */
 int qemb_op_rdm2_assemble(int kind, int64_t o, int64_t v, const double* t1, const double* t2, const double* dm1c, double* out);
+/* E_(T) of qemb_frag_ccsd_t from handed-in DEVICE arrays: t1 [o][v], t2 [o][o][v][v], ovvv [o][v][v][v] = (ia|bc), ovoo [o][v][o][o] = (ia|jk),
+ * ovov [o][v][o][v] = (ia|jb), eo [o], ev [v]; tile >= 1: the tile of the virtual orbitals (cut to v), forced.  *e_t: host.  o < 2 or v < 2 (no triples): 0.0 without a launch. */
+int qemb_op_ccsd_t(int o, int v, const double* t1, const double* t2, const double* ovvv, const double* ovoo, const double* ovov, const double* eo, const double* ev, int tile, double* e_t);
 /* The full-basis passes of BE.rdm12_fullbasis / compute_energy_full on [m]^4 tensors (device pointers; molbe/mbe.py:543-620, :781-789):
  *   rdm2_add_nc:     X[i,j,k,l] += alpha (g[i,j] g[k,l] - g[i,l] g[j,k] / 2), g m x m
  *   rdm2_symmetrize: X = (X + X^T) / 2 in place with X^T[p,q,r,s] = X[s,r,q,p]; g != NULL: plus the non-connected part of g

@@ -237,6 +237,11 @@ def _declare(lib):
     f("qemb_op_sci_rdm12", I, I, I, P, P, L, P, P, P, I, P, P)
     f("qemb_frag_rdm2", I, V, I, I, P)
     f("qemb_frag_rdm2_mem_limit", I, V, L)
+    f("qemb_frag_ccsd_t", I, V, DP, IP, C.POINTER(L), P)
+    f("qemb_frag_ccsd_t_bytes", I, V, I, I, C.POINTER(L))
+    f("qemb_frag_ccsd_t_mem_limit", I, V, L)
+    f("qemb_frag_drop_amplitudes", I, V)
+    f("qemb_op_ccsd_t", I, I, I, P, P, P, P, P, P, P, I, DP)
     f("qemb_frag_rdm2_dev", I, V, I, I, P)
     f("qemb_rdm2_full_guard", I, L, L, L)
     f("qemb_frag_lambda_iters", I, P, C.POINTER(C.c_int))

@@ -422,6 +422,11 @@ int qemb_op_rdm2_assemble(int kind, int64_t o, int64_t v, const double* t1, cons
   return dev_sync();
 }
 
+int qemb_op_ccsd_t(int o, int v, const double* t1, const double* t2, const double* ovvv, const double* ovoo, const double* ovov, const double* eo, const double* ev, int tile, double* e_t) {
+  if (!e_t) { set_error("qemb_op_ccsd_t: e_t is NULL"); return QEMB_ERR_ARG; }
+  return ccsd_t_energy(o, v, t1, t2, ovvv, ovoo, ovov, eo, ev, tile, e_t, nullptr);
+}
+
 int qemb_op_rdm2_add_nc(int64_t m, const double* g, double alpha, double* X) { return dev_rdm2_add_nc(m, g, alpha, X); }
 int qemb_op_rdm2_symmetrize(int64_t m, const double* g, double* X) { return dev_rdm2_symmetrize(m, g, X); }
 int qemb_op_rdm2_eri_dot(int64_t m, int sym, const double* eri, const double* K, double* e_host) {
@@ -875,6 +880,25 @@ int qemb_rdm2_full_guard(int64_t nao, int64_t need_bytes, int64_t limit_bytes) {
   return QEMB_OK;
 }
 int qemb_frag_rdm2_mem_limit(qemb_frag_t f, int64_t bytes) { CHECK_FRAG(f); FRAG(f)->set_rdm2_mem_limit(bytes); return QEMB_OK; }
+int qemb_frag_ccsd_t(qemb_frag_t f, double* e_t, int* tile, int64_t* n_tile_triples, double* ms4) {
+  CHECK_FRAG(f);
+  CcsdTStats st;
+  double ms_int = 0.0;
+  const int rc = FRAG(f)->ccsd_t(e_t, &st, &ms_int);
+  if (tile) *tile = st.tile;
+  if (n_tile_triples) *n_tile_triples = st.n_tile_triples;
+  if (ms4) { ms4[0] = st.ms_images; ms4[1] = st.ms_gemm; ms4[2] = st.ms_assemble; ms4[3] = ms_int; }
+  return rc;
+}
+int qemb_frag_ccsd_t_bytes(qemb_frag_t f, int nsocc, int tile, int64_t* bytes) {
+  CHECK_FRAG(f);
+  if (nsocc == 0) nsocc = FRAG(f)->last_nsocc();      // as many as the last solve had
+  if (nsocc <= 0 || nsocc > FRAG(f)->n() || tile < 1 || !bytes) { set_error("qemb_frag_ccsd_t_bytes: bad arguments (need 0 < nsocc <= n -- or 0 after a solve -- and tile >= 1)"); return QEMB_ERR_ARG; }
+  *bytes = FRAG(f)->ccsd_t_work_bytes(nsocc, tile);
+  return QEMB_OK;
+}
+int qemb_frag_ccsd_t_mem_limit(qemb_frag_t f, int64_t bytes) { CHECK_FRAG(f); FRAG(f)->set_ccsd_t_mem_limit(bytes); return QEMB_OK; }
+int qemb_frag_drop_amplitudes(qemb_frag_t f) { CHECK_FRAG(f); FRAG(f)->drop_amplitudes(); return QEMB_OK; }
 int qemb_frag_lambda_iters(qemb_frag_t f, int* n_iter) { CHECK_FRAG(f); if (n_iter) *n_iter = FRAG(f)->last_lambda_iters; return QEMB_OK; }
 int qemb_frag_scf(qemb_frag_t f, int nsocc, const double* h, const double* dm0, const qemb_solver_opts* opts, double* mo_coeff,
                   double* mo_energy, double* J, double* K, double* e_scf, int* converged, int* cycles) {

@@ -106,7 +106,7 @@ int dev_timer_reset(int slot);
 int dev_ctx_timer_read(int ctx, int slot, double* total_ms, int64_t* count, int reset);   // another context's timers (idle context)
 int dev_timer_live_events(int slot);   // event pairs currently held by the calling context's slot (bounded; test hook)
 enum { TIMER_LADDER = 0, TIMER_RINGS = 1, TIMER_ITER = 2, TIMER_AO2MO = 3, TIMER_SCF = 4,
-       TIMER_GEMM_ANY = 5, TIMER_SCHMIDT = 6, TIMER_DF = 7, TIMER_NSLOTS = 16 };
+       TIMER_GEMM_ANY = 5, TIMER_SCHMIDT = 6, TIMER_DF = 7, TIMER_T_IMAGES = 12, TIMER_T_GEMM = 13, TIMER_T_ASSEMBLE = 14, TIMER_NSLOTS = 16 };
 // A lap that always ends: the stop event is recorded when the scope is left, also on an early (error) return of the bracketed region.
 struct TimerScope {
   int slot; bool open;
@@ -494,6 +494,17 @@ int dev_sci_csr_fill(int n, const double* h, const double* V, int64_t N, const u
 int dev_sci_spmv(int64_t N, const int64_t* rowptr, const int32_t* col, const double* val, const double* x, double* y);
 int dev_sci_rdm(int n, int64_t N, const uint64_t* keys, const int64_t* rowptr, const int32_t* col, const double* c, double* dm1, double* dm2);
 int dev_sci_dm2_finish(int n, int o_cum, const double* dm1, double* dm2);
+
+// ---- perturbative triples of CCSD (ccsd_t.cpp; kernels in ccsd_t_ops.hip, scalar restatement for the mock in ccsd_t_ops_hostcheck.cpp; the arithmetic of both in
+//      ccsd_t_core.h, which defines CcsdTArgs) ------------
+//   assemble: partial[(la, lb, lc)] = weight / 3 * sum_ijk W r3(V) / D for every (a,b,c), a >= b >= c and not a = b = c, of one tile triple (0 elsewhere), from the six product
+//             buffers of the triple (particle and hole term: ccsd_t.cpp), t1, ovov and the orbital energies.  One workgroup per element, no atomics.
+//   sum:      out[slot] = the sum of m doubles in one fixed order (one workgroup: 256 strided sums, then a tree)
+//   total:    out[0] = in[0] + ... + in[m - 1] in ascending order
+struct CcsdTArgs;
+int dev_ccsd_t_assemble(const CcsdTArgs& A);
+int dev_ccsd_t_sum(int64_t m, const double* in, double* out, int64_t slot);
+int dev_ccsd_t_total(int64_t m, const double* in, double* out);
 
 // ---- k-point density fitting (kdf.cpp; kernels in kdf_ops.hip, scalar restatement for the mock in kdf_ops_hostcheck.cpp) -------------------------
 // Three HBM passes around the two quarter transforms of KdfContext::transform; no atomics, every output element written once.

@@ -1193,6 +1193,58 @@ int Fragment::rdm2(int kind, int with_dm1, double* out, bool out_on_device) {
   return dev_d2h(out, R, sizeof(double) * n2 * n2);
 }
 
+// ---- the perturbative triples correction of the last CCSD solve (ccsd_t.cpp), on MO blocks formed again as rdm2() forms again what it needs
+int64_t Fragment::ccsd_t_work_bytes(int o, int tile) const {
+  const int64_t n = n_, v = n - o, O = o, n2 = n * n, np = npair(n), npv = v * (v + 1) / 2, nm = v * (v - 1) / 2;
+  const int64_t kept = O * v * v * v + O * O * O * v + O * O * v * v;
+  // mo_transform / mo_transform_factor without site rows: X0, X1, the six blocks, the packed ovvv of the factor route and the (+/-) packed ladder operands
+  // (rows padded to an even length); on the factor route the unpacked and half-transformed factor and its packed MO image
+  int64_t transform = 2 * mo_transform_work(n_) + O * O * O * O + kept + 2 * O * O * v * v + npv * (npv + 1) + std::max<int64_t>(nm, 1) * (nm + 2);
+  if (use_factor_route()) transform += (int64_t)df_naux_ * (2 * n2 + np) + O * v * npv;
+  return std::max(8 * transform, 8 * kept + ccsd_t_bytes(O, v, tile));
+}
+int Fragment::ccsd_t(double* e_t, CcsdTStats* stats, double* ms_integrals) {
+  if (e_t) *e_t = 0.0;
+  if (stats) *stats = CcsdTStats();
+  if (ms_integrals) *ms_integrals = 0.0;
+  if (last_kind_ < 0) { set_error("Fragment::ccsd_t: no solve has run on this fragment since its ERIs or orbitals were last set"); return QEMB_ERR_ARG; }
+  if (last_kind_ != QEMB_RDM2_CCSD) {
+    set_error(std::string("Fragment::ccsd_t: the last solve of this fragment was ") + (last_kind_ == QEMB_RDM2_MP2 ? "MP2" : last_kind_ == QEMB_RDM2_FCI ? "FCI" : "SCI") + ", not CCSD");
+    return QEMB_ERR_ARG;
+  }
+  const int n = n_, o = last_o_, v = n - o;
+  if (v == 0) return 0;      // a single determinant
+  if (!t_prev_.p || t_prev_o_ != o) { set_error("Fragment::ccsd_t: the amplitudes of the last CCSD solve were not kept"); return QEMB_ERR_ARG; }
+  if (o < 2 || v < 2) return 0;      // no triples: nothing is formed
+  // ---- the guard, before anything is allocated: the largest tile whose working set fits
+  double room = 0.0;
+  QTRY(device_room(ccsd_t_mem_limit_, &room));
+  const int64_t kept = 8 * ((int64_t)o * v * v * v + (int64_t)o * o * o * v + (int64_t)o * o * v * v);      // the three blocks beside the working set of ccsd_t_energy
+  const int tile = (double)ccsd_t_work_bytes(o, 1) <= room ? ccsd_t_pick_tile(o, v, room - (double)kept) : 0;
+  if (tile < 1) {
+    const double need = (double)ccsd_t_work_bytes(o, 1);
+    set_error("Fragment::ccsd_t: n = " + std::to_string(n) + ", n_occ = " + std::to_string(o) + ": the triples correction takes " + std::to_string((int64_t)need) + " bytes (" +
+              std::to_string(need * 1e-9) + " GB) with the smallest tile, more than the " + std::to_string(room * 1e-9) + " GB of device memory it may take");
+    return QEMB_ERR_ALLOC;
+  }
+  // ---- ovvv, ovoo, ovov by the route the fragment would take; everything else the transformation leaves goes back at once
+  const auto t0 = std::chrono::steady_clock::now();
+  DBuf ovvv, ovoo, ovov;
+  {
+    const bool route = last_route_factor_;      // (mo_route_used keeps describing the solve)
+    DBuf X1; bool unpacked = false; MoIntegrals ints;
+    int rc = scf_operand(X1, &unpacked);
+    if (rc == 0) rc = mo_integrals(o, 0, X1, unpacked, ints, false, false);
+    last_route_factor_ = route;
+    s4_transient_.release();
+    if (rc) return rc;
+    ovvv = std::move(ints.ovvv); ovoo = std::move(ints.ovoo); ovov = std::move(ints.ovov);
+  }
+  QTRY(dev_sync());
+  if (ms_integrals) *ms_integrals = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return ccsd_t_energy(o, v, t_prev_.p, t_prev_.p + (int64_t)o * v, ovvv, ovoo, ovov, eps_, eps_.p + o, tile, e_t, stats);
+}
+
 int Fragment::solve_mp2_batch(const std::vector<Fragment*>& frs, const std::vector<int>& o, const std::vector<const double*>& h, const std::vector<const double*>& dm0,
                               const FragmentOptions& opt, int eeval, std::vector<FragmentResult>& res, const std::vector<BatchOutputs>& outs) {
   const int F = (int)frs.size();

@@ -10,6 +10,7 @@
 #include "scf.h"
 #include "fci.h"
 #include "sci.h"
+#include "ccsd_t.h"
 
 namespace qemb {
 
@@ -122,6 +123,20 @@ class Fragment {
   int sci_pt2(double eps_pt, int64_t max_ext, double* e_pt2, int64_t* n_ext, int* batches, double* ms3);
   static int64_t sci_pt2_work_bytes(int n, int nsocc, int64_t ndet, int64_t max_ext);      // sci_pt2_bytes and the n^4 pieces of fci_mo_integrals, h
   double fci_residual() const { return fci_residual_; }
+  // The perturbative triples correction E_(T) (ccsd_t.h) of the last CCSD solve of this fragment, relaxed or not, from the kept t1 / t2, the orbital energies
+  // and ovvv, ovoo, ovov formed again by the route the fragment would take (factor or block), as rdm2() forms t2 of an MP2 solve again.  A diagnostic of the
+  // embedding problem: it is added to no energy.  No solve, a last solve that was not CCSD, amplitudes that were not kept, or ERIs / orbitals changed since:
+  // QEMB_ERR_ARG.  The tile is the largest of kCcsdTTiles whose working set ccsd_t_work_bytes fits the room (free device memory, or set_ccsd_t_mem_limit); if
+  // Tv = 1 does not fit: QEMB_ERR_ALLOC naming n, before anything is allocated.  mo_route_used, resident_bytes and the kept amplitudes stay as the solve left
+  // them.  No virtual orbitals: 0.0.  ms_integrals: host wall time of forming the blocks again.  Outputs nullable.
+  int ccsd_t(double* e_t, CcsdTStats* stats, double* ms_integrals);
+  void set_ccsd_t_mem_limit(int64_t bytes) { ccsd_t_mem_limit_ = bytes; }
+  // device bytes of ccsd_t() with that tile: the larger of the transformation (its two work buffers, every block it leaves, the factor's images on that route)
+  // and of the three kept blocks with ccsd_t_bytes
+  int64_t ccsd_t_work_bytes(int o, int tile) const;
+  // the kept t1 / t2 and Lambda multipliers go back to the pool: the next solve starts from the MP2 guess; rdm2(QEMB_RDM2_CCSD) and ccsd_t() are refused until then
+  void drop_amplitudes() { t_prev_.release(); z_prev_.release(); t_prev_o_ = z_prev_o_ = -1; }
+  int last_nsocc() const { return last_kind_ >= 0 ? last_o_ : -1; }      // occupied orbitals of the last solve; -1: none since the ERIs or orbitals were set
   // Frags.rdm2__ (molbe/solver.py:528) of the last solve in the fragment-MO basis, out: n^4 (host).  kind QEMB_RDM2_CCSD: make_rdm2_urlx from the kept t1 / t2;
   // QEMB_RDM2_MP2: mp2.make_rdm2, t2 formed again from the resident orbitals (an MP2 solve keeps no amplitudes).  One kernel writes the tensor (rdm2_ops.hip).
   // A relaxed solve: QEMB_ERR_UNSUPPORTED; no solve of that kind, or ERIs / orbitals changed since: QEMB_ERR_ARG.
@@ -199,6 +214,7 @@ class Fragment {
   int last_kind_ = -1, last_o_ = 0; bool last_relaxed_ = false;
   std::vector<double> mp2_dm1_;
   int64_t rdm2_mem_limit_ = -1;
+  int64_t ccsd_t_mem_limit_ = -1;
   // after an FCI solve: the CI vector (device, ns * ns)
   DBuf fci_c_;
   double fci_residual_ = 0.0;

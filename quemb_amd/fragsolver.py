@@ -252,6 +252,35 @@ class DeviceFragment:
             raise
         return out
 
+    def ccsd_t(self):
+        """the perturbative triples correction E_(T) of the last `solve` (CCSD, relaxed or not) of this fragment (qemb_frag_ccsd_t), from the t1 / t2 it left on
+        the device, the orbital energies, and (ia|bc), (ia|jk), (ia|jb) formed again from the resident factor or block.  Closed shell, Fock = diag(mo_energy):
+            g[i,j,k,a,b,c] = sum_f (ia|fb) t2[k,j,c,f] - sum_m (ia|mj) t2[m,k,b,c];   W = the sum of g over the six simultaneous permutations of (i,a), (j,b), (k,c);
+            V = W + t1[i,a] (jb|kc) + t1[j,b] (ia|kc) + t1[k,c] (ia|jb);   E_(T) = 1/3 sum W r3(V) / (e_i + e_j + e_k - e_a - e_b - e_c)   (not guarded).
+        Returns dict(e_t, tile, n_tile_triples, bytes, ms) -- the tile of the virtual orbitals the call chose, the tile triples A >= B >= C it visited, the device
+        bytes of its working set, ms: dict(images, gemm, assemble, integrals).  The same bits on every call.  E_(T) is the triples energy of the EMBEDDING problem
+        of this fragment, a diagnostic of what CCSD leaves out: it is added to no fragment or BE energy, and a centre-projected BE-level (T) energy is not formed."""
+        e, tile, ntt, ms = C.c_double(), C.c_int(), C.c_int64(), (C.c_double * 4)()
+        check(self.lib.qemb_frag_ccsd_t(self.h, C.byref(e), C.byref(tile), C.byref(ntt), ms), "qemb_frag_ccsd_t", self.lib)
+        nbytes = self.ccsd_t_bytes(0, tile.value) if tile.value > 0 else 0
+        return dict(e_t=e.value, tile=int(tile.value), n_tile_triples=int(ntt.value), bytes=nbytes, ms=dict(zip(("images", "gemm", "assemble", "integrals"), (float(x) for x in ms))))
+
+    def ccsd_t_bytes(self, nsocc, tile):
+        """device bytes `ccsd_t` takes with nsocc occupied orbitals (0: as many as the last solve had) and that tile of the virtual orbitals
+        (qemb_frag_ccsd_t_bytes): the larger of the integral transformation and of the kept MO blocks with the images, the six product buffers and the partial sums"""
+        b = C.c_int64()
+        check(self.lib.qemb_frag_ccsd_t_bytes(self.h, int(nsocc), int(tile), C.byref(b)), "qemb_frag_ccsd_t_bytes", self.lib)
+        return int(b.value)
+
+    def drop_amplitudes(self):
+        """releases the t1 / t2 (and Lambda multipliers) kept from the last CCSD solve (qemb_frag_drop_amplitudes): `make_rdm2("CCSD")` and `ccsd_t` are refused
+        until the fragment is solved again"""
+        check(self.lib.qemb_frag_drop_amplitudes(self.h), "qemb_frag_drop_amplitudes", self.lib)
+
+    def set_ccsd_t_mem_limit(self, nbytes):
+        """device bytes `ccsd_t` of this fragment may take (qemb_frag_ccsd_t_mem_limit); negative: whatever is free"""
+        check(self.lib.qemb_frag_ccsd_t_mem_limit(self.h, int(nbytes)), "qemb_frag_ccsd_t_mem_limit", self.lib)
+
     def set_rdm2_mem_limit(self, nbytes):
         """device bytes `make_rdm2` of this fragment may take, tensor and workspace (qemb_frag_rdm2_mem_limit); negative: whatever is free"""
         check(self.lib.qemb_frag_rdm2_mem_limit(self.h, int(nbytes)), "qemb_frag_rdm2_mem_limit", self.lib)
@@ -314,6 +343,30 @@ class DeviceFragment:
 
 RDM2_KINDS = {"CCSD": 0, "MP2": 1, "FCI-hip": 2, "SCI-hip": 3}      # QEMB_RDM2_CCSD, _MP2, _FCI, _SCI (include/qemb_hip.h)
 SOLVERS = ("CCSD", "MP2", "FCI-hip", "SCI-hip")                      # the solver literals of be_func; everything else (the bare "FCI" and "SCI" included) is refused
+
+
+def ccsd_t(t1, t2, ovvv, ovoo, ovov, eo, ev, tile=8, lib=None):
+    """E_(T) of handed-in amplitudes and MO blocks (qemb_op_ccsd_t; the expression is in DeviceFragment.ccsd_t): t1 (o, v), t2 (o, o, v, v), ovvv (o, v, v, v) =
+    (ia|bc), ovoo (o, v, o, o) = (ia|jk), ovov (o, v, o, v) = (ia|jb), eo (o,), ev (v,); tile: the tile of the virtual orbitals, forced (cut to v)."""
+    from ._lib import DeviceBuffer
+    lib = lib or _lib.init()
+    t1 = np.ascontiguousarray(t1, dtype=np.float64)
+    o, v = t1.shape
+    shapes = dict(t2=(o, o, v, v), ovvv=(o, v, v, v), ovoo=(o, v, o, o), ovov=(o, v, o, v), eo=(o,), ev=(v,))
+    arrs = dict(t2=t2, ovvv=ovvv, ovoo=ovoo, ovov=ovov, eo=eo, ev=ev)
+    for k, a in arrs.items():
+        if np.shape(a) != shapes[k]:
+            raise ValueError(f"ccsd_t: {k} must have the shape {shapes[k]}, not {np.shape(a)}")
+    if int(tile) < 1:
+        raise ValueError("ccsd_t: tile must be at least 1")
+    bufs = [DeviceBuffer.from_numpy(a, lib=lib) for a in (t1, t2, ovvv, ovoo, ovov, eo, ev)]
+    try:
+        e = C.c_double()
+        check(lib.qemb_op_ccsd_t(o, v, *(b.ptr for b in bufs), int(tile), C.byref(e)), "qemb_op_ccsd_t", lib)
+        return e.value
+    finally:
+        for b in bufs:
+            b.free()
 
 
 def rdm2_from_amplitudes(t1, t2, dm1=None, kind="CCSD", lib=None):

@@ -634,6 +634,16 @@ class BE:
             raise RuntimeError("BE.sci_pt2: run oneshot or optimize with solver='SCI-hip' first")
         return [f.sci_pt2(eps_pt, max_ext) if f in mine else None for f in self.Fobjs]
 
+    def ccsd_t(self):
+        """after `oneshot` / `optimize` with solver="CCSD": the perturbative triples correction E_(T) of every fragment's last solve (Frags.ccsd_t), one
+        dict(e_t, tile, n_tile_triples, bytes, ms) per fragment in fragment order (None for a fragment another rank owns).  Raises ValueError before a sweep and
+        after a sweep with another solver.  E_(T) is the triples energy of each fragment's embedding problem -- the standard measure of what CCSD leaves out
+        there -- and a per-fragment diagnostic: it is added to no BE energy, and a centre-projected BE-level (T) energy is not formed."""
+        mine = [f for i, f in enumerate(self.Fobjs) if self.world <= 1 or self.owner[i] == self.rank]
+        if not mine or any(f._solver != "CCSD" for f in mine):
+            raise ValueError("BE.ccsd_t: run oneshot or optimize with solver='CCSD' first")
+        return [f.ccsd_t() if f in mine else None for f in self.Fobjs]
+
     def optimize(self, solver="CCSD", method="QN", only_chem=False, use_cumulant=True, conv_tol=1.0e-6, relax_density=False,
                  jac_solver="HF", nproc=1, ompnum=1, max_iter=500, trust_region=False, step_size=1e-6, solver_args=None,
                  warm_start=True):

@@ -65,6 +65,7 @@ class Frags:
         self.fci_slab_rows = 0   # slab height of solver="FCI-hip" on this fragment (DeviceFragment.set_fci_slab; BE(fci_slab_rows=...)); the other solvers do not read it
         self._solver = None      # the solver of the last solve ("CCSD" / "MP2" / "FCI-hip"): what make_rdm2 assembles
         self.e_pt2 = None        # the second-order correction of the last `sci_pt2` call (a diagnostic, added to nothing)
+        self.e_t = None          # the triples correction of the last `ccsd_t` call (a diagnostic, added to nothing)
 
     # ------------------------------------------------------------------ Schmidt (pfrag.py:146-180)
     def sd(self, lao, lmo, nocc, thr_bath, norb=None, method="eigh"):
@@ -193,6 +194,16 @@ class Frags:
             raise RuntimeError("sci_pt2: solve the fragment with solver='SCI-hip' first")
         out = self.dev.sci_pt2(eps_pt, max_ext)
         self.e_pt2 = out["e_pt2"]
+        return out
+
+    def ccsd_t(self):
+        """the perturbative triples correction E_(T) of this fragment's last solve with solver="CCSD" (DeviceFragment.ccsd_t): dict(e_t, tile, n_tile_triples,
+        bytes, ms); the correction is also kept as `self.e_t`.  It is the triples energy of the embedding problem of this fragment, a diagnostic of what CCSD
+        leaves out, and is added to no fragment or BE energy; a centre-projected BE-level (T) energy is not formed."""
+        if self._solver != "CCSD":
+            raise ValueError("ccsd_t: solve the fragment with solver='CCSD' first")
+        out = self.dev.ccsd_t()
+        self.e_t = out["e_t"]
         return out
 
     def make_rdm2(self, with_dm1=True):

@@ -111,10 +111,11 @@ def sci_opts_from_args(solver, solver_args, lib=None):
 
 
 def _solve_fragment(name, solver, keys, h, eri_s4, nsocc, dm0, *, n_frag, rdm_return, rdm2_return, use_cumulant, opts, lib, df_factor=None, fci_opts=None, sci_opts=None,
-                    slab_rows=0, pt2_eps=None):
+                    slab_rows=0, pt2_eps=None, triples=False):
     """What solve_ccsd / solve_mp2 / solve_fci share: a fragment with its ERIs (or living on its 3-index factor) is created, solved without energies and freed.
     Returns (out[keys[0]], out[keys[1]]), then rdm1_mo and mo_coeff with rdm_return; rdm2_return: the 2-RDM of the solve takes the place of mo_coeff
-    (solver.py:940-942), or is appended without rdm_return.  pt2_eps (read for "SCI-hip" alone): the second-order correction at that threshold is the last element."""
+    (solver.py:940-942), or is appended without rdm_return.  pt2_eps (read for "SCI-hip" alone): the second-order correction at that threshold is the last element;
+    triples (read for "CCSD" alone): E_(T) is the last element."""
     fr = DeviceFragment(h.shape[0], n_frag, lib=lib)
     try:
         if eri_s4 is not None:
@@ -130,6 +131,8 @@ def _solve_fragment(name, solver, keys, h, eri_s4, nsocc, dm0, *, n_frag, rdm_re
         out = fr.solve_as(solver, nsocc, h, dm0, opts=opts, eeval=False, want_amplitudes=True, fci_opts=fci_opts, sci_opts=sci_opts)
         rdm2 = fr.make_rdm2(solver, with_dm1=not use_cumulant) if rdm2_return else None
         tail = () if pt2_eps is None else (fr.sci_pt2(pt2_eps)["e_pt2"],)
+        if triples:
+            tail = (fr.ccsd_t()["e_t"],)
     finally:
         fr.free()
     head = (out[keys[0]], out[keys[1]])
@@ -139,18 +142,20 @@ def _solve_fragment(name, solver, keys, h, eri_s4, nsocc, dm0, *, n_frag, rdm_re
 
 
 def solve_ccsd(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, relax=False, use_cumulant=True,
-               opts=None, lib=None):
+               opts=None, lib=None, triples=False):
     """Device counterpart of solve_ccsd (molbe/solver.py:829-946).  The reference takes a PySCF mean-field object;
     here the fragment RHF is part of the device call, so the inputs are what `get_scfObj` would have been given:
     h = fock + heff, the 4-fold packed fragment ERIs, nsocc and dm0.
     Returns (t1, t2) or (t1, t2, rdm1_mo, mo_coeff) with rdm_return.  rdm2_return: the fragment 2-RDM in the MO basis,
     make_rdm2_urlx(t1, t2, with_dm1=not use_cumulant), assembled on the device, takes the place of mo_coeff -- (t1, t2, rdm1_mo, rdm2) as
-    solver.py:940-942 -- or is appended to (t1, t2) without rdm_return.  Unrelaxed only: with relax it raises NotImplementedError.  The energies of a sweep never need it: `Frags.solve` contracts it in place."""
+    solver.py:940-942 -- or is appended to (t1, t2) without rdm_return.  Unrelaxed only: with relax it raises NotImplementedError.  The energies of a sweep never need it: `Frags.solve` contracts it in place.
+    triples: the perturbative triples correction E_(T) of the solve (DeviceFragment.ccsd_t) is appended as the last element -- the triples energy of this
+    embedding problem, a diagnostic contained in none of the other results."""
     if relax:
         opts = SolverOpts.from_buffer_copy(opts) if opts is not None else default_opts(lib)
         opts.relax_density = 1
     return _solve_fragment("solve_ccsd", "CCSD", ("t1", "t2"), h, eri_s4, nsocc, dm0, n_frag=n_frag, rdm_return=rdm_return, rdm2_return=rdm2_return,
-                           use_cumulant=use_cumulant, opts=opts, lib=lib)
+                           use_cumulant=use_cumulant, opts=opts, lib=lib, triples=triples)
 
 
 def solve_mp2(h, eri_s4, nsocc, dm0=None, *, n_frag=0, rdm_return=False, rdm2_return=False, use_cumulant=True, df_factor=None, opts=None, lib=None):

@@ -259,7 +259,6 @@ int qemb_op_ccsd_y_traces_add(int64_t o, int64_t v, const double* ZC, const doub
 int qemb_op_pack_w_pm_sum(int64_t o, const double* Wt, const double* X, const double* At, double* Ap, int64_t lda_p, double* Am, int64_t lda_m) {
   return dev_pack_w_pm_sum(o, Wt, X, At, Ap, lda_p, Am, lda_m);
 }
-int qemb_op_ccsd_t1_small(int64_t o, int64_t v, const double* t1, const double* Lvv, const double* Loo, const double* Fov, double* t1n) { return dev_ccsd_t1_small(o, v, t1, Lvv, Loo, Fov, t1n); }
 int qemb_op_ccsd_t1_assemble(int64_t o, int64_t v, const double* t1, const double* Lvv, const double* Loo, const double* Fov, const double* S, const double* Lph1,
                              const double* PA, int SA, int64_t strideA, const double* PB, int SB, int64_t strideB, double* t1n) {
   return dev_ccsd_t1_assemble(o, v, t1, Lvv, Loo, Fov, S, Lph1, PA, SA, strideA, PB, SB, strideB, t1n);
@@ -270,9 +269,6 @@ int qemb_op_gemv_rows_two(int64_t rows1, int64_t cols1, const double* T1, int64_
 }
 int qemb_op_ccsd_y_traces_slabs(int64_t o, int64_t v, const double* ZC, const double* ZB, double* Y, const double* add, int S, int64_t stride, double scale) {
   return dev_ccsd_y_traces(o, v, ZC, ZB, Y, add, S, stride, scale);
-}
-int qemb_op_gemv_rows2(int64_t rows, int64_t cols, const double* T1, int64_t ld1, const double* x1, const double* T2, int64_t ld2, const double* x2, double* y, double alpha, double beta) {
-  return dev_gemv_rows2(rows, cols, T1, ld1, x1, T2, ld2, x2, y, alpha, beta);
 }
 int qemb_op_ccsd_finish_t2_rings(int64_t o, int64_t v, double* t2n, const double* U, const double* OV, const double* RS, const double* M, const double* eo, const double* ev, double* t1n) {
   return dev_ccsd_finish_t2_rings(o, v, t2n, U, OV, RS, M, eo, ev, t1n);

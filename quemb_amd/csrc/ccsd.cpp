@@ -480,16 +480,15 @@ CcsdGemmPlans ccsd_gemm_plans(int64_t o, int64_t v) {
 // The ring products (update_amps has the reasons):
 //   o v >= 2048: the 128 x 256 tile;
 //   1024 <= o v < 2048, one mid-size fragment on the chip: 96 x 96 tiles with K in two slices -- 15 x 15 x 2 workgroups at o v = 1440, 119 us against the 151 us
-//     of 23 x 23 tiles of 64 x 64; tools/mid_gemm_bench.py.  QEMB_RING96=0: the 64 x 64 tiles, for A/B runs;
+//     of 23 x 23 tiles of 64 x 64; tools/mid_gemm_bench.py;
 //   below: 64 x 64 tiles once there are 200 of them, else the dispatcher's choice -- 32 x 32 at the o v = 441 of an octane fragment.
 // The K slices of a product are summed from the split-K workspace, S (ov)^2 doubles per product -- S = 2 for the mid-size tiles, and the six slices that dev_gemm
 // cuts by itself for the 16 x 8 tiles of o v = 2048 (gemm_auto_ksplit; below o v = 1024 K is too short for a split) -- and the last two products form one
 // parallel region: 32 (ov)^2 bytes for 1024 <= o v < 2048, 403 MB at o v = 2048, the last shape of the replay regime.
 CcsdRingPlan ccsd_ring_plan(int64_t o, int64_t v) {
-  static const bool ring96 = env_flag("QEMB_RING96", true);
   const int64_t nov = o * v;
   CcsdRingPlan r;
-  const bool mid_ring = ring96 && nov >= 1024 && nov < 2048;
+  const bool mid_ring = nov >= 1024 && nov < 2048;
   r.cfg = (nov >= 2048) ? GEMM_128x256 : mid_ring ? GEMM_96x96 : (nov >= 256 && gemm_tile_count(GEMM_64x64, nov, nov) >= 200) ? GEMM_64x64 : -1;
   r.ks = mid_ring ? 2 : 0;
   const int S = gemm_slab_count(nov, r.ks > 1 ? r.ks : r.cfg >= 0 ? gemm_auto_ksplit(gemm_tile_count(r.cfg, nov, nov), nov) : 0);
@@ -850,13 +849,12 @@ int CcsdSolver::post_wait(int step) {
   post_pending_ = false;
   return 0;
 }
-// (the fused launches take up to eight stored vectors and o^2 <= 16384 tiles; QEMB_POST_FUSED=0: the pass-by-pass form, for A/B runs)
+// (the fused launches take up to eight stored vectors and o^2 <= 16384 tiles; beyond that the pass-by-pass form)
 bool CcsdSolver::fused_post() const {
-  static const bool on = env_flag("QEMB_POST_FUSED", true);
-  return on && !(last_use_diis_ && diis_[0].space() > 8) && (int64_t)o_ * o_ <= 16384 && v_ <= 4096;
+  return !(last_use_diis_ && diis_[0].space() > 8) && (int64_t)o_ * o_ <= 16384 && v_ <= 4096;
 }
-// step 1: diff = t_new - t (also the DIIS error vector: trial minus previously returned vector) and its Gram row -- one launch whose last
-// workgroup leaves the row (|t_new - t|^2 is its diagonal element) in pinned host memory
+// step 1: diff = t_new - t (also the DIIS error vector: trial minus previously returned vector) and its Gram row -- one launch and its small
+// finishing kernel, which leaves the row (|t_new - t|^2 is its diagonal element) in pinned host memory
 int CcsdSolver::post_issue() {
   const int64_t na = n_amp();
   double* out = last_out_;

@@ -179,14 +179,13 @@ inline const char* gemm_desc_error(const GemmDesc& d) {
 // 16-byte loads of an operand tile: an M/N-contiguous operand needs pairs that are entirely inside or outside the matrix and 16-byte aligned (even extent, ld,
 // batch stride; aligned base); a K-contiguous one takes any K and ld -- its pairs are read at 8-byte alignment and the odd last element of a row alone (round 5:
 // fragments with an odd n_occ n_virt ran the 8-byte kernels, and could not share a grouped launch with their even neighbours of a lock-step sweep).
-// relaxed = false: the round-4 rule (K-contiguous operands as strict as the others).
-inline bool gemm_operand_vec2_ok(const double* p, int64_t ld, int64_t stride, int64_t contig_extent, bool kcontig, bool relaxed = true) {
-  if (kcontig && relaxed) return (reinterpret_cast<uintptr_t>(p) & 7) == 0;
+inline bool gemm_operand_vec2_ok(const double* p, int64_t ld, int64_t stride, int64_t contig_extent, bool kcontig) {
+  if (kcontig) return (reinterpret_cast<uintptr_t>(p) & 7) == 0;
   return ((reinterpret_cast<uintptr_t>(p) & 15) == 0) && (ld % 2 == 0) && (stride % 2 == 0) && (contig_extent % 2 == 0);
 }
-inline bool gemm_desc_vec2(const GemmDesc& d, bool relaxed = true) {
-  return gemm_operand_vec2_ok(d.A, d.lda, d.strideA, d.a_kcontig ? d.K : d.M, d.a_kcontig != 0, relaxed) &&
-         gemm_operand_vec2_ok(d.B, d.ldb, d.strideB, d.b_kcontig ? d.K : d.N, d.b_kcontig != 0, relaxed);
+inline bool gemm_desc_vec2(const GemmDesc& d) {
+  return gemm_operand_vec2_ok(d.A, d.lda, d.strideA, d.a_kcontig ? d.K : d.M, d.a_kcontig != 0) &&
+         gemm_operand_vec2_ok(d.B, d.ldb, d.strideB, d.b_kcontig ? d.K : d.N, d.b_kcontig != 0);
 }
 // the epilogue's `wide` predicate (16-byte pair stores of C, gemm_f64.hip) restated on the host: true when EVERY one of the nz matrices C + z * strideC
 // takes the wide path
@@ -299,9 +298,8 @@ int dev_pack_pm_ovvv(int64_t o, int64_t v, const double* ovvv, double* Op, int64
 // add (laid out like out): out = scatter + add.  Sp / Sm > 1: Xp / Xm are split-K slabs (stride strideP / strideM apart) that are added up on the way, in slab order
 int dev_scatter_pm_rows(int64_t o, int64_t ncols, const double* Xp, const double* Xm, double* out, const double* add = nullptr, int Sp = 1, int64_t strideP = 0,
                         int Sm = 1, int64_t strideM = 0);
-// CCSD doubles update, last step in one pass:  t2n[i,j,a,b] = (t2n[i,j,a,b] + OV[i,j,a,b] + U[i,j,a,b] + U[j,i,b,a]) / (eo[i]+eo[j]-ev[a]-ev[b])
-int dev_ccsd_finish_t2(int64_t o, int64_t v, double* t2n, const double* U, const double* OV, const double* eo, const double* ev);
-// The same with the two ring products taken in place (no transposing accumulation passes over U first) and the t1 denominators on the way:
+// CCSD doubles update, last step in one pass, with the two ring products taken in place (no transposing accumulation passes over U first) and the t1
+// denominators on the way:
 //   F[i,j,a,b] = U[i,j,a,b] + RS[i,a,j,b] - 1/2 M[i,a,j,b] - M[i,b,j,a]      (RS, M: [o][v][o][v])
 //   t2n[i,j,a,b] = t2n[j,i,b,a] = (t2n[i,j,a,b] + OV[i,j,a,b] + F[i,j,a,b] + F[j,i,b,a]) / (eo[i] + eo[j] - ev[a] - ev[b])   -- each (i >= j) pair of tiles once
 //   t1n[i,a] /= eo[i] - ev[a]   (t1n may be null)
@@ -321,18 +319,15 @@ int dev_pack_w_pm(int64_t o, const double* W, double* Ap, int64_t lda_p, double*
 // the same for W[k,l,i,j] = Wt[i,j,k,l] + X[i,j,k,l] + At[j,i,k,l] + At[i,j,l,k] formed on the fly (the Woooo intermediate of the CCSD update: never stored; every
 // operand with the row pair (i,j) of the packed images as its slow indices, so that a row of the images reads contiguous blocks)
 int dev_pack_w_pm_sum(int64_t o, const double* Wt, const double* X, const double* At, double* Ap, int64_t lda_p, double* Am, int64_t lda_m);
-// t1n[i,a] = sum_c t1[i,c] Lvv[a,c] - sum_k Loo[k,i] t1[k,a] + sum_k Q[i,k] t1[k,a],  Q[i,k] = sum_c t1[i,c] Fov[k,c]   (the four small products of the T1 equation)
-int dev_ccsd_t1_small(int64_t o, int64_t v, const double* t1, const double* Lvv, const double* Loo, const double* Fov, double* t1n);
 // The whole right-hand side of the T1 equation in one launch, one workgroup per element (i,a):
-//   t1n[ia] = [the small products of dev_ccsd_t1_small] + S[(ia),:] . Fov + Lph1[(ia),:] . t1 + sum_s PA[s][(ia)] - sum_s PB[s][(ia)]
+//   small[i,a] = sum_c t1[i,c] Lvv[a,c] - sum_k Loo[k,i] t1[k,a] + sum_k Q[i,k] t1[k,a],  Q[i,k] = sum_c t1[i,c] Fov[k,c]   (the four small products)
+//   t1n[ia] = small[ia] + S[(ia),:] . Fov + Lph1[(ia),:] . t1 + sum_s PA[s][(ia)] - sum_s PB[s][(ia)]
 // PA / PB: the two long-K products (ovvv . Theta, Lovoo . T) as the split-K slabs their GEMMs left (SA / SB of them, strideA / strideB apart)
 int dev_ccsd_t1_assemble(int64_t o, int64_t v, const double* t1, const double* Lvv, const double* Loo, const double* Fov, const double* S, const double* Lph1,
                          const double* PA, int SA, int64_t strideA, const double* PB, int SB, int64_t strideB, double* t1n);
 // two independent matrix-vector passes in one launch: y1 = a1 T1 x1 + b1 y1 (rows1 x cols1) and y2 = a2 T2 x2 + b2 y2 (rows2 x cols2)
 int dev_gemv_rows_two(int64_t rows1, int64_t cols1, const double* T1, int64_t ld1, const double* x1, double* y1, double a1, double b1,
                       int64_t rows2, int64_t cols2, const double* T2, int64_t ld2, const double* x2, double* y2, double a2, double b2);
-// y[r] = alpha (T1[r,:] . x1 + T2[r,:] . x2) + beta y[r]: two matrix-vector products in one pass
-int dev_gemv_rows2(int64_t rows, int64_t cols, const double* T1, int64_t ld1, const double* x1, const double* T2, int64_t ld2, const double* x2, double* y, double alpha, double beta);
 // F[k,i] = sum_l (2 X[i,l,k,l] - X[l,i,k,l]) for X[i,j,k,l] (o^4): the occupied-occupied intermediate sum_{lcd} (2 ovov[kcld] - ovov[kdlc]) tau[ilcd]
 // as a partial trace of X[i,j,k,l] = sum_cd ovov[kcld] tau[ijcd], which the Woooo build forms anyway
 int dev_foo_from_x(int64_t o, const double* X, double* F);
@@ -612,9 +607,9 @@ int dev_dot(int64_t n, const double* x, const double* y, double* out_dev);
 int dev_absmax(int64_t n, const double* x, double* out_dev);
 // out_dev[j] = <x, ys[j]> for j < m <= 8 in one pass over x (each result bit-identical to dev_dot)
 int dev_dot_many(int64_t n, const double* x, int m, const double* const* ys, double* out_dev);
-// DIIS push for an error vector that is a difference, ONE pass and one launch:  e[i] = trial[i] - prev[i],  xcopy[i] = trial[i] (xcopy may be
+// DIIS push for an error vector that is a difference, ONE pass over the vectors (and a one-workgroup kernel that finishes the sums):  e[i] = trial[i] - prev[i],  xcopy[i] = trial[i] (xcopy may be
 // null, and may alias prev),  row[j] = <e, ys[j]> for j < m <= 8 with ys[self] == e (the new vector's own slot).  The row lands in row_dev AND in
-// the pinned host block row_host (written by the last workgroup of the launch: no copy node, valid after a wait of this context's stream).
+// the pinned host block row_host (written by the finishing kernel: no copy node, valid after a wait of this context's stream).
 // Same partition and summation order as dev_dot / dev_dot_many.
 // flag_host (may be null): a pinned host word that receives `seq` AFTER the results (system-scope release): dev_wait_flag spins on it -- a
 // microsecond or two after the kernel's last store instead of the ~13 us of a stream wait.
@@ -627,9 +622,9 @@ int dev_batch_begin();
 int dev_batch_flush();
 // wait until the pinned host word holds `seq` (written by a kernel of THIS context's stream; a stream that has drained without writing it is an error)
 int dev_wait_flag(const void* flag_host, unsigned long long seq);
-// End of a CCSD iteration in one launch:  amp = sum_k coef[k] xs[k] over the packed amplitudes [t1 (o v) | t2 (o,o,v,v)] (nterms <= 8; amp may
+// End of a CCSD iteration in one pass (and the finishing kernel of the energy):  amp = sum_k coef[k] xs[k] over the packed amplitudes [t1 (o v) | t2 (o,o,v,v)] (nterms <= 8; amp may
 // be xs[0] when nterms == 1 and coef[0] == 1: nothing is rewritten),  tau = t2 + t1 (x) t1 of the NEW amplitudes,  E = <L, tau> to e_dev and to
-// the pinned host word e_host (last workgroup).  o * o <= 16384.
+// the pinned host word e_host.  o * o <= 16384.
 int dev_ccsd_extrapolate_energy(int64_t o, int64_t v, int nterms, const double* coef, const double* const* xs, double* amp, const double* L,
                                 double* tau, double* e_dev, double* e_host, void* flag_host = nullptr, unsigned long long seq = 0);
 

@@ -107,8 +107,7 @@ int dev_init(int device) {
   }
   HIP_TRY(hipSetDevice(device));
   HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-  HIP_TRY(hipMalloc((void**)&c.partials, (8 * NPART + 8) * sizeof(double)));
-  HIP_TRY(hipMemset(c.partials + 8 * NPART, 0, 8 * sizeof(double)));      // the "workgroups done" counter of the single-launch reductions
+  HIP_TRY(hipMalloc((void**)&c.partials, 8 * NPART * sizeof(double)));
   g_device = device;
   return QEMB_OK;
 }
@@ -140,8 +139,7 @@ int dev_ctx_count(int n) {
   while ((int)g_extra_ctx.size() + 1 < n) {
     DevCtx* c = new DevCtx();
     hipError_t e = create_ctx_stream(&c->stream, (int)g_extra_ctx.size());
-    if (e == hipSuccess) e = hipMalloc((void**)&c->partials, (8 * NPART + 8) * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(c->partials + 8 * NPART, 0, 8 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->partials, 8 * NPART * sizeof(double));
     if (e != hipSuccess) { delete c; set_error(std::string("dev_ctx_count: ") + hipGetErrorString(e)); return QEMB_ERR_DEVICE; }
     g_extra_ctx.push_back(c);
   }
@@ -339,11 +337,10 @@ int dev_free(void* p) {
 // synchronously and under locks that the host threads of a batched sweep queue on (six fragments x ~8 small copies in the RHF phase of an octane sweep: the phase took
 // 3 x the time of one fragment alone).  Upload: the bytes are copied into the next slot of a ring and leave from there asynchronously -- no wait at all (the caller's
 // buffer is free on return, the stream orders the copy before later launches; a slot is reused only after the event of its last upload).  Download: device -> slot,
-// one stream wait, slot -> destination.  QEMB_STAGED_COPIES=0: the plain calls, for A/B runs.
+// one stream wait, slot -> destination.  While capturing, and above STAGE_SLOT, the plain calls.
 static constexpr size_t STAGE_SLOT = 256 * 1024;      // (n x n doubles up to n = 181)
 static bool stage_ready(DevCtx& c) {
-  static const bool on = env_flag("QEMB_STAGED_COPIES", true);
-  if (!on || c.capturing) return false;
+  if (c.capturing) return false;
   if (c.stage) return true;
   void* q = nullptr;
   if (hipHostMalloc(&q, 8 * STAGE_SLOT, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return false; }
@@ -410,7 +407,7 @@ int dev_pinned_alloc(void** p, size_t bytes) {
     if (it != g_pinned_free.end() && !it->second.empty()) { *p = it->second.back(); it->second.pop_back(); g_pinned_live[*p] = cls; return QEMB_OK; }
   }
   HIP_TRY(hipHostMalloc(p, cls, hipHostMallocDefault));
-  {  // kernels write their scalar results straight into these blocks (single-launch reductions): the host address must be the device address
+  {  // kernels write their scalar results straight into these blocks (finish_partials_kernel): the host address must be the device address
     void* dp = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&dp, *p, 0));
     if (dp != *p) { (void)hipHostFree(*p); *p = nullptr; set_error("pinned host memory is not mapped at its host address on this platform"); return QEMB_ERR_DEVICE; }
@@ -545,7 +542,6 @@ int dev_graph_destroy(dev_graph_t g) { if (g) (void)hipGraphExecDestroy((hipGrap
 // with its block index inside that member.  Kernels are registered by the address of their wrapper, which is what a captured graph node
 // carries; the registrars run when the library is loaded, so the map below is complete before anything reads it (grouped_launch.h).
 std::map<const void*, GroupInfo>& groupable() { static std::map<const void*, GroupInfo> m; return m; }
-bool group_xcd_mode() { static const bool on = env_flag("QEMB_GROUP_XCD", false); return on; }
 
 // ---- tapes: captured launch sequences executed together -------------------------------------------------------------------------------
 // A tape keeps the captured hipGraph alive (it owns the argument storage of its nodes) and lists the nodes in execution order.
@@ -700,7 +696,7 @@ static std::vector<TapePlan*> g_plans;        // small: one per distinct set of 
 // kernel and block shape become grouped launches of up to GROUP_MAX members (arguments by value), the rest is issued singly.  (A member table in device
 // memory with up to 64 members per launch was measured in round 5: six fragments x two chains in one launch were 0.5 ms per octane BE2 sweep SLOWER than two
 // launches of six -- the table is chased through memory by every workgroup where the by-value arguments are scalar loads.)
-static void plan_emit(TapePlan* plan, const std::vector<const TapeNode*>& here, bool grouping) {
+static void plan_emit(TapePlan* plan, const std::vector<const TapeNode*>& here) {
   std::vector<unsigned char>& host = plan->args;
   auto reserve = [&](std::vector<unsigned char>& v, size_t bytes) { const size_t off = (v.size() + 255) / 256 * 256; v.resize(off + bytes); return off; };
   plan->ops += (long long)here.size();
@@ -711,7 +707,7 @@ static void plan_emit(TapePlan* plan, const std::vector<const TapeNode*>& here, 
     std::vector<const TapeNode*> grp{na};
     const GroupInfo* gi = nullptr;
     const int cap = GROUP_MAX;
-    if (grouping && na->type == hipGraphNodeTypeKernel) {
+    if (na->type == hipGraphNodeTypeKernel) {
       auto it = groupable().find(na->k.func);
       if (it != groupable().end()) {
         gi = &it->second;
@@ -760,7 +756,6 @@ static std::vector<TapeSegment> tape_segments(const Tape* t) {
 }
 
 static int build_plan(const dev_tape_t* tapes, int n, TapePlan** out) {
-  static const bool grouping = env_flag("QEMB_TAPE_GROUP", true);
   const bool regions_on = regions_enabled();
   TapePlan* plan = new TapePlan();
   for (int f = 0; f < n; ++f) plan->key.push_back(tapes[f]);
@@ -782,7 +777,7 @@ static int build_plan(const dev_tape_t* tapes, int n, TapePlan** out) {
         for (size_t i = 0; i < longest; ++i) {
           std::vector<const TapeNode*> here;
           for (int f = 0; f < n; ++f) { const Tape* t = (const Tape*)tapes[f]; const size_t j = segs[f][k].begin + i; if (j < segs[f][k].end) here.push_back(&t->nodes[j]); }
-          plan_emit(plan, here, grouping);
+          plan_emit(plan, here);
         }
       } else {                          // parallel region: level by level over every chain of every tape
         size_t depth = 0;
@@ -790,7 +785,7 @@ static int build_plan(const dev_tape_t* tapes, int n, TapePlan** out) {
         for (size_t lev = 0; lev < depth; ++lev) {
           std::vector<const TapeNode*> here;
           for (int f = 0; f < n; ++f) for (const auto& c : segs[f][k].chains) if (lev < c.size()) here.push_back(c[lev]);
-          plan_emit(plan, here, grouping);
+          plan_emit(plan, here);
         }
       }
     }
@@ -800,7 +795,7 @@ static int build_plan(const dev_tape_t* tapes, int n, TapePlan** out) {
     for (size_t i = 0; i < longest; ++i) {
       std::vector<const TapeNode*> here;
       for (int f = 0; f < n; ++f) { const Tape* t = (const Tape*)tapes[f]; if (i < t->nodes.size()) here.push_back(&t->nodes[i]); }
-      plan_emit(plan, here, grouping);
+      plan_emit(plan, here);
     }
   }
   *out = plan;
@@ -1930,45 +1925,7 @@ int dev_scatter_pm_rows(int64_t o, int64_t ncols, const double* Xp, const double
   if (npo > 65535) { set_error("dev_scatter_pm_rows: too many pairs"); return QEMB_ERR_ARG; }
   return launch("dev_scatter_pm_rows", scatter_pm_rows_kernel, dim3((unsigned)std::min<long long>((ncols + 255) / 256, 64), (unsigned)npo), dim3(256), 0, g_stream, o, ncols, Xp, Xm, out, add, std::max(Sp, 1), strideP, std::max(Sm, 1), strideM);
 }
-// grid (32 x 32 tiles of (a,b), o*o): U[j,i,b,a] is read with a fastest (coalesced) and transposed through LDS
-__device__ __forceinline__ void ccsd_finish_t2_kernel_body(const uint3 BID, const uint3 GDIM, long long o, long long v, double* __restrict__ t2n, const double* __restrict__ U,
-                                                            const double* __restrict__ OV, const double* __restrict__ eo, const double* __restrict__ ev) {
-  __shared__ double tile[32][33];
-  const long long ij = BID.y, i = ij / o, j = ij - i * o;
-  const long long nt = (v + 31) / 32;
-  const long long ta = BID.x / nt, tb = BID.x - ta * nt;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const double* Uji = U + (j * o + i) * v * v;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {      // tile[bb][aa] = U[j,i,b,a]
-    const int bb = ty + 8 * k;
-    const long long b = tb * 32 + bb, a = ta * 32 + tx;
-    tile[bb][tx] = (a < v && b < v) ? Uji[b * v + a] : 0.0;
-  }
-  __syncthreads();
-  const double eij = eo[i] + eo[j];
-  const long long base = ij * v * v;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int aa = ty + 8 * k;
-    const long long a = ta * 32 + aa, b = tb * 32 + tx;
-    if (a < v && b < v) {
-      const long long idx = base + a * v + b;
-      t2n[idx] = (t2n[idx] + OV[idx] + U[idx] + tile[tx][aa]) / (eij - ev[a] - ev[b]);
-    }
-  }
-}
-__global__ void __launch_bounds__(256) ccsd_finish_t2_kernel(long long o, long long v, double* __restrict__ t2n, const double* __restrict__ U,
-                                                            const double* __restrict__ OV, const double* __restrict__ eo, const double* __restrict__ ev) { ccsd_finish_t2_kernel_body(block_id(), grid_dim(), o, v, t2n, U, OV, eo, ev); }
-static const Groupable<ccsd_finish_t2_kernel_body, 256> reg_ccsd_finish_t2(ccsd_finish_t2_kernel);
-int dev_ccsd_finish_t2(int64_t o, int64_t v, double* t2n, const double* U, const double* OV, const double* eo, const double* ev) {
-  REQUIRE_INIT();
-  if (o <= 0 || v <= 0) return QEMB_OK;
-  if (o * o > 65535) { set_error("dev_ccsd_finish_t2: too many occupied pairs"); return QEMB_ERR_ARG; }
-  const long long nt = (v + 31) / 32;
-  return launch("dev_ccsd_finish_t2", ccsd_finish_t2_kernel, dim3((unsigned)(nt * nt), (unsigned)(o * o)), dim3(256), 0, g_stream, o, v, t2n, U, OV, eo, ev);
-}
-// finish_t2 with the two ring products taken where the GEMMs left them ([o][v][o][v]) and every (i >= j) PAIR of tiles handled once: the tile (ta,tb) of
+// The last step of the doubles update, with the two ring products taken where the GEMMs left them ([o][v][o][v]) and every (i >= j) PAIR of tiles handled once: the tile (ta,tb) of
 // t2n[i,j] and the tile (tb,ta) of t2n[j,i] are transposes of each other, so one workgroup reads the ten operand tiles, forms the 32 x 32 result once and
 // stores it both ways (the second through LDS).  grid (nt * nt tiles, npair(o)); a diagonal pair i == j does its tiles twice over (ta,tb) and (tb,ta): same values.
 __device__ __forceinline__ void ccsd_finish_t2_rings_kernel_body(const uint3 BID, const uint3 GDIM, long long o, long long v, double* __restrict__ t2n, const double* __restrict__ U,
@@ -2274,34 +2231,14 @@ int dev_dot_many(int64_t n, const double* x, int m, const double* const* ys, dou
   QTRY(launch("dev_dot_many", dot_many_stage1, dim3(np), dim3(256), 0, g_stream, n, x, k, g_partials, np));
   return launch("dev_dot_many", dot_many_stage2, dim3(m), dim3(256), 0, g_stream, np, g_partials, out_dev);
 }
-// ---- single-launch reductions: every workgroup leaves its partial sums, the LAST one to finish (device-scope counter) adds them up in the
-// fixed order of the two-stage reductions above and writes the result to device memory and to a pinned host word -- no second kernel, no copy
-// node.  The counter lives behind the context's partials and is left at zero.
-// finish: 2 = thread 0 alone fences (it is the only writer of the partials; its acquire fence empties the caches the whole workgroup reads through),
-// 0 = do not finish here (a second small kernel does, QEMB_POST_FINISH=0).  (Every THREAD fencing, the textbook form, costs ~90 us per launch
-// here -- each fence is an L2 write-back -- and made the fused launches slower than the five they replace.)
-__device__ __forceinline__ bool last_workgroup(unsigned* counter, unsigned total, int finish) {
-  __shared__ unsigned ticket;
-  if (finish == 0) return false;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    __threadfence();                                 // this workgroup's partials are visible device wide before its ticket is
-    ticket = atomicAdd(counter, 1u);
-    if (ticket == total - 1) __threadfence();        // ... and the last one sees everybody's
-  }
-  __syncthreads();
-  return ticket == total - 1;
-}
+// ---- fused reductions: every workgroup of the first kernel leaves its partial sums; finish_partials_kernel adds them up in the fixed order of the
+// two-stage reductions above and writes the result to device memory and to a pinned host word -- no copy node.
 __device__ __forceinline__ void publish_flag(unsigned long long* flag_host, unsigned long long seq) {   // one thread, after its result stores
   if (!flag_host) return;
   __threadfence_system();
   __hip_atomic_store(flag_host, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-static int post_finish_mode() {
-  static const int m = env_int("QEMB_POST_FINISH", 0) == 2 ? 2 : 0;
-  return m;
-}
-// second kernel of the QEMB_POST_FINISH=0 form: out[j] = sum of the np partials of reduction j, j < m, to device and pinned host memory
+// second kernel: out[j] = sum of the np partials of reduction j, j < m, to device and pinned host memory
 __device__ __forceinline__ void finish_partials_kernel_body(const uint3 BID, const uint3 GDIM, int m, int np, const double* __restrict__ partial, double* out_dev, double* out_host,
                                                               unsigned long long* flag_host, unsigned long long seq) {
   __shared__ double sh[4];
@@ -2353,13 +2290,13 @@ struct BatchEntry {
   // arguments, in kernel order (pointers into this entry are what the grouped launch reads)
   long long n; const double* trial; const double* prev; double* e; double* xcopy; DiisPushK pk;
   int o, v, rows; ExtrapK ek; double* amp; const double* L; double* tau;
-  double* partial; unsigned* counter; double* out_dev; double* out_host; int finish; unsigned long long* flag; unsigned long long seq;
+  double* partial; double* out_dev; double* out_host; unsigned long long* flag; unsigned long long seq;
   int fin_m, fin_np;
-  void* params[16]; void* fparams[8];
+  void* params[8]; void* fparams[8];
 };
 struct BatchCollector { bool on = false; std::vector<BatchEntry> entries; double* scratch = nullptr; size_t scratch_regions = 0; };
 static thread_local BatchCollector t_batch;
-static constexpr size_t BATCH_REGION = 8 * NPART + 8;      // doubles per collected call
+static constexpr size_t BATCH_REGION = 8 * NPART;      // doubles per collected call
 static double* batch_region(size_t k) {
   if (k >= t_batch.scratch_regions) {
     const size_t want = std::max<size_t>(16, 2 * (k + 1));
@@ -2375,8 +2312,7 @@ static double* batch_region(size_t k) {
 // with it for the loads that fed the store: two dependent round trips to HBM per step instead of one.
 template <bool VEC2>
 __device__ __forceinline__ void diis_push_kernel_body(const uint3 BID, const uint3 GDIM, long long n, const double* trial, const double* prev, double* e, double* xcopy,
-                                                        DiisPushK k, double* partial, unsigned* counter, double* row_dev, double* row_host, int finish,
-                                                        unsigned long long* flag_host, unsigned long long seq) {
+                                                        DiisPushK k, double* partial) {
   __shared__ double sh[4];
   const int np = (int)GDIM.x;
   constexpr int W = VEC2 ? 2 : 1;
@@ -2417,20 +2353,10 @@ __device__ __forceinline__ void diis_push_kernel_body(const uint3 BID, const uin
     if (threadIdx.x == 0) partial[(long long)j * np + BID.x] = r;
     __syncthreads();
   }
-  if (!last_workgroup(counter, (unsigned)np, finish)) return;
-  for (int j = 0; j < k.m; ++j) {
-    double a = 0.0;
-    for (int i = threadIdx.x; i < np; i += blockDim.x) a += __builtin_nontemporal_load(partial + (long long)j * np + i);
-    const double r = block_reduce<false>(a, sh);
-    if (threadIdx.x == 0) { row_dev[j] = r; row_host[j] = r; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { *counter = 0u; publish_flag(flag_host, seq); }
 }
 template <bool VEC2>
-__global__ void __launch_bounds__(256) diis_push_kernel(long long n, const double* trial, const double* prev, double* e, double* xcopy, DiisPushK k, double* partial,
-                                                        unsigned* counter, double* row_dev, double* row_host, int finish, unsigned long long* flag_host, unsigned long long seq) {
-  diis_push_kernel_body<VEC2>(block_id(), grid_dim(), n, trial, prev, e, xcopy, k, partial, counter, row_dev, row_host, finish, flag_host, seq);
+__global__ void __launch_bounds__(256) diis_push_kernel(long long n, const double* trial, const double* prev, double* e, double* xcopy, DiisPushK k, double* partial) {
+  diis_push_kernel_body<VEC2>(block_id(), grid_dim(), n, trial, prev, e, xcopy, k, partial);
 }
 static const Groupable<diis_push_kernel_body<false>, 256> reg_diis_push_w1(diis_push_kernel<false>);
 static const Groupable<diis_push_kernel_body<true>, 256> reg_diis_push_w2(diis_push_kernel<true>);
@@ -2450,23 +2376,20 @@ int dev_diis_push(int64_t n, const double* trial, const double* prev, double* e,
     BatchEntry b{};
     b.kind = vec2 ? 1 : 0; b.gx = (unsigned)np; b.gy = 1; b.lds = 0;
     b.n = n; b.trial = trial; b.prev = prev; b.e = e; b.xcopy = xcopy; b.pk = k;
-    b.out_dev = row_dev; b.out_host = row_host; b.finish = 0; b.flag = (unsigned long long*)flag_host; b.seq = seq; b.fin_m = m; b.fin_np = np;
+    b.out_dev = row_dev; b.out_host = row_host; b.flag = (unsigned long long*)flag_host; b.seq = seq; b.fin_m = m; b.fin_np = np;
     t_batch.entries.push_back(b);
     return QEMB_OK;
   }
-  if (vec2) QTRY(launch("dev_diis_push", diis_push_kernel<true>, dim3(np), dim3(256), 0, g_stream, n, trial, prev, e, xcopy, k, g_partials, (unsigned*)(g_partials + 8 * NPART), row_dev, row_host, post_finish_mode(),
-                        (unsigned long long*)flag_host, seq));
-  else QTRY(launch("dev_diis_push", diis_push_kernel<false>, dim3(np), dim3(256), 0, g_stream, n, trial, prev, e, xcopy, k, g_partials, (unsigned*)(g_partials + 8 * NPART), row_dev, row_host, post_finish_mode(),
-                   (unsigned long long*)flag_host, seq));
-  if (post_finish_mode() == 0) QTRY(launch("dev_diis_push", finish_partials_kernel, dim3(1), dim3(256), 0, g_stream, m, np, g_partials, row_dev, row_host, (unsigned long long*)flag_host, seq));
+  if (vec2) QTRY(launch("dev_diis_push", diis_push_kernel<true>, dim3(np), dim3(256), 0, g_stream, n, trial, prev, e, xcopy, k, g_partials));
+  else QTRY(launch("dev_diis_push", diis_push_kernel<false>, dim3(np), dim3(256), 0, g_stream, n, trial, prev, e, xcopy, k, g_partials));
+  QTRY(launch("dev_diis_push", finish_partials_kernel, dim3(1), dim3(256), 0, g_stream, m, np, g_partials, row_dev, row_host, (unsigned long long*)flag_host, seq));
   return QEMB_OK;
 }
 // grid (o * o tiles (i,j), chunks of `rows` rows a): the workgroup forms the new t1[i, its rows] and t1[j, :] in LDS, then streams its rows of the tile --
 // every load of a step before the stores (amp may be x[0]), 16-byte accesses when v is even
 template <bool VEC2>
 __device__ __forceinline__ void ccsd_extrapolate_energy_kernel_body(const uint3 BID, const uint3 GDIM, int o, int v, int rows, ExtrapK k, double* amp, const double* __restrict__ L,
-                                                                      double* __restrict__ tau, double* partial, unsigned* counter, double* e_dev, double* e_host, int finish,
-                                                                      unsigned long long* flag_host, unsigned long long seq) {
+                                                                      double* __restrict__ tau, double* partial) {
   extern __shared__ double t1rows[];                 // the new t1[i, a0 .. a1) and t1[j, :]
   __shared__ double sh[4];
   constexpr int W = VEC2 ? 2 : 1;
@@ -2517,19 +2440,14 @@ __device__ __forceinline__ void ccsd_extrapolate_energy_kernel_body(const uint3 
       tau[pos] = tv[0];
     }
   }
-  const unsigned np = GDIM.x * GDIM.y, me = BID.y * GDIM.x + BID.x;
+  const unsigned me = BID.y * GDIM.x + BID.x;
   const double r = block_reduce<false>(acc, sh);
   if (threadIdx.x == 0) partial[me] = r;
-  if (!last_workgroup(counter, np, finish)) return;
-  double a = 0.0;
-  for (unsigned q = threadIdx.x; q < np; q += blockDim.x) a += __builtin_nontemporal_load(partial + q);
-  const double e = block_reduce<false>(a, sh);
-  if (threadIdx.x == 0) { e_dev[0] = e; e_host[0] = e; *counter = 0u; publish_flag(flag_host, seq); }
 }
 template <bool VEC2>
 __global__ void __launch_bounds__(256) ccsd_extrapolate_energy_kernel(int o, int v, int rows, ExtrapK k, double* amp, const double* __restrict__ L, double* __restrict__ tau,
-                                                                      double* partial, unsigned* counter, double* e_dev, double* e_host, int finish, unsigned long long* flag_host, unsigned long long seq) {
-  ccsd_extrapolate_energy_kernel_body<VEC2>(block_id(), grid_dim(), o, v, rows, k, amp, L, tau, partial, counter, e_dev, e_host, finish, flag_host, seq);
+                                                                      double* partial) {
+  ccsd_extrapolate_energy_kernel_body<VEC2>(block_id(), grid_dim(), o, v, rows, k, amp, L, tau, partial);
 }
 static const Groupable<ccsd_extrapolate_energy_kernel_body<false>, 256> reg_ccsd_extrapolate_energy_w1(ccsd_extrapolate_energy_kernel<false>);
 static const Groupable<ccsd_extrapolate_energy_kernel_body<true>, 256> reg_ccsd_extrapolate_energy_w2(ccsd_extrapolate_energy_kernel<true>);
@@ -2553,15 +2471,15 @@ int dev_ccsd_extrapolate_energy(int64_t o, int64_t v, int nterms, const double* 
     BatchEntry b{};
     b.kind = vec2 ? 3 : 2; b.gx = (unsigned)(o * o); b.gy = (unsigned)chunks; b.lds = lds;
     b.o = (int)o; b.v = (int)v; b.rows = rows; b.ek = k; b.amp = amp; b.L = L; b.tau = tau;
-    b.out_dev = e_dev; b.out_host = e_host; b.finish = 0; b.flag = (unsigned long long*)flag_host; b.seq = seq; b.fin_m = 1; b.fin_np = (int)(o * o * chunks);
+    b.out_dev = e_dev; b.out_host = e_host; b.flag = (unsigned long long*)flag_host; b.seq = seq; b.fin_m = 1; b.fin_np = (int)(o * o * chunks);
     t_batch.entries.push_back(b);
     return QEMB_OK;
   }
   if (vec2) QTRY(launch("dev_ccsd_extrapolate_energy", ccsd_extrapolate_energy_kernel<true>, dim3((unsigned)(o * o), (unsigned)chunks), dim3(256), lds, g_stream, (int)o, (int)v, rows, k, amp, L, tau,
-                        g_partials, (unsigned*)(g_partials + 8 * NPART), e_dev, e_host, post_finish_mode(), (unsigned long long*)flag_host, seq));
+                        g_partials));
   else QTRY(launch("dev_ccsd_extrapolate_energy", ccsd_extrapolate_energy_kernel<false>, dim3((unsigned)(o * o), (unsigned)chunks), dim3(256), lds, g_stream, (int)o, (int)v, rows, k, amp, L, tau,
-                   g_partials, (unsigned*)(g_partials + 8 * NPART), e_dev, e_host, post_finish_mode(), (unsigned long long*)flag_host, seq));
-  if (post_finish_mode() == 0) QTRY(launch("dev_ccsd_extrapolate_energy", finish_partials_kernel, dim3(1), dim3(256), 0, g_stream, 1, (int)(o * o * chunks), g_partials, e_dev, e_host, (unsigned long long*)flag_host, seq));
+                   g_partials));
+  QTRY(launch("dev_ccsd_extrapolate_energy", finish_partials_kernel, dim3(1), dim3(256), 0, g_stream, 1, (int)(o * o * chunks), g_partials, e_dev, e_host, (unsigned long long*)flag_host, seq));
   return QEMB_OK;
 }
 int dev_batch_begin() {
@@ -2582,12 +2500,12 @@ int dev_batch_flush() {
                              (const void*)ccsd_extrapolate_energy_kernel<true>};
   for (size_t k = 0; k < ent.size(); ++k) {
     BatchEntry& b = ent[k];
-    b.partial = batch_region(k); b.counter = (unsigned*)(b.partial + 8 * NPART);
+    b.partial = batch_region(k);
     if (b.kind < 2) {
-      void* pp[13] = {&b.n, &b.trial, &b.prev, &b.e, &b.xcopy, &b.pk, &b.partial, &b.counter, &b.out_dev, &b.out_host, &b.finish, &b.flag, &b.seq};
+      void* pp[7] = {&b.n, &b.trial, &b.prev, &b.e, &b.xcopy, &b.pk, &b.partial};
       std::memcpy(b.params, pp, sizeof(pp));
     } else {
-      void* pp[14] = {&b.o, &b.v, &b.rows, &b.ek, &b.amp, &b.L, &b.tau, &b.partial, &b.counter, &b.out_dev, &b.out_host, &b.finish, &b.flag, &b.seq};
+      void* pp[8] = {&b.o, &b.v, &b.rows, &b.ek, &b.amp, &b.L, &b.tau, &b.partial};
       std::memcpy(b.params, pp, sizeof(pp));
     }
     void* fp[7] = {&b.fin_m, &b.fin_np, &b.partial, &b.out_dev, &b.out_host, &b.flag, &b.seq};
@@ -2661,65 +2579,6 @@ int dev_gemv_rows(int64_t rows, int64_t cols, const double* T, int64_t ldt, cons
   if (rows <= 0) return QEMB_OK;
   const unsigned grid = (unsigned)std::min<int64_t>(rows, 1 << 20);
   return launch("dev_gemv_rows", gemv_rows_kernel, dim3(grid), dim3(256), 0, g_stream, rows, cols, T, ldt, x, y, alpha, beta);
-}
-
-// two matrix-vector products into one result, one pass: y[r] = alpha (T1[r,:] . x1 + T2[r,:] . x2) + beta y[r]
-__device__ __forceinline__ void gemv_rows2_kernel_body(const uint3 BID, const uint3 GDIM, long long rows, long long cols, const double* T1, long long ld1, const double* x1,
-                                                         const double* T2, long long ld2, const double* x2, double* y, double alpha, double beta) {
-  __shared__ double sh[4];
-  for (long long r = BID.x; r < rows; r += GDIM.x) {
-    const double* r1 = T1 + r * ld1;
-    const double* r2 = T2 + r * ld2;
-    double a1 = 0.0, a2 = 0.0;
-    for (long long c = threadIdx.x; c < cols; c += blockDim.x) { a1 += r1[c] * x1[c]; a2 += r2[c] * x2[c]; }
-    const double s = block_reduce<false>(a1 + a2, sh);
-    if (threadIdx.x == 0) y[r] = (beta != 0.0) ? alpha * s + beta * y[r] : alpha * s;
-  }
-}
-__global__ void __launch_bounds__(256) gemv_rows2_kernel(long long rows, long long cols, const double* T1, long long ld1, const double* x1, const double* T2, long long ld2, const double* x2,
-                                                         double* y, double alpha, double beta) {
-  gemv_rows2_kernel_body(block_id(), grid_dim(), rows, cols, T1, ld1, x1, T2, ld2, x2, y, alpha, beta);
-}
-static const Groupable<gemv_rows2_kernel_body, 256> reg_gemv_rows2(gemv_rows2_kernel);
-int dev_gemv_rows2(int64_t rows, int64_t cols, const double* T1, int64_t ld1, const double* x1, const double* T2, int64_t ld2, const double* x2, double* y, double alpha, double beta) {
-  REQUIRE_INIT();
-  if (rows <= 0) return QEMB_OK;
-  const unsigned grid = (unsigned)std::min<int64_t>(rows, 1 << 20);
-  return launch("dev_gemv_rows2", gemv_rows2_kernel, dim3(grid), dim3(256), 0, g_stream, rows, cols, T1, ld1, x1, T2, ld2, x2, y, alpha, beta);
-}
-// The four small products of the T1 equation in one launch.  grid (o, chunks of 64 rows a): every workgroup forms Q[i,:] for its i (o dot products over v),
-// then one wave per row a:  t1n[i,a] = sum_c t1[i,c] Lvv[a,c] + sum_k (Q[i,k] - Loo[k,i]) t1[k,a]
-__device__ __forceinline__ void ccsd_t1_small_kernel_body(const uint3 BID, const uint3 GDIM, int o, int v, const double* __restrict__ t1, const double* __restrict__ Lvv,
-                                                            const double* __restrict__ Loo, const double* __restrict__ Fov, double* __restrict__ t1n) {
-  __shared__ double w[1024];              // Q[i,k] - Loo[k,i], k < o <= 1024
-  const int i = (int)BID.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const double* ti = t1 + (long long)i * v;
-  for (int k = wave; k < o; k += nw) {
-    double acc = 0.0;
-    for (int c = lane; c < v; c += 64) acc += ti[c] * Fov[(long long)k * v + c];
-    acc = wave_sum(acc);
-    if (lane == 0) w[k] = acc - Loo[(long long)k * o + i];
-  }
-  __syncthreads();
-  const int a1 = min(v, ((int)BID.y + 1) * 64);
-  for (int a = (int)BID.y * 64 + wave; a < a1; a += nw) {
-    double acc = 0.0;
-    for (int c = lane; c < v; c += 64) acc += ti[c] * Lvv[(long long)a * v + c];
-    for (int k = lane; k < o; k += 64) acc += w[k] * t1[(long long)k * v + a];
-    acc = wave_sum(acc);
-    if (lane == 0) t1n[(long long)i * v + a] = acc;
-  }
-}
-__global__ void __launch_bounds__(256) ccsd_t1_small_kernel(int o, int v, const double* __restrict__ t1, const double* __restrict__ Lvv, const double* __restrict__ Loo,
-                                                            const double* __restrict__ Fov, double* __restrict__ t1n) {
-  ccsd_t1_small_kernel_body(block_id(), grid_dim(), o, v, t1, Lvv, Loo, Fov, t1n);
-}
-static const Groupable<ccsd_t1_small_kernel_body, 256> reg_ccsd_t1_small(ccsd_t1_small_kernel);
-int dev_ccsd_t1_small(int64_t o, int64_t v, const double* t1, const double* Lvv, const double* Loo, const double* Fov, double* t1n) {
-  REQUIRE_INIT();
-  if (o <= 0 || v <= 0) return QEMB_OK;
-  if (o > 1024 || (v + 63) / 64 > 65535) { set_error("dev_ccsd_t1_small: n_occ <= 1024"); return QEMB_ERR_ARG; }
-  return launch("dev_ccsd_t1_small", ccsd_t1_small_kernel, dim3((unsigned)o, (unsigned)((v + 63) / 64)), dim3(256), 0, g_stream, (int)o, (int)v, t1, Lvv, Loo, Fov, t1n);
 }
 // The right-hand side of the T1 equation, one workgroup per element r = (i,a): the o dot products Q[i,k] - Loo[k,i] first (waves over k), then every thread
 // strides over the two long rows S[r,:], Lph1[r,:], the short rows of the small products and the slabs of the two long-K products; one block sum.
@@ -3011,12 +2870,12 @@ __device__ __forceinline__ double row16_sum_dpp(double v) {      // total over t
   v += dpp_take_f64<0x140, 0xF>(v);
   return v;
 }
-// GL = lanes per row group (16: four rows per wave step, 32: two); NKS = ceil(n / (2 GL)) 16-byte column slots per lane
-template <int GL, int NKS, bool WITH_J>
+// NKS = ceil(n / 32) 16-byte column slots per lane
+template <int NKS, bool WITH_J>
 __global__ void __launch_bounds__(256, 2) jk_packed_rowgroups(int n, const double* __restrict__ S4, const double* __restrict__ D,
                                                            const double* __restrict__ Dp, double* __restrict__ Jp, double* __restrict__ P1,
                                                            double* __restrict__ P2) {
-  constexpr int G = 64 / GL, NSLOT = 4 * G, BAND = 2 * GL;      // row groups per wave; (wave, group) partial vectors; rows per band
+  constexpr int GL = 16, G = 64 / GL, NSLOT = 4 * G, BAND = 2 * GL;      // lanes per row group; row groups per wave; (wave, group) partial vectors; rows per band
   extern __shared__ double sm[];
   double* yl1 = sm; double* yl2 = sm + n; double* part = sm + 2 * n;      // part[(wave * G + group) * 2 + vector][n]; jw behind it
   double* jw = part + 2 * NSLOT * n;
@@ -3075,13 +2934,10 @@ __global__ void __launch_bounds__(256, 2) jk_packed_rowgroups(int n, const doubl
         up[k][0] += cx * dp_r; up[k][1] += cy * dp_r;
       }
       a1 = row16_sum_dpp(a1); a2 = row16_sum_dpp(a2);
-      if (GL == 32) {       // row_bcast:15 into DPP rows 1 and 3: their lanes then hold the sum over the 32 lanes of the group
-        a1 += dpp_take_f64<0x142, 0xA>(a1); a2 += dpp_take_f64<0x142, 0xA>(a2);
-      }
       if (c == GL - 1 && valid) { yl1[r] = a1; yl2[r] = a2; }
     };
-    // (requesting the pieces of the wave's next step before the current one is consumed -- two register sets -- was measured: slower,
-    //  1.49 vs 1.32 ms at n = 220 with 32-lane groups, no gain with 16-lane groups; the pass is not latency bound)
+    // (requesting the pieces of the wave's next step before the current one is consumed -- two register sets -- was measured: no gain;
+    //  the pass is not latency bound)
     for (int Q = STEPS * b + wave; Q < qend; Q += 4) {
       D2u x[KM], w[KM];
       fetch(Q, x, w);
@@ -3124,34 +2980,20 @@ int dev_jk_from_packed(int64_t n, const double* S4, const double* D, const doubl
   if (rc) return rc;
   double* P1 = g_ws; double* P2 = g_ws + np * n;
   hipError_t attr_err = hipSuccess;
-  static const bool old_kernel = env_flag("QEMB_JK_V1", false);      // A/B measurements (tools/hbm_kernels.py)
-  static const int gl = (int)env_int("QEMB_JK_GL", 16);      // 16: 1.28 ms, 32: 1.32 ms at n = 220
-  if (n >= 2 && n <= 448 && !old_kernel) {
-    // 32-lane row groups (two rows per wave step): 8 partial vectors; 16-lane groups (four rows): 16
-    const int nslot = gl == 16 ? 16 : 8;
-    const size_t lds = (size_t)((2 + 2 * nslot) * n + 8) * sizeof(double);   // n = 220: 31.7 KB (GL 32) / 59.9 KB (GL 16) per workgroup
+  if (n >= 2 && n <= 448) {
+    const size_t lds = (size_t)((2 + 2 * 16) * n + 8) * sizeof(double);   // 16 (wave, group) partial vector pairs; n = 220: 59.9 KB per workgroup
     auto launch = [&](auto kern) {
       if (lds > 64 * 1024) attr_err = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (attr_err == hipSuccess) hipLaunchKernelGGL(kern, dim3((unsigned)np), dim3(256), lds, g_stream, (int)n, S4, D, Dp, Jp, P1, P2);
     };
-#define QEMB_JK_CASE(GL, NKS) do { if (Jp) launch(jk_packed_rowgroups<GL, NKS, true>); else launch(jk_packed_rowgroups<GL, NKS, false>); } while (0)
-    if (gl == 16) {
-      const int nks = (int)((n + 31) / 32);
-      if (nks <= 1) QEMB_JK_CASE(16, 1);
-      else if (nks <= 2) QEMB_JK_CASE(16, 2);
-      else if (nks <= 4) QEMB_JK_CASE(16, 4);
-      else if (nks <= 7) QEMB_JK_CASE(16, 7);
-      else if (nks <= 10) QEMB_JK_CASE(16, 10);
-      else QEMB_JK_CASE(16, 14);
-    } else {
-      const int nks = (int)((n + 63) / 64);
-      if (nks <= 1) QEMB_JK_CASE(32, 1);
-      else if (nks <= 2) QEMB_JK_CASE(32, 2);
-      else if (nks <= 3) QEMB_JK_CASE(32, 3);
-      else if (nks <= 4) QEMB_JK_CASE(32, 4);
-      else if (nks <= 5) QEMB_JK_CASE(32, 5);
-      else QEMB_JK_CASE(32, 7);
-    }
+#define QEMB_JK_CASE(NKS) do { if (Jp) launch(jk_packed_rowgroups<NKS, true>); else launch(jk_packed_rowgroups<NKS, false>); } while (0)
+    const int nks = (int)((n + 31) / 32);
+    if (nks <= 1) QEMB_JK_CASE(1);
+    else if (nks <= 2) QEMB_JK_CASE(2);
+    else if (nks <= 4) QEMB_JK_CASE(4);
+    else if (nks <= 7) QEMB_JK_CASE(7);
+    else if (nks <= 10) QEMB_JK_CASE(10);
+    else QEMB_JK_CASE(14);
 #undef QEMB_JK_CASE
   } else {
     const size_t lds = (size_t)(10 * n + 8) * sizeof(double);
@@ -3178,11 +3020,9 @@ int dev_jk_from_packed(int64_t n, const double* S4, const double* D, const doubl
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ long long pair_idx(long long i, long long j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
 
-// row walkers per tile of the tiled unpack: enough blocks for 8 per CU and some slack for the tail (QEMB_UNPACK_WALKERS overrides: A/B runs)
+// row walkers per tile of the tiled unpack: one row per block measured best (profiles/r03_hbm_kernels.jsonl), up to the grid's y limit
 static int64_t unpack_walkers(int64_t rows, int64_t ntiles) {
-  static const int64_t forced = env_int("QEMB_UNPACK_WALKERS", 0);
-  const int64_t want = forced > 0 ? forced : 65535;      // one row per block measured best (profiles/r03_hbm_kernels.jsonl)
-  return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(rows, 65535), want));
+  return std::max<int64_t>(1, std::min<int64_t>(rows, 65535));
 }
 // Tiled triangular unpack: one workgroup per packed row, 32 x 32 tiles of the lower triangle staged through LDS so that
 // both the [k][l] image and its mirror [l][k] are written in 256-byte runs and every packed element is read once.

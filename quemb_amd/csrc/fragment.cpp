@@ -148,8 +148,7 @@ int Fragment::set_mo_route(int route) {
   return 0;
 }
 bool Fragment::use_factor_route() const {
-  static const bool off = !env_flag("QEMB_MO_FROM_FACTOR", true);      // A/B measurements
-  if (!df_factor_.p || mo_route_ == 0 || off) return false;
+  if (!df_factor_.p || mo_route_ == 0) return false;
   if (!eri_s4_.p) return true;      // a fragment that lives on its factor: forming the block first would cost what the factor's own product costs
   return mo_route_ == 1 || mo_factor_route_pays(n_, df_naux_);
 }
@@ -432,12 +431,12 @@ struct Fanout {
   int F; bool threaded = false; PhasePool* pool = nullptr; std::vector<int> rc; std::vector<std::string> msg;
   explicit Fanout(int F_) : F(F_), rc(F_, 0), msg(F_) {}
   ~Fanout() { if (pool) pool->release(); }
-  int init(bool use_pool) {
+  int init() {
     const int have = dev_ctx_count(F + 1);
     if (have < 0) return have;
     // a backend with a single execution context (the scalar mock of tests/hostcheck) runs the per-fragment phases one after the other
     threaded = have >= F + 1 && F > 1;
-    if (threaded && use_pool) pool = PhasePool::acquire(F);
+    if (threaded) pool = PhasePool::acquire(F);      // (busy with another caller's batch: none, a std::thread per fragment and phase)
     return 0;
   }
   template <class Fn> int operator()(Fn fn) {
@@ -473,9 +472,8 @@ int Fragment::solve_batch(const std::vector<Fragment*>& frs, const std::vector<i
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_start = now();
   res.assign(F, FragmentResult());
-  static const bool pool_on = env_flag("QEMB_PHASE_POOL", true);      // (0: a std::thread per fragment and phase, for A/B runs)
   Fanout per_fragment(F);
-  QTRY(per_fragment.init(pool_on));
+  QTRY(per_fragment.init());
   const bool threaded = per_fragment.threaded;
   // Before the iterations: the fragment RHF per fragment (host round trips inside), then MO integrals + CCSD set-up + starting amplitudes, each fragment on its own
   // stream.  (One pass of the host threads for both halves of the begin phase: a fragment goes on to its integrals as soon as ITS RHF is through instead of
@@ -586,7 +584,7 @@ int Fragment::solve_begin_cc() {
 // The recorded update of a lock-step sweep.  Recording costs a stream capture and ~50 node queries per fragment and sweep (0.4-0.5 ms of the begin phase of an
 // octane sweep, the six host threads queueing on the runtime's capture lock), and a new tape means a new merge plan in dev_tape_run.  The tape only names
 // buffers and sizes: when this solve's allocations landed where the last solve's did (the pool hands blocks back in the order they came -- sp_.alloc_hash), the
-// last tape IS this solve's tape.  QEMB_TAPE_CACHE=0: record every time; QEMB_TAPE_CACHE_CHECK=1: record anyway and compare with the kept tape (tests).
+// last tape IS this solve's tape.  QEMB_TAPE_CACHE_CHECK=1: record anyway and compare with the kept tape (tests).
 static std::atomic<long long> g_tape_reused{0}, g_tape_recorded{0};
 void tape_cache_counters(long long* reused, long long* recorded, int reset) {
   if (reused) *reused = g_tape_reused.load();
@@ -595,13 +593,12 @@ void tape_cache_counters(long long* reused, long long* recorded, int reset) {
 }
 // (peers: the fragment count of the sweep; it only enters the key)
 int Fragment::tape_for_lockstep(int peers) {
-  static const bool cache_on = env_flag("QEMB_TAPE_CACHE", true);
   const bool check = env_flag("QEMB_TAPE_CACHE_CHECK", false);
   unsigned long long key = sp_.alloc_hash ^ (0x9e3779b97f4a7c15ull * (unsigned long long)(peers + 1)) ^ ((unsigned long long)sp_.o << 40) ^ ((unsigned long long)n_ << 20);
   if (key == 0) key = 1;
   tape_key_ = key;
   if (env_flag("QEMB_TAPE_CACHE_TRACE", false)) std::fprintf(stderr, "[qemb tape cache] fragment %p n %d: key %016llx, kept %016llx\n", (void*)this, n_, key, tape_cache_.tape ? tape_cache_.key : 0ull);
-  if (cache_on && tape_cache_.tape && tape_cache_.key == key) {
+  if (tape_cache_.tape && tape_cache_.key == key) {
     if (check) {
       QTRY(cc_->prepare_tape());
       if (cc_->tape() && !dev_tape_equal(cc_->tape(), tape_cache_.tape)) { set_error(std::string("the kept tape differs from a fresh recording at the same buffer layout: ") + last_error()); return QEMB_ERR_DEVICE; }
@@ -1251,7 +1248,7 @@ int Fragment::solve_mp2_batch(const std::vector<Fragment*>& frs, const std::vect
   if (F == 0) return 0;
   res.assign(F, FragmentResult());
   Fanout per_fragment(F);
-  QTRY(per_fragment.init(true));
+  QTRY(per_fragment.init());
   return per_fragment([&](int f) {
     return frs[f]->solve_mp2(o[f], h[f], dm0[f], opt, eeval, &res[f], outs[f].mo_coeff, outs[f].mo_energy, outs[f].rdm1_emb, outs[f].rdm1_mo, outs[f].t2);
   });

@@ -625,9 +625,8 @@ static int launch_cfg(const GemmDesc& d, hipStream_t s) {
   }
   {
     // super-blocks of 32 tiles (the workgroups one XCD runs at a time at one workgroup per CU): the shape that moves the fewest operand bytes
-    // per k-step, sb_m x |A tile| + sb_n x |B tile|, among the shapes that divide the tile grid (QEMB_GEMM_SB=0: the m-fastest walk, for A/B runs)
-    static const bool sb_on = env_flag("QEMB_GEMM_SB", true);
-    if (sb_on && d.batch == 1 && d.ksplit <= 1 && g.tiles_m >= 8 && g.tiles_n >= 4 && ((long long)g.tiles_m * g.tiles_n) % 256 == 0) {
+    // per k-step, sb_m x |A tile| + sb_n x |B tile|, among the shapes that divide the tile grid (other shapes: the m-fastest walk)
+    if (d.batch == 1 && d.ksplit <= 1 && g.tiles_m >= 8 && g.tiles_n >= 4 && ((long long)g.tiles_m * g.tiles_n) % 256 == 0) {
       long long best = -1;
       for (int sm = 1; sm <= 32; sm *= 2) {
         const int sn = 32 / sm;
@@ -706,12 +705,6 @@ static int launch_tile(const GemmDesc& d, hipStream_t s, bool vec2) {
   constexpr GemmTile t = gemm_tile(ID);
   static_assert(t.wm > 0, "not a tile of gemm_tiles.h");
   return launch_layout<t.wm, t.wn, t.waves_m, t.waves_n, t.bk, TAG, MODE>(d, s, vec2);
-}
-
-// 16-byte loads of an operand tile: the rule is gemm_operand_vec2_ok (dev_ops.h); QEMB_GEMM_VEC2_ODD=0 selects the round-4 rule, for A/B runs
-static bool gemm_vec2_relaxed() {
-  static const bool relaxed = env_flag("QEMB_GEMM_VEC2_ODD", true);
-  return relaxed;
 }
 
 // ---- calibration: v_mfma_f64_16x16x4_f64 issue rate of the whole chip, registers only (no LDS, no memory traffic) -----------
@@ -860,7 +853,7 @@ static int dev_gemm_dispatch(const GemmDesc& d) {
       std::fflush(shapelog);
     }
   }
-  const bool vec2 = gemm_desc_vec2(d, gemm_vec2_relaxed());
+  const bool vec2 = gemm_desc_vec2(d);      // 16-byte loads of an operand tile: the rule is stated in dev_ops.h
   // tile choice: biggest tile that still gives the 256 CUs >= ~2 workgroups each; small problems
   // fall to 64x64 / 32x32 tiles so the grid is not a handful of blocks.
   const int64_t t128 = ((d.M + 127) / 128) * ((d.N + 127) / 128) * d.batch;

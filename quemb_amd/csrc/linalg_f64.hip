@@ -314,6 +314,7 @@ __global__ void __launch_bounds__(1024) jacobi_eigh_small_kernel(const double* _
 // place.  The partner of index i in round r of the round-robin is (2 r - i) mod (np - 1) (np - 1 itself pairs with r).  Largest rotated element per
 // thread in a register, combined once per sweep.  Same pairs, same angles, same order of rounds as jacobi_eigh_small_kernel.
 constexpr int JE_DB_MAX = 80;
+static_assert(JE_DB_MAX <= JE_MAX, "the single-launch bound of dev_jacobi_eigh must fit both small kernels");
 // Fused form for the fragment RHF (round 5; Cp != nullptr or dm_out != nullptr): the matrix is first rotated into the basis Cp (A = Cp^T F Cp, the orbitals of the last
 // SCF cycle, in which F is nearly diagonal), the eigenvectors are rotated back (C = Cp V, columns in ascending order of the eigenvalues), written to V_out and --
 // when asked -- a second time to C2_out (which may be Cp itself: the next cycle's basis), and dm_out = 2 C_occ C_occ^T of the lowest `nocc` columns.  One launch
@@ -672,9 +673,8 @@ static int jacobi_rows(int nvec, int64_t len, double* W, int64_t ldw, double* Vt
   if (nvec < 2) { if (sweeps_out) *sweeps_out = 0; return QEMB_OK; }
   const int np = (nvec % 2 == 0) ? nvec : nvec + 1;
   // (64 < nvec <= 96 take the block rounds below since round 5: n = 96 cold 3.2-3.4 -> 1.35 ms, warm 1.28 -> 0.60 ms; n = 80 2.1 -> 1.34 / 0.89 -> 0.60 ms -- one
-  //  workgroup is bound by the LDS bandwidth of its CU there; at n = 57 the single workgroup is still the faster one, 0.86 vs 0.92 ms.  QEMB_JACOBI_ROWS_SMALL_MAX=96: as before)
-  static const int rows_small_max = (int)env_int("QEMB_JACOBI_ROWS_SMALL_MAX", 64);
-  if (Vt && nvec <= JS_MAX && len <= JS_MAX && nvec <= rows_small_max) {   // LDS-resident single-workgroup path
+  //  workgroup is bound by the LDS bandwidth of its CU there; at n = 57 the single workgroup is still the faster one, 0.86 vs 0.92 ms)
+  if (Vt && nvec <= JS_MAX && len <= JS_MAX && nvec <= 64) {   // LDS-resident single-workgroup path
     int* d_sw = nullptr;
     QTRY_ALLOC(d_sw, sizeof(int));
     const double tol_s = std::max(1.0e-15, std::sqrt((double)len) * 2.22e-16);
@@ -768,9 +768,8 @@ static int jacobi_eigh_impl(int64_t n64, double* A, double* w, double* V, int* s
   // small matrices: the whole eigensolve in one launch (two-sided Jacobi in LDS; QEMB_JACOBI_TWOSIDED=0: the one-sided path below, for A/B runs)
   static const bool two_sided = env_flag("QEMB_JACOBI_TWOSIDED", true);
   // (n <= 80: the one-barrier kernel; 80 < n <= 96 went through the three-barrier kernel until round 5 -- 1.28 ms warm, bound by the LDS bandwidth of its one CU -- and take
-  //  the block rounds of jacobi_rows now, 0.60 ms; QEMB_JACOBI_SMALL_MAX=96: as before)
-  static const int small_max = std::min((int)env_int("QEMB_JACOBI_SMALL_MAX", JE_DB_MAX), JE_MAX);
-  if (two_sided && n <= small_max) {
+  //  the block rounds of jacobi_rows now, 0.60 ms)
+  if (two_sided && n <= JE_DB_MAX) {
     int* d_st = nullptr;
     QTRY_ALLOC(d_st, sizeof(int));
     const int ld = n + 1 + (n & 1), nh = (n + (n & 1)) / 2;
@@ -839,10 +838,7 @@ static int jacobi_eigh_impl(int64_t n64, double* A, double* w, double* V, int* s
 }
 
 // ---- fused steps of the fragment RHF of small fragments (scf.cpp)
-int dev_scf_fused_max() {
-  static const int m = env_flag("QEMB_SCF_FUSED", true) ? JE_DB_MAX : 0;      // (QEMB_SCF_FUSED=0: the launch-by-launch cycle, for A/B runs)
-  return m;
-}
+int dev_scf_fused_max() { return JE_DB_MAX; }      // (larger n: the launch-by-launch cycle)
 int dev_jacobi_eigh_in_basis(int64_t n64, const double* F, const double* Cp, double* w, double* C_out, double* C2_out, int nocc, double* dm_out, double stop_below,
                              int* status_dev) {
   hipStream_t s = hip_stream();

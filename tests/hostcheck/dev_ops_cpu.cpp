@@ -294,7 +294,8 @@ int dev_pack_w_pm_sum(int64_t o, const double* Wt, const double* X, const double
     W[(size_t)(((k * o + l) * o + i) * o + j)] = ((Wt[((i * o + j) * o + k) * o + l] + X[((i * o + j) * o + k) * o + l]) + At[((j * o + i) * o + k) * o + l]) + At[((i * o + j) * o + l) * o + k];
   return dev_pack_w_pm(o, W.data(), Ap, lda_p, Am, lda_m);
 }
-int dev_ccsd_t1_small(int64_t o, int64_t v, const double* t1, const double* Lvv, const double* Loo, const double* Fov, double* t1n) {
+// the four small products of the T1 equation: t1n[i,a] = sum_c t1[i,c] Lvv[a,c] - sum_k Loo[k,i] t1[k,a] + sum_k Q[i,k] t1[k,a],  Q[i,k] = sum_c t1[i,c] Fov[k,c]
+static int t1_small_products(int64_t o, int64_t v, const double* t1, const double* Lvv, const double* Loo, const double* Fov, double* t1n) {
   for (int64_t i = 0; i < o; ++i) {
     std::vector<double> w((size_t)o);
     for (int64_t k = 0; k < o; ++k) { double q = 0; for (int64_t c = 0; c < v; ++c) q += t1[i * v + c] * Fov[k * v + c]; w[(size_t)k] = q - Loo[k * o + i]; }
@@ -311,7 +312,7 @@ int dev_ccsd_t1_assemble(int64_t o, int64_t v, const double* t1, const double* L
                          const double* PA, int SA, int64_t strideA, const double* PB, int SB, int64_t strideB, double* t1n) {
   const int64_t nov = o * v;
   std::vector<double> out((size_t)nov);
-  int rc = dev_ccsd_t1_small(o, v, t1, Lvv, Loo, Fov, out.data());
+  int rc = t1_small_products(o, v, t1, Lvv, Loo, Fov, out.data());
   if (rc) return rc;
   for (int64_t r = 0; r < nov; ++r) {
     double s = out[(size_t)r];
@@ -372,13 +373,6 @@ int dev_scale_rows(int64_t nrows, int64_t len, double* x, const double* s) { for
 int dev_threshold_mask(int64_t n, const double* x, double eps, double* out) { for (int64_t i = 0; i < n; ++i) out[i] = std::fabs(x[i]) >= eps ? 1.0 : 0.0; return 0; }
 int dev_mul_bcast_rows(int64_t rows, int64_t cols, double* x, const double* m) { for (int64_t r = 0; r < rows; ++r) for (int64_t c = 0; c < cols; ++c) x[r * cols + c] *= m[c]; return 0; }
 int dev_dot(int64_t n, const double* x, const double* y, double* o) { long double s = 0; for (int64_t i = 0; i < n; ++i) s += (long double)x[i] * y[i]; *o = (double)s; return 0; }
-int dev_ccsd_finish_t2(int64_t o, int64_t v, double* t2n, const double* U, const double* OV, const double* eo, const double* ev) {
-  for (int64_t i = 0; i < o; ++i) for (int64_t j = 0; j < o; ++j) for (int64_t a = 0; a < v; ++a) for (int64_t b = 0; b < v; ++b) {
-    const int64_t idx = ((i * o + j) * v + a) * v + b;
-    t2n[idx] = (t2n[idx] + OV[idx] + U[idx] + U[((j * o + i) * v + b) * v + a]) / (eo[i] + eo[j] - ev[a] - ev[b]);
-  }
-  return 0;
-}
 int dev_dot_many(int64_t n, const double* x, int m, const double* const* ys, double* o) {
   for (int j = 0; j < m; ++j) { double s = 0; for (int64_t i = 0; i < n; ++i) s += x[i] * ys[j][i]; o[j] = s; }
   return 0;
@@ -414,14 +408,6 @@ int dev_ccsd_extrapolate_energy(int64_t o, int64_t v, int nterms, const double* 
 int dev_absmax(int64_t n, const double* x, double* o) { double m = 0; for (int64_t i = 0; i < n; ++i) m = std::max(m, std::fabs(x[i])); *o = m; return 0; }
 int dev_gemv_rows(int64_t rows, int64_t cols, const double* T, int64_t ldt, const double* x, double* y, double alpha, double beta) {
   for (int64_t r = 0; r < rows; ++r) { double s = 0; for (int64_t c = 0; c < cols; ++c) s += T[r * ldt + c] * x[c]; y[r] = (beta != 0.0) ? alpha * s + beta * y[r] : alpha * s; }
-  return 0;
-}
-int dev_gemv_rows2(int64_t rows, int64_t cols, const double* T1, int64_t ld1, const double* x1, const double* T2, int64_t ld2, const double* x2, double* y, double alpha, double beta) {
-  for (int64_t r = 0; r < rows; ++r) {
-    double s = 0;
-    for (int64_t c = 0; c < cols; ++c) s += T1[r * ld1 + c] * x1[c] + T2[r * ld2 + c] * x2[c];
-    y[r] = (beta != 0.0) ? alpha * s + beta * y[r] : alpha * s;
-  }
   return 0;
 }
 int dev_gemv_rows_two(int64_t rows1, int64_t cols1, const double* T1, int64_t ld1, const double* x1, double* y1, double a1, double b1,

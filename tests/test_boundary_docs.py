@@ -125,7 +125,8 @@ def test_readme_ladder_agreement_lines_follow_their_csv():
 
 def test_every_switch_is_read_through_the_helpers_and_listed_once():
     """Every QEMB_* switch of the library is read through env_flag / env_int / env_real / env_str (quemb_amd/csrc/env.h) with its name as a literal, and the
-    switch table of DESIGN.md section 5 lists exactly those names, each once; no getenv("QEMB_...") is left beside the helpers."""
+    switch table of DESIGN.md section 5 lists exactly those names, each once; no getenv("QEMB_...") is left beside the helpers.  The files the table names as
+    users of a switch exist and name it, and a switch nobody uses is either a diagnostic / operating limit of the short list below or does not exist."""
     csrc = ROOT / "quemb_amd" / "csrc"
     srcs = [f for f in sorted(csrc.iterdir()) if f.suffix in (".cpp", ".hip", ".h", ".inc")]
     read = set()
@@ -141,3 +142,20 @@ def test_every_switch_is_read_through_the_helpers_and_listed_once():
     assert all(ln.count("|") == 5 for ln in rows)            # switch, default, what the other value does, who sets it
     assert len(listed) == len(set(listed)), "a switch is listed twice"
     assert read and set(listed) == read, (sorted(read - set(listed)), sorted(set(listed) - read))
+    # the last column names real users: every path in it exists and contains the switch's name
+    for name, ln in zip(listed, rows):
+        for path in re.findall(r"`([\w./-]+\.\w+)`", ln.split("|")[4]):
+            assert (ROOT / path).is_file(), f"{name}: the table names {path}, which does not exist"
+            assert name in (ROOT / path).read_text(), f"{name}: {path} does not name it"
+    # ... and a switch has a user -- a test, a tool, bench.py or the Python package -- or is one of the few diagnostics and operating limits that are
+    # set by hand.  An A/B switch whose experiment is over is retired with its code (docs/history.md, "Retired switches"), not kept for later.
+    by_hand = ("QEMB_LAMBDA_TRACE", "QEMB_TAPE_CACHE_TRACE", "QEMB_BACKTRACE", "QEMB_TIMERS", "QEMB_POOL_CAP_GB", "QEMB_CU_SPLIT")
+    users = [f for d in ("tests", "tools") for f in sorted((ROOT / d).rglob("*")) if f.is_file() and f.suffix in (".py", ".sh", ".cpp", ".h", ".md")]
+    users += [ROOT / "bench.py"] + sorted((ROOT / "quemb_amd").glob("*.py"))
+    users = [f for f in users if f.resolve() != Path(__file__).resolve()]
+    texts = [f.read_text() for f in users]
+    used = {name for name in listed if any(re.search(r"\b" + name + r"\b", t) for t in texts)}
+    assert not used & set(by_hand), f"set by a test or tool, so not needed in the by-hand list: {sorted(used & set(by_hand))}"
+    assert set(by_hand) <= set(listed), f"not a switch of the library any more: {sorted(set(by_hand) - set(listed))}"
+    unused = sorted(set(listed) - used - set(by_hand))
+    assert not unused, f"no test, tool, bench.py or quemb_amd/*.py names {unused}: retire the switch with the code only it reaches"

@@ -648,8 +648,8 @@ def test_gemm_tiny_result_long_k(qlib, shape, a_kc, b_kc):
 
 @pytest.mark.parametrize("o,v", [(1, 1), (2, 3), (4, 33), (7, 70), (21, 21), (5, 64), (3, 97)])
 def test_ccsd_update_fused_passes(qlib, o, v):
-    """The fused passes of update_amps against NumPy: Woooo packed from its four terms, the four small T1 products, the double matrix-vector pass,
-    the finishing pass that takes the ring products where the GEMMs leave them, the transposing pass with a second output, and the addends of
+    """The fused passes of update_amps against NumPy: Woooo packed from its four terms, the whole T1 right-hand side, the two matrix-vector passes
+    of one launch, the finishing pass that takes the ring products where the GEMMs leave them, the transposing pass with a second output, and the addends of
     scatter_pm_rows / y_traces."""
     rng = np.random.default_rng(31 * o + v)
     nov = o * v
@@ -665,21 +665,10 @@ def test_ccsd_update_fused_passes(qlib, o, v):
     assert np.abs(outs[0].numpy((npo, lwp)) - outs[2].numpy((npo, lwp))).max() < 1e-13
     if nmo:
         assert np.abs(outs[1].numpy((nmo, lwm)) - outs[3].numpy((nmo, lwm))).max() < 1e-13
-    # --- t1_small
+    # --- the whole T1 right-hand side in one launch: small products + the two long rows + slab sums
     t1, Fov = rng.standard_normal((o, v)), rng.standard_normal((o, v))
     Lvv, Loo = rng.standard_normal((v, v)), rng.standard_normal((o, o))
-    d = [DeviceBuffer.from_numpy(a) for a in (t1, Lvv, Loo, Fov)]
     dt1n = DeviceBuffer(nov)
-    check(qlib.qemb_op_ccsd_t1_small(o, v, d[0].ptr, d[1].ptr, d[2].ptr, d[3].ptr, dt1n.ptr))
-    ref = t1 @ Lvv.T - Loo.T @ t1 + (t1 @ Fov.T) @ t1
-    assert np.abs(dt1n.numpy((o, v)) - ref).max() < 1e-12 * max(1.0, np.abs(ref).max())
-    # --- gemv_rows2
-    T1, T2, x1, x2, y0 = rng.standard_normal((nov, nov)), rng.standard_normal((nov, nov)), rng.standard_normal(nov), rng.standard_normal(nov), rng.standard_normal(nov)
-    d = [DeviceBuffer.from_numpy(a) for a in (T1, x1, T2, x2, y0)]
-    check(qlib.qemb_op_gemv_rows2(nov, nov, d[0].ptr, nov, d[1].ptr, d[2].ptr, nov, d[3].ptr, d[4].ptr, 0.75, 1.0))
-    ref = 0.75 * (T1 @ x1 + T2 @ x2) + y0
-    assert np.abs(d[4].numpy((nov,)) - ref).max() < 1e-12 * max(1.0, np.abs(ref).max())
-    # --- the whole T1 right-hand side in one launch: small products + the two long rows + slab sums
     Sm, Lph1 = rng.standard_normal((nov, nov)), rng.standard_normal((nov, nov))
     SA, SB = 5, 3
     PA, PB = rng.standard_normal((SA, nov)), rng.standard_normal((SB, nov))
@@ -755,8 +744,8 @@ def test_ccsd_update_fused_passes(qlib, o, v):
 
 @pytest.mark.parametrize("o,v,m", [(1, 1, 1), (3, 5, 2), (4, 33, 6), (7, 70, 8), (21, 21, 6), (20, 100, 6)])
 def test_ccsd_iteration_end_single_launch_kernels(qlib, o, v, m):
-    """diis_push (error vector, stored trial vector, Gram row) and ccsd_extrapolate_energy (amplitudes, tau, energy) -- one launch each, the last
-    workgroup finishing the reduction -- against NumPy; launched repeatedly so that the workgroup counter is seen to be left at zero."""
+    """diis_push (error vector, stored trial vector, Gram row) and ccsd_extrapolate_energy (amplitudes, tau, energy) -- one pass each and the small
+    kernel that finishes the reduction -- against NumPy; launched repeatedly so that nothing is seen to be left over from one call to the next."""
     rng = np.random.default_rng(7 * o + v + m)
     nov, n = o * v, o * v + o * o * v * v
     trial, prev = rng.standard_normal(n), rng.standard_normal(n)

@@ -1,7 +1,7 @@
 """GPU micro-benchmark of the HBM-bound kernels of one fragment solve at the benchmarked size (n = 220, n_occ = 20, n_virt = 200), each on its
 own with the operand shapes of the solve: algorithmic bytes (every operand read or written once) / HIP-event time, against 8 TB/s.
 
-    python tools/hbm_kernels.py [name ...]          # default: all;   QEMB_JK_V1=1 ... : the round-2 J/K kernel (A/B)
+    python tools/hbm_kernels.py [name ...]          # default: all
 """
 import ctypes as C
 import json

@@ -67,10 +67,36 @@ def test_tiled_twin_is_the_full_twin(n, o):
     assert abs(a["e_t"] - b["e_t"]) <= 1e-12 * a["abs_sum"] and abs(a["abs_sum"] - b["abs_sum"]) <= 1e-12 * a["abs_sum"]
 
 
+@pytest.mark.parametrize("o,v", [(3, 5), (5, 17), (7, 9), (11, 8)])
+def test_slabbed_twin_is_the_full_twin(o, v):
+    """two NumPy summation orders of the same terms: 1e-13 of abs_sum (measured: at most 6e-16)"""
+    args = tc.pin_inputs(o, v)
+    a, b = tn.full(*args), tn.slabbed(*args)
+    print(f"slabbed ({o},{v}): |d e_t| / abs_sum = {abs(a['e_t'] - b['e_t']) / a['abs_sum']:.2e}, |d abs_sum| / abs_sum = {abs(a['abs_sum'] - b['abs_sum']) / a['abs_sum']:.2e}")
+    assert a["e_t"] != 0.0 and abs(a["e_t"] - b["e_t"]) <= 1e-13 * a["abs_sum"] and abs(a["abs_sum"] - b["abs_sum"]) <= 1e-13 * a["abs_sum"]
+
+
+def test_stored_pins_are_the_twin():
+    """tests/golden/ccsd_t_pins.npz holds every pinned shape, and every one of them but (20, 64) -- minutes of NumPy -- is what `slabbed` gives today"""
+    pins = tc.stored_pins()
+    assert list(pins) == tc.pinned_shapes()
+    for (o, v), ref in pins.items():
+        if (o, v) == tc.PRODUCTION_PIN[:2]:
+            continue
+        now = tn.slabbed(*tc.pin_inputs(o, v))
+        assert abs(now["e_t"] - ref["e_t"]) <= 1e-13 * ref["abs_sum"] and abs(now["abs_sum"] - ref["abs_sum"]) <= 1e-13 * ref["abs_sum"], (o, v, now, ref)
+
+
 # ---------------------------------------------------------------- the cases on the mock
 @pytest.mark.parametrize("o,v", tc.op_shapes())
 def test_op_against_the_twin(hlib, o, v):
     tc.check_op_against_twin(hlib, o, v)
+
+
+@pytest.mark.parametrize("o,v,tile", tc.PIN_CASES)
+def test_op_against_the_stored_twin(hlib, o, v, tile):
+    """the production tile, the wave counts between one and sixteen, both sides of the LDS cap; (20, 64) takes the scalar mock minutes and runs on the device only"""
+    tc.check_op_against_pin(hlib, o, v, tile)
 
 
 def test_empty_cases_and_bad_arguments(hlib):
@@ -81,6 +107,17 @@ def test_empty_cases_and_bad_arguments(hlib):
 @pytest.mark.parametrize("n,o", tc.FRAGMENTS)
 def test_fragment(hlib, n, o, residency):
     tc.check_fragment(hlib, n, o, residency)
+
+
+@pytest.mark.parametrize("n,o,residency", tc.CAP_FRAGMENTS)
+def test_fragment_at_the_tile_caps(hlib, n, o, residency):
+    tc.check_cap_fragment(hlib, n, o, residency)
+
+
+def test_expected_tile_at_the_borders():
+    """the restated rule at the borders derived from the constants: o <= 10: 16, o = 11 .. 20: 8, o = 21 .. 40: 4, and the cut to v"""
+    assert [tc.expected_tile(o, 64) for o in (2, 10, 11, 20, 21, 40, 41)] == [16, 16, 8, 8, 4, 4, 2]
+    assert tc.expected_tile(21, 5) == 5 and tc.expected_tile(6, 14) == 14 and tc.expected_tile(11, 19) == 8 and tc.expected_tile(1000, 64) == 1
 
 
 def test_solver_function_appends_it(hlib):
